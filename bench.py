@@ -15,10 +15,15 @@ value = N*K*batch / time.  Strong scaling (`--total-samples S`, e.g. BASELINE co
 fixed, K = S / (N * batch) is derived, `scaling` is "strong"; each rank of a multi-GPU run keeps its own MIOpen user database /
 kernel cache so that N find-mode warm-ups do not serialise on one sqlite file.
 
-The timed pass is repeated `--repeats` times (default 5, each on a freshly built graph, each timing
+A plain run does only what the headline needs: set up, warm up (convolution solvers from MIOpen's immediate mode; `--full`
+and `--miopen-find 1` run its find mode), ONE timed pass of exactly K steps, the outputs when
+`--dump-outputs DIR` is given (the activation scales / offsets the pass rendered, float32 .npy; the same arguments give the
+same inputs in every run), and the JSON line (`roofline`, `cpu_baseline`, `cpu_ops` null, `config.variants` empty).
+Everything below -- repeated passes, the roofline pass, PMC / kernel-trace children, the variants, the CPU legs -- runs
+with `--full`.  There the timed pass is repeated `--repeats` times (default 5, each on a freshly built graph, each timing
 exactly K steps); `value` is the MEDIAN pass and `values` / `spread_pct` report all of them.
 
-Rank 0 prints ONE JSON line; `roofline` describes the dominant ppq_amd kernel of the timed workload
+Rank 0 prints ONE JSON line; with `--full`, `roofline` describes the dominant ppq_amd kernel of the timed workload
 (hipEvent pairs on the launch stream, collected in one more identical pass; `traffic` = HBM bytes per
 launch from rocprofv3 PMC passes of this very command run as child processes, FETCH_SIZE and WRITE_SIZE
 separately, gfx950 correction applied -- null when rocprofv3 is unavailable), `cpu_baseline` is PPQ's
@@ -27,7 +32,7 @@ copy is importable) on a bounded sample of the same workload, `cpu_ops` the per-
 section 3 (N == 1 only).
 
 Because the driver keeps the SCALAR keys of `config` and drops nested ones, every figure of `config.variants` that matters is
-repeated as a flat scalar of `config` (N == 1, default run): `batch1_x256_samples_per_s`, `seam_{kernels,pass}_b{32,1}_samples_per_s`,
+repeated as a flat scalar of `config` (N == 1, --full run): `batch1_x256_samples_per_s`, `seam_{kernels,pass}_b{32,1}_samples_per_s`,
 `cfg3 / cfg4 / cfg5_samples_per_s` (+ their `_roofline_frac`, `_spread_pct`), `cfg5_replay_ms_per_step`, `kl4096_`, `percentile_`,
 `reuse_activations_samples_per_s`, and the north star's own tensor (tools/north_star.py): `B_<kernel>_rocprof_median_us` / `_p10_us` /
 `_frac_of_8TBps` / `_over_floor` = the MEDIAN device duration of the single-tensor launch on B = [1,512,56,56] from a `rocprofv3
@@ -38,7 +43,7 @@ repeated as a flat scalar of `config` (N == 1, default run): `batch1_x256_sample
 whether the rocprofv3 child worked and, if not, why (stderr tail).  `roofline.rocprof_median_us` / `rocprof_frac` = the dominant kernel's
 median duration from a clean `rocprofv3 --kernel-trace` child pass of this command, next to the event-timed `avg_launch_us`.
 
-`config.variants` (N == 1, default run) also carries, each timed on this box in this run:
+`config.variants` (N == 1, --full run) also carries, each timed on this box in this run:
   * SURVEY 8(d)'s own protocol (batch 1 x 256 steps) with its wall time decomposed by phase / render and the eager step's
     host-issue vs device time;
   * the same pass with `reuse_activations`;
@@ -62,6 +67,12 @@ import sys
 import tempfile
 import time
 
+T_START = time.perf_counter()
+
+
+def log_phase(what: str) -> None:
+    """One line of the run's timeline on stderr: seconds since this file started, and what just finished."""
+    print(f'[bench] {time.perf_counter() - T_START:8.2f} s  {what}', file=sys.stderr, flush=True)
 
 
 def host_cpus() -> int:
@@ -264,6 +275,40 @@ def run_pass(graph, ex, batches, steps, method, async_observe=False, hip_graph=F
         p.calibrate, p._render = cal, ren
     p.optimize(graph, dataloader=batches, executor=ex, calib_steps=steps)
     return p
+
+
+DUMP_MAX_PARAMETER_VALUES = 4 << 20      # 16 MB of float32: a fixed, seeded sample of the weights when there are more
+
+
+def dump_outputs(graph, out_dir, parameters=False):
+    """--dump-outputs: what a caller of the timed pass receives, from its last timed pass, as float32 .npy files -- the scale and
+    offset of every ACTIVATED activation config in graph order, and (`parameters`: the LSQ workload, which trains them) the
+    parameter configs' scales / offsets and the weights themselves (a fixed, seeded sample past DUMP_MAX_PARAMETER_VALUES)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    kinds = {'activation': ([], []), 'parameter': ([], [])}
+    weights = []
+    for op in graph.operations.values():
+        if not hasattr(op, 'config'): continue
+        for c, v in op.config_with_variable:
+            if v.is_parameter and parameters and v.value is not None and v.value.is_floating_point():
+                weights.append(v.value.detach().reshape(-1).float().cpu())
+            if int(getattr(c.state, 'value', c.state)) != 4 or c.scale is None: continue
+            scales, offsets = kinds['parameter' if v.is_parameter else 'activation']
+            scales.append(torch.as_tensor(c.scale).detach().reshape(-1).float().cpu())
+            offsets.append(torch.as_tensor(0.0 if c.offset is None else c.offset).detach().reshape(-1).float().cpu())
+    arrays = {}
+    for kind, (scales, offsets) in kinds.items():
+        if kind == 'parameter' and not parameters: continue
+        arrays[f'{kind}_scale'] = torch.cat(scales).numpy() if scales else np.zeros(0, np.float32)
+        arrays[f'{kind}_offset'] = torch.cat(offsets).numpy() if offsets else np.zeros(0, np.float32)
+    if parameters:
+        flat = torch.cat(weights).numpy() if weights else np.zeros(0, np.float32)
+        if flat.size > DUMP_MAX_PARAMETER_VALUES:
+            flat = flat[np.sort(np.random.default_rng(0).choice(flat.size, DUMP_MAX_PARAMETER_VALUES, replace=False))]
+        arrays['parameter_values'] = flat
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f'{name}.npy'), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def collect_prof():
@@ -597,7 +642,7 @@ def workload_variants(args):
         # config 5's timed pass is 0.24 s of host-driven work (27 captures, 27 eager first steps, 189 replays): three passes spread 10-20 %
         # by max - min (BENCH_r05: 21.9 %); seven passes, value = their median, spread = (p90 - p10) / median, all seven in `values`
         reps = '7' if name == 'yolov6s_int4_lsq' else '3'
-        cmd = [sys.executable, os.path.abspath(__file__), '--warmup', '1', '--repeats', reps, '--variants', '0', '--pmc', '0',
+        cmd = [sys.executable, os.path.abspath(__file__), '--full', '--warmup', '1', '--repeats', reps, '--variants', '0', '--pmc', '0',
                '--no-cpu-baseline', '--no-cpu-ops', '--settle-ms', '100', '--miopen-find', find] + extra
         try:
             t0 = time.perf_counter()
@@ -678,9 +723,10 @@ def main_lsq(args, rank, world, dev):
         times.append(elapsed)
         del ex
     elapsed = sorted(times)[len(times) // 2]
+    if args.dump_outputs and rank == 0: dump_outputs(graph, args.dump_outputs, parameters=True)
     blocks = len(p.report)
     roof, prof_rows, launches_per_step, per_tensor_eager_s, phase_ms, step_report = None, [], None, 1.0, None, None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         graph2, ex2 = build()
         torch.cuda.synchronize(); _lib.lib.ppqhip_prof_enable(1)
         # launch statistics come from an EAGER pass (events cannot time launches that sit inside a replayed HIP graph)
@@ -764,7 +810,7 @@ def main_lsq(args, rank, world, dev):
                        'replay_ms_per_step': (step_report or {}).get('replay_ms_per_step'),
                        'replay_ms_per_step_round4_form': (step_report or {}).get('replay_ms_per_step_round4_form'),
                        'steps500_blocks3_samples_per_s': ((step_report or {}).get('steps500_blocks3') or {}).get('samples_per_s'),
-                       'per_tensor_eager_samples_per_s': round(samples / per_tensor_eager_s, 2) if (rank == 0 and world == 1) else None},
+                       'per_tensor_eager_samples_per_s': round(samples / per_tensor_eager_s, 2) if (rank == 0 and world == 1 and args.full) else None},
             'roofline': roof, 'cpu_baseline': None,
             'kernels': [{'name': r['name'], 'launches': r['launches'], 'total_ms': round(r['total_ms'], 3),
                          'GBps': round(r['total_bytes'] / max(r['total_ms'], 1e-9) / 1e6, 1)} for r in prof_rows]}), file=JSON_OUT, flush=True)
@@ -786,11 +832,18 @@ def main():
     ap.add_argument('--method', type=str, default='kl')
     ap.add_argument('--workload', type=str, default='resnet50', choices=sorted(WORKLOADS),
                     help='resnet50 = BASELINE config 2 (the metric); resnet50_cfg3 / vit_b16_fp8 = configs 3 / 4 at size')
-    ap.add_argument('--repeats', type=int, default=5, help='timed passes (each exactly K steps); value = median')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: repeated timed passes, the roofline pass, the variants, PMC / kernel-trace '
+                         'children, the CPU baseline and per-op table (a plain run times exactly --steps steps once and prints the line)')
+    ap.add_argument('--dump-outputs', type=str, default=None, metavar='DIR',
+                    help='after the timed steps write what the last timed pass computed as DIR/<name>.npy (float32)')
+    ap.add_argument('--repeats', type=int, default=None, help='timed passes (each exactly K steps); value = median (default: 1, with --full 5)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-cpu-ops', action='store_true')
-    ap.add_argument('--variants', type=int, default=1, help="also time SURVEY 8(d)'s own protocol (batch 1 x 256 steps) once and report it in config.variants")
-    ap.add_argument('--pmc', type=int, default=1, help='measure roofline.traffic with two rocprofv3 --pmc child passes of this command')
+    ap.add_argument('--variants', type=int, default=None,
+                    help="also time SURVEY 8(d)'s own protocol (batch 1 x 256 steps) once and report it in config.variants (default: on with --full)")
+    ap.add_argument('--pmc', type=int, default=None,
+                    help='measure roofline.traffic with two rocprofv3 --pmc child passes of this command (default: on with --full)')
     ap.add_argument('--pmc-child', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--kt-child', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--host-selftest', action='store_true', help='CPU-only check of spawn + rendezvous + merge (gloo); no GPU work')
@@ -809,8 +862,16 @@ def main():
     ap.add_argument('--queue-mib', type=int, default=0, help='debug: ObservationQueue flush threshold (MiB), 0 = default')
     ap.add_argument('--channels-last', type=int, default=0, help='activations and conv weights in channels-last (NHWC) memory format')
     ap.add_argument('--cache-params', type=int, default=0, help='keep fake-quantised weights resident between forwards')
-    ap.add_argument('--miopen-find', type=int, default=1, help='torch.backends.cudnn.benchmark (MIOpen find mode)')
+    ap.add_argument('--miopen-find', type=int, default=None,
+                    help='torch.backends.cudnn.benchmark (MIOpen find mode; default: on with --full, off in a plain run, where a '
+                         'fresh user database makes the search 45-55 s of compiling and timing candidate kernels)')
     args = ap.parse_args()
+    # a plain run is the headline alone: one timed pass of exactly --steps steps; --full restores every other leg
+    if args.repeats is None: args.repeats = 5 if args.full else 1
+    if args.variants is None: args.variants = int(args.full)
+    if args.pmc is None: args.pmc = int(args.full)
+    if not args.full: args.no_cpu_baseline = args.no_cpu_ops = True
+    if args.miopen_find is None: args.miopen_find = int(args.full)
 
     global WORKLOAD
     WORKLOAD = args.workload
@@ -831,10 +892,12 @@ def main():
     dev = f'cuda:{local}'
     import ppq_amd  # noqa: F401  (fails loudly without libppq_hip.so)
     from ppq_amd import _lib
+    log_phase(f'device {dev} and library ready')
     if WORKLOAD == 'yolov6s_int4_lsq': return main_lsq(args, rank, world, dev)
 
     g = torch.Generator(device=dev).manual_seed(1234 + rank)
     batches = [torch.rand(args.batch, 3, 224, 224, device=dev, generator=g) for _ in range(args.steps)]
+    log_phase('inputs resident')
     # HIP-graph replay only pays for launch-bound steps (small batches); at batch >= 16 the step is GPU-bound
     # and 'auto' used to flip on a noisy host-enqueue measurement (round 1's driver run: 15.0 vs 11.0 ms/step)
     hip_graph = {'0': False, '1': True, 'auto': 'auto' if args.batch < 16 else False}[args.hip_graph]
@@ -844,12 +907,14 @@ def main():
         graph, ex = build_workload(dev, args.bins, args.method, args.cache_params, args.fuse_params, bool(args.channels_last))
         run_pass(graph, ex, batches[: max(1, min(args.warmup, args.steps))], max(1, min(args.warmup, args.steps)), args.method,
                  bool(args.async_observe), False, bool(args.batch_observations))
+        log_phase('warm-up pass')
         # keep the device under the workload's own load profile for a moment: a GPU that sat idle (fresh
         # box) otherwise spends the first timed steps in clock / power transitions
         t_settle = time.perf_counter()
         while (time.perf_counter() - t_settle) * 1e3 < args.settle_ms:
             for b in batches[:2]: ex.forward(b)
             torch.cuda.synchronize()
+        log_phase('settle forwards')
         del graph, ex
 
     # timed region(s): `repeats` independent passes of exactly K steps each
@@ -887,7 +952,9 @@ def main():
         times.append(elapsed)
         del ex
     elapsed = sorted(times)[len(times) // 2]
+    log_phase(f'{len(times)} timed pass(es) of {args.steps} steps')
     if args.pmc_child or args.kt_child: return     # the rocprofv3 children: counters / kernel trace only, no JSON line
+    if args.dump_outputs and rank == 0: dump_outputs(graph, args.dump_outputs)
     n_obs = sum(1 for op in graph.operations.values() if hasattr(op, 'config') for c, v in op.config_with_variable
                 if not v.is_parameter and int(getattr(c.state, 'value', c.state)) == 4)      # activation configs this pass calibrated
     scale_checksum = float(sum(float(c.scale.sum()) for op in graph.operations.values() if hasattr(op, 'config')
@@ -899,7 +966,7 @@ def main():
     # (measured right behind the timed passes, before the variants churn the allocator: the same tensors in the same memory state)
     roof = None
     prof_rows = []
-    if rank == 0:
+    if rank == 0 and args.full:
         graph2, ex2 = build_workload(dev, args.bins, args.method, args.cache_params, args.fuse_params, bool(args.channels_last))
         torch.cuda.synchronize()
         _lib.lib.ppqhip_prof_enable(1)
@@ -1079,7 +1146,7 @@ def main():
                        'async_observe': bool(args.async_observe), 'cache_params': bool(args.cache_params),
                        'channels_last': bool(args.channels_last), 'fuse_params': bool(args.fuse_params), 'batch_observations': bool(args.batch_observations),
                        'reuse_activations': bool(args.reuse_activations), 'replayed_batches': p.replayed_batches,
-                       'hip_graph': args.hip_graph, 'graph_replays': p.graph_replays,
+                       'hip_graph': args.hip_graph, 'graph_replays': p.graph_replays, 'miopen_find': bool(args.miopen_find),
                        'graph_decisions': [{k: (round(v, 3) if isinstance(v, float) else v) for k, v in d.items()}
                                            for d in p.graph_decisions]},
             'roofline': roof, 'cpu_baseline': cpu, 'cpu_ops': cpu_ops,
@@ -1088,6 +1155,7 @@ def main():
             'scale_checksum': scale_checksum,
         }
         if trace is not None: out['trace_steps'] = trace
+        log_phase('result line')
         print(json.dumps(out), file=JSON_OUT, flush=True)
     if world > 1:
         import torch.distributed as dist

@@ -19,6 +19,9 @@ kernels.  Outputs (committed, all small):
                                       from the reference's OWN `__global__` kernel bodies (sort.cu / linear.cu / floating.cu) run on
                                       the host (oracle/_ref/libref_kernels.so; --kernels-only regenerates just this file)
     tests/golden/isotone.npz          TorchIsotoneObserver results (--isotone-only regenerates just this file)
+    tests/golden/reference_api.json   the API surface the drop-in must match: ppq.core.ffi.CUDA's static methods (parameter
+                                      names, order, defaults), the pybind names of csrc/export.cc and the values of the
+                                      RoundingPolicy / QuantizationProperty / QuantizationStates enums (--api-only)
 
 Import shims (the container has no onnx and a newer protobuf/numpy than ppq expects):
 stub `onnx*` modules, PROTOCOL_BUFFERS_PYTHON_IMPLEMENTATION=python, and a float() cast in
@@ -464,8 +467,31 @@ def gen_isotone():
     print('isotone.npz', k)
 
 
+def gen_reference_api():
+    import ast
+    import json
+    import re
+    src = os.path.dirname(os.path.abspath(ppq.__file__))             # the reference's own package directory
+    tree = ast.parse(open(os.path.join(src, 'core', 'ffi.py')).read())
+    cls = next(n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == 'CUDA')
+    cuda = [{'name': fn.name, 'args': [a.arg for a in fn.args.args],
+             'defaults': [ast.literal_eval(ast.unparse(d).replace('- ', '-').replace('+ ', '+')) for d in fn.args.defaults]}
+            for fn in cls.body if isinstance(fn, ast.FunctionDef)]
+    pybind = re.findall(r'm\.def\("(\w+)"', open(os.path.join(src, 'csrc', 'export.cc')).read())
+    out = {'CUDA': cuda, 'pybind_names': pybind,
+           'RoundingPolicy': {m.name: m.value for m in RoundingPolicy},
+           'QuantizationProperty': {m.name: m.value for m in QuantizationProperty},
+           'QuantizationStates': {m.name: m.value for m in QuantizationStates}}
+    with open(os.path.join(HERE, 'reference_api.json'), 'w') as f:
+        json.dump(out, f, indent=1)
+        f.write('\n')
+    print('reference_api.json', len(cuda), 'CUDA methods,', len(pybind), 'pybind names')
+
+
 if __name__ == '__main__':
     torch.set_num_threads(8)
+    if '--api-only' in sys.argv:
+        gen_reference_api(); sys.exit(0)
     if '--to-int-only' in sys.argv:
         gen_to_int(); sys.exit(0)
     if '--fp8-only' in sys.argv:
@@ -486,3 +512,4 @@ if __name__ == '__main__':
     gen_to_int()
     gen_dynamic()
     gen_isotone()
+    gen_reference_api()

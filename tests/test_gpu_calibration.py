@@ -1098,7 +1098,7 @@ def test_bench_two_ranks_on_one_gpu():
     statistics are sums / minima over shards, so the scales do not depend on how many ranks there were:
     the checksum equals a 1-rank run over the same 2 x K batches... which needs the same seeds, so here
     only the contract is checked: n_gpus, merge records, value = all ranks' samples / max time."""
-    small = ['--steps', '2', '--warmup', '1', '--batch', '4', '--repeats', '1', '--no-cpu-baseline', '--no-cpu-ops',
+    small = ['--full', '--steps', '2', '--warmup', '1', '--batch', '4', '--repeats', '1', '--no-cpu-baseline', '--no-cpu-ops',
              '--pmc', '0', '--settle-ms', '0', '--variants', '0']
     out = _run_bench('--gpus', '2', '--backend', 'gloo', '--single-device', '1', *small)
     assert out['n_gpus'] == 2 and out['config']['rccl_ranks'] == 2 and out['config']['samples'] == 2 * 2 * 4
@@ -1132,6 +1132,23 @@ def test_bench_strong_scaling_mode_two_ranks_on_one_gpu():
     assert r.returncode != 0 and 'not a multiple' in (r.stderr + r.stdout)
 
 
+def test_bench_plain_run_times_the_steps_once_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run is the headline alone: ONE timed pass of exactly --steps steps, none of the --full legs (roofline
+    pass, CPU baseline / per-op table, variants); `--dump-outputs DIR` writes what that pass rendered -- one float32 scale and
+    offset per calibrated activation tensor."""
+    import numpy as np
+    out = _run_bench('--steps', '2', '--warmup', '1', '--batch', '4', '--settle-ms', '0', '--miopen-find', '0', '--dump-outputs', str(tmp_path))
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert key in out
+    assert out['steps'] == 2 and out['repeats'] == 1 and out['config']['samples'] == 2 * 4
+    assert out['roofline'] is None and out['cpu_baseline'] is None and out['cpu_ops'] is None and out['config']['variants'] == []
+    assert abs(out['value'] - out['config']['samples'] / (out['ms_per_step'] * out['steps'] * 1e-3)) < 0.02 * out['value']
+    s, o = np.load(tmp_path / 'activation_scale.npy'), np.load(tmp_path / 'activation_offset.npy')
+    assert s.dtype == np.float32 and o.dtype == np.float32
+    assert s.shape == o.shape == (out['config']['observed_tensors'],) and out['config']['observed_tensors'] == 72
+    assert np.isfinite(s).all() and (s > 0).all() and (o == 0).all()          # symmetric per-tensor INT8 activations
+
+
 @pytest.mark.parametrize('workload', ['resnet50_cfg3', 'yolov6s_int4_lsq'])
 def test_bench_two_ranks_on_one_gpu_configs_3_and_5(workload):
     """BASELINE configs 3 (ResNet-50, MSE search, asymmetric, histograms merged with an all-reduce) and 5 (YOLOv6-s-like INT4 LSQ,
@@ -1139,7 +1156,8 @@ def test_bench_two_ranks_on_one_gpu_configs_3_and_5(workload):
     duplicate devices; the N-GPU run over RCCL is the driver's).  The contract of the 2-rank JSON line: n_gpus / rccl_ranks = 2,
     whole-job samples, the merge records of config 3 (a layout probe + ONE data collective per phase, the asymmetric range and
     the int32 histograms of all 72 observers in one flat buffer each), every block of config 5 trained on both ranks."""
-    small = ['--warmup', '1', '--repeats', '1', '--no-cpu-baseline', '--no-cpu-ops', '--pmc', '0', '--settle-ms', '0', '--variants', '0', '--miopen-find', '0']
+    small = ['--full', '--warmup', '1', '--repeats', '1', '--no-cpu-baseline', '--no-cpu-ops', '--pmc', '0', '--settle-ms', '0', '--variants', '0',
+             '--miopen-find', '0']
     if workload == 'resnet50_cfg3':
         out = _run_bench('--gpus', '2', '--backend', 'gloo', '--single-device', '1', '--workload', workload, '--steps', '2', '--batch', '4', *small)
         assert out['n_gpus'] == 2 and out['config']['rccl_ranks'] == 2 and out['config']['samples'] == 2 * 2 * 4

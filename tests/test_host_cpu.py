@@ -97,7 +97,12 @@ def test_minmax_to_scale_offset_matches_reference(golden_dir):
             assert np.array_equal(np.array([v[1] for v in so], np.float32), z[f'minmax_{k}_offset'])
 
 
-def test_core_types_mirror_reference_values():
+def _reference_api(golden_dir):
+    import json
+    with open(os.path.join(golden_dir, 'reference_api.json')) as f: return json.load(f)
+
+
+def test_core_types_mirror_reference_values(golden_dir):
     from ppq_amd import (FloatingQuantizationConfig, LinearQuantizationConfig, QuantizationPolicy,
                          QuantizationProperty as P, QuantizationStates as S, RoundingPolicy as R)
     assert [r.value for r in R] == [0, 1, 2, 3, 4, 5, 6]
@@ -111,38 +116,31 @@ def test_core_types_mirror_reference_values():
     assert c.policy.has_property(P.PER_CHANNEL) and c.policy.has_property(P.ASYMMETRICAL) and c.channel_axis == 1
     f = FloatingQuantizationConfig()
     assert (f.exponent_bits, f.mantissa_bits, f.quant_min, f.quant_max) == (4, 3, -448.0, 448.0)
-    if os.path.isdir('/root/reference'):      # the values are the reference's own
-        src = open('/root/reference/ppq/core/quant.py').read()
-        for name, val in (('ROUND_HALF_EVEN', 0), ('ROUND_UP', 6)):
-            assert re.search(rf'{name}\s*=\s*{val}\b', src)
-        assert re.search(r'POWER_OF_2\s*=\s*0x00000040', src) and re.search(r'ACTIVATED\s*=\s*4', src)
+    # the values are the reference's own (tests/golden/reference_api.json, make_golden.py::gen_reference_api)
+    api = _reference_api(golden_dir)
+    for enum, name in ((R, 'RoundingPolicy'), (P, 'QuantizationProperty'), (S, 'QuantizationStates')):
+        assert {m.name: m.value for m in enum} == api[name], name
 
 
-def test_cuda_facade_signatures_match_reference():
+def test_cuda_facade_signatures_match_reference(golden_dir):
     """Every static method of ppq.core.ffi.CUDA exists on ppq_amd.CUDA with the same parameter names,
-    order and defaults (parsed from the reference source; no import of ppq needed)."""
-    if not os.path.isdir('/root/reference'):
-        pytest.skip('reference not present on this machine')
-    import ast
+    order and defaults (parsed from the reference source into tests/golden/reference_api.json; no import of ppq needed)."""
     import inspect
     from ppq_amd import CUDA
-    tree = ast.parse(open('/root/reference/ppq/core/ffi.py').read())
-    ref = next(n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == 'CUDA')
+    api = _reference_api(golden_dir)
     checked = 0
-    for fn in ref.body:
-        if not isinstance(fn, ast.FunctionDef) or fn.name == 'OrderPreservingObserve':   # mis-wired in the reference
+    for fn in api['CUDA']:
+        if fn['name'] == 'OrderPreservingObserve':   # mis-wired in the reference
             continue
-        ours = inspect.signature(getattr(CUDA, fn.name))
-        ref_args = [a.arg for a in fn.args.args]
-        assert list(ours.parameters) == ref_args, (fn.name, list(ours.parameters), ref_args)
-        ref_defaults = [ast.literal_eval(ast.unparse(d).replace('- ', '-').replace('+ ', '+')) for d in fn.args.defaults]
+        ours = inspect.signature(getattr(CUDA, fn['name']))
+        assert list(ours.parameters) == fn['args'], (fn['name'], list(ours.parameters), fn['args'])
         our_defaults = [p.default for p in ours.parameters.values() if p.default is not inspect._empty]
-        assert our_defaults == ref_defaults, (fn.name, our_defaults, ref_defaults)
+        assert our_defaults == fn['defaults'], (fn['name'], our_defaults, fn['defaults'])
         checked += 1
     assert checked >= 20
     # and the extension object carries the 20 pybind names of csrc/export.cc
     from ppq_amd import HIP_EXTENSION
-    names = re.findall(r'm\.def\("(\w+)"', open('/root/reference/ppq/csrc/export.cc').read())
+    names = api['pybind_names']
     assert len(set(names)) == 20
     for n in names: assert callable(getattr(HIP_EXTENSION, n)), n
 
@@ -150,8 +148,8 @@ def test_cuda_facade_signatures_match_reference():
 def test_install_into_reference_ppq_routes_calls():
     """Drop-in seam: after install_into_ppq() an UNMODIFIED ppq.core.ffi.CUDA wrapper calls our
     extension object with the pybind argument order (recorded with a spy; no kernel runs)."""
-    if not os.path.isdir('/root/reference'):
-        pytest.skip('reference not present on this machine')
+    from oracle import reference_import as RI
+    if RI.find_reference() is None: pytest.skip('reference not present on this machine')
     import subprocess
     import sys
     code = r'''
@@ -160,7 +158,7 @@ from unittest.mock import MagicMock
 os.environ['PROTOCOL_BUFFERS_PYTHON_IMPLEMENTATION'] = 'python'
 for n in ['onnx','onnx.helper','onnx.numpy_helper','onnx.mapping','onnx.onnx_pb','onnx.checker','onnx.external_data_helper','onnx.shape_inference','onnx.version_converter']:
     m = MagicMock(); m.__spec__ = importlib.machinery.ModuleSpec(n, None); m.__path__ = []; sys.modules[n] = m
-sys.path.insert(0, '/root/reference'); sys.path.insert(0, %r)
+sys.path.insert(0, %r); sys.path.insert(0, %r)
 import torch, ppq
 import ppq_amd
 from ppq.core import CUDA, PPQ_CONFIG
@@ -198,7 +196,7 @@ ppq_amd.uninstall_from_ppq()
 assert 'complie' not in vars(CUDA_COMPLIER) and CUDA_COMPLIER.complie.__func__ is ComplieHelper.complie
 with ppq_amd.ENABLE_CUDA_KERNEL(): assert ppq_amd.PPQ_CONFIG.USING_CUDA_KERNEL is True
 print('ROUTED', len(calls))
-''' % ROOT
+''' % (RI.find_reference(), ROOT)
     out = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=300)
     assert 'ROUTED 8' in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
 
@@ -883,8 +881,8 @@ def test_fast_observers_option_wraps_and_restores_the_reference_method():
     """install_into_ppq(fast_observers=True) replaces TorchMinMaxObserver.observe on the reference's class (no file touched) and
     uninstall_from_ppq() puts the reference's own function back; without a device tensor the wrapper defers to it (the host path
     of the reference is untouched)."""
-    if not os.path.isdir('/root/reference'):
-        pytest.skip('reference not present on this machine')
+    from oracle import reference_import as RI
+    if RI.find_reference() is None: pytest.skip('reference not present on this machine')
     import subprocess
     import sys
     code = r'''
@@ -893,7 +891,7 @@ from unittest.mock import MagicMock
 os.environ['PROTOCOL_BUFFERS_PYTHON_IMPLEMENTATION'] = 'python'
 for n in ['onnx','onnx.helper','onnx.numpy_helper','onnx.mapping','onnx.onnx_pb','onnx.checker','onnx.external_data_helper','onnx.shape_inference','onnx.version_converter']:
     m = MagicMock(); m.__spec__ = importlib.machinery.ModuleSpec(n, None); m.__path__ = []; sys.modules[n] = m
-sys.path.insert(0, '/root/reference'); sys.path.insert(0, %r)
+sys.path.insert(0, %r); sys.path.insert(0, %r)
 import torch, ppq
 import ppq_amd
 from ppq.quantization.observer.range import TorchMinMaxObserver, TorchHistObserver
@@ -915,12 +913,12 @@ assert abs(float(cfg.scale) - 2 * 11.0 / 255) < 1e-7
 ppq_amd.uninstall_from_ppq()
 assert TorchMinMaxObserver.observe is original
 print('OK')
-''' % ROOT
+''' % (RI.find_reference(), ROOT)
     r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and 'OK' in r.stdout, (r.stdout[-500:], r.stderr[-1500:])
 
 
-def test_to_int_dispatch_and_no_cpu_path():
+def test_to_int_dispatch_and_no_cpu_path(monkeypatch):
     """PPQLinearQuant_toInt mirrors the reference's dispatch (qfunction/linear.py:218-238): non-linear configs raise, fewer than
     8 bits raise, and -- like every kernel-backed function here -- a host tensor is never computed on the CPU (with a device it
     is staged through the kernel, tests/test_gpu_kernels.py; without one, as here, it raises); PPQuantFunction_toInt refuses dynamic / non-linear policies (qfunction/__init__.py:47-60)."""
@@ -928,7 +926,12 @@ def test_to_int_dispatch_and_no_cpu_path():
     t = torch.zeros(4, 6)
     cfg = LinearQuantizationConfig(symmetrical=True, num_of_bits=8)
     cfg.scale, cfg.offset, cfg.state = torch.ones(1), torch.zeros(1), QuantizationStates.ACTIVATED
-    with pytest.raises(RuntimeError, match='no CPU path'): qfunction.PPQLinearQuant_toInt(t, cfg)
+    if torch.cuda.is_available():        # a device is here: the host tensor is staged through the kernel and comes back as integers
+        q = qfunction.PPQLinearQuant_toInt(t, cfg)
+        assert q.device.type == 'cpu' and q.dtype == torch.int8 and torch.equal(q, torch.zeros(4, 6, dtype=torch.int8))
+    with monkeypatch.context() as m:     # and without one it raises
+        m.setattr(torch.cuda, 'is_available', lambda: False)
+        with pytest.raises(RuntimeError, match='no CPU path'): qfunction.PPQLinearQuant_toInt(t, cfg)
     low = LinearQuantizationConfig(symmetrical=True, num_of_bits=4, quant_min=-8, quant_max=7)
     low.scale, low.offset = torch.ones(1), torch.zeros(1)
     with pytest.raises(Exception, match='num of bits is unexpected'): qfunction.PPQLinearQuant_toInt(t, low)

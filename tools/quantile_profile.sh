@@ -25,9 +25,9 @@ cd /tmp
 timeout 300 rocprofv3 --output-format csv --kernel-trace --stats -d $O/trace -o micro -- python $R/tools/microbench.py --tensors Bx32 --only "quantile_t (hinted),minmax_c,lsq_bwd_t" > /dev/null 2>&1
 cd $R
 python tools/kernel_times.py $(find $O/trace -name "*kernel_trace.csv" | head -1) > $O/kernel_times_micro.txt 2>&1
-timeout 400 python bench.py --method percentile --no-cpu-baseline --no-cpu-ops --pmc 0 --variants 0 > $O/bench_percentile.json 2> $O/bench_percentile.err
+timeout 400 python bench.py --full --method percentile --no-cpu-baseline --no-cpu-ops --pmc 0 --variants 0 > $O/bench_percentile.json 2> $O/bench_percentile.err
 cd /tmp
-timeout 400 rocprofv3 --output-format csv --kernel-trace --stats -d $O/trace2 -o insitu -- python $R/bench.py --method percentile --no-cpu-baseline --no-cpu-ops --pmc 0 --variants 0 > /dev/null 2>&1
+timeout 400 rocprofv3 --output-format csv --kernel-trace --stats -d $O/trace2 -o insitu -- python $R/bench.py --full --method percentile --no-cpu-baseline --no-cpu-ops --pmc 0 --variants 0 > /dev/null 2>&1
 cd $R
 python tools/kernel_times.py $(find $O/trace2 -name "*kernel_trace.csv" | head -1) quantile > $O/kernel_times_insitu.txt 2>&1
 find $O -name "*.db" -delete 2>/dev/null; find $O -name "*_agent_info.csv" -delete 2>/dev/null; find $O -name "*kernel_trace.csv" -delete 2>/dev/null

@@ -8,13 +8,13 @@ R=$PWD
 O=$R/gpurun_out/${1:-r4}
 rm -rf $O; mkdir -p $O
 # 1. the driver's command (headline + variants + live PMC + cpu baseline)
-(time python bench.py --steps 20 --warmup 5) > $O/bench.json 2> $O/bench.err
+(time python bench.py --full --steps 20 --warmup 5) > $O/bench.json 2> $O/bench.err
 # 2. the same command under rocprofv3 (no PMC, no variants): per-kernel average durations
-B="python $R/bench.py --no-cpu-baseline --no-cpu-ops --pmc 0 --variants 0 --steps 20 --warmup 5"
+B="python $R/bench.py --full --no-cpu-baseline --no-cpu-ops --pmc 0 --variants 0 --steps 20 --warmup 5"
 cd /tmp
 timeout 500 rocprofv3 --output-format csv --kernel-trace --stats -d $O/trace -o bench -- $B > $O/bench_traced.json 2>/dev/null
 # 3. config 5 under rocprofv3: the multi-tensor LSQ backward in situ
-timeout 400 rocprofv3 --output-format csv --kernel-trace --stats -d $O/trace5 -o cfg5 -- python $R/bench.py --workload yolov6s_int4_lsq --steps 8 --batch 8 \
+timeout 400 rocprofv3 --output-format csv --kernel-trace --stats -d $O/trace5 -o cfg5 -- python $R/bench.py --full --workload yolov6s_int4_lsq --steps 8 --batch 8 \
     --warmup 1 --repeats 1 --variants 0 --pmc 0 --no-cpu-baseline --no-cpu-ops --settle-ms 0 --miopen-find 0 > $O/bench_cfg5_traced.json 2>/dev/null
 cd $R
 # 4. single-tensor microbench (rotating buffers), multi-tensor bench, facade host time

@@ -13,13 +13,13 @@ rm -f $R/gpurun_out/parity_residue.jsonl
 tail -3 $O/pytest_gpu.txt
 cp $R/gpurun_out/parity_residue.jsonl $O/ 2>/dev/null
 # 1. the driver's command (headline + variants + live PMC + cpu baseline)
-(time python bench.py --steps 20 --warmup 5) > $O/bench.json 2> $O/bench.err
+(time python bench.py --full --steps 20 --warmup 5) > $O/bench.json 2> $O/bench.err
 # 2. the same command under rocprofv3 (no PMC, no variants): per-kernel average durations
-B="python $R/bench.py --no-cpu-baseline --no-cpu-ops --pmc 0 --variants 0 --steps 20 --warmup 5"
+B="python $R/bench.py --full --no-cpu-baseline --no-cpu-ops --pmc 0 --variants 0 --steps 20 --warmup 5"
 cd /tmp
 timeout 500 rocprofv3 --output-format csv --kernel-trace --stats -d $O/trace -o bench -- $B > $O/bench_traced.json 2>/dev/null
 # 3. config 5 under rocprofv3: kernels per replayed step
-timeout 500 rocprofv3 --output-format csv --kernel-trace --stats -d $O/trace5 -o cfg5 -- python $R/bench.py --workload yolov6s_int4_lsq --steps 8 --batch 8 \
+timeout 500 rocprofv3 --output-format csv --kernel-trace --stats -d $O/trace5 -o cfg5 -- python $R/bench.py --full --workload yolov6s_int4_lsq --steps 8 --batch 8 \
     --warmup 1 --repeats 1 --variants 0 --pmc 0 --no-cpu-baseline --no-cpu-ops --settle-ms 0 --miopen-find 1 > $O/bench_cfg5_traced.json 2>/dev/null
 cd $R
 # 4. the floor table on B (floor kernels + the library at HEAD + round 4's library, interleaved, 3 rounds) and on A / Bx8 / Bx32

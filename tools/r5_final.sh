@@ -11,8 +11,8 @@ rm -f $R/gpurun_out/parity_residue.jsonl
 grep -E "passed|failed" $O/pytest_gpu.txt | tail -2
 cp $R/gpurun_out/parity_residue.jsonl $O/ 2>/dev/null
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; echo "smoke rc=$?"; tail -3 $O/smoke.txt
-(time python bench.py --steps 20 --warmup 5) > $O/bench.json 2> $O/bench.err
-B="python $R/bench.py --no-cpu-baseline --no-cpu-ops --pmc 0 --variants 0 --steps 20 --warmup 5"
+(time python bench.py --full --steps 20 --warmup 5) > $O/bench.json 2> $O/bench.err
+B="python $R/bench.py --full --no-cpu-baseline --no-cpu-ops --pmc 0 --variants 0 --steps 20 --warmup 5"
 cd /tmp
 timeout 500 rocprofv3 --output-format csv --kernel-trace --stats -d $O/trace -o bench -- $B > $O/bench_traced.json 2>/dev/null
 timeout 600 rocprofv3 --output-format csv --kernel-trace -d $O/trace_b -o floor -- python $R/tools/floor_table.py --tag b --rounds 3 --libs r04=variants/lib_r04.so > $O/l2l_b.txt 2>&1

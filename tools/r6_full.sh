@@ -10,7 +10,7 @@ tail -6 $O/pytest_gpu.txt
 (time python -c "import __graft_entry__ as g; g.smoke()") > $O/smoke.txt 2>&1; tail -3 $O/smoke.txt
 (time timeout 600 python tools/north_star.py --mode both --report $O/frac_vs_size.txt --json $O/north_star.json) > $O/north_star_scalars.json 2> $O/north_star.err
 cut -c1-150 $O/frac_vs_size.txt | grep -vE "floor_copy|fq_linear_t|asym"
-(time python bench.py --steps 20 --warmup 5) > $O/bench.json 2> $O/bench.err
+(time python bench.py --full --steps 20 --warmup 5) > $O/bench.json 2> $O/bench.err
 tail -1 $O/bench.json | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); c=j['config']

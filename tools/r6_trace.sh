@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 R=$PWD
 O=$R/gpurun_out/${1:-r6trace}
 rm -rf $O; mkdir -p $O
-B="python $R/bench.py --no-cpu-baseline --no-cpu-ops --pmc 0 --variants 0 --steps 20 --warmup 5"
+B="python $R/bench.py --full --no-cpu-baseline --no-cpu-ops --pmc 0 --variants 0 --steps 20 --warmup 5"
 cd /tmp
 timeout 500 rocprofv3 --output-format csv --kernel-trace --stats -d $O/trace -o bench -- $B > $O/bench_traced.json 2>/dev/null
 timeout 400 rocprofv3 --output-format csv --kernel-trace --stats -d $O/micro_trace -o micro -- python $R/tools/microbench.py --tensors B,Bx32 > $O/microbench_randn.txt 2>&1
