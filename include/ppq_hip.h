@@ -241,7 +241,7 @@ int ppqhip_hist_asym_c_ranges(const float* x, int64_t n, int64_t num_channel, in
  * thresholds that worked in it, and the next call with the same n and q skips the sampling launch that
  * otherwise estimates them (words: [0] hi valid, [1] T_hi key, [2] lo valid, [3] T_lo key, [4] n, [5] k_hi,
  * [6] k_lo, [7] calls settled from the hint; a valid word is 1 in its low byte -- bits 8-9 hold how long a list the side's next
- * threshold is aimed at, raised when a batch used the list up, see quantile.hip: qh_target).  A stale or foreign hint costs time, never correctness -- but the words belong
+ * threshold is aimed at, raised when a batch used the list up, see quantile.hpp).  A stale or foreign hint costs time, never correctness -- but the words belong
  * to the call until `stream` has passed it: its launches read and write them, so nothing else may touch them meanwhile.
  * One tensor WITH a hint (16-B aligned, n >= 2^18, at most 8192 wanted keys per side) takes two launches: a filter that
  * leaves every workgroup's keys in its own record, and a select that settles both sides from the records or -- no usable
@@ -271,7 +271,7 @@ int ppqhip_quantile_t_multi(const ppqhip_quantile_job* jobs, int num_jobs, float
  * out[0] bytes before job 0's state, [1] words per job, [2] side records, [3] filter record, [4] tickets,
  * [5] byte offset of the job table, [6] / [7] word offsets of the list / tie counters in the filter record. */
 void ppqhip_quantile_debug_layout(int64_t* out);
-/* the same for the two-launch path of one hinted tensor (quantile.hip "ONE hinted tensor"), in uint32 words: out[0] words of the
+/* the same for the two-launch path of one hinted tensor (quantile_hot.hip), in uint32 words: out[0] words of the
  * whole layout, [1] first record, [2] first head, [3] first slot, [4] filter workgroups at most, [5] keys per slot, [6] first word
  * the filter does NOT zero (the header, flags and exact histograms lie below it), [7] keys per head. */
 void ppqhip_quantile_hot_layout(int64_t* out);

@@ -156,9 +156,6 @@ __device__ __forceinline__ float fq_linear_scalar(float x, float s, int o, int q
 //     |t| >= 2^19 -- take the true division (see rne_tie_margin for NaN / inf).
 //   * rc must be a normal number for the error bound to hold: scales outside [2^-100, 2^100] (and <= 0, NaN) hand back
 //     NaN, which sends every lane through the division.
-#ifndef PPQHIP_FQ_RCP
-#define PPQHIP_FQ_RCP 1
-#endif
 __device__ __forceinline__ float fq_safe_rcp(float s) {
     const float a = __builtin_fabsf(s);
     return (a >= 0x1p-100f && a <= 0x1p100f) ? __builtin_amdgcn_rcpf(s) : __builtin_nanf("");
@@ -176,7 +173,7 @@ __device__ __forceinline__ float rne_tie_margin(float t, float d) {             
 // division otherwise.  ONE divergent region per float4.
 template <int R>
 __device__ __forceinline__ void round_quotient4(const float4& a, float s, float rc, int rounding, int (&r)[4]) {
-    if constexpr (R == ROUND_HALF_EVEN && PPQHIP_FQ_RCP != 0) {
+    if constexpr (R == ROUND_HALF_EVEN) {
         typedef float pk2 __attribute__((ext_vector_type(2)));                   // v_pk_mul_f32 / v_pk_add_f32: two lanes' worth per instruction
         const pk2 t01 = pk2{a.x, a.y} * rc, t23 = pk2{a.z, a.w} * rc;
         float r0 = __builtin_rintf(t01.x), r1 = __builtin_rintf(t01.y), r2 = __builtin_rintf(t23.x), r3 = __builtin_rintf(t23.y);
@@ -326,9 +323,6 @@ __device__ __forceinline__ void stream_tiles(const float* __restrict__ x, uint32
     }
 }
 
-#ifndef PPQHIP_HIST_ASM
-#define PPQHIP_HIST_ASM 1              // EXEC-mask commits in inline assembly (WaveBinCounter::commit4_exec); 0 = compiler-generated
-#endif
 constexpr int kHotMinLanes = 12;       // lanes that must share the candidate bin to make it hot
 
 // One wavefront's counting state over an LDS histogram (`h` = the copy this wave adds into, `last` = bins - 1):
@@ -374,7 +368,6 @@ struct WaveBinCounter {
     // Only SGPR / VCC / EXEC hand-offs that the hardware interlocks are used (VALU-written VCC is read by
     // SALU only; EXEC is restored from an SGPR pair before control returns to compiled code).
     __device__ __forceinline__ void commit4_exec(const int (&b)[4]) {
-#if PPQHIP_HIST_ASM
         unsigned long long save;
         int t0, a0r;
         int cnt = __builtin_amdgcn_readfirstlane(hot_cnt);
@@ -419,9 +412,6 @@ struct WaveBinCounter {
               [base] "v"(base), [one] "v"(1)
             : "vcc", "scc", "memory");
         hot_cnt = cnt;
-#else
-        commit<true>(b[0], true); commit<true>(b[1], true); commit<true>(b[2], true); commit<true>(b[3], true);
-#endif
     }
 
     __device__ __forceinline__ void flush_hot() {

@@ -27,40 +27,21 @@
 //     caller's persistent [rows][bins] accumulator (plain stream-ordered read-modify-write), folded
 //     once at render; the one-shot entry points store rows to scratch + one reduce launch, or use
 //     device atomics when only a handful of workgroups run (small tensors: one launch).
-#include <cstdlib>
-
 #include "common.hpp"
 
 namespace ppqhip {
 
 constexpr int kMaxLdsBins = 16384;     // 64 KiB of int32 per copy at most
-#ifndef PPQHIP_HIST_LDS_INTS
-#define PPQHIP_HIST_LDS_INTS 2048      // copies * bins <= this many ints: ONE copy at >= 2048 bins (more copies cost
+constexpr int kLdsBudgetInts = 2048;   // copies * bins <= this many ints: ONE copy at >= 2048 bins (more copies cost
                                        // zeroing / flush time and buy nothing: LDS conflicts arise within a wave only)
-#endif
-#ifndef PPQHIP_HIST_BLOCK
-#define PPQHIP_HIST_BLOCK 512
-#endif
-#ifndef PPQHIP_HIST_WGPC
-#define PPQHIP_HIST_WGPC 2
-#endif
-#ifndef PPQHIP_HIST_U
-#define PPQHIP_HIST_U 2               // MI355X sweep (tools/hist_variants.py, profiles/r02_hist_variants.txt): in situ
-#endif                                // 512x2/CU: U=2 327 us, U=1 333, U=3 330, U=4 345; 1024x1 339; 256x4 332; 768x1 328
-#ifndef PPQHIP_HIST_MIN_TILES
-#define PPQHIP_HIST_MIN_TILES 2        // a workgroup is worth launching for at least this many tiles
-#endif
-#ifndef PPQHIP_HIST_ATOMIC_MAX_WG
-#define PPQHIP_HIST_ATOMIC_MAX_WG 128  // one-shot entry points: flush with device atomics up to this grid (B = [1,512,56,56]:
+constexpr int kHistBlock = 512;        // threads per histogram workgroup (multiple of 64)
+constexpr int kHistWgPerCu = 2;        // co-resident workgroups per CU
+constexpr int kHistU = 2;              // float4 loads in flight per lane and register tile.  MI355X sweep (profiles/r02_hist_variants.txt),
+                                       // in situ 512x2/CU: U=2 327 us, U=1 333, U=3 330, U=4 345; 1024x1 339; 256x4 332; 768x1 328
+constexpr int kHistMinTiles = 2;       // a workgroup is worth launching for at least this many tiles
+constexpr int kHistAtomicMaxWg = 128;  // one-shot entry points: flush with device atomics up to this grid (B = [1,512,56,56]:
                                        // ONE launch of 7.4 us instead of 8.3 us + a 4.0 us reduce launch; rocprofv3 durations)
-#endif
-#ifndef PPQHIP_HIST_NT_ELEMS
-#define PPQHIP_HIST_NT_ELEMS (48ll << 20)   // streaming (nontemporal) loads beyond cache residency
-#endif
-constexpr int kLdsBudgetInts = PPQHIP_HIST_LDS_INTS;
-constexpr int kHistBlock = PPQHIP_HIST_BLOCK;          // threads per histogram workgroup (multiple of 64)
-constexpr int kHistWgPerCu = PPQHIP_HIST_WGPC;         // co-resident workgroups per CU
-constexpr int kHistU = PPQHIP_HIST_U;                  // float4 loads in flight per lane and register tile
+constexpr long long kHistNtElems = 48ll << 20;   // streaming (nontemporal) loads beyond cache residency
 constexpr int kHistRows = kNumCU * kHistWgPerCu;       // grid limit == rows of a persistent accumulator
 constexpr uint32_t kTileVec = (uint32_t)kHistBlock * kHistU;   // float4 per tile
 constexpr uint32_t kTileElems = kTileVec * 4;
@@ -333,7 +314,7 @@ void hist_persistent_kernel(const HistJobs jobs) {
 // 8 16-B loads per lane before anything else, zeroes the LDS copy while they fly and bins them in arrival order with the same
 // Binner.  Counts are the same integers whatever the traversal.  Flush: device atomics either into the caller's histogram (few
 // workgroups: every workgroup touches every 64-B line of the histogram once and the memory-side atomic unit serialises the
-// operations on a line, ~15 ns each -- tools/floor_table.py, `floor_atomic`) or into the workgroup's OWN row of a persistent
+// operations on a line, ~15 ns each: the `floor_atomic` kernel of tools/floor/) or into the workgroup's OWN row of a persistent
 // accumulator (no contention at all, so the grid can cover every CU; atomics instead of a load-add-store keep the row's
 // read latency out of the chain).
 // PING (mid-size tensors, tens of MB: a share of many rows): two register tiles of kSmallK rows ping-pong, as in the persistent kernel, but
@@ -482,9 +463,7 @@ __global__ __launch_bounds__(kBlock) void hist_t_global_kernel(const float* __re
 // rows (stride C * epc) as one virtual float4 range with the persistent kernel's machinery (two ping-pong register tiles,
 // packed-f32 binning, EXEC-mask LDS commits, hot bin) and adds its histogram to the channel's row of `hist` ONCE -- with
 // plain read-modify-writes when it is the channel's only workgroup (splits == 1: no atomics at all).
-#ifndef PPQHIP_HIST_C_WGPC
-#define PPQHIP_HIST_C_WGPC 1             // workgroups per CU a launch should have before channels stop being split
-#endif
+constexpr int kHistCWgPerCu = 1;         // workgroups per CU a launch should have before channels stop being split
 template <bool ASYM, bool CLIP, bool NT>
 __global__ __launch_bounds__(kHistBlock, (kHistBlock * kHistWgPerCu + 255) / 256)
 void hist_c_channel_kernel(const float* __restrict__ x, FastDiv vec_per_row, uint32_t C, uint32_t outer, uint32_t splits,
@@ -674,49 +653,23 @@ static void launch_persistent(const HistJobs& args, int grid, int asym, int clip
 #undef PPQ_LAUNCH_HIST
 }
 
-// grid for `tiles` tiles: every workgroup gets at least PPQHIP_HIST_MIN_TILES of them (twice that once the grid would
+// grid for `tiles` tiles: every workgroup gets at least kHistMinTiles of them (twice that once the grid would
 // no longer fit the single-launch atomic flush), at most kHistRows workgroups
 static int persistent_grid(uint32_t tiles) {
-    uint32_t g = tiles / PPQHIP_HIST_MIN_TILES;
-    if (g > PPQHIP_HIST_ATOMIC_MAX_WG) g = tiles / (2 * PPQHIP_HIST_MIN_TILES);
-#ifdef PPQHIP_DEV_KNOBS                       // measurement builds only (tools/floor_table.py sweeps the grid of the one-shot launch)
-    if (const char* e = getenv("PPQHIP_DEV_HIST_WG")) { const int v = atoi(e); if (v > 0) g = (uint32_t)v; }
-#endif
+    uint32_t g = tiles / kHistMinTiles;
+    if (g > kHistAtomicMaxWg) g = tiles / (2 * kHistMinTiles);
     if (g < 1) g = 1;
     const uint32_t cap = (uint32_t)(num_cu() * kHistWgPerCu);      // <= kHistRows: a partitioned device runs a smaller grid
     if (g > cap) g = cap;
     return (int)g;
 }
 
-static bool dev_force_atomic() {
-#ifdef PPQHIP_DEV_KNOBS
-    if (const char* e = getenv("PPQHIP_DEV_HIST_ATOMIC")) return atoi(e) != 0;
-#endif
-    return false;
-}
-
 // one-shot histogram of one tensor, accumulated into hist[bins] (rows == nullptr) or into the caller's
 // persistent rows[kHistRows][bins]
-#ifndef PPQHIP_HIST_SMALL_ELEMS
-#define PPQHIP_HIST_SMALL_ELEMS (4ll << 20)     // single tensors up to 16 MB take hist_small_kernel
-#endif
-#ifndef PPQHIP_HIST_SMALL_WG_ATOMIC
-#define PPQHIP_HIST_SMALL_WG_ATOMIC 112         // one-shot (shared histogram): workgroups at most
-#endif
-static int dev_knob(const char* name, int fallback) {
-#ifdef PPQHIP_DEV_KNOBS
-    if (const char* e = getenv(name)) return atoi(e);
-#endif
-    (void)name;
-    return fallback;
-}
-
-#ifndef PPQHIP_HIST_STREAM_K
-#define PPQHIP_HIST_STREAM_K 2                  // rows per register tile of the ping-pong form
-#endif
-#ifndef PPQHIP_HIST_STREAM_ELEMS
-#define PPQHIP_HIST_STREAM_ELEMS (0x7fffffffll) // single tensors up to here take the ping-pong form of hist_small_kernel when they have own rows
-#endif
+constexpr long long kHistSmallElems = 4ll << 20;     // single tensors up to 16 MB take hist_small_kernel
+constexpr int kHistSmallWgAtomic = 112;              // one-shot (shared histogram): workgroups at most
+constexpr int kHistStreamK = 2;                      // rows per register tile of the ping-pong form
+constexpr long long kHistStreamElems = 0x7fffffffll; // single tensors up to here take the ping-pong form of hist_small_kernel when they have own rows
 // mid-size and large single tensors with own rows: hist_small_kernel<.., PING>
 // partial rows of the one-shot form: the grid adds with device atomics into row g % R of the zero-kept arena (R rows instead of
 // one: 512 workgroups on ONE row serialise on its 128 lines -- floor_atomic 6.5 us against 3.4 us for 8 rows, profiles/r05_floor_table_head.txt),
@@ -733,49 +686,36 @@ __global__ __launch_bounds__(kBlock) void hist_partial_reduce_kernel(int* __rest
     for (int r = 0; r < 32; r++) { t += v[r]; if (r < R && v[r] != 0) partial[(size_t)r * bins + b] = 0; }
     if (t) hist[b] = hv + t;
 }
-#ifndef PPQHIP_HIST_ONESHOT_ROWS
-#define PPQHIP_HIST_ONESHOT_ROWS 8
-#endif
+constexpr int kHistOneshotRows = 8;
+static_assert(kHistOneshotRows >= 1 && kHistOneshotRows <= 32, "hist_partial_reduce_kernel folds at most 32 rows");
 
 static bool launch_hist_stream(const float* x, int64_t n, BinRule rule, hipStream_t s, int32_t* rows, int32_t* hist = nullptr) {
-    const int kk = dev_knob("PPQHIP_DEV_HIST_STREAM", PPQHIP_HIST_STREAM_K);
     int R = 0;
-    bool direct = false;
     if (rows == nullptr) {                                                // one-shot: partial rows in the zero-kept arena
-        R = dev_knob("PPQHIP_DEV_HIST_ONESHOT", PPQHIP_HIST_ONESHOT_ROWS);
-        if (R == 0 || hist == nullptr) return false;
-        if (R > 32) R = 32;
         // (measured and not kept: every workgroup adding into the caller's histogram -- 512 adds per line are +3.7 us behind a 34 us
         // stream, a wash against the 4.7 us a dependent reduce launch costs whatever it reads, and +6.7 us on Bx4 / Bx8;
-        // profiles/r06_hist_variants.txt.  PPQHIP_DEV_HIST_ONESHOT=-1 in a developer build still selects it.)
-        if (R < 0) { direct = true; rows = hist; }
-        else {
-            rows = (int32_t*)zeroed_arena(s, sizeof(int) * (size_t)R * rule.bins);
-            if (rows == nullptr) return false;                            // (first use inside a graph capture: the reduce-launch form)
-        }
+        // profiles/r06_hist_variants.txt)
+        if (hist == nullptr) return false;
+        R = kHistOneshotRows;
+        rows = (int32_t*)zeroed_arena(s, sizeof(int) * (size_t)R * rule.bins);
+        if (rows == nullptr) return false;                                // (first use inside a graph capture: the reduce-launch form)
     }
-    if (kk <= 0 || n > PPQHIP_HIST_STREAM_ELEMS || !aligned16(x)) return false;
+    if (n > kHistStreamElems || !aligned16(x)) return false;
     const uint32_t full_rows = (uint32_t)((n >> 2) / kHistBlock);
-    uint32_t g = full_rows / (2u * (uint32_t)kk);                         // at least two tiles per workgroup
+    uint32_t g = full_rows / (2u * (uint32_t)kHistStreamK);               // at least two tiles per workgroup
     const uint32_t cap = (uint32_t)(num_cu() * kHistWgPerCu);
     if (g > cap) g = cap;
-    g = (uint32_t)dev_knob("PPQHIP_DEV_HIST_WG", (int)g);
     if (g > (uint32_t)kHistRows) g = kHistRows;
     if (g < 1) g = 1;
     const int copies = pick_copies(rule.bins, kHistBlock);
-    const bool nt = n >= PPQHIP_HIST_NT_ELEMS;
-    const uint32_t row_mod = direct ? 0u : (R ? (uint32_t)R : (uint32_t)kHistRows);
-#define PPQ_LAUNCH_HIST_STREAM_K(A, C, K)                                                                             \
-    do {                                                                                                              \
-        if (nt) hipLaunchKernelGGL((hist_small_kernel<A, C, K, true, true>), dim3(g), dim3(kHistBlock), lds_bytes(rule.bins, copies), s, x, \
-                                   (uint32_t)n, rule.a, rule.hs, rule.bins, copies, rows, row_mod);                  \
-        else hipLaunchKernelGGL((hist_small_kernel<A, C, K, true, false>), dim3(g), dim3(kHistBlock), lds_bytes(rule.bins, copies), s, x, \
-                                (uint32_t)n, rule.a, rule.hs, rule.bins, copies, rows, row_mod);                     \
-    } while (0)
+    const bool nt = n >= kHistNtElems;
+    const uint32_t row_mod = R ? (uint32_t)R : (uint32_t)kHistRows;
 #define PPQ_LAUNCH_HIST_STREAM(A, C)                                                                                  \
     do {                                                                                                              \
-        if (kk >= 4) PPQ_LAUNCH_HIST_STREAM_K(A, C, 4);                                                               \
-        else PPQ_LAUNCH_HIST_STREAM_K(A, C, 2);                                                                       \
+        if (nt) hipLaunchKernelGGL((hist_small_kernel<A, C, kHistStreamK, true, true>), dim3(g), dim3(kHistBlock),     \
+                                   lds_bytes(rule.bins, copies), s, x, (uint32_t)n, rule.a, rule.hs, rule.bins, copies, rows, row_mod); \
+        else hipLaunchKernelGGL((hist_small_kernel<A, C, kHistStreamK, true, false>), dim3(g), dim3(kHistBlock),       \
+                                lds_bytes(rule.bins, copies), s, x, (uint32_t)n, rule.a, rule.hs, rule.bins, copies, rows, row_mod); \
     } while (0)
     switch ((rule.asym ? 2 : 0) | (rule.clip ? 1 : 0)) {
         case 0: PPQ_LAUNCH_HIST_STREAM(false, false); break;
@@ -784,20 +724,18 @@ static bool launch_hist_stream(const float* x, int64_t n, BinRule rule, hipStrea
         default: PPQ_LAUNCH_HIST_STREAM(true, true); break;
     }
 #undef PPQ_LAUNCH_HIST_STREAM
-#undef PPQ_LAUNCH_HIST_STREAM_K
     if (R > 0) hipLaunchKernelGGL(hist_partial_reduce_kernel, dim3((rule.bins + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (int*)rows, R, rule.bins, (int*)hist);
     return true;
 }
 
 static bool launch_hist_small(const float* x, int64_t n, BinRule rule, int32_t* hist, hipStream_t s, int32_t* rows) {
-    if (!dev_knob("PPQHIP_DEV_HIST_SMALL", 1) || n > dev_knob("PPQHIP_DEV_HIST_SMALL_ELEMS", (int)PPQHIP_HIST_SMALL_ELEMS) || !aligned16(x)) return false;
+    if (n > kHistSmallElems || !aligned16(x)) return false;
     const uint32_t full_rows = (uint32_t)((n >> 2) / kHistBlock);
     uint32_t g;
     if (rows) g = (full_rows + 1) / 2;                                   // own rows: no contention, two loads per lane
     else g = full_rows / 4;                                              // shared histogram: every workgroup touches every line
-    const uint32_t cap = rows ? (uint32_t)(num_cu() * kHistWgPerCu) : (uint32_t)PPQHIP_HIST_SMALL_WG_ATOMIC;
+    const uint32_t cap = rows ? (uint32_t)(num_cu() * kHistWgPerCu) : (uint32_t)kHistSmallWgAtomic;
     if (g > cap) g = cap;
-    g = (uint32_t)dev_knob("PPQHIP_DEV_HIST_WG", (int)g);
     if (g > (uint32_t)kHistRows) g = kHistRows;
     if (g < 1) g = 1;
     const int copies = pick_copies(rule.bins, kHistBlock);
@@ -836,13 +774,13 @@ static int launch_hist_one(const float* x, int64_t n, BinRule rule, int32_t* his
     const int grid = persistent_grid(args.total_tiles);
     int* partial = nullptr;
     if (rows) { args.mode = FLUSH_ROWS_ADD; d.rows = rows; }
-    else if (grid <= PPQHIP_HIST_ATOMIC_MAX_WG || dev_force_atomic()) { args.mode = FLUSH_ATOMIC; d.rows = hist; }
+    else if (grid <= kHistAtomicMaxWg) { args.mode = FLUSH_ATOMIC; d.rows = hist; }
     else {
         partial = workspace ? (int*)workspace : (int*)scratch(s, sizeof(int) * (size_t)grid * rule.bins);
         if (partial == nullptr) return PPQHIP_ERR_HIP;
         args.mode = FLUSH_ROWS_STORE; d.rows = partial;
     }
-    launch_persistent(args, grid, rule.asym, rule.clip, n >= PPQHIP_HIST_NT_ELEMS, s);
+    launch_persistent(args, grid, rule.asym, rule.clip, n >= kHistNtElems, s);
     if (partial) launch_reduce(partial, grid, rule.bins, hist, s);
     return PPQHIP_OK;
 }
@@ -876,7 +814,7 @@ static int launch_hist_multi(const ppqhip_hist_job* jobs, int count, int bins, i
             elems += src.n;
         }
         args.total_tiles = tiles;
-        launch_persistent(args, persistent_grid(tiles), asym, clip, elems >= PPQHIP_HIST_NT_ELEMS, s);
+        launch_persistent(args, persistent_grid(tiles), asym, clip, elems >= kHistNtElems, s);
     }
     return PPQHIP_OK;
 }
@@ -997,15 +935,15 @@ static int hist_c_impl(const float* x, int64_t n, int64_t num_channel, int64_t e
     if (elem_per_channel % 4 == 0 && elem_per_channel >= 64 && aligned16(x) && num_bins <= kMaxLdsBins) {
         const uint32_t C = (uint32_t)num_channel, outer = (uint32_t)(n / (num_channel * elem_per_channel));
         // one workgroup per channel; channels are split over row ranges only while that is what fills the chip
-        const uint32_t want_wgs = (uint32_t)num_cu() * PPQHIP_HIST_C_WGPC;
+        const uint32_t want_wgs = (uint32_t)num_cu() * kHistCWgPerCu;
         uint32_t splits = C >= want_wgs ? 1u : (want_wgs + C - 1) / C;
         const uint64_t tiles_per_channel = ((uint64_t)outer * (uint64_t)(elem_per_channel / 4)) / kTileVec;      // a split should have >= 1 full tile
         if (splits > tiles_per_channel) splits = tiles_per_channel > 0 ? (uint32_t)tiles_per_channel : 1u;
         const int copies = pick_copies(rule.bins, kHistBlock);
         // a channel's only workgroup adds with plain read-modify-writes when the launch is HBM bound; on a latency-bound
         // tensor the (uncontended) atomic form keeps the read of the counter row out of the dependent chain
-        const int flush_mode = (splits == 1 && n > PPQHIP_HIST_SMALL_ELEMS) ? FLUSH_ROWS_ADD : FLUSH_ATOMIC;
-        const bool nt = n >= PPQHIP_HIST_NT_ELEMS;      // streaming loads beyond cache residency, as in the per-tensor kernel
+        const int flush_mode = (splits == 1 && n > kHistSmallElems) ? FLUSH_ROWS_ADD : FLUSH_ATOMIC;
+        const bool nt = n >= kHistNtElems;      // streaming loads beyond cache residency, as in the per-tensor kernel
 #define PPQ_LAUNCH_HIST_CC(A, CL)                                                                                     \
         do {                                                                                                          \
             if (nt) hipLaunchKernelGGL((hist_c_channel_kernel<A, CL, true>), dim3(C * splits), dim3(kHistBlock), lds_bytes(rule.bins, copies), s, x, \
@@ -1024,7 +962,7 @@ static int hist_c_impl(const float* x, int64_t n, int64_t num_channel, int64_t e
 #undef PPQ_LAUNCH_HIST_CC
     } else if (n / num_channel >= 256 && num_bins <= kMaxLdsBins) {        // >= 256 elements per channel, not float4-addressable
         const uint32_t C = (uint32_t)num_channel, outer = (uint32_t)(n / (num_channel * elem_per_channel));
-        const uint32_t want_wgs = (uint32_t)num_cu() * PPQHIP_HIST_C_WGPC;
+        const uint32_t want_wgs = (uint32_t)num_cu() * kHistCWgPerCu;
         uint32_t splits = C >= want_wgs ? 1u : (want_wgs + C - 1) / C;
         const uint64_t trips_per_channel = ((uint64_t)outer * (uint64_t)elem_per_channel) / (kHistBlock * 8);   // >= 8 trips per split
         if (splits > trips_per_channel) splits = trips_per_channel > 0 ? (uint32_t)trips_per_channel : 1u;

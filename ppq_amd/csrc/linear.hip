@@ -231,15 +231,9 @@ __device__ __forceinline__ float block_sum(float v, float* lds) {
 // per tensor: one contiguous chunk per workgroup, 16-B loads of x and dy, 16-B stores of grad_x;
 // the workgroup's partial d(loss)/d(scale) goes to partial[blockIdx.x] (no same-address atomics),
 // lsq_finish_kernel sums the partials in double and applies grad_factor.
-#ifndef PPQHIP_LSQ_U
-#define PPQHIP_LSQ_U 4                  // (x, dy) 16-B load pairs in flight per lane (MI355X sweep, Bx32: U=1 152 us, 2 127, 4 116)
-#endif
-#ifndef PPQHIP_LSQ_C_U
-#define PPQHIP_LSQ_C_U 4
-#endif
-#ifndef PPQHIP_LSQ_MAX_WG
-#define PPQHIP_LSQ_MAX_WG 65536         // workgroups per launch (one partial sum each)
-#endif
+constexpr int kLsqU = 4;                // (x, dy) 16-B load pairs in flight per lane (MI355X sweep, Bx32: U=1 152 us, 2 127, 4 116)
+constexpr int kLsqCU = 4;
+constexpr int kLsqMaxWg = 65536;        // workgroups per launch (one partial sum each)
 template <int R, bool NT, int U>
 __global__ __launch_bounds__(kBlock) void fq_linear_t_bwd_kernel(
     const float* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ offset,
@@ -390,7 +384,7 @@ __global__ __launch_bounds__(kBlock) void fq_linear_c_bwd_row_kernel(
         float4* gv = reinterpret_cast<float4*>(gx + base);
         // U (x, dy) load pairs in flight per lane: a 56 x 56 row (784 float4) is ONE trip of 4, all 8 loads issued up front
         // (one pair per dependent trip kept this kernel at 0.68 of the roofline on [32, 512, 56, 56])
-        constexpr int U = PPQHIP_LSQ_C_U;
+        constexpr int U = kLsqCU;
         const uint32_t v1 = hi >> 2;
         for (uint32_t v = (lo >> 2) + threadIdx.x; v < v1; v += kBlock * U) {
             float4 a[U], d[U];
@@ -481,17 +475,9 @@ constexpr int64_t kStreamElems = 48ll << 20;
 // the last-arriving wave is exposed, so U = 1 (twice the waves, half the work behind each load) is 0.2 us faster on
 // B = [1,512,56,56]: 4.28 -> 4.08 us per tensor, 4.44 -> 4.24 per channel (rocprofv3 medians, interleaved A/B,
 // profiles/r05_floor_table.txt); the copy floor of the same 12.8 MB is 3.88 us.
-#ifndef PPQHIP_FQ_U
-#define PPQHIP_FQ_U 2
-#endif
-#ifndef PPQHIP_FQ_SMALL_U
-#define PPQHIP_FQ_SMALL_U 1
-#endif
-#ifndef PPQHIP_FQ_SMALL_ELEMS
-#define PPQHIP_FQ_SMALL_ELEMS (4ll << 20)      // up to 16 MB in + 16 MB out
-#endif
-constexpr int kTileU = PPQHIP_FQ_U;
-constexpr int kSmallU = PPQHIP_FQ_SMALL_U;
+constexpr int kTileU = 2;
+constexpr int kSmallU = 1;
+constexpr long long kFqSmallElems = 4ll << 20;      // up to 16 MB in + 16 MB out
 
 template <int R>
 static void launch_lt(const float* x, const float* scale, const float* offset, float* out, int64_t n,
@@ -505,7 +491,7 @@ static void launch_lt(const float* x, const float* scale, const float* offset, f
         hipLaunchKernelGGL((fq_linear_t_tile_kernel<R, U, NT>), dim3((nvec + kBlock * U - 1) / (kBlock * U)), dim3(kBlock), 0, st, \
                            (const float4*)x, scale, offset, (float4*)out, nvec, xt, ot, ntail, qmin, qmax, rounding)
         if (n >= kStreamElems) PPQ_LAUNCH_LT(kTileU, true);
-        else if (n <= PPQHIP_FQ_SMALL_ELEMS) PPQ_LAUNCH_LT(kSmallU, false);
+        else if (n <= kFqSmallElems) PPQ_LAUNCH_LT(kSmallU, false);
         else PPQ_LAUNCH_LT(kTileU, false);
 #undef PPQ_LAUNCH_LT
     } else {
@@ -524,7 +510,7 @@ static void launch_lc(const float* x, const float* scale, const float* offset, f
         hipLaunchKernelGGL((fq_linear_c_tile_kernel<R, U, NT>), dim3((nvec + kBlock * U - 1) / (kBlock * U)), dim3(kBlock), 0, st, \
                            (const float4*)x, scale, offset, (float4*)out, nvec, vpc, nc, qmin, qmax, rounding)
         if (n >= kStreamElems) PPQ_LAUNCH_LC(kTileU, true);
-        else if (n <= PPQHIP_FQ_SMALL_ELEMS) PPQ_LAUNCH_LC(kSmallU, false);
+        else if (n <= kFqSmallElems) PPQ_LAUNCH_LC(kSmallU, false);
         else PPQ_LAUNCH_LC(kTileU, false);
 #undef PPQ_LAUNCH_LC
     } else {
@@ -664,7 +650,7 @@ __global__ __launch_bounds__(kBlock) void fq_linear_c_bwd_multi_kernel(const Lsq
             const float4* xv = reinterpret_cast<const float4*>(j.x + base);
             const float4* dv = reinterpret_cast<const float4*>(j.dy + base);
             float4* gv = reinterpret_cast<float4*>(j.gx + base);
-            constexpr int U = PPQHIP_LSQ_C_U;
+            constexpr int U = kLsqCU;
             const uint32_t v1 = epc >> 2;
             for (uint32_t v = threadIdx.x; v < v1; v += kBlock * U) {
                 float4 a[U], d[U];
@@ -747,10 +733,7 @@ int ppqhip_fq_linear_multi(const ppqhip_fq_job* jobs, int num_jobs, int rounding
         bytes += 8.0 * (double)jobs[k].n;
     }
     LaunchScope scope(K_FQ_LINEAR_C, bytes, s);
-#ifndef PPQHIP_FQM_U
-#define PPQHIP_FQM_U 2
-#endif
-    constexpr int U = PPQHIP_FQM_U;
+    constexpr int U = 2;
     for (int base = 0; base < num_jobs; base += kFqMultiMax) {
         const int count = (num_jobs - base) < kFqMultiMax ? (num_jobs - base) : kFqMultiMax;
         FqMultiArgs args;
@@ -848,11 +831,9 @@ int ppqhip_to_int_c(const float* x, const float* scale, const float* offset, voi
 // (x, dy) load pairs per lane and workgroup: 4 for HBM-bound tensors (sweep in profiles/r03_lsq_variants.txt), 1 for the
 // latency-bound ones (up to 16 MB per operand: four times the waves, a quarter of the arithmetic behind each load -- the
 // activations of a block-wise LSQ step are 0.05 .. 6 MB)
-#ifndef PPQHIP_LSQ_SMALL_U
-#define PPQHIP_LSQ_SMALL_U 1
-#endif
-static int lsq_t_u(int64_t n) { return n <= (4ll << 20) ? PPQHIP_LSQ_SMALL_U : PPQHIP_LSQ_U; }
-static int lsq_t_grid(int64_t n) { return stream_grid(n, kBlock * 4 * lsq_t_u(n), PPQHIP_LSQ_MAX_WG); }
+constexpr int kLsqSmallU = 1;
+static int lsq_t_u(int64_t n) { return n <= (4ll << 20) ? kLsqSmallU : kLsqU; }
+static int lsq_t_grid(int64_t n) { return stream_grid(n, kBlock * 4 * lsq_t_u(n), kLsqMaxWg); }
 
 static void launch_lsq_t_main(const float* x, const float* scale, const float* offset, const float* grad_y, float* grad_x,
                               float* partial, int64_t n, int grid, int clip_min, int clip_max, int rounding, hipStream_t s) {
@@ -861,10 +842,10 @@ static void launch_lsq_t_main(const float* x, const float* scale, const float* o
 #define PPQ_LAUNCH_LSQ_T(R, NT, U)                                                                                  \
     hipLaunchKernelGGL((fq_linear_t_bwd_kernel<R, NT, U>), dim3(grid), dim3(kBlock), 0, s, x, scale, offset, grad_y, \
                        grad_x, partial, (uint32_t)n, vec_ok, clip_min, clip_max, rounding)
-    if (lsq_t_u(n) == PPQHIP_LSQ_SMALL_U) {          // never nontemporal: these tensors are cache resident
-        if (rounding == ROUND_HALF_EVEN) PPQ_LAUNCH_LSQ_T(ROUND_HALF_EVEN, false, PPQHIP_LSQ_SMALL_U); else PPQ_LAUNCH_LSQ_T(-1, false, PPQHIP_LSQ_SMALL_U);
-    } else if (rounding == ROUND_HALF_EVEN) { if (nt) PPQ_LAUNCH_LSQ_T(ROUND_HALF_EVEN, true, PPQHIP_LSQ_U); else PPQ_LAUNCH_LSQ_T(ROUND_HALF_EVEN, false, PPQHIP_LSQ_U); }
-    else { if (nt) PPQ_LAUNCH_LSQ_T(-1, true, PPQHIP_LSQ_U); else PPQ_LAUNCH_LSQ_T(-1, false, PPQHIP_LSQ_U); }
+    if (lsq_t_u(n) == kLsqSmallU) {          // never nontemporal: these tensors are cache resident
+        if (rounding == ROUND_HALF_EVEN) PPQ_LAUNCH_LSQ_T(ROUND_HALF_EVEN, false, kLsqSmallU); else PPQ_LAUNCH_LSQ_T(-1, false, kLsqSmallU);
+    } else if (rounding == ROUND_HALF_EVEN) { if (nt) PPQ_LAUNCH_LSQ_T(ROUND_HALF_EVEN, true, kLsqU); else PPQ_LAUNCH_LSQ_T(ROUND_HALF_EVEN, false, kLsqU); }
+    else { if (nt) PPQ_LAUNCH_LSQ_T(-1, true, kLsqU); else PPQ_LAUNCH_LSQ_T(-1, false, kLsqU); }
 #undef PPQ_LAUNCH_LSQ_T
 }
 
@@ -913,7 +894,7 @@ int ppqhip_fq_linear_t_bwd(const float* x, const float* scale, const float* offs
     LaunchScope scope(K_FQ_LINEAR_T_BWD, 12.0 * (double)n, s);
     // rsqrtf(((double)n * (clip_max - clip_min))): linear.cu:299
     const float grad_factor = (float)(1.0 / sqrt((double)n * (double)(clip_max - clip_min)));
-    // one tile per workgroup while that keeps the grid below PPQHIP_LSQ_MAX_WG: tens of thousands of short
+    // one tile per workgroup while that keeps the grid below kLsqMaxWg: tens of thousands of short
     // workgroups stream better than a chip-sized persistent grid for this 2-reads + 1-write pattern (same finding as
     // the forward tile kernels).  Measured again in round 3 with ping-pong register tiles and the partial sum folded into
     // the launch (last workgroup, sharded tickets): 512 x 2 / CU 120 us, 512 x 4 122, 256 x 8 125, U = 4 124 -- against

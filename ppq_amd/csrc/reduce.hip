@@ -63,20 +63,9 @@ __global__ __launch_bounds__(kBlock) void minmax_t_kernel(const float* __restric
 // a workgroup walks its contiguous tile range with two ping-pong register tiles and folds its running
 // (min, max) into ITS OWN slot of every job it touches (plain stream-ordered read-modify-write).
 constexpr int kMinMaxMultiMax = 96;              // jobs per launch (2.3 KB of kernel arguments)
-#ifndef PPQHIP_MM_BLOCK
-#define PPQHIP_MM_BLOCK 256
-#endif
-#ifndef PPQHIP_MM_STREAM
-#define PPQHIP_MM_STREAM 1                 // single tensors beyond 16 MB: the ping-pong form of minmax_small_kernel
-#endif
-#ifndef PPQHIP_MM_WGPC
-#define PPQHIP_MM_WGPC 8
-#endif
-#ifndef PPQHIP_MM_U
-#define PPQHIP_MM_U 2
-#endif
-constexpr int kMMBlock = PPQHIP_MM_BLOCK, kMMU = PPQHIP_MM_U;
-constexpr int kMMGrid = kNumCU * PPQHIP_MM_WGPC;                 // <= ppqhip_minmax_slots()
+constexpr int kMMBlock = 256, kMMU = 2;
+constexpr int kMMWgPerCu = 8;
+constexpr int kMMGrid = kNumCU * kMMWgPerCu;                     // <= ppqhip_minmax_slots()
 constexpr uint32_t kMMTileVec = (uint32_t)kMMBlock * kMMU, kMMTileElems = kMMTileVec * 4;
 static_assert(kMMGrid <= kNumCU * 8, "one slot per workgroup");
 struct MinMaxJob {
@@ -261,13 +250,8 @@ __global__ __launch_bounds__(kBlock) void minmax_finish_kernel(const float* __re
 // of a [32, 512, 56, 56] activation and kept one load per lane in flight: 0.68 of the roofline, this one 0.73.  Sweep in
 // profiles/r03_minmax_c_variants.txt: U = 4 / 8 / 16, 8 .. 64 waves per CU, predicated instead of clamped loads -- all within
 // 35.1 .. 37.2 us; shipped: U = 16 (a 56 x 56 row is one trip) and >= 16 waves per CU.)
-#ifndef PPQHIP_MMC_U
-#define PPQHIP_MMC_U 16
-#endif
-#ifndef PPQHIP_MMC_WPC
-#define PPQHIP_MMC_WPC 16            // waves per CU a launch should at least have before a wave takes several rows
-#endif
-constexpr int kMMCU = PPQHIP_MMC_U;
+constexpr int kMMCU = 16;
+constexpr int kMMCWavesPerCu = 16;   // waves per CU a launch should at least have before a wave takes several rows
 constexpr uint32_t kMMCChunk = 8192;            // elements per chunk of a long row
 __global__ __launch_bounds__(kBlock) void minmax_c_wave_kernel(const float* __restrict__ x, uint32_t epc, int vec_ok, uint32_t C,
                                                                uint32_t outer, uint32_t K, uint32_t chunks, uint32_t items,
@@ -615,7 +599,7 @@ int64_t ppqhip_minmax_slots(void) { return (int64_t)kNumCU * 8; }
 static void launch_minmax_persistent(const MinMaxJobs& args, int64_t elems, hipStream_t s) {
     uint32_t grid = args.total_tiles / 2;                       // at least two tiles per workgroup
     if (grid < 1) grid = 1;
-    const uint32_t mm_cap = (uint32_t)(num_cu() * PPQHIP_MM_WGPC);      // <= kMMGrid (one slot per workgroup)
+    const uint32_t mm_cap = (uint32_t)(num_cu() * kMMWgPerCu);      // <= kMMGrid (one slot per workgroup)
     if (grid > mm_cap) grid = mm_cap;
     // streaming (nontemporal) loads once the data cannot be cache resident
     if (elems >= (48ll << 20)) hipLaunchKernelGGL((minmax_persistent_kernel<true>), dim3(grid), dim3(kMMBlock), 0, s, args);
@@ -630,7 +614,7 @@ int ppqhip_minmax_t_slots(const float* x, int64_t n, float* slots, void* stream)
     if (n <= (4ll << 20) && aligned16(x)) {                       // up to 16 MB: the lean kernel, two rows (8 KB) per workgroup
         const uint32_t full_rows = (uint32_t)((n >> 2) / kMMBlock);
         uint32_t grid = (full_rows + 1) / 2;
-        const uint32_t cap = (uint32_t)(num_cu() * PPQHIP_MM_WGPC);     // one slot per workgroup
+        const uint32_t cap = (uint32_t)(num_cu() * kMMWgPerCu);     // one slot per workgroup
         if (grid > cap) grid = cap;
         if (grid < 1) grid = 1;
         const uint32_t share = (full_rows + grid - 1) / grid;
@@ -639,18 +623,16 @@ int ppqhip_minmax_t_slots(const float* x, int64_t n, float* slots, void* stream)
         else hipLaunchKernelGGL((minmax_small_kernel<8>), dim3(grid), dim3(kMMBlock), 0, s, x, (uint32_t)n, slots);
         return finish_launch("minmax_t_slots");
     }
-#if PPQHIP_MM_STREAM
     if (aligned16(x)) {                                           // beyond 16 MB: the same kernel with two ping-pong tiles of two rows
         const uint32_t full_rows = (uint32_t)((n >> 2) / kMMBlock);
         uint32_t grid = full_rows / 8;                            // >= two tile pairs per workgroup
-        const uint32_t cap = (uint32_t)(num_cu() * PPQHIP_MM_WGPC);
+        const uint32_t cap = (uint32_t)(num_cu() * kMMWgPerCu);
         if (grid > cap) grid = cap;
         if (grid < 1) grid = 1;
         if (n >= (48ll << 20)) hipLaunchKernelGGL((minmax_small_kernel<2, true, true>), dim3(grid), dim3(kMMBlock), 0, s, x, (uint32_t)n, slots);
         else hipLaunchKernelGGL((minmax_small_kernel<2, true, false>), dim3(grid), dim3(kMMBlock), 0, s, x, (uint32_t)n, slots);
         return finish_launch("minmax_t_slots");
     }
-#endif
     MinMaxJobs args;
     args.count = 1;
     args.job[0].x = x; args.job[0].slots = slots; args.job[0].n = (uint32_t)n; args.job[0].first_tile = 0;
@@ -713,7 +695,7 @@ int ppqhip_minmax_c(const float* x, int64_t n, int64_t num_channel, int64_t elem
         // short rows: K rows of a channel per wave while that leaves the chip >= 32 waves per CU
         uint32_t K = 1;
         if (chunks == 1) {
-            K = (uint32_t)(rows / (num_cu() * PPQHIP_MMC_WPC));
+            K = (uint32_t)(rows / (num_cu() * kMMCWavesPerCu));
             const uint32_t k_bytes = (uint32_t)(65536 / (elem_per_channel * 4));       // <= 64 KB per wave
             if (K > k_bytes) K = k_bytes;
             if (K > outer) K = outer;
@@ -742,10 +724,7 @@ int ppqhip_channel_sum(const float* x, int64_t n, int64_t num_channel, int64_t e
     LaunchScope scope(K_CHANNEL_SUM, 4.0 * (double)n, s);
     const uint32_t C = (uint32_t)num_channel, epc = (uint32_t)elem_per_channel;
     const uint32_t outer = (uint32_t)(n / (num_channel * elem_per_channel));
-#ifndef PPQHIP_CSUM_SINGLE
-#define PPQHIP_CSUM_SINGLE 1
-#endif
-    if (PPQHIP_CSUM_SINGLE && epc >= 64 && epc % 4 == 0 && aligned16(x) && C >= 2u * (uint32_t)num_cu()) {
+    if (epc >= 64 && epc % 4 == 0 && aligned16(x) && C >= 2u * (uint32_t)num_cu()) {
         hipLaunchKernelGGL(channel_sum_single_kernel, dim3(C), dim3(kBlock), 0, s, x, outer, C, epc, sums);
     } else if (epc >= 64) {
         uint32_t S = (4 * (uint32_t)num_cu() + C - 1) / C;            // >= 4 workgroups per CU in total

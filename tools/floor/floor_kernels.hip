@@ -1,7 +1,7 @@
 // floor_kernels.hip -- MEASUREMENT AID, not part of libppq_hip.so: the cheapest kernels that do what each phase of the
 // single-tensor launches on B = [1,512,56,56] must do, so that `rocprofv3 --kernel-trace` prices the library's kernels against
 // a floor measured under the same tracer on the same box ("Next round" item 1).  Built by tools/floor/build.sh into
-// tools/floor/libfloor.so; driven by tools/floor_table.py.
+// tools/floor/libfloor.so; driven by tools/north_star.py.
 //
 //   floor_empty    : nothing (dispatch + wave launch + end of kernel)
 //   floor_read     : every workgroup loads its contiguous share with 16-B loads, all in flight, folds a max, ONE 4-B store per WG

@@ -3,7 +3,7 @@ a device sort (the reference's index rule, sort.cu:13-19) -- while a second stre
 where a missing release / acquire in the exact passes' "last workgroup" tails would show (MI355X_MICROARCH.md: test every
 hand-off under uneven load).
     python tools/quantile_soak.py [rounds] [seed] [big | single]
-`single`: only the single-tensor entry point with an observer's hint (quantile.hip "ONE hinted tensor: two launches"): sizes on every
+`single`: only the single-tensor entry point with an observer's hint (quantile_hot.hip, "ONE hinted tensor in two launches"): sizes on every
 geometry of its filter, slots of every length (a hot channel fills one workgroup's slot, an outlier burst overflows it), stale, garbage and
 fresh hints, two streams at once."""
 import os

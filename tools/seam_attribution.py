@@ -4,7 +4,7 @@ pass in the same reference pipeline (`install_plugins_into_ppq()`).  Per stack a
   * wall time of the pass and of its four parts (collect min/max, render, collect histograms, render): the reference's
     `calibrate` / observer `render_quantization_config` wrapped with timers (this tool only);
   * cProfile of one pass: top functions by own time;
-  * run under `rocprofv3 --kernel-trace` (tools/r6_seam.sh) the kernel trace is summed per category: this library, torch's
+  * run under `rocprofv3 --kernel-trace` the kernel trace is summed per category: this library, torch's
     reductions (the reference observers' value.min() / value.max()), MIOpen / rocBLAS, other torch kernels.
     python tools/seam_attribution.py [--batch 32] [--steps 20] [--stack kernels|fast|observers|pass] [--profile]"""
 import argparse
