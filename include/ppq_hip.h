@@ -42,7 +42,9 @@ typedef enum {
 
 #define PPQHIP_ABI_VERSION 4   /* 2: quantile hints (round 3); 3: *_multi LSQ / min-max entry points, quantile sequence (round 4);
                                 * 4: ppqhip_minmax_c_multi carries its job table in the kernel arguments (no device table / upload); split per-tensor LSQ
- *    backward (ppqhip_fq_linear_t_bwd_main / ppqhip_lsq_finish_multi) (round 5) */
+ *    backward (ppqhip_fq_linear_t_bwd_main / ppqhip_lsq_finish_multi) (round 5); the convolution epilogues
+ *    (ppqhip_bias_act / ppqhip_bias_add_act) were ADDED under 4: no existing signature changed, and a library without
+ *    them fails at load (_lib.py resolves every declared symbol) */
 
 /* library / device introspection ------------------------------------------------------------- */
 const char* ppqhip_last_error(void);
@@ -403,6 +405,21 @@ int ppqhip_rounding_loss_bwd(const float* x, const float* dy, const float* scale
                              const float* offset, float* dx, int64_t n, int64_t num_channel,
                              int64_t elem_per_channel, int clip_min, int clip_max, int rounding,
                              void* stream);
+
+/* convolution epilogues (MI355X-native addition) ------------------------------------------------ */
+/* The elementwise tail of a convolution in one pass, bitwise the PyTorch sequence it replaces:
+ * `conv(x, w, None)` then `+ bias[c]` (how PyTorch's MIOpen path applies a conv bias), then the graph's Add(a, b),
+ * then F.relu.  Every add is one rounded fp32 add in that operand order; ReLU is clamp_min's
+ * `isnan(v) ? v : max(v, 0.f)`.  Tensors are dense in the same layout; channel(i) = (i / elem_per_channel) % num_channel
+ * (NCHW: num_channel = C, elem_per_channel = H*W; channels-last: C, 1).  bias vectors have num_channel elements.
+ * No atomics, no synchronisation between workgroups: capturable into a HIP graph. */
+/* y[i] = act(y[i] + bias[c]) in place; act = ReLU when relu != 0, identity otherwise */
+int ppqhip_bias_act(float* y, const float* bias, int64_t n, int64_t num_channel, int64_t elem_per_channel,
+                    int relu, void* stream);
+/* a[i] += bias_a[c] (stored); if bias_b: b[i] += bias_b[c] (stored), else b is read as is (identity);
+ * out[i] = act(a[i] + b[i])  -- operand order of the graph's Add(a, b) */
+int ppqhip_bias_add_act(float* a, const float* bias_a, float* b, const float* bias_b, float* out,
+                        int64_t n, int64_t num_channel, int64_t elem_per_channel, int relu, void* stream);
 
 /* profiling aid used by bench.py: when enabled, every kernel launch made through this library
  * on this thread is bracketed by hipEvents on its own stream; ppqhip_prof_collect() synchronises

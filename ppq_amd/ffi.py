@@ -196,6 +196,50 @@ def _owner_quantile_hint(device: torch.device, numel: int, q: float):
 _HIST_JOB = np.dtype([('x', '<u8'), ('rows', '<u8'), ('n', '<i8'), ('p0', '<f4'), ('p1', '<f4')])
 
 
+# ---- convolution epilogues (include/ppq_hip.h ppqhip_bias_act / ppqhip_bias_add_act) ---------------------------------
+def _epilogue_geometry(ts, bias_list):
+    """(num_channel, elem_per_channel) when every tensor of `ts` is a float32 CUDA 4-D tensor of one shape and one dense
+    layout (contiguous -> (C, H*W), channels-last -> (C, 1), by _dense's rules) and every bias a contiguous float32 CUDA
+    vector of C elements on the same device; None otherwise (the caller runs the unfused ops: nothing is copied)."""
+    t0 = ts[0]
+    if not isinstance(t0, torch.Tensor) or t0.dtype is not _F32 or not t0.is_cuda or t0.dim() != 4 or t0.numel() == 0:
+        return None
+    shape, strides, dev = t0.shape, t0.stride(), t0.device
+    for t in ts[1:]:
+        if not isinstance(t, torch.Tensor) or t.dtype is not _F32 or t.device != dev or t.shape != shape or t.stride() != strides:
+            return None
+    C = int(shape[1])
+    for bias in bias_list:
+        if (not isinstance(bias, torch.Tensor) or bias.dtype is not _F32 or bias.device != dev or bias.dim() != 1
+                or bias.numel() != C or not bias.is_contiguous()):
+            return None
+    if t0.is_contiguous(): return C, int(shape[2]) * int(shape[3])
+    if t0.is_contiguous(memory_format=torch.channels_last): return C, 1
+    return None
+
+
+def bias_act_(y: torch.Tensor, bias: torch.Tensor, relu: bool) -> bool:
+    """In place ``y = act(y + bias.view(1, C, 1, 1))`` with act = F.relu when `relu`, one launch; bitwise
+    ``F.relu(F.conv2d(x, w, None) + b)``'s elementwise tail.  False (nothing done) when the operands are not fusable."""
+    geo = _epilogue_geometry([y], [bias])
+    if geo is None: return False
+    with _DeviceOf(y):
+        _raise(lib.ppqhip_bias_act(y.data_ptr(), bias.data_ptr(), y.numel(), geo[0], geo[1], 1 if relu else 0, _stream()))
+    return True
+
+
+def bias_add_act(a: torch.Tensor, bias_a: torch.Tensor, b: torch.Tensor, bias_b, relu: bool):
+    """``a += bias_a``, ``b += bias_b`` (when given, else b is only read), returns ``act(a + b)`` in a new tensor of a's
+    layout: the conv bias(es), the graph's Add(a, b) and F.relu in one launch.  None (nothing done) when not fusable."""
+    geo = _epilogue_geometry([a, b], [bias_a] if bias_b is None else [bias_a, bias_b])
+    if geo is None or a.data_ptr() == b.data_ptr(): return None
+    out = torch.empty_like(a)
+    with _DeviceOf(a):
+        _raise(lib.ppqhip_bias_add_act(a.data_ptr(), bias_a.data_ptr(), b.data_ptr(), 0 if bias_b is None else bias_b.data_ptr(),
+                                       out.data_ptr(), a.numel(), geo[0], geo[1], 1 if relu else 0, _stream()))
+    return out
+
+
 class LinearQuantizePlan:
     """Fake-quantise MANY tensors with ONE launch per call (``ppqhip_fq_linear_multi``): the weights of
     a graph, which the executor quantises again on every forward.  Built once from

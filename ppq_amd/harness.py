@@ -173,6 +173,111 @@ def _forward(op: Operation, x: List[torch.Tensor]):
     raise NotImplementedError(f'Graph op: {op.name}({op.type}) has no backend implementation')
 
 
+# ------------------------------------------------------------------------------------ convolution epilogues
+class EpilogueGroup:
+    """Consecutive operations whose elementwise tail runs as ONE epilogue launch (ffi.bias_act_ / ffi.bias_add_act):
+    ``P1``  Conv(bias) -> Relu;  ``P2``  Conv_a(bias) [, Conv_b(bias)] -> Add(a, b) -> Relu.
+    ``ops``: the members in execution order; ``convs``: the convolutions, Add input 0's producer first; ``add`` / ``relu``."""
+    __slots__ = ('kind', 'ops', 'convs', 'add', 'relu')
+
+    def __init__(self, kind, ops, convs, add, relu):
+        self.kind, self.ops, self.convs, self.add, self.relu = kind, ops, convs, add, relu
+
+    def __repr__(self): return f'{self.kind}({", ".join(op.name for op in self.ops)})'
+
+
+def _in_cfg(op, i):
+    return op.config.input_quantization_config[i] if isinstance(op, QuantableOperation) else None
+
+
+def _out_cfg(op, i):
+    return op.config.output_quantization_config[i] if isinstance(op, QuantableOperation) else None
+
+
+def plan_epilogues(operations: List[Operation], hooks: Dict[str, object] = None, keep=(), passes_through: Callable = None,
+                   grad_enabled: bool = False) -> List[EpilogueGroup]:
+    """The epilogue groups of `operations` (in execution order).  No device, no tensor values: graph, configs and hooks.
+
+    A group is formed only when (1) its members are consecutive in `operations`; (2) every intermediate tensor has its
+    group successor as only consumer and is not in `keep` (graph outputs, requested outputs); (3) every config of a tensor
+    the kernel does NOT write -- P1: the conv output, P2: the Add output, as producer output and as consumer input --
+    passes through (`passes_through(cfg)`: not activated, not delegated), and so do the configs between a conv and the
+    Add (the Add must see the biased conv output itself); (4) the hooks of the members are absent or plain
+    ``observer.CalibrationHook``s that observe none of the configs of (3); (5) autograd is off."""
+    if grad_enabled: return []
+    from .observer import CalibrationHook
+    hooks = hooks or {}
+    keep = set(keep)
+    if passes_through is None:
+        def passes_through(c): return not QuantizationStates.is_activated(c.state)
+
+    def through(*cfgs): return all(c is None or passes_through(c) for c in cfgs)
+
+    def hooks_ok(members, unwritten):
+        for op in members:
+            h = hooks.get(op.name)
+            if h is None: continue
+            if type(h) is not CalibrationHook: return False
+            if any(c is not None and c in h._observer_table for c in unwritten): return False
+        return True
+
+    def conv_ok(op):
+        return (op.type == 'Conv' and len(op.inputs) == 3 and op.inputs[2].is_parameter and len(op.outputs) == 1
+                and op.outputs[0].name not in keep)
+
+    def only_feeds(v, op): return len(v.dest_ops) == 1 and v.dest_ops[0] is op
+
+    def relu_after(op, i):
+        if i >= len(operations): return None
+        r = operations[i]
+        out = op.outputs[0]
+        if r.type != 'Relu' or len(r.inputs) != 1 or r.inputs[0] is not out or not only_feeds(out, r) or out.name in keep:
+            return None
+        return r
+
+    def try_p2(i):
+        for n_conv in (2, 1):
+            j = i + n_conv
+            if j + 1 >= len(operations): continue
+            add, convs = operations[j], operations[i:j]
+            if add.type != 'Add' or len(add.inputs) != 2 or len(add.outputs) != 1 or not all(conv_ok(c) for c in convs): continue
+            by_out = {c.outputs[0].name: c for c in convs}
+            x0, x1 = add.inputs
+            if x0.name not in by_out or x0 is x1: continue
+            if n_conv == 2 and x1.name not in by_out: continue
+            ordered = [by_out[x0.name]] + ([by_out[x1.name]] if n_conv == 2 else [])
+            if not all(only_feeds(c.outputs[0], add) for c in convs): continue
+            relu = relu_after(add, j + 1)
+            if relu is None: continue
+            unwritten = (_out_cfg(add, 0), _in_cfg(relu, 0))
+            between = [_out_cfg(c, 0) for c in convs] + [_in_cfg(add, 0), _in_cfg(add, 1)]
+            if not through(*unwritten, *between): return None
+            members = list(operations[i:j + 2])
+            if not hooks_ok(members, unwritten): return None
+            return EpilogueGroup('P2', members, ordered, add, relu)
+        return None
+
+    def try_p1(i):
+        conv = operations[i]
+        if not conv_ok(conv): return None
+        relu = relu_after(conv, i + 1)
+        if relu is None: return None
+        unwritten = (_out_cfg(conv, 0), _in_cfg(relu, 0))
+        if not through(*unwritten) or not hooks_ok([conv, relu], unwritten): return None
+        return EpilogueGroup('P1', [conv, relu], [conv], None, relu)
+
+    groups, i = [], 0
+    while i < len(operations):
+        g = try_p2(i) if operations[i].type == 'Conv' else None
+        if g is None and operations[i].type == 'Conv': g = try_p1(i)
+        if g is None:
+            i += 1
+            continue
+        groups.append(g)
+        i += len(g.ops)
+    return groups
+
+
 class TorchExecutor:
     """The forward loop of ppq/executor/torch.py:457-577 (hook protocol of executor/base.py:44-102)."""
     def __init__(self, graph: BaseGraph, device: str = 'cuda'):
@@ -187,6 +292,8 @@ class TorchExecutor:
         self._plan_cache: Dict[tuple, list] = {}
         self._fused: Dict[tuple, torch.Tensor] = {}
         self._delegates: Dict[object, Callable] = {}
+        self.fuse_epilogues = True                    # conv bias [+ residual Add] + Relu in ONE launch: plan_epilogues
+        self._epilogue_cache: Dict[tuple, dict] = {}
         self.channels_last = False                    # see use_channels_last()
         for v in graph.variables.values():
             if v.is_parameter and v.value is not None: v.value = v.value.to(device)
@@ -238,7 +345,18 @@ class TorchExecutor:
         for name, value in feed_dict.items(): g.variables[name].value = self._place(value)
         results = [None] * len(output_names)
         self._fused_parameters(operations)            # the multi-tensor plan covers the parameters of THESE operations only
+        plan, fused_done = self._epilogue_plan(operations, None, output_names), set()
         for op in operations:
+            if op.name in fused_done: continue
+            grp = plan.get(op.name)
+            vals = self._run_epilogue(grp, lambda v: v.value, None) if grp is not None else None
+            if vals is not None:
+                for m in grp.ops:
+                    fused_done.add(m.name)
+                    for v in m.outputs:
+                        v.value = vals[v.name]
+                        if v.name in output_names: results[output_names.index(v.name)] = v.value
+                continue
             raw_in = [v.value for v in op.inputs]
             if any(x is None for x in raw_in):
                 raise ValueError(f'partial_graph_forward: input of {op.name} was not fed')
@@ -309,6 +427,97 @@ class TorchExecutor:
         for plan, keys in self._plans:
             for key, out in zip(keys, plan.run()): self._fused[key] = out
 
+    def _epilogue_plan(self, operations: List[Operation], hooks, output_names) -> Dict[str, EpilogueGroup]:
+        """First member name -> group, for a forward over `operations` (plan_epilogues), cached per (operations, hooks,
+        requested outputs, delegates, config states) signature like the parameter plans."""
+        if not self.fuse_epilogues or torch.is_grad_enabled() or self._default_quant_fn is not PPQuantFunction: return {}
+        states = tuple(c.state for op in operations if isinstance(op, QuantableOperation)
+                       for c in (*op.config.input_quantization_config, *op.config.output_quantization_config))
+        sig = (tuple(op.name for op in operations), tuple((k, id(h)) for k, h in hooks.items()) if hooks else (),
+               tuple(output_names or ()), tuple(id(c) for c in self._delegates), states)
+        plan = self._epilogue_cache.get(sig)
+        if plan is None:
+            delegates = self._delegates
+
+            def passes_through(c): return not QuantizationStates.is_activated(c.state) and c not in delegates
+            groups = plan_epilogues(operations, hooks, set(self._graph.outputs) | set(output_names or ()), passes_through)
+            plan = {g.ops[0].name: g for g in groups}
+            if len(self._epilogue_cache) >= 8: self._epilogue_cache.pop(next(iter(self._epilogue_cache)))
+            self._epilogue_cache[sig] = plan
+        return plan
+
+    def _run_epilogue(self, grp: EpilogueGroup, raw_of: Callable, hooks) -> Optional[Dict[str, torch.Tensor]]:
+        """Run one planned group: every conv without bias, ONE epilogue launch, then -- member by member, in op order --
+        the quantize_function calls and hooks of the unfused loop on the tensors the kernel wrote (the planner guarantees
+        that the configs of the tensors it did not write pass through and are not observed).  Returns variable name ->
+        value for the outputs of every member, or None before anything ran when the operands' layout does not qualify."""
+        from .ffi import bias_act_, bias_add_act
+        for conv in grp.convs:                       # conv output layout follows x / w: both dense, both in one format
+            x, w = raw_of(conv.inputs[0]), conv.inputs[1].value
+            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+                    and isinstance(w, torch.Tensor) and w.dim() == 4): return None
+            fmt = torch.channels_last if self.channels_last else torch.contiguous_format
+            if not (x.is_contiguous(memory_format=fmt) and w.is_contiguous(memory_format=fmt)): return None
+        if grp.add is not None:
+            b_var = grp.add.inputs[1]
+            if b_var.source_op not in grp.convs:
+                b = raw_of(b_var)
+                if not (isinstance(b, torch.Tensor) and b.is_cuda and b.dtype == torch.float32): return None
+        hooks = hooks or {}
+        ys, biases, qins = {}, {}, {}
+        for conv in grp.ops[:len(grp.convs)]:        # the convolutions, in execution order
+            raw_in = [raw_of(v) for v in conv.inputs]
+            qin, in_cfgs = raw_in, None
+            if isinstance(conv, QuantableOperation):
+                in_cfgs = list(conv.config.input_quantization_config)
+                qin = [self._quantize_parameter(v, c) if v.is_parameter else self.quantize_function(x, c)
+                       for v, x, c in zip(conv.inputs, raw_in, in_cfgs)]
+            hook = hooks.get(conv.name)
+            if hook is not None: qin = hook.pre_forward_hook(inputs=raw_in, quant_inputs=qin, quant_configs=in_cfgs)
+            a = conv.attributes
+            ys[conv.name] = F.conv2d(qin[0], qin[1], None, stride=a.get('strides', 1), padding=a.get('pads', 0),
+                                     groups=a.get('group', 1))
+            biases[conv.name] = qin[2]
+            qins[conv.name] = qin
+        if grp.kind == 'P1':
+            conv = grp.convs[0]
+            y = ys[conv.name]
+            if not bias_act_(y, biases[conv.name], relu=True):
+                y.add_(biases[conv.name].view(1, -1, 1, 1)).relu_()      # PyTorch's own conv-bias step, then F.relu
+            tail = {conv.name: y, grp.relu.name: y}
+        else:
+            conv_a = grp.convs[0]
+            a = ys[conv_a.name]
+            conv_b = grp.convs[1] if len(grp.convs) > 1 else None
+            b = ys[conv_b.name] if conv_b is not None else raw_of(grp.add.inputs[1])
+            out = bias_add_act(a, biases[conv_a.name], b, biases[conv_b.name] if conv_b is not None else None, relu=True)
+            if out is None:
+                a.add_(biases[conv_a.name].view(1, -1, 1, 1))
+                if conv_b is not None: b.add_(biases[conv_b.name].view(1, -1, 1, 1))
+                out = F.relu(a + b)
+            tail = {conv_a.name: a, grp.add.name: out, grp.relu.name: out}
+            if conv_b is not None: tail[conv_b.name] = b
+        values: Dict[str, torch.Tensor] = {}
+        for op in grp.ops:
+            hook = hooks.get(op.name)
+            quantable = isinstance(op, QuantableOperation)
+            if op.type != 'Conv':                   # Add / Relu: their input side of the unfused loop
+                raw_in = [values[v.name] if v.name in values else raw_of(v) for v in op.inputs]
+                qin, in_cfgs = raw_in, None
+                if quantable:
+                    in_cfgs = list(op.config.input_quantization_config)
+                    qin = [self.quantize_function(x, c) for x, c in zip(raw_in, in_cfgs)]
+                if hook is not None: hook.pre_forward_hook(inputs=raw_in, quant_inputs=qin, quant_configs=in_cfgs)
+            outs = fp_outs = [tail[op.name]]
+            out_cfgs = None
+            if quantable:
+                out_cfgs = list(op.config.output_quantization_config)
+                outs = [self.quantize_function(y, c) for y, c in zip(outs, out_cfgs)]
+            if hook is not None:
+                outs = hook.post_forward_hook(outputs=fp_outs, quant_outputs=outs, quant_configs=out_cfgs)
+            for v, y in zip(op.outputs, outs): values[v.name] = y
+        return values
+
     def _quantize_parameter(self, var: Variable, config) -> torch.Tensor:
         hit = self._fused.get((var.name, id(config)))
         if hit is not None: return hit
@@ -349,7 +558,19 @@ class TorchExecutor:
             stack.extend(op.inputs)
         ops = [op for op in g.topological_sort() if op.name in need]
         if ops: self._fused_parameters(ops)
+        plan, fused_done = (self._epilogue_plan(ops, None, output_names) if ops else {}), set()
         for op in ops:
+            if op.name in fused_done: continue
+            grp = plan.get(op.name)
+            vals = (self._run_epilogue(grp, lambda v: v.value if v.is_parameter else cache[v.name], None)
+                    if grp is not None else None)
+            if vals is not None:
+                hidden = grp.relu.inputs[0].name       # never materialised on its own: a later request recomputes it
+                for m in grp.ops:
+                    fused_done.add(m.name)
+                    for v in m.outputs:
+                        if v.name != hidden: cache[v.name] = vals[v.name]
+                continue
             raw_in = [v.value if v.is_parameter else cache[v.name] for v in op.inputs]
             if isinstance(op, QuantableOperation):
                 qin = [self._quantize_parameter(v, c) if v.is_parameter else self.quantize_function(x, c)
@@ -375,7 +596,27 @@ class TorchExecutor:
         results = [None] * len(output_names)
         visited = set()
         self._fused_parameters()
-        for op in g.topological_sort():
+        ops = g.topological_sort()
+        plan, fused_done = self._epilogue_plan(ops, hooks, output_names), set()
+
+        def finish(op, outs):
+            for v, y in zip(op.outputs, outs):
+                v.value = y
+                if v.name in output_names: results[output_names.index(v.name)] = y
+            visited.add(op.name)
+            for v in op.inputs:                      # runtime clear, torch.py:564-568
+                if not v.is_parameter and all(d.name in visited for d in v.dest_ops): v.value = None
+
+        for op in ops:
+            if op.name in fused_done: continue
+            grp = plan.get(op.name)
+            vals = self._run_epilogue(grp, lambda v: v.value, hooks) if grp is not None else None
+            if vals is not None:
+                for m in grp.ops:
+                    fused_done.add(m.name)
+                    finish(m, [vals[v.name] for v in m.outputs])
+                if stop_early and all(r is not None for r in results): break
+                continue
             hook = hooks.get(op.name) if hooks else None
             raw_in = [v.value for v in op.inputs]
             qin = raw_in
@@ -394,12 +635,7 @@ class TorchExecutor:
                 outs = [self.quantize_function(y, c) for y, c in zip(outs, out_cfgs)]
             if hook is not None:
                 outs = hook.post_forward_hook(outputs=fp_outs, quant_outputs=outs, quant_configs=out_cfgs)
-            for v, y in zip(op.outputs, outs):
-                v.value = y
-                if v.name in output_names: results[output_names.index(v.name)] = y
-            visited.add(op.name)
-            for v in op.inputs:                      # runtime clear, torch.py:564-568
-                if not v.is_parameter and all(d.name in visited for d in v.dest_ops): v.value = None
+            finish(op, outs)
             if stop_early and all(r is not None for r in results): break      # nothing downstream was asked for
         for v in g.variables.values():
             if not v.is_parameter: v.value = None
