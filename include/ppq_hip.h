@@ -421,6 +421,29 @@ int ppqhip_bias_act(float* y, const float* bias, int64_t n, int64_t num_channel,
 int ppqhip_bias_add_act(float* a, const float* bias_a, float* b, const float* bias_b, float* out,
                         int64_t n, int64_t num_channel, int64_t elem_per_channel, int relu, void* stream);
 
+/* AdaRound (MI355X-native addition; ppq_amd/adaround.py) ------------------------------------------- */
+/* One job per AdaRound weight of a block; a per-tensor job has num_channel = 1, elem_per_channel = n.  `jobs` is a HOST
+ * array copied into the kernel arguments (<= 16 jobs per launch, more are chunked): no upload, capturable into a HIP graph.
+ * Everything in fp32 with the rounding steps of the torch expressions they replace; clamps keep NaN.  No atomics. */
+typedef struct ppqhip_adaround_job {
+    const float* w;        /* weight, n floats */
+    const float* v;        /* rounding parameter V, n floats */
+    const float* scale;    /* num_channel floats */
+    const float* offset;   /* num_channel floats, used as is (not rounded) */
+    float* out;            /* forward: fake-quantised weight; backward: dV (overwritten) */
+    const float* dy;       /* backward: gradient of the forward output; unused by the forward */
+    int64_t n, num_channel, elem_per_channel;
+    int32_t qmin, qmax;
+} ppqhip_adaround_job;
+/* AdaRoundDelegator.__call__, ppq/quantization/optim/legacy.py:122-132 with rectified_sigmoid :55-56:
+ *   out = (clamp(floor(w / s) + clamp(sigmoid(v) * 1.2f + -0.1f, 0, 1) + o, qmin, qmax) - o) * s */
+int ppqhip_adaround_fwd_multi(const ppqhip_adaround_job* jobs, int num_jobs, void* stream);
+/* dV of the expression above as torch autograd computes it (legacy.py:122-132; W and the scale get no gradient), plus the
+ * gradient of the regulariser AdaroundRegTerm.forward (legacy.py:58-64) scaled by the pass's gamma.  `reg`: DEVICE
+ * float[3] = {k, beta, beta - 1} with k = float32(gamma) * float32(alpha) rounded to float32 and beta - 1 formed in double;
+ * k == 0 means the reference's term is the integer 0 (warm-up): nothing is added. */
+int ppqhip_adaround_bwd_multi(const ppqhip_adaround_job* jobs, int num_jobs, const float* reg, void* stream);
+
 /* profiling aid used by bench.py: when enabled, every kernel launch made through this library
  * on this thread is bracketed by hipEvents on its own stream; ppqhip_prof_collect() synchronises
  * those events and returns, per kernel id, launches / total ms / total algorithmic bytes. */

@@ -240,6 +240,60 @@ def bias_add_act(a: torch.Tensor, bias_a: torch.Tensor, b: torch.Tensor, bias_b,
     return out
 
 
+# ---- AdaRound (include/ppq_hip.h ppqhip_adaround_fwd_multi / ppqhip_adaround_bwd_multi) ------------------------------------
+_ADAROUND_JOB = np.dtype([('w', '<u8'), ('v', '<u8'), ('scale', '<u8'), ('offset', '<u8'), ('out', '<u8'), ('dy', '<u8'),
+                          ('n', '<i8'), ('num_channel', '<i8'), ('elem_per_channel', '<i8'), ('qmin', '<i4'), ('qmax', '<i4')])
+
+
+def _adaround_table(items, outs, dys=None):
+    """items[k] = (w, v, scale, offset, channel_axis or None, quant_min, quant_max): w, v and outs[k] (and dys[k]) contiguous
+    float32 CUDA tensors of one shape on one device, scale / offset contiguous float32 with one element per channel."""
+    n = len(items)
+    if len(outs) != n or (dys is not None and len(dys) != n):
+        raise RuntimeError(_KERNEL_FAILURE + 'AdaRound: argument lists differ in length')
+    jobs = np.zeros(n, dtype=_ADAROUND_JOB)
+    dev = items[0][0].device
+    for k, (w, v, s, o, axis, qmin, qmax) in enumerate(items):
+        ts = [('Value', w), ('Rounding', v), ('Scale', s), ('Offset', o), ('Out', outs[k])] + ([('Dy', dys[k])] if dys is not None else [])
+        for name, t in ts:
+            _f32(t, name)
+            if t.device != dev: raise RuntimeError(_KERNEL_FAILURE + f'AdaRound: item {k}: {name} is on another device')
+            if not t.is_contiguous(): raise RuntimeError(_KERNEL_FAILURE + f'AdaRound: item {k}: {name} is not contiguous')
+        for name, t in ts[1:2] + ts[4:]:
+            if t.shape != w.shape: raise RuntimeError(_KERNEL_FAILURE + f'AdaRound: item {k}: {name} is not shaped like the weight')
+        C, epc = _geometry(w.shape, axis) if axis is not None else (1, w.numel())
+        if s.numel() != C or o.numel() != C:
+            raise RuntimeError(_KERNEL_FAILURE + f'AdaRound: item {k}: scale / offset need {C} elements')
+        jobs[k] = (w.data_ptr(), v.data_ptr(), s.data_ptr(), o.data_ptr(), outs[k].data_ptr(),
+                   dys[k].data_ptr() if dys is not None else 0, w.numel(), C, epc, int(qmin), int(qmax))
+    return jobs
+
+
+def adaround_forward_multi(items, outs=None) -> List[torch.Tensor]:
+    """AdaRoundDelegator.__call__ (ppq/quantization/optim/legacy.py:122-132) for every item in ONE launch; ``outs`` (optional,
+    caller-owned) receive the fake-quantised weights.  The job table travels in the kernel arguments: capturable."""
+    if not items: return []
+    if outs is None: outs = [torch.empty_like(it[0]) for it in items]
+    jobs = _adaround_table(items, outs)
+    with _DeviceOf(items[0][0]):
+        _raise(lib.ppqhip_adaround_fwd_multi(jobs.ctypes.data, len(items), _stream()))
+    return outs
+
+
+def adaround_backward_multi(items, dys, reg: torch.Tensor, dvs=None) -> List[torch.Tensor]:
+    """dV of every item in ONE launch: torch autograd's gradient through AdaRoundDelegator.__call__ plus, when ``reg[0]`` != 0,
+    the gradient of gamma * AdaroundRegTerm (legacy.py:58-64).  ``reg``: float32 CUDA tensor {k, beta, beta - 1}."""
+    if not items: return []
+    _f32(reg, 'Reg')
+    if reg.numel() != 3 or not reg.is_contiguous() or reg.device != items[0][0].device:
+        raise RuntimeError(_KERNEL_FAILURE + 'AdaRound: reg must be a contiguous float32[3] on the weights\' device')
+    if dvs is None: dvs = [torch.empty_like(it[0]) for it in items]
+    jobs = _adaround_table(items, dvs, dys)
+    with _DeviceOf(items[0][0]):
+        _raise(lib.ppqhip_adaround_bwd_multi(jobs.ctypes.data, len(items), reg.data_ptr(), _stream()))
+    return dvs
+
+
 class LinearQuantizePlan:
     """Fake-quantise MANY tensors with ONE launch per call (``ppqhip_fq_linear_multi``): the weights of
     a graph, which the executor quantises again on every forward.  Built once from
@@ -1108,7 +1162,7 @@ def install_plugins_into_ppq(observers: bool = True) -> None:
     * ``ppq.quantization.optim.base.QuantizationOptimizationPass`` is an ABC and PPQ's pipeline admits a pass by
       ``isinstance`` (optim/base.py:60-82): this package's pass base class is registered, so
       ``ppq_amd.calibration.RuntimeCalibrationPass`` (and the parameter / LSQ / bias-correction passes) go into
-      ``ppq.lib.Pipeline``; ``TorchQuantizeDelegator`` likewise admits this package's ``LSQDelegator`` to
+      ``ppq.lib.Pipeline``; ``TorchQuantizeDelegator`` likewise admits this package's ``LSQDelegator`` and ``AdaRoundDelegator`` to
       ``TorchExecutor.register_quantize_delegate``;
     * with ``observers=True`` PPQ's ``OBSERVER_TABLE`` (observer/__init__.py:15-23) is updated with the HIP-backed
       observers, so PPQ's OWN ``RuntimeCalibrationPass`` builds them; its two-phase test is by exact type
@@ -1123,10 +1177,11 @@ def install_plugins_into_ppq(observers: bool = True) -> None:
 
     from ppq.executor.torch import TorchQuantizeDelegator
 
-    from . import calibration, lsq, observer
+    from . import adaround, calibration, lsq, observer
     QuantOPRuntimeHook.register(observer.CalibrationHook)
     RefPass.register(calibration.QuantizationOptimizationPass)
     TorchQuantizeDelegator.register(lsq.LSQDelegator)      # register_quantize_delegate admits by isinstance (torch.py:317-320)
+    TorchQuantizeDelegator.register(adaround.AdaRoundDelegator)
     if observers:
         import ppq.quantization.observer as ref_observer
         import ppq.quantization.optim.calibration as ref_calibration

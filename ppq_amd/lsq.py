@@ -425,16 +425,19 @@ class LearnedStepSizePass(QuantizationOptimizationPass):
             if any({k: (tuple(v.shape), v.dtype) for k, v in d.items()} != first for d in dicts[1:]): return False
         return True
 
-    def _train_with_graph(self, train_step, qt_inputs, fp_outputs) -> int:
+    def _train_with_graph(self, train_step, qt_inputs, fp_outputs, before_step=None) -> int:
         """Step 0 eagerly on a side stream, ONE capture of the same step on that stream, replays for the rest; returns the
-        number of steps done (0 or 1 when the capture failed: the caller finishes eagerly and later blocks do not retry)."""
+        number of steps done (0 or 1 when the capture failed: the caller finishes eagerly and later blocks do not retry).
+        ``before_step(step)``: called where the batch of a step is staged (step 0 and before every replay), to refresh other
+        device inputs of the step the same way."""
         n = len(qt_inputs)
         static_in = {k: torch.empty_like(v) for k, v in qt_inputs[0].items()}
         static_fp = {k: torch.empty_like(v) for k, v in fp_outputs[0].items()}
 
         def load(i: int) -> None:
-            for k, v in static_in.items(): v.copy_(qt_inputs[i][k])
-            for k, v in static_fp.items(): v.copy_(fp_outputs[i][k])
+            for k, v in static_in.items(): v.copy_(qt_inputs[i % n][k])
+            for k, v in static_fp.items(): v.copy_(fp_outputs[i % n][k])
+            if before_step is not None: before_step(i)
 
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -476,11 +479,28 @@ class LearnedStepSizePass(QuantizationOptimizationPass):
         self.stats['graph_blocks'] += 1
         with self._phase('graph_replays'):
             for step in range(1, self.steps):
-                load(step % n)
+                load(step)
                 graph.replay()
                 self.stats['graph_replays'] += 1
             torch.cuda.current_stream().synchronize()   # the graph's private pool dies with `graph`: no replay may be in flight
         return self.steps
+
+    def _make_optimizer(self, uniq, graphable: bool):
+        """The user's optimizer class when given; on the HIP-graph path the capturable Adam (fused when available); else the
+        reference's ``torch.optim.Adam``."""
+        if self.optimizer is not None: return self.optimizer(uniq, lr=self.lr)
+        if not graphable: return torch.optim.Adam(uniq, lr=self.lr)
+        opt = None
+        if self.fused_adam:                        # ONE multi-tensor kernel per step instead of the foreach form's 6-8 small ones
+            try: opt = torch.optim.Adam(uniq, lr=self.lr, capturable=True, fused=True)
+            except (RuntimeError, ValueError, TypeError) as e:
+                self.stats['fused_adam_error'] = f'{type(e).__name__}: {str(e)[:200]}'
+                if not getattr(LearnedStepSizePass, '_warned_fused_adam', False):
+                    LearnedStepSizePass._warned_fused_adam = True
+                    warnings.warn(f'LearnedStepSizePass: fused Adam unavailable ({self.stats["fused_adam_error"]}); using the foreach capturable form')
+        if opt is None: return torch.optim.Adam(uniq, lr=self.lr, capturable=True)
+        self.stats['fused_adam_blocks'] = self.stats.get('fused_adam_blocks', 0) + 1
+        return opt
 
     def finetune(self, block, executor, qt_inputs, fp_outputs):
         """training.py:728-826 for one block."""
@@ -520,19 +540,7 @@ class LearnedStepSizePass(QuantizationOptimizationPass):
         self.stats['grouped_weights'] += sum(len(g.members) for g in groups)
         self.stats['grouped_activations'] += len(act_group.members) if act_group is not None else 0
         graphable = self._graphable(qt_inputs, fp_outputs, uniq)
-        if self.optimizer is not None: opt = self.optimizer(uniq, lr=self.lr)
-        elif graphable:
-            opt = None
-            if self.fused_adam:                        # ONE multi-tensor kernel per step instead of the foreach form's 6-8 small ones
-                try: opt = torch.optim.Adam(uniq, lr=self.lr, capturable=True, fused=True)
-                except (RuntimeError, ValueError, TypeError) as e:
-                    self.stats['fused_adam_error'] = f'{type(e).__name__}: {str(e)[:200]}'
-                    if not getattr(LearnedStepSizePass, '_warned_fused_adam', False):
-                        LearnedStepSizePass._warned_fused_adam = True
-                        warnings.warn(f'LearnedStepSizePass: fused Adam unavailable ({self.stats["fused_adam_error"]}); using the foreach capturable form')
-            if opt is None: opt = torch.optim.Adam(uniq, lr=self.lr, capturable=True)
-            else: self.stats['fused_adam_blocks'] = self.stats.get('fused_adam_blocks', 0) + 1
-        else: opt = torch.optim.Adam(uniq, lr=self.lr)
+        opt = self._make_optimizer(uniq, graphable)
 
         def train_step(qt_input, fp_output) -> None:
             opt.zero_grad()
