@@ -444,6 +444,49 @@ int ppqhip_adaround_fwd_multi(const ppqhip_adaround_job* jobs, int num_jobs, voi
  * k == 0 means the reference's term is the integer 0 (warm-up): nothing is added. */
 int ppqhip_adaround_bwd_multi(const ppqhip_adaround_job* jobs, int num_jobs, const float* reg, void* stream);
 
+/* quantization error analysis (MI355X-native addition; ppq_amd/analyse.py, ppq_amd/measure.py) -------- */
+/* All three take a HOST array of jobs that is copied into the kernel arguments (more jobs than fit one launch are chunked):
+ * no upload, no synchronisation, no atomics, capturable into a HIP graph.  rows, row_len, count <= 2^31 - 1. */
+/* batch_random_fetch (ppq/utils/fetch.py:98-122) of many tensors: out[b * count + i] = x[b * row_len + index[i]] for
+ * b < rows, i < count.  `index`: DEVICE int32[count], values in [0, row_len) (a value outside is clamped into the row). */
+typedef struct ppqhip_fetch_rows_job {
+    const float* x;         /* rows x row_len */
+    const int32_t* index;   /* count */
+    float* out;             /* rows x count */
+    int64_t rows, row_len, count;
+} ppqhip_fetch_rows_job;
+int ppqhip_fetch_rows_multi(const ppqhip_fetch_rows_job* jobs, int num_jobs, void* stream);
+/* Per row b the four sums the measures of ppq/quantization/measure are made of, sums[b] = {noise, signal, pp, pr}:
+ *   noise = sum (p - r)^2,  signal = sum r * r,  pp = sum p * p,  pr = sum p * r    over the count elements of the row.
+ * r is dense (rows x count).  p is dense too when index == NULL (row_len == count), otherwise element i of row b is
+ * p[b * row_len + index[i]]: the fetch above fused into the measure.  Each difference and product is ONE fp32 operation,
+ * every accumulation a double add in an order fixed by (rows, count) alone: two calls give identical bits. */
+typedef struct ppqhip_measure_rows_job {
+    const float* p;
+    const float* r;
+    const int32_t* index;   /* NULL: p is dense */
+    double* sums;           /* rows x 4, overwritten */
+    int64_t rows, row_len, count;
+} ppqhip_measure_rows_job;
+int ppqhip_measure_rows_multi(const ppqhip_measure_rows_job* jobs, int num_jobs, void* stream);
+/* The per-row measure of each job's row sums, rounded to fp32 as the reference's expressions are:
+ *   snr    (float)noise / ((float)signal + 1e-7f)                       measure/norm.py:88-90
+ *   mse    (float)(noise / count)                                       measure/norm.py:42-43
+ *   cosine (float)(pr / (max(sqrt(pp), 1e-8) * max(sqrt(signal), 1e-8)))  torch.cosine_similarity
+ * row_out (optional): float[rows], the per-row values.  acc (optional): the running state of one MeasureRecorder,
+ *   mean: acc[0] += (double)(float)mean_over_rows * rows      max: acc[0] = max(acc[0], max_over_rows)      acc[1] += rows
+ * The acc of the jobs of ONE call must be distinct. */
+enum { PPQHIP_MEASURE_SNR = 0, PPQHIP_MEASURE_MSE = 1, PPQHIP_MEASURE_COSINE = 2 };
+enum { PPQHIP_REDUCE_MEAN = 0, PPQHIP_REDUCE_MAX = 1 };
+typedef struct ppqhip_measure_finish_job {
+    const double* sums;     /* rows x 4, as ppqhip_measure_rows_multi writes them */
+    double* acc;            /* 2 doubles, or NULL */
+    float* row_out;         /* rows floats, or NULL */
+    int64_t rows, count;
+    int32_t method, reduce;
+} ppqhip_measure_finish_job;
+int ppqhip_measure_finish_multi(const ppqhip_measure_finish_job* jobs, int num_jobs, void* stream);
+
 /* profiling aid used by bench.py: when enabled, every kernel launch made through this library
  * on this thread is bracketed by hipEvents on its own stream; ppqhip_prof_collect() synchronises
  * those events and returns, per kernel id, launches / total ms / total algorithmic bytes. */

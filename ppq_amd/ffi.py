@@ -294,6 +294,90 @@ def adaround_backward_multi(items, dys, reg: torch.Tensor, dvs=None) -> List[tor
     return dvs
 
 
+# ---- error analysis (include/ppq_hip.h ppqhip_fetch_rows_multi / ppqhip_measure_rows_multi / ppqhip_measure_finish_multi) ----
+_FETCH_JOB = np.dtype([('x', '<u8'), ('index', '<u8'), ('out', '<u8'), ('rows', '<i8'), ('row_len', '<i8'), ('count', '<i8')])
+_MEASURE_JOB = np.dtype([('p', '<u8'), ('r', '<u8'), ('index', '<u8'), ('sums', '<u8'), ('rows', '<i8'), ('row_len', '<i8'),
+                         ('count', '<i8')])
+_FINISH_JOB = np.dtype([('sums', '<u8'), ('acc', '<u8'), ('row_out', '<u8'), ('rows', '<i8'), ('count', '<i8'),
+                        ('method', '<i4'), ('reduce', '<i4')])
+MEASURE_METHODS = {'snr': 0, 'mse': 1, 'cosine': 2}
+MEASURE_REDUCES = {'mean': 0, 'max': 1}
+
+
+def _rows_of(t: torch.Tensor, name: str):
+    """(rows, row_len) of a batched tensor read as [shape[0], rest], which must be float32, on the GPU and contiguous."""
+    _f32(t, name)
+    if not t.is_contiguous(): raise RuntimeError(_KERNEL_FAILURE + f'{name} is not contiguous')
+    if t.dim() < 1: raise RuntimeError(_KERNEL_FAILURE + f'{name} has no batch dimension')
+    return t.shape[0], t.numel() // t.shape[0]
+
+
+def _index_of(index: torch.Tensor, row_len: int, dev) -> int:
+    if index.dtype != torch.int32 or not index.is_cuda or not index.is_contiguous() or index.dim() != 1 or index.numel() == 0:
+        raise RuntimeError(_KERNEL_FAILURE + 'Index must be a contiguous 1-D int32 tensor on the GPU')
+    if index.device != dev: raise RuntimeError(_KERNEL_FAILURE + 'Index is on another device')
+    return index.numel()
+
+
+def fetch_rows_multi(items, outs=None) -> List[torch.Tensor]:
+    """``batch_random_fetch`` (ppq/utils/fetch.py:98-122) of every ``(x, index)`` item in ONE launch:
+    ``out[b, i] = x[b].flatten()[index[i]]``; ``index`` is a device int32 table with values below ``x[0].numel()``."""
+    if not items: return []
+    dev = items[0][0].device
+    if outs is None: outs = [torch.empty([x.shape[0], index.numel()], dtype=torch.float32, device=dev) for x, index in items]
+    jobs = np.zeros(len(items), dtype=_FETCH_JOB)
+    for k, ((x, index), out) in enumerate(zip(items, outs)):
+        rows, row_len = _rows_of(x, 'Value')
+        count = _index_of(index, row_len, dev)
+        if x.device != dev or out.device != dev: raise RuntimeError(_KERNEL_FAILURE + f'fetch: item {k} is on another device')
+        if _rows_of(out, 'Out') != (rows, count): raise RuntimeError(_KERNEL_FAILURE + f'fetch: item {k}: Out is not [{rows}, {count}]')
+        jobs[k] = (x.data_ptr(), index.data_ptr(), out.data_ptr(), rows, row_len, count)
+    with _DeviceOf(items[0][0]):
+        _raise(lib.ppqhip_fetch_rows_multi(jobs.ctypes.data, len(items), _stream()))
+    return outs
+
+
+def measure_rows_multi(items, sums=None) -> List[torch.Tensor]:
+    """The row sums ``[rows, 4]`` (float64: noise, signal, pp, pr) of every ``(p, r, index)`` item in ONE launch.  ``index``
+    None: p and r have one shape.  Otherwise r is ``[rows, index.numel()]`` and p is read through the table (the fetch fused)."""
+    if not items: return []
+    dev = items[0][0].device
+    if sums is None: sums = [torch.empty([p.shape[0], 4], dtype=torch.float64, device=dev) for p, _, _ in items]
+    jobs = np.zeros(len(items), dtype=_MEASURE_JOB)
+    for k, ((p, r, index), out) in enumerate(zip(items, sums)):
+        rows, row_len = _rows_of(p, 'Pred')
+        r_rows, count = _rows_of(r, 'Real')
+        if p.device != dev or r.device != dev or out.device != dev:
+            raise RuntimeError(_KERNEL_FAILURE + f'measure: item {k} is on another device')
+        if r_rows != rows or (index is None and count != row_len) or (index is not None and _index_of(index, row_len, dev) != count):
+            raise RuntimeError(_KERNEL_FAILURE + f'measure: item {k}: Pred {tuple(p.shape)} and Real {tuple(r.shape)} do not match')
+        if out.dtype != torch.float64 or out.numel() != rows * 4 or not out.is_contiguous():
+            raise RuntimeError(_KERNEL_FAILURE + f'measure: item {k}: Sums must be a contiguous float64 [{rows}, 4]')
+        jobs[k] = (p.data_ptr(), r.data_ptr(), 0 if index is None else index.data_ptr(), out.data_ptr(), rows, row_len, count)
+    with _DeviceOf(items[0][0]):
+        _raise(lib.ppqhip_measure_rows_multi(jobs.ctypes.data, len(items), _stream()))
+    return sums
+
+
+def measure_finish_multi(items, method: str, reduce: str = 'mean') -> None:
+    """Per ``(sums, count, acc, row_out)`` item: the per-row measure of ``sums`` ([rows, 4] float64 of a row of ``count``
+    elements) in fp32, written to ``row_out`` (float32 [rows] or None) and folded into ``acc`` (float64 [2]: running
+    numerator and row count of one MeasureRecorder, or None).  ONE launch; the ``acc`` of the items must be distinct."""
+    if not items: return
+    jobs = np.zeros(len(items), dtype=_FINISH_JOB)
+    m, rd = MEASURE_METHODS[method], MEASURE_REDUCES[reduce]
+    for k, (sums, count, acc, row_out) in enumerate(items):
+        rows = sums.numel() // 4
+        for name, t, dt, n in (('Sums', sums, torch.float64, rows * 4), ('Acc', acc, torch.float64, 2), ('RowOut', row_out, torch.float32, rows)):
+            if t is None: continue
+            if t.dtype != dt or not t.is_cuda or not t.is_contiguous() or t.numel() != n or n == 0 or t.device != sums.device:
+                raise RuntimeError(_KERNEL_FAILURE + f'measure finish: item {k}: {name} must be a contiguous {dt} tensor of {n} on the GPU')
+        jobs[k] = (sums.data_ptr(), 0 if acc is None else acc.data_ptr(), 0 if row_out is None else row_out.data_ptr(),
+                   rows, int(count), m, rd)
+    with _DeviceOf(items[0][0]):
+        _raise(lib.ppqhip_measure_finish_multi(jobs.ctypes.data, len(items), _stream()))
+
+
 class LinearQuantizePlan:
     """Fake-quantise MANY tensors with ONE launch per call (``ppqhip_fq_linear_multi``): the weights of
     a graph, which the executor quantises again on every forward.  Built once from
