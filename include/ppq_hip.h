@@ -444,6 +444,24 @@ int ppqhip_adaround_fwd_multi(const ppqhip_adaround_job* jobs, int num_jobs, voi
  * k == 0 means the reference's term is the integer 0 (warm-up): nothing is added. */
 int ppqhip_adaround_bwd_multi(const ppqhip_adaround_job* jobs, int num_jobs, const float* reg, void* stream);
 
+/* round tuning (MI355X-native addition; ppq_amd/roundtune.py) ---------------------------------------- */
+/* One job per round-tuned weight of a block, in the launch form of the AdaRound jobs above (HOST array copied into the kernel
+ * arguments, <= 16 jobs per launch, more are chunked; a per-tensor job has num_channel = 1, elem_per_channel = n). */
+typedef struct ppqhip_roundtune_job {
+    const float* w;        /* the pre-floored weight floor(W / s) * s, n floats */
+    const float* r;        /* rounding parameter R, n floats */
+    const float* scale;    /* num_channel floats */
+    const float* offset;   /* num_channel floats, used as is (not rounded) */
+    float* out;            /* fake-quantised weight (overwritten) */
+    int64_t n, num_channel, elem_per_channel;
+    int32_t qmin, qmax;
+} ppqhip_roundtune_job;
+/* TensorwiseRoundTuningImpl / ChannelwiseRoundTuningImpl.forward, ppq/quantization/algorithm/training.py:490-527:
+ *   out = (clamp(w / s + (r > .5 ? 1 : 0) + o, qmin, qmax) - o) * s
+ * w / s is the IEEE quotient and is NOT rounded to an integer (the reference does not); r NaN adds 0.  The reference's backward
+ * is the identity for w and for r (:502-504), so there is no backward entry point. */
+int ppqhip_roundtune_fwd_multi(const ppqhip_roundtune_job* jobs, int num_jobs, void* stream);
+
 /* quantization error analysis (MI355X-native addition; ppq_amd/analyse.py, ppq_amd/measure.py) -------- */
 /* All three take a HOST array of jobs that is copied into the kernel arguments (more jobs than fit one launch are chunked):
  * no upload, no synchronisation, no atomics, capturable into a HIP graph.  rows, row_len, count <= 2^31 - 1. */

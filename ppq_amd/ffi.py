@@ -294,6 +294,45 @@ def adaround_backward_multi(items, dys, reg: torch.Tensor, dvs=None) -> List[tor
     return dvs
 
 
+# ---- round tuning (include/ppq_hip.h ppqhip_roundtune_fwd_multi) -------------------------------------------------------------
+_ROUNDTUNE_JOB = np.dtype([('w', '<u8'), ('r', '<u8'), ('scale', '<u8'), ('offset', '<u8'), ('out', '<u8'),
+                           ('n', '<i8'), ('num_channel', '<i8'), ('elem_per_channel', '<i8'), ('qmin', '<i4'), ('qmax', '<i4')])
+
+
+def _roundtune_table(items, outs):
+    """items[k] = (w, r, scale, offset, channel_axis or None, quant_min, quant_max): w (the pre-floored weight), r and outs[k]
+    contiguous float32 CUDA tensors of one shape on one device, scale / offset contiguous float32 with one element per channel."""
+    n = len(items)
+    if len(outs) != n: raise RuntimeError(_KERNEL_FAILURE + 'RoundTuning: argument lists differ in length')
+    jobs = np.zeros(n, dtype=_ROUNDTUNE_JOB)
+    dev = items[0][0].device
+    for k, (w, r, s, o, axis, qmin, qmax) in enumerate(items):
+        ts = [('Value', w), ('Rounding', r), ('Scale', s), ('Offset', o), ('Out', outs[k])]
+        for name, t in ts:
+            _f32(t, name)
+            if t.device != dev: raise RuntimeError(_KERNEL_FAILURE + f'RoundTuning: item {k}: {name} is on another device')
+            if not t.is_contiguous(): raise RuntimeError(_KERNEL_FAILURE + f'RoundTuning: item {k}: {name} is not contiguous')
+        for name, t in ts[1:2] + ts[4:]:
+            if t.shape != w.shape: raise RuntimeError(_KERNEL_FAILURE + f'RoundTuning: item {k}: {name} is not shaped like the weight')
+        C, epc = _geometry(w.shape, axis) if axis is not None else (1, w.numel())
+        if s.numel() != C or o.numel() != C:
+            raise RuntimeError(_KERNEL_FAILURE + f'RoundTuning: item {k}: scale / offset need {C} elements')
+        jobs[k] = (w.data_ptr(), r.data_ptr(), s.data_ptr(), o.data_ptr(), outs[k].data_ptr(), w.numel(), C, epc, int(qmin), int(qmax))
+    return jobs
+
+
+def roundtune_forward_multi(items, outs=None) -> List[torch.Tensor]:
+    """RoundTruningDelegator.__call__ (ppq/quantization/algorithm/training.py:490-527, :580-590) for every item in ONE launch;
+    ``outs`` (optional, caller-owned) receive the fake-quantised weights.  The job table travels in the kernel arguments:
+    capturable.  The reference's backward is the identity, so there is nothing else to launch."""
+    if not items: return []
+    if outs is None: outs = [torch.empty_like(it[0]) for it in items]
+    jobs = _roundtune_table(items, outs)
+    with _DeviceOf(items[0][0]):
+        _raise(lib.ppqhip_roundtune_fwd_multi(jobs.ctypes.data, len(items), _stream()))
+    return outs
+
+
 # ---- error analysis (include/ppq_hip.h ppqhip_fetch_rows_multi / ppqhip_measure_rows_multi / ppqhip_measure_finish_multi) ----
 _FETCH_JOB = np.dtype([('x', '<u8'), ('index', '<u8'), ('out', '<u8'), ('rows', '<i8'), ('row_len', '<i8'), ('count', '<i8')])
 _MEASURE_JOB = np.dtype([('p', '<u8'), ('r', '<u8'), ('index', '<u8'), ('sums', '<u8'), ('rows', '<i8'), ('row_len', '<i8'),
@@ -1246,7 +1285,8 @@ def install_plugins_into_ppq(observers: bool = True) -> None:
     * ``ppq.quantization.optim.base.QuantizationOptimizationPass`` is an ABC and PPQ's pipeline admits a pass by
       ``isinstance`` (optim/base.py:60-82): this package's pass base class is registered, so
       ``ppq_amd.calibration.RuntimeCalibrationPass`` (and the parameter / LSQ / bias-correction passes) go into
-      ``ppq.lib.Pipeline``; ``TorchQuantizeDelegator`` likewise admits this package's ``LSQDelegator`` and ``AdaRoundDelegator`` to
+      ``ppq.lib.Pipeline``; ``TorchQuantizeDelegator`` likewise admits this package's ``LSQDelegator``, ``AdaRoundDelegator`` and
+      ``RoundTuningDelegator`` to
       ``TorchExecutor.register_quantize_delegate``;
     * with ``observers=True`` PPQ's ``OBSERVER_TABLE`` (observer/__init__.py:15-23) is updated with the HIP-backed
       observers, so PPQ's OWN ``RuntimeCalibrationPass`` builds them; its two-phase test is by exact type
@@ -1261,11 +1301,12 @@ def install_plugins_into_ppq(observers: bool = True) -> None:
 
     from ppq.executor.torch import TorchQuantizeDelegator
 
-    from . import adaround, calibration, lsq, observer
+    from . import adaround, calibration, lsq, observer, roundtune
     QuantOPRuntimeHook.register(observer.CalibrationHook)
     RefPass.register(calibration.QuantizationOptimizationPass)
     TorchQuantizeDelegator.register(lsq.LSQDelegator)      # register_quantize_delegate admits by isinstance (torch.py:317-320)
     TorchQuantizeDelegator.register(adaround.AdaRoundDelegator)
+    TorchQuantizeDelegator.register(roundtune.RoundTuningDelegator)
     if observers:
         import ppq.quantization.observer as ref_observer
         import ppq.quantization.optim.calibration as ref_calibration
