@@ -505,6 +505,49 @@ typedef struct ppqhip_measure_finish_job {
 } ppqhip_measure_finish_job;
 int ppqhip_measure_finish_multi(const ppqhip_measure_finish_job* jobs, int num_jobs, void* stream);
 
+/* layerwise equalization (ppq_amd/equalization.py; ADDED under ABI 4 like the entries above) ---------- */
+/* Both take a HOST array of jobs that is copied into the kernel arguments (chunked when it does not fit one launch): no
+ * upload, no synchronisation, no atomics.  Every extent is checked on the host before anything is launched. */
+/* One segment = the elements of ONE tensor that belong to the key of channel c:
+ *   base[(c / div) * a + (c % div) * b + o * stride + e]   for o < outer, e < run      (all counts in floats, < 2^31)
+ * `extent`: floats addressable from base (bounds check).  Covers a contiguous upstream weight row (div = 1, a = row length,
+ * outer = 1), a bias / activation-maximum element (a = 1, run = 1), a column of a Gemm weight (a = 1, outer = rows, stride =
+ * row length, run = 1) and the slice of a grouped downstream Conv in the reference's (cin_local, group) row order (div = G). */
+typedef struct ppqhip_equalize_segment {
+    const float* base;
+    int64_t extent;
+    int64_t div, a, b;
+    int64_t outer, stride, run;
+    float multiplier;        /* the key reads |x * multiplier| */
+    int32_t downstream;      /* 0: the segment belongs to the upstream key, else to the downstream key */
+} ppqhip_equalize_segment;
+/* EqualizationPair.calculate_scale over reduce_by_axis(ABSOLUTE_MAX), ppq/quantization/algorithm/equalization.py:419-436:
+ *   up / down = max |x * m| over the upstream / downstream segments (a NaN wins, as in torch.max)
+ *   s = clamp(1.0f / sqrt(up / down), 0.1f, 10.0f)  (each step ONE correctly rounded fp32 operation, NaN kept by the clamp)
+ *   s = 1 where up + down < value_threshold                                          scale[c] = s, c < num_channel */
+typedef struct ppqhip_equalize_scale_job {
+    const ppqhip_equalize_segment* segments;   /* HOST array; at least one upstream and one downstream segment */
+    float* scale;                              /* num_channel floats (overwritten) */
+    int32_t num_segments, num_channel;
+    float value_threshold;
+    int32_t reserved;
+} ppqhip_equalize_scale_job;
+int ppqhip_equalize_scale_multi(const ppqhip_equalize_scale_job* jobs, int num_jobs, void* stream);
+/* EqualizationHelper.scale_to_upstream / scale_to_downstream (:139-198), in place on one dense tensor per job:
+ *   row = i / run;  k = row % inner + (group_out ? (row / inner / group_out) * inner : 0)
+ *   x[i] = divide ? x[i] / scale[k] (IEEE quotient) : x[i] * scale[k]
+ * upstream [O, ...]: run = elements per output channel, inner = O; a Gemm weight stored [I, O]: run = 1, inner = O; bias: run = 1;
+ * downstream Conv [O, I / G, k...]: run = prod(k), inner = I / G, group_out = O / G; downstream Gemm [O, I]: run = 1, inner = I.
+ * The tensors of the jobs of ONE call must not overlap. */
+typedef struct ppqhip_equalize_apply_job {
+    float* x;
+    const float* scale;
+    int64_t n, run, inner, group_out;
+    int64_t num_scale;       /* elements of scale (bounds check) */
+    int32_t divide, reserved;
+} ppqhip_equalize_apply_job;
+int ppqhip_equalize_apply_multi(const ppqhip_equalize_apply_job* jobs, int num_jobs, void* stream);
+
 /* profiling aid used by bench.py: when enabled, every kernel launch made through this library
  * on this thread is bracketed by hipEvents on its own stream; ppqhip_prof_collect() synchronises
  * those events and returns, per kernel id, launches / total ms / total algorithmic bytes. */

@@ -97,6 +97,8 @@ PROTOTYPES = {
     'ppqhip_adaround_fwd_multi': (c_int, [c_vp, c_int, c_vp]),
     'ppqhip_adaround_bwd_multi': (c_int, [c_vp, c_int, c_f32p, c_vp]),
     'ppqhip_roundtune_fwd_multi': (c_int, [c_vp, c_int, c_vp]),
+    'ppqhip_equalize_scale_multi': (c_int, [c_vp, c_int, c_vp]),
+    'ppqhip_equalize_apply_multi': (c_int, [c_vp, c_int, c_vp]),
     'ppqhip_fetch_rows_multi': (c_int, [c_vp, c_int, c_vp]),
     'ppqhip_measure_rows_multi': (c_int, [c_vp, c_int, c_vp]),
     'ppqhip_measure_finish_multi': (c_int, [c_vp, c_int, c_vp]),

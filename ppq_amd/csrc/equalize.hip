@@ -1,0 +1,321 @@
+// equalize.hip -- layerwise equalization: the scales of a group of independent pairs in ONE launch, their application in another.
+// Mirror of ppq/quantization/algorithm/equalization.py:27-198 (EqualizationHelper) and :419-436 (calculate_scale over
+// reduce_by_axis(ABSOLUTE_MAX)), which the reference runs as ~20 small torch ops per pair and iteration.
+//
+// Bitwise the torch sequence (fp32, -ffp-contract=off, correctly rounded division and square root: common.hpp), op for op:
+//   up = max |x * m| over the upstream rows, down = the same over the downstream slices (max is order independent; a NaN wins as
+//   in torch.max)      q = up / down      r = sqrt(q)      s = 1.0f / r      s = clamp(s, 0.1f, 10.0f) (NaN kept)
+//   s = 1 where up + down < threshold
+//   upstream weight / bias: x = x * s[c]          downstream weight: x = x / s[k]  (IEEE quotient)
+//
+// Two kernels, not one per channel: for a grouped downstream Conv the reference orders its key rows (cin_local, group) but applies
+// the scale in (group, cin_local) order, so the slice a channel READS for its key is not the slice its scale is APPLIED to -- a
+// fused reduce-and-apply workgroup would race with its neighbours.
+//
+// Jobs and segments travel in the kernel arguments (chunked when they do not fit): no upload.  No atomics; the reductions are the
+// wave64 shuffle + LDS pattern of reduce.hip.
+#include <algorithm>
+#include <vector>
+
+#include "common.hpp"
+
+namespace ppqhip {
+namespace {
+
+// ------------------------------------------------------------------------------------ scale
+constexpr int kEqMaxJobs = 32;                     // pairs per launch
+constexpr int kEqMaxSegs = 72;                     // segments per launch (a ResNet stage pair with bias and activations has ~30)
+
+struct EqSeg {                                     // 40 B
+    const float* base;
+    uint32_t div, a, b;                            // offset of channel c: (c / div) * a + (c % div) * b
+    uint32_t outer, stride, run;
+    float mult;
+    uint32_t flags;                                // bit 0: downstream key; bit 1: 16-B loads (base, a, b, stride, run all 4-aligned)
+};
+struct EqScaleJob {                                // 24 B
+    float* scale;
+    uint32_t C;
+    float threshold;
+    uint32_t seg_begin, seg_count;
+};
+struct EqScaleArgs {
+    EqSeg segs[kEqMaxSegs];
+    EqScaleJob jobs[kEqMaxJobs];
+    uint32_t first_block[kEqMaxJobs];
+    uint32_t count;
+};
+static_assert(sizeof(EqScaleArgs) <= 4096, "kernel arguments are limited to 4 KB");
+
+__device__ __forceinline__ float eq_clamp_nan(float v, float lo, float hi) {    // torch's clamp: NaN passes through
+    return __builtin_isnan(v) ? v : __builtin_fminf(__builtin_fmaxf(v, lo), hi);
+}
+
+// one workgroup per (job, channel): lanes stride over the channel's elements of every segment
+__global__ __launch_bounds__(kBlock) void equalize_scale_kernel(const EqScaleArgs args) {
+    __shared__ float lds[4 * (kBlock / kWave)];
+    uint32_t lo = 0, hi = args.count;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (args.first_block[mid] <= blockIdx.x) lo = mid; else hi = mid;
+    }
+    lo = __builtin_amdgcn_readfirstlane(lo);
+    const EqScaleJob& j = args.jobs[lo];
+    const uint32_t c = blockIdx.x - args.first_block[lo];
+    float key[2] = {0.f, 0.f}, bad[2] = {0.f, 0.f};                       // [0] upstream, [1] downstream; |x| >= 0, so 0 is neutral
+    for (uint32_t k = 0; k < j.seg_count; k++) {
+        const EqSeg& g = args.segs[j.seg_begin + k];
+        const uint32_t q = c / g.div;
+        const float* p = g.base + (size_t)q * g.a + (size_t)(c - q * g.div) * g.b;
+        const float mult = g.mult;
+        float m = 0.f, nan = 0.f;
+        auto fold = [&](float x) {
+            const float t = __builtin_fabsf(x * mult);
+            m = fmaxf(m, t);                                               // drops a NaN operand: tracked on its own
+            nan = (t != t) ? 1.f : nan;
+        };
+        if (g.flags & 2u) {
+            const uint32_t run4 = g.run >> 2, total = g.outer * run4;
+            for (uint32_t i = threadIdx.x; i < total; i += kBlock) {
+                const uint32_t o = (g.outer == 1) ? 0u : i / run4, e = i - o * run4;
+                const float4 v = reinterpret_cast<const float4*>(p + (size_t)o * g.stride)[e];
+                fold(v.x); fold(v.y); fold(v.z); fold(v.w);
+            }
+        } else {
+            const uint32_t total = g.outer * g.run;
+            for (uint32_t i = threadIdx.x; i < total; i += kBlock) {
+                const uint32_t o = (g.outer == 1) ? 0u : (g.run == 1 ? i : i / g.run), e = i - o * g.run;
+                fold(p[(size_t)o * g.stride + e]);
+            }
+        }
+        const uint32_t side = g.flags & 1u;                                // wave-uniform
+        key[side] = fmaxf(key[side], m);
+        bad[side] = fmaxf(bad[side], nan);
+    }
+    float up = wave_max(key[0]), dn = wave_max(key[1]), up_nan = wave_max(bad[0]), dn_nan = wave_max(bad[1]);
+    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) { lds[4 * wid] = up; lds[4 * wid + 1] = dn; lds[4 * wid + 2] = up_nan; lds[4 * wid + 3] = dn_nan; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kBlock / kWave; w++) {
+            up = fmaxf(up, lds[4 * w]); dn = fmaxf(dn, lds[4 * w + 1]);
+            up_nan = fmaxf(up_nan, lds[4 * w + 2]); dn_nan = fmaxf(dn_nan, lds[4 * w + 3]);
+        }
+        if (up_nan > 0.f) up = __builtin_nanf("");
+        if (dn_nan > 0.f) dn = __builtin_nanf("");
+        const float q = up / dn;
+        const float r = __builtin_sqrtf(q);
+        float s = 1.0f / r;
+        s = eq_clamp_nan(s, 0.1f, 10.0f);
+        if (up + dn < j.threshold) s = 1.0f;
+        j.scale[c] = s;
+    }
+}
+
+// ------------------------------------------------------------------------------------ apply
+constexpr int kEqApMaxJobs = 32;
+constexpr uint32_t kEqApMaxBlocksPerJob = 1024;    // grid-strided beyond
+
+struct EqApJob {                                   // 80 B
+    float* x;
+    const float* scale;
+    uint32_t n, nvec;                              // nvec: float4 count (0: 4-B accesses); then `run` holds run / 4
+    FastDiv run, inner, og;
+    uint32_t grouped, divide, blocks, pad;
+};
+struct EqApArgs {
+    EqApJob jobs[kEqApMaxJobs];
+    uint32_t first_block[kEqApMaxJobs];
+    uint32_t count;
+};
+static_assert(sizeof(EqApArgs) <= 4096, "kernel arguments are limited to 4 KB");
+
+__device__ __forceinline__ uint32_t eq_scale_index(const EqApJob& j, uint32_t unit) {       // unit: element (or float4) index
+    const uint32_t row = fdiv(unit, j.run);
+    const uint32_t o = fdiv(row, j.inner);
+    uint32_t k = row - o * j.inner.d;
+    if (j.grouped) k += fdiv(o, j.og) * j.inner.d;
+    return k;
+}
+
+__global__ __launch_bounds__(kBlock) void equalize_apply_kernel(const EqApArgs args) {
+    uint32_t lo = 0, hi = args.count;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (args.first_block[mid] <= blockIdx.x) lo = mid; else hi = mid;
+    }
+    lo = __builtin_amdgcn_readfirstlane(lo);
+    const EqApJob& j = args.jobs[lo];
+    const uint32_t stride = j.blocks * kBlock;
+    const uint32_t first = (blockIdx.x - args.first_block[lo]) * kBlock + threadIdx.x;
+    if (j.nvec == 0) {                                                    // unaligned pointer or run % 4 != 0
+        for (uint32_t i = first; i < j.n; i += stride) {
+            const float s = j.scale[eq_scale_index(j, i)];
+            const float x = j.x[i];
+            j.x[i] = j.divide ? x / s : x * s;
+        }
+        return;
+    }
+    float4* x4 = reinterpret_cast<float4*>(j.x);
+    for (uint32_t q = first; q < j.nvec; q += stride) {                   // one channel per float4
+        const float s = j.scale[eq_scale_index(j, q)];
+        float4 v = x4[q];
+        if (j.divide) { v.x = v.x / s; v.y = v.y / s; v.z = v.z / s; v.w = v.w / s; }
+        else { v.x = v.x * s; v.y = v.y * s; v.z = v.z * s; v.w = v.w * s; }
+        x4[q] = v;
+    }
+}
+
+constexpr int64_t kEqMax = 0x7fffffffLL;
+
+int validate_scale(const ppqhip_equalize_scale_job* jobs, int num_jobs) {
+    const char* what = "equalize_scale_multi";
+    if (num_jobs < 0 || (num_jobs > 0 && jobs == nullptr)) { set_error("%s: bad job table", what); return PPQHIP_ERR_INVALID_VALUE; }
+    for (int k = 0; k < num_jobs; k++) {
+        const ppqhip_equalize_scale_job& j = jobs[k];
+        if (j.segments == nullptr || j.scale == nullptr || j.num_channel <= 0 || j.num_segments <= 0) {
+            set_error("%s: job %d: null pointer, no channel or no segment", what, k); return PPQHIP_ERR_INVALID_VALUE;
+        }
+        if (j.num_segments > kEqMaxSegs) {
+            set_error("%s: job %d: %d segments, at most %d fit one launch", what, k, j.num_segments, kEqMaxSegs);
+            return PPQHIP_ERR_UNSUPPORTED;
+        }
+        bool has_up = false, has_down = false;
+        for (int t = 0; t < j.num_segments; t++) {
+            const ppqhip_equalize_segment& g = j.segments[t];
+            if (g.base == nullptr || g.div < 1 || g.a < 0 || g.b < 0 || g.outer < 1 || g.run < 1 || g.stride < 0 || g.extent < 1 ||
+                g.extent > kEqMax || g.div > kEqMax || g.a > kEqMax || g.b > kEqMax || g.outer > kEqMax || g.run > kEqMax ||
+                g.stride > kEqMax || g.outer * g.run > kEqMax) {
+                set_error("%s: job %d segment %d: bad geometry", what, k, t); return PPQHIP_ERR_INVALID_VALUE;
+            }
+            const int64_t C = j.num_channel;
+            const int64_t last = ((C - 1) / g.div) * g.a + (std::min<int64_t>(g.div, C) - 1) * g.b + (g.outer - 1) * g.stride + g.run - 1;
+            if (last >= g.extent) {
+                set_error("%s: job %d segment %d: reads element %lld of a tensor of %lld", what, k, t, (long long)last, (long long)g.extent);
+                return PPQHIP_ERR_INVALID_VALUE;
+            }
+            (g.downstream ? has_down : has_up) = true;
+        }
+        if (!has_up || !has_down) { set_error("%s: job %d needs an upstream and a downstream segment", what, k); return PPQHIP_ERR_INVALID_VALUE; }
+    }
+    return PPQHIP_OK;
+}
+
+void launch_scale(const ppqhip_equalize_scale_job* jobs, int num_jobs, hipStream_t s) {
+    for (int base = 0; base < num_jobs;) {
+        EqScaleArgs args;
+        uint32_t count = 0, segs = 0, blocks = 0;
+        while (base + (int)count < num_jobs && count < (uint32_t)kEqMaxJobs &&
+               segs + (uint32_t)jobs[base + count].num_segments <= (uint32_t)kEqMaxSegs) {
+            const ppqhip_equalize_scale_job& src = jobs[base + count];
+            EqScaleJob& d = args.jobs[count];
+            d.scale = src.scale; d.C = (uint32_t)src.num_channel; d.threshold = src.value_threshold;
+            d.seg_begin = segs; d.seg_count = (uint32_t)src.num_segments;
+            for (int t = 0; t < src.num_segments; t++) {
+                const ppqhip_equalize_segment& g = src.segments[t];
+                EqSeg& e = args.segs[segs++];
+                e.base = g.base; e.div = (uint32_t)g.div; e.a = (uint32_t)g.a; e.b = (uint32_t)g.b;
+                e.outer = (uint32_t)g.outer; e.stride = (uint32_t)g.stride; e.run = (uint32_t)g.run; e.mult = g.multiplier;
+                const bool vec = aligned16(g.base) && g.run % 4 == 0 && g.a % 4 == 0 && g.b % 4 == 0 && g.stride % 4 == 0;
+                e.flags = (g.downstream ? 1u : 0u) | (vec ? 2u : 0u);
+            }
+            args.first_block[count] = blocks;
+            blocks += d.C;
+            count++;
+        }
+        for (uint32_t k = segs; k < (uint32_t)kEqMaxSegs; k++) args.segs[k] = args.segs[0];
+        for (uint32_t k = count; k < (uint32_t)kEqMaxJobs; k++) { args.jobs[k] = args.jobs[0]; args.first_block[k] = blocks; }
+        args.count = count;
+        hipLaunchKernelGGL(equalize_scale_kernel, dim3(blocks), dim3(kBlock), 0, s, args);
+        base += (int)count;
+    }
+}
+
+int validate_apply(const ppqhip_equalize_apply_job* jobs, int num_jobs) {
+    const char* what = "equalize_apply_multi";
+    if (num_jobs < 0 || (num_jobs > 0 && jobs == nullptr)) { set_error("%s: bad job table", what); return PPQHIP_ERR_INVALID_VALUE; }
+    for (int k = 0; k < num_jobs; k++) {
+        const ppqhip_equalize_apply_job& j = jobs[k];
+        if (j.x == nullptr || j.scale == nullptr) { set_error("%s: job %d has a null pointer", what, k); return PPQHIP_ERR_INVALID_VALUE; }
+        if (j.n <= 0 || j.n > kEqMax || j.run <= 0 || j.inner <= 0 || j.group_out < 0 || j.num_scale <= 0 || j.n % j.run != 0 ||
+            j.inner > kEqMax || j.group_out > kEqMax) {
+            set_error("%s: job %d: bad geometry (n=%lld run=%lld inner=%lld group_out=%lld)", what, k, (long long)j.n, (long long)j.run,
+                      (long long)j.inner, (long long)j.group_out);
+            return PPQHIP_ERR_INVALID_VALUE;
+        }
+        const int64_t rows = j.n / j.run;
+        const int64_t last = std::min(j.inner, rows) - 1 + (j.group_out ? ((rows - 1) / j.inner / j.group_out) * j.inner : 0);
+        if (last >= j.num_scale) {
+            set_error("%s: job %d reads scale %lld of %lld", what, k, (long long)last, (long long)j.num_scale);
+            return PPQHIP_ERR_INVALID_VALUE;
+        }
+    }
+    std::vector<std::pair<const float*, const float*>> spans;             // in place: two jobs on one tensor would race
+    for (int k = 0; k < num_jobs; k++) spans.emplace_back(jobs[k].x, jobs[k].x + jobs[k].n);
+    std::sort(spans.begin(), spans.end());
+    for (size_t k = 1; k < spans.size(); k++) {
+        if (spans[k].first < spans[k - 1].second) { set_error("%s: two jobs overlap in memory", what); return PPQHIP_ERR_INVALID_VALUE; }
+    }
+    return PPQHIP_OK;
+}
+
+void launch_apply(const ppqhip_equalize_apply_job* jobs, int num_jobs, hipStream_t s) {
+    for (int base = 0; base < num_jobs; base += kEqApMaxJobs) {
+        EqApArgs args;
+        const int count = std::min(kEqApMaxJobs, num_jobs - base);
+        uint32_t blocks = 0;
+        for (int k = 0; k < count; k++) {
+            const ppqhip_equalize_apply_job& src = jobs[base + k];
+            EqApJob& d = args.jobs[k];
+            d.x = src.x; d.scale = src.scale; d.n = (uint32_t)src.n;
+            const bool vec = aligned16(src.x) && src.run % 4 == 0;
+            d.nvec = vec ? (uint32_t)(src.n >> 2) : 0u;
+            d.run = make_fastdiv((uint32_t)(vec ? src.run / 4 : src.run));
+            d.inner = make_fastdiv((uint32_t)src.inner);
+            d.og = make_fastdiv((uint32_t)(src.group_out ? src.group_out : 1));
+            d.grouped = src.group_out ? 1u : 0u; d.divide = src.divide ? 1u : 0u; d.pad = 0;
+            const uint64_t work = vec ? d.nvec : (uint64_t)src.n;
+            d.blocks = (uint32_t)std::min<uint64_t>((work + kBlock - 1) / kBlock, kEqApMaxBlocksPerJob);
+            args.first_block[k] = blocks;
+            blocks += d.blocks;
+        }
+        for (int k = count; k < kEqApMaxJobs; k++) { args.jobs[k] = args.jobs[0]; args.first_block[k] = blocks; }
+        args.count = (uint32_t)count;
+        hipLaunchKernelGGL(equalize_apply_kernel, dim3(blocks), dim3(kBlock), 0, s, args);
+    }
+}
+
+}  // namespace
+}  // namespace ppqhip
+
+using namespace ppqhip;
+
+extern "C" {
+
+int ppqhip_equalize_scale_multi(const ppqhip_equalize_scale_job* jobs, int num_jobs, void* stream) {
+    if (int st = validate_scale(jobs, num_jobs)) return st;
+    if (num_jobs == 0) return PPQHIP_OK;
+    hipStream_t s = (hipStream_t)stream;
+    double bytes = 0.0;
+    for (int k = 0; k < num_jobs; k++) {
+        for (int t = 0; t < jobs[k].num_segments; t++)
+            bytes += 4.0 * (double)jobs[k].num_channel * (double)(jobs[k].segments[t].outer * jobs[k].segments[t].run);
+        bytes += 4.0 * (double)jobs[k].num_channel;
+    }
+    LaunchScope scope(K_EQUALIZE_SCALE, bytes, s);
+    launch_scale(jobs, num_jobs, s);
+    return finish_launch("equalize_scale_multi");
+}
+
+int ppqhip_equalize_apply_multi(const ppqhip_equalize_apply_job* jobs, int num_jobs, void* stream) {
+    if (int st = validate_apply(jobs, num_jobs)) return st;
+    if (num_jobs == 0) return PPQHIP_OK;
+    hipStream_t s = (hipStream_t)stream;
+    double bytes = 0.0;
+    for (int k = 0; k < num_jobs; k++) bytes += 8.0 * (double)jobs[k].n;           // x in, x out
+    LaunchScope scope(K_EQUALIZE_APPLY, bytes, s);
+    launch_apply(jobs, num_jobs, s);
+    return finish_launch("equalize_apply_multi");
+}
+
+}  // extern "C"

@@ -333,6 +333,81 @@ def roundtune_forward_multi(items, outs=None) -> List[torch.Tensor]:
     return outs
 
 
+# ---- layerwise equalization (include/ppq_hip.h ppqhip_equalize_scale_multi / ppqhip_equalize_apply_multi) --------------------
+_EQ_SEGMENT = np.dtype([('base', '<u8'), ('extent', '<i8'), ('div', '<i8'), ('a', '<i8'), ('b', '<i8'), ('outer', '<i8'),
+                        ('stride', '<i8'), ('run', '<i8'), ('multiplier', '<f4'), ('downstream', '<i4')])
+_EQ_SCALE_JOB = np.dtype([('segments', '<u8'), ('scale', '<u8'), ('num_segments', '<i4'), ('num_channel', '<i4'),
+                          ('value_threshold', '<f4'), ('reserved', '<i4')])
+_EQ_APPLY_JOB = np.dtype([('x', '<u8'), ('scale', '<u8'), ('n', '<i8'), ('run', '<i8'), ('inner', '<i8'), ('group_out', '<i8'),
+                          ('num_scale', '<i8'), ('divide', '<i4'), ('reserved', '<i4')])
+
+
+def _eq_tensor(t, what: str, k: int, dev):
+    _f32(t, what)
+    if t.device != dev: raise RuntimeError(_KERNEL_FAILURE + f'Equalization: item {k}: {what} is on another device')
+    if not t.is_contiguous(): raise RuntimeError(_KERNEL_FAILURE + f'Equalization: item {k}: {what} is not contiguous')
+
+
+class EqualizeTable:
+    """The host job table of one equalization launch, built once and launched every iteration: the jobs hold POINTERS and the
+    pass changes its tensors in place.  Keeps the tensors (and the segment array the jobs point into) alive."""
+    __slots__ = ('jobs', 'segments', 'keep', 'entry')
+
+    def __init__(self, jobs, segments, keep, entry):
+        self.jobs, self.segments, self.keep, self.entry = jobs, segments, keep, entry
+
+    def __len__(self) -> int: return len(self.jobs)
+
+    def run(self) -> None:
+        if len(self.jobs) == 0: return
+        with _DeviceOf(self.keep[0]):
+            _raise(self.entry(self.jobs.ctypes.data, len(self.jobs), _stream()))
+
+
+def equalize_scale_table(items) -> EqualizeTable:
+    """items[k] = (scale, value_threshold, segments): ``scale`` a contiguous float32[C] CUDA tensor that receives the pair's
+    scale; segments[t] = (tensor, div, a, b, outer, stride, run, multiplier, downstream) as ``ppqhip_equalize_segment``
+    describes them, ``tensor`` contiguous float32 on the same device (its numel is the extent the library checks against)."""
+    jobs = np.zeros(len(items), dtype=_EQ_SCALE_JOB)
+    segs = np.zeros(sum(len(it[2]) for it in items), dtype=_EQ_SEGMENT)
+    keep, at = [], 0
+    dev = items[0][0].device if items else None
+    for k, (scale, threshold, segments) in enumerate(items):
+        _eq_tensor(scale, 'Scale', k, dev)
+        keep.append(scale)
+        jobs[k] = (segs.ctypes.data + at * _EQ_SEGMENT.itemsize, scale.data_ptr(), len(segments), scale.numel(), float(threshold), 0)
+        for t, div, a, b, outer, stride, run, mult, down in segments:
+            _eq_tensor(t, 'Value', k, dev)
+            keep.append(t)
+            segs[at] = (t.data_ptr(), t.numel(), int(div), int(a), int(b), int(outer), int(stride), int(run), float(mult), 1 if down else 0)
+            at += 1
+    return EqualizeTable(jobs, segs, keep, lib.ppqhip_equalize_scale_multi)
+
+
+def equalize_apply_table(items) -> EqualizeTable:
+    """items[k] = (x, scale, run, inner, group_out, divide) as ``ppqhip_equalize_apply_job`` describes them: ``x`` is changed in
+    place.  The tensors of one table must not overlap (the library refuses)."""
+    jobs = np.zeros(len(items), dtype=_EQ_APPLY_JOB)
+    keep = []
+    dev = items[0][0].device if items else None
+    for k, (x, scale, run, inner, group_out, divide) in enumerate(items):
+        _eq_tensor(x, 'Value', k, dev); _eq_tensor(scale, 'Scale', k, dev)
+        keep += [x, scale]
+        jobs[k] = (x.data_ptr(), scale.data_ptr(), x.numel(), int(run), int(inner), int(group_out), scale.numel(), 1 if divide else 0, 0)
+    return EqualizeTable(jobs, None, keep, lib.ppqhip_equalize_apply_multi)
+
+
+def equalize_scale_multi(items) -> None:
+    """EqualizationPair.calculate_scale over reduce_by_axis (ppq/quantization/algorithm/equalization.py:419-436) for every item
+    (an :class:`EqualizeTable` or the items of :func:`equalize_scale_table`) in ONE launch."""
+    (items if isinstance(items, EqualizeTable) else equalize_scale_table(items)).run()
+
+
+def equalize_apply_multi(items) -> None:
+    """EqualizationHelper.scale_to_upstream / scale_to_downstream (:139-198) for every item in ONE launch, in place."""
+    (items if isinstance(items, EqualizeTable) else equalize_apply_table(items)).run()
+
+
 # ---- error analysis (include/ppq_hip.h ppqhip_fetch_rows_multi / ppqhip_measure_rows_multi / ppqhip_measure_finish_multi) ----
 _FETCH_JOB = np.dtype([('x', '<u8'), ('index', '<u8'), ('out', '<u8'), ('rows', '<i8'), ('row_len', '<i8'), ('count', '<i8')])
 _MEASURE_JOB = np.dtype([('p', '<u8'), ('r', '<u8'), ('index', '<u8'), ('sums', '<u8'), ('rows', '<i8'), ('row_len', '<i8'),
