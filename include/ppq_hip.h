@@ -548,6 +548,60 @@ typedef struct ppqhip_equalize_apply_job {
 } ppqhip_equalize_apply_job;
 int ppqhip_equalize_apply_multi(const ppqhip_equalize_apply_job* jobs, int num_jobs, void* stream);
 
+/* SSD equalization (ppq_amd/ssd.py; ADDED under ABI 4 like the entries above) ------------------------- */
+/* All three take a HOST array of jobs that is copied into the kernel arguments (chunked when it does not fit one launch): no
+ * upload, no synchronisation, no atomics, capturable.  Every extent is checked on the host before anything is launched. */
+/* The four candidate scales of one pair, one_step_equalization of ppq/quantization/optim/ssd.py:288-320 on the ranges of
+ * prepare_weight_for_equalization (:152-210).  `first`: the key of OUTPUT channel c of the pair's first weight; `last`: the key
+ * of INPUT channel c of its last weight, for a grouped Conv in the natural (group, cin_local) order (div = I / G, a = the group
+ * stride, b = prod(k), outer = O / G, stride = I / G * prod(k), run = prod(k)); multiplier / downstream are not read.
+ *   ranges[0][c] = max |first key|, ranges[1][c] = max |last key|          (a NaN wins, as in torch.max)
+ *   scales[0][c] = clamp(sqrt(last / (first + 1e-8f)), 0.1f, 10.0f)
+ *   algo 1-3: first / last floored at their max * channel_ratio, act_range floored at 0.01f;
+ *             ks = max(first) / (first + 1e-8f), nks = the same of last, as = the same of act_range
+ *   scales[1][c] = min(ks, as)
+ *   scales[2][c] = clamp(t / min_c(t), 1.0f, 2.0f),  t = min(min(ks / nks, as / nks), 8.0f)
+ *   scales[3][c] = clamp(sqrt(as * sqrt(ks / nks)), 1.0f, 2.0f)
+ * Each step is ONE correctly rounded fp32 operation in that order; the cross-channel max / min are exact; NaN is kept. */
+typedef struct ppqhip_ssd_scales_job {
+    ppqhip_equalize_segment first, last;
+    const float* act_range;  /* num_channel floats */
+    float* scales;           /* 4 x num_channel floats (overwritten) */
+    float* ranges;           /* 2 x num_channel floats (overwritten) */
+    int32_t num_channel;
+    float channel_ratio;
+} ppqhip_ssd_scales_job;
+int ppqhip_ssd_scales_multi(const ppqhip_ssd_scales_job* jobs, int num_jobs, void* stream);
+/* write_back (:212-262) of all four candidates of one dense tensor, OUT OF PLACE (x is only read), geometry as in
+ * ppqhip_equalize_apply_job:   row = i / run;  k = row % inner + (group_out ? (row / inner / group_out) * inner : 0)
+ *   out[cand * n + i] = divide ? x[i] / scales[cand * num_channel + k] (IEEE quotient) : x[i] * scales[cand * num_channel + k]
+ * for cand < 4.  No output may overlap an input or another output of the same call. */
+typedef struct ppqhip_ssd_apply_job {
+    const float* x;
+    float* out;              /* 4 x n floats */
+    const float* scales;     /* 4 x num_channel floats */
+    int64_t n, run, inner, group_out;
+    int64_t num_channel;
+    int32_t divide, reserved;
+} ppqhip_ssd_apply_job;
+int ppqhip_ssd_apply_multi(const ppqhip_ssd_apply_job* jobs, int num_jobs, void* stream);
+/* sums[b] = the four row sums of ppqhip_measure_rows_multi between p = fake_quant(y) and r (both dense rows x count), the
+ * fake-quant of a linear config done in registers: channel of element e of a row = e / elem_per_channel, count == num_channel *
+ * elem_per_channel (per tensor: num_channel = 1).  Bit-identical to ppqhip_fq_linear_t / _c of y (viewed as [rows, num_channel,
+ * elem_per_channel]) into a buffer followed by ppqhip_measure_rows_multi on that buffer; y and r are read once, nothing else
+ * is written. */
+typedef struct ppqhip_fq_measure_rows_job {
+    const float* y;
+    const float* r;
+    const float* scale;      /* num_channel floats */
+    const float* offset;     /* num_channel floats */
+    double* sums;            /* rows x 4, overwritten */
+    int64_t rows, count;
+    int64_t num_channel, elem_per_channel;
+    int32_t clip_min, clip_max, rounding, reserved;
+} ppqhip_fq_measure_rows_job;
+int ppqhip_fq_measure_rows_multi(const ppqhip_fq_measure_rows_job* jobs, int num_jobs, void* stream);
+
 /* profiling aid used by bench.py: when enabled, every kernel launch made through this library
  * on this thread is bracketed by hipEvents on its own stream; ppqhip_prof_collect() synchronises
  * those events and returns, per kernel id, launches / total ms / total algorithmic bytes. */

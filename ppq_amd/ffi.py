@@ -408,6 +408,86 @@ def equalize_apply_multi(items) -> None:
     (items if isinstance(items, EqualizeTable) else equalize_apply_table(items)).run()
 
 
+# ---- SSD equalization (include/ppq_hip.h ppqhip_ssd_scales_multi / ppqhip_ssd_apply_multi / ppqhip_fq_measure_rows_multi) ----
+_SSD_SCALES_JOB = np.dtype([('first', _EQ_SEGMENT), ('last', _EQ_SEGMENT), ('act_range', '<u8'), ('scales', '<u8'), ('ranges', '<u8'),
+                            ('num_channel', '<i4'), ('channel_ratio', '<f4')])
+_SSD_APPLY_JOB = np.dtype([('x', '<u8'), ('out', '<u8'), ('scales', '<u8'), ('n', '<i8'), ('run', '<i8'), ('inner', '<i8'),
+                           ('group_out', '<i8'), ('num_channel', '<i8'), ('divide', '<i4'), ('reserved', '<i4')])
+_FQ_MEASURE_JOB = np.dtype([('y', '<u8'), ('r', '<u8'), ('scale', '<u8'), ('offset', '<u8'), ('sums', '<u8'), ('rows', '<i8'),
+                            ('count', '<i8'), ('num_channel', '<i8'), ('elem_per_channel', '<i8'), ('clip_min', '<i4'),
+                            ('clip_max', '<i4'), ('rounding', '<i4'), ('reserved', '<i4')])
+
+
+def ssd_scales_multi(items) -> None:
+    """The four candidate scales of every pair of ``items`` in ONE call (ppq/quantization/optim/ssd.py:288-320 without the
+    write-back).  items[k] = (first, last, act_range, channel_ratio, scales, ranges): ``first`` / ``last`` are segments
+    (tensor, div, a, b, outer, stride, run) as ``ppqhip_equalize_segment`` describes them -- the rows of output channel c of the
+    pair's first weight and the slices of input channel c of its last weight; ``act_range`` float32 [C]; ``scales`` float32
+    [4, C] and ``ranges`` float32 [2, C] are overwritten.  Everything contiguous float32 on one device."""
+    if not items: return
+    jobs = np.zeros(len(items), dtype=_SSD_SCALES_JOB)
+    dev = items[0][2].device
+    for k, (first, last, act, ratio, scales, ranges) in enumerate(items):
+        C = act.numel()
+        for what, t, n in (('ActRange', act, C), ('Scales', scales, 4 * C), ('Ranges', ranges, 2 * C)):
+            _eq_tensor(t, what, k, dev)
+            if t.numel() != n: raise RuntimeError(_KERNEL_FAILURE + f'SSD scales: item {k}: {what} must hold {n} floats')
+        segs = []
+        for what, (t, div, a, b, outer, stride, run) in (('First', first), ('Last', last)):
+            _eq_tensor(t, what, k, dev)
+            segs.append((t.data_ptr(), t.numel(), int(div), int(a), int(b), int(outer), int(stride), int(run), 1.0, 0))
+        jobs[k] = (segs[0], segs[1], act.data_ptr(), scales.data_ptr(), ranges.data_ptr(), C, float(ratio))
+    with _DeviceOf(items[0][2]):
+        _raise(lib.ppqhip_ssd_scales_multi(jobs.ctypes.data, len(items), _stream()))
+
+
+def ssd_apply_multi(items) -> None:
+    """write_back (ssd.py:212-262) of all four candidates of every tensor of ``items`` in ONE launch, out of place.
+    items[k] = (x, out, scales, run, inner, group_out, divide): ``out`` float32 [4, *x.shape] receives x * s_k (or the IEEE
+    quotient x / s_k) for the four rows s_k of ``scales`` [4, C]; geometry as in :func:`equalize_apply_table`.  x is not
+    written."""
+    if not items: return
+    jobs = np.zeros(len(items), dtype=_SSD_APPLY_JOB)
+    dev = items[0][0].device
+    for k, (x, out, scales, run, inner, group_out, divide) in enumerate(items):
+        _eq_tensor(x, 'Value', k, dev); _eq_tensor(out, 'Out', k, dev); _eq_tensor(scales, 'Scales', k, dev)
+        if out.numel() != 4 * x.numel(): raise RuntimeError(_KERNEL_FAILURE + f'SSD apply: item {k}: Out must hold 4 x {x.numel()} floats')
+        if scales.numel() % 4: raise RuntimeError(_KERNEL_FAILURE + f'SSD apply: item {k}: Scales must be [4, C]')
+        jobs[k] = (x.data_ptr(), out.data_ptr(), scales.data_ptr(), x.numel(), int(run), int(inner), int(group_out),
+                   scales.numel() // 4, 1 if divide else 0, 0)
+    with _DeviceOf(items[0][0]):
+        _raise(lib.ppqhip_ssd_apply_multi(jobs.ctypes.data, len(items), _stream()))
+
+
+def fq_measure_rows_multi(items, sums=None) -> List[torch.Tensor]:
+    """The row sums ``[rows, 4]`` of :func:`measure_rows_multi` between ``fake_quant(y)`` and ``r`` for every item, the
+    fake-quant done in registers: ONE launch, y and r read once, nothing else written, bit-identical to ``LinearQuantize_T/C``
+    into a buffer followed by ``measure_rows_multi``.  items[k] = (y, r, scale, offset, channel_axis, quant_min, quant_max,
+    rounding): a linear config, ``channel_axis`` None (per tensor) or 1 (the axis behind the batch axis)."""
+    if not items: return []
+    dev = items[0][0].device
+    if sums is None: sums = [torch.empty([it[0].shape[0], 4], dtype=torch.float64, device=dev) for it in items]
+    jobs = np.zeros(len(items), dtype=_FQ_MEASURE_JOB)
+    for k, ((y, r, scale, offset, axis, qmin, qmax, rounding), out) in enumerate(zip(items, sums)):
+        rows, count = _rows_of(y, 'Value')
+        if _rows_of(r, 'Real') != (rows, count): raise RuntimeError(_KERNEL_FAILURE + f'fq measure: item {k}: Value {tuple(y.shape)} and Real {tuple(r.shape)} do not match')
+        _f32(scale, 'Scale'); _f32(offset, 'Offset')
+        if axis is None: C, epc = 1, count
+        else:
+            if axis % y.dim() != 1: raise RuntimeError(_KERNEL_FAILURE + f'fq measure: item {k}: channel_axis must be 1, {axis} was given')
+            C, epc = _geometry(y.shape, 1)
+        if scale.numel() != C or offset.numel() != C or not scale.is_contiguous() or not offset.is_contiguous():
+            raise RuntimeError(_KERNEL_FAILURE + f'fq measure: item {k}: Scale / Offset must be contiguous with {C} element(s)')
+        if any(t.device != dev for t in (y, r, scale, offset, out)): raise RuntimeError(_KERNEL_FAILURE + f'fq measure: item {k} is on another device')
+        if out.dtype != torch.float64 or out.numel() != rows * 4 or not out.is_contiguous():
+            raise RuntimeError(_KERNEL_FAILURE + f'fq measure: item {k}: Sums must be a contiguous float64 [{rows}, 4]')
+        jobs[k] = (y.data_ptr(), r.data_ptr(), scale.data_ptr(), offset.data_ptr(), out.data_ptr(), rows, count, C, epc,
+                   int(qmin), int(qmax), int(rounding), 0)
+    with _DeviceOf(items[0][0]):
+        _raise(lib.ppqhip_fq_measure_rows_multi(jobs.ctypes.data, len(items), _stream()))
+    return sums
+
+
 # ---- error analysis (include/ppq_hip.h ppqhip_fetch_rows_multi / ppqhip_measure_rows_multi / ppqhip_measure_finish_multi) ----
 _FETCH_JOB = np.dtype([('x', '<u8'), ('index', '<u8'), ('out', '<u8'), ('rows', '<i8'), ('row_len', '<i8'), ('count', '<i8')])
 _MEASURE_JOB = np.dtype([('p', '<u8'), ('r', '<u8'), ('index', '<u8'), ('sums', '<u8'), ('rows', '<i8'), ('row_len', '<i8'),
