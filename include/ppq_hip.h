@@ -602,10 +602,37 @@ typedef struct ppqhip_fq_measure_rows_job {
 } ppqhip_fq_measure_rows_job;
 int ppqhip_fq_measure_rows_multi(const ppqhip_fq_measure_rows_job* jobs, int num_jobs, void* stream);
 
+/* statistical reports (ppq_amd/statistics.py; ADDED under ABI 4 like the entries above) ------------------ */
+/* Both take a HOST array of jobs that is copied into the kernel arguments (chunked when it does not fit one launch): no
+ * upload, no synchronisation, no global atomics, capturable.  A job is one float32 series of n <= 2^31 - 1 elements -- p itself
+ * (r == NULL) or the differences fl32(p[i] - r[i]) -- and its record of 4-byte words in DEVICE memory:
+ *   rec[0] mean  rec[1] std  rec[2] min  rec[3] max  rec[4] skewness  rec[5] kurtosis  rec[6] NOISE:SIGNAL  rec[7] 0
+ *   rec[8 .. 8 + bins): int32 histogram counts                                      (bins <= 64; 0: no histogram)
+ * Two calls give identical bits, whatever the alignment of p and r. */
+typedef struct ppqhip_stat_job {
+    const float* p;
+    const float* r;          /* NULL: the series is p */
+    float* rec;              /* 8 + bins words */
+    int64_t n;
+    int32_t bins, reserved;
+} ppqhip_stat_job;
+/* rec[0..3], rec[6..7].  n, mean and M2 = sum (x - mean)^2 are accumulated in double, two-pass inside a piece of 16384
+ * elements, the pieces merged as (n, mean, M2) triples in a fixed order:
+ *   rec[0] = (float)mean    rec[1] = (float)sqrt(M2 / (n - 1))  (NaN for n = 1, as torch.std)    rec[2], rec[3]: exact
+ * With r: rec[6] = (float)sum (p - r)^2 / ((float)sum r * r + 1e-7f), torch_snr_error(p, r) (measure/norm.py:88-90), each
+ * difference and product ONE fp32 operation, double adds.  Without r: rec[6] = 0. */
+int ppqhip_stat_moments_multi(const ppqhip_stat_job* jobs, int num_jobs, void* stream);
+/* rec[4], rec[5] and the counts, from rec[0..3] as ppqhip_stat_moments_multi wrote them (read on the device).  Every step is
+ * ONE IEEE fp32 operation; the sums are double:
+ *   t = (x - mean) / std;  t2 = t * t;  skewness = (float)(sum t2 * t / n);  kurtosis = (float)(sum t2 * t2 / n) - 3.0f
+ *   std == 0: both NaN (analyse/graphwise.py:287-293 divides by it)
+ *   lo = min, hi = max; lo == hi: lo - 1, hi + 1 (torch.histc);  pos = ((x - lo) * bins) / (hi - lo);  bin = min((int)pos, bins - 1) */
+int ppqhip_stat_shape_multi(const ppqhip_stat_job* jobs, int num_jobs, void* stream);
+
 /* profiling aid used by bench.py: when enabled, every kernel launch made through this library
  * on this thread is bracketed by hipEvents on its own stream; ppqhip_prof_collect() synchronises
  * those events and returns, per kernel id, launches / total ms / total algorithmic bytes. */
-#define PPQHIP_PROF_MAX_KERNELS 32
+#define PPQHIP_PROF_MAX_KERNELS 40
 typedef struct {
     char name[48];
     int64_t launches;

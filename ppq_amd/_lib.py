@@ -105,6 +105,8 @@ PROTOTYPES = {
     'ppqhip_fetch_rows_multi': (c_int, [c_vp, c_int, c_vp]),
     'ppqhip_measure_rows_multi': (c_int, [c_vp, c_int, c_vp]),
     'ppqhip_measure_finish_multi': (c_int, [c_vp, c_int, c_vp]),
+    'ppqhip_stat_moments_multi': (c_int, [c_vp, c_int, c_vp]),
+    'ppqhip_stat_shape_multi': (c_int, [c_vp, c_int, c_vp]),
     'ppqhip_prof_enable': (c_int, [c_int]),
     'ppqhip_prof_collect': (c_int, [ctypes.POINTER(ProfEntry), c_int]),
     'ppqhip_prof_event_overhead_us': (ctypes.c_double, [c_vp, c_int]),

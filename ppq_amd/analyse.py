@@ -12,6 +12,9 @@ against those samples, every analysed output of a forward shares one launch (``c
 accumulated in double, and ONE copy at the very end brings the per-operation results to the host.
 ``fetchs=None`` measures whole tensors instead of samples.  ``use_kernels=False`` runs the reference's procedure itself
 (torch ``index_select``, a copy per operation, the measure on the CPU): the comparison arm, and the path of a CPU executor.
+
+``statistical_analyse``, ``parameter_analyse`` and ``variable_analyse`` live in ``ppq_amd/statistics.py`` and are re-exported at
+the end of this module.
 """
 import math
 from typing import Callable, Dict, Iterable, Iterator, List, Optional, Union
@@ -397,3 +400,8 @@ def layerwise_error_analyse(graph: BaseGraph, dataloader: Iterator, interested_o
     last_analysis_stats.clear(); last_analysis_stats.update(stats)
     if verbose and results: _report(results, method)
     return results
+
+
+# ---- the statistical reports (ppq/quantization/analyse: statistical_analyse, parameter_analyse, variable_analyse) ------------
+from .statistics import (collect_samples, parameter_analyse, series_statistics, statistical_analyse,  # noqa: E402,F401
+                         variable_analyse)

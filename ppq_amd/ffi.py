@@ -572,6 +572,62 @@ def measure_finish_multi(items, method: str, reduce: str = 'mean') -> None:
         _raise(lib.ppqhip_measure_finish_multi(jobs.ctypes.data, len(items), _stream()))
 
 
+# ---- statistical reports (include/ppq_hip.h ppqhip_stat_moments_multi / ppqhip_stat_shape_multi) ----
+_STAT_JOB = np.dtype([('p', '<u8'), ('r', '<u8'), ('rec', '<u8'), ('n', '<i8'), ('bins', '<i4'), ('reserved', '<i4')])
+STAT_WORDS = 8                                     # words of a record in front of its histogram counts
+STAT_MAX_BINS = 64
+
+
+def stat_table(num_series: int, bins: int, device) -> torch.Tensor:
+    """The records of ``num_series`` series: float32 ``[num_series, 8 + bins]``; row k is mean, std, min, max, skewness,
+    kurtosis, NOISE:SIGNAL, 0 and then the ``bins`` histogram counts as int32 bit patterns (``stat_counts`` reads them)."""
+    if not 0 <= bins <= STAT_MAX_BINS: raise RuntimeError(_KERNEL_FAILURE + f'statistics: {bins} bins (at most {STAT_MAX_BINS})')
+    return torch.zeros([num_series, STAT_WORDS + bins], dtype=torch.float32, device=device)
+
+
+def stat_counts(table: torch.Tensor) -> torch.Tensor:
+    """The histogram counts of a record table (device or host copy) as int32 ``[num_series, bins]``."""
+    return table.view(torch.int32)[:, STAT_WORDS:]
+
+
+def _stat_jobs(items, table: torch.Tensor) -> np.ndarray:
+    if table.dtype != torch.float32 or not table.is_cuda or not table.is_contiguous() or table.dim() != 2 \
+            or table.shape[0] != len(items) or not STAT_WORDS <= table.shape[1] <= STAT_WORDS + STAT_MAX_BINS:
+        raise RuntimeError(_KERNEL_FAILURE + f'statistics: Table must be a contiguous float32 [{len(items)}, 8 + bins] tensor on the GPU')
+    jobs = np.zeros(len(items), dtype=_STAT_JOB)
+    words = table.shape[1]
+    for k, (p, r) in enumerate(items):
+        _f32(p, 'Series')
+        if not p.is_contiguous(): raise RuntimeError(_KERNEL_FAILURE + f'statistics: item {k}: Series is not contiguous')
+        if p.device != table.device: raise RuntimeError(_KERNEL_FAILURE + f'statistics: item {k} is on another device')
+        if r is not None:
+            _f32(r, 'Real')
+            if not r.is_contiguous() or r.numel() != p.numel() or r.device != table.device:
+                raise RuntimeError(_KERNEL_FAILURE + f'statistics: item {k}: Real must be contiguous, on the same device and as long as Series')
+        jobs[k] = (p.data_ptr(), 0 if r is None else r.data_ptr(), table.data_ptr() + 4 * words * k, p.numel(), words - STAT_WORDS, 0)
+    return jobs
+
+
+def stat_moments_multi(items, table: torch.Tensor) -> torch.Tensor:
+    """Mean, std (n - 1), min, max of every ``(p, r)`` series in ONE call -- ``r`` None: the series is ``p``, otherwise
+    ``p - r`` and the record also gets ``torch_snr_error(p, r)`` -- into words 0..3 and 6 of row k of ``table`` (``stat_table``)."""
+    if not items: return table
+    jobs = _stat_jobs(items, table)
+    with _DeviceOf(table):
+        _raise(lib.ppqhip_stat_moments_multi(jobs.ctypes.data, len(items), _stream()))
+    return table
+
+
+def stat_shape_multi(items, table: torch.Tensor) -> torch.Tensor:
+    """Skewness, kurtosis and the ``table.shape[1] - 8``-bin histogram of every series from the mean, std, min and max that
+    ``stat_moments_multi`` left in ``table`` (read on the device), into words 4, 5 and 8.. of its row.  ONE call."""
+    if not items: return table
+    jobs = _stat_jobs(items, table)
+    with _DeviceOf(table):
+        _raise(lib.ppqhip_stat_shape_multi(jobs.ctypes.data, len(items), _stream()))
+    return table
+
+
 class LinearQuantizePlan:
     """Fake-quantise MANY tensors with ONE launch per call (``ppqhip_fq_linear_multi``): the weights of
     a graph, which the executor quantises again on every forward.  Built once from
