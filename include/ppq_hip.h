@@ -548,6 +548,40 @@ typedef struct ppqhip_equalize_apply_job {
 } ppqhip_equalize_apply_job;
 int ppqhip_equalize_apply_multi(const ppqhip_equalize_apply_job* jobs, int num_jobs, void* stream);
 
+/* channelwise split (ppq_amd/channel_split.py; ADDED under ABI 4 like the entries above) -------------- */
+/* Both take a HOST array of jobs that is copied into the kernel arguments (chunked when it does not fit one launch): no
+ * upload, no synchronisation, no atomics.  Every extent is checked on the host before anything is launched. */
+/* The split plan of one pair, EqualizationPair.channel_split (ppq/quantization/algorithm/equalization.py:361-393) up to its mask:
+ *   up / down = max |x * m| over the upstream / downstream segments, as in ppqhip_equalize_scale_job: a NaN wins
+ *   split[c] = up >= value_threshold && down >= value_threshold                    (a NaN key never splits)
+ *   d[c] = exclusive prefix sum of 1 + split[c];   src_of[d[c]] = c;   where split[c]: src_of[d[c] + 1] = c, bit 31 set on both
+ *   *count = the new channel count.  Entries of src_of at or beyond *count are unspecified.
+ * The src_of and count of the jobs of ONE call must overlap neither each other nor a segment's tensor (checked). */
+typedef struct ppqhip_split_plan_job {
+    const ppqhip_equalize_segment* segments;   /* HOST array; at least one upstream and one downstream segment */
+    int32_t* src_of;                           /* 2 x num_channel int32 (overwritten) */
+    int32_t* count;                            /* one int32 (overwritten) */
+    int32_t num_segments, num_channel;
+    float value_threshold;
+    int32_t reserved;
+} ppqhip_split_plan_job;
+int ppqhip_split_plan_multi(const ppqhip_split_plan_job* jobs, int num_jobs, void* stream);
+/* ChannelSplitHelper.split_by_mask (:203-220) of one dense tensor viewed as [outer, num_channel, run], OUT OF PLACE into
+ * [outer, count, run] (outer = n / (num_channel * run)):
+ *   out[o, d, e] = x[o, src_of[d] & 0x7fffffff, e]      times 0.70710677f -- ONE fp32 multiply -- when bit 31 of src_of[d] is set
+ * upstream Conv weight / bias: outer = 1; upstream Gemm weight stored [I, O]: outer = I, run = 1; downstream Conv [O, C, k...]:
+ * outer = O, run = prod(k); downstream Gemm [O, I]: outer = O, run = 1; downstream Gemm [I, O]: outer = 1, run = O.
+ * `count` is what the plan wrote, read back by the host: num_channel <= count <= 2 * num_channel.  No output may overlap an
+ * input (x, src_of) or another output of the same call. */
+typedef struct ppqhip_split_apply_job {
+    const float* x;
+    float* out;              /* n / num_channel * count floats */
+    const int32_t* src_of;   /* count entries are read */
+    int64_t n, run;          /* n: floats of x */
+    int32_t num_channel, count;
+} ppqhip_split_apply_job;
+int ppqhip_split_apply_multi(const ppqhip_split_apply_job* jobs, int num_jobs, void* stream);
+
 /* SSD equalization (ppq_amd/ssd.py; ADDED under ABI 4 like the entries above) ------------------------- */
 /* All three take a HOST array of jobs that is copied into the kernel arguments (chunked when it does not fit one launch): no
  * upload, no synchronisation, no atomics, capturable.  Every extent is checked on the host before anything is launched. */

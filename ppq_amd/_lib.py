@@ -99,6 +99,8 @@ PROTOTYPES = {
     'ppqhip_roundtune_fwd_multi': (c_int, [c_vp, c_int, c_vp]),
     'ppqhip_equalize_scale_multi': (c_int, [c_vp, c_int, c_vp]),
     'ppqhip_equalize_apply_multi': (c_int, [c_vp, c_int, c_vp]),
+    'ppqhip_split_plan_multi': (c_int, [c_vp, c_int, c_vp]),
+    'ppqhip_split_apply_multi': (c_int, [c_vp, c_int, c_vp]),
     'ppqhip_ssd_scales_multi': (c_int, [c_vp, c_int, c_vp]),
     'ppqhip_ssd_apply_multi': (c_int, [c_vp, c_int, c_vp]),
     'ppqhip_fq_measure_rows_multi': (c_int, [c_vp, c_int, c_vp]),

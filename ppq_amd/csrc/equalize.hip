@@ -18,21 +18,13 @@
 #include <vector>
 
 #include "common.hpp"
+#include "equalize_key.hpp"
 
 namespace ppqhip {
 namespace {
 
 // ------------------------------------------------------------------------------------ scale
 constexpr int kEqMaxJobs = 32;                     // pairs per launch
-constexpr int kEqMaxSegs = 72;                     // segments per launch (a ResNet stage pair with bias and activations has ~30)
-
-struct EqSeg {                                     // 40 B
-    const float* base;
-    uint32_t div, a, b;                            // offset of channel c: (c / div) * a + (c % div) * b
-    uint32_t outer, stride, run;
-    float mult;
-    uint32_t flags;                                // bit 0: downstream key; bit 1: 16-B loads (base, a, b, stride, run all 4-aligned)
-};
 struct EqScaleJob {                                // 24 B
     float* scale;
     uint32_t C;
@@ -62,47 +54,9 @@ __global__ __launch_bounds__(kBlock) void equalize_scale_kernel(const EqScaleArg
     lo = __builtin_amdgcn_readfirstlane(lo);
     const EqScaleJob& j = args.jobs[lo];
     const uint32_t c = blockIdx.x - args.first_block[lo];
-    float key[2] = {0.f, 0.f}, bad[2] = {0.f, 0.f};                       // [0] upstream, [1] downstream; |x| >= 0, so 0 is neutral
-    for (uint32_t k = 0; k < j.seg_count; k++) {
-        const EqSeg& g = args.segs[j.seg_begin + k];
-        const uint32_t q = c / g.div;
-        const float* p = g.base + (size_t)q * g.a + (size_t)(c - q * g.div) * g.b;
-        const float mult = g.mult;
-        float m = 0.f, nan = 0.f;
-        auto fold = [&](float x) {
-            const float t = __builtin_fabsf(x * mult);
-            m = fmaxf(m, t);                                               // drops a NaN operand: tracked on its own
-            nan = (t != t) ? 1.f : nan;
-        };
-        if (g.flags & 2u) {
-            const uint32_t run4 = g.run >> 2, total = g.outer * run4;
-            for (uint32_t i = threadIdx.x; i < total; i += kBlock) {
-                const uint32_t o = (g.outer == 1) ? 0u : i / run4, e = i - o * run4;
-                const float4 v = reinterpret_cast<const float4*>(p + (size_t)o * g.stride)[e];
-                fold(v.x); fold(v.y); fold(v.z); fold(v.w);
-            }
-        } else {
-            const uint32_t total = g.outer * g.run;
-            for (uint32_t i = threadIdx.x; i < total; i += kBlock) {
-                const uint32_t o = (g.outer == 1) ? 0u : (g.run == 1 ? i : i / g.run), e = i - o * g.run;
-                fold(p[(size_t)o * g.stride + e]);
-            }
-        }
-        const uint32_t side = g.flags & 1u;                                // wave-uniform
-        key[side] = fmaxf(key[side], m);
-        bad[side] = fmaxf(bad[side], nan);
-    }
-    float up = wave_max(key[0]), dn = wave_max(key[1]), up_nan = wave_max(bad[0]), dn_nan = wave_max(bad[1]);
-    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) { lds[4 * wid] = up; lds[4 * wid + 1] = dn; lds[4 * wid + 2] = up_nan; lds[4 * wid + 3] = dn_nan; }
-    __syncthreads();
+    float up, dn;
+    eq_channel_keys(args.segs + j.seg_begin, j.seg_count, c, lds, up, dn);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < kBlock / kWave; w++) {
-            up = fmaxf(up, lds[4 * w]); dn = fmaxf(dn, lds[4 * w + 1]);
-            up_nan = fmaxf(up_nan, lds[4 * w + 2]); dn_nan = fmaxf(dn_nan, lds[4 * w + 3]);
-        }
-        if (up_nan > 0.f) up = __builtin_nanf("");
-        if (dn_nan > 0.f) dn = __builtin_nanf("");
         const float q = up / dn;
         const float r = __builtin_sqrtf(q);
         float s = 1.0f / r;
@@ -166,8 +120,6 @@ __global__ __launch_bounds__(kBlock) void equalize_apply_kernel(const EqApArgs a
     }
 }
 
-constexpr int64_t kEqMax = 0x7fffffffLL;
-
 int validate_scale(const ppqhip_equalize_scale_job* jobs, int num_jobs) {
     const char* what = "equalize_scale_multi";
     if (num_jobs < 0 || (num_jobs > 0 && jobs == nullptr)) { set_error("%s: bad job table", what); return PPQHIP_ERR_INVALID_VALUE; }
@@ -176,27 +128,7 @@ int validate_scale(const ppqhip_equalize_scale_job* jobs, int num_jobs) {
         if (j.segments == nullptr || j.scale == nullptr || j.num_channel <= 0 || j.num_segments <= 0) {
             set_error("%s: job %d: null pointer, no channel or no segment", what, k); return PPQHIP_ERR_INVALID_VALUE;
         }
-        if (j.num_segments > kEqMaxSegs) {
-            set_error("%s: job %d: %d segments, at most %d fit one launch", what, k, j.num_segments, kEqMaxSegs);
-            return PPQHIP_ERR_UNSUPPORTED;
-        }
-        bool has_up = false, has_down = false;
-        for (int t = 0; t < j.num_segments; t++) {
-            const ppqhip_equalize_segment& g = j.segments[t];
-            if (g.base == nullptr || g.div < 1 || g.a < 0 || g.b < 0 || g.outer < 1 || g.run < 1 || g.stride < 0 || g.extent < 1 ||
-                g.extent > kEqMax || g.div > kEqMax || g.a > kEqMax || g.b > kEqMax || g.outer > kEqMax || g.run > kEqMax ||
-                g.stride > kEqMax || g.outer * g.run > kEqMax) {
-                set_error("%s: job %d segment %d: bad geometry", what, k, t); return PPQHIP_ERR_INVALID_VALUE;
-            }
-            const int64_t C = j.num_channel;
-            const int64_t last = ((C - 1) / g.div) * g.a + (std::min<int64_t>(g.div, C) - 1) * g.b + (g.outer - 1) * g.stride + g.run - 1;
-            if (last >= g.extent) {
-                set_error("%s: job %d segment %d: reads element %lld of a tensor of %lld", what, k, t, (long long)last, (long long)g.extent);
-                return PPQHIP_ERR_INVALID_VALUE;
-            }
-            (g.downstream ? has_down : has_up) = true;
-        }
-        if (!has_up || !has_down) { set_error("%s: job %d needs an upstream and a downstream segment", what, k); return PPQHIP_ERR_INVALID_VALUE; }
+        if (int st = validate_segments(what, k, j.segments, j.num_segments, j.num_channel)) return st;
     }
     return PPQHIP_OK;
 }
@@ -211,14 +143,7 @@ void launch_scale(const ppqhip_equalize_scale_job* jobs, int num_jobs, hipStream
             EqScaleJob& d = args.jobs[count];
             d.scale = src.scale; d.C = (uint32_t)src.num_channel; d.threshold = src.value_threshold;
             d.seg_begin = segs; d.seg_count = (uint32_t)src.num_segments;
-            for (int t = 0; t < src.num_segments; t++) {
-                const ppqhip_equalize_segment& g = src.segments[t];
-                EqSeg& e = args.segs[segs++];
-                e.base = g.base; e.div = (uint32_t)g.div; e.a = (uint32_t)g.a; e.b = (uint32_t)g.b;
-                e.outer = (uint32_t)g.outer; e.stride = (uint32_t)g.stride; e.run = (uint32_t)g.run; e.mult = g.multiplier;
-                const bool vec = aligned16(g.base) && g.run % 4 == 0 && g.a % 4 == 0 && g.b % 4 == 0 && g.stride % 4 == 0;
-                e.flags = (g.downstream ? 1u : 0u) | (vec ? 2u : 0u);
-            }
+            for (int t = 0; t < src.num_segments; t++) args.segs[segs++] = pack_segment(src.segments[t]);
             args.first_block[count] = blocks;
             blocks += d.C;
             count++;

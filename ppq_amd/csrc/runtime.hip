@@ -32,7 +32,8 @@ const char* const kKernelNames[K_NUM] = {
     "fq_float_bwd", "hist_sym_t", "hist_asym_t", "hist_sym_c", "quantile_t", "isotone_t", "minmax_t",
     "minmax_c", "mse_search", "kl_losses", "tensor_clip", "rounding_loss", "channel_sum", "float_scale_search", "lsq_finish",
     "adaround_fwd", "adaround_bwd", "fetch_rows", "measure_rows", "measure_finish", "roundtune_fwd", "equalize_scale",
-    "equalize_apply", "ssd_scales", "ssd_apply", "fq_measure_rows", "stat_moments", "stat_shape"};
+    "equalize_apply", "ssd_scales", "ssd_apply", "fq_measure_rows", "stat_moments", "stat_shape",
+    "split_plan", "split_apply"};
 
 int num_cu() {
     static std::mutex mu;

@@ -233,9 +233,10 @@ def _weight(op) -> torch.Tensor:
 
 
 def pair_jobs(pair: EqualizationPair, scale: torch.Tensor, value_threshold: float, including_bias: bool, including_act: bool,
-              bias_multiplier: float, act_multiplier: float, activations: Dict[str, torch.Tensor]):
-    """(scale item, apply items) of one pair for ``ffi.equalize_scale_table`` / ``ffi.equalize_apply_table``."""
-    C = scale.numel()
+              bias_multiplier: float, act_multiplier: float, activations: Dict[str, torch.Tensor], num_channel: int = None):
+    """(scale item, apply items) of one pair for ``ffi.equalize_scale_table`` / ``ffi.equalize_apply_table``.  ``num_channel``:
+    the pair's channel count where no ``scale`` is there to tell it (channel_split.py wants the key segments alone)."""
+    C = scale.numel() if num_channel is None else int(num_channel)
     segments, applies = [], []
 
     def need(count, op):

@@ -408,6 +408,87 @@ def equalize_apply_multi(items) -> None:
     (items if isinstance(items, EqualizeTable) else equalize_apply_table(items)).run()
 
 
+# ---- channelwise split (include/ppq_hip.h ppqhip_split_plan_multi / ppqhip_split_apply_multi) --------------------------------
+_SPLIT_PLAN_JOB = np.dtype([('segments', '<u8'), ('src_of', '<u8'), ('count', '<u8'), ('num_segments', '<i4'), ('num_channel', '<i4'),
+                            ('value_threshold', '<f4'), ('reserved', '<i4')])
+_SPLIT_APPLY_JOB = np.dtype([('x', '<u8'), ('out', '<u8'), ('src_of', '<u8'), ('n', '<i8'), ('run', '<i8'), ('num_channel', '<i4'),
+                             ('count', '<i4')])
+SPLIT_MAX_JOBS, SPLIT_MAX_SEGMENTS = 32, 72        # what one launch holds (csrc/split.hip kSpMaxJobs / kSpApMaxJobs, kEqMaxSegs)
+SPLIT_BIT = -0x80000000                            # bit 31 of an int32 plan entry: the channel is one half of a split
+
+
+def _i32(t, what: str, k: int, dev, numel: int):
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == numel):
+        raise RuntimeError(_KERNEL_FAILURE + f'Channel split: item {k}: {what} must be a contiguous int32 tensor of {numel}')
+    if not t.is_cuda: raise RuntimeError(_KERNEL_FAILURE + f'Channel split: item {k}: {what} is not on the GPU')
+    if t.device != dev: raise RuntimeError(_KERNEL_FAILURE + f'Channel split: item {k}: {what} is on another device')
+
+
+def split_plan_table(items) -> EqualizeTable:
+    """items[k] = (src_of, count, value_threshold, segments): ``src_of`` a contiguous int32[2 C] CUDA tensor that receives the
+    pair's plan, ``count`` an int32[1] tensor (a view into one buffer per level: one copy reads them all) that receives the new
+    channel count; segments as in :func:`equalize_scale_table`."""
+    jobs = np.zeros(len(items), dtype=_SPLIT_PLAN_JOB)
+    segs = np.zeros(sum(len(it[3]) for it in items), dtype=_EQ_SEGMENT)
+    keep, at = [], 0
+    dev = items[0][0].device if items else None
+    for k, (src_of, count, threshold, segments) in enumerate(items):
+        if src_of.numel() % 2: raise RuntimeError(_KERNEL_FAILURE + f'Channel split: item {k}: SrcOf must hold 2 x C entries')
+        _i32(src_of, 'SrcOf', k, dev, src_of.numel()); _i32(count, 'Count', k, dev, 1)
+        keep += [src_of, count]
+        jobs[k] = (segs.ctypes.data + at * _EQ_SEGMENT.itemsize, src_of.data_ptr(), count.data_ptr(), len(segments), src_of.numel() // 2,
+                   float(threshold), 0)
+        for t, div, a, b, outer, stride, run, mult, down in segments:
+            _eq_tensor(t, 'Value', k, dev)
+            keep.append(t)
+            segs[at] = (t.data_ptr(), t.numel(), int(div), int(a), int(b), int(outer), int(stride), int(run), float(mult), 1 if down else 0)
+            at += 1
+    return EqualizeTable(jobs, segs, keep, lib.ppqhip_split_plan_multi)
+
+
+def split_apply_table(items) -> EqualizeTable:
+    """items[k] = (x, out, src_of, num_channel, count, run): ``x`` viewed as [outer, num_channel, run] is gathered into ``out``
+    [outer, count, run] as ``ppqhip_split_apply_job`` describes; ``count`` is the host's copy of what the plan wrote."""
+    jobs = np.zeros(len(items), dtype=_SPLIT_APPLY_JOB)
+    keep = []
+    dev = items[0][0].device if items else None
+    for k, (x, out, src_of, C, count, run) in enumerate(items):
+        _eq_tensor(x, 'Value', k, dev); _eq_tensor(out, 'Out', k, dev)
+        _i32(src_of, 'SrcOf', k, dev, src_of.numel())
+        C, count, run = int(C), int(count), int(run)
+        if C > 0 and run > 0 and x.numel() % (C * run) == 0 and C <= count <= 2 * C:       # else the library says what is wrong
+            if out.numel() != x.numel() // C * count or src_of.numel() < count:
+                raise RuntimeError(_KERNEL_FAILURE + f'Channel split: item {k}: Out must hold {x.numel() // C * count} floats and SrcOf {count} entries')
+        keep += [x, out, src_of]
+        jobs[k] = (x.data_ptr(), out.data_ptr(), src_of.data_ptr(), x.numel(), run, C, count)
+    return EqualizeTable(jobs, None, keep, lib.ppqhip_split_apply_multi)
+
+
+def split_plan_launches(items) -> int:
+    """Kernel launches of :func:`split_plan_multi` on these items: two (mask, scan) per chunk of at most 32 jobs / 72 segments."""
+    chunks = jobs = segs = 0
+    for it in items:
+        n = len(it[3])
+        if jobs == 0 or jobs == SPLIT_MAX_JOBS or segs + n > SPLIT_MAX_SEGMENTS: chunks, jobs, segs = chunks + 1, 0, 0
+        jobs, segs = jobs + 1, segs + n
+    return 2 * chunks
+
+
+def split_apply_launches(items) -> int:
+    return (len(items) + SPLIT_MAX_JOBS - 1) // SPLIT_MAX_JOBS
+
+
+def split_plan_multi(items) -> None:
+    """The split plan of EqualizationPair.channel_split (ppq/quantization/algorithm/equalization.py:361-393) for every item (an
+    :class:`EqualizeTable` or the items of :func:`split_plan_table`): keys and mask in one launch, the scan in another."""
+    (items if isinstance(items, EqualizeTable) else split_plan_table(items)).run()
+
+
+def split_apply_multi(items) -> None:
+    """ChannelSplitHelper.split_by_mask (:203-220) for every item in ONE launch, out of place."""
+    (items if isinstance(items, EqualizeTable) else split_apply_table(items)).run()
+
+
 # ---- SSD equalization (include/ppq_hip.h ppqhip_ssd_scales_multi / ppqhip_ssd_apply_multi / ppqhip_fq_measure_rows_multi) ----
 _SSD_SCALES_JOB = np.dtype([('first', _EQ_SEGMENT), ('last', _EQ_SEGMENT), ('act_range', '<u8'), ('scales', '<u8'), ('ranges', '<u8'),
                             ('num_channel', '<i4'), ('channel_ratio', '<f4')])
