@@ -22,9 +22,9 @@ from typing import Callable, Dict, Iterable, List, Sequence, Union
 
 import torch
 
-from .calibration import QuantizationOptimizationPass
 from .equalization import (_LINEAR_TYPES, EqualizationPair, LayerwiseEqualizationPass, _check_endpoint, _has_bias, _trans_b,
-                           build_schedule, key_value_from_downstream, key_value_from_upstream, pair_jobs, reduce_by_axis)
+                           build_schedule, channel_axis, key_value_from_downstream, key_value_from_upstream, pair_jobs,
+                           parameters_on_device, reduce_by_axis)
 
 SPLIT_FACTOR = 1 / sqrt(2)              # channel_split hands this Python float to torch: float32 0.70710677 on a float32 tensor
 
@@ -112,10 +112,9 @@ def split_tensors(pair: EqualizationPair) -> List[tuple]:
     """(variable, channel axis) of every tensor a split of this (ungrouped) pair replaces."""
     out = []
     for op in pair.upstream_layers:
-        out.append((op.inputs[1], 1 if (op.type in _LINEAR_TYPES and _trans_b(op) == 0) else 0))
+        out.append((op.inputs[1], channel_axis(op, False)))
         if _has_bias(op): out.append((op.inputs[-1], 0))
-    for op in pair.downstream_layers:
-        out.append((op.inputs[1], (1 if _trans_b(op) != 0 else 0) if op.type in _LINEAR_TYPES else 1))
+    for op in pair.downstream_layers: out.append((op.inputs[1], channel_axis(op, True)))
     return out
 
 
@@ -138,27 +137,17 @@ class ChannelwiseSplitPass(LayerwiseEqualizationPass):
     arm's ``tolist()`` per tensor are not counted), ``channels_before`` / ``channels_after`` (summed over the pairs),
     ``split_channels`` (one entry per iteration) and ``collect_launches``.  ``keep_masks = True`` keeps every mask in
     ``masks[(iteration, pair index)]`` (an inspection aid)."""
+    PASS_NAME = 'PPQ Channelwise Split Pass'
+
     def __init__(self, iterations: int, threshold: float = 2, including_bias: bool = False, bias_multiplier: float = 0.5,
                  including_act: bool = False, act_multiplier: float = 0.5, interested_layers: List[str] = None,
                  optimize_level: int = 2, verbose: bool = False, use_kernels: bool = True, schedule: str = 'levelled') -> None:
-        if schedule not in {'levelled', 'sequential'}: raise ValueError(f'schedule is levelled or sequential, {schedule} was given.')
-        self.optimize_level = optimize_level
-        self.iterations = iterations
-        self.value_threshold = threshold
-        self.including_bias = including_bias
-        self.bias_multiplier = bias_multiplier
-        self.including_act = including_act
-        self.act_multiplier = act_multiplier
-        self.interested_layers = interested_layers
-        self.verbose = verbose
-        self.use_kernels = use_kernels
-        self.schedule = schedule
+        super().__init__(iterations=iterations, value_threshold=threshold, including_bias=including_bias, bias_multiplier=bias_multiplier,
+                         including_act=including_act, act_multiplier=act_multiplier, interested_layers=interested_layers,
+                         optimize_level=optimize_level, verbose=verbose, use_kernels=use_kernels, schedule=schedule)
         self.keep_masks = False
-        self.masks: Dict[tuple, torch.Tensor] = {}
-        self.pairs: List[EqualizationPair] = []
-        self.activations: Dict[str, torch.Tensor] = {}      # the LAST iteration's maxima, owned by the pass
+        self.masks: Dict[tuple, torch.Tensor] = {}          # ``activations`` holds the LAST iteration's maxima here
         self.stats: Dict[str, object] = {}
-        QuantizationOptimizationPass.__init__(self, name='PPQ Channelwise Split Pass')
 
     def optimize(self, graph, dataloader: Iterable = None, executor=None, collate_fn: Callable = None,
                  activations: Union[Dict[str, torch.Tensor], Sequence[Dict[str, torch.Tensor]]] = None, **kwargs) -> None:
@@ -170,9 +159,7 @@ class ChannelwiseSplitPass(LayerwiseEqualizationPass):
         for p in active:
             for op in pairs[p].operations: _check_endpoint(op)
         params = [v.value for p in active for op in pairs[p].operations for v in op.inputs[1:] if v.is_parameter]
-        on_device = self.use_kernels and bool(params) and all(isinstance(t, torch.Tensor) and t.is_cuda for t in params)
-        if self.use_kernels and not on_device and any(isinstance(t, torch.Tensor) and t.is_cuda for t in params):
-            raise TypeError('ChannelwiseSplitPass: the parameters of the pairs are partly on the GPU and partly not')
+        on_device = parameters_on_device(params, self.use_kernels, 'ChannelwiseSplitPass')
         if isinstance(activations, dict): activations = [activations]
         if self.including_act and activations is not None and len(activations) < self.iterations:
             raise ValueError(f'ChannelwiseSplitPass: {self.iterations} iterations need as many activation records, {len(activations)} given')

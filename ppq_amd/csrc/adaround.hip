@@ -14,11 +14,11 @@
 //   r = -k;  x = |h - 0.5| * 2;  r = r * (beta * pow(x, beta - 1));  r = r * 2;  r = r * sgn(h - 0.5);  mask on a;  r = r * 1.2f;
 //   r = (r * (1 - sg)) * sg;  dv = dv + r
 //
-// Jobs: the table travels in the kernel arguments (<= kArMaxJobs per launch, more are chunked): no upload, capturable into a HIP
-// graph.  channel(i) = (i / elem_per_channel) % num_channel with FastDiv (a per-tensor job has num_channel = 1).  16-B loads and
+// Job table: DESIGN.md, "Job tables" (capturable into a HIP graph).  channel(i) = (i / elem_per_channel) % num_channel with FastDiv (a per-tensor job has num_channel = 1).  16-B loads and
 // stores where every pointer of the job is aligned, the n % 4 tail by the job's first workgroup; element-wise otherwise.  No
 // atomics, no reductions.
 #include "common.hpp"
+#include "job_table.hpp"
 
 namespace ppqhip {
 namespace {
@@ -46,10 +46,6 @@ struct ArArgs {
     const float* reg;                              // backward: {k, beta, beta - 1}
 };
 static_assert(sizeof(ArArgs) <= 4096, "kernel arguments are limited to 4 KB");
-
-__device__ __forceinline__ float clamp_nan(float v, float lo, float hi) {       // torch's clamp: NaN passes through
-    return __builtin_isnan(v) ? v : __builtin_fminf(__builtin_fmaxf(v, lo), hi);
-}
 
 __device__ __forceinline__ uint32_t ar_channel(uint32_t i, const FastDiv& epc, const FastDiv& nc) {
     const uint32_t row = fdiv(i, epc);
@@ -99,16 +95,6 @@ __device__ __forceinline__ float ar_backward(float w, float v, float s, float o,
         dv = dv + r;
     }
     return dv;
-}
-
-__device__ __forceinline__ uint32_t ar_job_of(const ArArgs& args, uint32_t& local) {
-    uint32_t lo = 0, hi = args.count;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (args.first_block[mid] <= blockIdx.x) lo = mid; else hi = mid;
-    }
-    local = blockIdx.x - args.first_block[lo];
-    return lo;
 }
 
 template <bool BWD, bool REG>
@@ -167,14 +153,13 @@ __device__ __forceinline__ void ar_job(const ArJob& j, uint32_t local, float k, 
 
 __global__ __launch_bounds__(kBlock) void adaround_fwd_kernel(const ArArgs args) {
     uint32_t local;
-    const uint32_t jk = ar_job_of(args, local);
-    ar_job<false, false>(args.jobs[__builtin_amdgcn_readfirstlane(jk)], local, 0.f, 0.f, 0.f);
+    const uint32_t jk = job_of(args, local);
+    ar_job<false, false>(args.jobs[jk], local, 0.f, 0.f, 0.f);
 }
 
 __global__ __launch_bounds__(kBlock) void adaround_bwd_kernel(const ArArgs args) {
     uint32_t local;
-    const uint32_t jk = ar_job_of(args, local);
-    const ArJob& j = args.jobs[__builtin_amdgcn_readfirstlane(jk)];
+    const ArJob& j = args.jobs[job_of(args, local)];
     // every lane reads the same three floats: the branch on k is wave-uniform
     const float k = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, args.reg[0])));
     if (k == 0.0f) { ar_job<true, false>(j, local, 0.f, 0.f, 0.f); return; }
@@ -182,7 +167,7 @@ __global__ __launch_bounds__(kBlock) void adaround_bwd_kernel(const ArArgs args)
 }
 
 int validate_jobs(const ppqhip_adaround_job* jobs, int num_jobs, bool bwd, const char* what) {
-    if (num_jobs < 0 || (num_jobs > 0 && jobs == nullptr)) { set_error("%s: bad job table", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (int st = check_job_table(what, jobs, num_jobs)) return st;
     for (int k = 0; k < num_jobs; k++) {
         const ppqhip_adaround_job& j = jobs[k];
         if (j.n <= 0 || j.n > 0x7fffffffLL) {
@@ -225,8 +210,7 @@ int launch_adaround(const ppqhip_adaround_job* jobs, int num_jobs, bool bwd, con
             args.first_block[k] = blocks;
             blocks += d.blocks;
         }
-        for (int k = count; k < kArMaxJobs; k++) { args.jobs[k] = args.jobs[0]; args.first_block[k] = blocks; }
-        args.count = (uint32_t)count;
+        pad_job_table(args, (uint32_t)count, blocks);
         args.reg = reg;
         if (bwd) hipLaunchKernelGGL(adaround_bwd_kernel, dim3(blocks), dim3(kBlock), 0, s, args);
         else hipLaunchKernelGGL(adaround_fwd_kernel, dim3(blocks), dim3(kBlock), 0, s, args);

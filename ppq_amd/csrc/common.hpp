@@ -105,6 +105,9 @@ __device__ __forceinline__ int d2i_sat(double v) {
 __device__ __forceinline__ int add_sat(int a, int b) { return __builtin_elementwise_add_sat(a, b); }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v > hi ? hi : (v < lo ? lo : v); }
+__device__ __forceinline__ float clamp_nan(float v, float lo, float hi) {       // torch's clamp: NaN passes through
+    return __builtin_isnan(v) ? v : __builtin_fminf(__builtin_fmaxf(v, lo), hi);
+}
 
 // _round2int, common.cuh:88-114.  HALF_UP / HALF_DOWN evaluate `value + .5` in double exactly as
 // the reference does (the literal .5 is a double there).

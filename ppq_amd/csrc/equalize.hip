@@ -12,13 +12,11 @@
 // the scale in (group, cin_local) order, so the slice a channel READS for its key is not the slice its scale is APPLIED to -- a
 // fused reduce-and-apply workgroup would race with its neighbours.
 //
-// Jobs and segments travel in the kernel arguments (chunked when they do not fit): no upload.  No atomics; the reductions are the
-// wave64 shuffle + LDS pattern of reduce.hip.
-#include <algorithm>
-#include <vector>
-
+// Job tables: DESIGN.md, "Job tables".  No atomics; the reductions are the wave64 shuffle + LDS pattern of reduce.hip.
+#include "channel_scale.hpp"
 #include "common.hpp"
 #include "equalize_key.hpp"
+#include "job_table.hpp"
 
 namespace ppqhip {
 namespace {
@@ -39,28 +37,18 @@ struct EqScaleArgs {
 };
 static_assert(sizeof(EqScaleArgs) <= 4096, "kernel arguments are limited to 4 KB");
 
-__device__ __forceinline__ float eq_clamp_nan(float v, float lo, float hi) {    // torch's clamp: NaN passes through
-    return __builtin_isnan(v) ? v : __builtin_fminf(__builtin_fmaxf(v, lo), hi);
-}
-
 // one workgroup per (job, channel): lanes stride over the channel's elements of every segment
 __global__ __launch_bounds__(kBlock) void equalize_scale_kernel(const EqScaleArgs args) {
     __shared__ float lds[4 * (kBlock / kWave)];
-    uint32_t lo = 0, hi = args.count;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (args.first_block[mid] <= blockIdx.x) lo = mid; else hi = mid;
-    }
-    lo = __builtin_amdgcn_readfirstlane(lo);
-    const EqScaleJob& j = args.jobs[lo];
-    const uint32_t c = blockIdx.x - args.first_block[lo];
+    uint32_t c;
+    const EqScaleJob& j = args.jobs[job_of(args, c)];
     float up, dn;
     eq_channel_keys(args.segs + j.seg_begin, j.seg_count, c, lds, up, dn);
     if (threadIdx.x == 0) {
         const float q = up / dn;
         const float r = __builtin_sqrtf(q);
         float s = 1.0f / r;
-        s = eq_clamp_nan(s, 0.1f, 10.0f);
+        s = clamp_nan(s, 0.1f, 10.0f);
         if (up + dn < j.threshold) s = 1.0f;
         j.scale[c] = s;
     }
@@ -68,14 +56,10 @@ __global__ __launch_bounds__(kBlock) void equalize_scale_kernel(const EqScaleArg
 
 // ------------------------------------------------------------------------------------ apply
 constexpr int kEqApMaxJobs = 32;
-constexpr uint32_t kEqApMaxBlocksPerJob = 1024;    // grid-strided beyond
-
-struct EqApJob {                                   // 80 B
+struct EqApJob {                                   // 72 B
     float* x;
     const float* scale;
-    uint32_t n, nvec;                              // nvec: float4 count (0: 4-B accesses); then `run` holds run / 4
-    FastDiv run, inner, og;
-    uint32_t grouped, divide, blocks, pad;
+    ChannelScaleMap g;
 };
 struct EqApArgs {
     EqApJob jobs[kEqApMaxJobs];
@@ -84,37 +68,25 @@ struct EqApArgs {
 };
 static_assert(sizeof(EqApArgs) <= 4096, "kernel arguments are limited to 4 KB");
 
-__device__ __forceinline__ uint32_t eq_scale_index(const EqApJob& j, uint32_t unit) {       // unit: element (or float4) index
-    const uint32_t row = fdiv(unit, j.run);
-    const uint32_t o = fdiv(row, j.inner);
-    uint32_t k = row - o * j.inner.d;
-    if (j.grouped) k += fdiv(o, j.og) * j.inner.d;
-    return k;
-}
-
 __global__ __launch_bounds__(kBlock) void equalize_apply_kernel(const EqApArgs args) {
-    uint32_t lo = 0, hi = args.count;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (args.first_block[mid] <= blockIdx.x) lo = mid; else hi = mid;
-    }
-    lo = __builtin_amdgcn_readfirstlane(lo);
-    const EqApJob& j = args.jobs[lo];
-    const uint32_t stride = j.blocks * kBlock;
-    const uint32_t first = (blockIdx.x - args.first_block[lo]) * kBlock + threadIdx.x;
-    if (j.nvec == 0) {                                                    // unaligned pointer or run % 4 != 0
-        for (uint32_t i = first; i < j.n; i += stride) {
-            const float s = j.scale[eq_scale_index(j, i)];
+    uint32_t local;
+    const EqApJob& j = args.jobs[job_of(args, local)];
+    const ChannelScaleMap& g = j.g;
+    const uint32_t stride = g.blocks * kBlock;
+    const uint32_t first = local * kBlock + threadIdx.x;
+    if (g.nvec == 0) {                                                    // unaligned pointer or run % 4 != 0
+        for (uint32_t i = first; i < g.n; i += stride) {
+            const float s = j.scale[channel_scale_index(g, i)];
             const float x = j.x[i];
-            j.x[i] = j.divide ? x / s : x * s;
+            j.x[i] = g.divide ? x / s : x * s;
         }
         return;
     }
     float4* x4 = reinterpret_cast<float4*>(j.x);
-    for (uint32_t q = first; q < j.nvec; q += stride) {                   // one channel per float4
-        const float s = j.scale[eq_scale_index(j, q)];
+    for (uint32_t q = first; q < g.nvec; q += stride) {                   // one channel per float4
+        const float s = j.scale[channel_scale_index(g, q)];
         float4 v = x4[q];
-        if (j.divide) { v.x = v.x / s; v.y = v.y / s; v.z = v.z / s; v.w = v.w / s; }
+        if (g.divide) { v.x = v.x / s; v.y = v.y / s; v.z = v.z / s; v.w = v.w / s; }
         else { v.x = v.x * s; v.y = v.y * s; v.z = v.z * s; v.w = v.w * s; }
         x4[q] = v;
     }
@@ -122,7 +94,7 @@ __global__ __launch_bounds__(kBlock) void equalize_apply_kernel(const EqApArgs a
 
 int validate_scale(const ppqhip_equalize_scale_job* jobs, int num_jobs) {
     const char* what = "equalize_scale_multi";
-    if (num_jobs < 0 || (num_jobs > 0 && jobs == nullptr)) { set_error("%s: bad job table", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (int st = check_job_table(what, jobs, num_jobs)) return st;
     for (int k = 0; k < num_jobs; k++) {
         const ppqhip_equalize_scale_job& j = jobs[k];
         if (j.segments == nullptr || j.scale == nullptr || j.num_channel <= 0 || j.num_segments <= 0) {
@@ -149,8 +121,7 @@ void launch_scale(const ppqhip_equalize_scale_job* jobs, int num_jobs, hipStream
             count++;
         }
         for (uint32_t k = segs; k < (uint32_t)kEqMaxSegs; k++) args.segs[k] = args.segs[0];
-        for (uint32_t k = count; k < (uint32_t)kEqMaxJobs; k++) { args.jobs[k] = args.jobs[0]; args.first_block[k] = blocks; }
-        args.count = count;
+        pad_job_table(args, count, blocks);
         hipLaunchKernelGGL(equalize_scale_kernel, dim3(blocks), dim3(kBlock), 0, s, args);
         base += (int)count;
     }
@@ -158,30 +129,15 @@ void launch_scale(const ppqhip_equalize_scale_job* jobs, int num_jobs, hipStream
 
 int validate_apply(const ppqhip_equalize_apply_job* jobs, int num_jobs) {
     const char* what = "equalize_apply_multi";
-    if (num_jobs < 0 || (num_jobs > 0 && jobs == nullptr)) { set_error("%s: bad job table", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (int st = check_job_table(what, jobs, num_jobs)) return st;
     for (int k = 0; k < num_jobs; k++) {
         const ppqhip_equalize_apply_job& j = jobs[k];
         if (j.x == nullptr || j.scale == nullptr) { set_error("%s: job %d has a null pointer", what, k); return PPQHIP_ERR_INVALID_VALUE; }
-        if (j.n <= 0 || j.n > kEqMax || j.run <= 0 || j.inner <= 0 || j.group_out < 0 || j.num_scale <= 0 || j.n % j.run != 0 ||
-            j.inner > kEqMax || j.group_out > kEqMax) {
-            set_error("%s: job %d: bad geometry (n=%lld run=%lld inner=%lld group_out=%lld)", what, k, (long long)j.n, (long long)j.run,
-                      (long long)j.inner, (long long)j.group_out);
-            return PPQHIP_ERR_INVALID_VALUE;
-        }
-        const int64_t rows = j.n / j.run;
-        const int64_t last = std::min(j.inner, rows) - 1 + (j.group_out ? ((rows - 1) / j.inner / j.group_out) * j.inner : 0);
-        if (last >= j.num_scale) {
-            set_error("%s: job %d reads scale %lld of %lld", what, k, (long long)last, (long long)j.num_scale);
-            return PPQHIP_ERR_INVALID_VALUE;
-        }
+        if (int st = validate_channel_scale(what, k, kEqMax, j.n, j.run, j.inner, j.group_out, j.num_scale)) return st;
     }
-    std::vector<std::pair<const float*, const float*>> spans;             // in place: two jobs on one tensor would race
-    for (int k = 0; k < num_jobs; k++) spans.emplace_back(jobs[k].x, jobs[k].x + jobs[k].n);
-    std::sort(spans.begin(), spans.end());
-    for (size_t k = 1; k < spans.size(); k++) {
-        if (spans[k].first < spans[k - 1].second) { set_error("%s: two jobs overlap in memory", what); return PPQHIP_ERR_INVALID_VALUE; }
-    }
-    return PPQHIP_OK;
+    std::vector<Span> ins, outs;                                          // in place: two jobs on one tensor would race
+    for (int k = 0; k < num_jobs; k++) outs.push_back(span_of(jobs[k].x, jobs[k].n));
+    return check_overlap(what, ins, outs);
 }
 
 void launch_apply(const ppqhip_equalize_apply_job* jobs, int num_jobs, hipStream_t s) {
@@ -192,20 +148,12 @@ void launch_apply(const ppqhip_equalize_apply_job* jobs, int num_jobs, hipStream
         for (int k = 0; k < count; k++) {
             const ppqhip_equalize_apply_job& src = jobs[base + k];
             EqApJob& d = args.jobs[k];
-            d.x = src.x; d.scale = src.scale; d.n = (uint32_t)src.n;
-            const bool vec = aligned16(src.x) && src.run % 4 == 0;
-            d.nvec = vec ? (uint32_t)(src.n >> 2) : 0u;
-            d.run = make_fastdiv((uint32_t)(vec ? src.run / 4 : src.run));
-            d.inner = make_fastdiv((uint32_t)src.inner);
-            d.og = make_fastdiv((uint32_t)(src.group_out ? src.group_out : 1));
-            d.grouped = src.group_out ? 1u : 0u; d.divide = src.divide ? 1u : 0u; d.pad = 0;
-            const uint64_t work = vec ? d.nvec : (uint64_t)src.n;
-            d.blocks = (uint32_t)std::min<uint64_t>((work + kBlock - 1) / kBlock, kEqApMaxBlocksPerJob);
+            d.x = src.x; d.scale = src.scale;
+            d.g = pack_channel_scale(aligned16(src.x), src.n, src.run, src.inner, src.group_out, src.divide);
             args.first_block[k] = blocks;
-            blocks += d.blocks;
+            blocks += d.g.blocks;
         }
-        for (int k = count; k < kEqApMaxJobs; k++) { args.jobs[k] = args.jobs[0]; args.first_block[k] = blocks; }
-        args.count = (uint32_t)count;
+        pad_job_table(args, (uint32_t)count, blocks);
         hipLaunchKernelGGL(equalize_apply_kernel, dim3(blocks), dim3(kBlock), 0, s, args);
     }
 }

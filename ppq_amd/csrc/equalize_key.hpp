@@ -1,10 +1,12 @@
 // equalize_key.hpp -- the per-channel KEY of an equalization pair, shared by the scale kernel (equalize.hip) and the split-plan
-// kernel (split.hip): the packed segment, its host-side validation and the walk of one workgroup over the segments of one channel.
+// kernel (split.hip): the packed segment (ssd.hip's ranges kernel reads it too), its host-side validation and the walk of one
+// workgroup over the segments of one channel.
 //   up = max |x * m| over the upstream segments, down = the same over the downstream ones (reduce_by_axis(ABSOLUTE_MAX) of
 //   ppq/quantization/algorithm/equalization.py:428-436; max is order independent, a NaN wins as in torch.max).
 #pragma once
 
 #include <algorithm>
+#include <cstdio>
 
 #include "common.hpp"
 
@@ -21,7 +23,22 @@ struct EqSeg {                                     // 40 B
     uint32_t flags;                                // bit 0: downstream key; bit 1: 16-B loads (base, a, b, stride, run all 4-aligned)
 };
 
-// every extent of the segments of job k, checked against the tensors they read; at least one upstream and one downstream segment
+// one segment of job k: every extent, checked against the tensor it reads.  A message names it "<side> segment", or
+// "segment <t>" without a side.
+inline int validate_segment(const char* what, int k, const char* side, int t, const ppqhip_equalize_segment& g, int64_t C) {
+    const bool bad = g.base == nullptr || g.div < 1 || g.a < 0 || g.b < 0 || g.outer < 1 || g.run < 1 || g.stride < 0 || g.extent < 1 ||
+                     g.extent > kEqMax || g.div > kEqMax || g.a > kEqMax || g.b > kEqMax || g.outer > kEqMax || g.run > kEqMax ||
+                     g.stride > kEqMax || g.outer * g.run > kEqMax;
+    const int64_t last = bad ? 0 : ((C - 1) / g.div) * g.a + (std::min<int64_t>(g.div, C) - 1) * g.b + (g.outer - 1) * g.stride + g.run - 1;
+    if (!bad && last < g.extent) return PPQHIP_OK;
+    char label[32];
+    if (side) snprintf(label, sizeof(label), "%s segment", side); else snprintf(label, sizeof(label), "segment %d", t);
+    if (bad) set_error("%s: job %d %s: bad geometry", what, k, label);
+    else set_error("%s: job %d %s: reads element %lld of a tensor of %lld", what, k, label, (long long)last, (long long)g.extent);
+    return PPQHIP_ERR_INVALID_VALUE;
+}
+
+// the segments of job k: each one as above; at least one upstream and one downstream segment
 inline int validate_segments(const char* what, int k, const ppqhip_equalize_segment* segments, int num_segments, int64_t C) {
     if (num_segments > kEqMaxSegs) {
         set_error("%s: job %d: %d segments, at most %d fit one launch", what, k, num_segments, kEqMaxSegs);
@@ -29,18 +46,8 @@ inline int validate_segments(const char* what, int k, const ppqhip_equalize_segm
     }
     bool has_up = false, has_down = false;
     for (int t = 0; t < num_segments; t++) {
-        const ppqhip_equalize_segment& g = segments[t];
-        if (g.base == nullptr || g.div < 1 || g.a < 0 || g.b < 0 || g.outer < 1 || g.run < 1 || g.stride < 0 || g.extent < 1 ||
-            g.extent > kEqMax || g.div > kEqMax || g.a > kEqMax || g.b > kEqMax || g.outer > kEqMax || g.run > kEqMax ||
-            g.stride > kEqMax || g.outer * g.run > kEqMax) {
-            set_error("%s: job %d segment %d: bad geometry", what, k, t); return PPQHIP_ERR_INVALID_VALUE;
-        }
-        const int64_t last = ((C - 1) / g.div) * g.a + (std::min<int64_t>(g.div, C) - 1) * g.b + (g.outer - 1) * g.stride + g.run - 1;
-        if (last >= g.extent) {
-            set_error("%s: job %d segment %d: reads element %lld of a tensor of %lld", what, k, t, (long long)last, (long long)g.extent);
-            return PPQHIP_ERR_INVALID_VALUE;
-        }
-        (g.downstream ? has_down : has_up) = true;
+        if (int st = validate_segment(what, k, nullptr, t, segments[t], C)) return st;
+        (segments[t].downstream ? has_down : has_up) = true;
     }
     if (!has_up || !has_down) { set_error("%s: job %d needs an upstream and a downstream segment", what, k); return PPQHIP_ERR_INVALID_VALUE; }
     return PPQHIP_OK;

@@ -16,14 +16,14 @@
 // per row;  above: ceil(count / kChunk) workgroups per row write partials into the stream's scratch and a second kernel folds
 // them (a wave per row).  kChunk is a constant: the split of a row never depends on the device or on the other jobs.
 //
-// Jobs: the table travels BY VALUE in the kernel arguments (<= kMsMaxJobs per launch, more are chunked): no upload, no
-// synchronisation, capturable into a HIP graph (a first use of the split path on a stream grows its scratch: run it once
-// eagerly before capturing, as for the other scratch users).
+// Job tables: DESIGN.md, "Job tables" (a first use of the split path on a stream grows its scratch: run it once eagerly before
+// capturing, as for the other scratch users).
 // The row-sum machinery itself (job layout, guarded loads, Sums4, the walk of a row piece) lives in measure_rows.hpp, which
 // ssd.hip shares for its fake-quant-and-measure launch.
 #include <algorithm>
 
 #include "common.hpp"
+#include "job_table.hpp"
 #include "measure_rows.hpp"
 
 namespace ppqhip {
@@ -154,7 +154,7 @@ extern "C" {
 
 int ppqhip_fetch_rows_multi(const ppqhip_fetch_rows_job* jobs, int num_jobs, void* stream) {
     if (num_jobs <= 0) return PPQHIP_OK;
-    if (jobs == nullptr) { set_error("fetch_rows_multi: jobs is null"); return PPQHIP_ERR_INVALID_VALUE; }
+    if (int st = check_job_table("fetch_rows_multi", jobs, num_jobs)) return st;
     hipStream_t s = (hipStream_t)stream;
     double bytes = 0.0;
     for (int k = 0; k < num_jobs; k++) {
@@ -181,8 +181,7 @@ int ppqhip_fetch_rows_multi(const ppqhip_fetch_rows_job* jobs, int num_jobs, voi
             args.first_block[count] = (uint32_t)blocks;
             blocks += need;
         }
-        for (int k = count; k < kFtMaxJobs; k++) { args.jobs[k] = args.jobs[0]; args.first_block[k] = (uint32_t)blocks; }
-        args.count = (uint32_t)count;
+        pad_job_table(args, (uint32_t)count, (uint32_t)blocks);
         hipLaunchKernelGGL(fetch_rows_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s, args);
         base += count;
     }
@@ -191,7 +190,7 @@ int ppqhip_fetch_rows_multi(const ppqhip_fetch_rows_job* jobs, int num_jobs, voi
 
 int ppqhip_measure_rows_multi(const ppqhip_measure_rows_job* jobs, int num_jobs, void* stream) {
     if (num_jobs <= 0) return PPQHIP_OK;
-    if (jobs == nullptr) { set_error("measure_rows_multi: jobs is null"); return PPQHIP_ERR_INVALID_VALUE; }
+    if (int st = check_job_table("measure_rows_multi", jobs, num_jobs)) return st;
     hipStream_t s = (hipStream_t)stream;
     double bytes = 0.0;
     for (int k = 0; k < num_jobs; k++) {
@@ -232,8 +231,7 @@ int ppqhip_measure_rows_multi(const ppqhip_measure_rows_job* jobs, int num_jobs,
                 partials += need;
             }
         }
-        for (int k = count; k < kMsMaxJobs; k++) { args.jobs[k] = args.jobs[0]; args.first_block[k] = (uint32_t)blocks; }
-        args.count = (uint32_t)count;
+        pad_job_table(args, (uint32_t)count, (uint32_t)blocks);
         args.scratch = nullptr;
         if (folds > 0) {
             args.scratch = (double*)scratch(s, (size_t)partials * 4 * sizeof(double));
@@ -241,8 +239,7 @@ int ppqhip_measure_rows_multi(const ppqhip_measure_rows_job* jobs, int num_jobs,
         }
         hipLaunchKernelGGL(measure_rows_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s, args);
         if (folds > 0) {
-            for (int k = folds; k < kMsMaxJobs; k++) { fold.jobs[k] = fold.jobs[0]; fold.first_block[k] = (uint32_t)fold_blocks; }
-            fold.count = (uint32_t)folds;
+            pad_job_table(fold, (uint32_t)folds, (uint32_t)fold_blocks);
             fold.scratch = args.scratch;
             hipLaunchKernelGGL(measure_fold_kernel, dim3((uint32_t)fold_blocks), dim3(kBlock), 0, s, fold);
         }
@@ -253,7 +250,7 @@ int ppqhip_measure_rows_multi(const ppqhip_measure_rows_job* jobs, int num_jobs,
 
 int ppqhip_measure_finish_multi(const ppqhip_measure_finish_job* jobs, int num_jobs, void* stream) {
     if (num_jobs <= 0) return PPQHIP_OK;
-    if (jobs == nullptr) { set_error("measure_finish_multi: jobs is null"); return PPQHIP_ERR_INVALID_VALUE; }
+    if (int st = check_job_table("measure_finish_multi", jobs, num_jobs)) return st;
     hipStream_t s = (hipStream_t)stream;
     double bytes = 0.0;
     for (int k = 0; k < num_jobs; k++) {

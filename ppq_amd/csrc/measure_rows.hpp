@@ -52,17 +52,6 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 
 __device__ __forceinline__ bool aligned16_d(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-template <typename A>
-__device__ __forceinline__ uint32_t job_of(const A& args, uint32_t& local) {
-    uint32_t lo = 0, hi = args.count;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (args.first_block[mid] <= blockIdx.x) lo = mid; else hi = mid;
-    }
-    local = blockIdx.x - args.first_block[lo];
-    return __builtin_amdgcn_readfirstlane(lo);
-}
-
 // four consecutive elements x[e .. e + 4) of a row of `len`; slots past the end read as 0 (they add +0.0 to every sum)
 __device__ __forceinline__ float4 load4_guarded(const float* __restrict__ x, uint32_t e, uint32_t len, bool vec) {
     if (vec && e + 4 <= len) return *reinterpret_cast<const float4*>(x + e);

@@ -8,11 +8,11 @@
 //   out = (clamp(q, qmin, qmax) - o) * s
 // clamp is torch's `isnan(v) ? v : min(max(v, lo), hi)` with the Python ints converted to float: NaN in, NaN out.
 //
-// Jobs: the table travels in the kernel arguments (<= kRtMaxJobs per launch, more are chunked): no upload, capturable into a HIP
-// graph.  channel(i) = (i / elem_per_channel) % num_channel with FastDiv (a per-tensor job has num_channel = 1).  16-B loads and
+// Job table: DESIGN.md, "Job tables" (capturable into a HIP graph).  channel(i) = (i / elem_per_channel) % num_channel with FastDiv (a per-tensor job has num_channel = 1).  16-B loads and
 // stores where every pointer of the job is aligned, the n % 4 tail by the job's first workgroup; element-wise otherwise.  No
 // atomics, no reductions.
 #include "common.hpp"
+#include "job_table.hpp"
 
 namespace ppqhip {
 namespace {
@@ -39,10 +39,6 @@ struct RtArgs {
 };
 static_assert(sizeof(RtArgs) <= 4096, "kernel arguments are limited to 4 KB");
 
-__device__ __forceinline__ float rt_clamp_nan(float v, float lo, float hi) {    // torch's clamp: NaN passes through
-    return __builtin_isnan(v) ? v : __builtin_fminf(__builtin_fmaxf(v, lo), hi);
-}
-
 __device__ __forceinline__ uint32_t rt_channel(uint32_t i, const FastDiv& epc, const FastDiv& nc) {
     const uint32_t row = fdiv(i, epc);
     return row - fdiv(row, nc) * nc.d;
@@ -53,7 +49,7 @@ __device__ __forceinline__ float rt_forward(float w, float r, float s, float o, 
     const float q = w / s;
     const float u = q + (r > 0.5f ? 1.0f : 0.0f);
     const float t = u + o;
-    const float c = rt_clamp_nan(t, qmin, qmax);
+    const float c = clamp_nan(t, qmin, qmax);
     return (c - o) * s;
 }
 
@@ -92,16 +88,13 @@ __device__ __forceinline__ void rt_job(const RtJob& j, uint32_t local) {
 }
 
 __global__ __launch_bounds__(kBlock) void roundtune_fwd_kernel(const RtArgs args) {
-    uint32_t lo = 0, hi = args.count;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (args.first_block[mid] <= blockIdx.x) lo = mid; else hi = mid;
-    }
-    rt_job(args.jobs[__builtin_amdgcn_readfirstlane(lo)], blockIdx.x - args.first_block[lo]);
+    uint32_t local;
+    const uint32_t k = job_of(args, local);
+    rt_job(args.jobs[k], local);
 }
 
 int validate_jobs(const ppqhip_roundtune_job* jobs, int num_jobs, const char* what) {
-    if (num_jobs < 0 || (num_jobs > 0 && jobs == nullptr)) { set_error("%s: bad job table", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (int st = check_job_table(what, jobs, num_jobs)) return st;
     for (int k = 0; k < num_jobs; k++) {
         const ppqhip_roundtune_job& j = jobs[k];
         if (j.n <= 0 || j.n > 0x7fffffffLL) {
@@ -144,8 +137,7 @@ void launch_roundtune(const ppqhip_roundtune_job* jobs, int num_jobs, hipStream_
             args.first_block[k] = blocks;
             blocks += d.blocks;
         }
-        for (int k = count; k < kRtMaxJobs; k++) { args.jobs[k] = args.jobs[0]; args.first_block[k] = blocks; }
-        args.count = (uint32_t)count;
+        pad_job_table(args, (uint32_t)count, blocks);
         hipLaunchKernelGGL(roundtune_fwd_kernel, dim3(blocks), dim3(kBlock), 0, s, args);
     }
 }

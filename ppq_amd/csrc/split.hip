@@ -11,12 +11,10 @@
 // of channel c waits in src_of[2 * c] -- the scan of a chunk of kBlock channels writes no further than src_of[2 * c + 1] of its
 // last channel, so it never overwrites a mask it has not read: no scratch buffer, no atomics.
 //
-// Jobs and segments travel in the kernel arguments (chunked when they do not fit): no upload.
-#include <algorithm>
-#include <vector>
-
+// Job tables: DESIGN.md, "Job tables".
 #include "common.hpp"
 #include "equalize_key.hpp"
+#include "job_table.hpp"
 
 namespace ppqhip {
 namespace {
@@ -45,14 +43,8 @@ static_assert(sizeof(SpPlanArgs) <= 4096, "kernel arguments are limited to 4 KB"
 // one workgroup per (job, channel): src_of[2 * c] = split[c]
 __global__ __launch_bounds__(kBlock) void split_mask_kernel(const SpPlanArgs args) {
     __shared__ float lds[4 * (kBlock / kWave)];
-    uint32_t lo = 0, hi = args.count;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (args.first_block[mid] <= blockIdx.x) lo = mid; else hi = mid;
-    }
-    lo = __builtin_amdgcn_readfirstlane(lo);
-    const SpPlanJob& j = args.jobs[lo];
-    const uint32_t c = blockIdx.x - args.first_block[lo];
+    uint32_t c;
+    const SpPlanJob& j = args.jobs[job_of(args, c)];
     float up, dn;
     eq_channel_keys(args.segs + j.seg_begin, j.seg_count, c, lds, up, dn);
     if (threadIdx.x == 0) j.src_of[2 * c] = (up >= j.threshold && dn >= j.threshold) ? 1u : 0u;     // a NaN key compares false
@@ -95,23 +87,9 @@ __global__ __launch_bounds__(kBlock) void split_scan_kernel(const SpPlanArgs arg
     if (threadIdx.x == 0) *j.count = (int32_t)carry;
 }
 
-// no output may overlap another output or an input of the same call (`outs` is sorted here)
-typedef std::pair<const char*, const char*> Span;
-int check_overlap(const char* what, const std::vector<Span>& ins, std::vector<Span>& outs) {
-    std::sort(outs.begin(), outs.end());
-    for (size_t k = 1; k < outs.size(); k++) {
-        if (outs[k].first < outs[k - 1].second) { set_error("%s: two outputs overlap in memory", what); return PPQHIP_ERR_INVALID_VALUE; }
-    }
-    for (const Span& in : ins) {                   // the first output that ends behind the input's start must begin at or behind its end
-        auto it = std::upper_bound(outs.begin(), outs.end(), in.first, [](const char* p, const Span& o) { return p < o.second; });
-        if (it != outs.end() && it->first < in.second) { set_error("%s: an output overlaps an input", what); return PPQHIP_ERR_INVALID_VALUE; }
-    }
-    return PPQHIP_OK;
-}
-
 int validate_plan(const ppqhip_split_plan_job* jobs, int num_jobs) {
     const char* what = "split_plan_multi";
-    if (num_jobs < 0 || (num_jobs > 0 && jobs == nullptr)) { set_error("%s: bad job table", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (int st = check_job_table(what, jobs, num_jobs)) return st;
     for (int k = 0; k < num_jobs; k++) {
         const ppqhip_split_plan_job& j = jobs[k];
         if (j.segments == nullptr || j.src_of == nullptr || j.count == nullptr || j.num_channel <= 0 || j.num_segments <= 0) {
@@ -123,10 +101,9 @@ int validate_plan(const ppqhip_split_plan_job* jobs, int num_jobs) {
     // the plans of one call are written while its segments are read: an output shares memory with nothing else of the call
     std::vector<Span> ins, outs;
     for (int k = 0; k < num_jobs; k++) {
-        outs.emplace_back((const char*)jobs[k].src_of, (const char*)(jobs[k].src_of + 2 * (int64_t)jobs[k].num_channel));
-        outs.emplace_back((const char*)jobs[k].count, (const char*)(jobs[k].count + 1));
-        for (int t = 0; t < jobs[k].num_segments; t++)
-            ins.emplace_back((const char*)jobs[k].segments[t].base, (const char*)(jobs[k].segments[t].base + jobs[k].segments[t].extent));
+        outs.push_back(span_of(jobs[k].src_of, 2 * (int64_t)jobs[k].num_channel));
+        outs.push_back(span_of(jobs[k].count, 1));
+        for (int t = 0; t < jobs[k].num_segments; t++) ins.push_back(span_of(jobs[k].segments[t].base, jobs[k].segments[t].extent));
     }
     return check_overlap(what, ins, outs);
 }
@@ -148,8 +125,7 @@ void launch_plan(const ppqhip_split_plan_job* jobs, int num_jobs, hipStream_t s)
             count++;
         }
         for (uint32_t k = segs; k < (uint32_t)kEqMaxSegs; k++) args.segs[k] = args.segs[0];
-        for (uint32_t k = count; k < (uint32_t)kSpMaxJobs; k++) { args.jobs[k] = args.jobs[0]; args.first_block[k] = blocks; }
-        args.count = count;
+        pad_job_table(args, count, blocks);
         hipLaunchKernelGGL(split_mask_kernel, dim3(blocks), dim3(kBlock), 0, s, args);
         hipLaunchKernelGGL(split_scan_kernel, dim3(count), dim3(kBlock), 0, s, args);
         base += (int)count;
@@ -177,15 +153,10 @@ static_assert(sizeof(SpApArgs) <= 4096, "kernel arguments are limited to 4 KB");
 
 // the destination drives the loop: every output unit is written once
 __global__ __launch_bounds__(kBlock) void split_apply_kernel(const SpApArgs args) {
-    uint32_t lo = 0, hi = args.count;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (args.first_block[mid] <= blockIdx.x) lo = mid; else hi = mid;
-    }
-    lo = __builtin_amdgcn_readfirstlane(lo);
-    const SpApJob& j = args.jobs[lo];
+    uint32_t local;
+    const SpApJob& j = args.jobs[job_of(args, local)];
     const uint32_t stride = j.blocks * kBlock;
-    const uint32_t first = (blockIdx.x - args.first_block[lo]) * kBlock + threadIdx.x;
+    const uint32_t first = local * kBlock + threadIdx.x;
     for (uint32_t i = first; i < j.n_out; i += stride) {
         const uint32_t row = fdiv(i, j.run), e = i - row * j.run.d;
         const uint32_t o = fdiv(row, j.count), d = row - o * j.count.d;    // d < count: inside the plan
@@ -206,7 +177,7 @@ __global__ __launch_bounds__(kBlock) void split_apply_kernel(const SpApArgs args
 
 int validate_apply(const ppqhip_split_apply_job* jobs, int num_jobs) {
     const char* what = "split_apply_multi";
-    if (num_jobs < 0 || (num_jobs > 0 && jobs == nullptr)) { set_error("%s: bad job table", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (int st = check_job_table(what, jobs, num_jobs)) return st;
     std::vector<Span> ins, outs;
     for (int k = 0; k < num_jobs; k++) {
         const ppqhip_split_apply_job& j = jobs[k];
@@ -222,9 +193,9 @@ int validate_apply(const ppqhip_split_apply_job* jobs, int num_jobs) {
         }
         const int64_t n_out = j.n / j.num_channel * j.count;
         if (n_out > kEqMax) { set_error("%s: job %d writes %lld elements, more than 2^31 - 1", what, k, (long long)n_out); return PPQHIP_ERR_INVALID_VALUE; }
-        ins.emplace_back((const char*)j.x, (const char*)(j.x + j.n));
-        ins.emplace_back((const char*)j.src_of, (const char*)(j.src_of + j.count));
-        outs.emplace_back((const char*)j.out, (const char*)(j.out + n_out));
+        ins.push_back(span_of(j.x, j.n));
+        ins.push_back(span_of(j.src_of, j.count));
+        outs.push_back(span_of(j.out, n_out));
     }
     return check_overlap(what, ins, outs);
 }
@@ -249,8 +220,7 @@ void launch_apply(const ppqhip_split_apply_job* jobs, int num_jobs, hipStream_t 
             args.first_block[k] = blocks;
             blocks += d.blocks;
         }
-        for (int k = count; k < kSpApMaxJobs; k++) { args.jobs[k] = args.jobs[0]; args.first_block[k] = blocks; }
-        args.count = (uint32_t)count;
+        pad_job_table(args, (uint32_t)count, blocks);
         hipLaunchKernelGGL(split_apply_kernel, dim3(blocks), dim3(kBlock), 0, s, args);
     }
 }

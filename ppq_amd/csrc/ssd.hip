@@ -20,23 +20,18 @@
 //    accumulation of measure_rows.hpp -- the same lanes, the same order: bit-identical to ppqhip_fq_linear_{t,c} into a buffer
 //    followed by ppqhip_measure_rows_multi on that buffer, with one read of y and r and no write.
 //
-// Jobs travel BY VALUE in the kernel arguments (chunked when they do not fit): no upload, no synchronisation, no atomics.
-#include <algorithm>
-#include <vector>
-
+// Job tables: DESIGN.md, "Job tables".  No synchronisation, no atomics.
+#include "channel_scale.hpp"
 #include "common.hpp"
+#include "equalize_key.hpp"
+#include "job_table.hpp"
 #include "measure_rows.hpp"
 
 namespace ppqhip {
 namespace {
 
-constexpr int64_t kSsdMax = 0x7fffffffLL;
-
 __device__ __forceinline__ float nan_min(float a, float b) { return (a != a) ? a : ((b != b) ? b : __builtin_fminf(a, b)); }
 __device__ __forceinline__ float nan_max(float a, float b) { return (a != a) ? a : ((b != b) ? b : __builtin_fmaxf(a, b)); }
-__device__ __forceinline__ float nan_clamp(float v, float lo, float hi) {        // torch's clamp: NaN passes through
-    return (v != v) ? v : __builtin_fminf(__builtin_fmaxf(v, lo), hi);
-}
 
 // NaN-propagating max / min of one value per thread over the workgroup; every thread gets the result.  `lds`: kWaves floats.
 template <bool MAX>
@@ -54,22 +49,17 @@ __device__ __forceinline__ float block_extreme(float v, float* lds) {
 // ------------------------------------------------------------------------------------ scales
 constexpr int kSsdMaxJobs = 24;
 
-struct SsdSeg {                                    // 32 B
-    const float* base;
-    uint32_t div, a, b;                            // offset of channel c: (c / div) * a + (c % div) * b
-    uint32_t outer, stride, run;
-};
-struct SsdScaleJob {                               // 104 B
-    SsdSeg seg[2];                                 // [0] first weight, [1] last weight
+struct SsdScaleJob {                               // 112 B
+    EqSeg seg[2];                                  // [0] first weight, [1] last weight (mult and flags are not read)
     const float* act;
     float* scales;                                 // [4][C]
     float* ranges;                                 // [2][C]
     uint32_t C;
     float ratio;
-    uint32_t first_block, pad;
 };
 struct SsdScaleArgs {
     SsdScaleJob jobs[kSsdMaxJobs];
+    uint32_t first_block[kSsdMaxJobs];
     uint32_t count;
 };
 static_assert(sizeof(SsdScaleArgs) <= 4096, "kernel arguments are limited to 4 KB");
@@ -77,17 +67,11 @@ static_assert(sizeof(SsdScaleArgs) <= 4096, "kernel arguments are limited to 4 K
 // one workgroup per (job, channel): ranges[side][c] = max |w| over the channel's elements of the segment
 __global__ __launch_bounds__(kBlock) void ssd_ranges_kernel(const SsdScaleArgs args) {
     __shared__ float lds[kWaves];
-    uint32_t lo = 0, hi = args.count;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (args.jobs[mid].first_block <= blockIdx.x) lo = mid; else hi = mid;
-    }
-    lo = __builtin_amdgcn_readfirstlane(lo);
-    const SsdScaleJob& j = args.jobs[lo];
-    const uint32_t c = blockIdx.x - j.first_block;
+    uint32_t c;
+    const SsdScaleJob& j = args.jobs[job_of(args, c)];
 #pragma unroll
     for (int side = 0; side < 2; side++) {
-        const SsdSeg& g = j.seg[side];
+        const EqSeg& g = j.seg[side];
         const uint32_t q = c / g.div;
         const float* p = g.base + (size_t)q * g.a + (size_t)(c - q * g.div) * g.b;
         const uint32_t total = g.outer * g.run;
@@ -141,42 +125,25 @@ __global__ __launch_bounds__(kBlock) void ssd_scales_kernel(const SsdScaleArgs a
     low = block_extreme<false>(low, lds);
     for (uint32_t c = threadIdx.x; c < C; c += kBlock) {
         const float q0 = last[c] / (first[c] + eps);
-        j.scales[c] = nan_clamp(__builtin_sqrtf(q0), 0.1f, 10.0f);
+        j.scales[c] = clamp_nan(__builtin_sqrtf(q0), 0.1f, 10.0f);
         const SsdPre p = pre(c);
         j.scales[(size_t)C + c] = nan_min(p.ks, p.as);
         const float s2 = algo2(p) / low;
-        j.scales[(size_t)2 * C + c] = nan_clamp(s2, 1.0f, 2.0f);
+        j.scales[(size_t)2 * C + c] = clamp_nan(s2, 1.0f, 2.0f);
         const float k3 = __builtin_sqrtf(p.ks / p.nks);
         const float s3 = __builtin_sqrtf(p.as * k3);
-        j.scales[(size_t)3 * C + c] = nan_clamp(s3, 1.0f, 2.0f);
+        j.scales[(size_t)3 * C + c] = clamp_nan(s3, 1.0f, 2.0f);
     }
-}
-
-int validate_segment(const ppqhip_equalize_segment& g, int64_t C, const char* what, int k, const char* side) {
-    if (g.base == nullptr || g.div < 1 || g.a < 0 || g.b < 0 || g.outer < 1 || g.run < 1 || g.stride < 0 || g.extent < 1 ||
-        g.extent > kSsdMax || g.div > kSsdMax || g.a > kSsdMax || g.b > kSsdMax || g.outer > kSsdMax || g.run > kSsdMax ||
-        g.stride > kSsdMax || g.outer * g.run > kSsdMax) {
-        set_error("%s: job %d: %s segment: bad geometry", what, k, side); return PPQHIP_ERR_INVALID_VALUE;
-    }
-    const int64_t last = ((C - 1) / g.div) * g.a + (std::min<int64_t>(g.div, C) - 1) * g.b + (g.outer - 1) * g.stride + g.run - 1;
-    if (last >= g.extent) {
-        set_error("%s: job %d: %s segment reads element %lld of a tensor of %lld", what, k, side, (long long)last, (long long)g.extent);
-        return PPQHIP_ERR_INVALID_VALUE;
-    }
-    return PPQHIP_OK;
 }
 
 // ------------------------------------------------------------------------------------ apply
 constexpr int kSsdApMaxJobs = 32;
-constexpr uint32_t kSsdApMaxBlocksPerJob = 1024;   // grid-strided beyond
-
 struct SsdApJob {                                  // 88 B
     const float* x;
     float* out;                                    // [4][n]
     const float* scale;                            // [4][C]
-    uint32_t n, nvec;                              // nvec: float4 count (0: 4-B accesses); then `run` holds run / 4
-    FastDiv run, inner, og;
-    uint32_t grouped, divide, blocks, C;
+    ChannelScaleMap g;
+    uint32_t C;
 };
 struct SsdApArgs {
     SsdApJob jobs[kSsdApMaxJobs];
@@ -185,47 +152,35 @@ struct SsdApArgs {
 };
 static_assert(sizeof(SsdApArgs) <= 4096, "kernel arguments are limited to 4 KB");
 
-__device__ __forceinline__ uint32_t ssd_scale_index(const SsdApJob& j, uint32_t unit) {       // unit: element (or float4) index
-    const uint32_t row = fdiv(unit, j.run);
-    const uint32_t o = fdiv(row, j.inner);
-    uint32_t k = row - o * j.inner.d;
-    if (j.grouped) k += fdiv(o, j.og) * j.inner.d;
-    return k;
-}
-
 __global__ __launch_bounds__(kBlock) void ssd_apply_kernel(const SsdApArgs args) {
-    uint32_t lo = 0, hi = args.count;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (args.first_block[mid] <= blockIdx.x) lo = mid; else hi = mid;
-    }
-    lo = __builtin_amdgcn_readfirstlane(lo);
-    const SsdApJob& j = args.jobs[lo];
-    const uint32_t stride = j.blocks * kBlock;
-    const uint32_t first = (blockIdx.x - args.first_block[lo]) * kBlock + threadIdx.x;
-    if (j.nvec == 0) {                                                    // unaligned pointer or run % 4 != 0
-        for (uint32_t i = first; i < j.n; i += stride) {
-            const uint32_t k = ssd_scale_index(j, i);
+    uint32_t local;
+    const SsdApJob& j = args.jobs[job_of(args, local)];
+    const ChannelScaleMap& g = j.g;
+    const uint32_t stride = g.blocks * kBlock;
+    const uint32_t first = local * kBlock + threadIdx.x;
+    if (g.nvec == 0) {                                                    // unaligned pointer or run % 4 != 0
+        for (uint32_t i = first; i < g.n; i += stride) {
+            const uint32_t k = channel_scale_index(g, i);
             const float x = j.x[i];
 #pragma unroll
             for (uint32_t cand = 0; cand < 4; cand++) {
                 const float s = j.scale[(size_t)cand * j.C + k];
-                j.out[(size_t)cand * j.n + i] = j.divide ? x / s : x * s;
+                j.out[(size_t)cand * g.n + i] = g.divide ? x / s : x * s;
             }
         }
         return;
     }
     const float4* x4 = reinterpret_cast<const float4*>(j.x);
-    for (uint32_t q = first; q < j.nvec; q += stride) {                   // one channel per float4
-        const uint32_t k = ssd_scale_index(j, q);
+    for (uint32_t q = first; q < g.nvec; q += stride) {                   // one channel per float4
+        const uint32_t k = channel_scale_index(g, q);
         const float4 v = x4[q];
 #pragma unroll
         for (uint32_t cand = 0; cand < 4; cand++) {
             const float s = j.scale[(size_t)cand * j.C + k];
             float4 r;
-            if (j.divide) { r.x = v.x / s; r.y = v.y / s; r.z = v.z / s; r.w = v.w / s; }
+            if (g.divide) { r.x = v.x / s; r.y = v.y / s; r.z = v.z / s; r.w = v.w / s; }
             else { r.x = v.x * s; r.y = v.y * s; r.z = v.z * s; r.w = v.w * s; }
-            reinterpret_cast<float4*>(j.out + (size_t)cand * j.n)[q] = r;   // n % 4 == 0 here: every candidate stays 16-B aligned
+            reinterpret_cast<float4*>(j.out + (size_t)cand * g.n)[q] = r;   // n % 4 == 0 here: every candidate stays 16-B aligned
         }
     }
 }
@@ -290,7 +245,7 @@ extern "C" {
 
 int ppqhip_ssd_scales_multi(const ppqhip_ssd_scales_job* jobs, int num_jobs, void* stream) {
     const char* what = "ssd_scales_multi";
-    if (num_jobs < 0 || (num_jobs > 0 && jobs == nullptr)) { set_error("%s: bad job table", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (int st = check_job_table(what, jobs, num_jobs)) return st;
     if (num_jobs == 0) return PPQHIP_OK;
     double bytes = 0.0;
     for (int k = 0; k < num_jobs; k++) {
@@ -298,8 +253,8 @@ int ppqhip_ssd_scales_multi(const ppqhip_ssd_scales_job* jobs, int num_jobs, voi
         if (j.act_range == nullptr || j.scales == nullptr || j.ranges == nullptr || j.num_channel <= 0) {
             set_error("%s: job %d: null pointer or no channel", what, k); return PPQHIP_ERR_INVALID_VALUE;
         }
-        if (int st = validate_segment(j.first, j.num_channel, what, k, "first")) return st;
-        if (int st = validate_segment(j.last, j.num_channel, what, k, "last")) return st;
+        if (int st = validate_segment(what, k, "first", 0, j.first, j.num_channel)) return st;
+        if (int st = validate_segment(what, k, "last", 1, j.last, j.num_channel)) return st;
         bytes += 4.0 * (double)j.num_channel * (double)(j.first.outer * j.first.run + j.last.outer * j.last.run + 7);
     }
     hipStream_t s = (hipStream_t)stream;
@@ -311,19 +266,13 @@ int ppqhip_ssd_scales_multi(const ppqhip_ssd_scales_job* jobs, int num_jobs, voi
         for (int k = 0; k < count; k++) {
             const ppqhip_ssd_scales_job& src = jobs[base + k];
             SsdScaleJob& d = args.jobs[k];
-            const ppqhip_equalize_segment* segs[2] = {&src.first, &src.last};
-            for (int t = 0; t < 2; t++) {
-                const ppqhip_equalize_segment& g = *segs[t];
-                SsdSeg& e = d.seg[t];
-                e.base = g.base; e.div = (uint32_t)g.div; e.a = (uint32_t)g.a; e.b = (uint32_t)g.b;
-                e.outer = (uint32_t)g.outer; e.stride = (uint32_t)g.stride; e.run = (uint32_t)g.run;
-            }
+            d.seg[0] = pack_segment(src.first); d.seg[1] = pack_segment(src.last);
             d.act = src.act_range; d.scales = src.scales; d.ranges = src.ranges;
-            d.C = (uint32_t)src.num_channel; d.ratio = src.channel_ratio; d.first_block = blocks; d.pad = 0;
+            d.C = (uint32_t)src.num_channel; d.ratio = src.channel_ratio;
+            args.first_block[k] = blocks;
             blocks += d.C;
         }
-        for (int k = count; k < kSsdMaxJobs; k++) { args.jobs[k] = args.jobs[0]; args.jobs[k].first_block = blocks; }
-        args.count = (uint32_t)count;
+        pad_job_table(args, (uint32_t)count, blocks);
         hipLaunchKernelGGL(ssd_ranges_kernel, dim3(blocks), dim3(kBlock), 0, s, args);
         hipLaunchKernelGGL(ssd_scales_kernel, dim3((uint32_t)count), dim3(kBlock), 0, s, args);
     }
@@ -332,35 +281,20 @@ int ppqhip_ssd_scales_multi(const ppqhip_ssd_scales_job* jobs, int num_jobs, voi
 
 int ppqhip_ssd_apply_multi(const ppqhip_ssd_apply_job* jobs, int num_jobs, void* stream) {
     const char* what = "ssd_apply_multi";
-    if (num_jobs < 0 || (num_jobs > 0 && jobs == nullptr)) { set_error("%s: bad job table", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (int st = check_job_table(what, jobs, num_jobs)) return st;
     if (num_jobs == 0) return PPQHIP_OK;
     double bytes = 0.0;
-    std::vector<std::pair<const float*, const float*>> spans;             // an output over an input (or another output) would race
+    std::vector<Span> ins, outs;                                          // an output over an input (or another output) would race
     for (int k = 0; k < num_jobs; k++) {
         const ppqhip_ssd_apply_job& j = jobs[k];
         if (j.x == nullptr || j.out == nullptr || j.scales == nullptr) { set_error("%s: job %d has a null pointer", what, k); return PPQHIP_ERR_INVALID_VALUE; }
-        if (j.n <= 0 || j.n > kSsdMax / 4 || j.run <= 0 || j.inner <= 0 || j.group_out < 0 || j.num_channel <= 0 || j.n % j.run != 0 ||
-            j.inner > kSsdMax || j.group_out > kSsdMax || j.num_channel > kSsdMax) {
-            set_error("%s: job %d: bad geometry (n=%lld run=%lld inner=%lld group_out=%lld)", what, k, (long long)j.n, (long long)j.run,
-                      (long long)j.inner, (long long)j.group_out);
-            return PPQHIP_ERR_INVALID_VALUE;
-        }
-        const int64_t rows = j.n / j.run;
-        const int64_t last = std::min(j.inner, rows) - 1 + (j.group_out ? ((rows - 1) / j.inner / j.group_out) * j.inner : 0);
-        if (last >= j.num_channel) {
-            set_error("%s: job %d reads scale %lld of %lld", what, k, (long long)last, (long long)j.num_channel);
-            return PPQHIP_ERR_INVALID_VALUE;
-        }
-        spans.emplace_back(j.x, j.x + j.n);
-        spans.emplace_back(j.out, j.out + 4 * j.n);
+        if (j.num_channel > kEqMax) { set_error("%s: job %d: more than 2^31 - 1 channels", what, k); return PPQHIP_ERR_INVALID_VALUE; }
+        if (int st = validate_channel_scale(what, k, kEqMax / 4, j.n, j.run, j.inner, j.group_out, j.num_channel)) return st;   // out is [4][n]
+        ins.push_back(span_of(j.x, j.n));
+        outs.push_back(span_of(j.out, 4 * j.n));
         bytes += 20.0 * (double)j.n;                                      // x in, four candidates out
     }
-    std::sort(spans.begin(), spans.end());
-    for (size_t k = 1; k < spans.size(); k++) {
-        if (spans[k].first < spans[k - 1].second) {
-            set_error("%s: an output overlaps an input or another output", what); return PPQHIP_ERR_INVALID_VALUE;
-        }
-    }
+    if (int st = check_overlap(what, ins, outs)) return st;
     hipStream_t s = (hipStream_t)stream;
     LaunchScope scope(K_SSD_APPLY, bytes, s);
     for (int base = 0; base < num_jobs; base += kSsdApMaxJobs) {
@@ -370,20 +304,12 @@ int ppqhip_ssd_apply_multi(const ppqhip_ssd_apply_job* jobs, int num_jobs, void*
         for (int k = 0; k < count; k++) {
             const ppqhip_ssd_apply_job& src = jobs[base + k];
             SsdApJob& d = args.jobs[k];
-            d.x = src.x; d.out = src.out; d.scale = src.scales; d.n = (uint32_t)src.n; d.C = (uint32_t)src.num_channel;
-            const bool vec = aligned16(src.x) && aligned16(src.out) && src.run % 4 == 0;
-            d.nvec = vec ? (uint32_t)(src.n >> 2) : 0u;
-            d.run = make_fastdiv((uint32_t)(vec ? src.run / 4 : src.run));
-            d.inner = make_fastdiv((uint32_t)src.inner);
-            d.og = make_fastdiv((uint32_t)(src.group_out ? src.group_out : 1));
-            d.grouped = src.group_out ? 1u : 0u; d.divide = src.divide ? 1u : 0u;
-            const uint64_t work = vec ? d.nvec : (uint64_t)src.n;
-            d.blocks = (uint32_t)std::min<uint64_t>((work + kBlock - 1) / kBlock, kSsdApMaxBlocksPerJob);
+            d.x = src.x; d.out = src.out; d.scale = src.scales; d.C = (uint32_t)src.num_channel;
+            d.g = pack_channel_scale(aligned16(src.x) && aligned16(src.out), src.n, src.run, src.inner, src.group_out, src.divide);
             args.first_block[k] = blocks;
-            blocks += d.blocks;
+            blocks += d.g.blocks;
         }
-        for (int k = count; k < kSsdApMaxJobs; k++) { args.jobs[k] = args.jobs[0]; args.first_block[k] = blocks; }
-        args.count = (uint32_t)count;
+        pad_job_table(args, (uint32_t)count, blocks);
         hipLaunchKernelGGL(ssd_apply_kernel, dim3(blocks), dim3(kBlock), 0, s, args);
     }
     return finish_launch(what);
@@ -392,7 +318,7 @@ int ppqhip_ssd_apply_multi(const ppqhip_ssd_apply_job* jobs, int num_jobs, void*
 int ppqhip_fq_measure_rows_multi(const ppqhip_fq_measure_rows_job* jobs, int num_jobs, void* stream) {
     const char* what = "fq_measure_rows_multi";
     if (num_jobs <= 0) return PPQHIP_OK;
-    if (jobs == nullptr) { set_error("%s: jobs is null", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (int st = check_job_table(what, jobs, num_jobs)) return st;
     hipStream_t s = (hipStream_t)stream;
     double bytes = 0.0;
     for (int k = 0; k < num_jobs; k++) {
@@ -438,8 +364,8 @@ int ppqhip_fq_measure_rows_multi(const ppqhip_fq_measure_rows_job* jobs, int num
                 partials += need;
             }
         }
-        for (int k = count; k < kFqMsMaxJobs; k++) { args.jobs[k] = args.jobs[0]; args.fx[k] = args.fx[0]; args.first_block[k] = (uint32_t)blocks; }
-        args.count = (uint32_t)count;
+        for (int k = count; k < kFqMsMaxJobs; k++) args.fx[k] = args.fx[0];
+        pad_job_table(args, (uint32_t)count, (uint32_t)blocks);
         args.scratch = nullptr;
         if (folds > 0) {
             args.scratch = (double*)scratch(s, (size_t)partials * 4 * sizeof(double));
@@ -447,8 +373,7 @@ int ppqhip_fq_measure_rows_multi(const ppqhip_fq_measure_rows_job* jobs, int num
         }
         hipLaunchKernelGGL(fq_measure_rows_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s, args);
         if (folds > 0) {
-            for (int k = folds; k < kMsMaxJobs; k++) { fold.jobs[k] = fold.jobs[0]; fold.first_block[k] = (uint32_t)fold_blocks; }
-            fold.count = (uint32_t)folds;
+            pad_job_table(fold, (uint32_t)folds, (uint32_t)fold_blocks);
             fold.scratch = args.scratch;
             launch_measure_fold(fold, (uint32_t)fold_blocks, s);
         }

@@ -26,11 +26,11 @@
 // lanes fold in the xor tree, waves in index order, pieces as above: the bits depend on n alone, not on the pointers, the other
 // jobs or the device.  No global atomics.  NaN in a series is not ordered by min / max (v_min / v_max drop it).
 //
-// Jobs travel BY VALUE in the kernel arguments (<= kStMaxJobs per launch, more are chunked): no upload, no synchronisation,
-// capturable (a first use of the split path on a stream grows its scratch: run it once eagerly before capturing).
+// Job tables: DESIGN.md, "Job tables" (a first use of the split path on a stream grows its scratch: run it once eagerly before capturing).
 #include <algorithm>
 
 #include "common.hpp"
+#include "job_table.hpp"
 #include "measure_rows.hpp"
 
 namespace ppqhip {
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(kBlock) void stat_shape_fold_kernel(const StArgs ar
 }
 
 int validate(const ppqhip_stat_job* jobs, int num_jobs, bool shape, const char* what, double& bytes) {
-    if (jobs == nullptr) { set_error("%s: jobs is null", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (int st = check_job_table(what, jobs, num_jobs)) return st;
     for (int k = 0; k < num_jobs; k++) {
         const ppqhip_stat_job& j = jobs[k];
         if (j.n <= 0 || j.n > 0x7fffffffLL) { set_error("%s: job %d is empty or has more than 2^31 - 1 elements", what, k); return PPQHIP_ERR_INVALID_VALUE; }
@@ -295,8 +295,7 @@ int launch_all(const ppqhip_stat_job* jobs, int num_jobs, int partial_doubles, h
             blocks += chunks;
             if (chunks > 1) { fold.jobs[folds++] = d; partials += chunks; }
         }
-        for (int k = count; k < kStMaxJobs; k++) { args.jobs[k] = args.jobs[0]; args.first_block[k] = (uint32_t)blocks; }
-        args.count = (uint32_t)count;
+        pad_job_table(args, (uint32_t)count, (uint32_t)blocks);
         args.scratch = nullptr;
         if (folds > 0) {
             args.scratch = (double*)scratch(s, (size_t)partials * partial_doubles * sizeof(double));

@@ -137,8 +137,7 @@ class EqualizationPair:
 
     def num_channel(self) -> int:
         op = self.upstream_layers[0]
-        w = op.inputs[1].value
-        return int(w.shape[1] if (op.type in _LINEAR_TYPES and _trans_b(op) == 0) else w.shape[0])
+        return int(op.inputs[1].value.shape[channel_axis(op, False)])
 
     def equalize(self, value_threshold: float, including_weight: bool = True, weight_multiplier: float = 1.0,
                  including_act: bool = False, act_multiplier: float = 0.5, including_bias: bool = False,
@@ -232,6 +231,45 @@ def _weight(op) -> torch.Tensor:
     return w
 
 
+def channel_axis(op, downstream: bool) -> int:
+    """Which axis of the weight of ``op`` is the pair's channel: the OUTPUT channels of an upstream operation, the INPUT channels
+    of a downstream one.  A Conv stores [out, in / groups, k...], a Gemm [out, in] (``transB``) or [in, out], a MatMul [in, out]."""
+    if op.type in _LINEAR_TYPES: return int((_trans_b(op) != 0) == downstream)
+    return int(downstream)
+
+
+def endpoint_layout(op, downstream: bool, reference_key_order: bool = True) -> tuple:
+    """How the kernels address the weight of one endpoint of a pair: (weight variable, channel axis, the pair's channel count
+    as this weight tells it, key segment, apply geometry) with the segment (div, a, b, outer, stride, run) of
+    ``ppqhip_equalize_segment`` -- the elements the key of channel c is taken over -- and (run, inner, group_out) of
+    ``ppqhip_equalize_apply_job`` -- the scale every element takes.  The scale of a grouped downstream Conv is applied in the
+    natural (group, cin_local) order; ``reference_key_order`` lists its KEY rows in the reference's (cin_local, group) order
+    (what equalization and the channel split reproduce; SSD reads the natural order)."""
+    var = op.inputs[1]
+    w = var.value
+    if downstream and op.type not in _LINEAR_TYPES:                                # [G * og, ipg, k...]: channel g * ipg + i reads
+        G = int(op.attributes.get('group', 1))                                     # w[g * og : (g + 1) * og, i]
+        og, ipg, K = w.shape[0] // G, w.shape[1], w.numel() // (w.shape[0] * w.shape[1])
+        # the reference's key row of that channel is r = i * G + g, the natural one r = g * ipg + i
+        segment = (G, K, og * ipg * K, og, ipg * K, K) if reference_key_order else (ipg, og * ipg * K, K, og, ipg * K, K)
+        return var, 1, G * ipg, segment, (K, ipg, og)
+    if channel_axis(op, downstream) == 1:                                          # [rows, C]: channel c is column c
+        rows, C = w.shape
+        return var, 1, C, (1, 1, 0, rows, C, 1), (1, C, 0)
+    C = w.shape[0]                                                                 # [C, ...]: channel c is row c
+    epc = w.numel() // C
+    return var, 0, C, (1, epc, 0, 1, 0, epc), (epc, C, 0)
+
+
+def parameters_on_device(params: list, use_kernels: bool, who: str) -> bool:
+    """The kernel arm runs when it is wanted and every parameter is on the GPU; CPU parameters take the torch arm; a mixture is
+    refused."""
+    cuda = [isinstance(t, torch.Tensor) and t.is_cuda for t in params]
+    if not use_kernels or not any(cuda): return False
+    if not all(cuda): raise TypeError(f'{who}: the parameters of the pairs are partly on the GPU and partly not')
+    return True
+
+
 def pair_jobs(pair: EqualizationPair, scale: torch.Tensor, value_threshold: float, including_bias: bool, including_act: bool,
               bias_multiplier: float, act_multiplier: float, activations: Dict[str, torch.Tensor], num_channel: int = None):
     """(scale item, apply items) of one pair for ``ffi.equalize_scale_table`` / ``ffi.equalize_apply_table``.  ``num_channel``:
@@ -245,15 +283,10 @@ def pair_jobs(pair: EqualizationPair, scale: torch.Tensor, value_threshold: floa
     for op in pair.upstream_layers:
         _check_endpoint(op)
         w = _weight(op)
-        if op.type in _LINEAR_TYPES and _trans_b(op) == 0:                       # [in, out]: channel c is column c
-            need(w.shape[1], op)
-            segments.append((w, 1, 1, 0, w.shape[0], w.shape[1], 1, 1.0, False))
-            applies.append((w, scale, 1, C, 0, False))
-        else:                                                                      # [out, ...]: channel c is row c
-            need(w.shape[0], op)
-            epc = w.numel() // C
-            segments.append((w, 1, epc, 0, 1, 0, epc, 1.0, False))
-            applies.append((w, scale, epc, C, 0, False))
+        _, _, count, segment, apply = endpoint_layout(op, False)
+        need(count, op)
+        segments.append((w, *segment, 1.0, False))
+        applies.append((w, scale, *apply, False))
         if _has_bias(op):
             if not op.inputs[-1].is_parameter: raise ValueError(f'Bias of Op {op.name} is non-static.')
             b = op.inputs[-1].value
@@ -269,22 +302,11 @@ def pair_jobs(pair: EqualizationPair, scale: torch.Tensor, value_threshold: floa
         w = _weight(op)
         if op.type in _LINEAR_TYPES:
             if w.ndim != 2: raise ValueError(f'Unexpected Error, Parameter of MatMul {op.name} should be 2-d.')
-            if _trans_b(op) != 0:                                                  # [out, in]: channel c is column c
-                need(w.shape[1], op)
-                segments.append((w, 1, 1, 0, w.shape[0], w.shape[1], 1, 1.0, True))
-                applies.append((w, scale, 1, C, 0, True))
-            else:                                                                  # [in, out]: channel c is row c
-                need(w.shape[0], op)
-                segments.append((w, 1, w.shape[1], 0, 1, 0, w.shape[1], 1.0, True))
-                applies.append((w, scale, w.shape[1], C, 0, True))
-        else:
-            if w.ndim not in (3, 4, 5): raise ValueError(f'Unexpected dimension of weight of {op.name}.')
-            G = int(op.attributes.get('group', 1))
-            og, ipg, K = w.shape[0] // G, w.shape[1], w.numel() // (w.shape[0] * w.shape[1])
-            need(G * ipg, op)
-            # key row r = cin_local * G + g (the reference's order) reads w[g * og : (g + 1) * og, cin_local]
-            segments.append((w, G, K, og * ipg * K, og, ipg * K, K, 1.0, True))
-            applies.append((w, scale, K, ipg, og, True))                           # applied in (g, cin_local) order
+        elif w.ndim not in (3, 4, 5): raise ValueError(f'Unexpected dimension of weight of {op.name}.')
+        _, _, count, segment, apply = endpoint_layout(op, True)
+        need(count, op)
+        segments.append((w, *segment, 1.0, True))
+        applies.append((w, scale, *apply, True))
     return (scale, value_threshold, segments), applies
 
 
@@ -300,6 +322,8 @@ class LayerwiseEqualizationPass(QuantizationOptimizationPass):
     segments is chunked inside the library), ``channels``, and -- counted on the device over the LAST iteration's scales, one copy
     at the end -- ``scaled_channels`` (s != 1) and ``clipped_channels`` (s at 0.1 or 10).  ``keep_scales = True`` keeps a copy of
     every scale in ``scales[(iteration, pair index)]`` (an inspection aid: one device copy per pair instance)."""
+    PASS_NAME = 'PPQ Layerwise Equalization Pass'
+
     def __init__(self, iterations: int, value_threshold: float = 0.5, including_weight: bool = True,
                  weight_multiplier: float = 1.0, including_bias: bool = False, including_act: bool = False,
                  bias_multiplier: float = 0.5, act_multiplier: float = 0.5, interested_layers: List[str] = None,
@@ -323,7 +347,7 @@ class LayerwiseEqualizationPass(QuantizationOptimizationPass):
         self.pairs: List[EqualizationPair] = []
         self.activations: Dict[str, torch.Tensor] = {}      # {output variable name: per-channel |max|}, owned by the pass
         self.stats: Dict[str, int] = {}
-        super().__init__(name='PPQ Layerwise Equalization Pass')
+        super().__init__(name=self.PASS_NAME)
 
     def find_equalization_pair(self, graph, interested_operations: list) -> List[EqualizationPair]:
         return find_equalization_pair(graph, interested_operations, self.optimize_level)
@@ -387,9 +411,7 @@ class LayerwiseEqualizationPass(QuantizationOptimizationPass):
         for pair in pairs:
             for op in pair.operations: _check_endpoint(op)
         params = [v.value for pair in pairs for op in pair.operations for v in op.inputs[1:] if v.is_parameter]
-        on_device = self.use_kernels and bool(params) and all(isinstance(t, torch.Tensor) and t.is_cuda for t in params)
-        if self.use_kernels and not on_device and any(isinstance(t, torch.Tensor) and t.is_cuda for t in params):
-            raise TypeError('LayerwiseEqualizationPass: the parameters of the pairs are partly on the GPU and partly not')
+        on_device = parameters_on_device(params, self.use_kernels, 'LayerwiseEqualizationPass')
         self.stats = dict(pairs=len(pairs), levels=0, launches=0, channels=0, scaled_channels=0, clipped_channels=0)
         self.scales = {}
 

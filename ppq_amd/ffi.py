@@ -348,6 +348,14 @@ def _eq_tensor(t, what: str, k: int, dev):
     if not t.is_contiguous(): raise RuntimeError(_KERNEL_FAILURE + f'Equalization: item {k}: {what} is not contiguous')
 
 
+def _segment_record(segment, k: int, dev, what: str = 'Value') -> tuple:
+    """One ``ppqhip_equalize_segment`` of item ``k`` from (tensor, div, a, b, outer, stride, run, multiplier, downstream): the
+    tensor contiguous float32 on ``dev`` (its numel is the extent the library checks against)."""
+    t, div, a, b, outer, stride, run, mult, down = segment
+    _eq_tensor(t, what, k, dev)
+    return (t.data_ptr(), t.numel(), int(div), int(a), int(b), int(outer), int(stride), int(run), float(mult), 1 if down else 0)
+
+
 class EqualizeTable:
     """The host job table of one equalization launch, built once and launched every iteration: the jobs hold POINTERS and the
     pass changes its tensors in place.  Keeps the tensors (and the segment array the jobs point into) alive."""
@@ -370,17 +378,16 @@ def equalize_scale_table(items) -> EqualizeTable:
     describes them, ``tensor`` contiguous float32 on the same device (its numel is the extent the library checks against)."""
     jobs = np.zeros(len(items), dtype=_EQ_SCALE_JOB)
     segs = np.zeros(sum(len(it[2]) for it in items), dtype=_EQ_SEGMENT)
-    keep, at = [], 0
+    keep, records = [], []
     dev = items[0][0].device if items else None
     for k, (scale, threshold, segments) in enumerate(items):
         _eq_tensor(scale, 'Scale', k, dev)
         keep.append(scale)
-        jobs[k] = (segs.ctypes.data + at * _EQ_SEGMENT.itemsize, scale.data_ptr(), len(segments), scale.numel(), float(threshold), 0)
-        for t, div, a, b, outer, stride, run, mult, down in segments:
-            _eq_tensor(t, 'Value', k, dev)
-            keep.append(t)
-            segs[at] = (t.data_ptr(), t.numel(), int(div), int(a), int(b), int(outer), int(stride), int(run), float(mult), 1 if down else 0)
-            at += 1
+        jobs[k] = (segs.ctypes.data + len(records) * _EQ_SEGMENT.itemsize, scale.data_ptr(), len(segments), scale.numel(), float(threshold), 0)
+        for segment in segments:
+            records.append(_segment_record(segment, k, dev))
+            keep.append(segment[0])
+    segs[:] = records                                                     # one assignment: element-wise ones cost a microsecond each
     return EqualizeTable(jobs, segs, keep, lib.ppqhip_equalize_scale_multi)
 
 
@@ -430,19 +437,18 @@ def split_plan_table(items) -> EqualizeTable:
     channel count; segments as in :func:`equalize_scale_table`."""
     jobs = np.zeros(len(items), dtype=_SPLIT_PLAN_JOB)
     segs = np.zeros(sum(len(it[3]) for it in items), dtype=_EQ_SEGMENT)
-    keep, at = [], 0
+    keep, records = [], []
     dev = items[0][0].device if items else None
     for k, (src_of, count, threshold, segments) in enumerate(items):
         if src_of.numel() % 2: raise RuntimeError(_KERNEL_FAILURE + f'Channel split: item {k}: SrcOf must hold 2 x C entries')
         _i32(src_of, 'SrcOf', k, dev, src_of.numel()); _i32(count, 'Count', k, dev, 1)
         keep += [src_of, count]
-        jobs[k] = (segs.ctypes.data + at * _EQ_SEGMENT.itemsize, src_of.data_ptr(), count.data_ptr(), len(segments), src_of.numel() // 2,
+        jobs[k] = (segs.ctypes.data + len(records) * _EQ_SEGMENT.itemsize, src_of.data_ptr(), count.data_ptr(), len(segments), src_of.numel() // 2,
                    float(threshold), 0)
-        for t, div, a, b, outer, stride, run, mult, down in segments:
-            _eq_tensor(t, 'Value', k, dev)
-            keep.append(t)
-            segs[at] = (t.data_ptr(), t.numel(), int(div), int(a), int(b), int(outer), int(stride), int(run), float(mult), 1 if down else 0)
-            at += 1
+        for segment in segments:
+            records.append(_segment_record(segment, k, dev))
+            keep.append(segment[0])
+    segs[:] = records                                                     # one assignment: element-wise ones cost a microsecond each
     return EqualizeTable(jobs, segs, keep, lib.ppqhip_split_plan_multi)
 
 
@@ -513,10 +519,7 @@ def ssd_scales_multi(items) -> None:
         for what, t, n in (('ActRange', act, C), ('Scales', scales, 4 * C), ('Ranges', ranges, 2 * C)):
             _eq_tensor(t, what, k, dev)
             if t.numel() != n: raise RuntimeError(_KERNEL_FAILURE + f'SSD scales: item {k}: {what} must hold {n} floats')
-        segs = []
-        for what, (t, div, a, b, outer, stride, run) in (('First', first), ('Last', last)):
-            _eq_tensor(t, what, k, dev)
-            segs.append((t.data_ptr(), t.numel(), int(div), int(a), int(b), int(outer), int(stride), int(run), 1.0, 0))
+        segs = [_segment_record(tuple(seg) + (1.0, False), k, dev, what) for what, seg in (('First', first), ('Last', last))]
         jobs[k] = (segs[0], segs[1], act.data_ptr(), scales.data_ptr(), ranges.data_ptr(), C, float(ratio))
     with _DeviceOf(items[0][2]):
         _raise(lib.ppqhip_ssd_scales_multi(jobs.ctypes.data, len(items), _stream()))

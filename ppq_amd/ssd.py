@@ -25,7 +25,7 @@ import torch.nn.functional as F
 from .calibration import QuantizationOptimizationPass
 from .core import QuantizationProperty as P
 from .core import QuantizationStates, rounding_value, state_value
-from .equalization import _check_endpoint, _trans_b
+from .equalization import _check_endpoint, _trans_b, endpoint_layout, parameters_on_device
 from .qfunction import PPQLinearQuantFunction
 
 OPTIMIZATION_LAYERTYPE_CONFIG = {                                       # optim/ssd.py:24-26
@@ -108,34 +108,15 @@ def pair_geometry(pair: list):
     ``ppqhip_equalize_segment``.  None for a Gemm behind a flattened Conv (the reshape branches of :190-204 / :245-259), which
     the torch arm's expressions handle."""
     first, last = pair[0], pair[-1]
-    w1, w2 = first.parameters[0].value, last.parameters[0].value
-    if first.type == 'Gemm' and _trans_b(first) == 0:                              # [in, out]: channel c is column c
-        C = w1.shape[1]
-        seg1 = (w1, 1, 1, 0, w1.shape[0], w1.shape[1], 1)
-        applies = [(first.parameters[0], 1, C, 0, False)]
-    else:                                                                          # [out, ...]: channel c is row c
-        C = w1.shape[0]
-        epc = w1.numel() // C
-        seg1 = (w1, 1, epc, 0, 1, 0, epc)
-        applies = [(first.parameters[0], epc, C, 0, False)]
+    w1, _, C, seg1, apply1 = endpoint_layout(first, False)
+    w2, _, count, seg2, apply2 = endpoint_layout(last, True, reference_key_order=False)
+    applies = [(w1, *apply1, False)]
     if len(first.parameters) > 1: applies.append((first.parameters[1], 1, C, 0, False))
-    if last.type == 'Gemm':
-        if _trans_b(last) != 0:                                                    # [out, in]: channel c is column c
-            if w2.shape[1] != C: return None
-            seg2 = (w2, 1, 1, 0, w2.shape[0], w2.shape[1], 1)
-            applies.append((last.parameters[0], 1, C, 0, True))
-        else:                                                                      # [in, out]: channel c is row c
-            if w2.shape[0] != C: return None
-            seg2 = (w2, 1, w2.shape[1], 0, 1, 0, w2.shape[1])
-            applies.append((last.parameters[0], w2.shape[1], C, 0, True))
-    else:
-        G = int(last.attributes.get('group', 1))
-        og, ipg, K = w2.shape[0] // G, w2.shape[1], w2.numel() // (w2.shape[0] * w2.shape[1])
-        if G * ipg != C: raise ValueError(f'SSDEqualizationPass: {last.name} has {G * ipg} input channels, its pair has {C}')
-        # channel c = g * ipg + i, the natural order: reads w2[g * og : (g + 1) * og, i]
-        seg2 = (w2, ipg, og * ipg * K, K, og, ipg * K, K)
-        applies.append((last.parameters[0], K, ipg, og, True))
-    return C, seg1, seg2, applies
+    if count != C:
+        if last.type == 'Gemm': return None
+        raise ValueError(f'SSDEqualizationPass: {last.name} has {count} input channels, its pair has {C}')
+    applies.append((w2, *apply2, True))
+    return C, (w1.value, *seg1), (w2.value, *seg2), applies
 
 
 class SSDEqualizationPass(QuantizationOptimizationPass):
@@ -503,10 +484,7 @@ class SSDEqualizationPass(QuantizationOptimizationPass):
 
     def _on_device(self, pairs: List[list]) -> bool:
         params = [var.value for pair in pairs for op in (pair[0], pair[-1]) for var in op.parameters]
-        if not self.use_kernels or not params: return False
-        cuda = [isinstance(t, torch.Tensor) and t.is_cuda for t in params]
-        if not any(cuda): return False
-        if not all(cuda): raise TypeError('SSDEqualizationPass: the parameters of the pairs are partly on the GPU and partly not')
+        if not parameters_on_device(params, self.use_kernels, 'SSDEqualizationPass'): return False
         for pair in pairs:
             for op in (pair[0], pair[-1]):
                 for var in op.parameters:
