@@ -663,6 +663,31 @@ int ppqhip_stat_moments_multi(const ppqhip_stat_job* jobs, int num_jobs, void* s
  *   lo = min, hi = max; lo == hi: lo - 1, hi + 1 (torch.histc);  pos = ((x - lo) * bins) / (hi - lo);  bin = min((int)pos, bins - 1) */
 int ppqhip_stat_shape_multi(const ppqhip_stat_job* jobs, int num_jobs, void* stream);
 
+/* OCP Microscaling (MX) block-scaled fake quant (ppq_amd/mx.py; ADDED under ABI 4 like the entries above) -- */
+/* The tensor is addressed as contiguous [outer, axis_len, inner]; a block is up to 32 consecutive elements along the middle axis
+ * (the last block of an axis is short when axis_len % 32 != 0 and uses only its own elements).  Per block:
+ *   amax = max |v| over the FINITE elements;  se = clamp(floor(log2(amax)) - emax, -127, 127), -127 when amax == 0;  X = 2^se
+ *   y = cast(v / X) * X;  cast = the nearest element value of the format (subnormals included), ties to the even encoding,
+ *   saturating at +- the largest normal;  zero keeps its sign;  NaN is copied bit for bit;  +-Inf -> +- largest normal * X
+ *   scale_codes (optional, NULL: not written): the E8M0 code se + 127 of every block, uint8 [outer, ceil(axis_len / 32), inner]
+ * emax / largest normal: E4M3 8 / 448, E5M2 15 / 57344, E3M2 4 / 28, E2M3 2 / 7.5, E2M1 2 / 6, MXINT8 0 / 127/64 (k / 64, |k| <= 127).
+ * Every step is exact in float32: two calls, and any two implementations of this contract, give identical bits.  y == x (in place)
+ * is allowed; any other overlap of an output with an input or another output is refused.  Sizes of 0 launch nothing. */
+enum { PPQHIP_MXFP8_E4M3 = 0, PPQHIP_MXFP8_E5M2 = 1, PPQHIP_MXFP6_E3M2 = 2, PPQHIP_MXFP6_E2M3 = 3, PPQHIP_MXFP4_E2M1 = 4,
+       PPQHIP_MXINT8 = 5 };
+int ppqhip_mx_fq(const float* x, float* y, uint8_t* scale_codes, int64_t outer, int64_t axis_len, int64_t inner, int format,
+                 void* stream);
+/* many tensors, one launch: every job exactly as ppqhip_mx_fq.  `jobs` is a HOST array that is copied into the kernel arguments
+ * (chunked when it does not fit one launch): no upload, no synchronisation, no atomics, capturable into a HIP graph. */
+typedef struct ppqhip_mx_job {
+    const float* x;
+    float* y;
+    uint8_t* scale_codes;    /* or NULL */
+    int64_t outer, axis_len, inner;
+    int32_t format, reserved;
+} ppqhip_mx_job;
+int ppqhip_mx_fq_multi(const ppqhip_mx_job* jobs, int num_jobs, void* stream);
+
 /* profiling aid used by bench.py: when enabled, every kernel launch made through this library
  * on this thread is bracketed by hipEvents on its own stream; ppqhip_prof_collect() synchronises
  * those events and returns, per kernel id, launches / total ms / total algorithmic bytes. */

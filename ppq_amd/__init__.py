@@ -8,7 +8,8 @@ from .core import (PPQ_CONFIG, FloatingQuantizationConfig, LinearQuantizationCon
                    QuantizationProperty, QuantizationStates, RoundingPolicy, TensorQuantizationConfig)
 from .ffi import (CUDA, CUDA_COMPLIER, ENABLE_CUDA_KERNEL, HIP_EXTENSION, install_into_ppq, install_plugins_into_ppq,
                   uninstall_from_ppq)
+from .mx import MXDelegator, MXFormat, mx_fake_quant, quantize_graph_mx
 
-__all__ = ['CUDA', 'CUDA_COMPLIER', 'ENABLE_CUDA_KERNEL', 'HIP_EXTENSION', 'install_into_ppq', 'install_plugins_into_ppq', 'uninstall_from_ppq', 'PPQ_CONFIG', 'RoundingPolicy',
+__all__ = ['MXFormat', 'MXDelegator', 'mx_fake_quant', 'quantize_graph_mx','CUDA', 'CUDA_COMPLIER', 'ENABLE_CUDA_KERNEL', 'HIP_EXTENSION', 'install_into_ppq', 'install_plugins_into_ppq', 'uninstall_from_ppq', 'PPQ_CONFIG', 'RoundingPolicy',
            'QuantizationProperty', 'QuantizationPolicy', 'QuantizationStates', 'TensorQuantizationConfig',
            'LinearQuantizationConfig', 'FloatingQuantizationConfig']

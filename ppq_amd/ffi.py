@@ -820,6 +820,93 @@ class FloatingQuantizePlan:
         return self._outs
 
 
+# ---- OCP Microscaling (include/ppq_hip.h ppqhip_mx_fq / ppqhip_mx_fq_multi) ----
+_MX_JOB = np.dtype([('x', '<u8'), ('y', '<u8'), ('scale_codes', '<u8'), ('outer', '<i8'), ('axis_len', '<i8'), ('inner', '<i8'),
+                    ('format', '<i4'), ('reserved', '<i4')])
+MX_BLOCK = 32
+MX_FORMATS = {'MXFP8_E4M3': 0, 'MXFP8_E5M2': 1, 'MXFP6_E3M2': 2, 'MXFP6_E2M3': 3, 'MXFP4_E2M1': 4, 'MXINT8': 5}      # PPQHIP_MX*
+
+
+def mx_format_id(format) -> int:
+    """The library's id of an MX format given as ``ppq_amd.mx.MXFormat``, its name or the id itself."""
+    key = getattr(format, 'name', format)
+    if isinstance(key, str) and key in MX_FORMATS: return MX_FORMATS[key]
+    if isinstance(key, int) and not isinstance(key, bool) and key in MX_FORMATS.values(): return key
+    raise ValueError(f'unknown MX format {format!r}: expected one of {", ".join(MX_FORMATS)}')
+
+
+def _mx_axis(ndim: int, axis: int) -> int:
+    if not isinstance(axis, int) or not -ndim <= axis < ndim:
+        raise RuntimeError(_KERNEL_FAILURE + f'axis {axis} out of range for a {ndim}-d tensor')
+    return axis % ndim
+
+
+def _mx_channels_last(t: torch.Tensor, axis: int) -> bool:
+    """A dense 4-D channels-last tensor quantised along its channels: the blocks are contiguous in storage as they are."""
+    return t.dim() == 4 and axis == 1 and not t.is_contiguous() and t.is_contiguous(memory_format=torch.channels_last)
+
+
+def _mx_geometry(t: torch.Tensor, axis: int):
+    """(outer, axis_len, inner) of the storage of ``t`` (contiguous, or channels-last with axis 1) and the shape of its scale codes."""
+    shape = list(t.shape)
+    codes = shape[:axis] + [(shape[axis] + MX_BLOCK - 1) // MX_BLOCK] + shape[axis + 1:]
+    if _mx_channels_last(t, axis): return t.numel() // shape[1], shape[1], 1, codes
+    inner = 1
+    for d in shape[axis + 1:]: inner *= int(d)
+    return t.numel() // (shape[axis] * inner), shape[axis], inner, codes
+
+
+def _mx_dense(t: torch.Tensor, axis: int) -> torch.Tensor:
+    return t if t.is_contiguous() or _mx_channels_last(t, axis) else t.contiguous()
+
+
+def _mx_codes_like(v: torch.Tensor, axis: int, shape) -> torch.Tensor:
+    fmt = torch.channels_last if _mx_channels_last(v, axis) else torch.contiguous_format
+    return torch.empty(shape, dtype=torch.uint8, device=v.device, memory_format=fmt)
+
+
+class MXQuantizePlan:
+    """MX fake-quant of MANY tensors with ONE launch per call (``ppqhip_mx_fq_multi``): the MX weights of a graph.  Built once from
+    ``(value, format, axis)`` items; ``run()`` re-quantises all of them into one resident arena and returns views shaped like the
+    inputs -- bits identical to ``CUDA.MXQuantize`` per item.  The job table travels in the kernel arguments and holds POINTERS to
+    the callers' tensors: in-place updates are seen by later runs, a REPLACED tensor needs a new plan.  A value that is not dense
+    (contiguous, or 4-D channels-last along axis 1) would need a private copy that later updates never reach: refused
+    (``accepts()``).  ``with_codes``: also keep every item's E8M0 scale codes (``codes``)."""
+    @ staticmethod
+    def accepts(value, axis) -> bool:
+        return value.dim() > 0 and -value.dim() <= axis < value.dim() and _mx_dense(value, axis % value.dim()) is value
+
+    def __init__(self, items, with_codes: bool = False):
+        if not items: raise ValueError('MXQuantizePlan needs at least one item')
+        dev = items[0][0].device
+        total = 0
+        for value, format, axis in items:
+            _f32(value, 'Value')
+            if value.device != dev: raise RuntimeError(_KERNEL_FAILURE + 'MXQuantizePlan: every tensor must live on one device')
+            if not MXQuantizePlan.accepts(value, _mx_axis(value.dim(), axis)):
+                raise RuntimeError(_KERNEL_FAILURE + 'MXQuantizePlan: value must be dense in storage order (a private copy would go stale); see accepts()')
+            total += (value.numel() + 3) // 4 * 4
+        self._arena = torch.empty(total, dtype=torch.float32, device=dev)
+        self._jobs = np.zeros(len(items), dtype=_MX_JOB)
+        self._keep, self._outs, self.codes = [], [], []
+        at = 0
+        for k, (v, format, axis) in enumerate(items):
+            axis = _mx_axis(v.dim(), axis)
+            outer, length, inner, codes_shape = _mx_geometry(v, axis)
+            out = self._arena[at: at + v.numel()].as_strided(v.shape, v.stride())     # same memory format as the input
+            at += (v.numel() + 3) // 4 * 4                                             # every output starts 16-B aligned
+            codes = _mx_codes_like(v, axis, codes_shape) if with_codes else None
+            self._keep.append(v); self._outs.append(out); self.codes.append(codes)
+            self._jobs[k] = (v.data_ptr(), out.data_ptr(), codes.data_ptr() if with_codes else 0, outer, length, inner,
+                             mx_format_id(format), 0)
+        self.bytes = 8 * sum(v.numel() for v in self._keep)
+
+    def run(self) -> List[torch.Tensor]:
+        with _DeviceOf(self._arena):
+            _raise(lib.ppqhip_mx_fq_multi(self._jobs.ctypes.data, len(self._jobs), _stream()))
+        return self._outs
+
+
 class _HipExtension:
     """Same callables as the pybind module built from ppq/csrc/export.cc:8-34."""
     __name__ = 'PPQ_Hip_Impls'
@@ -1858,6 +1945,31 @@ class CUDA:
     @ staticmethod
     def MseSearch(histogram, hist_scale, min_value, quant_min: int, quant_max: int, symmetrical: bool):
         return HIP_EXTENSION.MSE_Search(histogram, hist_scale, min_value, quant_min, quant_max, symmetrical)
+
+    @ staticmethod
+    def MXQuantize(tensor, format, axis: int, block_size: int = MX_BLOCK, scale_codes=None):
+        """OCP Microscaling fake quant (MI355X-native; the contract is DESIGN.md section 9): blocks of 32 along ``axis`` share one
+        power-of-two scale, elements are cast to ``format`` (``ppq_amd.mx.MXFormat``, its name or id).  ``scale_codes``: an
+        optional uint8 tensor with the input's shape, the axis replaced by ceil(len / 32), that receives the E8M0 codes.
+        A 4-D channels-last tensor quantised along axis 1 is read in storage order; any other non-contiguous one is copied."""
+        if block_size != MX_BLOCK: raise ValueError(f'MX block size is {MX_BLOCK}, got {block_size}')
+        fmt = mx_format_id(format)
+        _f32(tensor, 'Value')
+        axis = _mx_axis(tensor.dim(), axis)
+        v = _mx_dense(tensor, axis)
+        outer, length, inner, codes_shape = _mx_geometry(v, axis)
+        codes = None
+        if scale_codes is not None:
+            if not (isinstance(scale_codes, torch.Tensor) and scale_codes.dtype == torch.uint8 and list(scale_codes.shape) == codes_shape):
+                raise RuntimeError(_KERNEL_FAILURE + f'scale_codes must be a uint8 tensor of shape {codes_shape}')
+            if scale_codes.device != v.device: raise RuntimeError(_KERNEL_FAILURE + 'scale_codes is on another device')
+            codes = scale_codes if scale_codes.stride() == _mx_codes_like(v, axis, codes_shape).stride() else _mx_codes_like(v, axis, codes_shape)
+        out = torch.empty_like(v)
+        with _DeviceOf(v):
+            _raise(lib.ppqhip_mx_fq(v.data_ptr(), out.data_ptr(), codes.data_ptr() if codes is not None else 0, outer, length, inner,
+                                    fmt, _stream()))
+        if codes is not None and codes is not scale_codes: scale_codes.copy_(codes)
+        return out
 
     @ staticmethod
     def Sync():

@@ -1,0 +1,272 @@
+"""OCP Microscaling (MX) block-scaled fake quant: MXFP8 (E4M3 / E5M2), MXFP6 (E3M2 / E2M3), MXFP4 (E2M1) and MXINT8.
+
+32 consecutive values along one axis share a power-of-two E8M0 scale taken from the block itself -- nothing is calibrated.  The
+reference has no MX: the contract (restated by ``tests/mx_reference.py``) is this package's own.  Per block
+
+    amax = max |v| over the finite elements;  se = clamp(floor(log2(amax)) - emax, -127, 127), -127 when amax == 0;  X = 2^se
+    y = cast(v / X) * X       cast: nearest element value, ties to the even encoding, saturating at the largest normal
+
+NaN passes through, +-Inf saturates, zero keeps its sign, float32 subnormals are honoured.  Every step is exact in float32, so the
+HIP kernels (``ppq_amd/csrc/mx.hip``, ``use_kernels=True``) and the torch restatement below (``use_kernels=False``, any device)
+give identical bits.
+
+``quantize_graph_mx`` puts MX on the inputs of Conv / Gemm / MatMul of a harness graph through the executor's delegator seam
+(``TorchExecutor.register_quantize_delegate``): ``MXDelegator`` follows the reference's delegator protocol
+(``delegator(tensor, config)``, ppq/executor/torch.py:296-323) and works in its executor unchanged.
+"""
+from enum import Enum
+from typing import List, Optional
+
+import torch
+from torch.autograd import Function
+
+from .core import (FloatingQuantizationConfig, LinearQuantizationConfig, QuantizationStates)
+from .ffi import CUDA, MX_BLOCK, MX_FORMATS, MXQuantizePlan, mx_format_id
+
+# name -> (exponent bits, mantissa bits, smallest normal exponent, emax, largest normal); MXINT8: k / 64 with |k| <= 127
+_SPEC = {
+    'MXFP8_E4M3': (4, 3, -6, 8, 448.0),
+    'MXFP8_E5M2': (5, 2, -14, 15, 57344.0),
+    'MXFP6_E3M2': (3, 2, -2, 4, 28.0),
+    'MXFP6_E2M3': (2, 3, 0, 2, 7.5),
+    'MXFP4_E2M1': (2, 1, 0, 2, 6.0),
+    'MXINT8': (0, 6, None, 0, 127.0 / 64.0),
+}
+
+
+class MXFormat(Enum):
+    """The element formats of OCP MX v1.0; the value is the id the HIP library knows the format by."""
+    MXFP8_E4M3 = MX_FORMATS['MXFP8_E4M3']
+    MXFP8_E5M2 = MX_FORMATS['MXFP8_E5M2']
+    MXFP6_E3M2 = MX_FORMATS['MXFP6_E3M2']
+    MXFP6_E2M3 = MX_FORMATS['MXFP6_E2M3']
+    MXFP4_E2M1 = MX_FORMATS['MXFP4_E2M1']
+    MXINT8 = MX_FORMATS['MXINT8']
+
+    @ property
+    def exponent_bits(self) -> int: return _SPEC[self.name][0]
+
+    @ property
+    def mantissa_bits(self) -> int: return _SPEC[self.name][1]
+
+    @ property
+    def emax(self) -> int: return _SPEC[self.name][3]
+
+    @ property
+    def max_normal(self) -> float: return _SPEC[self.name][4]
+
+    @ property
+    def is_float(self) -> bool: return self is not MXFormat.MXINT8
+
+    @ classmethod
+    def of(cls, format) -> 'MXFormat':
+        """``format`` as a member: a member, its name, or the library's id."""
+        if isinstance(format, cls): return format
+        return cls(mx_format_id(format))
+
+
+def _bits_to_float(bits: torch.Tensor) -> torch.Tensor:
+    return bits.to(torch.int32).view(torch.float32)
+
+
+def _pow2(biased: torch.Tensor) -> torch.Tensor:
+    """2^(biased - 127) for 0 <= biased <= 254 (2^-127 is the subnormal 0x00400000)."""
+    return _bits_to_float(torch.where(biased > 0, biased << 23, torch.full_like(biased, 0x00400000)))
+
+
+def _mx_torch(tensor: torch.Tensor, format: MXFormat, axis: int, scale_codes: Optional[torch.Tensor]) -> torch.Tensor:
+    """The contract in torch ops, on the tensor's device: integer arithmetic on the float32 patterns, exact float32 products."""
+    _, m, emin, emax, max_normal = _SPEC[format.name]
+    length = tensor.shape[axis]
+    nb = (length + MX_BLOCK - 1) // MX_BLOCK
+    x = tensor.movedim(axis, -1)
+    lead = list(x.shape[:-1])
+    x = x.contiguous()
+    if nb * MX_BLOCK != length:                       # zeros take no part in amax; the padding is cut off again below
+        x = torch.nn.functional.pad(x, (0, nb * MX_BLOCK - length))
+    x = x.reshape(lead + [nb, MX_BLOCK])
+    bits = x.view(torch.int32)
+    mag = bits & 0x7fffffff
+    amax = torch.where(mag < 0x7f800000, mag, torch.zeros_like(mag)).amax(dim=-1, keepdim=True)
+    code = ((amax >> 23) - emax).clamp_(min=0)
+    scale, inv = _pow2(code), _pow2(254 - code)
+    u = x * inv
+    ubits = u.view(torch.int32)
+    umag = ubits & 0x7fffffff
+    sign = ubits & -0x80000000
+    max_bits = int(torch.tensor(max_normal, dtype=torch.float32).view(torch.int32))
+    if format.is_float:
+        shift = 23 - m
+        finite = torch.where(umag > 0x7f800000, torch.zeros_like(umag), umag)                         # a NaN pattern plus the rounding add would wrap
+        normal = (finite + ((1 << (shift - 1)) - 1) + ((finite >> shift) & 1)) & ~((1 << shift) - 1)  # RNE on the mantissa
+        grid = (torch.round(_bits_to_float(umag) * 2.0 ** (m - emin)) * 2.0 ** (emin - m)).view(torch.int32)
+        r = torch.where(umag < ((emin + 127) << 23), grid, normal)
+    else:
+        r = (torch.round(_bits_to_float(umag) * 64.0) * 0.015625).view(torch.int32)
+    r = torch.minimum(r, torch.full_like(r, max_bits))
+    y = _bits_to_float(r | sign) * scale
+    y = torch.where(umag > 0x7f800000, x, y)          # NaN: the input's own bits
+    y = y.reshape(lead + [nb * MX_BLOCK])[..., :length].movedim(-1, axis)
+    if scale_codes is not None:
+        scale_codes.copy_(code.reshape(lead + [nb]).movedim(-1, axis).to(torch.uint8))
+    return y.contiguous()
+
+
+def _check_codes(tensor: torch.Tensor, axis: int, scale_codes) -> None:
+    if scale_codes is None: return
+    want = list(tensor.shape)
+    want[axis] = (want[axis] + MX_BLOCK - 1) // MX_BLOCK
+    if not (isinstance(scale_codes, torch.Tensor) and scale_codes.dtype == torch.uint8 and list(scale_codes.shape) == want):
+        raise RuntimeError(f'scale_codes must be a uint8 tensor of shape {want}')
+
+
+class _MXFakeQuant(Function):
+    @ staticmethod
+    def forward(ctx, tensor, format, axis, scale_codes, use_kernels):
+        if use_kernels: return CUDA.MXQuantize(tensor, format, axis, MX_BLOCK, scale_codes)
+        return _mx_torch(tensor, format, axis, scale_codes)
+
+    @ staticmethod
+    def backward(ctx, dy: torch.Tensor):
+        return dy, None, None, None, None
+
+
+def mx_fake_quant(tensor: torch.Tensor, format, axis: int = -1, scale_codes: torch.Tensor = None, use_kernels: bool = True) -> torch.Tensor:
+    """MX fake quant of ``tensor`` with blocks of 32 along ``axis``; straight-through backward (``dy`` as it is).
+    ``scale_codes``: optional uint8 tensor (the input's shape, the axis replaced by ceil(len / 32)) that receives the E8M0 codes.
+    ``use_kernels=True``: the HIP kernels (the tensor must be on the GPU).  ``False``: the torch restatement of the same contract
+    on whatever device the tensor lives on -- identical bits."""
+    format = MXFormat.of(format)
+    if not isinstance(tensor, torch.Tensor): raise TypeError(f'expected a torch.Tensor, got {type(tensor)}')
+    if tensor.dtype != torch.float32: raise RuntimeError('Kernel Failure, Invalid dtype of Input tensor: Value(Expect to be FP32)')
+    if tensor.dim() == 0 or not isinstance(axis, int) or not -tensor.dim() <= axis < tensor.dim():
+        raise RuntimeError(f'Kernel Failure, axis {axis} out of range for a {tensor.dim()}-d tensor')
+    if tensor.numel() == 0: raise RuntimeError('Kernel Failure, Tensor is empty: Value')
+    axis %= tensor.dim()
+    _check_codes(tensor, axis, scale_codes)
+    return _MXFakeQuant.apply(tensor, format, axis, scale_codes, use_kernels)
+
+
+def _activated(config) -> bool:
+    return config is None or QuantizationStates.is_activated(config.state)
+
+
+class MXWeightGroup:
+    """The MX weights of one graph as ONE launch (``ffi.MXQuantizePlan`` -> ``ppqhip_mx_fq_multi``), shared by their delegators.
+    The arena is refilled when a member is asked for and ITS weight is not the one the arena was filled from: another tensor
+    (``data_ptr``, shape or strides changed: the plan is rebuilt) or the same one written in place (``_version``).  One refill
+    serves every member, so a forward over unchanged weights launches nothing, and a step that updated all of them launches once."""
+    def __init__(self, members):
+        self.members = members                      # [(variable, format, axis)]
+        self.plan = None
+        self.stamps: List[tuple] = [None] * len(members)
+        self.outputs = None
+        self.launches = 0
+
+    @ staticmethod
+    def eligible(var, axis: int) -> bool:
+        v = var.value
+        return (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float32 and v.numel() > 0 and not v.requires_grad
+                and MXQuantizePlan.accepts(v, axis))
+
+    @ staticmethod
+    def _stamp(v: torch.Tensor) -> tuple:
+        return (v.data_ptr(), v._version, tuple(v.shape), v.stride())
+
+    def output(self, slot: int) -> torch.Tensor:
+        if self.stamps[slot] != self._stamp(self.members[slot][0].value): self.refresh()
+        return self.outputs[slot]
+
+    def refresh(self) -> None:
+        stamps = [self._stamp(var.value) for var, _, _ in self.members]
+        same = self.plan is not None and all(a is not None and a[0] == b[0] and a[2:] == b[2:] for a, b in zip(self.stamps, stamps))
+        if not same: self.plan = MXQuantizePlan([(var.value, fmt, axis) for var, fmt, axis in self.members])
+        self.outputs = self.plan.run()
+        self.stamps = stamps
+        self.launches += 1
+
+
+class MXDelegator:
+    """``delegator(tensor, config)`` for ``TorchExecutor.register_quantize_delegate`` (this package's harness and the reference's
+    executor alike): MX fake quant of the tensor with blocks along ``axis``.  A config that is not activated (a dequantised
+    operation) passes the tensor through, as the default quantize function does."""
+    def __init__(self, format, axis: int, use_kernels: bool = True):
+        self.format = MXFormat.of(format)
+        self.axis = axis
+        self.use_kernels = use_kernels
+        self.group, self.slot, self.var = None, None, None     # set by quantize_graph_mx: this weight rides the graph's one launch
+
+    def __call__(self, tensor: torch.Tensor, config=None) -> torch.Tensor:
+        if not _activated(config): return tensor
+        if self.group is not None and tensor is self.var.value and MXWeightGroup.eligible(self.var, self.axis):
+            return self.group.output(self.slot)
+        return mx_fake_quant(tensor, self.format, self.axis, use_kernels=self.use_kernels)
+
+
+def _mx_config(format: MXFormat, device):
+    """An ACTIVATED config that describes the element format to every report that reads configs; scale 1, offset 0 (the block
+    scales live in the data, not in the config)."""
+    if format.is_float:
+        c = FloatingQuantizationConfig(exponent=format.exponent_bits, mantissa=format.mantissa_bits, quant_min=-format.max_normal,
+                                       quant_max=format.max_normal, calibration='mx')
+    else:
+        c = LinearQuantizationConfig(symmetrical=True, power_of_2=True, quant_min=-127, quant_max=127, num_of_bits=8, calibration='mx')
+    c.scale = torch.ones(1, dtype=torch.float32, device=device)
+    c.offset = torch.zeros(1, dtype=torch.float32, device=device)
+    c.state = QuantizationStates.ACTIVATED
+    c.detail['MX_FORMAT'] = format.name
+    return c
+
+
+MX_OPERATIONS = ('Conv', 'Gemm', 'MatMul')
+
+
+def mx_block_axis(op_type: str, input_index: int) -> int:
+    """The axis MX blocks run along for input ``input_index`` of a Conv / Gemm / MatMul: the reduction axis, along which the scaled
+    MFMA shares a scale.  Conv: channels (axis 1) of activation and weight; Gemm: the last axis of the activation and of the
+    harness's [out, in] weight; MatMul: the last axis of the left operand, the second to last of the right one (axis 0 of a 2-D
+    [in, out] weight)."""
+    if op_type == 'Conv': return 1
+    if op_type == 'MatMul' and input_index == 1: return -2
+    return -1
+
+
+def quantize_graph_mx(graph, executor, weight_format, activation_format, operations=None, use_kernels: bool = True) -> dict:
+    """The policy of ``harness.quantize_graph_fp8`` with MX formats: only the inputs of Conv / Gemm / MatMul are quantised, weights
+    with ``weight_format`` and activations with ``activation_format``, blocks along the reduction
+    axis (``mx_block_axis``); bias and everything else stay FP32.  Each quantised input gets an ACTIVATED config and an
+    ``MXDelegator`` registered on ``executor``; with ``use_kernels`` all weights share one ``MXWeightGroup``.  ``operations``: names
+    of the operations to quantise (default: all).  Returns config -> delegator."""
+    from .harness import OperationQuantizationConfig, QuantableOperation
+    wfmt, afmt = MXFormat.of(weight_format), MXFormat.of(activation_format)
+    device = getattr(executor, '_device', 'cuda')
+    delegators, weights = {}, []
+
+    def fp32():
+        c = LinearQuantizationConfig()
+        c.state = QuantizationStates.FP32
+        return c
+
+    for name, op in list(graph.operations.items()):
+        if operations is not None and name not in operations: continue
+        in_cfgs = []
+        for i, v in enumerate(op.inputs):
+            fmt = None
+            if op.type in MX_OPERATIONS and i < 2: fmt = wfmt if v.is_parameter else afmt
+            if fmt is None:
+                in_cfgs.append(fp32())
+                continue
+            c = _mx_config(fmt, device)
+            d = MXDelegator(fmt, mx_block_axis(op.type, i), use_kernels)
+            if v.is_parameter: weights.append((d, v))
+            in_cfgs.append(c)
+            delegators[c] = d
+        qop = QuantableOperation(op, OperationQuantizationConfig(in_cfgs, [fp32() for _ in op.outputs]))
+        for v in qop.inputs: v.dest_ops[v.dest_ops.index(op)] = qop
+        for v in qop.outputs: v.source_op = qop
+        graph.operations[name] = qop
+    for c, d in delegators.items(): executor.register_quantize_delegate(c, d)
+    if use_kernels and weights:
+        group = MXWeightGroup([(v, d.format, d.axis) for d, v in weights])
+        for k, (d, v) in enumerate(weights): d.group, d.slot, d.var = group, k, v
+    return delegators
