@@ -688,6 +688,47 @@ typedef struct ppqhip_mx_job {
 } ppqhip_mx_job;
 int ppqhip_mx_fq_multi(const ppqhip_mx_job* jobs, int num_jobs, void* stream);
 
+/* Packed MX export (ppq_amd/mx.py mx_quantize / mx_dequantize; ADDED under ABI 4) ------------------ */
+/* Blocks, amax, shared exponent, cast and saturation are exactly those of ppqhip_mx_fq.  x is contiguous [outer, axis_len, inner];
+ * the packed tensor is two uint8 arrays with the BLOCK AXIS LAST and every block at full size (nb = ceil(axis_len / 32)):
+ *   scales    [outer, inner, nb]       the E8M0 code of each block (what ppqhip_mx_fq writes to scale_codes, transposed)
+ *   elements  [outer, inner, nb * B]   B bytes per block: 32 (MXFP8, MXINT8), 24 (MXFP6), 16 (MXFP4); the elements a short last
+ *                                      block lacks are encoded as +0
+ * Element codes (OCP MX v1.0): floats are sign | exponent | mantissa with bias 7 (E4M3), 15 (E5M2), 3 (E3M2), 1 (E2M3), 1 (E2M1),
+ * subnormals as the format defines them; MXINT8 is the two's-complement int8 k of the value k / 64.  Element i of a block occupies
+ * bits [i * w, i * w + w) (w = 8, 6, 4) of the block's bytes read as one little-endian bit string: FP4 element 2i is the low nibble
+ * of byte i, four FP6 elements make three bytes.  These are dense layouts; operand swizzles of particular MFMA instructions are
+ * not produced.
+ *   +-Inf saturates to the largest normal (the E5M2 Inf codes are never written); zero keeps its sign in the float formats, MXINT8
+ *   writes 0;  NaN in MXFP8: the element is S.1111.111 (E4M3) / S.11111.11 (E5M2) with the input's sign, the scale comes from the
+ *   finite elements;  NaN in MXFP6 / MXFP4 / MXINT8 (no NaN encoding): the block's scale is 0xFF (the E8M0 NaN) and its element
+ *   bytes are zero.
+ * Unpack: y = value(code) * 2^(scale - 127) in float32, the tail padding dropped, y contiguous [outer, axis_len, inner].  Scale 0xFF
+ * makes the whole block NaN, an MXFP8 NaN code gives NaN, an E5M2 Inf code +-Inf; every NaN is 0x7fc00000, in MXFP8 with the
+ * element's sign bit on top.  For inputs without NaN, unpack(pack(x)) has the bits of ppqhip_mx_fq(x) (MXINT8: -0 becomes +0).
+ * All three pointers are required; no output may overlap an input or another output (there is no in-place form).  Sizes of 0
+ * launch nothing.  The _multi forms take a HOST array that travels in the kernel arguments, as ppqhip_mx_fq_multi does. */
+int ppqhip_mx_pack(const float* x, uint8_t* elements, uint8_t* scales, int64_t outer, int64_t axis_len, int64_t inner, int format,
+                   void* stream);
+typedef struct ppqhip_mx_pack_job {
+    const float* x;
+    uint8_t* elements;
+    uint8_t* scales;
+    int64_t outer, axis_len, inner;
+    int32_t format, reserved;
+} ppqhip_mx_pack_job;
+int ppqhip_mx_pack_multi(const ppqhip_mx_pack_job* jobs, int num_jobs, void* stream);
+int ppqhip_mx_unpack(const uint8_t* elements, const uint8_t* scales, float* y, int64_t outer, int64_t axis_len, int64_t inner,
+                     int format, void* stream);
+typedef struct ppqhip_mx_unpack_job {
+    const uint8_t* elements;
+    const uint8_t* scales;
+    float* y;
+    int64_t outer, axis_len, inner;
+    int32_t format, reserved;
+} ppqhip_mx_unpack_job;
+int ppqhip_mx_unpack_multi(const ppqhip_mx_unpack_job* jobs, int num_jobs, void* stream);
+
 /* profiling aid used by bench.py: when enabled, every kernel launch made through this library
  * on this thread is bracketed by hipEvents on its own stream; ppqhip_prof_collect() synchronises
  * those events and returns, per kernel id, launches / total ms / total algorithmic bytes. */

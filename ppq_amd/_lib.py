@@ -111,6 +111,10 @@ PROTOTYPES = {
     'ppqhip_stat_shape_multi': (c_int, [c_vp, c_int, c_vp]),
     'ppqhip_mx_fq': (c_int, [c_f32p, c_f32p, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),
     'ppqhip_mx_fq_multi': (c_int, [c_vp, c_int, c_vp]),
+    'ppqhip_mx_pack': (c_int, [c_f32p, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),
+    'ppqhip_mx_pack_multi': (c_int, [c_vp, c_int, c_vp]),
+    'ppqhip_mx_unpack': (c_int, [c_vp, c_vp, c_f32p, c_i64, c_i64, c_i64, c_int, c_vp]),
+    'ppqhip_mx_unpack_multi': (c_int, [c_vp, c_int, c_vp]),
     'ppqhip_prof_enable': (c_int, [c_int]),
     'ppqhip_prof_collect': (c_int, [ctypes.POINTER(ProfEntry), c_int]),
     'ppqhip_prof_event_overhead_us': (ctypes.c_double, [c_vp, c_int]),

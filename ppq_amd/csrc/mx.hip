@@ -16,52 +16,15 @@
 //   rows1   inner == 1 otherwise: one element per lane, 32 lanes per block, five shuffles -- the same arithmetic
 //   strided inner > 1: one lane per (outer, block, inner) triple, numbered with inner fastest, so that each of the 32 loads of a
 //           wave is coalesced along inner and a wave stays full when inner is small (9 for a 3x3 weight)
+// The description of a format, the scale code and the rounding of an element live in mx_common.hpp, shared with mx_pack.hip.
 #include "common.hpp"
 #include "job_table.hpp"
+#include "mx_common.hpp"
 
 namespace ppqhip {
 namespace {
 
-struct MxFmt {                 // 28 B
-    uint32_t emax;             // the element format's largest exponent: the shared exponent is exponent(amax) - emax
-    uint32_t shift;            // 23 - mantissa bits: float32 mantissa bits a normal element drops
-    uint32_t half_m1;          // (1 << (shift - 1)) - 1: with the kept LSB added, a carry out of the dropped bits <=> round up (RNE)
-    uint32_t sub_limit;        // |u| patterns below this are on the format's fixed-point grid (its subnormals; all of MXINT8)
-    float sub_scale;           // 1 / that grid's spacing
-    float sub_quantum;         // the grid's spacing
-    uint32_t max_bits;         // pattern of the largest normal
-};
-
-constexpr uint32_t f32_bits(int exponent) { return (uint32_t)(exponent + 127) << 23; }      // 2^exponent, -126 <= exponent <= 127
-
-// float formats: mantissa bits m, smallest normal exponent emin = 1 - bias, largest normal (2 - 2^-m) 2^emax -- E4M3 gives its
-// all-ones mantissa at emax to NaN, so its largest normal is 1.75 * 2^8
-bool make_mx_fmt(int format, MxFmt* f) {
-    int m, emin, emax;
-    uint32_t top_mantissa;     // mantissa field of the largest normal, in m bits
-    switch (format) {
-        case PPQHIP_MXFP8_E4M3: m = 3; emin = -6; emax = 8; top_mantissa = 6; break;
-        case PPQHIP_MXFP8_E5M2: m = 2; emin = -14; emax = 15; top_mantissa = 3; break;
-        case PPQHIP_MXFP6_E3M2: m = 2; emin = -2; emax = 4; top_mantissa = 3; break;
-        case PPQHIP_MXFP6_E2M3: m = 3; emin = 0; emax = 2; top_mantissa = 7; break;
-        case PPQHIP_MXFP4_E2M1: m = 1; emin = 0; emax = 2; top_mantissa = 1; break;
-        case PPQHIP_MXINT8:                                                      // k / 64, |k| <= 127: one fixed-point grid
-            f->emax = 0; f->shift = 17; f->half_m1 = (1u << 16) - 1u; f->sub_limit = 0x7f800000u;
-            f->sub_scale = 64.0f; f->sub_quantum = 0.015625f; f->max_bits = f32_bits(0) | (63u << 17);      // 127 / 64
-            return true;
-        default: return false;
-    }
-    f->emax = (uint32_t)emax; f->shift = (uint32_t)(23 - m); f->half_m1 = (1u << (22 - m)) - 1u;
-    f->sub_limit = f32_bits(emin);
-    union { uint32_t d; float v; } s, q;
-    s.d = f32_bits(m - emin); q.d = f32_bits(emin - m);
-    f->sub_scale = s.v; f->sub_quantum = q.v;
-    f->max_bits = f32_bits(emax) | (top_mantissa << (23 - m));
-    return true;
-}
-
 enum : uint32_t { MX_ROWS4 = 0, MX_ROWS1 = 1, MX_STRIDED = 2 };
-constexpr uint32_t kMxBlock = 32;                 // elements per MX block
 
 struct MxJob {                                    // 88 B
     const float* x;
@@ -80,33 +43,7 @@ struct MxArgs {
     uint32_t first_block[CAP];
     uint32_t count;
 };
-constexpr int kMxMaxJobs = 40;
 static_assert(sizeof(MxArgs<kMxMaxJobs>) <= 4096, "kernel arguments are limited to 4 KB");
-
-__device__ __forceinline__ uint32_t mx_finite_mag(float v) {                     // |v|'s pattern; NaN and Inf do not take part
-    const uint32_t m = __float_as_uint(v) & 0x7fffffffu;
-    return m < 0x7f800000u ? m : 0u;
-}
-// E8M0 code of a block from the pattern of its amax: a subnormal or zero amax has exponent field 0 and clamps to code 0 (2^-127)
-__device__ __forceinline__ uint32_t mx_code(uint32_t amax_bits, const MxFmt& f) {
-    const uint32_t e = amax_bits >> 23;
-    return e > f.emax ? e - f.emax : 0u;
-}
-__device__ __forceinline__ float mx_pow2(uint32_t biased) {                      // 2^(biased - 127), 0 <= biased <= 254
-    return __uint_as_float(biased ? biased << 23 : 0x00400000u);
-}
-// cast(v / X) * X on the float32 pattern.  Normal elements: round the mantissa to nearest even with one integer add (the carry runs
-// into the exponent as it should); the fixed-point grid: rint() of the scaled magnitude (round half to even = the even encoding);
-// both saturate at the largest normal, which also takes Inf.
-__device__ __forceinline__ float mx_elem(float v, float inv, float X, const MxFmt& f) {
-    const float u = v * inv;
-    const uint32_t bits = __float_as_uint(u), sign = bits & 0x80000000u, mag = bits & 0x7fffffffu;
-    const uint32_t rn = (mag + f.half_m1 + ((mag >> f.shift) & 1u)) & ~((1u << f.shift) - 1u);
-    const uint32_t rs = __float_as_uint(__builtin_rintf(__uint_as_float(mag) * f.sub_scale) * f.sub_quantum);
-    const uint32_t r = min(mag < f.sub_limit ? rs : rn, f.max_bits);
-    const float q = __uint_as_float(r | sign) * X;
-    return mag > 0x7f800000u ? v : q;
-}
 
 template <int U, bool NT>
 __device__ __forceinline__ void mx_rows4(const MxJob& j, uint32_t local) {
@@ -195,8 +132,6 @@ __global__ __launch_bounds__(kBlock) void mx_fq_kernel(const MxArgs<CAP> args) {
     else if (j.path == MX_ROWS1) mx_rows1(j, local);
     else mx_strided(j, local);
 }
-
-constexpr int64_t kMxMax = 0x7fffffffLL;
 
 // the checks of one job; *n = its elements (0: nothing to do)
 int validate_job(const char* what, int k, const ppqhip_mx_job& j, int64_t* n) {

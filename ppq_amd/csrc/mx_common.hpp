@@ -1,0 +1,84 @@
+// mx_common.hpp -- what the MX fake-quant kernels (mx.hip) and the packed MX export (mx_pack.hip) share: the description of an
+// element format, the E8M0 code of a block and THE rounding of an element.  Both paths take the rounded float32 pattern from
+// mx_round, so the packed codes can never disagree with the fake-quantised values on a rounding.
+#pragma once
+
+#include "common.hpp"
+
+namespace ppqhip {
+
+struct MxFmt {                 // 28 B
+    uint32_t emax;             // the element format's largest exponent: the shared exponent is exponent(amax) - emax
+    uint32_t shift;            // 23 - mantissa bits: float32 mantissa bits a normal element drops
+    uint32_t half_m1;          // (1 << (shift - 1)) - 1: with the kept LSB added, a carry out of the dropped bits <=> round up (RNE)
+    uint32_t sub_limit;        // |u| patterns below this are on the format's fixed-point grid (its subnormals; all of MXINT8)
+    float sub_scale;           // 1 / that grid's spacing
+    float sub_quantum;         // the grid's spacing
+    uint32_t max_bits;         // pattern of the largest normal
+};
+
+constexpr uint32_t f32_bits(int exponent) { return (uint32_t)(exponent + 127) << 23; }      // 2^exponent, -126 <= exponent <= 127
+
+// float formats: mantissa bits m, smallest normal exponent emin = 1 - bias, largest normal (2 - 2^-m) 2^emax -- E4M3 gives its
+// all-ones mantissa at emax to NaN, so its largest normal is 1.75 * 2^8
+inline bool make_mx_fmt(int format, MxFmt* f) {
+    int m, emin, emax;
+    uint32_t top_mantissa;     // mantissa field of the largest normal, in m bits
+    switch (format) {
+        case PPQHIP_MXFP8_E4M3: m = 3; emin = -6; emax = 8; top_mantissa = 6; break;
+        case PPQHIP_MXFP8_E5M2: m = 2; emin = -14; emax = 15; top_mantissa = 3; break;
+        case PPQHIP_MXFP6_E3M2: m = 2; emin = -2; emax = 4; top_mantissa = 3; break;
+        case PPQHIP_MXFP6_E2M3: m = 3; emin = 0; emax = 2; top_mantissa = 7; break;
+        case PPQHIP_MXFP4_E2M1: m = 1; emin = 0; emax = 2; top_mantissa = 1; break;
+        case PPQHIP_MXINT8:                                                      // k / 64, |k| <= 127: one fixed-point grid
+            f->emax = 0; f->shift = 17; f->half_m1 = (1u << 16) - 1u; f->sub_limit = 0x7f800000u;
+            f->sub_scale = 64.0f; f->sub_quantum = 0.015625f; f->max_bits = f32_bits(0) | (63u << 17);      // 127 / 64
+            return true;
+        default: return false;
+    }
+    f->emax = (uint32_t)emax; f->shift = (uint32_t)(23 - m); f->half_m1 = (1u << (22 - m)) - 1u;
+    f->sub_limit = f32_bits(emin);
+    union { uint32_t d; float v; } s, q;
+    s.d = f32_bits(m - emin); q.d = f32_bits(emin - m);
+    f->sub_scale = s.v; f->sub_quantum = q.v;
+    f->max_bits = f32_bits(emax) | (top_mantissa << (23 - m));
+    return true;
+}
+
+constexpr uint32_t kMxBlock = 32;                 // elements per MX block
+constexpr int kMxMaxJobs = 40;                    // jobs of one launch (the table travels in the kernel arguments)
+constexpr int64_t kMxMax = 0x7fffffffLL;          // elements of one tensor
+
+#if defined(__HIPCC__)
+
+__device__ __forceinline__ uint32_t mx_finite_mag(float v) {                     // |v|'s pattern; NaN and Inf do not take part
+    const uint32_t m = __float_as_uint(v) & 0x7fffffffu;
+    return m < 0x7f800000u ? m : 0u;
+}
+// E8M0 code of a block from the pattern of its amax: a subnormal or zero amax has exponent field 0 and clamps to code 0 (2^-127)
+__device__ __forceinline__ uint32_t mx_code(uint32_t amax_bits, const MxFmt& f) {
+    const uint32_t e = amax_bits >> 23;
+    return e > f.emax ? e - f.emax : 0u;
+}
+__device__ __forceinline__ float mx_pow2(uint32_t biased) {                      // 2^(biased - 127), 0 <= biased <= 254
+    return __uint_as_float(biased ? biased << 23 : 0x00400000u);
+}
+// The cast of |u| = |v / X| on its float32 pattern.  Normal elements: round the mantissa to nearest even with one integer add (the
+// carry runs into the exponent as it should); the fixed-point grid: rint() of the scaled magnitude (round half to even = the even
+// encoding); both saturate at the largest normal, which also takes Inf.  (A NaN pattern gives a pattern nobody may use.)
+__device__ __forceinline__ uint32_t mx_round(uint32_t mag, const MxFmt& f) {
+    const uint32_t rn = (mag + f.half_m1 + ((mag >> f.shift) & 1u)) & ~((1u << f.shift) - 1u);
+    const uint32_t rs = __float_as_uint(__builtin_rintf(__uint_as_float(mag) * f.sub_scale) * f.sub_quantum);
+    return min(mag < f.sub_limit ? rs : rn, f.max_bits);
+}
+// cast(v / X) * X
+__device__ __forceinline__ float mx_elem(float v, float inv, float X, const MxFmt& f) {
+    const float u = v * inv;
+    const uint32_t bits = __float_as_uint(u), sign = bits & 0x80000000u, mag = bits & 0x7fffffffu;
+    const float q = __uint_as_float(mx_round(mag, f) | sign) * X;
+    return mag > 0x7f800000u ? v : q;
+}
+
+#endif  // __HIPCC__
+
+}  // namespace ppqhip

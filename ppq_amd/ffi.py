@@ -16,6 +16,7 @@ All tensor arguments must live on the GPU.  There is no CPU path: a CPU tensor r
 Errors follow the reference's convention as seen from Python: the C++ ``ValueTypeException`` /
 ``InvalidValueException`` (common.cuh:32-48) surface as ``RuntimeError``.
 """
+import math
 import threading
 import weakref
 from typing import List
@@ -904,6 +905,71 @@ class MXQuantizePlan:
     def run(self) -> List[torch.Tensor]:
         with _DeviceOf(self._arena):
             _raise(lib.ppqhip_mx_fq_multi(self._jobs.ctypes.data, len(self._jobs), _stream()))
+        return self._outs
+
+
+# ---- packed MX export (include/ppq_hip.h ppqhip_mx_pack / ppqhip_mx_unpack and their _multi forms) ----
+_MX_PACK_JOB = np.dtype([('x', '<u8'), ('elements', '<u8'), ('scales', '<u8'), ('outer', '<i8'), ('axis_len', '<i8'), ('inner', '<i8'),
+                         ('format', '<i4'), ('reserved', '<i4')])
+_MX_UNPACK_JOB = np.dtype([('elements', '<u8'), ('scales', '<u8'), ('y', '<u8'), ('outer', '<i8'), ('axis_len', '<i8'), ('inner', '<i8'),
+                           ('format', '<i4'), ('reserved', '<i4')])
+MX_BLOCK_BYTES = {'MXFP8_E4M3': 32, 'MXFP8_E5M2': 32, 'MXFP6_E3M2': 24, 'MXFP6_E2M3': 24, 'MXFP4_E2M1': 16, 'MXINT8': 32}
+_MX_BLOCK_BYTES_BY_ID = {MX_FORMATS[k]: v for k, v in MX_BLOCK_BYTES.items()}
+
+
+def mx_block_bytes(format) -> int:
+    """Bytes of one packed block of 32 elements: 32 (MXFP8, MXINT8), 24 (MXFP6), 16 (MXFP4)."""
+    return _MX_BLOCK_BYTES_BY_ID[mx_format_id(format)]
+
+
+def mx_packed_shapes(shape, axis: int, format):
+    """(shape of ``elements``, shape of ``scales``) of a tensor of ``shape`` packed along ``axis`` (not negative): the shape without
+    the axis, plus [nb * B] resp. [nb] -- the block axis is last."""
+    shape = [int(d) for d in shape]
+    nb = (shape[axis] + MX_BLOCK - 1) // MX_BLOCK
+    lead = shape[:axis] + shape[axis + 1:]
+    return lead + [nb * mx_block_bytes(format)], lead + [nb]
+
+
+class MXPackPlan:
+    """The sibling of ``MXQuantizePlan`` for the packed export: MANY tensors packed with ONE launch per call
+    (``ppqhip_mx_pack_multi``).  Built once from ``(value, format, axis)`` items; ``run()`` packs all of them into one resident
+    uint8 arena (every ``elements`` and every ``scales`` starts 16-B aligned) and returns ``[(elements, scales)]`` -- bytes identical
+    to ``CUDA.MXPack`` per item.  The table holds POINTERS to the callers' tensors: in-place updates are seen by later runs; a value
+    that is not dense in storage order is refused (``MXQuantizePlan.accepts``)."""
+    accepts = staticmethod(MXQuantizePlan.accepts)
+
+    def __init__(self, items):
+        if not items: raise ValueError('MXPackPlan needs at least one item')
+        dev = items[0][0].device
+        geometry, total = [], 0
+        for value, format, axis in items:
+            _f32(value, 'Value')
+            if value.device != dev: raise RuntimeError(_KERNEL_FAILURE + 'MXPackPlan: every tensor must live on one device')
+            axis = _mx_axis(value.dim(), axis)
+            if not MXQuantizePlan.accepts(value, axis):
+                raise RuntimeError(_KERNEL_FAILURE + 'MXPackPlan: value must be dense in storage order (a private copy would go stale); see accepts()')
+            eshape, sshape = mx_packed_shapes(value.shape, axis, format)
+            geometry.append((axis, eshape, sshape))
+            total += (math.prod(eshape) + 15) // 16 * 16 + (math.prod(sshape) + 15) // 16 * 16
+        self._arena = torch.empty(total, dtype=torch.uint8, device=dev)
+        self._jobs = np.zeros(len(items), dtype=_MX_PACK_JOB)
+        self._keep, self._outs = [], []
+        at = 0
+        for k, ((v, format, _), (axis, eshape, sshape)) in enumerate(zip(items, geometry)):
+            outer, length, inner, _ = _mx_geometry(v, axis)
+            ne, ns = math.prod(eshape), math.prod(sshape)
+            elements = self._arena[at: at + ne].view(eshape)
+            at += (ne + 15) // 16 * 16
+            scales = self._arena[at: at + ns].view(sshape)
+            at += (ns + 15) // 16 * 16
+            self._keep.append(v); self._outs.append((elements, scales))
+            self._jobs[k] = (v.data_ptr(), elements.data_ptr(), scales.data_ptr(), outer, length, inner, mx_format_id(format), 0)
+        self.bytes = sum(4 * v.numel() + e.numel() + s.numel() for v, (e, s) in zip(self._keep, self._outs))
+
+    def run(self):
+        with _DeviceOf(self._arena):
+            _raise(lib.ppqhip_mx_pack_multi(self._jobs.ctypes.data, len(self._jobs), _stream()))
         return self._outs
 
 
@@ -1969,6 +2035,44 @@ class CUDA:
             _raise(lib.ppqhip_mx_fq(v.data_ptr(), out.data_ptr(), codes.data_ptr() if codes is not None else 0, outer, length, inner,
                                     fmt, _stream()))
         if codes is not None and codes is not scale_codes: scale_codes.copy_(codes)
+        return out
+
+    @ staticmethod
+    def MXPack(tensor, format, axis: int, block_size: int = MX_BLOCK):
+        """Packed OCP Microscaling export: ``(elements, scales)``, two uint8 tensors with the block axis
+        LAST -- the input's shape without ``axis`` plus ``[nb * B]`` resp. ``[nb]`` (nb = ceil(len / 32); B = 32 / 24 / 16 bytes per
+        block for 8 / 6 / 4-bit elements).  Blocks, scales and rounding are those of ``MXQuantize``.  A 4-D channels-last tensor packed
+        along axis 1 is read in storage order; any other non-contiguous one is copied."""
+        if block_size != MX_BLOCK: raise ValueError(f'MX block size is {MX_BLOCK}, got {block_size}')
+        fmt = mx_format_id(format)
+        _f32(tensor, 'Value')
+        axis = _mx_axis(tensor.dim(), axis)
+        v = _mx_dense(tensor, axis)
+        outer, length, inner, _ = _mx_geometry(v, axis)
+        eshape, sshape = mx_packed_shapes(v.shape, axis, fmt)
+        elements = torch.empty(eshape, dtype=torch.uint8, device=v.device)
+        scales = torch.empty(sshape, dtype=torch.uint8, device=v.device)
+        with _DeviceOf(v):
+            _raise(lib.ppqhip_mx_pack(v.data_ptr(), elements.data_ptr(), scales.data_ptr(), outer, length, inner, fmt, _stream()))
+        return elements, scales
+
+    @ staticmethod
+    def MXUnpack(elements, scales, format, shape, axis: int):
+        """The inverse of ``MXPack``: a contiguous float32 tensor of ``shape`` whose blocks along ``axis`` are
+        value(code) * 2^(scale - 127); scale 0xFF and the NaN codes of MXFP8 give NaN, the tail padding is dropped."""
+        fmt = mx_format_id(format)
+        shape = [int(d) for d in shape]
+        axis = _mx_axis(len(shape), axis)
+        _check(elements, torch.uint8, 'Elements(Expect to be UINT8)'); _check(scales, torch.uint8, 'Scales(Expect to be UINT8)')
+        eshape, sshape = mx_packed_shapes(shape, axis, fmt)
+        if list(elements.shape) != eshape or list(scales.shape) != sshape:
+            raise RuntimeError(_KERNEL_FAILURE + f'elements / scales of shape {list(elements.shape)} / {list(scales.shape)}, expected {eshape} / {sshape}')
+        if scales.device != elements.device: raise RuntimeError(_KERNEL_FAILURE + 'scales is on another device')
+        elements, scales = elements.contiguous(), scales.contiguous()
+        out = torch.empty(shape, dtype=torch.float32, device=elements.device)
+        outer, length, inner, _ = _mx_geometry(out, axis)
+        with _DeviceOf(out):
+            _raise(lib.ppqhip_mx_unpack(elements.data_ptr(), scales.data_ptr(), out.data_ptr(), outer, length, inner, fmt, _stream()))
         return out
 
     @ staticmethod

@@ -10,18 +10,23 @@ NaN passes through, +-Inf saturates, zero keeps its sign, float32 subnormals are
 HIP kernels (``ppq_amd/csrc/mx.hip``, ``use_kernels=True``) and the torch restatement below (``use_kernels=False``, any device)
 give identical bits.
 
+``mx_quantize`` / ``mx_dequantize`` are the export: the element codes and E8M0 scales a block-scaled GEMM or a checkpoint stores
+(``MXTensor``; the packed contract is DESIGN.md section 9.13, restated by ``tests/mx_pack_reference.py``), cut from the same rounded
+patterns as the fake quant, so that ``mx_dequantize(mx_quantize(x))`` has the bits of ``mx_fake_quant(x)``.  ``export_graph_mx`` packs
+every MX weight of a graph in one launch.
+
 ``quantize_graph_mx`` puts MX on the inputs of Conv / Gemm / MatMul of a harness graph through the executor's delegator seam
 (``TorchExecutor.register_quantize_delegate``): ``MXDelegator`` follows the reference's delegator protocol
 (``delegator(tensor, config)``, ppq/executor/torch.py:296-323) and works in its executor unchanged.
 """
 from enum import Enum
-from typing import List, Optional
+from typing import Dict, List, Optional
 
 import torch
 from torch.autograd import Function
 
 from .core import (FloatingQuantizationConfig, LinearQuantizationConfig, QuantizationStates)
-from .ffi import CUDA, MX_BLOCK, MX_FORMATS, MXQuantizePlan, mx_format_id
+from .ffi import CUDA, MX_BLOCK, MX_FORMATS, MXPackPlan, MXQuantizePlan, mx_format_id, mx_packed_shapes
 
 # name -> (exponent bits, mantissa bits, smallest normal exponent, emax, largest normal); MXINT8: k / 64 with |k| <= 127
 _SPEC = {
@@ -120,6 +125,16 @@ def _check_codes(tensor: torch.Tensor, axis: int, scale_codes) -> None:
         raise RuntimeError(f'scale_codes must be a uint8 tensor of shape {want}')
 
 
+def _check_input(tensor, axis) -> int:
+    """The argument checks of ``mx_fake_quant`` and ``mx_quantize``; returns the axis counted from the front."""
+    if not isinstance(tensor, torch.Tensor): raise TypeError(f'expected a torch.Tensor, got {type(tensor)}')
+    if tensor.dtype != torch.float32: raise RuntimeError('Kernel Failure, Invalid dtype of Input tensor: Value(Expect to be FP32)')
+    if tensor.dim() == 0 or not isinstance(axis, int) or not -tensor.dim() <= axis < tensor.dim():
+        raise RuntimeError(f'Kernel Failure, axis {axis} out of range for a {tensor.dim()}-d tensor')
+    if tensor.numel() == 0: raise RuntimeError('Kernel Failure, Tensor is empty: Value')
+    return axis % tensor.dim()
+
+
 class _MXFakeQuant(Function):
     @ staticmethod
     def forward(ctx, tensor, format, axis, scale_codes, use_kernels):
@@ -137,14 +152,166 @@ def mx_fake_quant(tensor: torch.Tensor, format, axis: int = -1, scale_codes: tor
     ``use_kernels=True``: the HIP kernels (the tensor must be on the GPU).  ``False``: the torch restatement of the same contract
     on whatever device the tensor lives on -- identical bits."""
     format = MXFormat.of(format)
-    if not isinstance(tensor, torch.Tensor): raise TypeError(f'expected a torch.Tensor, got {type(tensor)}')
-    if tensor.dtype != torch.float32: raise RuntimeError('Kernel Failure, Invalid dtype of Input tensor: Value(Expect to be FP32)')
-    if tensor.dim() == 0 or not isinstance(axis, int) or not -tensor.dim() <= axis < tensor.dim():
-        raise RuntimeError(f'Kernel Failure, axis {axis} out of range for a {tensor.dim()}-d tensor')
-    if tensor.numel() == 0: raise RuntimeError('Kernel Failure, Tensor is empty: Value')
-    axis %= tensor.dim()
+    axis = _check_input(tensor, axis)
     _check_codes(tensor, axis, scale_codes)
     return _MXFakeQuant.apply(tensor, format, axis, scale_codes, use_kernels)
+
+
+# ---- the packed export (DESIGN.md section 9.13) ------------------------------------------------------------------------------------
+def _element_bits(format: MXFormat) -> int:
+    return 8 if format is MXFormat.MXINT8 else 1 + format.exponent_bits + format.mantissa_bits
+
+
+def _mx_pack_torch(tensor: torch.Tensor, format: MXFormat, axis: int):
+    """The packed contract in torch ops, on the tensor's device: the rounded pattern of ``_mx_torch``, then the code read off it."""
+    _, m, emin, emax, max_normal = _SPEC[format.name]
+    width, fp8 = _element_bits(format), format in (MXFormat.MXFP8_E4M3, MXFormat.MXFP8_E5M2)
+    length = tensor.shape[axis]
+    nb = (length + MX_BLOCK - 1) // MX_BLOCK
+    x = tensor.movedim(axis, -1)
+    lead = list(x.shape[:-1])
+    x = x.contiguous()
+    if nb * MX_BLOCK != length: x = torch.nn.functional.pad(x, (0, nb * MX_BLOCK - length))      # +0: code 0
+    x = x.reshape(lead + [nb, MX_BLOCK])
+    bits = x.view(torch.int32)
+    mag = bits & 0x7fffffff
+    sign = (bits >> 31) & 1
+    isnan = mag > 0x7f800000
+    amax = torch.where(mag < 0x7f800000, mag, torch.zeros_like(mag)).amax(dim=-1, keepdim=True)
+    scale = ((amax >> 23) - emax).clamp_(min=0)
+    umag = (x * _pow2(254 - scale)).view(torch.int32) & 0x7fffffff
+    max_bits = int(torch.tensor(max_normal, dtype=torch.float32).view(torch.int32))
+    if format.is_float:
+        shift = 23 - m
+        finite = torch.where(umag > 0x7f800000, torch.zeros_like(umag), umag)
+        normal = (finite + ((1 << (shift - 1)) - 1) + ((finite >> shift) & 1)) & ~((1 << shift) - 1)
+        grid = (torch.round(_bits_to_float(umag) * 2.0 ** (m - emin)) * 2.0 ** (emin - m)).view(torch.int32)
+        r = torch.where(umag < ((emin + 127) << 23), grid, normal)
+        r = torch.minimum(r, torch.full_like(r, max_bits))
+        index = (_bits_to_float(r) * 2.0 ** (m - emin)).to(torch.int32)                            # the grid's index: exact
+        code = torch.where(r < ((emin + 127) << 23), index, (r >> shift) - ((emin + 126) << m))     # emin + 126 = 127 - bias
+        if fp8: code = torch.where(isnan, torch.full_like(code, 0x7f), code)
+        code = code | (sign << (width - 1))
+    else:
+        r = (torch.round(_bits_to_float(umag) * 64.0) * 0.015625).view(torch.int32)
+        r = torch.minimum(r, torch.full_like(r, max_bits))
+        k = (_bits_to_float(r) * 64.0).to(torch.int32)
+        code = torch.where(sign == 1, -k, k) & 0xff
+    if not fp8:                                        # no NaN encoding: the block is NaN as a whole
+        dead = isnan.any(dim=-1, keepdim=True)
+        code = torch.where(dead, torch.zeros_like(code), code)
+        scale = torch.where(dead, torch.full_like(scale, 0xff), scale)
+    if width == 4:
+        packed = code[..., 0::2] | (code[..., 1::2] << 4)
+    elif width == 6:                                   # four codes, three bytes
+        c = code.reshape(lead + [nb, MX_BLOCK // 4, 4])
+        packed = torch.stack([c[..., 0] | (c[..., 1] << 6), (c[..., 1] >> 2) | (c[..., 2] << 4), (c[..., 2] >> 4) | (c[..., 3] << 2)], dim=-1) & 0xff
+    else:
+        packed = code
+    elements = packed.reshape(lead + [nb * 4 * width]).to(torch.uint8)
+    return elements, scale.reshape(lead + [nb]).to(torch.uint8)
+
+
+def _mx_unpack_torch(elements: torch.Tensor, scales: torch.Tensor, format: MXFormat, shape, axis: int) -> torch.Tensor:
+    """value(code) * 2^(scale - 127) in torch ops, on the tensors' device."""
+    _, m, emin, _, _ = _SPEC[format.name]
+    width, fp8 = _element_bits(format), format in (MXFormat.MXFP8_E4M3, MXFormat.MXFP8_E5M2)
+    lead, nb = list(scales.shape[:-1]), scales.shape[-1]
+    e = elements.to(torch.int32)
+    if width == 4:
+        code = torch.stack([e & 15, e >> 4], dim=-1)
+    elif width == 6:
+        b = e.reshape(lead + [nb * MX_BLOCK // 4, 3])
+        code = torch.stack([b[..., 0], (b[..., 0] >> 6) | (b[..., 1] << 2), (b[..., 1] >> 4) | (b[..., 2] << 4), b[..., 2] >> 2], dim=-1) & 63
+    else:
+        code = e
+    code = code.reshape(lead + [nb, MX_BLOCK])
+    s = scales.to(torch.int32).unsqueeze(-1)
+    X = _pow2(s.clamp(max=254))
+    nan = (s == 0xff).expand_as(code)
+    nan_bits = torch.full_like(code, 0x7fc00000)
+    if format.is_float:
+        shift = 23 - m
+        sign = ((code >> (width - 1)) & 1) << 31
+        mag = code & ((1 << (width - 1)) - 1)
+        field, man = mag >> m, mag & ((1 << m) - 1)
+        sub = (man.to(torch.float32) * 2.0 ** (emin - m)).view(torch.int32)
+        y = _bits_to_float(torch.where(field > 0, (mag << shift) + ((emin + 126) << 23), sub) | sign) * X
+        if format is MXFormat.MXFP8_E4M3: nan = nan | (mag == 0x7f)
+        if format is MXFormat.MXFP8_E5M2:
+            nan = nan | ((field == 31) & (man != 0))
+            y = torch.where((field == 31) & (man == 0), _bits_to_float(sign | 0x7f800000), y)
+        if fp8: nan_bits = nan_bits | sign
+    else:
+        y = torch.where(code >= 128, code - 256, code).to(torch.float32) * 0.015625 * X
+    y = torch.where(nan, _bits_to_float(nan_bits), y)
+    return y.reshape(lead + [nb * MX_BLOCK])[..., :shape[axis]].movedim(-1, axis).contiguous()
+
+
+class MXTensor:
+    """A tensor in packed MX form: ``elements`` (uint8, ``shape`` without ``axis`` plus ``[nb * B]``) and ``scales`` (uint8 E8M0
+    codes, ``shape`` without ``axis`` plus ``[nb]``) -- the block axis is last; ``format`` is an ``MXFormat``, ``shape`` the shape of
+    the float tensor and ``axis`` (counted from the front) the axis its blocks run along."""
+    def __init__(self, format, shape, axis: int, elements: torch.Tensor, scales: torch.Tensor):
+        self.format = MXFormat.of(format)
+        self.shape = tuple(int(d) for d in shape)
+        if not isinstance(axis, int) or isinstance(axis, bool) or not self.shape or not -len(self.shape) <= axis < len(self.shape):
+            raise ValueError(f'MXTensor: axis {axis!r} out of range for shape {list(self.shape)}')
+        self.axis = axis % len(self.shape)
+        eshape, sshape = mx_packed_shapes(self.shape, self.axis, self.format)
+        for name, t, want in (('elements', elements, eshape), ('scales', scales, sshape)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8: raise ValueError(f'MXTensor: {name} must be a uint8 tensor')
+            if list(t.shape) != want:
+                raise ValueError(f'MXTensor: {name} of shape {list(t.shape)}, but {self.format.name} of {list(self.shape)} along axis {self.axis} has {want}')
+        if elements.device != scales.device: raise ValueError('MXTensor: elements and scales live on different devices')
+        self.elements, self.scales = elements, scales
+
+    @ property
+    def nbytes(self) -> int: return self.elements.numel() + self.scales.numel()
+
+    @ property
+    def device(self): return self.elements.device
+
+    def to(self, device) -> 'MXTensor':
+        return MXTensor(self.format, self.shape, self.axis, self.elements.to(device), self.scales.to(device))
+
+    def dequantize(self, use_kernels: bool = True) -> torch.Tensor:
+        """The float32 tensor of ``shape``: value(code) * 2^(scale - 127).  ``use_kernels=True``: the HIP kernel (the tensors must
+        be on the GPU); ``False``: torch ops on whatever device they live on -- identical bits."""
+        if use_kernels: return CUDA.MXUnpack(self.elements, self.scales, self.format, self.shape, self.axis)
+        return _mx_unpack_torch(self.elements, self.scales, self.format, self.shape, self.axis)
+
+    def to_dict(self) -> dict:
+        """Tensors, ints and the format's name only: ``torch.save`` round-trips it (``from_dict``)."""
+        return {'format': self.format.name, 'shape': torch.tensor(self.shape, dtype=torch.int64), 'axis': self.axis,
+                'elements': self.elements, 'scales': self.scales}
+
+    @ classmethod
+    def from_dict(cls, d: dict) -> 'MXTensor':
+        """The inverse of ``to_dict``; dtype and shapes are checked against format, shape and axis (ValueError)."""
+        missing = [k for k in ('format', 'shape', 'axis', 'elements', 'scales') if k not in d]
+        if missing: raise ValueError(f'MXTensor.from_dict: missing {missing}')
+        return cls(d['format'], [int(v) for v in d['shape']], d['axis'], d['elements'], d['scales'])
+
+    def __repr__(self) -> str:
+        return f'MXTensor({self.format.name}, shape={list(self.shape)}, axis={self.axis}, {self.nbytes} bytes on {self.device})'
+
+
+def mx_quantize(tensor: torch.Tensor, format, axis: int = -1, use_kernels: bool = True) -> MXTensor:
+    """``tensor`` in packed MX form, blocks of 32 along ``axis``: the blocks, scales and roundings of ``mx_fake_quant``, stored as
+    element codes and E8M0 scale codes.  ``use_kernels=True``: the HIP kernel (the tensor must be on the GPU); ``False``: the torch
+    restatement on whatever device the tensor lives on -- identical bytes."""
+    format = MXFormat.of(format)
+    axis = _check_input(tensor, axis)
+    elements, scales = CUDA.MXPack(tensor, format, axis, MX_BLOCK) if use_kernels else _mx_pack_torch(tensor.detach(), format, axis)
+    return MXTensor(format, tensor.shape, axis, elements, scales)
+
+
+def mx_dequantize(mxt: MXTensor, use_kernels: bool = True) -> torch.Tensor:
+    """``mxt`` as float32.  Without NaN in the source, ``mx_dequantize(mx_quantize(x))`` has the bits of ``mx_fake_quant(x)``
+    (MXINT8: -0 comes back as +0)."""
+    if not isinstance(mxt, MXTensor): raise TypeError(f'expected an MXTensor, got {type(mxt)}')
+    return mxt.dequantize(use_kernels)
 
 
 def _activated(config) -> bool:
@@ -270,3 +437,31 @@ def quantize_graph_mx(graph, executor, weight_format, activation_format, operati
         group = MXWeightGroup([(v, d.format, d.axis) for d, v in weights])
         for k, (d, v) in enumerate(weights): d.group, d.slot, d.var = group, k, v
     return delegators
+
+
+def export_graph_mx(graph, delegators=None, use_kernels: bool = True) -> Dict[str, MXTensor]:
+    """Every parameter ``quantize_graph_mx`` put an MX config on, in packed form, keyed by the variable's name.  The format is the
+    ``MXDelegator``'s (``delegators``: what ``quantize_graph_mx`` returned) or, without delegators, ``config.detail['MX_FORMAT']``;
+    the axis is ``mx_block_axis``.  With ``use_kernels`` all of them are packed by ONE launch (``ffi.MXPackPlan``)."""
+    from .harness import QuantableOperation
+    names, items = [], []
+    for op in graph.operations.values():
+        if not isinstance(op, QuantableOperation) or op.type not in MX_OPERATIONS: continue
+        for i, (v, c) in enumerate(zip(op.inputs, op.config.input_quantization_config)):
+            if not v.is_parameter or i >= 2 or v.name in names: continue
+            if delegators is not None:
+                d = delegators.get(c)
+                if not isinstance(d, MXDelegator): continue
+                fmt = d.format
+            elif 'MX_FORMAT' in getattr(c, 'detail', {}): fmt = MXFormat.of(c.detail['MX_FORMAT'])
+            else: continue
+            value = v.value
+            _check_input(value, mx_block_axis(op.type, i))
+            names.append(v.name)
+            items.append((value.detach(), fmt, mx_block_axis(op.type, i) % value.dim()))
+    if not items: return {}
+    if not use_kernels:
+        return {n: mx_quantize(v, fmt, axis, use_kernels=False) for n, (v, fmt, axis) in zip(names, items)}
+    items = [(v if MXPackPlan.accepts(v, axis) else v.contiguous(), fmt, axis) for v, fmt, axis in items]
+    packed = MXPackPlan(items).run()
+    return {n: MXTensor(fmt, v.shape, axis, e, s) for n, (v, fmt, axis), (e, s) in zip(names, items, packed)}
