@@ -729,6 +729,22 @@ typedef struct ppqhip_mx_unpack_job {
 } ppqhip_mx_unpack_job;
 int ppqhip_mx_unpack_multi(const ppqhip_mx_unpack_job* jobs, int num_jobs, void* stream);
 
+/* GEMM on packed MX operands (ppq_amd/mx.py mx_matmul / mx_linear; ADDED under ABI 4) --------------- */
+/* c[m, n] (float32, row-major) = A[m, k] . B[n, k]^T (+ bias[n]) on v_mfma_scale_f32_16x16x128_f8f6f4.  Both operands are packed
+ * along their LAST axis exactly as ppqhip_mx_pack leaves them (inner == 1): elements [rows, nb * B], scales [rows, nb],
+ * nb = ceil(k / 32); B as [n, k] is a Gemm weight [out, in].  a_format / b_format: any of the five float formats, independently;
+ * PPQHIP_MXINT8 is not an operand type of the instruction and is refused.  The instruction receives the blocks' bytes and scale
+ * codes as stored; every product of two element values is exact, every scale a power of two, the sum over k is accumulated in
+ * float32 in one fixed order (no atomics, no split-K): two calls give identical bits, and for every output
+ *   |c - c_float64| <= k * 2^-23 * sum_k |a_k| |b_k|      (exact wherever every partial sum is representable).
+ * bias (may be NULL) is added with one float32 add per output.  An output is the quiet NaN 0x7fc00000 exactly where it sums over a
+ * block whose scale code is 0xFF or over an FP8 NaN code; E5M2 Inf codes (never exported) are outside the contract.
+ * Refused before any launch: MXINT8 and unknown formats, negative sizes or sizes above 2^31 - 1, null pointers (bias excepted),
+ * elements or c not 16-byte aligned, c overlapping any input.  m == 0 or n == 0 launches nothing; k == 0 writes the bias (or 0). */
+int ppqhip_mx_gemm(const uint8_t* a_elements, const uint8_t* a_scales, int a_format, const uint8_t* b_elements,
+                   const uint8_t* b_scales, int b_format, const float* bias, float* c, int64_t m, int64_t n, int64_t k,
+                   void* stream);
+
 /* profiling aid used by bench.py: when enabled, every kernel launch made through this library
  * on this thread is bracketed by hipEvents on its own stream; ppqhip_prof_collect() synchronises
  * those events and returns, per kernel id, launches / total ms / total algorithmic bytes. */

@@ -2076,6 +2076,35 @@ class CUDA:
         return out
 
     @ staticmethod
+    def MXMatmul(a_elements, a_scales, a_format, b_elements, b_scales, b_format, k: int, bias=None):
+        """``A[M, k] . B[N, k]^T (+ bias[N])`` as float32 ``[M, N]`` on the block-scaled MFMA.  Both operands
+        are packed along their last axis as ``MXPack`` leaves them: ``elements [rows, nb * B]`` and ``scales [rows, nb]``, uint8,
+        nb = ceil(k / 32).  The five float formats in any combination; MXINT8 is refused.  Non-contiguous inputs are copied."""
+        fa, fb = mx_format_id(a_format), mx_format_id(b_format)
+        k = int(k)
+        if k <= 0: raise RuntimeError(_KERNEL_FAILURE + f'k must be positive, got {k}')
+        for name, t in (('A elements', a_elements), ('A scales', a_scales), ('B elements', b_elements), ('B scales', b_scales)):
+            _check(t, torch.uint8, name + '(Expect to be UINT8)')
+            if t.dim() != 2: raise RuntimeError(_KERNEL_FAILURE + f'{name} must be 2-d, got {list(t.shape)}')
+            if t.device != a_elements.device: raise RuntimeError(_KERNEL_FAILURE + f'{name} is on another device')
+        m, n = a_elements.shape[0], b_elements.shape[0]
+        for name, e, s, rows, fmt in (('A', a_elements, a_scales, m, fa), ('B', b_elements, b_scales, n, fb)):
+            eshape, sshape = mx_packed_shapes([rows, k], 1, fmt)
+            if list(e.shape) != eshape or list(s.shape) != sshape:
+                raise RuntimeError(_KERNEL_FAILURE + f'{name}: elements / scales of shape {list(e.shape)} / {list(s.shape)}, expected {eshape} / {sshape} for k = {k}')
+        if bias is not None:
+            _f32(bias, 'Bias')
+            if list(bias.shape) != [n]: raise RuntimeError(_KERNEL_FAILURE + f'bias of shape {list(bias.shape)}, expected [{n}]')
+            if bias.device != a_elements.device: raise RuntimeError(_KERNEL_FAILURE + 'bias is on another device')
+            bias = bias.contiguous()
+        a_elements, a_scales, b_elements, b_scales = a_elements.contiguous(), a_scales.contiguous(), b_elements.contiguous(), b_scales.contiguous()
+        out = torch.empty([m, n], dtype=torch.float32, device=a_elements.device)
+        with _DeviceOf(out):
+            _raise(lib.ppqhip_mx_gemm(a_elements.data_ptr(), a_scales.data_ptr(), fa, b_elements.data_ptr(), b_scales.data_ptr(), fb,
+                                      bias.data_ptr() if bias is not None else 0, out.data_ptr(), m, n, k, _stream()))
+        return out
+
+    @ staticmethod
     def Sync():
         """Synchronize device (ffi.py:347-350)."""
         torch.cuda.synchronize()

@@ -13,7 +13,8 @@ give identical bits.
 ``mx_quantize`` / ``mx_dequantize`` are the export: the element codes and E8M0 scales a block-scaled GEMM or a checkpoint stores
 (``MXTensor``; the packed contract is DESIGN.md section 9.13, restated by ``tests/mx_pack_reference.py``), cut from the same rounded
 patterns as the fake quant, so that ``mx_dequantize(mx_quantize(x))`` has the bits of ``mx_fake_quant(x)``.  ``export_graph_mx`` packs
-every MX weight of a graph in one launch.
+every MX weight of a graph in one launch.  ``mx_matmul`` / ``mx_linear`` multiply two packed tensors on the block-scaled MFMA
+(``ppq_amd/csrc/mx_gemm.hip``): the hardware in the loop of both the simulation and the export.
 
 ``quantize_graph_mx`` puts MX on the inputs of Conv / Gemm / MatMul of a harness graph through the executor's delegator seam
 (``TorchExecutor.register_quantize_delegate``): ``MXDelegator`` follows the reference's delegator protocol
@@ -281,6 +282,10 @@ class MXTensor:
         if use_kernels: return CUDA.MXUnpack(self.elements, self.scales, self.format, self.shape, self.axis)
         return _mx_unpack_torch(self.elements, self.scales, self.format, self.shape, self.axis)
 
+    def matmul(self, other: 'MXTensor', bias: torch.Tensor = None, use_kernels: bool = True) -> torch.Tensor:
+        """``mx_matmul(self, other, bias, use_kernels)``: ``self . other^T`` in float32."""
+        return mx_matmul(self, other, bias, use_kernels)
+
     def to_dict(self) -> dict:
         """Tensors, ints and the format's name only: ``torch.save`` round-trips it (``from_dict``)."""
         return {'format': self.format.name, 'shape': torch.tensor(self.shape, dtype=torch.int64), 'axis': self.axis,
@@ -312,6 +317,48 @@ def mx_dequantize(mxt: MXTensor, use_kernels: bool = True) -> torch.Tensor:
     (MXINT8: -0 comes back as +0)."""
     if not isinstance(mxt, MXTensor): raise TypeError(f'expected an MXTensor, got {type(mxt)}')
     return mxt.dequantize(use_kernels)
+
+
+# ---- GEMM on the packed tensors (DESIGN.md section 9.14) ---------------------------------------------------------------------------
+def _check_matmul(a, b, bias):
+    """The argument checks of ``mx_matmul``; returns (lead shape of a, N, K)."""
+    for name, t in (('a', a), ('b', b)):
+        if not isinstance(t, MXTensor): raise TypeError(f'mx_matmul: {name}: expected an MXTensor, got {type(t)}')
+        if not t.format.is_float: raise RuntimeError(f'mx_matmul: {name} is {t.format.name}, which is not an operand type of the scaled MFMA')
+        if t.axis != len(t.shape) - 1:
+            raise RuntimeError(f'mx_matmul: {name} of shape {list(t.shape)} is packed along axis {t.axis}, not along its last axis')
+    if len(b.shape) != 2: raise RuntimeError(f'mx_matmul: b must be 2-d [N, K], got shape {list(b.shape)}')
+    if a.shape[-1] != b.shape[-1]: raise RuntimeError(f'mx_matmul: K mismatch: a has {a.shape[-1]}, b has {b.shape[-1]}')
+    if a.device != b.device: raise RuntimeError(f'mx_matmul: a is on {a.device}, b on {b.device}')
+    n = b.shape[0]
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32: raise RuntimeError('mx_matmul: bias must be a float32 tensor')
+        if list(bias.shape) != [n]: raise RuntimeError(f'mx_matmul: bias of shape {list(bias.shape)}, expected [{n}]')
+    return list(a.shape[:-1]), n, a.shape[-1]
+
+
+def mx_matmul(a: MXTensor, b: MXTensor, bias: torch.Tensor = None, use_kernels: bool = True) -> torch.Tensor:
+    """``a . b^T (+ bias)`` in float32: ``a`` is ``lead + [K]``, ``b`` is ``[N, K]`` (a Gemm weight [out, in], as ``export_graph_mx``
+    leaves it), both packed along their last axis in any of the five float formats; the result is ``lead + [N]``.
+    ``use_kernels=True``: the packed bytes go to the block-scaled MFMA as they are (``CUDA.MXMatmul``; the tensors must be on the
+    GPU).  ``False``: the readable reference on any device -- ``mx_dequantize`` of both, the product in float64, rounded to float32.
+    The two are NOT bit-identical: the kernel accumulates in float32 in the hardware's order (DESIGN.md section 9.14 bounds the
+    difference by K 2^-23 sum |a_k| |b_k|); they agree exactly wherever every partial sum is representable."""
+    lead, n, k = _check_matmul(a, b, bias)
+    if use_kernels:
+        e = a.elements.reshape(-1, a.elements.shape[-1])
+        s = a.scales.reshape(-1, a.scales.shape[-1])
+        return CUDA.MXMatmul(e, s, a.format, b.elements, b.scales, b.format, k, bias).reshape(lead + [n])
+    x, w = a.dequantize(use_kernels=False).to(torch.float64), b.dequantize(use_kernels=False).to(torch.float64)
+    y = x.reshape(-1, k) @ w.t()
+    if bias is not None: y = y + bias.to(torch.float64)
+    return y.to(torch.float32).reshape(lead + [n])
+
+
+def mx_linear(x: torch.Tensor, weight: MXTensor, activation_format, bias: torch.Tensor = None, use_kernels: bool = True) -> torch.Tensor:
+    """A linear layer on an MX weight as it runs in deployment: ``mx_quantize(x, activation_format, -1)``, then ``mx_matmul`` with
+    ``weight`` ``[N, K]`` -- two launches, the bias added in the GEMM's epilogue (one float32 add per output)."""
+    return mx_matmul(mx_quantize(x, activation_format, -1, use_kernels=use_kernels), weight, bias, use_kernels)
 
 
 def _activated(config) -> bool:
