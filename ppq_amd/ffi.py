@@ -2079,7 +2079,8 @@ class CUDA:
     def MXMatmul(a_elements, a_scales, a_format, b_elements, b_scales, b_format, k: int, bias=None):
         """``A[M, k] . B[N, k]^T (+ bias[N])`` as float32 ``[M, N]`` on the block-scaled MFMA.  Both operands
         are packed along their last axis as ``MXPack`` leaves them: ``elements [rows, nb * B]`` and ``scales [rows, nb]``, uint8,
-        nb = ceil(k / 32).  The five float formats in any combination; MXINT8 is refused.  Non-contiguous inputs are copied."""
+        nb = ceil(k / 32).  The five float formats in any combination; MXINT8 is refused.  Non-contiguous inputs are copied, and so is an ``elements`` tensor whose
+        data does not start on a 16-byte boundary (a row slice of a 6-bit operand with an odd nb: the row pitch is 24 nb)."""
         fa, fb = mx_format_id(a_format), mx_format_id(b_format)
         k = int(k)
         if k <= 0: raise RuntimeError(_KERNEL_FAILURE + f'k must be positive, got {k}')
@@ -2098,6 +2099,8 @@ class CUDA:
             if bias.device != a_elements.device: raise RuntimeError(_KERNEL_FAILURE + 'bias is on another device')
             bias = bias.contiguous()
         a_elements, a_scales, b_elements, b_scales = a_elements.contiguous(), a_scales.contiguous(), b_elements.contiguous(), b_scales.contiguous()
+        if a_elements.data_ptr() % 16: a_elements = a_elements.clone()                   # the kernel's 16-byte loads; the allocator aligns
+        if b_elements.data_ptr() % 16: b_elements = b_elements.clone()
         out = torch.empty([m, n], dtype=torch.float32, device=a_elements.device)
         with _DeviceOf(out):
             _raise(lib.ppqhip_mx_gemm(a_elements.data_ptr(), a_scales.data_ptr(), fa, b_elements.data_ptr(), b_scales.data_ptr(), fb,

@@ -343,7 +343,7 @@ def mx_matmul(a: MXTensor, b: MXTensor, bias: torch.Tensor = None, use_kernels: 
     ``use_kernels=True``: the packed bytes go to the block-scaled MFMA as they are (``CUDA.MXMatmul``; the tensors must be on the
     GPU).  ``False``: the readable reference on any device -- ``mx_dequantize`` of both, the product in float64, rounded to float32.
     The two are NOT bit-identical: the kernel accumulates in float32 in the hardware's order (DESIGN.md section 9.14 bounds the
-    difference by K 2^-23 sum |a_k| |b_k|); they agree exactly wherever every partial sum is representable."""
+    difference by K 2^-23 sum |a_k| |b_k|); they agree exactly on an output of one non-zero term, subnormal results included."""
     lead, n, k = _check_matmul(a, b, bias)
     if use_kernels:
         e = a.elements.reshape(-1, a.elements.shape[-1])

@@ -56,6 +56,114 @@ def test_generators_hold_their_preconditions_for_the_gpu_shapes():
             assert len(np.unique(c[:, 0])) == m and len(np.unique(c[0])) == n            # every row and column has its own power of two
         assert len(seen) == G.nblocks(k)
     with pytest.raises(AssertionError, match='more than 24 bits'): G.exact_case(2, 2, 1024, 'MXFP4_E2M1', 'MXFP4_E2M1')
+    for fa, fb in G.GRID_PAIRS:
+        for shape in G.GRID_SHAPES: G.exact_case(*shape, fa, fb)
+    for fa, fb in G.EDGE_PAIRS: G.exact_case(*G.LONG_K_SHAPE, fa, fb)
+    assert [((m + 63) // 64, (n + 63) // 64) for m, n, _ in G.GRID_SHAPES] == [(2, 3), (1, 7), (3, 6), (65, 1), (1, 8)]
+    assert G.nblocks(G.LONG_K_SHAPE[2]) == 31 and G.nblocks(G.LONG_K_RANDOM_SHAPE[2]) == 130 and G.LONG_K_RANDOM_SHAPE[2] % 32 == 8
+
+
+def torch_bits(a, b, fa, fb, k) -> np.ndarray:
+    """The torch arm on CPU tensors; a -0 (one term, no accumulator behind it) is taken as +0."""
+    return R.bits(mx_matmul(tensor(a, fa, k), tensor(b, fb, k), use_kernels=False).numpy() + np.float32(0))
+
+
+@pytest.mark.parametrize('fa,fb', G.PAIRS)
+def test_table_case_and_the_torch_arm_on_it(fa, fb):
+    """Every element code of both formats, at both K and in both arrangements: the generator's preconditions hold, and
+    ``mx_dequantize``'s torch arm decodes every code as the tables do."""
+    for k in G.TABLE_KS:
+        for one_hot in ('a', 'b'):
+            a, b, want = G.table_case(fa, fb, k, one_hot)
+            hot, dense = (a, b) if one_hot == 'a' else (b, a)
+            assert hot[0].shape[0] >= k and dense[0].shape[0] == len(G.all_codes(fb if one_hot == 'a' else fa))
+            nan = np.isnan(want)
+            assert nan.any() == (fa in G.NAN_CODES or fb in G.NAN_CODES)
+            for f, line in ((fa, nan.all(axis=1)), (fb, nan.all(axis=0))): assert line.sum() >= len(G.NAN_CODES.get(f, ()))
+            got = torch_bits(a, b, fa, fb, k)
+            assert np.array_equal(got[~nan], R.bits(want.astype(np.float32))[~nan]) and np.isnan(got.view(np.float32)[nan]).all()
+
+
+def test_all_codes_and_their_values():
+    assert [len(G.all_codes(f)) for f in G.FLOAT_FORMATS] == [256, 254, 64, 64, 16]
+    for fmt in G.FLOAT_FORMATS:
+        codes = G.all_codes(fmt)
+        v = G.code_values(codes, fmt)
+        ref = P.decode_bits(codes[None, :], np.full(1, 127, np.uint8), fmt).view(np.float32).astype(np.float64)[0]
+        assert np.array_equal(np.isnan(v), np.isnan(ref)) and np.array_equal(v[~np.isnan(v)], ref[~np.isnan(v)])
+        assert np.isnan(v).sum() == len(G.NAN_CODES.get(fmt, ())) and set(codes[np.isnan(v)]) == set(G.NAN_CODES.get(fmt, ()))
+        assert np.nanmax(v) == R.table(fmt)[-1] and np.nanmin(v) == -R.table(fmt)[-1] and np.signbit(v[v == 0]).any()
+    for fmt, pair in G.NAN_NEIGHBOURS.items():
+        assert list(G.code_values(np.asarray(pair, np.uint8), fmt)) == [R.table(fmt)[-1], -R.table(fmt)[-1]]
+
+
+def _wrong_decode(monkeypatch, mutate):
+    right = P.decode_bits
+    monkeypatch.setattr(P, 'decode_bits', lambda c, scales, fmt: mutate(right, c, scales, fmt))
+
+
+def test_the_table_catches_a_wrong_decode(monkeypatch):
+    """Three decodes that are wrong the way a kernel could be, put in place of the oracle's: the table's closed form refuses each
+    (its comparison with the oracle is the comparison the GPU test makes with the kernel).  The same cases pass unmutated above."""
+    def e5m2_subnormals_as_zero(right, c, scales, fmt):
+        out = right(c, scales, fmt)
+        return np.where((c & 0x7c) == 0, out & np.uint32(0x80000000), out) if fmt == 'MXFP8_E5M2' else out
+
+    def fp6_ids_swapped(right, c, scales, fmt):
+        return right(c, scales, {'MXFP6_E3M2': 'MXFP6_E2M3', 'MXFP6_E2M3': 'MXFP6_E3M2'}.get(fmt, fmt))
+
+    def fp8_half_under_its_lanes_scale(right, c, scales, fmt):
+        """The 16-element chunk q of a 128-element K-step scaled by block q % 4 of the step, not by its own block q // 2."""
+        if P.WIDTH[fmt] != 8: return right(c, scales, fmt)
+        nb = scales.shape[-1]
+        chunk = np.arange(2 * nb)
+        block = np.minimum(chunk // 8 * 4 + chunk % 8 % 4, nb - 1)
+        return right(c.reshape(c.shape[:-2] + (2 * nb, 16)), scales[..., block], fmt).reshape(c.shape)
+
+    cases = [(e5m2_subnormals_as_zero, ('MXFP8_E5M2', 'MXFP4_E2M1'), ('MXFP6_E2M3', 'MXFP8_E5M2')),
+             (fp6_ids_swapped, ('MXFP6_E3M2', 'MXFP4_E2M1'), ('MXFP8_E4M3', 'MXFP6_E2M3')),
+             (fp8_half_under_its_lanes_scale, ('MXFP8_E4M3', 'MXFP4_E2M1'), ('MXFP6_E3M2', 'MXFP8_E5M2'))]
+    for mutate, *pairs in cases:
+        for fa, fb in pairs:
+            for k in G.TABLE_KS:
+                for one_hot in ('a', 'b'):
+                    G.table_case(fa, fb, k, one_hot)
+                    with monkeypatch.context() as mp:
+                        _wrong_decode(mp, mutate)
+                        with pytest.raises(AssertionError): G.table_case(fa, fb, k, one_hot)
+
+
+@pytest.mark.parametrize('fa,fb', G.SWEEP_PAIRS)
+def test_scale_sweep_case_and_the_torch_arm_on_it(fa, fb):
+    """Every scale code on both sides: the torch arm gives float32(2^(i + j - 254)) -- +Inf from 2^128 on, the subnormals kept, +0
+    below 2^-149 -- whatever sits on the blocks of zeros."""
+    e = np.arange(255)[:, None] + np.arange(255)[None, :] - 254
+    for fill in ('neutral', 'same'):
+        a, b, want = G.scale_sweep_case(fa, fb, G.SWEEP_K, fill)
+        assert np.array_equal(want, np.exp2(e.astype(np.float64)))
+        assert (a[1] == 127).sum() >= 255 * 4 if fill == 'neutral' else (a[1] == np.arange(255, dtype=np.uint8)[:, None]).all()
+        with np.errstate(over='ignore'): want32 = want.astype(np.float32)
+        assert np.isposinf(want32[e >= 128]).all() and (want32[e < -149] == 0).all() and (want32[e >= -149] > 0).all()
+        assert np.array_equal(torch_bits(a, b, fa, fb, G.SWEEP_K), R.bits(want32))
+
+
+@pytest.mark.parametrize('fa,fb,side,kind', G.NAN_POSITION_CASES)
+def test_nan_position_case_and_the_torch_arm_on_it(fa, fb, side, kind):
+    k = G.NAN_POSITION_K
+    a, b, clean, c, nan = G.nan_position_case(fa, fb, k, side, kind)
+    fmt, poisoned = (fa, a) if side == 'a' else (fb, b)
+    codes = P.unpack_fields(poisoned[0].reshape(2 * k, G.nblocks(k), -1), P.WIDTH[fmt]).reshape(2 * k, -1)
+    before = P.unpack_fields(clean[0].reshape(2 * k, G.nblocks(k), -1), P.WIDTH[fmt]).reshape(2 * k, -1)
+    t = np.arange(k)
+    if kind == 'code':
+        assert set(codes[2 * t, t]) == set(G.NAN_CODES[fmt]) and np.array_equal(poisoned[1], clean[1])
+        assert (codes != before).sum() <= k and set(np.argwhere(codes != before)[:, 1]) <= set(t)
+    else:
+        assert (poisoned[1][2 * t, t % G.nblocks(k)] == 0xff).all() and (poisoned[1] == 0xff).sum() == k and np.array_equal(codes, before)
+    if fmt in G.NAN_NEIGHBOURS: assert set(codes[2 * t + 1, t]) == set(G.NAN_NEIGHBOURS[fmt])
+    assert np.array_equal(nan.all(axis=1 if side == 'a' else 0), np.arange(2 * k) % 2 == 0)
+    got = torch_bits(a, b, fa, fb, k)
+    assert np.array_equal(np.isnan(got.view(np.float32)), nan) and np.array_equal(got[~nan], R.bits(c.astype(np.float32))[~nan])
 
 
 # -------------------------------------------------------------------------------------------------------- the torch arm on the CPU
