@@ -745,10 +745,29 @@ int ppqhip_mx_gemm(const uint8_t* a_elements, const uint8_t* a_scales, int a_for
                    const uint8_t* b_scales, int b_format, const float* bias, float* c, int64_t m, int64_t n, int64_t k,
                    void* stream);
 
+/* Convolution on packed MX operands (ppq_amd/mx.py mx_conv2d / mx_conv2d_packed; ADDED under ABI 4) --- */
+/* y[n, oh, ow, o] (float32: the channels-last storage of [n, o, oh, ow]) = conv2d(x[n, c, h, w], w[o, c, kh, kw]) (+ bias[o]) on
+ * v_mfma_scale_f32_16x16x128_f8f6f4, as an implicit GEMM: no im2col buffer.  Both operands are packed along axis 1 exactly as
+ * ppqhip_mx_pack leaves them (the block axis stored last): x elements [n, h, w, nbc * B] and scales [n, h, w, nbc], w elements
+ * [o, kh, kw, nbc * B] and scales [o, kh, kw, nbc], nbc = ceil(c / 32).  The reduction runs over (ky, kx, channel block) in that
+ * order, one fixed float32 accumulation order (no atomics, no split-K): two calls give identical bits, the bits of ppqhip_mx_gemm
+ * on the gathered rows, and |y - y_float64| <= K * 2^-23 * sum |x| |w| with K = kh * kw * 32 * nbc.  oh = (h + 2 pad_h -
+ * dil_h (kh - 1) - 1) / stride_h + 1, likewise ow; padding is symmetric and contributes exact zeros (it is not read); groups = 1.
+ * An output is the quiet NaN 0x7fc00000 exactly where its window covers a block of x whose scale code is 0xFF or which holds an FP8
+ * NaN code, or where its output channel of w holds one.
+ * Refused before any launch: MXINT8 and unknown formats; negative sizes; sizes, n oh ow, kh kw nbc, the blocks of x or the workgroup
+ * count above 2^31 - 1; kernel size, stride or dilation below 1; a window that does not fit the padded input (oh or ow < 1); null
+ * pointers (bias excepted); elements or y not 16-byte aligned; y overlapping any input.  n == 0 or o == 0 launches nothing; c == 0
+ * (or an input without a pixel) writes the bias (or 0). */
+int ppqhip_mx_conv2d(const uint8_t* x_elements, const uint8_t* x_scales, int x_format, const uint8_t* w_elements,
+                     const uint8_t* w_scales, int w_format, const float* bias, float* y, int64_t n, int64_t c, int64_t h, int64_t w,
+                     int64_t o, int64_t kh, int64_t kw, int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
+                     int64_t dil_h, int64_t dil_w, void* stream);
+
 /* profiling aid used by bench.py: when enabled, every kernel launch made through this library
  * on this thread is bracketed by hipEvents on its own stream; ppqhip_prof_collect() synchronises
  * those events and returns, per kernel id, launches / total ms / total algorithmic bytes. */
-#define PPQHIP_PROF_MAX_KERNELS 40
+#define PPQHIP_PROF_MAX_KERNELS 48
 typedef struct {
     char name[48];
     int64_t launches;

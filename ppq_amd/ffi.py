@@ -2108,6 +2108,48 @@ class CUDA:
         return out
 
     @ staticmethod
+    def MXConv2d(x_elements, x_scales, x_format, w_elements, w_scales, w_format, c: int, bias=None, stride=(1, 1), padding=(0, 0),
+                 dilation=(1, 1)):
+        """``conv2d(x[N, c, H, W], w[O, c, kh, kw]) (+ bias[O])`` as float32 ``[N, O, OH, OW]`` with channels-last strides, on the
+        block-scaled MFMA as an implicit GEMM.  Both operands are packed along axis 1 as ``MXPack`` leaves
+        them: x ``elements [N, H, W, nbc * B]`` / ``scales [N, H, W, nbc]``, w ``elements [O, kh, kw, nbc * B]`` / ``scales
+        [O, kh, kw, nbc]``, uint8, nbc = ceil(c / 32).  The five float formats in any combination; MXINT8 is refused.  ``stride``,
+        ``padding`` (symmetric) and ``dilation`` are (h, w) pairs.  Non-contiguous inputs are copied, and so is an ``elements`` tensor
+        whose data does not start on a 16-byte boundary."""
+        fx, fw = mx_format_id(x_format), mx_format_id(w_format)
+        c = int(c)
+        if c <= 0: raise RuntimeError(_KERNEL_FAILURE + f'c must be positive, got {c}')
+        for name, t in (('x elements', x_elements), ('x scales', x_scales), ('w elements', w_elements), ('w scales', w_scales)):
+            _check(t, torch.uint8, name + '(Expect to be UINT8)')
+            if t.dim() != 4: raise RuntimeError(_KERNEL_FAILURE + f'{name} must be 4-d, got {list(t.shape)}')
+            if t.device != x_elements.device: raise RuntimeError(_KERNEL_FAILURE + f'{name} is on another device')
+        (n, h, w), (o, kh, kw) = x_scales.shape[:3], w_scales.shape[:3]
+        for name, e, s, shape, fmt in (('x', x_elements, x_scales, [n, c, h, w], fx), ('w', w_elements, w_scales, [o, c, kh, kw], fw)):
+            eshape, sshape = mx_packed_shapes(shape, 1, fmt)
+            if list(e.shape) != eshape or list(s.shape) != sshape:
+                raise RuntimeError(_KERNEL_FAILURE + f'{name}: elements / scales of shape {list(e.shape)} / {list(s.shape)}, expected {eshape} / {sshape} for c = {c}')
+        (sh, sw), (ph, pw), (dh, dw) = ([int(v) for v in pair] for pair in (stride, padding, dilation))
+        if min(sh, sw, dh, dw) < 1 or min(ph, pw) < 0:
+            raise RuntimeError(_KERNEL_FAILURE + f'stride {(sh, sw)} and dilation {(dh, dw)} must be at least 1, padding {(ph, pw)} at least 0')
+        oh, ow = (h + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (w + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+        if oh < 1 or ow < 1:
+            raise RuntimeError(_KERNEL_FAILURE + f'a {kh} x {kw} kernel with dilation {(dh, dw)} does not fit an input of {h} x {w} padded by {(ph, pw)}')
+        if bias is not None:
+            _f32(bias, 'Bias')
+            if list(bias.shape) != [o]: raise RuntimeError(_KERNEL_FAILURE + f'bias of shape {list(bias.shape)}, expected [{o}]')
+            if bias.device != x_elements.device: raise RuntimeError(_KERNEL_FAILURE + 'bias is on another device')
+            bias = bias.contiguous()
+        x_elements, x_scales, w_elements, w_scales = x_elements.contiguous(), x_scales.contiguous(), w_elements.contiguous(), w_scales.contiguous()
+        if x_elements.data_ptr() % 16: x_elements = x_elements.clone()                   # the kernel's 16-byte loads; the allocator aligns
+        if w_elements.data_ptr() % 16: w_elements = w_elements.clone()
+        out = torch.empty([n, oh, ow, o], dtype=torch.float32, device=x_elements.device)
+        with _DeviceOf(out):
+            _raise(lib.ppqhip_mx_conv2d(x_elements.data_ptr(), x_scales.data_ptr(), fx, w_elements.data_ptr(), w_scales.data_ptr(), fw,
+                                        bias.data_ptr() if bias is not None else 0, out.data_ptr(), n, c, h, w, o, kh, kw, sh, sw, ph, pw,
+                                        dh, dw, _stream()))
+        return out.permute(0, 3, 1, 2)
+
+    @ staticmethod
     def Sync():
         """Synchronize device (ffi.py:347-350)."""
         torch.cuda.synchronize()

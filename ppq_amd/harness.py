@@ -292,6 +292,7 @@ class TorchExecutor:
         self._plan_cache: Dict[tuple, list] = {}
         self._fused: Dict[tuple, torch.Tensor] = {}
         self._delegates: Dict[object, Callable] = {}
+        self._overrides: Dict[str, Callable] = {}     # operation name -> fn(op, raw inputs): register_operation_override
         self.fuse_epilogues = True                    # conv bias [+ residual Add] + Relu in ONE launch: plan_epilogues
         self._epilogue_cache: Dict[tuple, dict] = {}
         self.channels_last = False                    # see use_channels_last()
@@ -321,6 +322,18 @@ class TorchExecutor:
 
     def remove_quantize_delegate(self, config) -> None:
         self._delegates.pop(config, None)
+
+    def register_operation_override(self, op_name: str, fn: Callable) -> None:
+        """Run operation ``op_name`` as ``fn(op, raw_inputs)`` -- a tensor or a list of tensors, one per output -- in place of the
+        quantisation of its inputs and its torch forward (a deployed kernel that does both: ``mx.deploy_graph_mx``).  The output
+        configs are applied as usual.  A forward that hooks the operation runs the simulated path for it, so calibration and the
+        analysis passes see what they see without the override; an overridden operation joins no epilogue group."""
+        if op_name not in self._graph.operations: raise KeyError(f'register_operation_override: the graph has no operation {op_name!r}')
+        if not callable(fn): raise TypeError(f'register_operation_override: fn must be callable, got {type(fn)}')
+        self._overrides[op_name] = fn
+
+    def remove_operation_override(self, op_name: str) -> None:
+        self._overrides.pop(op_name, None)
 
     def quantize_function(self, tensor: torch.Tensor, config=None) -> torch.Tensor:
         if self._delegates and config in self._delegates:          # torch.py:610-613
@@ -360,11 +373,14 @@ class TorchExecutor:
             raw_in = [v.value for v in op.inputs]
             if any(x is None for x in raw_in):
                 raise ValueError(f'partial_graph_forward: input of {op.name} was not fed')
-            if isinstance(op, QuantableOperation):
-                qin = [self._quantize_parameter(v, c) if v.is_parameter else self.quantize_function(x, c)
-                       for v, x, c in zip(op.inputs, raw_in, op.config.input_quantization_config)]
-            else: qin = raw_in
-            outs = _forward(op, qin)
+            override = self._overrides.get(op.name)
+            if override is not None: outs = override(op, raw_in)
+            else:
+                if isinstance(op, QuantableOperation):
+                    qin = [self._quantize_parameter(v, c) if v.is_parameter else self.quantize_function(x, c)
+                           for v, x, c in zip(op.inputs, raw_in, op.config.input_quantization_config)]
+                else: qin = raw_in
+                outs = _forward(op, qin)
             outs = list(outs) if isinstance(outs, (list, tuple)) else [outs]
             if isinstance(op, QuantableOperation):
                 outs = [self.quantize_function(y, c) for y, c in zip(outs, op.config.output_quantization_config)]
@@ -434,13 +450,15 @@ class TorchExecutor:
         states = tuple(c.state for op in operations if isinstance(op, QuantableOperation)
                        for c in (*op.config.input_quantization_config, *op.config.output_quantization_config))
         sig = (tuple(op.name for op in operations), tuple((k, id(h)) for k, h in hooks.items()) if hooks else (),
-               tuple(output_names or ()), tuple(id(c) for c in self._delegates), states)
+               tuple(output_names or ()), tuple(id(c) for c in self._delegates), states, tuple(sorted(self._overrides)))
         plan = self._epilogue_cache.get(sig)
         if plan is None:
             delegates = self._delegates
 
             def passes_through(c): return not QuantizationStates.is_activated(c.state) and c not in delegates
             groups = plan_epilogues(operations, hooks, set(self._graph.outputs) | set(output_names or ()), passes_through)
+            if self._overrides:                       # an operation that runs its override is a member of no group
+                groups = [g for g in groups if not any(m.name in self._overrides and not (hooks and m.name in hooks) for m in g.ops)]
             plan = {g.ops[0].name: g for g in groups}
             if len(self._epilogue_cache) >= 8: self._epilogue_cache.pop(next(iter(self._epilogue_cache)))
             self._epilogue_cache[sig] = plan
@@ -572,11 +590,14 @@ class TorchExecutor:
                         if v.name != hidden: cache[v.name] = vals[v.name]
                 continue
             raw_in = [v.value if v.is_parameter else cache[v.name] for v in op.inputs]
-            if isinstance(op, QuantableOperation):
-                qin = [self._quantize_parameter(v, c) if v.is_parameter else self.quantize_function(x, c)
-                       for v, x, c in zip(op.inputs, raw_in, op.config.input_quantization_config)]
-            else: qin = raw_in
-            outs = _forward(op, qin)
+            override = self._overrides.get(op.name)
+            if override is not None: outs = override(op, raw_in)
+            else:
+                if isinstance(op, QuantableOperation):
+                    qin = [self._quantize_parameter(v, c) if v.is_parameter else self.quantize_function(x, c)
+                           for v, x, c in zip(op.inputs, raw_in, op.config.input_quantization_config)]
+                else: qin = raw_in
+                outs = _forward(op, qin)
             outs = list(outs) if isinstance(outs, (list, tuple)) else [outs]
             if isinstance(op, QuantableOperation):
                 outs = [self.quantize_function(y, c) for y, c in zip(outs, op.config.output_quantization_config)]
@@ -621,13 +642,16 @@ class TorchExecutor:
             raw_in = [v.value for v in op.inputs]
             qin = raw_in
             quantable = isinstance(op, QuantableOperation)
-            if quantable:
-                in_cfgs = list(op.config.input_quantization_config)
-                qin = [self._quantize_parameter(v, c) if v.is_parameter else self.quantize_function(x, c)
-                       for v, x, c in zip(op.inputs, raw_in, in_cfgs)]
-            if hook is not None:
-                qin = hook.pre_forward_hook(inputs=raw_in, quant_inputs=qin, quant_configs=in_cfgs)
-            outs = _forward(op, qin)
+            override = self._overrides.get(op.name) if hook is None else None        # a hooked operation runs the simulation
+            if override is not None: outs = override(op, raw_in)
+            else:
+                if quantable:
+                    in_cfgs = list(op.config.input_quantization_config)
+                    qin = [self._quantize_parameter(v, c) if v.is_parameter else self.quantize_function(x, c)
+                           for v, x, c in zip(op.inputs, raw_in, in_cfgs)]
+                if hook is not None:
+                    qin = hook.pre_forward_hook(inputs=raw_in, quant_inputs=qin, quant_configs=in_cfgs)
+                outs = _forward(op, qin)
             outs = list(outs) if isinstance(outs, (list, tuple)) else [outs]
             fp_outs = outs
             if quantable:

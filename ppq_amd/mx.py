@@ -14,7 +14,9 @@ give identical bits.
 (``MXTensor``; the packed contract is DESIGN.md section 9.13, restated by ``tests/mx_pack_reference.py``), cut from the same rounded
 patterns as the fake quant, so that ``mx_dequantize(mx_quantize(x))`` has the bits of ``mx_fake_quant(x)``.  ``export_graph_mx`` packs
 every MX weight of a graph in one launch.  ``mx_matmul`` / ``mx_linear`` multiply two packed tensors on the block-scaled MFMA
-(``ppq_amd/csrc/mx_gemm.hip``): the hardware in the loop of both the simulation and the export.
+(``ppq_amd/csrc/mx_gemm.hip``), ``mx_conv2d`` / ``mx_conv2d_packed`` convolve them (``mx_conv.hip``, an implicit
+GEMM; section 9.15): the hardware in the loop of both the simulation and the export.  ``deploy_graph_mx`` puts the Conv / Gemm /
+MatMul of a ``quantize_graph_mx`` graph on those kernels through the executor's operation overrides.
 
 ``quantize_graph_mx`` puts MX on the inputs of Conv / Gemm / MatMul of a harness graph through the executor's delegator seam
 (``TorchExecutor.register_quantize_delegate``): ``MXDelegator`` follows the reference's delegator protocol
@@ -286,6 +288,10 @@ class MXTensor:
         """``mx_matmul(self, other, bias, use_kernels)``: ``self . other^T`` in float32."""
         return mx_matmul(self, other, bias, use_kernels)
 
+    def conv2d(self, weight: 'MXTensor', bias: torch.Tensor = None, stride=1, padding=0, dilation=1, use_kernels: bool = True) -> torch.Tensor:
+        """``mx_conv2d_packed(self, weight, bias, stride, padding, dilation, use_kernels)``: ``self`` is the activation."""
+        return mx_conv2d_packed(self, weight, bias, stride, padding, dilation, use_kernels)
+
     def to_dict(self) -> dict:
         """Tensors, ints and the format's name only: ``torch.save`` round-trips it (``from_dict``)."""
         return {'format': self.format.name, 'shape': torch.tensor(self.shape, dtype=torch.int64), 'axis': self.axis,
@@ -359,6 +365,71 @@ def mx_linear(x: torch.Tensor, weight: MXTensor, activation_format, bias: torch.
     """A linear layer on an MX weight as it runs in deployment: ``mx_quantize(x, activation_format, -1)``, then ``mx_matmul`` with
     ``weight`` ``[N, K]`` -- two launches, the bias added in the GEMM's epilogue (one float32 add per output)."""
     return mx_matmul(mx_quantize(x, activation_format, -1, use_kernels=use_kernels), weight, bias, use_kernels)
+
+
+# ---- convolution on the packed tensors (DESIGN.md section 9.15) --------------------------------------------------------------------
+def _pair(value, name: str, least: int):
+    """An int or a pair of ints (h, w), each at least ``least``."""
+    pair = (value, value) if isinstance(value, int) and not isinstance(value, bool) else tuple(value)
+    if len(pair) != 2 or not all(isinstance(v, int) and not isinstance(v, bool) for v in pair):
+        raise RuntimeError(f'mx_conv2d: {name} must be an int or a pair of ints, got {value!r}')
+    if min(pair) < least: raise RuntimeError(f'mx_conv2d: {name} must be at least {least}, got {value!r}')
+    return pair
+
+
+def _check_conv(x, w, bias, stride, padding, dilation):
+    """The argument checks of ``mx_conv2d_packed``; returns (stride, padding, dilation, (OH, OW)), each a pair."""
+    for name, t in (('x', x), ('w', w)):
+        if not isinstance(t, MXTensor): raise TypeError(f'mx_conv2d: {name}: expected an MXTensor, got {type(t)}')
+        if not t.format.is_float: raise RuntimeError(f'mx_conv2d: {name} is {t.format.name}, which is not an operand type of the scaled MFMA')
+        if len(t.shape) != 4: raise RuntimeError(f'mx_conv2d: {name} must be 4-d, got shape {list(t.shape)}')
+        if t.axis != 1: raise RuntimeError(f'mx_conv2d: {name} of shape {list(t.shape)} is packed along axis {t.axis}, not along its channels (axis 1)')
+    if x.shape[1] != w.shape[1]:
+        raise RuntimeError(f'mx_conv2d: C mismatch: x has {x.shape[1]} channels, w has {w.shape[1]} (groups must be 1)')
+    if x.device != w.device: raise RuntimeError(f'mx_conv2d: x is on {x.device}, w on {w.device}')
+    if 0 in x.shape or 0 in w.shape: raise RuntimeError(f'mx_conv2d: empty operand: x {list(x.shape)}, w {list(w.shape)}')
+    stride, padding, dilation = _pair(stride, 'stride', 1), _pair(padding, 'padding', 0), _pair(dilation, 'dilation', 1)
+    out = tuple((x.shape[2 + i] + 2 * padding[i] - dilation[i] * (w.shape[2 + i] - 1) - 1) // stride[i] + 1 for i in range(2))
+    if min(out) < 1:
+        raise RuntimeError(f'mx_conv2d: a {w.shape[2]} x {w.shape[3]} kernel with dilation {dilation} does not fit an input of '
+                           f'{x.shape[2]} x {x.shape[3]} padded by {padding}')
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32: raise RuntimeError('mx_conv2d: bias must be a float32 tensor')
+        if list(bias.shape) != [w.shape[0]]: raise RuntimeError(f'mx_conv2d: bias of shape {list(bias.shape)}, expected [{w.shape[0]}]')
+    return stride, padding, dilation, out
+
+
+def mx_conv2d_packed(x: MXTensor, w: MXTensor, bias: torch.Tensor = None, stride=1, padding=0, dilation=1, use_kernels: bool = True) -> torch.Tensor:
+    """``conv2d(x, w) (+ bias)`` in float32: ``x`` is ``[N, C, H, W]``, ``w`` is ``[O, C, kh, kw]`` (a Conv weight as
+    ``export_graph_mx`` leaves it), both packed along axis 1 in any of the five float formats; ``stride``, ``padding`` (symmetric, as
+    ``F.conv2d`` takes it) and ``dilation`` are ints or (h, w) pairs, groups is 1.  The result is ``[N, O, OH, OW]``.
+    ``use_kernels=True``: the packed bytes go to the block-scaled MFMA as they are, the rows of the implicit GEMM gathered by address
+    (``CUDA.MXConv2d``; the tensors must be on the GPU); the result has channels-last strides.  ``False``: the readable reference
+    on any device -- ``mx_dequantize`` of both, the windows gathered by slicing, the product in float64, rounded to float32.
+    As for ``mx_matmul`` the two are not bit-identical (DESIGN.md section 9.15: K 2^-23 sum |x| |w| with K = kh kw 32 ceil(C / 32));
+    the kernel has the bits of ``mx_matmul`` on the gathered rows."""
+    (sh, sw), (ph, pw), (dh, dw), (oh, ow) = _check_conv(x, w, bias, stride, padding, dilation)
+    if use_kernels:
+        return CUDA.MXConv2d(x.elements, x.scales, x.format, w.elements, w.scales, w.format, x.shape[1], bias, (sh, sw), (ph, pw), (dh, dw))
+    n, c, _, _ = x.shape
+    o, _, kh, kw = w.shape
+    xf = torch.nn.functional.pad(x.dequantize(use_kernels=False).to(torch.float64), (pw, pw, ph, ph))
+    wf = w.dequantize(use_kernels=False).to(torch.float64)
+    taps = [xf[:, :, ky * dh: ky * dh + (oh - 1) * sh + 1: sh, kx * dw: kx * dw + (ow - 1) * sw + 1: sw] for ky in range(kh) for kx in range(kw)]
+    cols = torch.stack(taps, dim=1).permute(0, 3, 4, 1, 2).reshape(n * oh * ow, kh * kw * c)          # rows (n, oy, ox), K (ky, kx, c)
+    y = cols @ wf.permute(0, 2, 3, 1).reshape(o, kh * kw * c).t()
+    if bias is not None: y = y + bias.to(torch.float64)
+    return y.to(torch.float32).reshape(n, oh, ow, o).permute(0, 3, 1, 2)
+
+
+def mx_conv2d(x: torch.Tensor, weight: MXTensor, activation_format, bias: torch.Tensor = None, stride=1, padding=0, dilation=1,
+              groups: int = 1, use_kernels: bool = True) -> torch.Tensor:
+    """A convolution on an MX weight as it runs in deployment: ``mx_quantize(x, activation_format, 1)`` -- ``x`` ``[N, C, H, W]``,
+    contiguous or channels-last --, then ``mx_conv2d_packed`` with ``weight`` ``[O, C, kh, kw]``: two launches, the bias added in the
+    kernel's epilogue (one float32 add per output)."""
+    if groups != 1: raise RuntimeError(f'mx_conv2d: groups must be 1, got {groups}')
+    if isinstance(x, torch.Tensor) and x.dim() != 4: raise RuntimeError(f'mx_conv2d: x must be 4-d [N, C, H, W], got shape {list(x.shape)}')
+    return mx_conv2d_packed(mx_quantize(x, activation_format, 1, use_kernels=use_kernels), weight, bias, stride, padding, dilation, use_kernels)
 
 
 def _activated(config) -> bool:
@@ -512,3 +583,86 @@ def export_graph_mx(graph, delegators=None, use_kernels: bool = True) -> Dict[st
     items = [(v if MXPackPlan.accepts(v, axis) else v.contiguous(), fmt, axis) for v, fmt, axis in items]
     packed = MXPackPlan(items).run()
     return {n: MXTensor(fmt, v.shape, axis, e, s) for n, (v, fmt, axis), (e, s) in zip(names, items, packed)}
+
+
+# ---- the graph on the hardware path -----------------------------------------------------------------------
+class MXDeployment:
+    """What ``deploy_graph_mx`` did: ``deployed`` -- the names of the operations that run on the block-scaled MFMA --, ``skipped`` --
+    name -> reason for every MX operation that stays on the simulated path --, ``weights`` -- the packed weights
+    (``export_graph_mx``).  ``refresh()`` packs the weights again after they changed; ``remove()`` drops the overrides, after which
+    the executor runs the simulation again."""
+    def __init__(self, graph, executor, delegators=None, use_kernels: bool = True):
+        self.graph, self.executor, self.delegators, self.use_kernels = graph, executor, delegators, use_kernels
+        self.deployed: List[str] = []
+        self.skipped: Dict[str, str] = {}
+        self.weights: Dict[str, MXTensor] = {}
+        self._operands: Dict[str, MXTensor] = {}      # operation name -> its weight as the kernel takes it
+        self.refresh()
+
+    def _format(self, config) -> Optional[MXFormat]:
+        if self.delegators is not None:
+            d = self.delegators.get(config)
+            return d.format if isinstance(d, MXDelegator) else None
+        name = getattr(config, 'detail', {}).get('MX_FORMAT')
+        return MXFormat.of(name) if name is not None else None
+
+    def _plan(self, op):
+        """(run, operand) of an eligible operation, or the reason it is not one; None for an operation without MX inputs."""
+        cfgs = op.config.input_quantization_config
+        formats = [self._format(c) for c in cfgs[:2]]
+        if len(formats) < 2 or all(f is None for f in formats): return None
+        x_var, w_var = op.inputs[0], op.inputs[1]
+        if x_var.is_parameter or not w_var.is_parameter: return 'the operands are not an activation and a parameter'
+        afmt, wfmt = formats
+        if afmt is None or wfmt is None: return 'only one operand carries an MX format'
+        if not (afmt.is_float and wfmt.is_float): return 'MXINT8 is not an operand type of the scaled MFMA'
+        if not (_activated(cfgs[0]) and _activated(cfgs[1])): return 'an MX config is not activated'
+        packed = self.weights.get(w_var.name)
+        if packed is None: return 'export_graph_mx left the weight out'
+        use_kernels = self.use_kernels
+        if op.type == 'Conv':
+            a = op.attributes
+            if a.get('group', 1) != 1: return 'a grouped convolution'
+            if len(packed.shape) != 4: return f'a {len(packed.shape)}-d Conv weight'
+            stride, padding, operand = a.get('strides', 1), a.get('pads', 0), packed
+
+            def run(op, x):
+                return mx_conv2d(x[0], self._operands[op.name], afmt, x[2] if len(x) > 2 else None, stride, padding, use_kernels=use_kernels)
+        else:
+            if len(packed.shape) != 2: return f'a {len(packed.shape)}-d {op.type} weight'
+            # a MatMul weight [in, out] is packed along axis 0: its bytes are those of [out, in] packed along axis 1
+            operand = packed if op.type == 'Gemm' else MXTensor(packed.format, packed.shape[::-1], 1, packed.elements, packed.scales)
+
+            def run(op, x):
+                return mx_linear(x[0], self._operands[op.name], afmt, x[2] if len(x) > 2 else None, use_kernels=use_kernels)
+        return run, operand
+
+    def refresh(self) -> None:
+        """Pack the weights as they are now and (re)register the overrides."""
+        from .harness import QuantableOperation
+        self.remove()
+        self.weights = export_graph_mx(self.graph, self.delegators, self.use_kernels)
+        for name, op in self.graph.operations.items():
+            if not isinstance(op, QuantableOperation) or op.type not in MX_OPERATIONS: continue
+            plan = self._plan(op)
+            if plan is None: continue
+            if isinstance(plan, str):
+                self.skipped[name] = plan
+                continue
+            run, self._operands[name] = plan
+            self.executor.register_operation_override(name, run)
+            self.deployed.append(name)
+
+    def remove(self) -> None:
+        for name in self.deployed: self.executor.remove_operation_override(name)
+        self.deployed, self.skipped, self._operands = [], {}, {}
+
+
+def deploy_graph_mx(graph, executor, delegators=None, use_kernels: bool = True) -> MXDeployment:
+    """Put the MX operations of a ``quantize_graph_mx`` graph on the hardware path: the weights are packed (``export_graph_mx``) and
+    every eligible operation gets an operation override on ``executor`` that quantises its activation and runs the packed kernel --
+    a Conv with ``group`` 1 ``mx_conv2d`` (the activation delegator's format, the bias, ``strides`` and ``pads``), a Gemm ``mx_linear``,
+    a MatMul with a 2-D parameter on the right ``mx_linear`` on the weight's own bytes.  MXINT8 on either side, grouped convolutions,
+    a MatMul of two activations and weights the export left out stay on the simulated path (``.skipped``).  ``delegators``: what
+    ``quantize_graph_mx`` returned (default: the formats recorded in the configs).  ``use_kernels=False``: the torch arms, any device."""
+    return MXDeployment(graph, executor, delegators, use_kernels)
