@@ -43,7 +43,8 @@ typedef enum {
 #define PPQHIP_ABI_VERSION 4   /* 2: quantile hints (round 3); 3: *_multi LSQ / min-max entry points, quantile sequence (round 4);
                                 * 4: ppqhip_minmax_c_multi carries its job table in the kernel arguments (no device table / upload); split per-tensor LSQ
  *    backward (ppqhip_fq_linear_t_bwd_main / ppqhip_lsq_finish_multi) (round 5); the convolution epilogues
- *    (ppqhip_bias_act / ppqhip_bias_add_act) were ADDED under 4: no existing signature changed, and a library without
+ *    (ppqhip_bias_act / ppqhip_bias_add_act) and their statistics variants (ppqhip_bias_act_stats /
+ *    ppqhip_bias_add_act_stats) were ADDED under 4: no existing signature changed, and a library without
  *    them fails at load (_lib.py resolves every declared symbol) */
 
 /* library / device introspection ------------------------------------------------------------- */
@@ -420,6 +421,26 @@ int ppqhip_bias_act(float* y, const float* bias, int64_t n, int64_t num_channel,
  * out[i] = act(a[i] + b[i])  -- operand order of the graph's Add(a, b) */
 int ppqhip_bias_add_act(float* a, const float* bias_a, float* b, const float* bias_b, float* out,
                         int64_t n, int64_t num_channel, int64_t elem_per_channel, int relu, void* stream);
+
+/* The same two launches for a CALIBRATION forward: what they store is what the observers observe, so every stored tensor may
+ * come with a sink -- the observer's own running-range accumulator -- and the values are folded from the registers they are
+ * stored from instead of being read back by the observers' end-of-forward launch.
+ *   stored   bit for bit what ppqhip_bias_act / ppqhip_bias_add_act store (same arithmetic, same operand order);
+ *   folded   every stored element of a tensor, once, into that tensor's slots = float[ppqhip_minmax_slots()][2], as
+ *            ppqhip_minmax_t_slots accumulates them (same comparison: NaN dropped, -0.0 < +0.0).  After
+ *            ppqhip_minmax_slots_finish the range equals, bit for bit, the one that entry point gives on the stored tensor;
+ *            which slot a value lands in is unspecified, as it is there.
+ * A null slots pointer folds nothing for that tensor; slots_b needs bias_b (else b is not stored).  Workgroup g folds into
+ * slot g by plain read-modify-write: no atomics, nothing synchronises, launches on one stream accumulate in order, capturable
+ * into a HIP graph.
+ * Returns PPQHIP_NOT_FUSED -- NOTHING was launched and nothing is wrong -- when the kernel has no path for the call: a pointer
+ * that is not 16-B aligned, n < 4, no sink at all.  The caller then runs the plain entry point and observes as before. */
+#define PPQHIP_NOT_FUSED 1
+int ppqhip_bias_act_stats(float* y, const float* bias, int64_t n, int64_t num_channel, int64_t elem_per_channel,
+                          int relu, float* slots_y, void* stream);
+int ppqhip_bias_add_act_stats(float* a, const float* bias_a, float* b, const float* bias_b, float* out,
+                              int64_t n, int64_t num_channel, int64_t elem_per_channel, int relu,
+                              float* slots_a, float* slots_b, float* slots_out, void* stream);
 
 /* AdaRound (MI355X-native addition; ppq_amd/adaround.py) ------------------------------------------- */
 /* One job per AdaRound weight of a block; a per-tensor job has num_channel = 1, elem_per_channel = n.  `jobs` is a HOST

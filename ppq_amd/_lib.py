@@ -21,6 +21,9 @@ c_vp = ctypes.c_void_p
 ABI_VERSION = 4              # == PPQHIP_ABI_VERSION of include/ppq_hip.h; a library of any other version is refused below
 
 
+NOT_FUSED = 1                # PPQHIP_NOT_FUSED: a statistics epilogue launched nothing, the caller takes the plain path
+
+
 class ProfEntry(ctypes.Structure):
     _fields_ = [('name', ctypes.c_char * 48), ('launches', ctypes.c_int64),
                 ('total_ms', ctypes.c_double), ('total_bytes', ctypes.c_double)]
@@ -45,6 +48,9 @@ PROTOTYPES = {
     'ppqhip_lsq_finish_multi': (c_int, [c_vp, c_int, c_vp]),
     'ppqhip_bias_act': (c_int, [c_f32p, c_f32p, c_i64, c_i64, c_i64, c_int, c_vp]),
     'ppqhip_bias_add_act': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_i64, c_i64, c_int, c_vp]),
+    'ppqhip_bias_act_stats': (c_int, [c_f32p, c_f32p, c_i64, c_i64, c_i64, c_int, c_f32p, c_vp]),
+    'ppqhip_bias_add_act_stats': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_i64, c_i64, c_int, c_f32p, c_f32p,
+                                          c_f32p, c_vp]),
     'ppqhip_fq_float_t': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_int, c_int, c_flt, c_flt, c_int, c_vp]),
     'ppqhip_fq_float_c': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_i64, c_i64, c_int, c_int, c_flt, c_flt,
                                   c_int, c_vp]),

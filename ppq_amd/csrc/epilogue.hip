@@ -17,7 +17,19 @@
 // linear.hip's tile kernels), one workgroup per tile, grid sized to the tensor.  No atomics, no inter-workgroup sync: the
 // launch only enqueues on `stream` and is capturable into a HIP graph.  n % 4 trailing elements (odd tensors) are done by
 // workgroup 0; a tensor with a pointer that is not 16-B aligned takes the element-wise kernel.
+//
+// Statistics variant (ppqhip_bias_act_stats / ppqhip_bias_add_act_stats): during calibration every tensor these launches store
+// is observed, and the observers' end-of-forward launch would read it back from HBM although the epilogue held every value
+// in registers a moment earlier.  epilogue_stats_kernel runs the same per-float4 code (epilogue_vec / epilogue_elem: same
+// operand order, so the stored tensors are bit for bit the plain kernels') and hands what it stores to one SINK per
+// tensor -- the observer's own accumulator of the running range, float[minmax_slots][2], folded with the functions of
+// minmax_fold.hpp that reduce.hip's kernels use.  Its shape is that of the slot-owning statistics kernels instead of one
+// workgroup per tile: min(tiles, 2 per CU) workgroups of kEpStatBlock lanes, each walking a contiguous tile range with two
+// ping-pong register tiles and folding ONCE, at its end, into slot blockIdx.x -- a plain read-modify-write with one owner
+// per launch, stream ordered across launches.  No atomics on global memory, nothing synchronises: capturable into a HIP
+// graph like the plain launches.  (Histogram sinks for phase 2 of KL / MSE were measured and left out: DESIGN.md section 6.)
 #include "common.hpp"
+#include "minmax_fold.hpp"
 
 namespace ppqhip {
 namespace {
@@ -69,16 +81,36 @@ __device__ __forceinline__ float4 bias4(const float* __restrict__ bias, uint32_t
                        bias[channel_of(i + 3, epc, nc)]);
 }
 
+// What one position stores (for the statistics variant): a (bias_act: y), b (BIAS_B only), out (RESID only).
+template <typename T>
+struct EpStored { T a, b, out; };
+
 // one element i (channel from the per-element geometry `epc`)
 template <bool RESID, bool BIAS_B, bool RELU>
-__device__ __forceinline__ void epilogue_elem(const EpArgs& p, uint32_t i, const FastDiv& epc) {
+__device__ __forceinline__ EpStored<float> epilogue_elem(const EpArgs& p, uint32_t i, const FastDiv& epc) {
+    EpStored<float> s{};
     const uint32_t c = channel_of(i, epc, p.nc);
     const float x = p.a[i] + p.bias_a[c];
-    if (!RESID) { p.a[i] = act(x, RELU); return; }
-    p.a[i] = x;
+    if (!RESID) { p.a[i] = s.a = act(x, RELU); return s; }
+    p.a[i] = s.a = x;
     float y = p.b[i];
-    if (BIAS_B) { y = y + p.bias_b[c]; p.b[i] = y; }
-    p.out[i] = act(x + y, RELU);
+    if (BIAS_B) { y = y + p.bias_b[c]; p.b[i] = s.b = y; }
+    p.out[i] = s.out = act(x + y, RELU);
+    return s;
+}
+
+// float4 number vv from its loaded operands (a, b) and biases (ba, bb)
+template <bool RESID, bool BIAS_B, bool RELU>
+__device__ __forceinline__ EpStored<float4> epilogue_vec(float4* a4, float4* b4, float4* o4, uint32_t vv, const float4& a,
+                                                         const float4& ba, const float4& b, const float4& bb) {
+    EpStored<float4> s{};
+    const float4 x = add4(a, ba);
+    if (!RESID) { a4[vv] = s.a = act4<RELU>(x); return s; }
+    a4[vv] = s.a = x;
+    float4 y = b;
+    if (BIAS_B) { y = add4(y, bb); b4[vv] = s.b = y; }
+    o4[vv] = s.out = act4<RELU>(add4(x, y));
+    return s;
 }
 
 // RESID = false: a = act(a + bias_a[c]).  RESID = true: a += bias_a[c]; (BIAS_B) b += bias_b[c]; out = act(a + b).
@@ -89,7 +121,7 @@ __global__ __launch_bounds__(kBlock) void epilogue_kernel(EpArgs p) {
     float4* a4 = reinterpret_cast<float4*>(p.a);
     float4* b4 = reinterpret_cast<float4*>(p.b);
     float4* o4 = reinterpret_cast<float4*>(p.out);
-    float4 a[U], ba[U], b[U], bb[U];
+    float4 a[U], ba[U], b[U]{}, bb[U]{};
 #pragma unroll
     for (int k = 0; k < U; k++) {
         const uint32_t vv = min(base + k * kBlock, p.nvec - 1);      // clamped: all loads issue back to back
@@ -102,12 +134,7 @@ __global__ __launch_bounds__(kBlock) void epilogue_kernel(EpArgs p) {
     for (int k = 0; k < U; k++) {
         const uint32_t vv = base + k * kBlock;
         if (vv >= p.nvec) continue;
-        const float4 x = add4(a[k], ba[k]);
-        if (!RESID) { a4[vv] = act4<RELU>(x); continue; }
-        a4[vv] = x;
-        float4 y = b[k];
-        if (BIAS_B) { y = add4(y, bb[k]); b4[vv] = y; }
-        o4[vv] = act4<RELU>(add4(x, y));
+        epilogue_vec<RESID, BIAS_B, RELU>(a4, b4, o4, vv, a[k], ba[k], b[k], bb[k]);
     }
     if (!PLANE && blockIdx.x == 0 && (int)threadIdx.x < p.ntail)
         epilogue_elem<RESID, BIAS_B, RELU>(p, p.tail + threadIdx.x, p.epc);
@@ -146,6 +173,109 @@ void launch_epilogue(EpArgs p, int64_t n, int64_t C, int64_t epc, bool aligned, 
 #undef PPQ_LAUNCH_EP
 }
 
+// ---- the statistics variant ------------------------------------------------------------------------------------------
+// One min/max sink per stored tensor: index 0 = a (bias_act: y), 1 = b (BIAS_B only), 2 = out (RESID only);
+// nullptr: absent.  slots[k] is the observer's float[minmax_slots][2].
+struct EpSinks { float* slots[3]; };
+constexpr int kEpStatBlock = 512;              // lanes per workgroup
+constexpr int kEpStatWgPerCu = 2;              // co-resident workgroups per CU: the grid cap (2 * CUs <= minmax slots)
+
+// Same arithmetic as epilogue_kernel / its scalar tail; tiles of kEpStatBlock * U float4.  The host guarantees
+// gridDim.x <= tiles (every workgroup owns at least one tile), 16-B aligned pointers and nvec >= 1.
+template <int U, bool RESID, bool BIAS_B, bool RELU, bool PLANE>
+__global__ __launch_bounds__(kEpStatBlock, (kEpStatBlock * kEpStatWgPerCu + 255) / 256)
+void epilogue_stats_kernel(EpArgs p, EpSinks sk) {
+    __shared__ float lds[32];
+    constexpr int NS = RESID ? 3 : 1;
+    constexpr uint32_t kTile = (uint32_t)kEpStatBlock * U;
+    const uint32_t G = gridDim.x, g = blockIdx.x;
+    const uint32_t full = p.nvec / kTile, tiles = full + (p.nvec > full * kTile ? 1u : 0u);
+    uint32_t t, t_end;
+    even_split(tiles, G, g, t, t_end);
+    float4* a4 = reinterpret_cast<float4*>(p.a);
+    float4* b4 = reinterpret_cast<float4*>(p.b);
+    float4* o4 = reinterpret_cast<float4*>(p.out);
+
+    // sink k is live when the kernel stores its tensor and the caller gave it a destination (workgroup uniform)
+    bool live[NS];
+    float mn[NS], mx[NS];
+#pragma unroll
+    for (int k = 0; k < NS; k++) {
+        live[k] = sk.slots[k] != nullptr && (k != 1 || BIAS_B);
+        mn[k] = INFINITY; mx[k] = -INFINITY;
+    }
+    auto feed4 = [&](const EpStored<float4>& s) {
+        if (live[0]) minmax_fold4(mn[0], mx[0], s.a);
+        if (RESID) {
+            if (BIAS_B && live[1]) minmax_fold4(mn[1], mx[1], s.b);
+            if (live[NS - 1]) minmax_fold4(mn[NS - 1], mx[NS - 1], s.out);
+        }
+    };
+    auto feed1 = [&](const EpStored<float>& s) {
+        if (live[0]) minmax_fold1(mn[0], mx[0], s.a);
+        if (RESID) {
+            if (BIAS_B && live[1]) minmax_fold1(mn[1], mx[1], s.b);
+            if (live[NS - 1]) minmax_fold1(mn[NS - 1], mx[NS - 1], s.out);
+        }
+    };
+
+    struct Tile { float4 a[U], ba[U], b[U], bb[U]; };
+    auto fetch = [&](Tile& T, uint32_t tile) {                         // a full tile: no bounds logic
+        const uint32_t base = tile * kTile + threadIdx.x;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint32_t vv = base + u * kEpStatBlock;
+            T.a[u] = a4[vv];
+            T.ba[u] = bias4<PLANE>(p.bias_a, vv, p.epc, p.nc);
+            if (RESID) T.b[u] = b4[vv];
+            if (BIAS_B) T.bb[u] = bias4<PLANE>(p.bias_b, vv, p.epc, p.nc);
+        }
+    };
+    auto consume = [&](const Tile& T, uint32_t tile) {
+        const uint32_t base = tile * kTile + threadIdx.x;
+#pragma unroll
+        for (int u = 0; u < U; u++)
+            feed4(epilogue_vec<RESID, BIAS_B, RELU>(a4, b4, o4, base + u * kEpStatBlock, T.a[u], T.ba[u], T.b[u], T.bb[u]));
+    };
+    const uint32_t tf = min(t_end, full);                              // full tiles [t, tf)
+    if (t < tf) {
+        // ping-pong between two register tiles; the prefetch index is clamped (the last tile of the range is loaded twice,
+        // before anything is stored to it), so the loads stay unconditional straight-line code
+        Tile ta{}, tb{};
+        fetch(ta, t);
+        for (;;) {
+            fetch(tb, min(t + 1, tf - 1));
+            consume(ta, t);
+            if (++t >= tf) break;
+            fetch(ta, min(t + 1, tf - 1));
+            consume(tb, t);
+            if (++t >= tf) break;
+        }
+    }
+    if (t < t_end) {                                                    // the ragged last tile: clamped loads, predicated stores
+        const uint32_t base = t * kTile + threadIdx.x;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint32_t vv = base + u * kEpStatBlock;
+            const uint32_t vc = min(vv, p.nvec - 1);
+            const float4 a = a4[vc], ba = bias4<PLANE>(p.bias_a, vc, p.epc, p.nc);
+            float4 b{}, bb{};
+            if (RESID) b = b4[vc];
+            if (BIAS_B) bb = bias4<PLANE>(p.bias_b, vc, p.epc, p.nc);
+            if (vv < p.nvec) feed4(epilogue_vec<RESID, BIAS_B, RELU>(a4, b4, o4, vv, a, ba, b, bb));
+        }
+    }
+    if (!PLANE && g == G - 1 && (int)threadIdx.x < p.ntail)             // n % 4 trailing elements: the owner of the last tile
+        feed1(epilogue_elem<RESID, BIAS_B, RELU>(p, p.tail + threadIdx.x, p.epc));
+#pragma unroll
+    for (int k = 0; k < NS; k++) {
+        if (!live[k]) continue;
+        minmax_block_fold(mn[k], mx[k], lds);
+        if (threadIdx.x == 0) minmax_slot_fold(sk.slots[k] + 2 * g, mn[k], mx[k]);
+        __syncthreads();                                                // lds is reused by the next sink
+    }
+}
+
 int validate(int64_t n, int64_t C, int64_t epc, const char* what) {
     if (n <= 0 || n > 0x7fffffffLL) {
         set_error("%s: n=%lld is empty or has more than 2^31 - 1 elements", what, (long long)n);
@@ -157,6 +287,38 @@ int validate(int64_t n, int64_t C, int64_t epc, const char* what) {
         return PPQHIP_ERR_INVALID_VALUE;
     }
     return PPQHIP_OK;
+}
+
+// The statistics launch, or the reason there is none: PPQHIP_NOT_FUSED (nothing was launched, nothing is wrong: the caller
+// runs the plain epilogue and leaves the statistic to the observers' own launch) for what the kernel has no path for.
+template <bool RESID, bool BIAS_B>
+int launch_epilogue_stats(EpArgs p, int64_t n, int64_t C, int64_t epc, int relu, bool aligned, EpSinks sk, const char* what,
+                          hipStream_t st) {
+    if ((!sk.slots[0] && !sk.slots[1] && !sk.slots[2]) || !aligned || n < 4) return PPQHIP_NOT_FUSED;
+    p.nc = make_fastdiv((uint32_t)C);
+    p.nvec = (uint32_t)(n >> 2);
+    p.tail = p.nvec * 4u;
+    p.ntail = (int)(n & 3);
+    const bool plane = (epc % 4 == 0);
+    p.epc = make_fastdiv((uint32_t)(plane ? epc / 4 : epc));
+    const bool small = n <= kEpSmallElems;                               // the plain launch's rule
+    const uint32_t tile = (uint32_t)kEpStatBlock * (small ? kEpSmallU : kEpTileU), tiles = (p.nvec + tile - 1) / tile;
+    const uint32_t cap = (uint32_t)(num_cu() * kEpStatWgPerCu);          // one slot per workgroup
+    const uint32_t grid = tiles < cap ? tiles : cap;
+#define PPQ_LAUNCH_EPS(U, RELU, PLANE)                                                                                    \
+    hipLaunchKernelGGL((epilogue_stats_kernel<U, RESID, BIAS_B, RELU, PLANE>), dim3(grid), dim3(kEpStatBlock), 0, st, p, sk)
+    switch ((small ? 0 : 4) | (relu ? 2 : 0) | (plane ? 1 : 0)) {
+        case 0: PPQ_LAUNCH_EPS(kEpSmallU, false, false); break;
+        case 1: PPQ_LAUNCH_EPS(kEpSmallU, false, true); break;
+        case 2: PPQ_LAUNCH_EPS(kEpSmallU, true, false); break;
+        case 3: PPQ_LAUNCH_EPS(kEpSmallU, true, true); break;
+        case 4: PPQ_LAUNCH_EPS(kEpTileU, false, false); break;
+        case 5: PPQ_LAUNCH_EPS(kEpTileU, false, true); break;
+        case 6: PPQ_LAUNCH_EPS(kEpTileU, true, false); break;
+        default: PPQ_LAUNCH_EPS(kEpTileU, true, true); break;
+    }
+#undef PPQ_LAUNCH_EPS
+    return finish_launch(what);
 }
 
 }  // namespace
@@ -195,6 +357,31 @@ int ppqhip_bias_add_act(float* a, const float* bias_a, float* b, const float* bi
         else launch_epilogue<true, false, false>(p, n, num_channel, elem_per_channel, aligned, s);
     }
     return finish_launch("bias_add_act");
+}
+
+int ppqhip_bias_act_stats(float* y, const float* bias, int64_t n, int64_t num_channel, int64_t elem_per_channel, int relu,
+                          float* slots_y, void* stream) {
+    if (int st = validate(n, num_channel, elem_per_channel, "bias_act_stats")) return st;
+    if (!y || !bias) { set_error("bias_act_stats: null pointer"); return PPQHIP_ERR_INVALID_VALUE; }
+    EpArgs p{};
+    p.a = y; p.bias_a = bias;
+    return launch_epilogue_stats<false, false>(p, n, num_channel, elem_per_channel, relu, aligned16(y), EpSinks{{slots_y, nullptr, nullptr}},
+                                               "bias_act_stats", (hipStream_t)stream);
+}
+
+int ppqhip_bias_add_act_stats(float* a, const float* bias_a, float* b, const float* bias_b, float* out, int64_t n,
+                              int64_t num_channel, int64_t elem_per_channel, int relu, float* slots_a, float* slots_b,
+                              float* slots_out, void* stream) {
+    if (int st = validate(n, num_channel, elem_per_channel, "bias_add_act_stats")) return st;
+    if (!a || !bias_a || !b || !out) { set_error("bias_add_act_stats: null pointer"); return PPQHIP_ERR_INVALID_VALUE; }
+    if (!bias_b && slots_b) { set_error("bias_add_act_stats: without bias_b, b is only read: it has no sink"); return PPQHIP_ERR_INVALID_VALUE; }
+    EpArgs p{};
+    p.a = a; p.bias_a = bias_a; p.b = b; p.bias_b = bias_b; p.out = out;
+    const bool aligned = aligned16(a) && aligned16(b) && aligned16(out);
+    const EpSinks sk{{slots_a, slots_b, slots_out}};
+    hipStream_t s = (hipStream_t)stream;
+    if (bias_b) return launch_epilogue_stats<true, true>(p, n, num_channel, elem_per_channel, relu, aligned, sk, "bias_add_act_stats", s);
+    return launch_epilogue_stats<true, false>(p, n, num_channel, elem_per_channel, relu, aligned, sk, "bias_add_act_stats", s);
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "minmax_fold.hpp"
 
 namespace ppqhip {
 
@@ -38,17 +39,12 @@ template <int U, bool NT>
 __global__ __launch_bounds__(kBlock) void minmax_t_kernel(const float* __restrict__ x, uint32_t n, int vec_ok,
                                                           float* __restrict__ minmax, float* __restrict__ partial,
                                                           int accumulate) {
-    __shared__ float lds[16];
+    __shared__ float lds[32];
     float mn = INFINITY, mx = -INFINITY;
-    stream_elems<U, NT>(x, n, vec_ok != 0, [&](float a) { mn = fminf(mn, a); mx = fmaxf(mx, a); });
+    stream_elems<U, NT>(x, n, vec_ok != 0, [&](float a) { minmax_fold1(mn, mx, a); });
     if (partial == nullptr) { block_minmax_commit(mn, mx, &minmax[0], &minmax[1], lds); return; }
-    mn = wave_min(mn);
-    mx = wave_max(mx);
-    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) { lds[wid] = mn; lds[8 + wid] = mx; }
-    __syncthreads();
+    minmax_block_fold(mn, mx, lds);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < kBlock / kWave; w++) { mn = fminf(mn, lds[w]); mx = fmaxf(mx, lds[8 + w]); }
         if (accumulate) {   // persistent per-workgroup slot: race-free, stream-ordered read-modify-write
             mn = fminf(mn, partial[2 * blockIdx.x]);
             mx = fmaxf(mx, partial[2 * blockIdx.x + 1]);
@@ -119,10 +115,7 @@ __global__ __launch_bounds__(kMMBlock) void minmax_persistent_kernel(const MinMa
             };
             auto consume = [&](const float4 (&buf)[kMMU]) {
 #pragma unroll
-                for (int u = 0; u < kMMU; u++) {
-                    mn = fminf(fminf(mn, buf[u].x), fminf(buf[u].y, fminf(buf[u].z, buf[u].w)));
-                    mx = fmaxf(fmaxf(mx, buf[u].x), fmaxf(buf[u].y, fmaxf(buf[u].z, buf[u].w)));
-                }
+                for (int u = 0; u < kMMU; u++) minmax_fold4(mn, mx, buf[u]);
             };
             fetch(bufa, k);
             for (;;) {
@@ -139,19 +132,11 @@ __global__ __launch_bounds__(kMMBlock) void minmax_persistent_kernel(const MinMa
 #pragma unroll 4
             for (int r = 0; r < 4 * kMMU; r++) {
                 const uint32_t i = e0 + r * kMMBlock;
-                if (i < n) { const float a = x[i]; mn = fminf(mn, a); mx = fmaxf(mx, a); }
+                if (i < n) minmax_fold1(mn, mx, x[i]);
             }
         }
-        mn = wave_min(mn);
-        mx = wave_max(mx);
-        const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-        if (lane == 0) { lds[wid] = mn; lds[16 + wid] = mx; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int w = 1; w < kMMBlock / kWave; w++) { mn = fminf(mn, lds[w]); mx = fmaxf(mx, lds[16 + w]); }
-            job.slots[2 * g] = fminf(mn, job.slots[2 * g]);
-            job.slots[2 * g + 1] = fmaxf(mx, job.slots[2 * g + 1]);
-        }
+        minmax_block_fold(mn, mx, lds);
+        if (threadIdx.x == 0) minmax_slot_fold(job.slots + 2 * g, mn, mx);
         __syncthreads();
     }
 }
@@ -180,10 +165,7 @@ __global__ __launch_bounds__(kMMBlock) void minmax_small_kernel(const float* __r
     };
     auto fold = [&](const float4 (&buf)[K]) {
 #pragma unroll
-        for (int k = 0; k < K; k++) {
-            mn = fminf(fminf(mn, buf[k].x), fminf(buf[k].y, fminf(buf[k].z, buf[k].w)));
-            mx = fmaxf(fmaxf(mx, buf[k].x), fmaxf(buf[k].y, fmaxf(buf[k].z, buf[k].w)));
-        }
+        for (int k = 0; k < K; k++) minmax_fold4(mn, mx, buf[k]);
     };
     if (PING) {
         if (r0 < r1) {
@@ -209,15 +191,10 @@ __global__ __launch_bounds__(kMMBlock) void minmax_small_kernel(const float* __r
         }
     }
     if (g == G - 1) {                                                  // the ragged rest: < kMMBlock float4 + n % 4 elements
-        for (uint32_t i = full_rows * kMMBlock * 4 + threadIdx.x; i < n; i += kMMBlock) { const float a = x[i]; mn = fminf(mn, a); mx = fmaxf(mx, a); }
+        for (uint32_t i = full_rows * kMMBlock * 4 + threadIdx.x; i < n; i += kMMBlock) minmax_fold1(mn, mx, x[i]);
     }
-    mn = wave_min(mn);
-    mx = wave_max(mx);
-    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) { lds[wid] = mn; lds[16 + wid] = mx; }
-    __syncthreads();
+    minmax_block_fold(mn, mx, lds);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < kMMBlock / kWave; w++) { mn = fminf(mn, lds[w]); mx = fmaxf(mx, lds[16 + w]); }
         slots[2 * g] = fminf(mn, s_mn);
         slots[2 * g + 1] = fmaxf(mx, s_mx);
     }
@@ -225,22 +202,14 @@ __global__ __launch_bounds__(kMMBlock) void minmax_small_kernel(const float* __r
 
 __global__ __launch_bounds__(kBlock) void minmax_finish_kernel(const float* __restrict__ partial, uint32_t count,
                                                                float* __restrict__ minmax) {
-    __shared__ float lds[16];
+    __shared__ float lds[32];
     float mn = INFINITY, mx = -INFINITY;
     for (uint32_t i = threadIdx.x; i < count; i += kBlock) {
         mn = fminf(mn, partial[2 * i]);
         mx = fmaxf(mx, partial[2 * i + 1]);
     }
-    mn = wave_min(mn);
-    mx = wave_max(mx);
-    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) { lds[wid] = mn; lds[8 + wid] = mx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kBlock / kWave; w++) { mn = fminf(mn, lds[w]); mx = fmaxf(mx, lds[8 + w]); }
-        minmax[0] = fminf(minmax[0], mn);   // stream-ordered read-modify-write (accumulate semantics)
-        minmax[1] = fmaxf(minmax[1], mx);
-    }
+    minmax_block_fold(mn, mx, lds);
+    if (threadIdx.x == 0) minmax_slot_fold(minmax, mn, mx);   // stream-ordered read-modify-write (accumulate semantics)
 }
 
 // rows of `epc` contiguous elements, ONE WAVE per work item, no workgroup barrier anywhere: item i = (channel c = i % C,

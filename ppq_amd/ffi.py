@@ -241,6 +241,53 @@ def bias_add_act(a: torch.Tensor, bias_a: torch.Tensor, b: torch.Tensor, bias_b,
     return out
 
 
+def _sink_slots(job, dev) -> int:
+    """Device address of the slots of an observer's ``('minmax', slots)`` job (``BaseTensorObserver.stat_job``), 0 for no job.
+    Raises ValueError for a job the epilogue kernels have no sink for (the caller then does not fuse)."""
+    if job is None: return 0
+    slots = job[1]
+    if (job[0] != 'minmax' or slots.dtype is not _F32 or slots.device != dev or not slots.is_contiguous()
+            or slots.numel() != 2 * lib.ppqhip_minmax_slots()): raise ValueError('no sink for this job')
+    return slots.data_ptr()
+
+
+def _fused_or_raise(status: int) -> bool:
+    if status == _lib.NOT_FUSED: return False
+    _raise(status)
+    return True
+
+
+def bias_act_stats_(y: torch.Tensor, bias: torch.Tensor, relu: bool, job) -> bool:
+    """``bias_act_`` that also folds the stored ``y`` into the slots of ``job`` (an observer's ``('minmax', slots)``) from the
+    registers it is stored from (``ppqhip_bias_act_stats``).  False: NOTHING was launched (operands or job not fusable) --
+    the caller runs ``bias_act_`` and observes ``y`` as usual."""
+    geo = _epilogue_geometry([y], [bias])
+    if geo is None or job is None: return False
+    try: slots = _sink_slots(job, y.device)
+    except ValueError: return False
+    with _DeviceOf(y):
+        return _fused_or_raise(lib.ppqhip_bias_act_stats(y.data_ptr(), bias.data_ptr(), y.numel(), geo[0], geo[1],
+                                                         1 if relu else 0, slots, _stream()))
+
+
+def bias_add_act_stats(a: torch.Tensor, bias_a: torch.Tensor, b: torch.Tensor, bias_b, relu: bool, job_a, job_b, job_out):
+    """``bias_add_act`` that also folds the stored ``a``, ``b`` (only with ``bias_b``) and the returned ``out`` into the slots
+    of their ``('minmax', slots)`` jobs (None: that tensor is not folded) (``ppqhip_bias_add_act_stats``).
+    None: NOTHING was launched -- the caller runs ``bias_add_act`` and observes as usual."""
+    geo = _epilogue_geometry([a, b], [bias_a] if bias_b is None else [bias_a, bias_b])
+    if geo is None or a.data_ptr() == b.data_ptr(): return None
+    if bias_b is None and job_b is not None: return None
+    try: slots = [_sink_slots(j, a.device) for j in (job_a, job_b, job_out)]
+    except ValueError: return None
+    if not any(slots): return None
+    out = torch.empty_like(a)
+    with _DeviceOf(a):
+        ok = _fused_or_raise(lib.ppqhip_bias_add_act_stats(
+            a.data_ptr(), bias_a.data_ptr(), b.data_ptr(), 0 if bias_b is None else bias_b.data_ptr(), out.data_ptr(),
+            a.numel(), geo[0], geo[1], 1 if relu else 0, slots[0], slots[1], slots[2], _stream()))
+    return out if ok else None
+
+
 # ---- AdaRound (include/ppq_hip.h ppqhip_adaround_fwd_multi / ppqhip_adaround_bwd_multi) ------------------------------------
 _ADAROUND_JOB = np.dtype([('w', '<u8'), ('v', '<u8'), ('scale', '<u8'), ('offset', '<u8'), ('out', '<u8'), ('dy', '<u8'),
                           ('n', '<i8'), ('num_channel', '<i8'), ('elem_per_channel', '<i8'), ('qmin', '<i4'), ('qmax', '<i4')])

@@ -469,7 +469,7 @@ class TorchExecutor:
         the quantize_function calls and hooks of the unfused loop on the tensors the kernel wrote (the planner guarantees
         that the configs of the tensors it did not write pass through and are not observed).  Returns variable name ->
         value for the outputs of every member, or None before anything ran when the operands' layout does not qualify."""
-        from .ffi import bias_act_, bias_add_act
+        from .ffi import bias_act_, bias_act_stats_, bias_add_act, bias_add_act_stats
         for conv in grp.convs:                       # conv output layout follows x / w: both dense, both in one format
             x, w = raw_of(conv.inputs[0]), conv.inputs[1].value
             if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
@@ -500,7 +500,10 @@ class TorchExecutor:
         if grp.kind == 'P1':
             conv = grp.convs[0]
             y = ys[conv.name]
-            if not bias_act_(y, biases[conv.name], relu=True):
+            stored = {grp.relu.name: y}                  # member -> the tensor the launch stores as that member's output
+            fed = self._epilogue_sinks(grp, hooks, stored, y)
+            if fed is not None and not bias_act_stats_(y, biases[conv.name], True, fed[0].get(grp.relu.name)): fed = None
+            if fed is None and not bias_act_(y, biases[conv.name], relu=True):
                 y.add_(biases[conv.name].view(1, -1, 1, 1)).relu_()      # PyTorch's own conv-bias step, then F.relu
             tail = {conv.name: y, grp.relu.name: y}
         else:
@@ -508,13 +511,25 @@ class TorchExecutor:
             a = ys[conv_a.name]
             conv_b = grp.convs[1] if len(grp.convs) > 1 else None
             b = ys[conv_b.name] if conv_b is not None else raw_of(grp.add.inputs[1])
-            out = bias_add_act(a, biases[conv_a.name], b, biases[conv_b.name] if conv_b is not None else None, relu=True)
+            bias_b = biases[conv_b.name] if conv_b is not None else None
+            stored = {conv_a.name: a, grp.relu.name: None}                    # (out does not exist yet)
+            if conv_b is not None: stored[conv_b.name] = b
+            fed, out = self._epilogue_sinks(grp, hooks, stored, a), None
+            if fed is not None:
+                jobs = fed[0]
+                out = bias_add_act_stats(a, biases[conv_a.name], b, bias_b, True, jobs.get(conv_a.name),
+                                         jobs.get(conv_b.name) if conv_b is not None else None, jobs.get(grp.relu.name))
+                if out is None: fed = None
+                else: stored[grp.relu.name] = out
+            if out is None: out = bias_add_act(a, biases[conv_a.name], b, bias_b, relu=True)
             if out is None:
                 a.add_(biases[conv_a.name].view(1, -1, 1, 1))
                 if conv_b is not None: b.add_(biases[conv_b.name].view(1, -1, 1, 1))
                 out = F.relu(a + b)
             tail = {conv_a.name: a, grp.add.name: out, grp.relu.name: out}
             if conv_b is not None: tail[conv_b.name] = b
+        if fed is not None:                              # only after a launch that took place
+            for name, job in fed[0].items(): fed[1].prepay(stored[name], job[1])
         values: Dict[str, torch.Tensor] = {}
         for op in grp.ops:
             hook = hooks.get(op.name)
@@ -535,6 +550,27 @@ class TorchExecutor:
                 outs = hook.post_forward_hook(outputs=fp_outs, quant_outputs=outs, quant_configs=out_cfgs)
             for v, y in zip(op.outputs, outs): values[v.name] = y
         return values
+
+    @ staticmethod
+    def _epilogue_sinks(grp: EpilogueGroup, hooks, stored: Dict[str, torch.Tensor], like: torch.Tensor):
+        """Calibration forwards: ``({member name: ('minmax', slots)}, queue)`` when the running range every observer of the
+        group's stored outputs is about to queue can ride the epilogue launch instead (ffi.bias_act_stats_ /
+        bias_add_act_stats) -- each such observer has a job (``stat_job``), one queue, no side stream; None otherwise (no
+        hooks, nothing observed, or any observer without a job: today's path).  ``stored``: the members whose output the
+        launch stores; ``like``: a tensor on the launch's device."""
+        jobs, queue = {}, None
+        for op in grp.ops:
+            hook = hooks.get(op.name)
+            if hook is None or not isinstance(op, QuantableOperation): continue
+            for cfg in op.config.output_quantization_config:
+                ob = hook._observer_table.get(cfg)
+                if ob is None: continue
+                if op.name not in stored or op.name in jobs or hook.stream is not None or ob.queue is None: return None
+                if queue is not None and ob.queue is not queue: return None
+                job = ob.stat_job(like)
+                if job is None: return None
+                jobs[op.name], queue = job, ob.queue
+        return (jobs, queue) if jobs else None
 
     def _quantize_parameter(self, var: Variable, config) -> torch.Tensor:
         hit = self._fused.get((var.name, id(config)))

@@ -154,6 +154,7 @@ class ObservationQueue:
         self._max = max_pending_bytes
         self.launches = 0
         self.recorder: Optional[list] = None   # RuntimeCalibrationPass(reuse_activations=True): (observer, tensor) of phase 1
+        self._prepaid = set()              # (tensor data_ptr, slots data_ptr): ranges a producer launch already folded
 
     def __len__(self):
         return (len(self._minmax) + len(self._minmax_c) + sum(len(v) for v in self._hist.values())
@@ -161,9 +162,23 @@ class ObservationQueue:
 
     def _grow(self, value) -> None:
         self._bytes += value.numel() * 4
-        if self._bytes > self._max: self.flush()
+        if self._bytes > self._max: self._launch()           # (not flush(): pairs prepaid for this forward are still to be claimed)
+
+    def prepay(self, value: torch.Tensor, buffer: torch.Tensor) -> None:
+        """The launch that produced ``value`` has already folded it into ``buffer`` (an observer's slots: the statistics
+        variant of a convolution epilogue, ``TorchExecutor._run_epilogue``).  The ``add_minmax`` of exactly this pair that the
+        observer's ``observe`` is about to make is dropped, once; every other bookkeeping step of ``observe`` still runs.
+        ``flush`` forgets what was never claimed."""
+        self._prepaid.add((value.data_ptr(), buffer.data_ptr()))
+
+    def _claim(self, value: torch.Tensor, buffer: torch.Tensor) -> bool:
+        key = (value.data_ptr(), buffer.data_ptr())
+        if key not in self._prepaid: return False
+        self._prepaid.discard(key)
+        return True
 
     def add_minmax(self, value: torch.Tensor, slots: torch.Tensor) -> None:
+        if self._prepaid and self._claim(value, slots): return
         self._minmax.append((value, slots))
         self._grow(value)
 
@@ -172,7 +187,7 @@ class ObservationQueue:
         qualifies for being overwritten (``CUDA.minmax_c_fresh_ok``)."""
         # one buffer, one job per launch: a second observation of the same observer must not share a launch with a pending
         # `fresh` (overwriting) job of it -- the two would race on the buffer
-        if any(m.data_ptr() == mins.data_ptr() for _, _, m, _, _ in self._minmax_c): self.flush()
+        if any(m.data_ptr() == mins.data_ptr() for _, _, m, _, _ in self._minmax_c): self._launch()
         self._minmax_c.append((value, channel_axis, mins, maxs, bool(fresh)))
         self._grow(value)
 
@@ -189,6 +204,10 @@ class ObservationQueue:
         return dest
 
     def flush(self) -> None:
+        self._prepaid.clear()
+        self._launch()
+
+    def _launch(self) -> None:
         if self._quantile:
             pending, self._quantile = self._quantile, {}
             for (q, _), items in pending.items():
@@ -275,6 +294,12 @@ class BaseTensorObserver:
     def observe(self, value):
         raise NotImplementedError('Implement this function first.')
 
+    def stat_job(self, value) -> Optional[tuple]:
+        """What ``observe(value)`` would hand to ``ObservationQueue.add_minmax``: ``('minmax', slots)``, the buffers allocated
+        as ``observe`` allocates them -- or None when this observer would not queue a per-tensor running range for ``value``
+        (per channel, histogram phase, percentile, isotone, constant, a config that is no longer INITIAL)."""
+        return None
+
     def render_quantization_config(self):
         raise NotImplementedError('Implement this function first.')
 
@@ -340,12 +365,9 @@ class TorchMinMaxObserver(BaseTensorObserver):
         if not is_initial(self._quant_cfg): return
         cfg = self._quant_cfg
         if cfg.policy.has_property(P.PER_TENSOR):
-            if self._range is None:
-                seed = _range_seed(value.device)                 # device-side clones: no host-to-device copy per observer
-                self._range = seed[0].clone()
-                self._slots = seed[1].clone()
-            if self.queue is not None and value.is_cuda: self.queue.add_minmax(value, self._slots)
-            else: CUDA.MinMax_T_Slots(value, self._slots)    # no per-batch reduction kernel
+            _, slots = TorchMinMaxObserver.stat_job(self, value)
+            if self.queue is not None and value.is_cuda: self.queue.add_minmax(value, slots)
+            else: CUDA.MinMax_T_Slots(value, slots)          # no per-batch reduction kernel
             self._slots_dirty = True
         elif cfg.policy.has_property(P.PER_CHANNEL):
             # parameter-shaped tensors (channel axis outermost: one row per channel) join the forward's ONE multi-tensor
@@ -367,6 +389,15 @@ class TorchMinMaxObserver(BaseTensorObserver):
             raise TypeError('Min-max Observer only work with per-tensor or per-channel quantize policy.')
         self._observed = True
         self._host_range = None
+
+    def stat_job(self, value: torch.Tensor) -> Optional[tuple]:
+        cfg = self._quant_cfg
+        if not is_initial(cfg) or not cfg.policy.has_property(P.PER_TENSOR): return None
+        if self._range is None:
+            seed = _range_seed(value.device)                 # device-side clones: no host-to-device copy per observer
+            self._range = seed[0].clone()
+            self._slots = seed[1].clone()
+        return ('minmax', self._slots)
 
     def _fold(self) -> None:
         """Fold the per-workgroup slots into the running [min, max] (one tiny launch, at render)."""
@@ -470,6 +501,10 @@ class TorchHistObserver(TorchMinMaxObserver):
                     CUDA.Histogram_T(tensor=value, histogram=self._hist, scale=self._hist_scale)
             else:
                 raise TypeError('Quantization Property is invalid, expect either ASYMMETRICAL or SYMMETRICAL config here.')
+
+    def stat_job(self, value: torch.Tensor) -> Optional[tuple]:
+        # phase 1 only: the histogram rows of phase 2 have no sink in the epilogue launches
+        return super().stat_job(value) if self._phase == 'Detecting Minmax' else None
 
     def pending_range(self):
         return super().pending_range() if self._phase == 'Detecting Minmax' else None
