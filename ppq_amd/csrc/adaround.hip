@@ -14,9 +14,9 @@
 //   r = -k;  x = |h - 0.5| * 2;  r = r * (beta * pow(x, beta - 1));  r = r * 2;  r = r * sgn(h - 0.5);  mask on a;  r = r * 1.2f;
 //   r = (r * (1 - sg)) * sg;  dv = dv + r
 //
-// Job table: DESIGN.md, "Job tables" (capturable into a HIP graph).  channel(i) = (i / elem_per_channel) % num_channel with FastDiv (a per-tensor job has num_channel = 1).  16-B loads and
-// stores where every pointer of the job is aligned, the n % 4 tail by the job's first workgroup; element-wise otherwise.  No
-// atomics, no reductions.
+// Job table: DESIGN.md, "Job tables" (capturable into a HIP graph).  Geometry and walk: channel_axis.hpp (a per-tensor job has
+// num_channel = 1); 16-B loads and stores where every pointer of the job is aligned.  No atomics, no reductions.
+#include "channel_axis.hpp"
 #include "common.hpp"
 #include "job_table.hpp"
 
@@ -24,7 +24,6 @@ namespace ppqhip {
 namespace {
 
 constexpr int kArMaxJobs = 16;                     // 16 x 96 B of job table: well inside the 4 KB of kernel arguments
-constexpr uint32_t kArMaxBlocksPerJob = 1024;      // grid-strided beyond: 256 K lanes per job cover the largest weights in ~3 trips
 
 struct ArJob {                                     // 96 B
     const float* w;
@@ -33,11 +32,8 @@ struct ArJob {                                     // 96 B
     const float* offset;
     float* out;                                    // forward: fake-quantised weight; backward: dV
     const float* dy;                               // backward only
-    uint32_t n, nvec;                              // nvec: float4 count of the vector part (0: element-wise job)
-    FastDiv epc, nc;
+    ChannelAxisMap map;
     float qmin, qmax;
-    uint32_t plane;                                // epc % 4 == 0: one channel per float4
-    uint32_t blocks;                               // workgroups of this job
 };
 struct ArArgs {
     ArJob jobs[kArMaxJobs];
@@ -46,11 +42,6 @@ struct ArArgs {
     const float* reg;                              // backward: {k, beta, beta - 1}
 };
 static_assert(sizeof(ArArgs) <= 4096, "kernel arguments are limited to 4 KB");
-
-__device__ __forceinline__ uint32_t ar_channel(uint32_t i, const FastDiv& epc, const FastDiv& nc) {
-    const uint32_t row = fdiv(i, epc);
-    return row - fdiv(row, nc) * nc.d;
-}
 
 struct ArElem {
     float sg, a, t;
@@ -98,57 +89,27 @@ __device__ __forceinline__ float ar_backward(float w, float v, float s, float o,
 }
 
 template <bool BWD, bool REG>
-__device__ __forceinline__ void ar_elem(const ArJob& j, uint32_t i, uint32_t c, float k, float beta, float bm1) {
-    const float s = j.scale[c], o = j.offset[c];
-    if (BWD) j.out[i] = ar_backward<REG>(j.w[i], j.v[i], s, o, j.qmin, j.qmax, j.dy[i], k, beta, bm1);
-    else {
-        ArElem e;
-        j.out[i] = ar_forward(j.w[i], j.v[i], s, o, j.qmin, j.qmax, e);
-    }
-}
-
-template <bool BWD, bool REG>
 __device__ __forceinline__ void ar_job(const ArJob& j, uint32_t local, float k, float beta, float bm1) {
-    const uint32_t stride = j.blocks * kBlock;
-    const uint32_t first = local * kBlock + threadIdx.x;
-    if (j.nvec == 0) {                                               // unaligned pointers or n < 4: element-wise
-        for (uint32_t i = first; i < j.n; i += stride) ar_elem<BWD, REG>(j, i, ar_channel(i, j.epc, j.nc), k, beta, bm1);
-        return;
-    }
     const float4* w4 = reinterpret_cast<const float4*>(j.w);
     const float4* v4 = reinterpret_cast<const float4*>(j.v);
     const float4* d4 = reinterpret_cast<const float4*>(j.dy);
     float4* o4 = reinterpret_cast<float4*>(j.out);
-    for (uint32_t q = first; q < j.nvec; q += stride) {
-        const float4 w = w4[q], v = v4[q];
-        float4 dy = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (BWD) dy = d4[q];
-        const uint32_t i = q * 4u;
-        uint32_t c0, c1, c2, c3;
-        if (j.plane) { c0 = c1 = c2 = c3 = ar_channel(q, j.epc, j.nc); }            // j.epc holds epc / 4
-        else {
-            c0 = ar_channel(i, j.epc, j.nc); c1 = ar_channel(i + 1, j.epc, j.nc);
-            c2 = ar_channel(i + 2, j.epc, j.nc); c3 = ar_channel(i + 3, j.epc, j.nc);
-        }
-        float4 r;
-        if (BWD) {
-            r.x = ar_backward<REG>(w.x, v.x, j.scale[c0], j.offset[c0], j.qmin, j.qmax, dy.x, k, beta, bm1);
-            r.y = ar_backward<REG>(w.y, v.y, j.scale[c1], j.offset[c1], j.qmin, j.qmax, dy.y, k, beta, bm1);
-            r.z = ar_backward<REG>(w.z, v.z, j.scale[c2], j.offset[c2], j.qmin, j.qmax, dy.z, k, beta, bm1);
-            r.w = ar_backward<REG>(w.w, v.w, j.scale[c3], j.offset[c3], j.qmin, j.qmax, dy.w, k, beta, bm1);
-        } else {
-            ArElem e;
-            r.x = ar_forward(w.x, v.x, j.scale[c0], j.offset[c0], j.qmin, j.qmax, e);
-            r.y = ar_forward(w.y, v.y, j.scale[c1], j.offset[c1], j.qmin, j.qmax, e);
-            r.z = ar_forward(w.z, v.z, j.scale[c2], j.offset[c2], j.qmin, j.qmax, e);
-            r.w = ar_forward(w.w, v.w, j.scale[c3], j.offset[c3], j.qmin, j.qmax, e);
-        }
-        o4[q] = r;
-    }
-    if (local == 0 && threadIdx.x < j.n - j.nvec * 4u) {              // the n % 4 tail (never in the plane form: 4 | epc | n)
-        const uint32_t i = j.nvec * 4u + threadIdx.x;
-        ar_elem<BWD, REG>(j, i, ar_channel(i, j.epc, j.nc), k, beta, bm1);
-    }
+    auto one = [&](float w, float v, float dy, uint32_t c) {
+        const float s = j.scale[c], o = j.offset[c];
+        if (BWD) return ar_backward<REG>(w, v, s, o, j.qmin, j.qmax, dy, k, beta, bm1);
+        ArElem e;
+        return ar_forward(w, v, s, o, j.qmin, j.qmax, e);
+    };
+    walk_channel_axis(j.map, local,
+                      [&](uint32_t i, uint32_t c) { j.out[i] = one(j.w[i], j.v[i], BWD ? j.dy[i] : 0.f, c); },
+                      [&](uint32_t q) {
+                          const float4 w = w4[q], v = v4[q];
+                          float4 dy = make_float4(0.f, 0.f, 0.f, 0.f);
+                          if (BWD) dy = d4[q];
+                          const Channels4 c = channels_of_float4(j.map, q);             // behind the loads: channel_axis.hpp
+                          o4[q] = make_float4(one(w.x, v.x, dy.x, c.c0), one(w.y, v.y, dy.y, c.c1), one(w.z, v.z, dy.z, c.c2),
+                                              one(w.w, v.w, dy.w, c.c3));
+                      });
 }
 
 __global__ __launch_bounds__(kBlock) void adaround_fwd_kernel(const ArArgs args) {
@@ -170,16 +131,7 @@ int validate_jobs(const ppqhip_adaround_job* jobs, int num_jobs, bool bwd, const
     if (int st = check_job_table(what, jobs, num_jobs)) return st;
     for (int k = 0; k < num_jobs; k++) {
         const ppqhip_adaround_job& j = jobs[k];
-        if (j.n <= 0 || j.n > 0x7fffffffLL) {
-            set_error("%s: job %d: n=%lld is empty or has more than 2^31 - 1 elements", what, k, (long long)j.n);
-            return PPQHIP_ERR_INVALID_VALUE;
-        }
-        if (j.num_channel <= 0 || j.elem_per_channel <= 0 || j.num_channel > 0x7fffffffLL || j.elem_per_channel > 0x7fffffffLL ||
-            j.n % (j.num_channel * j.elem_per_channel) != 0) {
-            set_error("%s: job %d: n=%lld is not [outer, %lld channels, %lld elem/channel]", what, k, (long long)j.n,
-                      (long long)j.num_channel, (long long)j.elem_per_channel);
-            return PPQHIP_ERR_INVALID_VALUE;
-        }
+        if (int st = validate_channel_axis(what, j.n, j.num_channel, j.elem_per_channel, k)) return st;
         if (!j.w || !j.v || !j.scale || !j.offset || !j.out || (bwd && !j.dy)) {
             set_error("%s: job %d has a null pointer", what, k);
             return PPQHIP_ERR_INVALID_VALUE;
@@ -198,17 +150,11 @@ int launch_adaround(const ppqhip_adaround_job* jobs, int num_jobs, bool bwd, con
             const ppqhip_adaround_job& src = jobs[base + k];
             ArJob& d = args.jobs[k];
             d.w = src.w; d.v = src.v; d.scale = src.scale; d.offset = src.offset; d.out = src.out; d.dy = src.dy;
-            d.n = (uint32_t)src.n;
             const bool aligned = aligned16(src.w) && aligned16(src.v) && aligned16(src.out) && (!bwd || aligned16(src.dy));
-            d.nvec = (aligned && src.n >= 4) ? (uint32_t)(src.n >> 2) : 0u;
-            d.plane = (d.nvec > 0 && src.elem_per_channel % 4 == 0) ? 1u : 0u;
-            d.epc = make_fastdiv((uint32_t)(d.plane ? src.elem_per_channel / 4 : src.elem_per_channel));
-            d.nc = make_fastdiv((uint32_t)src.num_channel);
+            d.map = pack_channel_axis(aligned, src.n, src.num_channel, src.elem_per_channel);
             d.qmin = (float)src.qmin; d.qmax = (float)src.qmax;
-            const uint64_t work = d.nvec > 0 ? d.nvec : (uint64_t)src.n;
-            d.blocks = (uint32_t)std::min<uint64_t>((work + kBlock - 1) / kBlock, kArMaxBlocksPerJob);
             args.first_block[k] = blocks;
-            blocks += d.blocks;
+            blocks += d.map.blocks;
         }
         pad_job_table(args, (uint32_t)count, blocks);
         args.reg = reg;

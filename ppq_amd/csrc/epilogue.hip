@@ -28,6 +28,7 @@
 // ping-pong register tiles and folding ONCE, at its end, into slot blockIdx.x -- a plain read-modify-write with one owner
 // per launch, stream ordered across launches.  No atomics on global memory, nothing synchronises: capturable into a HIP
 // graph like the plain launches.  (Histogram sinks for phase 2 of KL / MSE were measured and left out: DESIGN.md section 6.)
+#include "channel_axis.hpp"
 #include "common.hpp"
 #include "minmax_fold.hpp"
 
@@ -50,11 +51,6 @@ struct EpArgs {
     FastDiv epc;           // elem_per_channel (per-element channel) or elem_per_channel / 4 (per-float4 channel)
     FastDiv nc;            // num_channel
 };
-
-__device__ __forceinline__ uint32_t channel_of(uint32_t i, const FastDiv& epc, const FastDiv& nc) {
-    const uint32_t row = fdiv(i, epc);
-    return row - fdiv(row, nc) * nc.d;
-}
 
 __device__ __forceinline__ float act(float v, bool relu) {
     return (relu && !__builtin_isnan(v)) ? __builtin_fmaxf(v, 0.f) : v;
@@ -148,20 +144,25 @@ __global__ __launch_bounds__(kBlock) void epilogue_scalar_kernel(EpArgs p) {
         epilogue_elem<RESID, BIAS_B, RELU>(p, i, p.epc);
 }
 
+// the geometry of the vector kernels (16-B aligned pointers, n >= 4); returns PLANE
+bool fill_vector_geometry(EpArgs& p, int64_t n, int64_t C, int64_t epc) {
+    const ChannelAxisMap g = pack_channel_axis(true, n, C, epc);
+    p.nc = g.nc; p.epc = g.epc;
+    p.nvec = g.nvec;
+    p.tail = g.nvec * 4u;
+    p.ntail = (int)(n & 3);
+    return g.plane != 0;
+}
+
 template <bool RESID, bool BIAS_B, bool RELU>
 void launch_epilogue(EpArgs p, int64_t n, int64_t C, int64_t epc, bool aligned, hipStream_t st) {
-    p.nc = make_fastdiv((uint32_t)C);
     if (!aligned || n < 4) {
         p.nvec = 0; p.tail = 0; p.ntail = (int)n;
-        p.epc = make_fastdiv((uint32_t)epc);
+        p.epc = make_fastdiv((uint32_t)epc); p.nc = make_fastdiv((uint32_t)C);
         hipLaunchKernelGGL((epilogue_scalar_kernel<RESID, BIAS_B, RELU>), dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, st, p);
         return;
     }
-    p.nvec = (uint32_t)(n >> 2);
-    p.tail = p.nvec * 4u;
-    p.ntail = (int)(n & 3);
-    const bool plane = (epc % 4 == 0);
-    p.epc = make_fastdiv((uint32_t)(plane ? epc / 4 : epc));
+    const bool plane = fill_vector_geometry(p, n, C, epc);
 #define PPQ_LAUNCH_EP(U, PLANE)                                                                                          \
     hipLaunchKernelGGL((epilogue_kernel<U, RESID, BIAS_B, RELU, PLANE>), dim3((p.nvec + kBlock * U - 1) / (kBlock * U)),   \
                        dim3(kBlock), 0, st, p)
@@ -276,31 +277,13 @@ void epilogue_stats_kernel(EpArgs p, EpSinks sk) {
     }
 }
 
-int validate(int64_t n, int64_t C, int64_t epc, const char* what) {
-    if (n <= 0 || n > 0x7fffffffLL) {
-        set_error("%s: n=%lld is empty or has more than 2^31 - 1 elements", what, (long long)n);
-        return PPQHIP_ERR_INVALID_VALUE;
-    }
-    if (C <= 0 || epc <= 0 || C > 0x7fffffffLL || epc > 0x7fffffffLL || n % (C * epc) != 0) {
-        set_error("%s: n=%lld is not [outer, %lld channels, %lld elem/channel]", what, (long long)n, (long long)C,
-                  (long long)epc);
-        return PPQHIP_ERR_INVALID_VALUE;
-    }
-    return PPQHIP_OK;
-}
-
 // The statistics launch, or the reason there is none: PPQHIP_NOT_FUSED (nothing was launched, nothing is wrong: the caller
 // runs the plain epilogue and leaves the statistic to the observers' own launch) for what the kernel has no path for.
 template <bool RESID, bool BIAS_B>
 int launch_epilogue_stats(EpArgs p, int64_t n, int64_t C, int64_t epc, int relu, bool aligned, EpSinks sk, const char* what,
                           hipStream_t st) {
     if ((!sk.slots[0] && !sk.slots[1] && !sk.slots[2]) || !aligned || n < 4) return PPQHIP_NOT_FUSED;
-    p.nc = make_fastdiv((uint32_t)C);
-    p.nvec = (uint32_t)(n >> 2);
-    p.tail = p.nvec * 4u;
-    p.ntail = (int)(n & 3);
-    const bool plane = (epc % 4 == 0);
-    p.epc = make_fastdiv((uint32_t)(plane ? epc / 4 : epc));
+    const bool plane = fill_vector_geometry(p, n, C, epc);
     const bool small = n <= kEpSmallElems;                               // the plain launch's rule
     const uint32_t tile = (uint32_t)kEpStatBlock * (small ? kEpSmallU : kEpTileU), tiles = (p.nvec + tile - 1) / tile;
     const uint32_t cap = (uint32_t)(num_cu() * kEpStatWgPerCu);          // one slot per workgroup
@@ -330,7 +313,7 @@ extern "C" {
 
 int ppqhip_bias_act(float* y, const float* bias, int64_t n, int64_t num_channel, int64_t elem_per_channel, int relu,
                     void* stream) {
-    if (int st = validate(n, num_channel, elem_per_channel, "bias_act")) return st;
+    if (int st = validate_channel_axis("bias_act", n, num_channel, elem_per_channel)) return st;
     if (!y || !bias) { set_error("bias_act: null pointer"); return PPQHIP_ERR_INVALID_VALUE; }
     hipStream_t s = (hipStream_t)stream;
     EpArgs p{};
@@ -343,7 +326,7 @@ int ppqhip_bias_act(float* y, const float* bias, int64_t n, int64_t num_channel,
 
 int ppqhip_bias_add_act(float* a, const float* bias_a, float* b, const float* bias_b, float* out, int64_t n,
                         int64_t num_channel, int64_t elem_per_channel, int relu, void* stream) {
-    if (int st = validate(n, num_channel, elem_per_channel, "bias_add_act")) return st;
+    if (int st = validate_channel_axis("bias_add_act", n, num_channel, elem_per_channel)) return st;
     if (!a || !bias_a || !b || !out) { set_error("bias_add_act: null pointer"); return PPQHIP_ERR_INVALID_VALUE; }
     hipStream_t s = (hipStream_t)stream;
     EpArgs p{};
@@ -361,7 +344,7 @@ int ppqhip_bias_add_act(float* a, const float* bias_a, float* b, const float* bi
 
 int ppqhip_bias_act_stats(float* y, const float* bias, int64_t n, int64_t num_channel, int64_t elem_per_channel, int relu,
                           float* slots_y, void* stream) {
-    if (int st = validate(n, num_channel, elem_per_channel, "bias_act_stats")) return st;
+    if (int st = validate_channel_axis("bias_act_stats", n, num_channel, elem_per_channel)) return st;
     if (!y || !bias) { set_error("bias_act_stats: null pointer"); return PPQHIP_ERR_INVALID_VALUE; }
     EpArgs p{};
     p.a = y; p.bias_a = bias;
@@ -372,7 +355,7 @@ int ppqhip_bias_act_stats(float* y, const float* bias, int64_t n, int64_t num_ch
 int ppqhip_bias_add_act_stats(float* a, const float* bias_a, float* b, const float* bias_b, float* out, int64_t n,
                               int64_t num_channel, int64_t elem_per_channel, int relu, float* slots_a, float* slots_b,
                               float* slots_out, void* stream) {
-    if (int st = validate(n, num_channel, elem_per_channel, "bias_add_act_stats")) return st;
+    if (int st = validate_channel_axis("bias_add_act_stats", n, num_channel, elem_per_channel)) return st;
     if (!a || !bias_a || !b || !out) { set_error("bias_add_act_stats: null pointer"); return PPQHIP_ERR_INVALID_VALUE; }
     if (!bias_b && slots_b) { set_error("bias_add_act_stats: without bias_b, b is only read: it has no sink"); return PPQHIP_ERR_INVALID_VALUE; }
     EpArgs p{};

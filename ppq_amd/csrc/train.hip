@@ -3,6 +3,7 @@
 // ABI completeness, plain grid-stride kernels, no tuning.
 #include <cmath>
 
+#include "channel_axis.hpp"
 #include "common.hpp"
 
 namespace ppqhip {
@@ -13,11 +14,7 @@ __global__ __launch_bounds__(kBlock) void tensor_clip_kernel(const float* __rest
                                                              int per_channel) {
     const uint32_t stride = gridDim.x * kBlock;
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-        uint32_t c = 0;
-        if (per_channel) {
-            const uint32_t row = fdiv(i, elem_per_channel);
-            c = row - fdiv(row, num_channel) * num_channel.d;
-        }
+        const uint32_t c = per_channel ? channel_of(i, elem_per_channel, num_channel) : 0u;
         const float l = limit[c], lo = ref[i] - l, hi = ref[i] + l, x = v[i];
         out[i] = x > hi ? hi : (x < lo ? lo : x);   // CLIP<float>, common.cuh:70-76
     }
@@ -47,11 +44,7 @@ __global__ __launch_bounds__(kBlock) void rounding_loss_kernel(const float* __re
     float acc = 0.f;
     const uint32_t stride = gridDim.x * kBlock;
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-        uint32_t c = 0;
-        if (per_channel) {
-            const uint32_t row = fdiv(i, elem_per_channel);
-            c = row - fdiv(row, num_channel) * num_channel.d;
-        }
+        const uint32_t c = per_channel ? channel_of(i, elem_per_channel, num_channel) : 0u;
         float dq;
         const float d = rl_elem(x[i], scale[c], offset[c], per_channel, qmin, qmax, rounding, &dq);
         acc += d < 0.f ? 0.f : d;
@@ -75,11 +68,7 @@ __global__ __launch_bounds__(kBlock) void rounding_loss_bwd_kernel(const float* 
     const float g = dy[0];
     const uint32_t stride = gridDim.x * kBlock;
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-        uint32_t c = 0;
-        if (per_channel) {
-            const uint32_t row = fdiv(i, elem_per_channel);
-            c = row - fdiv(row, num_channel) * num_channel.d;
-        }
+        const uint32_t c = per_channel ? channel_of(i, elem_per_channel, num_channel) : 0u;
         float dq;
         const float v = x[i];
         const float d = rl_elem(v, scale[c], offset[c], per_channel, qmin, qmax, rounding, &dq);

@@ -288,32 +288,37 @@ def bias_add_act_stats(a: torch.Tensor, bias_a: torch.Tensor, b: torch.Tensor, b
     return out if ok else None
 
 
-# ---- AdaRound (include/ppq_hip.h ppqhip_adaround_fwd_multi / ppqhip_adaround_bwd_multi) ------------------------------------
+# ---- the weight maps: AdaRound and round tuning (include/ppq_hip.h ppqhip_adaround_*_multi / ppqhip_roundtune_fwd_multi) ------
 _ADAROUND_JOB = np.dtype([('w', '<u8'), ('v', '<u8'), ('scale', '<u8'), ('offset', '<u8'), ('out', '<u8'), ('dy', '<u8'),
                           ('n', '<i8'), ('num_channel', '<i8'), ('elem_per_channel', '<i8'), ('qmin', '<i4'), ('qmax', '<i4')])
+_ROUNDTUNE_JOB = np.dtype([('w', '<u8'), ('r', '<u8'), ('scale', '<u8'), ('offset', '<u8'), ('out', '<u8'),
+                           ('n', '<i8'), ('num_channel', '<i8'), ('elem_per_channel', '<i8'), ('qmin', '<i4'), ('qmax', '<i4')])
 
 
-def _adaround_table(items, outs, dys=None):
-    """items[k] = (w, v, scale, offset, channel_axis or None, quant_min, quant_max): w, v and outs[k] (and dys[k]) contiguous
-    float32 CUDA tensors of one shape on one device, scale / offset contiguous float32 with one element per channel."""
+def _weight_map_table(label, dtype, items, outs, dys=None):
+    """items[k] = (w, rounding, scale, offset, channel_axis or None, quant_min, quant_max): w (round tuning: the pre-floored
+    weight), the rounding variable (AdaRound's V, round tuning's R) and outs[k] (and dys[k]) contiguous float32 CUDA tensors of
+    one shape on one device, scale / offset contiguous float32 with one element per channel.  ``dtype``: _ADAROUND_JOB (with
+    its ``dy`` column, 0 in the forward) or _ROUNDTUNE_JOB."""
     n = len(items)
     if len(outs) != n or (dys is not None and len(dys) != n):
-        raise RuntimeError(_KERNEL_FAILURE + 'AdaRound: argument lists differ in length')
-    jobs = np.zeros(n, dtype=_ADAROUND_JOB)
+        raise RuntimeError(_KERNEL_FAILURE + f'{label}: argument lists differ in length')
+    jobs = np.zeros(n, dtype=dtype)
     dev = items[0][0].device
     for k, (w, v, s, o, axis, qmin, qmax) in enumerate(items):
         ts = [('Value', w), ('Rounding', v), ('Scale', s), ('Offset', o), ('Out', outs[k])] + ([('Dy', dys[k])] if dys is not None else [])
         for name, t in ts:
             _f32(t, name)
-            if t.device != dev: raise RuntimeError(_KERNEL_FAILURE + f'AdaRound: item {k}: {name} is on another device')
-            if not t.is_contiguous(): raise RuntimeError(_KERNEL_FAILURE + f'AdaRound: item {k}: {name} is not contiguous')
+            if t.device != dev: raise RuntimeError(_KERNEL_FAILURE + f'{label}: item {k}: {name} is on another device')
+            if not t.is_contiguous(): raise RuntimeError(_KERNEL_FAILURE + f'{label}: item {k}: {name} is not contiguous')
         for name, t in ts[1:2] + ts[4:]:
-            if t.shape != w.shape: raise RuntimeError(_KERNEL_FAILURE + f'AdaRound: item {k}: {name} is not shaped like the weight')
+            if t.shape != w.shape: raise RuntimeError(_KERNEL_FAILURE + f'{label}: item {k}: {name} is not shaped like the weight')
         C, epc = _geometry(w.shape, axis) if axis is not None else (1, w.numel())
         if s.numel() != C or o.numel() != C:
-            raise RuntimeError(_KERNEL_FAILURE + f'AdaRound: item {k}: scale / offset need {C} elements')
-        jobs[k] = (w.data_ptr(), v.data_ptr(), s.data_ptr(), o.data_ptr(), outs[k].data_ptr(),
-                   dys[k].data_ptr() if dys is not None else 0, w.numel(), C, epc, int(qmin), int(qmax))
+            raise RuntimeError(_KERNEL_FAILURE + f'{label}: item {k}: scale / offset need {C} elements')
+        ptrs = [t.data_ptr() for _, t in ts[:5]]
+        if 'dy' in dtype.names: ptrs.append(dys[k].data_ptr() if dys is not None else 0)
+        jobs[k] = (*ptrs, w.numel(), C, epc, int(qmin), int(qmax))
     return jobs
 
 
@@ -322,7 +327,7 @@ def adaround_forward_multi(items, outs=None) -> List[torch.Tensor]:
     caller-owned) receive the fake-quantised weights.  The job table travels in the kernel arguments: capturable."""
     if not items: return []
     if outs is None: outs = [torch.empty_like(it[0]) for it in items]
-    jobs = _adaround_table(items, outs)
+    jobs = _weight_map_table('AdaRound', _ADAROUND_JOB, items, outs)
     with _DeviceOf(items[0][0]):
         _raise(lib.ppqhip_adaround_fwd_multi(jobs.ctypes.data, len(items), _stream()))
     return outs
@@ -336,37 +341,10 @@ def adaround_backward_multi(items, dys, reg: torch.Tensor, dvs=None) -> List[tor
     if reg.numel() != 3 or not reg.is_contiguous() or reg.device != items[0][0].device:
         raise RuntimeError(_KERNEL_FAILURE + 'AdaRound: reg must be a contiguous float32[3] on the weights\' device')
     if dvs is None: dvs = [torch.empty_like(it[0]) for it in items]
-    jobs = _adaround_table(items, dvs, dys)
+    jobs = _weight_map_table('AdaRound', _ADAROUND_JOB, items, dvs, dys)
     with _DeviceOf(items[0][0]):
         _raise(lib.ppqhip_adaround_bwd_multi(jobs.ctypes.data, len(items), reg.data_ptr(), _stream()))
     return dvs
-
-
-# ---- round tuning (include/ppq_hip.h ppqhip_roundtune_fwd_multi) -------------------------------------------------------------
-_ROUNDTUNE_JOB = np.dtype([('w', '<u8'), ('r', '<u8'), ('scale', '<u8'), ('offset', '<u8'), ('out', '<u8'),
-                           ('n', '<i8'), ('num_channel', '<i8'), ('elem_per_channel', '<i8'), ('qmin', '<i4'), ('qmax', '<i4')])
-
-
-def _roundtune_table(items, outs):
-    """items[k] = (w, r, scale, offset, channel_axis or None, quant_min, quant_max): w (the pre-floored weight), r and outs[k]
-    contiguous float32 CUDA tensors of one shape on one device, scale / offset contiguous float32 with one element per channel."""
-    n = len(items)
-    if len(outs) != n: raise RuntimeError(_KERNEL_FAILURE + 'RoundTuning: argument lists differ in length')
-    jobs = np.zeros(n, dtype=_ROUNDTUNE_JOB)
-    dev = items[0][0].device
-    for k, (w, r, s, o, axis, qmin, qmax) in enumerate(items):
-        ts = [('Value', w), ('Rounding', r), ('Scale', s), ('Offset', o), ('Out', outs[k])]
-        for name, t in ts:
-            _f32(t, name)
-            if t.device != dev: raise RuntimeError(_KERNEL_FAILURE + f'RoundTuning: item {k}: {name} is on another device')
-            if not t.is_contiguous(): raise RuntimeError(_KERNEL_FAILURE + f'RoundTuning: item {k}: {name} is not contiguous')
-        for name, t in ts[1:2] + ts[4:]:
-            if t.shape != w.shape: raise RuntimeError(_KERNEL_FAILURE + f'RoundTuning: item {k}: {name} is not shaped like the weight')
-        C, epc = _geometry(w.shape, axis) if axis is not None else (1, w.numel())
-        if s.numel() != C or o.numel() != C:
-            raise RuntimeError(_KERNEL_FAILURE + f'RoundTuning: item {k}: scale / offset need {C} elements')
-        jobs[k] = (w.data_ptr(), r.data_ptr(), s.data_ptr(), o.data_ptr(), outs[k].data_ptr(), w.numel(), C, epc, int(qmin), int(qmax))
-    return jobs
 
 
 def roundtune_forward_multi(items, outs=None) -> List[torch.Tensor]:
@@ -375,7 +353,7 @@ def roundtune_forward_multi(items, outs=None) -> List[torch.Tensor]:
     capturable.  The reference's backward is the identity, so there is nothing else to launch."""
     if not items: return []
     if outs is None: outs = [torch.empty_like(it[0]) for it in items]
-    jobs = _roundtune_table(items, outs)
+    jobs = _weight_map_table('RoundTuning', _ROUNDTUNE_JOB, items, outs)
     with _DeviceOf(items[0][0]):
         _raise(lib.ppqhip_roundtune_fwd_multi(jobs.ctypes.data, len(items), _stream()))
     return outs

@@ -37,8 +37,17 @@ def _item(w, v, s, o, axis, qmin, qmax):
     return (w, v, s, o, axis, qmin, qmax)
 
 
+# A job has at most 1024 workgroups of 256 lanes (csrc/channel_axis.hpp): a lane takes a second trip through the float4 loop from
+# 262,145 float4, through the element-wise loop (the unaligned variants) from 262,145 elements.  The three forms of the float4
+# loop: per tensor (four channel computations per float4 with one channel; n % 4 = 1), elem_per_channel = 209,924 (a multiple of
+# 4: one channel per float4; 262,405 float4) and elem_per_channel = 349,867 (odd: four channels per float4; 262,400 float4,
+# n % 4 = 1).
+_TRIP2 = (('trip2_pt', (1025, 1025), None, -128, 127), ('trip2_plane', (5, 52481, 2, 2), 0, -8, 7), ('trip2_lanes', (3, 349867), 0, -8, 7))
+
+
 def _cases(extra: bool = True):
-    """(name, w, v, scale, offset, axis, qmin, qmax, dy) on the GPU: the golden cases, and larger / unaligned ones."""
+    """(name, w, v, scale, offset, axis, qmin, qmax, dy) on the GPU: the golden cases, larger / unaligned ones, and the
+    smallest ones (_TRIP2) that send a lane through each loop of the kernels' walk a second time."""
     out = []
     for k, (name, shape, axis, qmin, qmax, _) in enumerate(AC.CASES):
         w, s, o, noise, dy = AC.case_tensors(k)
@@ -47,7 +56,7 @@ def _cases(extra: bool = True):
     if extra:
         g = torch.Generator().manual_seed(77)
         for name, shape, axis, qmin, qmax in (('conv_big_i4', (64, 32, 3, 3), 0, -8, 7), ('gemm_big_pt', (257, 129), None, -128, 127),
-                                              ('conv_plane7', (32, 16, 7, 7), 0, -128, 127)):
+                                              ('conv_plane7', (32, 16, 7, 7), 0, -128, 127)) + _TRIP2:
             w = torch.randn(shape, generator=g) * 0.3
             C = 1 if axis is None else shape[axis]
             s = (torch.rand(C, generator=g) * 0.02 + 0.01) if axis is not None else torch.tensor(0.013)
@@ -105,8 +114,8 @@ def test_main_path_dv_is_bit_exact_against_torch_autograd():
         un = adaround_backward_multi([_item(_unaligned(w), _unaligned(v), s, o, axis, qmin, qmax)], [_unaligned(dy)], reg)[0]
         assert np.array_equal(_bits(un), _bits(got)), name
     # -0.0 gradients keep their sign when the term is off (adding +0.0 would turn them into +0.0)
-    name, w, v, s, o, axis, qmin, qmax, dy = cases[-1]
-    got = got_all[-1].view(-1)[8:12]
+    k = [c[0] for c in cases].index('conv_plane7')
+    got = got_all[k].view(-1)[8:12]
     assert all(np.signbit(got.cpu().numpy())) and torch.all(got == 0)
 
 

@@ -33,9 +33,18 @@ def _bits(t: torch.Tensor) -> np.ndarray:
     return np.where(np.isnan(a), np.float32('nan'), a).view(np.uint32)
 
 
+# A job has at most 1024 workgroups of 256 lanes (csrc/channel_axis.hpp): a lane takes a second trip through the float4 loop from
+# 262,145 float4, through the element-wise loop (the unaligned variants) from 262,145 elements.  The three forms of the float4
+# loop: per tensor (four channel computations per float4 with one channel; n % 4 = 1), elem_per_channel = 209,924 (a multiple of
+# 4: one channel per float4; 262,405 float4) and elem_per_channel = 349,867 (odd: four channels per float4; 262,400 float4,
+# n % 4 = 1).
+_TRIP2 = (('trip2_pt', (1025, 1025), None, -128, 127), ('trip2_plane', (5, 52481, 2, 2), 0, -8, 7), ('trip2_lanes', (3, 349867), 0, -8, 7))
+
+
 def _cases(extra: bool = True):
     """(name, t, r, scale, offset, axis, qmin, qmax, dy) on the GPU: the golden cases (t = the floored weight, r = the
-    perturbed R), and larger / unaligned-plane ones with special values."""
+    perturbed R), larger / unaligned-plane ones with special values, and the smallest ones (_TRIP2) that send a lane through
+    each loop of the kernel's walk a second time."""
     out = []
     for k, (name, shape, axis, qmin, qmax, _, _) in enumerate(RC.CASES):
         w, s, o, noise, dy = RC.case_tensors(k)
@@ -44,7 +53,7 @@ def _cases(extra: bool = True):
     if extra:
         g = torch.Generator().manual_seed(78)
         for name, shape, axis, qmin, qmax in (('conv_big_i4', (64, 32, 3, 3), 0, -8, 7), ('gemm_big_pt', (257, 129), None, -128, 127),
-                                              ('conv_plane7', (32, 16, 7, 7), 0, -128, 127), ('convT_big_axis1', (16, 24, 3, 3), 1, -8, 7)):
+                                              ('conv_plane7', (32, 16, 7, 7), 0, -128, 127), ('convT_big_axis1', (16, 24, 3, 3), 1, -8, 7)) + _TRIP2:
             w = torch.randn(shape, generator=g) * 0.3
             C = 1 if axis is None else shape[axis]
             s = (torch.rand(C, generator=g) * 0.02 + 0.01) if axis is not None else torch.tensor(0.013)
