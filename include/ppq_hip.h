@@ -785,6 +785,31 @@ int ppqhip_mx_conv2d(const uint8_t* x_elements, const uint8_t* x_scales, int x_f
                      int64_t o, int64_t kh, int64_t kw, int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
                      int64_t dil_h, int64_t dil_w, void* stream);
 
+/* The same two with a fused epilogue (ppq_amd/mx.py residual= / relu= / out_format=; ADDED under ABI 4) ------ */
+/* Operands, sizes, accumulation and NaN flags are those of ppqhip_mx_gemm / ppqhip_mx_conv2d; the K loop is the same code.  Per output,
+ * in this order: v = acc + bias (bias set); v = v + residual[row, col] (residual set: float32 [m, n] row-major, for the conv
+ * [n, oh, ow, o], 4-byte aligned); v = 0x7fc00000 where the row or column is NaN-flagged (the flag wins over the residual); relu != 0:
+ * v = v > 0 ? v : +0 with a NaN staying a NaN (so -0 becomes +0); c / y set: v is stored as float32 in the plain call's layout;
+ * out_elements / out_scales set (both or neither): v is packed in out_format along the columns (output channels) in blocks of 32,
+ * out_scales [m, nbo] and out_elements [m, nbo * B], nbo = ceil(n / 32), B = 32 / 24 / 16 -- byte for byte what ppqhip_mx_pack makes
+ * of the float32 [m, n] along its last axis (for the conv: of [n, o, oh, ow] along axis 1, which is the x of ppqhip_mx_conv2d): a NaN
+ * gives the FP8 NaN code resp. scale 0xFF and zero element bytes for the whole block, a short last block holds +0 in the elements it
+ * lacks.  out_format: one of the five float formats; it is checked even when nothing is packed.
+ * Refused before any launch, beyond what the plain calls refuse: PPQHIP_MXINT8 or an unknown id as out_format; out_elements and
+ * out_scales not both set or both null; no output at all (c / y and out_elements null); out_elements not 16-byte aligned (c / y as in
+ * the plain call when set); more than 2^31 - 1 output blocks; an output overlapping an input (the residual included) or another
+ * output.  m == 0 or n == 0 (n == 0 or o == 0) launches nothing; k == 0 (c == 0) runs the epilogue on bias (or 0) plus residual.
+ * Two calls give identical bits.  Booked under "mx_gemm_fused" / "mx_conv_fused": the operands, and 4 m n bytes for each of residual
+ * and c, and the packed bytes, where present. */
+int ppqhip_mx_gemm_fused(const uint8_t* a_elements, const uint8_t* a_scales, int a_format, const uint8_t* b_elements,
+                         const uint8_t* b_scales, int b_format, const float* bias, const float* residual, int relu, float* c,
+                         uint8_t* out_elements, uint8_t* out_scales, int out_format, int64_t m, int64_t n, int64_t k, void* stream);
+int ppqhip_mx_conv2d_fused(const uint8_t* x_elements, const uint8_t* x_scales, int x_format, const uint8_t* w_elements,
+                           const uint8_t* w_scales, int w_format, const float* bias, const float* residual, int relu, float* y,
+                           uint8_t* out_elements, uint8_t* out_scales, int out_format, int64_t n, int64_t c, int64_t h, int64_t w,
+                           int64_t o, int64_t kh, int64_t kw, int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
+                           int64_t dil_h, int64_t dil_w, void* stream);
+
 /* profiling aid used by bench.py: when enabled, every kernel launch made through this library
  * on this thread is bracketed by hipEvents on its own stream; ppqhip_prof_collect() synchronises
  * those events and returns, per kernel id, launches / total ms / total algorithmic bytes. */

@@ -18,6 +18,8 @@
 // the bits are those of mx_gemm.hip on the gathered A operand: same instructions, same register contents, same order.
 // NaN: as in mx_gemm.hip; padding is not read, so an output is NaN exactly when its window covers a NaN block of x, or its output
 // channel holds one in w.
+// ppqhip_mx_conv2d_fused runs the same K loop with the fused epilogue of mx_mfma.hpp: residual, ReLU and the result
+// packed along the output columns, in a second set of 25 instantiations; the plain kernels keep their code.
 #include "common.hpp"
 #include "job_table.hpp"
 #include "mx_mfma.hpp"
@@ -120,8 +122,12 @@ __device__ __forceinline__ void load_activation(const MxConvArgs& g, const ConvR
     }
 }
 
-template <int FA, int FB>
-__global__ __launch_bounds__(kBlock) void mx_conv_kernel(const MxConvArgs g) {
+// F is empty -- the plain kernel, (g) alone -- or one MxFusedOut: the epilogue of mx_mfma.hpp (fused_epilogue) in place of the plain
+// one, (g, f).  Everything up to the epilogue is the same code; in the fused kernel g.y may be null.
+template <int FA, int FB, typename... F>
+__global__ __launch_bounds__(kBlock) void mx_conv_kernel(const MxConvArgs g, const F... f) {
+    constexpr bool FUSED = sizeof...(F) != 0;
+    static_assert(sizeof...(F) <= 1, "at most one MxFusedOut");
     constexpr int T = kGemmWaveTiles;
     constexpr uint32_t BB = 4u * gemm_elem_bits(FB);
     constexpr int HA = gemm_hw_format(FA), HB = gemm_hw_format(FB);               // immediates of the instruction
@@ -178,6 +184,11 @@ __global__ __launch_bounds__(kBlock) void mx_conv_kernel(const MxConvArgs g) {
     uint32_t rows_nan[T], cols_nan[T];
 #pragma unroll
     for (int t = 0; t < T; t++) { rows_nan[t] = tile_flags(nan_a[t]); cols_nan[t] = tile_flags(nan_b[t]); }
+    if constexpr (FUSED) {                                                       // the stage is wave-private: no barrier, the early return stands
+        __shared__ __attribute__((aligned(16))) uint8_t stage[kGemmWaves * kGemmWaves * kFusedStageBytes];
+        fused_epilogue(acc, rows_nan, cols_nan, g.bias, g.y, g.m, g.o, m0, n0, lane, f..., stage + wave * kFusedStageBytes);
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < T; j++) {
         const uint32_t col = n0 + j * kGemmTile + r;
@@ -198,19 +209,26 @@ __global__ __launch_bounds__(kBlock) void mx_conv_kernel(const MxConvArgs g) {
 }
 
 template <int FA, int FB>
-void launch(const MxConvArgs& g, uint32_t blocks, hipStream_t s) {
-    hipLaunchKernelGGL((mx_conv_kernel<FA, FB>), dim3(blocks), dim3(kBlock), 0, s, g);
+void launch(const MxConvArgs& g, const MxFusedOut* f, uint32_t blocks, hipStream_t s) {
+    if (f != nullptr) hipLaunchKernelGGL((mx_conv_kernel<FA, FB, MxFusedOut>), dim3(blocks), dim3(kBlock), 0, s, g, *f);
+    else hipLaunchKernelGGL((mx_conv_kernel<FA, FB>), dim3(blocks), dim3(kBlock), 0, s, g);
 }
 template <int FA>
-void launch_b(int fb, const MxConvArgs& g, uint32_t blocks, hipStream_t s) {
+void launch_b(int fb, const MxConvArgs& g, const MxFusedOut* f, uint32_t blocks, hipStream_t s) {
     switch (fb) {
-        case PPQHIP_MXFP8_E4M3: launch<FA, PPQHIP_MXFP8_E4M3>(g, blocks, s); break;
-        case PPQHIP_MXFP8_E5M2: launch<FA, PPQHIP_MXFP8_E5M2>(g, blocks, s); break;
-        case PPQHIP_MXFP6_E3M2: launch<FA, PPQHIP_MXFP6_E3M2>(g, blocks, s); break;
-        case PPQHIP_MXFP6_E2M3: launch<FA, PPQHIP_MXFP6_E2M3>(g, blocks, s); break;
-        default: launch<FA, PPQHIP_MXFP4_E2M1>(g, blocks, s); break;
+        case PPQHIP_MXFP8_E4M3: launch<FA, PPQHIP_MXFP8_E4M3>(g, f, blocks, s); break;
+        case PPQHIP_MXFP8_E5M2: launch<FA, PPQHIP_MXFP8_E5M2>(g, f, blocks, s); break;
+        case PPQHIP_MXFP6_E3M2: launch<FA, PPQHIP_MXFP6_E3M2>(g, f, blocks, s); break;
+        case PPQHIP_MXFP6_E2M3: launch<FA, PPQHIP_MXFP6_E2M3>(g, f, blocks, s); break;
+        default: launch<FA, PPQHIP_MXFP4_E2M1>(g, f, blocks, s); break;
     }
 }
+
+// what a fused call adds to a plain one, as the entry point received it
+struct ConvFusedHost {
+    const float* residual; int relu;
+    uint8_t* out_elements; uint8_t* out_scales; int out_format;
+};
 
 // a * b when it stays within 2^31 - 1 (both are within it already), -1 otherwise
 int64_t bounded_product(int64_t a, int64_t b) {
@@ -218,18 +236,18 @@ int64_t bounded_product(int64_t a, int64_t b) {
     return p > kMxMax ? -1 : p;
 }
 
-}  // namespace
-}  // namespace ppqhip
+// both entry points; `fused` is null for ppqhip_mx_conv2d, whose checks, strings and launch are unchanged
+int run_conv(const char* what, const uint8_t* x_elements, const uint8_t* x_scales, int x_format, const uint8_t* w_elements,
+             const uint8_t* w_scales, int w_format, const float* bias, float* y, int64_t n, int64_t c, int64_t h, int64_t w, int64_t o,
+             int64_t kh, int64_t kw, int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w,
+             const ConvFusedHost* fused, void* stream) {
 
-using namespace ppqhip;
-
-extern "C" int ppqhip_mx_conv2d(const uint8_t* x_elements, const uint8_t* x_scales, int x_format, const uint8_t* w_elements,
-                                const uint8_t* w_scales, int w_format, const float* bias, float* y, int64_t n, int64_t c, int64_t h,
-                                int64_t w, int64_t o, int64_t kh, int64_t kw, int64_t stride_h, int64_t stride_w, int64_t pad_h,
-                                int64_t pad_w, int64_t dil_h, int64_t dil_w, void* stream) {
-    const char* what = "mx_conv2d";
     if (int st = check_format(what, "x", x_format)) return st;
     if (int st = check_format(what, "w", w_format)) return st;
+    MxFusedOut f = {};
+    if (fused != nullptr) {
+        if (int st = check_fused_outputs(what, "y", y, fused->out_elements, fused->out_scales, fused->out_format, &f.fmt)) return st;
+    }
     const int64_t sizes[] = {n, c, h, w, o, kh, kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w};
     for (int64_t v : sizes) {
         if (v < 0) { set_error("%s: negative size", what); return PPQHIP_ERR_INVALID_VALUE; }
@@ -254,7 +272,7 @@ extern "C" int ppqhip_mx_conv2d(const uint8_t* x_elements, const uint8_t* x_scal
     if (n == 0 || o == 0) return PPQHIP_OK;
     const bool read_x = blocks_x > 0, read_w = read_x && nb > 0;     // an input without a pixel: every tap is padding, nothing is read
     const int64_t BA = 4 * (int64_t)gemm_elem_bits(x_format), BB = 4 * (int64_t)gemm_elem_bits(w_format);
-    if (y == nullptr || (read_x && (x_elements == nullptr || x_scales == nullptr)) || (read_w && (w_elements == nullptr || w_scales == nullptr))) {
+    if ((y == nullptr && fused == nullptr) || (read_x && (x_elements == nullptr || x_scales == nullptr)) || (read_w && (w_elements == nullptr || w_scales == nullptr))) {
         set_error("%s: null pointer", what); return PPQHIP_ERR_INVALID_VALUE;
     }
     if (!aligned16(y) || (read_x && !aligned16(x_elements)) || (read_w && !aligned16(w_elements))) {
@@ -266,7 +284,22 @@ extern "C" int ppqhip_mx_conv2d(const uint8_t* x_elements, const uint8_t* x_scal
     if (read_x) { ins.push_back(span_of(x_elements, blocks_x * BA)); ins.push_back(span_of(x_scales, blocks_x)); }
     if (read_w) { ins.push_back(span_of(w_elements, o * nb * BB)); ins.push_back(span_of(w_scales, o * nb)); }
     if (bias != nullptr) ins.push_back(span_of(bias, o));
-    outs.push_back(span_of(y, m * o));
+    if (y != nullptr) outs.push_back(span_of(y, m * o));
+    // booked: packed x once (a pixel is read by up to kh kw windows, from cache), packed w and 4 m o bytes of y; the launch does
+    // 2 m o nb 32 flops
+    double bytes = (double)blocks_x * (double)(BA + 1) + (double)o * (double)nb * (double)(BB + 1);
+    if (y != nullptr) bytes += 4.0 * (double)m * (double)o;
+    if (fused != nullptr) {                       // and what the fused epilogue moves: the residual and the packed result
+        const int64_t nbo = (o + kMxBlock - 1) / kMxBlock, BO = 4 * (int64_t)gemm_elem_bits(fused->out_format);
+        if (m * nbo > kMxMax) { set_error("%s: more than 2^31 - 1 output blocks", what); return PPQHIP_ERR_INVALID_VALUE; }
+        if (fused->residual != nullptr) { ins.push_back(span_of(fused->residual, m * o)); bytes += 4.0 * (double)m * (double)o; }
+        if (fused->out_elements != nullptr) {
+            outs.push_back(span_of(fused->out_elements, m * nbo * BO)); outs.push_back(span_of(fused->out_scales, m * nbo));
+            bytes += (double)m * (double)nbo * (double)(BO + 1);
+        }
+        f.residual = fused->residual; f.elements = fused->out_elements; f.scales = fused->out_scales;
+        f.relu = fused->relu ? 1u : 0u; f.format = (uint32_t)fused->out_format; f.nbo = (uint32_t)nbo;
+    }
     if (int st = check_overlap(what, ins, outs)) return st;
 
     MxConvArgs g;
@@ -281,16 +314,37 @@ extern "C" int ppqhip_mx_conv2d(const uint8_t* x_elements, const uint8_t* x_scal
     g.fnbc = make_fastdiv((uint32_t)std::max<int64_t>(nbc, 1)); g.fkw = make_fastdiv((uint32_t)kw);
     const uint32_t blocks = (uint32_t)(tiles_m * tiles_n);
     hipStream_t s = (hipStream_t)stream;
-    // booked: packed x once (a pixel is read by up to kh kw windows, from cache), packed w and 4 m o bytes of y; the launch does
-    // 2 m o nb 32 flops
-    const double bytes = (double)blocks_x * (double)(BA + 1) + (double)o * (double)nb * (double)(BB + 1) + 4.0 * (double)m * (double)o;
-    LaunchScope scope(K_MX_CONV, bytes, s);
+    const MxFusedOut* fp = fused != nullptr ? &f : nullptr;
+    LaunchScope scope(fused != nullptr ? K_MX_CONV_FUSED : K_MX_CONV, bytes, s);
     switch (x_format) {
-        case PPQHIP_MXFP8_E4M3: launch_b<PPQHIP_MXFP8_E4M3>(w_format, g, blocks, s); break;
-        case PPQHIP_MXFP8_E5M2: launch_b<PPQHIP_MXFP8_E5M2>(w_format, g, blocks, s); break;
-        case PPQHIP_MXFP6_E3M2: launch_b<PPQHIP_MXFP6_E3M2>(w_format, g, blocks, s); break;
-        case PPQHIP_MXFP6_E2M3: launch_b<PPQHIP_MXFP6_E2M3>(w_format, g, blocks, s); break;
-        default: launch_b<PPQHIP_MXFP4_E2M1>(w_format, g, blocks, s); break;
+        case PPQHIP_MXFP8_E4M3: launch_b<PPQHIP_MXFP8_E4M3>(w_format, g, fp, blocks, s); break;
+        case PPQHIP_MXFP8_E5M2: launch_b<PPQHIP_MXFP8_E5M2>(w_format, g, fp, blocks, s); break;
+        case PPQHIP_MXFP6_E3M2: launch_b<PPQHIP_MXFP6_E3M2>(w_format, g, fp, blocks, s); break;
+        case PPQHIP_MXFP6_E2M3: launch_b<PPQHIP_MXFP6_E2M3>(w_format, g, fp, blocks, s); break;
+        default: launch_b<PPQHIP_MXFP4_E2M1>(w_format, g, fp, blocks, s); break;
     }
     return finish_launch(what);
+}
+
+}  // namespace
+}  // namespace ppqhip
+
+using namespace ppqhip;
+
+extern "C" int ppqhip_mx_conv2d(const uint8_t* x_elements, const uint8_t* x_scales, int x_format, const uint8_t* w_elements,
+                                const uint8_t* w_scales, int w_format, const float* bias, float* y, int64_t n, int64_t c, int64_t h,
+                                int64_t w, int64_t o, int64_t kh, int64_t kw, int64_t stride_h, int64_t stride_w, int64_t pad_h,
+                                int64_t pad_w, int64_t dil_h, int64_t dil_w, void* stream) {
+    return run_conv("mx_conv2d", x_elements, x_scales, x_format, w_elements, w_scales, w_format, bias, y, n, c, h, w, o, kh, kw, stride_h,
+                    stride_w, pad_h, pad_w, dil_h, dil_w, nullptr, stream);
+}
+
+extern "C" int ppqhip_mx_conv2d_fused(const uint8_t* x_elements, const uint8_t* x_scales, int x_format, const uint8_t* w_elements,
+                                      const uint8_t* w_scales, int w_format, const float* bias, const float* residual, int relu, float* y,
+                                      uint8_t* out_elements, uint8_t* out_scales, int out_format, int64_t n, int64_t c, int64_t h,
+                                      int64_t w, int64_t o, int64_t kh, int64_t kw, int64_t stride_h, int64_t stride_w, int64_t pad_h,
+                                      int64_t pad_w, int64_t dil_h, int64_t dil_w, void* stream) {
+    const ConvFusedHost fused = {residual, relu, out_elements, out_scales, out_format};
+    return run_conv("mx_conv2d_fused", x_elements, x_scales, x_format, w_elements, w_scales, w_format, bias, y, n, c, h, w, o, kh, kw,
+                    stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, &fused, stream);
 }

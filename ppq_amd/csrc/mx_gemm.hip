@@ -24,6 +24,8 @@
 // NaN: the result is NaN wherever dequantise-then-multiply is, whatever the instruction itself makes of the codes: a scale code
 // 0xFF or an FP8 NaN code seen while a row's (column's) blocks are loaded flags the row (column), and flagged outputs are written
 // as the quiet NaN 0x7fc00000.
+// ppqhip_mx_gemm_fused runs the same K loop with the fused epilogue of mx_mfma.hpp: residual, ReLU and the result
+// packed along the output columns, in a second set of 25 instantiations; the plain kernels keep their code.
 #include "common.hpp"
 #include "job_table.hpp"
 #include "mx_mfma.hpp"
@@ -40,8 +42,12 @@ struct MxGemmArgs {
     FastDiv tiles_n;                              // workgroups along N
 };
 
-template <int FA, int FB>
-__global__ __launch_bounds__(kBlock) void mx_gemm_kernel(const MxGemmArgs g) {
+// F is empty -- the plain kernel, (g) alone -- or one MxFusedOut: the epilogue of mx_mfma.hpp (fused_epilogue) in place of the plain
+// one, (g, f).  Everything up to the epilogue is the same code; in the fused kernel g.c may be null.
+template <int FA, int FB, typename... F>
+__global__ __launch_bounds__(kBlock) void mx_gemm_kernel(const MxGemmArgs g, const F... f) {
+    constexpr bool FUSED = sizeof...(F) != 0;
+    static_assert(sizeof...(F) <= 1, "at most one MxFusedOut");
     constexpr int T = kGemmWaveTiles;
     constexpr uint32_t BA = 4u * gemm_elem_bits(FA), BB = 4u * gemm_elem_bits(FB);
     constexpr int HA = gemm_hw_format(FA), HB = gemm_hw_format(FB);               // immediates of the instruction
@@ -93,6 +99,11 @@ __global__ __launch_bounds__(kBlock) void mx_gemm_kernel(const MxGemmArgs g) {
     uint32_t rows_nan[T], cols_nan[T];
 #pragma unroll
     for (int t = 0; t < T; t++) { rows_nan[t] = tile_flags(nan_a[t]); cols_nan[t] = tile_flags(nan_b[t]); }
+    if constexpr (FUSED) {                                                       // the stage is wave-private: no barrier, the early return stands
+        __shared__ __attribute__((aligned(16))) uint8_t stage[kGemmWaves * kGemmWaves * kFusedStageBytes];
+        fused_epilogue(acc, rows_nan, cols_nan, g.bias, g.c, g.m, g.n, m0, n0, lane, f..., stage + wave * kFusedStageBytes);
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < T; j++) {
         const uint32_t col = n0 + j * kGemmTile + r;
@@ -113,37 +124,43 @@ __global__ __launch_bounds__(kBlock) void mx_gemm_kernel(const MxGemmArgs g) {
 }
 
 template <int FA, int FB>
-void launch(const MxGemmArgs& g, uint32_t blocks, hipStream_t s) {
-    hipLaunchKernelGGL((mx_gemm_kernel<FA, FB>), dim3(blocks), dim3(kBlock), 0, s, g);
+void launch(const MxGemmArgs& g, const MxFusedOut* f, uint32_t blocks, hipStream_t s) {
+    if (f != nullptr) hipLaunchKernelGGL((mx_gemm_kernel<FA, FB, MxFusedOut>), dim3(blocks), dim3(kBlock), 0, s, g, *f);
+    else hipLaunchKernelGGL((mx_gemm_kernel<FA, FB>), dim3(blocks), dim3(kBlock), 0, s, g);
 }
 template <int FA>
-void launch_b(int fb, const MxGemmArgs& g, uint32_t blocks, hipStream_t s) {
+void launch_b(int fb, const MxGemmArgs& g, const MxFusedOut* f, uint32_t blocks, hipStream_t s) {
     switch (fb) {
-        case PPQHIP_MXFP8_E4M3: launch<FA, PPQHIP_MXFP8_E4M3>(g, blocks, s); break;
-        case PPQHIP_MXFP8_E5M2: launch<FA, PPQHIP_MXFP8_E5M2>(g, blocks, s); break;
-        case PPQHIP_MXFP6_E3M2: launch<FA, PPQHIP_MXFP6_E3M2>(g, blocks, s); break;
-        case PPQHIP_MXFP6_E2M3: launch<FA, PPQHIP_MXFP6_E2M3>(g, blocks, s); break;
-        default: launch<FA, PPQHIP_MXFP4_E2M1>(g, blocks, s); break;
+        case PPQHIP_MXFP8_E4M3: launch<FA, PPQHIP_MXFP8_E4M3>(g, f, blocks, s); break;
+        case PPQHIP_MXFP8_E5M2: launch<FA, PPQHIP_MXFP8_E5M2>(g, f, blocks, s); break;
+        case PPQHIP_MXFP6_E3M2: launch<FA, PPQHIP_MXFP6_E3M2>(g, f, blocks, s); break;
+        case PPQHIP_MXFP6_E2M3: launch<FA, PPQHIP_MXFP6_E2M3>(g, f, blocks, s); break;
+        default: launch<FA, PPQHIP_MXFP4_E2M1>(g, f, blocks, s); break;
     }
 }
 
-}  // namespace
-}  // namespace ppqhip
+// what a fused call adds to a plain one, as the entry point received it
+struct GemmFusedHost {
+    const float* residual; int relu;
+    uint8_t* out_elements; uint8_t* out_scales; int out_format;
+};
 
-using namespace ppqhip;
-
-extern "C" int ppqhip_mx_gemm(const uint8_t* a_elements, const uint8_t* a_scales, int a_format, const uint8_t* b_elements,
-                              const uint8_t* b_scales, int b_format, const float* bias, float* c, int64_t m, int64_t n, int64_t k,
-                              void* stream) {
-    const char* what = "mx_gemm";
+// both entry points; `fused` is null for ppqhip_mx_gemm, whose checks, strings and launch are unchanged
+int run_gemm(const char* what, const uint8_t* a_elements, const uint8_t* a_scales, int a_format, const uint8_t* b_elements,
+             const uint8_t* b_scales, int b_format, const float* bias, float* c, int64_t m, int64_t n, int64_t k, const GemmFusedHost* fused,
+             void* stream) {
     if (int st = check_format(what, "A", a_format)) return st;
     if (int st = check_format(what, "B", b_format)) return st;
+    MxFusedOut f = {};
+    if (fused != nullptr) {
+        if (int st = check_fused_outputs(what, "c", c, fused->out_elements, fused->out_scales, fused->out_format, &f.fmt)) return st;
+    }
     if (m < 0 || n < 0 || k < 0) { set_error("%s: negative size", what); return PPQHIP_ERR_INVALID_VALUE; }
     if (m > kMxMax || n > kMxMax || k > kMxMax) { set_error("%s: a size above 2^31 - 1", what); return PPQHIP_ERR_INVALID_VALUE; }
     if (m == 0 || n == 0) return PPQHIP_OK;
     const int64_t nb = (k + kMxBlock - 1) / kMxBlock;
     const int64_t BA = 4 * (int64_t)gemm_elem_bits(a_format), BB = 4 * (int64_t)gemm_elem_bits(b_format);
-    if (c == nullptr || (nb > 0 && (a_elements == nullptr || a_scales == nullptr || b_elements == nullptr || b_scales == nullptr))) {
+    if ((c == nullptr && fused == nullptr) || (nb > 0 && (a_elements == nullptr || a_scales == nullptr || b_elements == nullptr || b_scales == nullptr))) {
         set_error("%s: null pointer", what); return PPQHIP_ERR_INVALID_VALUE;
     }
     if (!aligned16(c) || (nb > 0 && (!aligned16(a_elements) || !aligned16(b_elements)))) {
@@ -157,7 +174,21 @@ extern "C" int ppqhip_mx_gemm(const uint8_t* a_elements, const uint8_t* a_scales
         ins.push_back(span_of(b_elements, n * nb * BB)); ins.push_back(span_of(b_scales, n * nb));
     }
     if (bias != nullptr) ins.push_back(span_of(bias, n));
-    outs.push_back(span_of(c, m * n));
+    if (c != nullptr) outs.push_back(span_of(c, m * n));
+    // booked: the operands and 4 m n bytes of C; the launch does 2 m n nb 32 flops
+    double bytes = (double)m * (double)nb * (double)(BA + 1) + (double)n * (double)nb * (double)(BB + 1);
+    if (c != nullptr) bytes += 4.0 * (double)m * (double)n;
+    if (fused != nullptr) {                       // and what the fused epilogue moves: the residual and the packed result
+        const int64_t nbo = (n + kMxBlock - 1) / kMxBlock, BO = 4 * (int64_t)gemm_elem_bits(fused->out_format);
+        if (m * nbo > kMxMax) { set_error("%s: more than 2^31 - 1 output blocks", what); return PPQHIP_ERR_INVALID_VALUE; }
+        if (fused->residual != nullptr) { ins.push_back(span_of(fused->residual, m * n)); bytes += 4.0 * (double)m * (double)n; }
+        if (fused->out_elements != nullptr) {
+            outs.push_back(span_of(fused->out_elements, m * nbo * BO)); outs.push_back(span_of(fused->out_scales, m * nbo));
+            bytes += (double)m * (double)nbo * (double)(BO + 1);
+        }
+        f.residual = fused->residual; f.elements = fused->out_elements; f.scales = fused->out_scales;
+        f.relu = fused->relu ? 1u : 0u; f.format = (uint32_t)fused->out_format; f.nbo = (uint32_t)nbo;
+    }
     if (int st = check_overlap(what, ins, outs)) return st;
 
     MxGemmArgs g;
@@ -166,15 +197,33 @@ extern "C" int ppqhip_mx_gemm(const uint8_t* a_elements, const uint8_t* a_scales
     g.tiles_n = make_fastdiv((uint32_t)tiles_n);
     const uint32_t blocks = (uint32_t)(tiles_m * tiles_n);
     hipStream_t s = (hipStream_t)stream;
-    // booked: the operands and 4 m n bytes of C; the launch does 2 m n nb 32 flops
-    const double bytes = (double)m * (double)nb * (double)(BA + 1) + (double)n * (double)nb * (double)(BB + 1) + 4.0 * (double)m * (double)n;
-    LaunchScope scope(K_MX_GEMM, bytes, s);
+    const MxFusedOut* fp = fused != nullptr ? &f : nullptr;
+    LaunchScope scope(fused != nullptr ? K_MX_GEMM_FUSED : K_MX_GEMM, bytes, s);
     switch (a_format) {
-        case PPQHIP_MXFP8_E4M3: launch_b<PPQHIP_MXFP8_E4M3>(b_format, g, blocks, s); break;
-        case PPQHIP_MXFP8_E5M2: launch_b<PPQHIP_MXFP8_E5M2>(b_format, g, blocks, s); break;
-        case PPQHIP_MXFP6_E3M2: launch_b<PPQHIP_MXFP6_E3M2>(b_format, g, blocks, s); break;
-        case PPQHIP_MXFP6_E2M3: launch_b<PPQHIP_MXFP6_E2M3>(b_format, g, blocks, s); break;
-        default: launch_b<PPQHIP_MXFP4_E2M1>(b_format, g, blocks, s); break;
+        case PPQHIP_MXFP8_E4M3: launch_b<PPQHIP_MXFP8_E4M3>(b_format, g, fp, blocks, s); break;
+        case PPQHIP_MXFP8_E5M2: launch_b<PPQHIP_MXFP8_E5M2>(b_format, g, fp, blocks, s); break;
+        case PPQHIP_MXFP6_E3M2: launch_b<PPQHIP_MXFP6_E3M2>(b_format, g, fp, blocks, s); break;
+        case PPQHIP_MXFP6_E2M3: launch_b<PPQHIP_MXFP6_E2M3>(b_format, g, fp, blocks, s); break;
+        default: launch_b<PPQHIP_MXFP4_E2M1>(b_format, g, fp, blocks, s); break;
     }
     return finish_launch(what);
+}
+
+}  // namespace
+}  // namespace ppqhip
+
+using namespace ppqhip;
+
+extern "C" int ppqhip_mx_gemm(const uint8_t* a_elements, const uint8_t* a_scales, int a_format, const uint8_t* b_elements,
+                              const uint8_t* b_scales, int b_format, const float* bias, float* c, int64_t m, int64_t n, int64_t k,
+                              void* stream) {
+    return run_gemm("mx_gemm", a_elements, a_scales, a_format, b_elements, b_scales, b_format, bias, c, m, n, k, nullptr, stream);
+}
+
+extern "C" int ppqhip_mx_gemm_fused(const uint8_t* a_elements, const uint8_t* a_scales, int a_format, const uint8_t* b_elements,
+                                    const uint8_t* b_scales, int b_format, const float* bias, const float* residual, int relu, float* c,
+                                    uint8_t* out_elements, uint8_t* out_scales, int out_format, int64_t m, int64_t n, int64_t k,
+                                    void* stream) {
+    const GemmFusedHost fused = {residual, relu, out_elements, out_scales, out_format};
+    return run_gemm("mx_gemm_fused", a_elements, a_scales, a_format, b_elements, b_scales, b_format, bias, c, m, n, k, &fused, stream);
 }

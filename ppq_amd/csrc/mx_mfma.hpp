@@ -1,9 +1,11 @@
 // mx_mfma.hpp -- what the kernels on the block-scaled MFMA of gfx950 (v_mfma_scale_f32_16x16x128_f8f6f4) share: mx_gemm.hip and
 // mx_conv.hip.  The workgroup shape, the instruction's format ids, how a lane's operand registers and scale byte are read from an
-// operand packed along its last axis (DESIGN.md sections 9.13, 9.14), the NaN flags and the format check of the entry points.
+// operand packed along its last axis (DESIGN.md sections 9.13, 9.14), the NaN flags, the format check of the entry points and the fused
+// epilogue (residual, ReLU, MX re-quantisation of the result; section 9.16).
 #pragma once
 
 #include "common.hpp"
+#include "mx_coder.hpp"
 #include "mx_common.hpp"
 
 namespace ppqhip {
@@ -94,6 +96,124 @@ __device__ __forceinline__ void load_operand(const uint8_t* const (&e)[kGemmWave
 __device__ __forceinline__ uint32_t tile_flags(uint32_t lane_flag) {
     const unsigned long long b = __builtin_amdgcn_ballot_w64(lane_flag != 0u);
     return (uint32_t)((b | (b >> 16) | (b >> 32) | (b >> 48)) & 0xffffull);
+}
+
+// ---- the fused epilogue ----------------------------------------------------------------------------------
+// What a fused launch takes beyond the plain one: v = acc (+ bias) (+ residual), the NaN flags, the ReLU, then v as float32 (the
+// plain launch's output pointer, which may be null here) and / or v packed along the columns as ppqhip_mx_pack packs a row.
+struct MxFusedOut {
+    const float* residual;                        // [m, n] or null
+    uint8_t* elements; uint8_t* scales;           // [m, nbo * B], [m, nbo]; both null: no packed output
+    uint32_t relu, format;
+    uint32_t nbo;                                 // ceil(n / 32)
+    MxFmt fmt;
+};
+
+constexpr uint32_t kFusedStageBytes = 32u * kMxBlock;                            // a wave's 32 rows of 32 one-byte codes
+static_assert(kGemmTile * kGemmWaveTiles == (int)kMxBlock, "a wave's columns are exactly one MX block");
+
+// four one-byte codes of a dword as 4 x BITS bits
+template <uint32_t BITS>
+__device__ __forceinline__ uint32_t squeeze_codes(uint32_t w) {
+    return (w & 0xffu) | (((w >> 8) & 0xffu) << BITS) | (((w >> 16) & 0xffu) << (2u * BITS)) | ((w >> 24) << (3u * BITS));
+}
+
+// The epilogue of a wave that owns rows m0 .. m0 + 31 and columns n0 .. n0 + 31 (n0 % 32 == 0: block n0 / 32 of each of its rows) of
+// the [m, n] result; acc[i][j][q] is row m0 + 16 i + 4 grp + q, column n0 + 16 j + r.  Rows at or past m and columns at or past n
+// hold copies of the last one (the loads are clamped): they take no part in a block maximum, give code 0 and are not stored.
+// `stage` is this wave's own kFusedStageBytes of LDS: the codes of a row sit in 16 lanes x 2 tiles and are gathered through it, one
+// byte per code; then lane l packs half l & 1 of row l >> 1.  Only the wave itself touches its stage, so the wave is synchronised
+// and no workgroup barrier is needed: the waves that returned early are not waited for.
+__device__ __forceinline__ void fused_epilogue(const v4f (&acc)[kGemmWaveTiles][kGemmWaveTiles], const uint32_t (&rows_nan)[kGemmWaveTiles],
+                                               const uint32_t (&cols_nan)[kGemmWaveTiles], const float* bias, float* c, uint32_t m, uint32_t n,
+                                               uint32_t m0, uint32_t n0, uint32_t lane, const MxFusedOut& f, uint8_t* stage) {
+    constexpr int T = kGemmWaveTiles;
+    const uint32_t r = lane & 15u, grp = lane >> 4;
+    const bool pack = f.elements != nullptr;
+    const MxCoder coder = make_coder(f.format, f.fmt);
+    uint32_t col[T]; bool col_in[T], col_nan[T]; float b[T];
+#pragma unroll
+    for (int j = 0; j < T; j++) {
+        col[j] = n0 + j * kGemmTile + r;
+        col_in[j] = col[j] < n;
+        col[j] = min(col[j], n - 1u);
+        b[j] = bias != nullptr ? bias[col[j]] : 0.f;
+        col_nan[j] = (cols_nan[j] >> r) & 1u;
+    }
+    float res[T][4][T];
+#pragma unroll
+    for (int i = 0; i < T; i++)
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+#pragma unroll
+            for (int j = 0; j < T; j++) {
+                const uint32_t row = min(m0 + i * kGemmTile + grp * 4u + q, m - 1u);
+                res[i][q][j] = f.residual != nullptr ? f.residual[(size_t)row * n + col[j]] : 0.f;
+            }
+#pragma unroll
+    for (int i = 0; i < T; i++) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const uint32_t tr = grp * 4u + q, row = m0 + i * kGemmTile + tr;
+            const bool row_nan = (rows_nan[i] >> tr) & 1u;
+            float v[T]; bool live[T];
+            uint32_t mag = 0u;
+#pragma unroll
+            for (int j = 0; j < T; j++) {
+                float t = bias != nullptr ? acc[i][j][q] + b[j] : acc[i][j][q];
+                if (f.residual != nullptr) t = t + res[i][q][j];
+                if (row_nan || col_nan[j]) t = __uint_as_float(0x7fc00000u);
+                if (f.relu) t = t > 0.f ? t : (t != t ? t : 0.f);                 // -0 -> +0 (the sign of a zero is a code bit); NaN stays
+                v[j] = t;
+                live[j] = row < m && col_in[j];
+                if (live[j] && c != nullptr) c[(size_t)row * n + col[j]] = t;
+                mag = max(mag, live[j] ? mxp_mag(t, coder) : 0u);
+            }
+            if (!pack) continue;                                                 // wave-uniform
+            // the block maximum: the 16 lanes that share grp hold the row's 32 columns
+            mag = max(mag, (uint32_t)__shfl_xor((int)mag, 8, 64));
+            mag = max(mag, (uint32_t)__shfl_xor((int)mag, 4, 64));
+            mag = max(mag, (uint32_t)__shfl_xor((int)mag, 2, 64));
+            mag = max(mag, (uint32_t)__shfl_xor((int)mag, 1, 64));
+            float inv; bool dead;
+            const uint32_t scale = mxp_scale(mag, f.fmt, inv, dead);
+#pragma unroll
+            for (int j = 0; j < T; j++)
+                stage[(i * kGemmTile + tr) * kMxBlock + j * kGemmTile + r] = (uint8_t)(live[j] && !dead ? mxp_code(v[j], inv, f.fmt, coder) : 0u);
+            if (r == 0u && row < m) f.scales[(size_t)row * f.nbo + n0 / kMxBlock] = (uint8_t)scale;
+        }
+    }
+    if (!pack) return;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                        // the wave's own writes, read by its own lanes
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const uint32_t lr = lane >> 1, half = lane & 1u, row = m0 + lr;
+    const uint4 w = *reinterpret_cast<const uint4*>(stage + lr * kMxBlock + half * 16u);
+    if (row >= m) return;
+    const size_t block = (size_t)row * f.nbo + n0 / kMxBlock;
+    if (coder.bits == 8u) {
+        *reinterpret_cast<uint4*>(f.elements + block * 32u + half * 16u) = w;
+    } else if (coder.bits == 4u) {
+        const uint32_t d0 = squeeze_codes<4>(w.x) | (squeeze_codes<4>(w.y) << 16), d1 = squeeze_codes<4>(w.z) | (squeeze_codes<4>(w.w) << 16);
+        *reinterpret_cast<uint2*>(f.elements + block * 16u + half * 8u) = make_uint2(d0, d1);
+    } else {                                                                     // 4 x 24 bits = 12 bytes at 12 * half: dword stores
+        const uint32_t t0 = squeeze_codes<6>(w.x), t1 = squeeze_codes<6>(w.y), t2 = squeeze_codes<6>(w.z), t3 = squeeze_codes<6>(w.w);
+        uint32_t* out = reinterpret_cast<uint32_t*>(f.elements + block * 24u + half * 12u);
+        out[0] = t0 | (t1 << 24); out[1] = (t1 >> 8) | (t2 << 16); out[2] = (t2 >> 16) | (t3 << 8);
+    }
+}
+
+// the host side of MxFusedOut: what both fused entry points check about the outputs before anything else of theirs; fills *fmt
+inline int check_fused_outputs(const char* what, const char* float_name, const float* c, const uint8_t* out_elements, const uint8_t* out_scales,
+                               int out_format, MxFmt* fmt) {
+    if (out_format == PPQHIP_MXINT8) { set_error("%s: out_format: MXINT8 is not a format the fused epilogue packs", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (out_format < PPQHIP_MXFP8_E4M3 || out_format > PPQHIP_MXFP4_E2M1 || !make_mx_fmt(out_format, fmt)) {
+        set_error("%s: out_format: unknown MX format %d", what, out_format); return PPQHIP_ERR_INVALID_VALUE;
+    }
+    if ((out_elements == nullptr) != (out_scales == nullptr)) { set_error("%s: out_elements and out_scales must both be set or both be null", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (c == nullptr && out_elements == nullptr) { set_error("%s: no output: %s and out_elements are both null", what, float_name); return PPQHIP_ERR_INVALID_VALUE; }
+    if (out_elements != nullptr && !aligned16(out_elements)) { set_error("%s: out_elements must be 16-byte aligned", what); return PPQHIP_ERR_INVALID_VALUE; }
+    return PPQHIP_OK;
 }
 
 inline int check_format(const char* what, const char* operand, int format) {

@@ -22,6 +22,7 @@
 //           moves last.  The loads are coalesced along inner, as in mx.hip.
 #include "common.hpp"
 #include "job_table.hpp"
+#include "mx_coder.hpp"
 #include "mx_common.hpp"
 
 namespace ppqhip {
@@ -52,50 +53,9 @@ static_assert(sizeof(MxPackArgs<kMxMaxJobs>) <= 4096, "kernel arguments are limi
 
 constexpr uint32_t kQuietNaN = 0x7fc00000u;
 
-__host__ __device__ constexpr uint32_t mx_elem_bits(uint32_t format) {            // width of an element code
-    return format == PPQHIP_MXFP4_E2M1 ? 4u : (format == PPQHIP_MXFP6_E3M2 || format == PPQHIP_MXFP6_E2M3) ? 6u : 8u;
-}
+// the element coder (MxCoder, make_coder, mxp_mag, mxp_scale, mxp_code) is mx_coder.hpp: the fused epilogue of mx_mfma.hpp packs
+// with it too
 
-// what the element coder needs beyond MxFmt, all derived from it (wave-uniform)
-struct MxCoder {
-    uint32_t bits;             // 8, 6, 4
-    uint32_t code_bias;        // (127 - bias) << m: a normal's code is (pattern >> shift) - code_bias
-    bool is_int, has_nan;
-};
-__device__ __forceinline__ MxCoder make_coder(const MxPackJob& j) {
-    MxCoder c;
-    c.bits = mx_elem_bits(j.format);
-    c.code_bias = ((j.fmt.sub_limit >> 23) - 1u) << (23u - j.fmt.shift);          // emin + 127 = 128 - bias
-    c.is_int = j.format == PPQHIP_MXINT8;
-    c.has_nan = j.format == PPQHIP_MXFP8_E4M3 || j.format == PPQHIP_MXFP8_E5M2;
-    return c;
-}
-
-// the magnitude that takes part in the block maximum; in a format without a NaN encoding a NaN marks the whole block
-constexpr uint32_t kNaNBlock = 0xffffffffu;
-__device__ __forceinline__ uint32_t mxp_mag(float v, const MxCoder& c) {
-    const uint32_t m = __float_as_uint(v) & 0x7fffffffu;
-    return m < 0x7f800000u ? m : (m > 0x7f800000u && !c.has_nan ? kNaNBlock : 0u);
-}
-// scale code and 1 / X of a block from the reduced mxp_mag
-__device__ __forceinline__ uint32_t mxp_scale(uint32_t m, const MxFmt& f, float& inv, bool& dead) {
-    dead = m == kNaNBlock;
-    const uint32_t code = mx_code(dead ? 0u : m, f);
-    inv = mx_pow2(254u - code);
-    return dead ? 0xffu : code;
-}
-// the code of cast(v / X): read off the rounded pattern r.  On the fixed-point grid the code is the grid index r / quantum (exact);
-// a normal's exponent and mantissa fields are the pattern's own, rebiased.  The sign comes from v (1 / X > 0).
-__device__ __forceinline__ uint32_t mxp_code(float v, float inv, const MxFmt& f, const MxCoder& c) {
-    const uint32_t vb = __float_as_uint(v), sign = vb >> 31;
-    const uint32_t mag = __float_as_uint(v * inv) & 0x7fffffffu;
-    const uint32_t r = mx_round(mag, f);
-    const uint32_t k = (uint32_t)(__uint_as_float(r) * f.sub_scale);              // used below sub_limit only: 0 .. 127
-    if (c.is_int) return (sign ? 0u - k : k) & 0xffu;
-    uint32_t code = r < f.sub_limit ? k : (r >> f.shift) - c.code_bias;
-    if ((vb & 0x7fffffffu) > 0x7f800000u) code = 0x7fu;                          // reached by MXFP8 only
-    return code | (sign << (c.bits - 1u));
-}
 // value(code) * X
 __device__ __forceinline__ float mxp_value(uint32_t code, float X, bool scale_nan, const MxFmt& f, const MxCoder& c) {
     if (c.is_int) {
@@ -121,7 +81,7 @@ __device__ __forceinline__ float mxp_value(uint32_t code, float X, bool scale_na
 template <int U>
 __device__ __forceinline__ void pack_rows4(const MxPackJob& j, uint32_t local) {
     constexpr uint32_t kGroups = kBlock / 8;                                     // blocks per workgroup and step
-    const MxCoder c = make_coder(j);
+    const MxCoder c = make_coder(j.format, j.fmt);
     const uint32_t q = threadIdx.x & 7u;
     float4 a[U];
     uint32_t g[U];
@@ -164,7 +124,7 @@ __device__ __forceinline__ void pack_rows4(const MxPackJob& j, uint32_t local) {
 }
 
 __device__ __forceinline__ void pack_rows1(const MxPackJob& j, uint32_t local) {
-    const MxCoder c = make_coder(j);
+    const MxCoder c = make_coder(j.format, j.fmt);
     const uint32_t q = threadIdx.x & 31u;
     const uint32_t want = local * (kBlock / kMxBlock) + (threadIdx.x >> 5);
     const bool in = want < j.units;
@@ -216,7 +176,7 @@ __device__ __forceinline__ MxLane strided_lane(const MxPackJob& j, uint32_t loca
 template <int BITS, bool BYTES>
 __device__ __forceinline__ void pack_strided(const MxPackJob& j, uint32_t local) {
     constexpr int NW = BITS;                                                     // dwords per block: 32 * BITS / 32
-    const MxCoder c = make_coder(j);
+    const MxCoder c = make_coder(j.format, j.fmt);
     const MxLane l = strided_lane(j, local);
     float v[kMxBlock];
     uint32_t m = 0;
@@ -274,7 +234,7 @@ __global__ __launch_bounds__(kBlock) void mx_pack_kernel(const MxPackArgs<CAP> a
 template <int U>
 __device__ __forceinline__ void unpack_rows4(const MxPackJob& j, uint32_t local) {
     constexpr uint32_t kGroups = kBlock / 8;
-    const MxCoder c = make_coder(j);
+    const MxCoder c = make_coder(j.format, j.fmt);
     const uint32_t q = threadIdx.x & 7u;
     uint32_t mine[U], scale[U];                                                  // a lane's four codes; its block's scale
     size_t at[U];
@@ -311,7 +271,7 @@ __device__ __forceinline__ void unpack_rows4(const MxPackJob& j, uint32_t local)
 }
 
 __device__ __forceinline__ void unpack_rows1(const MxPackJob& j, uint32_t local) {
-    const MxCoder c = make_coder(j);
+    const MxCoder c = make_coder(j.format, j.fmt);
     const uint32_t q = threadIdx.x & 31u;
     const uint32_t want = local * (kBlock / kMxBlock) + (threadIdx.x >> 5);
     const bool in = want < j.units;
@@ -330,7 +290,7 @@ __device__ __forceinline__ void unpack_rows1(const MxPackJob& j, uint32_t local)
 template <int BITS, bool BYTES>
 __device__ __forceinline__ void unpack_strided(const MxPackJob& j, uint32_t local) {
     constexpr int NW = BITS;
-    const MxCoder c = make_coder(j);
+    const MxCoder c = make_coder(j.format, j.fmt);
     const MxLane l = strided_lane(j, local);
     const uint8_t* src = j.e + (size_t)l.blk * (4u * NW);
     uint32_t w[NW];

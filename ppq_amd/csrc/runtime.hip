@@ -33,7 +33,8 @@ const char* const kKernelNames[K_NUM] = {
     "minmax_c", "mse_search", "kl_losses", "tensor_clip", "rounding_loss", "channel_sum", "float_scale_search", "lsq_finish",
     "adaround_fwd", "adaround_bwd", "fetch_rows", "measure_rows", "measure_finish", "roundtune_fwd", "equalize_scale",
     "equalize_apply", "ssd_scales", "ssd_apply", "fq_measure_rows", "stat_moments", "stat_shape",
-    "split_plan", "split_apply", "mx_fq", "mx_pack", "mx_unpack", "mx_gemm", "mx_conv"};
+    "split_plan", "split_apply", "mx_fq", "mx_pack", "mx_unpack", "mx_gemm", "mx_conv",
+    "mx_gemm_fused", "mx_conv_fused"};
 
 int num_cu() {
     static std::mutex mu;

@@ -956,6 +956,77 @@ def mx_packed_shapes(shape, axis: int, format):
     return lead + [nb * mx_block_bytes(format)], lead + [nb]
 
 
+def _mx_matmul_args(a_elements, a_scales, a_format, b_elements, b_scales, b_format, k, bias):
+    """The checks of ``CUDA.MXMatmul`` / ``MXMatmulFused``; returns the tensors as the kernel takes them, the format ids, k, M and N."""
+    fa, fb = mx_format_id(a_format), mx_format_id(b_format)
+    k = int(k)
+    if k <= 0: raise RuntimeError(_KERNEL_FAILURE + f'k must be positive, got {k}')
+    for name, t in (('A elements', a_elements), ('A scales', a_scales), ('B elements', b_elements), ('B scales', b_scales)):
+        _check(t, torch.uint8, name + '(Expect to be UINT8)')
+        if t.dim() != 2: raise RuntimeError(_KERNEL_FAILURE + f'{name} must be 2-d, got {list(t.shape)}')
+        if t.device != a_elements.device: raise RuntimeError(_KERNEL_FAILURE + f'{name} is on another device')
+    m, n = a_elements.shape[0], b_elements.shape[0]
+    for name, e, s, rows, fmt in (('A', a_elements, a_scales, m, fa), ('B', b_elements, b_scales, n, fb)):
+        eshape, sshape = mx_packed_shapes([rows, k], 1, fmt)
+        if list(e.shape) != eshape or list(s.shape) != sshape:
+            raise RuntimeError(_KERNEL_FAILURE + f'{name}: elements / scales of shape {list(e.shape)} / {list(s.shape)}, expected {eshape} / {sshape} for k = {k}')
+    if bias is not None:
+        _f32(bias, 'Bias')
+        if list(bias.shape) != [n]: raise RuntimeError(_KERNEL_FAILURE + f'bias of shape {list(bias.shape)}, expected [{n}]')
+        if bias.device != a_elements.device: raise RuntimeError(_KERNEL_FAILURE + 'bias is on another device')
+        bias = bias.contiguous()
+    a_elements, a_scales, b_elements, b_scales = a_elements.contiguous(), a_scales.contiguous(), b_elements.contiguous(), b_scales.contiguous()
+    if a_elements.data_ptr() % 16: a_elements = a_elements.clone()                   # the kernel's 16-byte loads; the allocator aligns
+    if b_elements.data_ptr() % 16: b_elements = b_elements.clone()
+    return a_elements, a_scales, fa, b_elements, b_scales, fb, k, bias, m, n
+
+
+def _mx_conv_args(x_elements, x_scales, x_format, w_elements, w_scales, w_format, c, bias, stride, padding, dilation):
+    """The checks of ``CUDA.MXConv2d`` / ``MXConv2dFused``; returns the tensors as the kernel takes them, the format ids and
+    ``geo = (n, c, h, w, o, kh, kw, sh, sw, ph, pw, dh, dw, oh, ow)``: the entry point's sizes, then the output's."""
+    fx, fw = mx_format_id(x_format), mx_format_id(w_format)
+    c = int(c)
+    if c <= 0: raise RuntimeError(_KERNEL_FAILURE + f'c must be positive, got {c}')
+    for name, t in (('x elements', x_elements), ('x scales', x_scales), ('w elements', w_elements), ('w scales', w_scales)):
+        _check(t, torch.uint8, name + '(Expect to be UINT8)')
+        if t.dim() != 4: raise RuntimeError(_KERNEL_FAILURE + f'{name} must be 4-d, got {list(t.shape)}')
+        if t.device != x_elements.device: raise RuntimeError(_KERNEL_FAILURE + f'{name} is on another device')
+    (n, h, w), (o, kh, kw) = x_scales.shape[:3], w_scales.shape[:3]
+    for name, e, s, shape, fmt in (('x', x_elements, x_scales, [n, c, h, w], fx), ('w', w_elements, w_scales, [o, c, kh, kw], fw)):
+        eshape, sshape = mx_packed_shapes(shape, 1, fmt)
+        if list(e.shape) != eshape or list(s.shape) != sshape:
+            raise RuntimeError(_KERNEL_FAILURE + f'{name}: elements / scales of shape {list(e.shape)} / {list(s.shape)}, expected {eshape} / {sshape} for c = {c}')
+    (sh, sw), (ph, pw), (dh, dw) = ([int(v) for v in pair] for pair in (stride, padding, dilation))
+    if min(sh, sw, dh, dw) < 1 or min(ph, pw) < 0:
+        raise RuntimeError(_KERNEL_FAILURE + f'stride {(sh, sw)} and dilation {(dh, dw)} must be at least 1, padding {(ph, pw)} at least 0')
+    oh, ow = (h + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (w + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    if oh < 1 or ow < 1:
+        raise RuntimeError(_KERNEL_FAILURE + f'a {kh} x {kw} kernel with dilation {(dh, dw)} does not fit an input of {h} x {w} padded by {(ph, pw)}')
+    if bias is not None:
+        _f32(bias, 'Bias')
+        if list(bias.shape) != [o]: raise RuntimeError(_KERNEL_FAILURE + f'bias of shape {list(bias.shape)}, expected [{o}]')
+        if bias.device != x_elements.device: raise RuntimeError(_KERNEL_FAILURE + 'bias is on another device')
+        bias = bias.contiguous()
+    x_elements, x_scales, w_elements, w_scales = x_elements.contiguous(), x_scales.contiguous(), w_elements.contiguous(), w_scales.contiguous()
+    if x_elements.data_ptr() % 16: x_elements = x_elements.clone()                   # the kernel's 16-byte loads; the allocator aligns
+    if w_elements.data_ptr() % 16: w_elements = w_elements.clone()
+    return x_elements, x_scales, fx, w_elements, w_scales, fw, bias, (n, c, h, w, o, kh, kw, sh, sw, ph, pw, dh, dw, oh, ow)
+
+
+def _mx_fused_args(out_format, out_float, residual, shape, device):
+    """The checks the fused bindings add: returns the id of ``out_format`` (a float format; without one nothing is packed and the id
+    is a placeholder) and the residual, float32 of ``shape`` on ``device``."""
+    fo = mx_format_id(out_format) if out_format is not None else MX_FORMATS['MXFP8_E4M3']
+    if fo == MX_FORMATS['MXINT8']: raise RuntimeError(_KERNEL_FAILURE + 'out_format MXINT8 is not a format the fused epilogue packs')
+    if out_format is None and not out_float: raise RuntimeError(_KERNEL_FAILURE + 'no output: out_format is None and out_float is False')
+    if residual is not None:
+        _f32(residual, 'Residual')
+        if list(residual.shape) != list(shape): raise RuntimeError(_KERNEL_FAILURE + f'residual of shape {list(residual.shape)}, expected {list(shape)}')
+        if residual.device != device: raise RuntimeError(_KERNEL_FAILURE + 'residual is on another device')
+        if len(shape) == 2: residual = residual.contiguous()
+    return fo, residual
+
+
 class MXPackPlan:
     """The sibling of ``MXQuantizePlan`` for the packed export: MANY tensors packed with ONE launch per call
     (``ppqhip_mx_pack_multi``).  Built once from ``(value, format, axis)`` items; ``run()`` packs all of them into one resident
@@ -2106,31 +2177,35 @@ class CUDA:
         are packed along their last axis as ``MXPack`` leaves them: ``elements [rows, nb * B]`` and ``scales [rows, nb]``, uint8,
         nb = ceil(k / 32).  The five float formats in any combination; MXINT8 is refused.  Non-contiguous inputs are copied, and so is an ``elements`` tensor whose
         data does not start on a 16-byte boundary (a row slice of a 6-bit operand with an odd nb: the row pitch is 24 nb)."""
-        fa, fb = mx_format_id(a_format), mx_format_id(b_format)
-        k = int(k)
-        if k <= 0: raise RuntimeError(_KERNEL_FAILURE + f'k must be positive, got {k}')
-        for name, t in (('A elements', a_elements), ('A scales', a_scales), ('B elements', b_elements), ('B scales', b_scales)):
-            _check(t, torch.uint8, name + '(Expect to be UINT8)')
-            if t.dim() != 2: raise RuntimeError(_KERNEL_FAILURE + f'{name} must be 2-d, got {list(t.shape)}')
-            if t.device != a_elements.device: raise RuntimeError(_KERNEL_FAILURE + f'{name} is on another device')
-        m, n = a_elements.shape[0], b_elements.shape[0]
-        for name, e, s, rows, fmt in (('A', a_elements, a_scales, m, fa), ('B', b_elements, b_scales, n, fb)):
-            eshape, sshape = mx_packed_shapes([rows, k], 1, fmt)
-            if list(e.shape) != eshape or list(s.shape) != sshape:
-                raise RuntimeError(_KERNEL_FAILURE + f'{name}: elements / scales of shape {list(e.shape)} / {list(s.shape)}, expected {eshape} / {sshape} for k = {k}')
-        if bias is not None:
-            _f32(bias, 'Bias')
-            if list(bias.shape) != [n]: raise RuntimeError(_KERNEL_FAILURE + f'bias of shape {list(bias.shape)}, expected [{n}]')
-            if bias.device != a_elements.device: raise RuntimeError(_KERNEL_FAILURE + 'bias is on another device')
-            bias = bias.contiguous()
-        a_elements, a_scales, b_elements, b_scales = a_elements.contiguous(), a_scales.contiguous(), b_elements.contiguous(), b_scales.contiguous()
-        if a_elements.data_ptr() % 16: a_elements = a_elements.clone()                   # the kernel's 16-byte loads; the allocator aligns
-        if b_elements.data_ptr() % 16: b_elements = b_elements.clone()
+        a_elements, a_scales, fa, b_elements, b_scales, fb, k, bias, m, n = _mx_matmul_args(a_elements, a_scales, a_format, b_elements, b_scales, b_format, k, bias)
         out = torch.empty([m, n], dtype=torch.float32, device=a_elements.device)
         with _DeviceOf(out):
             _raise(lib.ppqhip_mx_gemm(a_elements.data_ptr(), a_scales.data_ptr(), fa, b_elements.data_ptr(), b_scales.data_ptr(), fb,
                                       bias.data_ptr() if bias is not None else 0, out.data_ptr(), m, n, k, _stream()))
         return out
+
+    @ staticmethod
+    def MXMatmulFused(a_elements, a_scales, a_format, b_elements, b_scales, b_format, k: int, bias=None, residual=None, relu: bool = False,
+                      out_format=None, out_float: bool = True):
+        """``MXMatmul`` with the fused epilogue: ``v = A . B^T (+ bias) (+ residual[M, N])``, then the ReLU
+        (``v > 0 ? v : +0``, NaN kept), in ONE launch.  Returns ``(c, elements, scales)``: ``c`` the float32 ``[M, N]`` (None with
+        ``out_float=False``), ``elements [M, nbo * B]`` / ``scales [M, nbo]`` ``v`` packed along its last axis in ``out_format``
+        exactly as ``MXPack`` packs it (None, None without ``out_format``).  ``out_format``: one of the five float formats."""
+        a_elements, a_scales, fa, b_elements, b_scales, fb, k, bias, m, n = _mx_matmul_args(a_elements, a_scales, a_format, b_elements, b_scales, b_format, k, bias)
+        fo, residual = _mx_fused_args(out_format, out_float, residual, [m, n], a_elements.device)
+        dev = a_elements.device
+        out = torch.empty([m, n], dtype=torch.float32, device=dev) if out_float else None
+        elements = scales = None
+        if out_format is not None:
+            eshape, sshape = mx_packed_shapes([m, n], 1, fo)
+            elements, scales = torch.empty(eshape, dtype=torch.uint8, device=dev), torch.empty(sshape, dtype=torch.uint8, device=dev)
+        with _DeviceOf(a_elements):
+            _raise(lib.ppqhip_mx_gemm_fused(a_elements.data_ptr(), a_scales.data_ptr(), fa, b_elements.data_ptr(), b_scales.data_ptr(), fb,
+                                            bias.data_ptr() if bias is not None else 0, residual.data_ptr() if residual is not None else 0,
+                                            1 if relu else 0, out.data_ptr() if out is not None else 0,
+                                            elements.data_ptr() if elements is not None else 0, scales.data_ptr() if scales is not None else 0,
+                                            fo, m, n, k, _stream()))
+        return out, elements, scales
 
     @ staticmethod
     def MXConv2d(x_elements, x_scales, x_format, w_elements, w_scales, w_format, c: int, bias=None, stride=(1, 1), padding=(0, 0),
@@ -2141,38 +2216,39 @@ class CUDA:
         [O, kh, kw, nbc]``, uint8, nbc = ceil(c / 32).  The five float formats in any combination; MXINT8 is refused.  ``stride``,
         ``padding`` (symmetric) and ``dilation`` are (h, w) pairs.  Non-contiguous inputs are copied, and so is an ``elements`` tensor
         whose data does not start on a 16-byte boundary."""
-        fx, fw = mx_format_id(x_format), mx_format_id(w_format)
-        c = int(c)
-        if c <= 0: raise RuntimeError(_KERNEL_FAILURE + f'c must be positive, got {c}')
-        for name, t in (('x elements', x_elements), ('x scales', x_scales), ('w elements', w_elements), ('w scales', w_scales)):
-            _check(t, torch.uint8, name + '(Expect to be UINT8)')
-            if t.dim() != 4: raise RuntimeError(_KERNEL_FAILURE + f'{name} must be 4-d, got {list(t.shape)}')
-            if t.device != x_elements.device: raise RuntimeError(_KERNEL_FAILURE + f'{name} is on another device')
-        (n, h, w), (o, kh, kw) = x_scales.shape[:3], w_scales.shape[:3]
-        for name, e, s, shape, fmt in (('x', x_elements, x_scales, [n, c, h, w], fx), ('w', w_elements, w_scales, [o, c, kh, kw], fw)):
-            eshape, sshape = mx_packed_shapes(shape, 1, fmt)
-            if list(e.shape) != eshape or list(s.shape) != sshape:
-                raise RuntimeError(_KERNEL_FAILURE + f'{name}: elements / scales of shape {list(e.shape)} / {list(s.shape)}, expected {eshape} / {sshape} for c = {c}')
-        (sh, sw), (ph, pw), (dh, dw) = ([int(v) for v in pair] for pair in (stride, padding, dilation))
-        if min(sh, sw, dh, dw) < 1 or min(ph, pw) < 0:
-            raise RuntimeError(_KERNEL_FAILURE + f'stride {(sh, sw)} and dilation {(dh, dw)} must be at least 1, padding {(ph, pw)} at least 0')
-        oh, ow = (h + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (w + 2 * pw - dw * (kw - 1) - 1) // sw + 1
-        if oh < 1 or ow < 1:
-            raise RuntimeError(_KERNEL_FAILURE + f'a {kh} x {kw} kernel with dilation {(dh, dw)} does not fit an input of {h} x {w} padded by {(ph, pw)}')
-        if bias is not None:
-            _f32(bias, 'Bias')
-            if list(bias.shape) != [o]: raise RuntimeError(_KERNEL_FAILURE + f'bias of shape {list(bias.shape)}, expected [{o}]')
-            if bias.device != x_elements.device: raise RuntimeError(_KERNEL_FAILURE + 'bias is on another device')
-            bias = bias.contiguous()
-        x_elements, x_scales, w_elements, w_scales = x_elements.contiguous(), x_scales.contiguous(), w_elements.contiguous(), w_scales.contiguous()
-        if x_elements.data_ptr() % 16: x_elements = x_elements.clone()                   # the kernel's 16-byte loads; the allocator aligns
-        if w_elements.data_ptr() % 16: w_elements = w_elements.clone()
-        out = torch.empty([n, oh, ow, o], dtype=torch.float32, device=x_elements.device)
+        x_elements, x_scales, fx, w_elements, w_scales, fw, bias, geo = _mx_conv_args(x_elements, x_scales, x_format, w_elements, w_scales, w_format, c, bias, stride, padding, dilation)
+        n, _, _, _, o, _, _ = geo[:7]
+        out = torch.empty([n, geo[-2], geo[-1], o], dtype=torch.float32, device=x_elements.device)
         with _DeviceOf(out):
             _raise(lib.ppqhip_mx_conv2d(x_elements.data_ptr(), x_scales.data_ptr(), fx, w_elements.data_ptr(), w_scales.data_ptr(), fw,
-                                        bias.data_ptr() if bias is not None else 0, out.data_ptr(), n, c, h, w, o, kh, kw, sh, sw, ph, pw,
-                                        dh, dw, _stream()))
+                                        bias.data_ptr() if bias is not None else 0, out.data_ptr(), *geo[:13], _stream()))
         return out.permute(0, 3, 1, 2)
+
+    @ staticmethod
+    def MXConv2dFused(x_elements, x_scales, x_format, w_elements, w_scales, w_format, c: int, bias=None, stride=(1, 1), padding=(0, 0),
+                      dilation=(1, 1), residual=None, relu: bool = False, out_format=None, out_float: bool = True):
+        """``MXConv2d`` with the fused epilogue: ``v = conv2d(x, w) (+ bias) (+ residual)``, then the ReLU
+        (``v > 0 ? v : +0``, NaN kept), in ONE launch.  ``residual`` is ``[N, O, OH, OW]``; a tensor that is not channels-last is
+        copied into that layout.  Returns ``(y, elements, scales)``: ``y`` the float32 ``[N, O, OH, OW]`` with channels-last strides
+        (None with ``out_float=False``), ``elements [N, OH, OW, nbo * B]`` / ``scales [N, OH, OW, nbo]`` ``v`` packed along axis 1 in
+        ``out_format`` exactly as ``MXPack`` packs it -- the x of the next ``MXConv2d`` -- (None, None without ``out_format``)."""
+        x_elements, x_scales, fx, w_elements, w_scales, fw, bias, geo = _mx_conv_args(x_elements, x_scales, x_format, w_elements, w_scales, w_format, c, bias, stride, padding, dilation)
+        n, o, oh, ow = geo[0], geo[4], geo[-2], geo[-1]
+        dev = x_elements.device
+        fo, residual = _mx_fused_args(out_format, out_float, residual, [n, o, oh, ow], dev)
+        if residual is not None: residual = residual.permute(0, 2, 3, 1).contiguous()               # no copy when it is channels-last
+        out = torch.empty([n, oh, ow, o], dtype=torch.float32, device=dev) if out_float else None
+        elements = scales = None
+        if out_format is not None:
+            eshape, sshape = mx_packed_shapes([n, o, oh, ow], 1, fo)
+            elements, scales = torch.empty(eshape, dtype=torch.uint8, device=dev), torch.empty(sshape, dtype=torch.uint8, device=dev)
+        with _DeviceOf(x_elements):
+            _raise(lib.ppqhip_mx_conv2d_fused(x_elements.data_ptr(), x_scales.data_ptr(), fx, w_elements.data_ptr(), w_scales.data_ptr(), fw,
+                                              bias.data_ptr() if bias is not None else 0, residual.data_ptr() if residual is not None else 0,
+                                              1 if relu else 0, out.data_ptr() if out is not None else 0,
+                                              elements.data_ptr() if elements is not None else 0, scales.data_ptr() if scales is not None else 0,
+                                              fo, *geo[:13], _stream()))
+        return (out.permute(0, 3, 1, 2) if out is not None else None), elements, scales
 
     @ staticmethod
     def Sync():

@@ -293,6 +293,8 @@ class TorchExecutor:
         self._fused: Dict[tuple, torch.Tensor] = {}
         self._delegates: Dict[object, Callable] = {}
         self._overrides: Dict[str, Callable] = {}     # operation name -> fn(op, raw inputs): register_operation_override
+        self._takes_packed: set = set()               # ... whose fn takes input 0 in the packed form a group override handed over
+        self._group_overrides: Dict[str, tuple] = {}  # first member's name -> (member names, fn): register_group_override
         self.fuse_epilogues = True                    # conv bias [+ residual Add] + Relu in ONE launch: plan_epilogues
         self._epilogue_cache: Dict[tuple, dict] = {}
         self.channels_last = False                    # see use_channels_last()
@@ -323,17 +325,95 @@ class TorchExecutor:
     def remove_quantize_delegate(self, config) -> None:
         self._delegates.pop(config, None)
 
-    def register_operation_override(self, op_name: str, fn: Callable) -> None:
+    def register_operation_override(self, op_name: str, fn: Callable, takes_packed: bool = False) -> None:
         """Run operation ``op_name`` as ``fn(op, raw_inputs)`` -- a tensor or a list of tensors, one per output -- in place of the
         quantisation of its inputs and its torch forward (a deployed kernel that does both: ``mx.deploy_graph_mx``).  The output
         configs are applied as usual.  A forward that hooks the operation runs the simulated path for it, so calibration and the
-        analysis passes see what they see without the override; an overridden operation joins no epilogue group."""
+        analysis passes see what they see without the override; an overridden operation joins no epilogue group.
+        ``takes_packed``: ``fn`` also accepts, as ``raw_inputs[0]``, the packed form of that input where a group override
+        (``register_group_override``) produced one; it is then never asked to quantise it again."""
         if op_name not in self._graph.operations: raise KeyError(f'register_operation_override: the graph has no operation {op_name!r}')
         if not callable(fn): raise TypeError(f'register_operation_override: fn must be callable, got {type(fn)}')
         self._overrides[op_name] = fn
+        if takes_packed: self._takes_packed.add(op_name)
+        else: self._takes_packed.discard(op_name)
 
     def remove_operation_override(self, op_name: str) -> None:
         self._overrides.pop(op_name, None)
+        self._takes_packed.discard(op_name)
+
+    def register_group_override(self, op_names: List[str], fn: Callable) -> None:
+        """Run the operations ``op_names`` -- a chain in execution order: every member's output feeds only the next member --
+        as ONE call ``fn(ops, inputs, need_float) -> (values, packed)`` at the position of the first (a deployed kernel with a
+        fused tail: ``mx.deploy_graph_mx(fuse=True)``).  ``inputs[k]`` are the raw inputs of member k (None where the input is
+        another member's output); input 0 of the first member arrives packed when a group handed it over packed and the member's
+        own override ``takes_packed``.  ``values``: variable name -> float tensor; ``packed``: variable name -> packed form.  Every
+        member's output must be in one of them, and every name in ``need_float`` in ``values``: the last output's name is in
+        ``need_float`` whenever anything but an override that ``takes_packed`` reads it in this forward -- a graph output, a
+        requested output, a consumer without such an override or with a hook.  The other outputs may alias the last one, as
+        the unwritten tensors of an epilogue group do.  No output config of a member is applied: the caller registers only
+        groups whose configs pass through.
+        A forward in which a member is hooked, an output other than the last is a graph output or requested, or a member is
+        missing from the operations that run, does not use the group: its operations run one by one, through their own
+        overrides or the simulated path.  ``forward_cached`` and ``partial_graph_forward`` ask for every group's last output as
+        float (a group may still hand its packed form to the next group's first member within the call); ``forward_cached`` caches
+        only that last output, so a later request for another member's output recomputes it."""
+        if not op_names: raise ValueError('register_group_override: no operations')
+        for name in op_names:
+            if name not in self._graph.operations: raise KeyError(f'register_group_override: the graph has no operation {name!r}')
+        if not callable(fn): raise TypeError(f'register_group_override: fn must be callable, got {type(fn)}')
+        self._group_overrides[op_names[0]] = (tuple(op_names), fn)
+
+    def remove_group_override(self, first_name: str) -> None:
+        self._group_overrides.pop(first_name, None)
+
+    def _group_plan(self, operations: List[Operation], hooks, output_names, all_float: bool) -> Dict[str, tuple]:
+        """First member's name -> (member ops, fn, need_float) for the group overrides this forward uses."""
+        if not self._group_overrides: return {}
+        hooks = hooks or {}
+        keep = set(self._graph.outputs) | set(output_names or ())
+        at = {op.name: i for i, op in enumerate(operations)}
+        plan = {}
+        for first, (names, fn) in self._group_overrides.items():
+            if any(n not in at or n in hooks for n in names): continue
+            if any(at[a] >= at[b] for a, b in zip(names, names[1:])): continue
+            ops = [operations[at[n]] for n in names]
+            if any(v.name in keep for m in ops[:-1] for v in m.outputs): continue
+            need = set()
+            for v in ops[-1].outputs:
+                handed = [d.name in self._takes_packed and d.name in self._overrides and d.name not in hooks and d.name in at
+                          and d.inputs[0] is v and sum(1 for x in d.inputs if x is v) == 1 for d in v.dest_ops]
+                if all_float or v.name in keep or not handed or not all(handed): need.add(v.name)
+            plan[first] = (ops, fn, need)
+        return plan
+
+    def _run_group(self, entry: tuple, raw_of: Callable, packed: Dict[str, object]) -> Dict[str, object]:
+        """Run one group override; returns variable name -> value for every member's output.  A tensor that left the launch
+        packed only is represented by its packed form, which no code that expects a float tensor can mistake for one."""
+        ops, fn, need = entry
+        inside = {v.name for m in ops for v in m.outputs}
+        inputs = [[None if v.name in inside else raw_of(v) for v in m.inputs] for m in ops]
+        head = ops[0]
+        if head.name in self._takes_packed and head.inputs[0].name in packed: inputs[0][0] = packed[head.inputs[0].name]
+        if any(x is None for k, m in enumerate(ops) for x, v in zip(inputs[k], m.inputs) if v.name not in inside):
+            raise ValueError(f'group override of {head.name}: an input was not computed')
+        values, handed = fn(ops, inputs, need)
+        out = {}
+        for m in ops:
+            for v in m.outputs:
+                if v.name in values: out[v.name] = values[v.name]
+                elif v.name in handed and v.name not in need: out[v.name] = handed[v.name]
+                else: raise RuntimeError(f'group override of {head.name}: no {"float " if v.name in need else ""}value for {v.name}')
+        packed.update(handed)
+        return out
+
+    def _override_inputs(self, op: Operation, raw_in: list, packed: Dict[str, object]) -> list:
+        """The raw inputs an operation override gets: input 0 in its packed form where a group handed one over and the override
+        takes it."""
+        if packed and op.name in self._takes_packed and op.inputs[0].name in packed:
+            raw_in = list(raw_in)
+            raw_in[0] = packed[op.inputs[0].name]
+        return raw_in
 
     def quantize_function(self, tensor: torch.Tensor, config=None) -> torch.Tensor:
         if self._delegates and config in self._delegates:          # torch.py:610-613
@@ -358,9 +438,18 @@ class TorchExecutor:
         for name, value in feed_dict.items(): g.variables[name].value = self._place(value)
         results = [None] * len(output_names)
         self._fused_parameters(operations)            # the multi-tensor plan covers the parameters of THESE operations only
-        plan, fused_done = self._epilogue_plan(operations, None, output_names), set()
+        groups, packed = self._group_plan(operations, None, output_names, True), {}
+        plan, fused_done = self._epilogue_plan(operations, None, output_names, [m.name for e in groups.values() for m in e[0]]), set()
         for op in operations:
             if op.name in fused_done: continue
+            if op.name in groups:
+                vals = self._run_group(groups[op.name], lambda v: v.value, packed)
+                for m in groups[op.name][0]:
+                    fused_done.add(m.name)
+                    for v in m.outputs:
+                        v.value = vals[v.name]
+                        if v.name in output_names: results[output_names.index(v.name)] = v.value
+                continue
             grp = plan.get(op.name)
             vals = self._run_epilogue(grp, lambda v: v.value, None) if grp is not None else None
             if vals is not None:
@@ -443,14 +532,14 @@ class TorchExecutor:
         for plan, keys in self._plans:
             for key, out in zip(keys, plan.run()): self._fused[key] = out
 
-    def _epilogue_plan(self, operations: List[Operation], hooks, output_names) -> Dict[str, EpilogueGroup]:
+    def _epilogue_plan(self, operations: List[Operation], hooks, output_names, grouped=()) -> Dict[str, EpilogueGroup]:
         """First member name -> group, for a forward over `operations` (plan_epilogues), cached per (operations, hooks,
         requested outputs, delegates, config states) signature like the parameter plans."""
         if not self.fuse_epilogues or torch.is_grad_enabled() or self._default_quant_fn is not PPQuantFunction: return {}
         states = tuple(c.state for op in operations if isinstance(op, QuantableOperation)
                        for c in (*op.config.input_quantization_config, *op.config.output_quantization_config))
         sig = (tuple(op.name for op in operations), tuple((k, id(h)) for k, h in hooks.items()) if hooks else (),
-               tuple(output_names or ()), tuple(id(c) for c in self._delegates), states, tuple(sorted(self._overrides)))
+               tuple(output_names or ()), tuple(id(c) for c in self._delegates), states, tuple(sorted(self._overrides)), tuple(sorted(grouped)))
         plan = self._epilogue_cache.get(sig)
         if plan is None:
             delegates = self._delegates
@@ -459,6 +548,8 @@ class TorchExecutor:
             groups = plan_epilogues(operations, hooks, set(self._graph.outputs) | set(output_names or ()), passes_through)
             if self._overrides:                       # an operation that runs its override is a member of no group
                 groups = [g for g in groups if not any(m.name in self._overrides and not (hooks and m.name in hooks) for m in g.ops)]
+            if grouped:                               # nor is a member of a group override that this forward uses
+                groups = [g for g in groups if not any(m.name in grouped for m in g.ops)]
             plan = {g.ops[0].name: g for g in groups}
             if len(self._epilogue_cache) >= 8: self._epilogue_cache.pop(next(iter(self._epilogue_cache)))
             self._epilogue_cache[sig] = plan
@@ -612,9 +703,17 @@ class TorchExecutor:
             stack.extend(op.inputs)
         ops = [op for op in g.topological_sort() if op.name in need]
         if ops: self._fused_parameters(ops)
-        plan, fused_done = (self._epilogue_plan(ops, None, output_names) if ops else {}), set()
+        groups, packed = self._group_plan(ops, None, output_names, True), {}
+        plan, fused_done = (self._epilogue_plan(ops, None, output_names, [m.name for e in groups.values() for m in e[0]]) if ops else {}), set()
         for op in ops:
             if op.name in fused_done: continue
+            if op.name in groups:
+                vals = self._run_group(groups[op.name], lambda v: v.value if v.is_parameter else cache[v.name], packed)
+                members = groups[op.name][0]
+                for m in members: fused_done.add(m.name)
+                # only the last output is cached: the others alias it and were never materialised; a later request recomputes them
+                for v in members[-1].outputs: cache[v.name] = vals[v.name]
+                continue
             grp = plan.get(op.name)
             vals = (self._run_epilogue(grp, lambda v: v.value if v.is_parameter else cache[v.name], None)
                     if grp is not None else None)
@@ -654,7 +753,8 @@ class TorchExecutor:
         visited = set()
         self._fused_parameters()
         ops = g.topological_sort()
-        plan, fused_done = self._epilogue_plan(ops, hooks, output_names), set()
+        groups, packed = self._group_plan(ops, hooks, output_names, False), {}
+        plan, fused_done = self._epilogue_plan(ops, hooks, output_names, [m.name for e in groups.values() for m in e[0]]), set()
 
         def finish(op, outs):
             for v, y in zip(op.outputs, outs):
@@ -666,6 +766,13 @@ class TorchExecutor:
 
         for op in ops:
             if op.name in fused_done: continue
+            if op.name in groups:
+                vals = self._run_group(groups[op.name], lambda v: v.value, packed)
+                for m in groups[op.name][0]:
+                    fused_done.add(m.name)
+                    finish(m, [vals[v.name] for v in m.outputs])
+                if stop_early and all(r is not None for r in results): break
+                continue
             grp = plan.get(op.name)
             vals = self._run_epilogue(grp, lambda v: v.value, hooks) if grp is not None else None
             if vals is not None:
@@ -679,7 +786,7 @@ class TorchExecutor:
             qin = raw_in
             quantable = isinstance(op, QuantableOperation)
             override = self._overrides.get(op.name) if hook is None else None        # a hooked operation runs the simulation
-            if override is not None: outs = override(op, raw_in)
+            if override is not None: outs = override(op, self._override_inputs(op, raw_in, packed))
             else:
                 if quantable:
                     in_cfgs = list(op.config.input_quantization_config)

@@ -325,6 +325,44 @@ def mx_dequantize(mxt: MXTensor, use_kernels: bool = True) -> torch.Tensor:
     return mxt.dequantize(use_kernels)
 
 
+# ---- the fused epilogue of the GEMM and the convolution ------------------------------------------------------
+def relu_positive_zero(v: torch.Tensor) -> torch.Tensor:
+    """The ReLU of the fused epilogue in torch ops: ``v > 0 ? v : +0`` with a NaN staying the NaN it is.  Unlike ``F.relu`` it never
+    returns -0: the sign of a zero is a bit of the packed code."""
+    return torch.where(v > 0, v, torch.where(v != v, v, torch.zeros_like(v)))
+
+
+def _check_fused(what: str, like, shape, residual, relu, out_format, out_float):
+    """The checks of the keywords ``residual`` / ``relu`` / ``out_format`` / ``out_float``; ``like`` is an operand (for the device),
+    ``shape`` the result's.  Returns (fused, out_format as a member or None, out_float as a bool)."""
+    fused = residual is not None or bool(relu) or out_format is not None or out_float is not None
+    if not fused: return False, None, True
+    if out_format is not None:
+        out_format = MXFormat.of(out_format)
+        if not out_format.is_float: raise RuntimeError(f'{what}: out_format {out_format.name} is not a format the fused epilogue packs')
+    if out_float is None: out_float = out_format is None
+    if out_format is None and not out_float: raise RuntimeError(f'{what}: no output: out_format is None and out_float is False')
+    if residual is not None:
+        if not isinstance(residual, torch.Tensor) or residual.dtype != torch.float32: raise RuntimeError(f'{what}: residual must be a float32 tensor')
+        if list(residual.shape) != list(shape): raise RuntimeError(f'{what}: residual of shape {list(residual.shape)}, expected {list(shape)}')
+        if residual.device != like.device: raise RuntimeError(f'{what}: residual is on {residual.device}, the operands on {like.device}')
+    return True, out_format, bool(out_float)
+
+
+def _fused_torch(y: torch.Tensor, residual, relu, out_format, out_float, axis: int):
+    """The torch arm of the fused epilogue on the float32 result ``y`` of the reference: the same order of operations."""
+    if residual is not None: y = y + residual
+    if relu: y = relu_positive_zero(y)
+    if out_format is None: return y
+    packed = mx_quantize(y, out_format, axis, use_kernels=False)
+    return (y, packed) if out_float else packed
+
+
+def _fused_result(y, packed, out_float):
+    if packed is None: return y
+    return (y, packed) if out_float else packed
+
+
 # ---- GEMM on the packed tensors (DESIGN.md section 9.14) ---------------------------------------------------------------------------
 def _check_matmul(a, b, bias):
     """The argument checks of ``mx_matmul``; returns (lead shape of a, N, K)."""
@@ -343,28 +381,42 @@ def _check_matmul(a, b, bias):
     return list(a.shape[:-1]), n, a.shape[-1]
 
 
-def mx_matmul(a: MXTensor, b: MXTensor, bias: torch.Tensor = None, use_kernels: bool = True) -> torch.Tensor:
+def mx_matmul(a: MXTensor, b: MXTensor, bias: torch.Tensor = None, use_kernels: bool = True, residual: torch.Tensor = None,
+              relu: bool = False, out_format=None, out_float: bool = None):
     """``a . b^T (+ bias)`` in float32: ``a`` is ``lead + [K]``, ``b`` is ``[N, K]`` (a Gemm weight [out, in], as ``export_graph_mx``
     leaves it), both packed along their last axis in any of the five float formats; the result is ``lead + [N]``.
     ``use_kernels=True``: the packed bytes go to the block-scaled MFMA as they are (``CUDA.MXMatmul``; the tensors must be on the
     GPU).  ``False``: the readable reference on any device -- ``mx_dequantize`` of both, the product in float64, rounded to float32.
     The two are NOT bit-identical: the kernel accumulates in float32 in the hardware's order (DESIGN.md section 9.14 bounds the
-    difference by K 2^-23 sum |a_k| |b_k|); they agree exactly on an output of one non-zero term, subnormal results included."""
+    difference by K 2^-23 sum |a_k| |b_k|); they agree exactly on an output of one non-zero term, subnormal results included.
+    The fused epilogue, all in the ONE launch: ``residual`` (float32, the result's shape) is added after the
+    bias; ``relu`` is ``v > 0 ? v : +0`` with NaN kept; ``out_format`` (a float MX format) returns the result as an ``MXTensor`` packed
+    along its last axis -- the bytes of ``mx_quantize`` of the float result --, ``out_format`` with ``out_float=True`` returns
+    ``(tensor, MXTensor)``; ``relu`` / ``residual`` alone return the float tensor.  With the defaults this is the plain kernel."""
     lead, n, k = _check_matmul(a, b, bias)
+    fused, out_format, out_float = _check_fused('mx_matmul', a, lead + [n], residual, relu, out_format, out_float)
     if use_kernels:
         e = a.elements.reshape(-1, a.elements.shape[-1])
         s = a.scales.reshape(-1, a.scales.shape[-1])
-        return CUDA.MXMatmul(e, s, a.format, b.elements, b.scales, b.format, k, bias).reshape(lead + [n])
+        if not fused: return CUDA.MXMatmul(e, s, a.format, b.elements, b.scales, b.format, k, bias).reshape(lead + [n])
+        y, oe, os_ = CUDA.MXMatmulFused(e, s, a.format, b.elements, b.scales, b.format, k, bias, residual.reshape(-1, n) if residual is not None else None,
+                                        relu, out_format, out_float)
+        if y is not None: y = y.reshape(lead + [n])
+        packed = MXTensor(out_format, lead + [n], len(lead), oe.reshape(lead + [oe.shape[-1]]), os_.reshape(lead + [os_.shape[-1]])) if oe is not None else None
+        return _fused_result(y, packed, out_float)
     x, w = a.dequantize(use_kernels=False).to(torch.float64), b.dequantize(use_kernels=False).to(torch.float64)
     y = x.reshape(-1, k) @ w.t()
     if bias is not None: y = y + bias.to(torch.float64)
-    return y.to(torch.float32).reshape(lead + [n])
+    y = y.to(torch.float32).reshape(lead + [n])
+    return _fused_torch(y, residual, relu, out_format, out_float, -1) if fused else y
 
 
-def mx_linear(x: torch.Tensor, weight: MXTensor, activation_format, bias: torch.Tensor = None, use_kernels: bool = True) -> torch.Tensor:
+def mx_linear(x: torch.Tensor, weight: MXTensor, activation_format, bias: torch.Tensor = None, use_kernels: bool = True,
+              residual: torch.Tensor = None, relu: bool = False, out_format=None, out_float: bool = None):
     """A linear layer on an MX weight as it runs in deployment: ``mx_quantize(x, activation_format, -1)``, then ``mx_matmul`` with
-    ``weight`` ``[N, K]`` -- two launches, the bias added in the GEMM's epilogue (one float32 add per output)."""
-    return mx_matmul(mx_quantize(x, activation_format, -1, use_kernels=use_kernels), weight, bias, use_kernels)
+    ``weight`` ``[N, K]`` -- two launches, the bias added in the GEMM's epilogue (one float32 add per output).  ``residual``, ``relu``,
+    ``out_format`` and ``out_float`` are ``mx_matmul``'s."""
+    return mx_matmul(mx_quantize(x, activation_format, -1, use_kernels=use_kernels), weight, bias, use_kernels, residual, relu, out_format, out_float)
 
 
 # ---- convolution on the packed tensors (DESIGN.md section 9.15) --------------------------------------------------------------------
@@ -399,7 +451,8 @@ def _check_conv(x, w, bias, stride, padding, dilation):
     return stride, padding, dilation, out
 
 
-def mx_conv2d_packed(x: MXTensor, w: MXTensor, bias: torch.Tensor = None, stride=1, padding=0, dilation=1, use_kernels: bool = True) -> torch.Tensor:
+def mx_conv2d_packed(x: MXTensor, w: MXTensor, bias: torch.Tensor = None, stride=1, padding=0, dilation=1, use_kernels: bool = True,
+                     residual: torch.Tensor = None, relu: bool = False, out_format=None, out_float: bool = None):
     """``conv2d(x, w) (+ bias)`` in float32: ``x`` is ``[N, C, H, W]``, ``w`` is ``[O, C, kh, kw]`` (a Conv weight as
     ``export_graph_mx`` leaves it), both packed along axis 1 in any of the five float formats; ``stride``, ``padding`` (symmetric, as
     ``F.conv2d`` takes it) and ``dilation`` are ints or (h, w) pairs, groups is 1.  The result is ``[N, O, OH, OW]``.
@@ -407,10 +460,21 @@ def mx_conv2d_packed(x: MXTensor, w: MXTensor, bias: torch.Tensor = None, stride
     (``CUDA.MXConv2d``; the tensors must be on the GPU); the result has channels-last strides.  ``False``: the readable reference
     on any device -- ``mx_dequantize`` of both, the windows gathered by slicing, the product in float64, rounded to float32.
     As for ``mx_matmul`` the two are not bit-identical (DESIGN.md section 9.15: K 2^-23 sum |x| |w| with K = kh kw 32 ceil(C / 32));
-    the kernel has the bits of ``mx_matmul`` on the gathered rows."""
+    the kernel has the bits of ``mx_matmul`` on the gathered rows.
+    The fused epilogue, all in the ONE launch: ``residual`` (float32 ``[N, O, OH, OW]``; channels-last is
+    read in place, anything else is copied) is added after the bias; ``relu`` is ``v > 0 ? v : +0`` with NaN kept; ``out_format`` (a
+    float MX format) returns the result as an ``MXTensor`` ``[N, O, OH, OW]`` packed along axis 1 -- the bytes of ``mx_quantize`` of
+    the float result, and what this function takes as ``x`` --, ``out_format`` with ``out_float=True`` returns ``(tensor, MXTensor)``;
+    ``relu`` / ``residual`` alone return the float tensor.  With the defaults this is the plain kernel."""
     (sh, sw), (ph, pw), (dh, dw), (oh, ow) = _check_conv(x, w, bias, stride, padding, dilation)
+    shape = [x.shape[0], w.shape[0], oh, ow]
+    fused, out_format, out_float = _check_fused('mx_conv2d', x, shape, residual, relu, out_format, out_float)
     if use_kernels:
-        return CUDA.MXConv2d(x.elements, x.scales, x.format, w.elements, w.scales, w.format, x.shape[1], bias, (sh, sw), (ph, pw), (dh, dw))
+        if not fused:
+            return CUDA.MXConv2d(x.elements, x.scales, x.format, w.elements, w.scales, w.format, x.shape[1], bias, (sh, sw), (ph, pw), (dh, dw))
+        y, oe, os_ = CUDA.MXConv2dFused(x.elements, x.scales, x.format, w.elements, w.scales, w.format, x.shape[1], bias, (sh, sw), (ph, pw), (dh, dw),
+                                        residual, relu, out_format, out_float)
+        return _fused_result(y, MXTensor(out_format, shape, 1, oe, os_) if oe is not None else None, out_float)
     n, c, _, _ = x.shape
     o, _, kh, kw = w.shape
     xf = torch.nn.functional.pad(x.dequantize(use_kernels=False).to(torch.float64), (pw, pw, ph, ph))
@@ -419,17 +483,20 @@ def mx_conv2d_packed(x: MXTensor, w: MXTensor, bias: torch.Tensor = None, stride
     cols = torch.stack(taps, dim=1).permute(0, 3, 4, 1, 2).reshape(n * oh * ow, kh * kw * c)          # rows (n, oy, ox), K (ky, kx, c)
     y = cols @ wf.permute(0, 2, 3, 1).reshape(o, kh * kw * c).t()
     if bias is not None: y = y + bias.to(torch.float64)
-    return y.to(torch.float32).reshape(n, oh, ow, o).permute(0, 3, 1, 2)
+    y = y.to(torch.float32).reshape(n, oh, ow, o).permute(0, 3, 1, 2)
+    return _fused_torch(y, residual, relu, out_format, out_float, 1) if fused else y
 
 
 def mx_conv2d(x: torch.Tensor, weight: MXTensor, activation_format, bias: torch.Tensor = None, stride=1, padding=0, dilation=1,
-              groups: int = 1, use_kernels: bool = True) -> torch.Tensor:
+              groups: int = 1, use_kernels: bool = True, residual: torch.Tensor = None, relu: bool = False, out_format=None,
+              out_float: bool = None):
     """A convolution on an MX weight as it runs in deployment: ``mx_quantize(x, activation_format, 1)`` -- ``x`` ``[N, C, H, W]``,
     contiguous or channels-last --, then ``mx_conv2d_packed`` with ``weight`` ``[O, C, kh, kw]``: two launches, the bias added in the
-    kernel's epilogue (one float32 add per output)."""
+    kernel's epilogue (one float32 add per output).  ``residual``, ``relu``, ``out_format`` and ``out_float`` are ``mx_conv2d_packed``'s."""
     if groups != 1: raise RuntimeError(f'mx_conv2d: groups must be 1, got {groups}')
     if isinstance(x, torch.Tensor) and x.dim() != 4: raise RuntimeError(f'mx_conv2d: x must be 4-d [N, C, H, W], got shape {list(x.shape)}')
-    return mx_conv2d_packed(mx_quantize(x, activation_format, 1, use_kernels=use_kernels), weight, bias, stride, padding, dilation, use_kernels)
+    return mx_conv2d_packed(mx_quantize(x, activation_format, 1, use_kernels=use_kernels), weight, bias, stride, padding, dilation, use_kernels,
+                            residual, relu, out_format, out_float)
 
 
 def _activated(config) -> bool:
@@ -585,18 +652,45 @@ def export_graph_mx(graph, delegators=None, use_kernels: bool = True) -> Dict[st
     return {n: MXTensor(fmt, v.shape, axis, e, s) for n, (v, fmt, axis), (e, s) in zip(names, items, packed)}
 
 
-# ---- the graph on the hardware path -----------------------------------------------------------------------
+# ---- the graph on the hardware path (DESIGN.md sections 9.15, 9.16) ------------------------------------------------------------------
+class MXFusedGroup:
+    """One fused launch of ``deploy_graph_mx(fuse=True)``: ``members`` -- the deployed operation, then the Add and / or Relu of its
+    tail --, ``residual`` -- the name of the Add's other operand --, ``relu``, ``output`` -- the name of the last tensor --,
+    ``out_format`` -- the format it leaves the launch packed in, or None -- and ``notes``: why an Add was not fused or the output
+    is float only."""
+    def __init__(self, members):
+        self.members: List[str] = list(members)
+        self.residual: Optional[str] = None
+        self.relu = False
+        self.output: Optional[str] = None
+        self.out_format: Optional[MXFormat] = None
+        self.notes: List[str] = []
+
+    def __repr__(self) -> str:
+        tail = (f' + {self.residual}' if self.residual else '') + (' relu' if self.relu else '')
+        return f'MXFusedGroup({" -> ".join(self.members)}{tail}; {self.out_format.name if self.out_format else "float"}{"; " + "; ".join(self.notes) if self.notes else ""})'
+
+
+def _handed(op, x: MXTensor, format: MXFormat, axis: int) -> MXTensor:
+    """The activation a fused producer handed over packed, checked against what this operation would have quantised itself."""
+    if x.format is not format or x.axis != axis:
+        raise RuntimeError(f'{op.name}: its activation arrived packed as {x.format.name} along axis {x.axis}, expected {format.name} along axis {axis}')
+    return x
+
+
 class MXDeployment:
     """What ``deploy_graph_mx`` did: ``deployed`` -- the names of the operations that run on the block-scaled MFMA --, ``skipped`` --
     name -> reason for every MX operation that stays on the simulated path --, ``weights`` -- the packed weights
     (``export_graph_mx``).  ``refresh()`` packs the weights again after they changed; ``remove()`` drops the overrides, after which
     the executor runs the simulation again."""
-    def __init__(self, graph, executor, delegators=None, use_kernels: bool = True):
-        self.graph, self.executor, self.delegators, self.use_kernels = graph, executor, delegators, use_kernels
+    def __init__(self, graph, executor, delegators=None, use_kernels: bool = True, fuse: bool = False):
+        self.graph, self.executor, self.delegators, self.use_kernels, self.fuse = graph, executor, delegators, use_kernels, fuse
         self.deployed: List[str] = []
         self.skipped: Dict[str, str] = {}
+        self.groups: Dict[str, MXFusedGroup] = {}     # fuse=True: first operation's name -> what its one launch covers
         self.weights: Dict[str, MXTensor] = {}
         self._operands: Dict[str, MXTensor] = {}      # operation name -> its weight as the kernel takes it
+        self._runs: Dict[str, object] = {}            # operation name -> its override
         self.refresh()
 
     def _format(self, config) -> Optional[MXFormat]:
@@ -626,15 +720,21 @@ class MXDeployment:
             if len(packed.shape) != 4: return f'a {len(packed.shape)}-d Conv weight'
             stride, padding, operand = a.get('strides', 1), a.get('pads', 0), packed
 
-            def run(op, x):
-                return mx_conv2d(x[0], self._operands[op.name], afmt, x[2] if len(x) > 2 else None, stride, padding, use_kernels=use_kernels)
+            def run(op, x, **tail):
+                bias = x[2] if len(x) > 2 else None
+                if isinstance(x[0], MXTensor):         # handed over packed by the producer's fused launch: nothing to quantise
+                    return mx_conv2d_packed(_handed(op, x[0], afmt, 1), self._operands[op.name], bias, stride, padding, use_kernels=use_kernels, **tail)
+                return mx_conv2d(x[0], self._operands[op.name], afmt, bias, stride, padding, use_kernels=use_kernels, **tail)
         else:
             if len(packed.shape) != 2: return f'a {len(packed.shape)}-d {op.type} weight'
             # a MatMul weight [in, out] is packed along axis 0: its bytes are those of [out, in] packed along axis 1
             operand = packed if op.type == 'Gemm' else MXTensor(packed.format, packed.shape[::-1], 1, packed.elements, packed.scales)
 
-            def run(op, x):
-                return mx_linear(x[0], self._operands[op.name], afmt, x[2] if len(x) > 2 else None, use_kernels=use_kernels)
+            def run(op, x, **tail):
+                bias = x[2] if len(x) > 2 else None
+                if isinstance(x[0], MXTensor):
+                    return mx_matmul(_handed(op, x[0], afmt, len(x[0].shape) - 1), self._operands[op.name], bias, use_kernels, **tail)
+                return mx_linear(x[0], self._operands[op.name], afmt, bias, use_kernels=use_kernels, **tail)
         return run, operand
 
     def refresh(self) -> None:
@@ -650,19 +750,109 @@ class MXDeployment:
                 self.skipped[name] = plan
                 continue
             run, self._operands[name] = plan
-            self.executor.register_operation_override(name, run)
+            self._runs[name] = run
+            self.executor.register_operation_override(name, run, takes_packed=self.fuse)
             self.deployed.append(name)
+        if self.fuse: self._plan_groups()
+
+    def _plan_groups(self) -> None:
+        """A tail behind every deployed operation -- an optional Add whose other operand is a float activation computed earlier,
+        then an optional Relu, every intermediate feeding only the next member and being no graph output, every config on the way
+        passing through -- and whether the tail's last tensor leaves the launch packed: when every deployed consumer reads it as
+        its activation, in one format, along the axis the launch packs (Conv -> Conv, Gemm / MatMul -> Gemm / MatMul)."""
+        from .harness import QuantableOperation
+        order = self.graph.topological_sort()
+        at = {op.name: i for i, op in enumerate(order)}
+        outputs, claimed = set(self.graph.outputs), set()
+
+        delegates = getattr(self.executor, '_delegates', {})
+
+        def passes(c) -> bool:                         # the rule of the executor's epilogue plan: not activated and not delegated
+            return not _activated(c) and c not in delegates
+
+        def through(op) -> bool:                       # nothing is applied to the tensors the launch does not write one by one
+            if not isinstance(op, QuantableOperation): return True
+            return all(passes(c) for c in (*op.config.input_quantization_config, *op.config.output_quantization_config))
+
+        def sole_consumer(v, op_type: str):
+            if v.name in outputs or len(v.dest_ops) != 1 or v.dest_ops[0].type != op_type: return None
+            return v.dest_ops[0]
+
+        for op in order:
+            if op.name not in self._runs: continue
+            group = MXFusedGroup([op.name])
+            t = op.outputs[0]
+            if len(op.outputs) != 1 or not all(passes(c) for c in op.config.output_quantization_config):
+                group.notes.append('the output config is activated or delegated: no tail, float output')
+                self.groups[op.name] = group
+                continue
+            add = sole_consumer(t, 'Add')
+            if add is not None:
+                other = [v for v in add.inputs if v is not t]
+                why = None
+                if len(add.inputs) != 2 or len(other) != 1 or len(add.outputs) != 1: why = 'the Add does not add this output to one other tensor'
+                elif add.name in claimed: why = 'the Add belongs to another group'
+                elif other[0].is_parameter: why = 'the other operand of the Add is a parameter'
+                elif other[0].source_op is not None and at[other[0].source_op.name] > at[op.name]: why = 'the other operand of the Add is computed later'
+                elif at[add.name] < at[op.name] or not through(add): why = 'a config of the Add is activated or delegated'
+                if why is None:
+                    group.members.append(add.name); group.residual = other[0].name
+                    claimed.add(add.name)
+                    t = add.outputs[0]
+                else: group.notes.append(f'Add {add.name} not fused: {why}')
+            if add is None or group.residual is not None:
+                relu = sole_consumer(t, 'Relu')
+                if relu is not None and len(relu.inputs) == 1 and len(relu.outputs) == 1 and through(relu) and relu.name not in claimed:
+                    group.members.append(relu.name); group.relu = True
+                    claimed.add(relu.name)
+                    t = relu.outputs[0]
+            group.output = t.name
+            takers = [d for d in t.dest_ops if d.name in self._runs]
+            kind = (lambda o: 'Conv' if o.type == 'Conv' else 'Gemm')
+            if not takers: group.notes.append('float output: no deployed consumer')
+            elif any(d.inputs[0] is not t or sum(1 for x in d.inputs if x is t) != 1 for d in takers): group.notes.append('float output: a deployed consumer does not read it as its activation')
+            elif any(kind(d) != kind(op) for d in takers): group.notes.append('float output: a deployed consumer packs along another axis')
+            elif len({self._format(d.config.input_quantization_config[0]) for d in takers}) != 1: group.notes.append('float output: the deployed consumers read it in different formats')
+            else: group.out_format = self._format(takers[0].config.input_quantization_config[0])
+            self.groups[op.name] = group
+            self.executor.register_group_override(group.members, self._group_run(group))
+
+    def _group_run(self, group: 'MXFusedGroup'):
+        run, names = self._runs[group.members[0]], group.members
+
+        def fn(ops, inputs, need_float):
+            residual = None
+            if group.residual is not None:
+                residual = next(x for x, v in zip(inputs[1], ops[1].inputs) if v.name == group.residual)
+                if isinstance(residual, MXTensor): raise RuntimeError(f'{names[0]}: the residual {group.residual} arrived packed, not as float32')
+            want_float = group.out_format is None or group.output in need_float
+            tail = {}
+            if residual is not None or group.relu or group.out_format is not None:
+                tail = dict(residual=residual, relu=group.relu, out_format=group.out_format, out_float=want_float)
+            out = run(ops[0], inputs[0], **tail)
+            y, packed = (out if isinstance(out, tuple) else (None, out) if isinstance(out, MXTensor) else (out, None))
+            inner = [v.name for m in ops for v in m.outputs]
+            if y is not None: return {n: y for n in inner}, ({group.output: packed} if packed is not None else {})
+            return {}, {n: packed for n in inner}
+        return fn
 
     def remove(self) -> None:
+        for name in getattr(self, 'groups', {}): self.executor.remove_group_override(name)
         for name in self.deployed: self.executor.remove_operation_override(name)
-        self.deployed, self.skipped, self._operands = [], {}, {}
+        self.deployed, self.skipped, self._operands, self._runs, self.groups = [], {}, {}, {}, {}
 
 
-def deploy_graph_mx(graph, executor, delegators=None, use_kernels: bool = True) -> MXDeployment:
+def deploy_graph_mx(graph, executor, delegators=None, use_kernels: bool = True, fuse: bool = False) -> MXDeployment:
     """Put the MX operations of a ``quantize_graph_mx`` graph on the hardware path: the weights are packed (``export_graph_mx``) and
     every eligible operation gets an operation override on ``executor`` that quantises its activation and runs the packed kernel --
     a Conv with ``group`` 1 ``mx_conv2d`` (the activation delegator's format, the bias, ``strides`` and ``pads``), a Gemm ``mx_linear``,
     a MatMul with a 2-D parameter on the right ``mx_linear`` on the weight's own bytes.  MXINT8 on either side, grouped convolutions,
     a MatMul of two activations and weights the export left out stay on the simulated path (``.skipped``).  ``delegators``: what
-    ``quantize_graph_mx`` returned (default: the formats recorded in the configs).  ``use_kernels=False``: the torch arms, any device."""
-    return MXDeployment(graph, executor, delegators, use_kernels)
+    ``quantize_graph_mx`` returned (default: the formats recorded in the configs).  ``use_kernels=False``: the torch arms, any device.
+    ``fuse=True``: every deployed operation additionally runs together with its tail -- an optional
+    residual ``Add``, then an optional ``Relu`` -- as ONE launch (``TorchExecutor.register_group_override``), and the tail's last
+    tensor leaves that launch packed when every deployed consumer reads it as its activation in one format (Conv -> Conv, Gemm ->
+    Gemm): the consumer then quantises nothing.  It is written as float32 only when something reads it as float.  ``.groups``
+    records every group: members, residual, relu, ``out_format`` and, in ``notes``, why an Add was not fused or the output not
+    packed.  A forward that hooks a member or asks for an intermediate runs that group's operations one by one, as ``fuse=False``."""
+    return MXDeployment(graph, executor, delegators, use_kernels, fuse)
