@@ -44,8 +44,9 @@ typedef enum {
                                 * 4: ppqhip_minmax_c_multi carries its job table in the kernel arguments (no device table / upload); split per-tensor LSQ
  *    backward (ppqhip_fq_linear_t_bwd_main / ppqhip_lsq_finish_multi) (round 5); the convolution epilogues
  *    (ppqhip_bias_act / ppqhip_bias_add_act) and their statistics variants (ppqhip_bias_act_stats /
- *    ppqhip_bias_add_act_stats) were ADDED under 4: no existing signature changed, and a library without
- *    them fails at load (_lib.py resolves every declared symbol) */
+ *    ppqhip_bias_add_act_stats, then ppqhip_bias_add_act_stats2 with its elide mask and the histogram-sink
+ *    forms ppqhip_bias_act_hist / ppqhip_bias_add_act_hist) were ADDED under 4: no existing signature changed,
+ *    and a library without them fails at load (_lib.py resolves every declared symbol) */
 
 /* library / device introspection ------------------------------------------------------------- */
 const char* ppqhip_last_error(void);
@@ -441,6 +442,40 @@ int ppqhip_bias_act_stats(float* y, const float* bias, int64_t n, int64_t num_ch
 int ppqhip_bias_add_act_stats(float* a, const float* bias_a, float* b, const float* bias_b, float* out,
                               int64_t n, int64_t num_channel, int64_t elem_per_channel, int relu,
                               float* slots_a, float* slots_b, float* slots_out, void* stream);
+
+/* Stores nothing reads.  In a calibration forward `a` and `b` of ppqhip_bias_add_act have two readers, the addition inside the
+ * launch and their observers; once an observer's statistic is taken inside the launch the store has no reader left.  `elide`
+ * names the tensors that are NOT stored: PPQHIP_ELIDE_A | PPQHIP_ELIDE_B (`out` is always stored).  An elided tensor is computed
+ * with the same arithmetic and fed to its sink from registers; its memory keeps the convolution output it held.  An elided
+ * tensor without a sink (or ELIDE_B without bias_b) is PPQHIP_ERR_INVALID_VALUE.  elide == 0: ppqhip_bias_add_act_stats. */
+#define PPQHIP_ELIDE_A 1
+#define PPQHIP_ELIDE_B 2
+int ppqhip_bias_add_act_stats2(float* a, const float* bias_a, float* b, const float* bias_b, float* out,
+                               int64_t n, int64_t num_channel, int64_t elem_per_channel, int relu,
+                               float* slots_a, float* slots_b, float* slots_out, int elide, void* stream);
+
+/* The histogram phase (phase 2 of KL / MSE): the sink of a stored tensor is the observer's persistent accumulator
+ * int32 rows[ppqhip_hist_rows()][num_bins] with its bin rule (p0, p1) = (hist_scale, unused) or, asymmetric, (min, max) --
+ * the arguments of ppqhip_hist_sym_t_rows / ppqhip_hist_asym_t_rows.  All sinks of one launch share num_bins, asymmetric and
+ * clip_outliers.  Stored tensors are bit for bit the plain launches'; every stored (or elided) element of a tensor with a sink
+ * is counted once, by the bin rule of those entry points (the same code), so the column sums of rows grow by exactly the
+ * counts their launch would add; which row a count lands in is unspecified.  Workgroup g adds into row g by plain
+ * read-modify-write: no atomics on global memory, nothing synchronises, capturable into a HIP graph.  A null rows pointer
+ * counts nothing for that tensor; rows_b needs bias_b.  The sinks of one launch are DISTINCT accumulators (a workgroup reads its
+ * row of each ahead and writes it back at the end): the same rows pointer twice is PPQHIP_ERR_INVALID_VALUE.  Like every
+ * epilogue launch these are not booked by the profiling aid (ppqhip_prof_*), whose records name the kernels of the
+ * calibration statistics proper.
+ * Returns PPQHIP_NOT_FUSED (nothing launched) for: a pointer that is not 16-B aligned, relu == 0, no sink at all, tensors of
+ * 2^20 elements or fewer (they stay with the observers' end-of-forward launch, which bins all of them behind one flush),
+ * live sinks x num_bins above 6144 counters. */
+int ppqhip_bias_act_hist(float* y, const float* bias, int64_t n, int64_t num_channel, int64_t elem_per_channel,
+                         int relu, int32_t* rows_y, float p0_y, float p1_y, int64_t num_bins, int asymmetric,
+                         int clip_outliers, void* stream);
+int ppqhip_bias_add_act_hist(float* a, const float* bias_a, float* b, const float* bias_b, float* out,
+                             int64_t n, int64_t num_channel, int64_t elem_per_channel, int relu,
+                             int32_t* rows_a, float p0_a, float p1_a, int32_t* rows_b, float p0_b, float p1_b,
+                             int32_t* rows_out, float p0_out, float p1_out, int64_t num_bins, int asymmetric,
+                             int clip_outliers, int elide, void* stream);
 
 /* AdaRound (MI355X-native addition; ppq_amd/adaround.py) ------------------------------------------- */
 /* One job per AdaRound weight of a block; a per-tensor job has num_channel = 1, elem_per_channel = n.  `jobs` is a HOST

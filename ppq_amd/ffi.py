@@ -270,9 +270,15 @@ def bias_act_stats_(y: torch.Tensor, bias: torch.Tensor, relu: bool, job) -> boo
                                                          1 if relu else 0, slots, _stream()))
 
 
-def bias_add_act_stats(a: torch.Tensor, bias_a: torch.Tensor, b: torch.Tensor, bias_b, relu: bool, job_a, job_b, job_out):
+ELIDE_A, ELIDE_B = 1, 2          # PPQHIP_ELIDE_A / PPQHIP_ELIDE_B: the tensors a statistics epilogue computes, feeds, and does NOT store
+
+
+def bias_add_act_stats(a: torch.Tensor, bias_a: torch.Tensor, b: torch.Tensor, bias_b, relu: bool, job_a, job_b, job_out,
+                       elide: int = 0):
     """``bias_add_act`` that also folds the stored ``a``, ``b`` (only with ``bias_b``) and the returned ``out`` into the slots
-    of their ``('minmax', slots)`` jobs (None: that tensor is not folded) (``ppqhip_bias_add_act_stats``).
+    of their ``('minmax', slots)`` jobs (None: that tensor is not folded) (``ppqhip_bias_add_act_stats``).  ``elide``
+    (ELIDE_A | ELIDE_B): those tensors are folded but not stored -- their memory keeps the convolution output
+    (``ppqhip_bias_add_act_stats2``; each needs a job).
     None: NOTHING was launched -- the caller runs ``bias_add_act`` and observes as usual."""
     geo = _epilogue_geometry([a, b], [bias_a] if bias_b is None else [bias_a, bias_b])
     if geo is None or a.data_ptr() == b.data_ptr(): return None
@@ -281,10 +287,63 @@ def bias_add_act_stats(a: torch.Tensor, bias_a: torch.Tensor, b: torch.Tensor, b
     except ValueError: return None
     if not any(slots): return None
     out = torch.empty_like(a)
+    args = (a.data_ptr(), bias_a.data_ptr(), b.data_ptr(), 0 if bias_b is None else bias_b.data_ptr(), out.data_ptr(),
+            a.numel(), geo[0], geo[1], 1 if relu else 0, slots[0], slots[1], slots[2])
     with _DeviceOf(a):
-        ok = _fused_or_raise(lib.ppqhip_bias_add_act_stats(
+        if elide: ok = _fused_or_raise(lib.ppqhip_bias_add_act_stats2(*args, int(elide), _stream()))
+        else: ok = _fused_or_raise(lib.ppqhip_bias_add_act_stats(*args, _stream()))
+    return out if ok else None
+
+
+def _sink_rows(job, dev) -> tuple:
+    """(rows address, p0, p1) of an observer's ``('hist_rows', rows, asymmetric, p0, p1, clip)`` job, (0, 0, 0) for no job.
+    Raises ValueError for a job the histogram sinks do not take."""
+    if job is None: return 0, 0.0, 0.0
+    if job[0] != 'hist_rows': raise ValueError('no sink for this job')
+    rows = job[1]
+    if (rows.dtype is not torch.int32 or rows.device != dev or rows.dim() != 2 or not rows.is_contiguous()
+            or rows.shape[0] != lib.ppqhip_hist_rows()): raise ValueError('no sink for this job')
+    return rows.data_ptr(), float(job[3]), float(job[4])
+
+
+def _hist_rule(jobs):
+    """(bins, asymmetric, clip) shared by the jobs of one launch; None when they differ or there is none."""
+    rules = {(int(j[1].shape[1]), bool(j[2]), bool(j[5])) for j in jobs if j is not None}
+    return next(iter(rules)) if len(rules) == 1 else None
+
+
+def bias_act_hist_(y: torch.Tensor, bias: torch.Tensor, relu: bool, job) -> bool:
+    """``bias_act_`` that also counts the stored ``y`` into the rows of ``job`` (an observer's ``('hist_rows', rows,
+    asymmetric, p0, p1, clip)``) from the registers it is stored from (``ppqhip_bias_act_hist``).  False: NOTHING was
+    launched -- the caller runs ``bias_act_`` and observes ``y`` as usual."""
+    geo = _epilogue_geometry([y], [bias])
+    if geo is None or job is None: return False
+    try: rows, p0, p1 = _sink_rows(job, y.device)
+    except ValueError: return False
+    bins, asym, clip = _hist_rule([job])
+    with _DeviceOf(y):
+        return _fused_or_raise(lib.ppqhip_bias_act_hist(y.data_ptr(), bias.data_ptr(), y.numel(), geo[0], geo[1],
+                                                        1 if relu else 0, rows, p0, p1, bins, int(asym), int(clip), _stream()))
+
+
+def bias_add_act_hist(a: torch.Tensor, bias_a: torch.Tensor, b: torch.Tensor, bias_b, relu: bool, job_a, job_b, job_out,
+                      elide: int = 0):
+    """``bias_add_act`` that also counts ``a``, ``b`` (only with ``bias_b``) and the returned ``out`` into the rows of their
+    ``'hist_rows'`` jobs (None: not counted), with ``elide`` as in ``bias_add_act_stats`` (``ppqhip_bias_add_act_hist``).
+    None: NOTHING was launched -- the caller runs ``bias_add_act`` and observes as usual."""
+    geo = _epilogue_geometry([a, b], [bias_a] if bias_b is None else [bias_a, bias_b])
+    if geo is None or a.data_ptr() == b.data_ptr(): return None
+    if bias_b is None and job_b is not None: return None
+    try: sinks = [_sink_rows(j, a.device) for j in (job_a, job_b, job_out)]
+    except ValueError: return None
+    rule = _hist_rule([job_a, job_b, job_out])
+    if rule is None: return None
+    out = torch.empty_like(a)
+    with _DeviceOf(a):
+        ok = _fused_or_raise(lib.ppqhip_bias_add_act_hist(
             a.data_ptr(), bias_a.data_ptr(), b.data_ptr(), 0 if bias_b is None else bias_b.data_ptr(), out.data_ptr(),
-            a.numel(), geo[0], geo[1], 1 if relu else 0, slots[0], slots[1], slots[2], _stream()))
+            a.numel(), geo[0], geo[1], 1 if relu else 0, *sinks[0], *sinks[1], *sinks[2], rule[0], int(rule[1]), int(rule[2]),
+            int(elide), _stream()))
     return out if ok else None
 
 

@@ -177,11 +177,12 @@ def _forward(op: Operation, x: List[torch.Tensor]):
 class EpilogueGroup:
     """Consecutive operations whose elementwise tail runs as ONE epilogue launch (ffi.bias_act_ / ffi.bias_add_act):
     ``P1``  Conv(bias) -> Relu;  ``P2``  Conv_a(bias) [, Conv_b(bias)] -> Add(a, b) -> Relu.
-    ``ops``: the members in execution order; ``convs``: the convolutions, Add input 0's producer first; ``add`` / ``relu``."""
-    __slots__ = ('kind', 'ops', 'convs', 'add', 'relu')
+    ``ops``: the members in execution order; ``convs``: the convolutions, Add input 0's producer first; ``add`` / ``relu``;
+    ``keep``: the variable names the planner was told to keep (graph outputs, requested outputs)."""
+    __slots__ = ('kind', 'ops', 'convs', 'add', 'relu', 'keep')
 
-    def __init__(self, kind, ops, convs, add, relu):
-        self.kind, self.ops, self.convs, self.add, self.relu = kind, ops, convs, add, relu
+    def __init__(self, kind, ops, convs, add, relu, keep=()):
+        self.kind, self.ops, self.convs, self.add, self.relu, self.keep = kind, ops, convs, add, relu, frozenset(keep)
 
     def __repr__(self): return f'{self.kind}({", ".join(op.name for op in self.ops)})'
 
@@ -254,7 +255,7 @@ def plan_epilogues(operations: List[Operation], hooks: Dict[str, object] = None,
             if not through(*unwritten, *between): return None
             members = list(operations[i:j + 2])
             if not hooks_ok(members, unwritten): return None
-            return EpilogueGroup('P2', members, ordered, add, relu)
+            return EpilogueGroup('P2', members, ordered, add, relu, keep)
         return None
 
     def try_p1(i):
@@ -264,7 +265,7 @@ def plan_epilogues(operations: List[Operation], hooks: Dict[str, object] = None,
         if relu is None: return None
         unwritten = (_out_cfg(conv, 0), _in_cfg(relu, 0))
         if not through(*unwritten) or not hooks_ok([conv, relu], unwritten): return None
-        return EpilogueGroup('P1', [conv, relu], [conv], None, relu)
+        return EpilogueGroup('P1', [conv, relu], [conv], None, relu, keep)
 
     groups, i = [], 0
     while i < len(operations):
@@ -276,6 +277,31 @@ def plan_epilogues(operations: List[Operation], hooks: Dict[str, object] = None,
         groups.append(g)
         i += len(g.ops)
     return groups
+
+
+def elidable_stores(grp: EpilogueGroup, hooks, jobs: Dict[str, tuple], recorder=None) -> set:
+    """The convolutions of a P2 group whose biased output ``a`` / ``b`` the epilogue launch need not STORE in this
+    calibration forward (ffi.ELIDE_A / ELIDE_B): the tensor then has no reader left.  Its graph consumer is the group's Add,
+    which happens inside the launch; its observer takes its statistic inside the launch too.  So a store stays unless
+    all of these hold: (1) the Add is the variable's only consumer; (2) it is no graph output and was not requested
+    (``grp.keep``); (3) its observer got a sink in this launch (``jobs``: member name -> job) and touches the tensor
+    through that job only (``reads_only_its_job``: not a subclass, not a replaced ``observe``); (4) nothing records the
+    tensors of this forward (``recorder``: ``ObservationQueue.recorder`` of ``reuse_activations``); (5) no other hook of
+    the group observes the variable (the Add's input side)."""
+    if grp.kind != 'P2' or recorder is not None or not hooks: return set()
+    add_hook = hooks.get(grp.add.name)
+    out = set()
+    for conv in grp.convs:
+        v, hook = conv.outputs[0], hooks.get(conv.name)
+        if len(v.dest_ops) != 1 or v.dest_ops[0] is not grp.add or v.name in grp.keep: continue
+        if conv.name not in jobs or hook is None or not isinstance(conv, QuantableOperation): continue
+        obs = [hook._observer_table.get(c) for c in conv.config.output_quantization_config]
+        if len(obs) != 1 or obs[0] is None or not obs[0].reads_only_its_job(): continue
+        if add_hook is not None and isinstance(grp.add, QuantableOperation) and any(
+                c in add_hook._observer_table for x, c in zip(grp.add.inputs, grp.add.config.input_quantization_config) if x is v):
+            continue
+        out.add(conv.name)
+    return out
 
 
 class TorchExecutor:
@@ -560,7 +586,8 @@ class TorchExecutor:
         the quantize_function calls and hooks of the unfused loop on the tensors the kernel wrote (the planner guarantees
         that the configs of the tensors it did not write pass through and are not observed).  Returns variable name ->
         value for the outputs of every member, or None before anything ran when the operands' layout does not qualify."""
-        from .ffi import bias_act_, bias_act_stats_, bias_add_act, bias_add_act_stats
+        from .ffi import (ELIDE_A, ELIDE_B, bias_act_, bias_act_hist_, bias_act_stats_, bias_add_act, bias_add_act_hist,
+                          bias_add_act_stats)
         for conv in grp.convs:                       # conv output layout follows x / w: both dense, both in one format
             x, w = raw_of(conv.inputs[0]), conv.inputs[1].value
             if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
@@ -593,10 +620,13 @@ class TorchExecutor:
             y = ys[conv.name]
             stored = {grp.relu.name: y}                  # member -> the tensor the launch stores as that member's output
             fed = self._epilogue_sinks(grp, hooks, stored, y)
-            if fed is not None and not bias_act_stats_(y, biases[conv.name], True, fed[0].get(grp.relu.name)): fed = None
+            if fed is not None:
+                job = fed[0].get(grp.relu.name)
+                launch = bias_act_hist_ if job is not None and job[0] == 'hist_rows' else bias_act_stats_
+                if not launch(y, biases[conv.name], True, job): fed = None
             if fed is None and not bias_act_(y, biases[conv.name], relu=True):
                 y.add_(biases[conv.name].view(1, -1, 1, 1)).relu_()      # PyTorch's own conv-bias step, then F.relu
-            tail = {conv.name: y, grp.relu.name: y}
+            tail, elided = {conv.name: y, grp.relu.name: y}, set()
         else:
             conv_a = grp.convs[0]
             a = ys[conv_a.name]
@@ -605,12 +635,15 @@ class TorchExecutor:
             bias_b = biases[conv_b.name] if conv_b is not None else None
             stored = {conv_a.name: a, grp.relu.name: None}                    # (out does not exist yet)
             if conv_b is not None: stored[conv_b.name] = b
-            fed, out = self._epilogue_sinks(grp, hooks, stored, a), None
+            fed, out, elided = self._epilogue_sinks(grp, hooks, stored, a), None, set()
             if fed is not None:
                 jobs = fed[0]
-                out = bias_add_act_stats(a, biases[conv_a.name], b, bias_b, True, jobs.get(conv_a.name),
-                                         jobs.get(conv_b.name) if conv_b is not None else None, jobs.get(grp.relu.name))
-                if out is None: fed = None
+                elided = elidable_stores(grp, hooks, jobs, fed[1].recorder)
+                mask = (ELIDE_A if conv_a.name in elided else 0) | (ELIDE_B if conv_b is not None and conv_b.name in elided else 0)
+                launch = bias_add_act_hist if next(iter(jobs.values()))[0] == 'hist_rows' else bias_add_act_stats
+                out = launch(a, biases[conv_a.name], b, bias_b, True, jobs.get(conv_a.name),
+                             jobs.get(conv_b.name) if conv_b is not None else None, jobs.get(grp.relu.name), mask)
+                if out is None: fed, elided = None, set()
                 else: stored[grp.relu.name] = out
             if out is None: out = bias_add_act(a, biases[conv_a.name], b, bias_b, relu=True)
             if out is None:
@@ -640,15 +673,23 @@ class TorchExecutor:
             if hook is not None:
                 outs = hook.post_forward_hook(outputs=fp_outs, quant_outputs=outs, quant_configs=out_cfgs)
             for v, y in zip(op.outputs, outs): values[v.name] = y
+        # a tensor the launch did not store still holds the convolution WITHOUT its bias.  The loop above handed it on all the
+        # same: to quantize_function, whose config is INITIAL (stat_job hands out jobs for INITIAL configs only) so that it
+        # passes the tensor through, and whose result is discarded here; and to the hook, whose observer claimed the prepaid
+        # pair without reading it (reads_only_its_job).  Nobody gets to read it afterwards -- the variable has no value
+        for name in elided:
+            for v in next(m for m in grp.ops if m.name == name).outputs: values[v.name] = None
         return values
 
     @ staticmethod
     def _epilogue_sinks(grp: EpilogueGroup, hooks, stored: Dict[str, torch.Tensor], like: torch.Tensor):
-        """Calibration forwards: ``({member name: ('minmax', slots)}, queue)`` when the running range every observer of the
-        group's stored outputs is about to queue can ride the epilogue launch instead (ffi.bias_act_stats_ /
-        bias_add_act_stats) -- each such observer has a job (``stat_job``), one queue, no side stream; None otherwise (no
-        hooks, nothing observed, or any observer without a job: today's path).  ``stored``: the members whose output the
-        launch stores; ``like``: a tensor on the launch's device."""
+        """Calibration forwards: ``({member name: job}, queue)`` when the statistic every observer of the group's stored
+        outputs is about to queue can ride the epilogue launch instead -- the running range in the min/max phase
+        (``('minmax', slots)``: ffi.bias_act_stats_ / bias_add_act_stats), the histogram rows in the histogram phase
+        (``('hist_rows', ...)``: ffi.bias_act_hist_ / bias_add_act_hist).  Each such observer has a job (``stat_job``),
+        one queue, no side stream, and all jobs of the group are of one kind; None otherwise (no hooks, nothing observed,
+        any observer without a job, mixed kinds: today's path).  ``stored``: the members whose output the launch stores;
+        ``like``: a tensor on the launch's device."""
         jobs, queue = {}, None
         for op in grp.ops:
             hook = hooks.get(op.name)
@@ -661,6 +702,7 @@ class TorchExecutor:
                 job = ob.stat_job(like)
                 if job is None: return None
                 jobs[op.name], queue = job, ob.queue
+        if len({job[0] for job in jobs.values()}) > 1: return None
         return (jobs, queue) if jobs else None
 
     def _quantize_parameter(self, var: Variable, config) -> torch.Tensor:

@@ -165,10 +165,10 @@ class ObservationQueue:
         if self._bytes > self._max: self._launch()           # (not flush(): pairs prepaid for this forward are still to be claimed)
 
     def prepay(self, value: torch.Tensor, buffer: torch.Tensor) -> None:
-        """The launch that produced ``value`` has already folded it into ``buffer`` (an observer's slots: the statistics
-        variant of a convolution epilogue, ``TorchExecutor._run_epilogue``).  The ``add_minmax`` of exactly this pair that the
-        observer's ``observe`` is about to make is dropped, once; every other bookkeeping step of ``observe`` still runs.
-        ``flush`` forgets what was never claimed."""
+        """The launch that produced ``value`` has already folded it into ``buffer`` (an observer's slots or histogram rows:
+        the statistics variants of a convolution epilogue, ``TorchExecutor._run_epilogue``).  The ``add_minmax`` /
+        ``add_hist`` of exactly this pair that the observer's ``observe`` is about to make is dropped, once; every other
+        bookkeeping step of ``observe`` still runs.  ``flush`` forgets what was never claimed."""
         self._prepaid.add((value.data_ptr(), buffer.data_ptr()))
 
     def _claim(self, value: torch.Tensor, buffer: torch.Tensor) -> bool:
@@ -192,6 +192,7 @@ class ObservationQueue:
         self._grow(value)
 
     def add_hist(self, value: torch.Tensor, rows: torch.Tensor, asymmetric: bool, p0: float, p1: float = 0.0) -> None:
+        if self._prepaid and self._claim(value, rows): return
         self._hist.setdefault((bool(asymmetric), rows.shape[1], value.device), []).append((value, rows, p0, p1))
         self._grow(value)
 
@@ -296,9 +297,17 @@ class BaseTensorObserver:
 
     def stat_job(self, value) -> Optional[tuple]:
         """What ``observe(value)`` would hand to ``ObservationQueue.add_minmax``: ``('minmax', slots)``, the buffers allocated
-        as ``observe`` allocates them -- or None when this observer would not queue a per-tensor running range for ``value``
-        (per channel, histogram phase, percentile, isotone, constant, a config that is no longer INITIAL)."""
+        as ``observe`` allocates them (the histogram observers, in their second phase, what it would hand to ``add_hist``:
+        ``TorchHistObserver.stat_job``) -- or None when this observer would not queue a per-tensor statistic for ``value``
+        (per channel, percentile, isotone, constant, a config that is no longer INITIAL)."""
         return None
+
+    def reads_only_its_job(self) -> bool:
+        """True when ``observe(value)`` touches the tensor ONLY through the launch its ``stat_job`` describes, so that a
+        producer which prepaid that job may leave the tensor unwritten (the store elision of ``TorchExecutor._run_epilogue``):
+        ``observe`` is this module's own method for exactly this class.  A subclass, or an ``observe`` somebody replaced
+        (a recorder, a spy that copies what it is shown), may read the values themselves."""
+        return _OWN_OBSERVE.get(type(self)) is type(self).observe
 
     def render_quantization_config(self):
         raise NotImplementedError('Implement this function first.')
@@ -480,11 +489,7 @@ class TorchHistObserver(TorchMinMaxObserver):
         elif self._phase == 'Collating Hist':
             self._losses = None                              # (a search result prefetched for an earlier state of the histogram)
             if getattr(self, '_best', None) is not None: self._best = None
-            if self._hist is None:
-                self._hist = torch.zeros(size=(self._hist_bins,), dtype=torch.int32, device=value.device)
-                if self._hist_bins <= 16384:
-                    self._rows = torch.zeros(size=(CUDA.hist_rows(), self._hist_bins), dtype=torch.int32,
-                                             device=value.device)
+            self._hist_buffers(value)
             if self._quant_cfg.policy.has_property(P.ASYMMETRICAL):
                 if self._rows is not None:
                     if self.queue is not None: self.queue.add_hist(value, self._rows, True, self._min, self._max)
@@ -502,9 +507,27 @@ class TorchHistObserver(TorchMinMaxObserver):
             else:
                 raise TypeError('Quantization Property is invalid, expect either ASYMMETRICAL or SYMMETRICAL config here.')
 
+    def _hist_buffers(self, value: torch.Tensor) -> None:
+        if self._hist is None:
+            self._hist = torch.zeros(size=(self._hist_bins,), dtype=torch.int32, device=value.device)
+            if self._hist_bins <= 16384:
+                self._rows = torch.zeros(size=(CUDA.hist_rows(), self._hist_bins), dtype=torch.int32,
+                                         device=value.device)
+
     def stat_job(self, value: torch.Tensor) -> Optional[tuple]:
-        # phase 1 only: the histogram rows of phase 2 have no sink in the epilogue launches
-        return super().stat_job(value) if self._phase == 'Detecting Minmax' else None
+        """Phase 1: the running range (``('minmax', slots)``).  Phase 2: what ``observe(value)`` would hand to
+        ``ObservationQueue.add_hist`` -- ``('hist_rows', rows, asymmetric, p0, p1, clip_outliers)``, the buffers allocated as
+        ``observe`` allocates them (the epilogue launches' histogram sinks) -- or None when it would
+        not: no queue, per channel, more bins than the rows form takes."""
+        if self._phase == 'Detecting Minmax': return super().stat_job(value)
+        cfg = self._quant_cfg
+        if (self._phase != 'Collating Hist' or not is_initial(cfg) or self.queue is None
+                or not cfg.policy.has_property(P.PER_TENSOR)): return None
+        self._hist_buffers(value)
+        if self._rows is None: return None
+        if cfg.policy.has_property(P.ASYMMETRICAL): return ('hist_rows', self._rows, True, self._min, self._max, True)
+        if cfg.policy.has_property(P.SYMMETRICAL): return ('hist_rows', self._rows, False, self._hist_scale, 0.0, True)
+        return None
 
     def pending_range(self):
         return super().pending_range() if self._phase == 'Detecting Minmax' else None
@@ -1069,6 +1092,11 @@ def register_calibration_observer(algorithm: str, observer: type) -> None:
     if not issubclass(observer, BaseTensorObserver):
         raise TypeError('Regitsing observer must be a subclass of BaseTensorObserver.')
     OBSERVER_TABLE[str(algorithm).lower()] = observer
+
+
+# class -> the ``observe`` it had when this module was loaded (BaseTensorObserver.reads_only_its_job): the observers whose
+# stat_job covers everything their observe does with the tensor
+_OWN_OBSERVE = {cls: cls.observe for cls in (TorchMinMaxObserver, TorchHistObserver, TorchMSEObserver)}
 
 
 class TensorObserverFactroy:
