@@ -18,6 +18,7 @@ observers touch, with the reference's names and call protocol --
 The dense math (conv / gemm) is PyTorch-ROCm (MIOpen / rocBLAS), exactly as in the reference; only
 the quantization simulation goes through this package's kernels.
 """
+import contextlib
 from typing import Callable, Dict, List, Optional
 
 import torch
@@ -446,8 +447,66 @@ class TorchExecutor:
             return self._delegates[config](tensor, config)
         return self._default_quant_fn(tensor, config)
 
+    def _input_side(self, op: Operation, raw_in: list, hook) -> list:
+        """Quantise the inputs of `op`, then ``pre_forward_hook``: what ``_forward`` computes with."""
+        qin, cfgs = raw_in, None
+        if isinstance(op, QuantableOperation):
+            cfgs = list(op.config.input_quantization_config)
+            qin = [self._quantize_parameter(v, c) if v.is_parameter else self.quantize_function(x, c)
+                   for v, x, c in zip(op.inputs, raw_in, cfgs)]
+        if hook is not None: qin = hook.pre_forward_hook(inputs=raw_in, quant_inputs=qin, quant_configs=cfgs)
+        return qin
+
+    def _output_side(self, op: Operation, outs, hook) -> list:
+        """What `op` computed as a list, quantised, then ``post_forward_hook``: the values of its output variables."""
+        fp_outs = outs = list(outs) if isinstance(outs, (list, tuple)) else [outs]
+        cfgs = None
+        if isinstance(op, QuantableOperation):
+            cfgs = list(op.config.output_quantization_config)
+            outs = [self.quantize_function(y, c) for y, c in zip(outs, cfgs)]
+        if hook is not None: outs = hook.post_forward_hook(outputs=fp_outs, quant_outputs=outs, quant_configs=cfgs)
+        return outs
+
+    def _step(self, op: Operation, raw_in: list, hook, packed: Optional[Dict[str, object]]) -> list:
+        """Run one operation (torch.py:499-563): its override, or input side -> ``_forward``; then the output side.  `packed`:
+        what the group overrides of this forward handed over, where an override may take it (``_override_inputs``)."""
+        override = self._overrides.get(op.name) if hook is None else None        # a hooked operation runs the simulation
+        if override is not None: outs = override(op, self._override_inputs(op, raw_in, packed))
+        else: outs = _forward(op, self._input_side(op, raw_in, hook))
+        return self._output_side(op, outs, hook)
+
+    def _walk(self, operations: List[Operation], hooks, output_names: List[str], read: Callable, write: Callable,
+              hand_packed: bool = False, write_aliases: bool = True, done: Callable = None, unfed: str = None) -> None:
+        """Run `operations` (in execution order) on the caller's store -- ``read(variable)``, ``write(op, outputs)`` -- each as part
+        of its group override, of its epilogue group, or through ``_step``.
+        ``hand_packed``: a group override may leave its last output packed only, and an operation override reads it so.
+        ``write_aliases``: also write the outputs a fused unit never materialised on their own -- all but the last of a group
+        override, the input of an epilogue group's Relu.  ``done()``: asked after every unit, true ends the walk.  ``unfed``:
+        the caller's name, to refuse an operation with an input nobody fed or computed."""
+        groups, packed = self._group_plan(operations, hooks, output_names, not hand_packed), {}
+        plan = self._epilogue_plan(operations, hooks, output_names, [m.name for e in groups.values() for m in e[0]])
+        fused_done = set()
+        for op in operations:
+            if op.name in fused_done: continue
+            vals = None
+            if op.name in groups:
+                members = groups[op.name][0]
+                vals, aliases = self._run_group(groups[op.name], read, packed), members[:-1]
+            elif op.name in plan:
+                grp = plan[op.name]
+                vals, members, aliases = self._run_epilogue(grp, read, hooks), grp.ops, (grp.add or grp.convs[0],)
+            if vals is None:
+                raw_in = [read(v) for v in op.inputs]
+                if unfed and any(x is None for x in raw_in): raise ValueError(f'{unfed}: input of {op.name} was not fed')
+                write(op, self._step(op, raw_in, hooks.get(op.name) if hooks else None, packed if hand_packed else None))
+            else:
+                for m in members:                     # a fused unit ran: its members are done
+                    fused_done.add(m.name)
+                    if write_aliases or m not in aliases: write(m, [vals[v.name] for v in m.outputs])
+            if done is not None and done(): break
+
     def forward_with_gradient(self, inputs, output_names: List[str] = None, hooks=None):
-        """torch.py:412-455: the same loop with autograd enabled (finetuning passes)."""
+        """torch.py:412-455: the same walk with autograd enabled (finetuning passes)."""
         return TorchExecutor.forward.__wrapped__(self, inputs, output_names, hooks)
 
     def partial_graph_forward(self, operations: List[Operation], feed_dict: Dict[str, torch.Tensor],
@@ -455,53 +514,17 @@ class TorchExecutor:
         """ppq/executor/torch.py:654-682: run only `operations` (already in execution order) on the
         given feeds -- the block forward of the training based passes.  Like ``forward`` it records no autograd
         graph unless ``with_gradient`` (the finetuning passes' training step) asks for one."""
-        if not with_gradient:
-            with torch.no_grad(): return self._partial_graph_forward(operations, feed_dict, output_names)
-        return self._partial_graph_forward(operations, feed_dict, output_names)
-
-    def _partial_graph_forward(self, operations, feed_dict, output_names):
         g = self._graph
-        for name, value in feed_dict.items(): g.variables[name].value = self._place(value)
         results = [None] * len(output_names)
-        self._fused_parameters(operations)            # the multi-tensor plan covers the parameters of THESE operations only
-        groups, packed = self._group_plan(operations, None, output_names, True), {}
-        plan, fused_done = self._epilogue_plan(operations, None, output_names, [m.name for e in groups.values() for m in e[0]]), set()
-        for op in operations:
-            if op.name in fused_done: continue
-            if op.name in groups:
-                vals = self._run_group(groups[op.name], lambda v: v.value, packed)
-                for m in groups[op.name][0]:
-                    fused_done.add(m.name)
-                    for v in m.outputs:
-                        v.value = vals[v.name]
-                        if v.name in output_names: results[output_names.index(v.name)] = v.value
-                continue
-            grp = plan.get(op.name)
-            vals = self._run_epilogue(grp, lambda v: v.value, None) if grp is not None else None
-            if vals is not None:
-                for m in grp.ops:
-                    fused_done.add(m.name)
-                    for v in m.outputs:
-                        v.value = vals[v.name]
-                        if v.name in output_names: results[output_names.index(v.name)] = v.value
-                continue
-            raw_in = [v.value for v in op.inputs]
-            if any(x is None for x in raw_in):
-                raise ValueError(f'partial_graph_forward: input of {op.name} was not fed')
-            override = self._overrides.get(op.name)
-            if override is not None: outs = override(op, raw_in)
-            else:
-                if isinstance(op, QuantableOperation):
-                    qin = [self._quantize_parameter(v, c) if v.is_parameter else self.quantize_function(x, c)
-                           for v, x, c in zip(op.inputs, raw_in, op.config.input_quantization_config)]
-                else: qin = raw_in
-                outs = _forward(op, qin)
-            outs = list(outs) if isinstance(outs, (list, tuple)) else [outs]
-            if isinstance(op, QuantableOperation):
-                outs = [self.quantize_function(y, c) for y, c in zip(outs, op.config.output_quantization_config)]
+
+        def write(op, outs):
             for v, y in zip(op.outputs, outs):
                 v.value = y
                 if v.name in output_names: results[output_names.index(v.name)] = y
+        with contextlib.nullcontext() if with_gradient else torch.no_grad():
+            for name, value in feed_dict.items(): g.variables[name].value = self._place(value)
+            self._fused_parameters(operations)            # the multi-tensor plan covers the parameters of THESE operations only
+            self._walk(operations, None, output_names, lambda v: v.value, write, unfed='partial_graph_forward')
         for v in g.variables.values():
             if not v.is_parameter: v.value = None
         return results
@@ -600,21 +623,13 @@ class TorchExecutor:
                 b = raw_of(b_var)
                 if not (isinstance(b, torch.Tensor) and b.is_cuda and b.dtype == torch.float32): return None
         hooks = hooks or {}
-        ys, biases, qins = {}, {}, {}
+        ys, biases = {}, {}
         for conv in grp.ops[:len(grp.convs)]:        # the convolutions, in execution order
-            raw_in = [raw_of(v) for v in conv.inputs]
-            qin, in_cfgs = raw_in, None
-            if isinstance(conv, QuantableOperation):
-                in_cfgs = list(conv.config.input_quantization_config)
-                qin = [self._quantize_parameter(v, c) if v.is_parameter else self.quantize_function(x, c)
-                       for v, x, c in zip(conv.inputs, raw_in, in_cfgs)]
-            hook = hooks.get(conv.name)
-            if hook is not None: qin = hook.pre_forward_hook(inputs=raw_in, quant_inputs=qin, quant_configs=in_cfgs)
+            qin = self._input_side(conv, [raw_of(v) for v in conv.inputs], hooks.get(conv.name))
             a = conv.attributes
             ys[conv.name] = F.conv2d(qin[0], qin[1], None, stride=a.get('strides', 1), padding=a.get('pads', 0),
                                      groups=a.get('group', 1))
             biases[conv.name] = qin[2]
-            qins[conv.name] = qin
         if grp.kind == 'P1':
             conv = grp.convs[0]
             y = ys[conv.name]
@@ -657,22 +672,9 @@ class TorchExecutor:
         values: Dict[str, torch.Tensor] = {}
         for op in grp.ops:
             hook = hooks.get(op.name)
-            quantable = isinstance(op, QuantableOperation)
-            if op.type != 'Conv':                   # Add / Relu: their input side of the unfused loop
-                raw_in = [values[v.name] if v.name in values else raw_of(v) for v in op.inputs]
-                qin, in_cfgs = raw_in, None
-                if quantable:
-                    in_cfgs = list(op.config.input_quantization_config)
-                    qin = [self.quantize_function(x, c) for x, c in zip(raw_in, in_cfgs)]
-                if hook is not None: hook.pre_forward_hook(inputs=raw_in, quant_inputs=qin, quant_configs=in_cfgs)
-            outs = fp_outs = [tail[op.name]]
-            out_cfgs = None
-            if quantable:
-                out_cfgs = list(op.config.output_quantization_config)
-                outs = [self.quantize_function(y, c) for y, c in zip(outs, out_cfgs)]
-            if hook is not None:
-                outs = hook.post_forward_hook(outputs=fp_outs, quant_outputs=outs, quant_configs=out_cfgs)
-            for v, y in zip(op.outputs, outs): values[v.name] = y
+            if op.type != 'Conv':                   # Add / Relu: their input side (the launch has computed them already)
+                self._input_side(op, [values[v.name] if v.name in values else raw_of(v) for v in op.inputs], hook)
+            for v, y in zip(op.outputs, self._output_side(op, tail[op.name], hook)): values[v.name] = y
         # a tensor the launch did not store still holds the convolution WITHOUT its bias.  The loop above handed it on all the
         # same: to quantize_function, whose config is INITIAL (stat_job hands out jobs for INITIAL configs only) so that it
         # passes the tensor through, and whose result is discarded here; and to the hook, whose observer claimed the prepaid
@@ -706,12 +708,12 @@ class TorchExecutor:
         return (jobs, queue) if jobs else None
 
     def _quantize_parameter(self, var: Variable, config) -> torch.Tensor:
-        hit = self._fused.get((var.name, id(config)))
-        if hit is not None: return hit
         """A parameter and its scale do not change between calibration forwards, so its fake-quantised
         value is computed once and kept resident (the reference recomputes it every forward until
         ParameterBakingPass; same values, ppq/executor/torch.py:516-518).  The cache entry is keyed on
         the identity + version of value, scale and offset and on the config state."""
+        hit = self._fused.get((var.name, id(config)))
+        if hit is not None: return hit
         if not self.cache_parameter_quantization or not QuantizationStates.is_activated(config.state):
             return self.quantize_function(var.value, config)
         key = (var.value.data_ptr(), var.value._version, id(config.scale), config.scale._version,
@@ -744,41 +746,13 @@ class TorchExecutor:
             need.add(op.name)
             stack.extend(op.inputs)
         ops = [op for op in g.topological_sort() if op.name in need]
-        if ops: self._fused_parameters(ops)
-        groups, packed = self._group_plan(ops, None, output_names, True), {}
-        plan, fused_done = (self._epilogue_plan(ops, None, output_names, [m.name for e in groups.values() for m in e[0]]) if ops else {}), set()
-        for op in ops:
-            if op.name in fused_done: continue
-            if op.name in groups:
-                vals = self._run_group(groups[op.name], lambda v: v.value if v.is_parameter else cache[v.name], packed)
-                members = groups[op.name][0]
-                for m in members: fused_done.add(m.name)
-                # only the last output is cached: the others alias it and were never materialised; a later request recomputes them
-                for v in members[-1].outputs: cache[v.name] = vals[v.name]
-                continue
-            grp = plan.get(op.name)
-            vals = (self._run_epilogue(grp, lambda v: v.value if v.is_parameter else cache[v.name], None)
-                    if grp is not None else None)
-            if vals is not None:
-                hidden = grp.relu.inputs[0].name       # never materialised on its own: a later request recomputes it
-                for m in grp.ops:
-                    fused_done.add(m.name)
-                    for v in m.outputs:
-                        if v.name != hidden: cache[v.name] = vals[v.name]
-                continue
-            raw_in = [v.value if v.is_parameter else cache[v.name] for v in op.inputs]
-            override = self._overrides.get(op.name)
-            if override is not None: outs = override(op, raw_in)
-            else:
-                if isinstance(op, QuantableOperation):
-                    qin = [self._quantize_parameter(v, c) if v.is_parameter else self.quantize_function(x, c)
-                           for v, x, c in zip(op.inputs, raw_in, op.config.input_quantization_config)]
-                else: qin = raw_in
-                outs = _forward(op, qin)
-            outs = list(outs) if isinstance(outs, (list, tuple)) else [outs]
-            if isinstance(op, QuantableOperation):
-                outs = [self.quantize_function(y, c) for y, c in zip(outs, op.config.output_quantization_config)]
+
+        def write(op, outs):
             for v, y in zip(op.outputs, outs): cache[v.name] = y
+        if ops:
+            self._fused_parameters(ops)
+            # what a fused unit never materialised on its own is not cached: it aliases another tensor; a later request recomputes it
+            self._walk(ops, None, output_names, lambda v: v.value if v.is_parameter else cache[v.name], write, write_aliases=False)
         return [cache[n] for n in output_names]
 
     @ torch.no_grad()
@@ -794,9 +768,6 @@ class TorchExecutor:
         results = [None] * len(output_names)
         visited = set()
         self._fused_parameters()
-        ops = g.topological_sort()
-        groups, packed = self._group_plan(ops, hooks, output_names, False), {}
-        plan, fused_done = self._epilogue_plan(ops, hooks, output_names, [m.name for e in groups.values() for m in e[0]]), set()
 
         def finish(op, outs):
             for v, y in zip(op.outputs, outs):
@@ -805,47 +776,8 @@ class TorchExecutor:
             visited.add(op.name)
             for v in op.inputs:                      # runtime clear, torch.py:564-568
                 if not v.is_parameter and all(d.name in visited for d in v.dest_ops): v.value = None
-
-        for op in ops:
-            if op.name in fused_done: continue
-            if op.name in groups:
-                vals = self._run_group(groups[op.name], lambda v: v.value, packed)
-                for m in groups[op.name][0]:
-                    fused_done.add(m.name)
-                    finish(m, [vals[v.name] for v in m.outputs])
-                if stop_early and all(r is not None for r in results): break
-                continue
-            grp = plan.get(op.name)
-            vals = self._run_epilogue(grp, lambda v: v.value, hooks) if grp is not None else None
-            if vals is not None:
-                for m in grp.ops:
-                    fused_done.add(m.name)
-                    finish(m, [vals[v.name] for v in m.outputs])
-                if stop_early and all(r is not None for r in results): break
-                continue
-            hook = hooks.get(op.name) if hooks else None
-            raw_in = [v.value for v in op.inputs]
-            qin = raw_in
-            quantable = isinstance(op, QuantableOperation)
-            override = self._overrides.get(op.name) if hook is None else None        # a hooked operation runs the simulation
-            if override is not None: outs = override(op, self._override_inputs(op, raw_in, packed))
-            else:
-                if quantable:
-                    in_cfgs = list(op.config.input_quantization_config)
-                    qin = [self._quantize_parameter(v, c) if v.is_parameter else self.quantize_function(x, c)
-                           for v, x, c in zip(op.inputs, raw_in, in_cfgs)]
-                if hook is not None:
-                    qin = hook.pre_forward_hook(inputs=raw_in, quant_inputs=qin, quant_configs=in_cfgs)
-                outs = _forward(op, qin)
-            outs = list(outs) if isinstance(outs, (list, tuple)) else [outs]
-            fp_outs = outs
-            if quantable:
-                out_cfgs = list(op.config.output_quantization_config)
-                outs = [self.quantize_function(y, c) for y, c in zip(outs, out_cfgs)]
-            if hook is not None:
-                outs = hook.post_forward_hook(outputs=fp_outs, quant_outputs=outs, quant_configs=out_cfgs)
-            finish(op, outs)
-            if stop_early and all(r is not None for r in results): break      # nothing downstream was asked for
+        self._walk(g.topological_sort(), hooks, output_names, lambda v: v.value, finish, hand_packed=True,
+                   done=(lambda: all(r is not None for r in results)) if stop_early else None)      # nothing downstream was asked for
         for v in g.variables.values():
             if not v.is_parameter: v.value = None
         return results
