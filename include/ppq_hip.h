@@ -45,7 +45,8 @@ typedef enum {
  *    backward (ppqhip_fq_linear_t_bwd_main / ppqhip_lsq_finish_multi) (round 5); the convolution epilogues
  *    (ppqhip_bias_act / ppqhip_bias_add_act) and their statistics variants (ppqhip_bias_act_stats /
  *    ppqhip_bias_add_act_stats, then ppqhip_bias_add_act_stats2 with its elide mask and the histogram-sink
- *    forms ppqhip_bias_act_hist / ppqhip_bias_add_act_hist) were ADDED under 4: no existing signature changed,
+ *    forms ppqhip_bias_act_hist / ppqhip_bias_add_act_hist, then the pooled forms ppqhip_bias_act_pool /
+ *    ppqhip_bias_act_pool_stats / ppqhip_bias_act_pool_hist) were ADDED under 4: no existing signature changed,
  *    and a library without them fails at load (_lib.py resolves every declared symbol) */
 
 /* library / device introspection ------------------------------------------------------------- */
@@ -476,6 +477,32 @@ int ppqhip_bias_add_act_hist(float* a, const float* bias_a, float* b, const floa
                              int32_t* rows_a, float p0_a, float p1_a, int32_t* rows_b, float p0_b, float p1_b,
                              int32_t* rows_out, float p0_out, float p1_out, int64_t num_bins, int asymmetric,
                              int clip_outliers, int elide, void* stream);
+
+/* The pooled form: Conv(bias) -> Relu -> MaxPool in one launch over contiguous NCHW, y = [n / (C * H * W), C, H, W]:
+ *   pool = MaxPool2d(kernel, stride, pad)(act(y + bias[c])),  pool = [.., C, OH, OW], OH = (H + 2 pad - kernel) / stride + 1.
+ * The add and the ReLU are those of ppqhip_bias_act; the pool is at::native::max_pool_forward_nchw's rule (start from -inf,
+ * scan the window row by row and left to right, skip padding taps, take val when `val > maxval || isnan(val)`), so pool is bit
+ * for bit F.max_pool2d(F.relu(y + bias)), signed zeros and NaN payloads included.  ppqhip_bias_act_pool also overwrites y with
+ * act(y + bias[c]) as ppqhip_bias_act does.  The _stats / _hist forms feed the Relu tensor to its sink exactly as
+ * ppqhip_bias_act_stats / ppqhip_bias_act_hist do (same fold, same bin rule, slot / row of workgroup g), and with
+ * store_relu == 0 leave y as it was -- the convolution output: in a calibration forward the Relu tensor's readers are its
+ * observer and the pool, both served inside the launch.  store_relu == 0 without a sink is PPQHIP_ERR_INVALID_VALUE.
+ * Each workgroup keeps one H x W plane in LDS; no atomics on global memory, nothing synchronises between workgroups:
+ * capturable into a HIP graph; not booked by the profiling aid.
+ * Returns PPQHIP_NOT_FUSED (nothing launched) for: y or pool not 16-B aligned; H * W no multiple of 4; a plane that does not
+ * fit a workgroup's 64 KB of LDS beside the sink's counters (num_bins * 4 B) and 4 KB of staging; kernel > 3, pad > kernel / 2
+ * (PyTorch refuses those itself), dilation != 1, ceil_mode != 0; the _stats / _hist forms without a sink; _hist with relu == 0
+ * or num_bins above 6144. */
+int ppqhip_bias_act_pool(float* y, const float* bias, float* pool, int64_t n, int64_t num_channel, int64_t height,
+                         int64_t width, int relu, int kernel, int stride, int pad, int dilation, int ceil_mode,
+                         void* stream);
+int ppqhip_bias_act_pool_stats(float* y, const float* bias, float* pool, int64_t n, int64_t num_channel, int64_t height,
+                               int64_t width, int relu, int kernel, int stride, int pad, int dilation, int ceil_mode,
+                               float* slots_y, int store_relu, void* stream);
+int ppqhip_bias_act_pool_hist(float* y, const float* bias, float* pool, int64_t n, int64_t num_channel, int64_t height,
+                              int64_t width, int relu, int kernel, int stride, int pad, int dilation, int ceil_mode,
+                              int32_t* rows_y, float p0_y, float p1_y, int64_t num_bins, int asymmetric,
+                              int clip_outliers, int store_relu, void* stream);
 
 /* AdaRound (MI355X-native addition; ppq_amd/adaround.py) ------------------------------------------- */
 /* One job per AdaRound weight of a block; a per-tensor job has num_channel = 1, elem_per_channel = n.  `jobs` is a HOST

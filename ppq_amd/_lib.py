@@ -57,6 +57,12 @@ PROTOTYPES = {
     'ppqhip_bias_add_act_hist': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_i64, c_i64, c_int,
                                          c_i32p, c_flt, c_flt, c_i32p, c_flt, c_flt, c_i32p, c_flt, c_flt, c_i64, c_int, c_int,
                                          c_int, c_vp]),
+    'ppqhip_bias_act_pool': (c_int, [c_f32p, c_f32p, c_f32p, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_int,
+                                     c_vp]),
+    'ppqhip_bias_act_pool_stats': (c_int, [c_f32p, c_f32p, c_f32p, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int,
+                                           c_int, c_f32p, c_int, c_vp]),
+    'ppqhip_bias_act_pool_hist': (c_int, [c_f32p, c_f32p, c_f32p, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int,
+                                          c_int, c_i32p, c_flt, c_flt, c_i64, c_int, c_int, c_int, c_vp]),
     'ppqhip_fq_float_t': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_int, c_int, c_flt, c_flt, c_int, c_vp]),
     'ppqhip_fq_float_c': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_i64, c_i64, c_int, c_int, c_flt, c_flt,
                                   c_int, c_vp]),

@@ -34,6 +34,14 @@
 // inside the launch and their observer; with a sink the observer is served inside the launch too, and the store -- 0.9 GB
 // of the 4.1 GB per ResNet-50 forward -- has no reader left.  The value is computed and fed all the same.
 // Measurements, and what the histogram sinks achieve of the streaming rate: DESIGN.md section 6, profiles/r15_epilogue_hist.txt.
+// The pooled form (ppqhip_bias_act_pool / _pool_stats / _pool_hist): Conv(bias) -> Relu -> MaxPool, the stem of ResNet-50, as
+// one launch.  The Relu tensor there is the largest activation of the network (103 MB at batch 32) and the MaxPool read it
+// back from HBM in a launch of its own.  epilogue_pool_kernel has the statistics kernels' shape and sinks (EpMinMaxSet /
+// EpHistSet as they are, or none) but walks (n, c) planes: it stages each activated plane in LDS, feeds the sink from
+// registers, pools from LDS by at::native::max_pool_forward_nchw's own rule and stores the pooled plane.  With a sink the
+// Relu store can be left out too (store_relu = 0): its readers, the observer and the pool, are both inside the launch.
+// Contiguous NCHW, H * W % 4 == 0, a plane that fits the LDS, kernel <= 3, dilation 1, floor mode; PPQHIP_NOT_FUSED otherwise.
+// Measurements: DESIGN.md section 6, profiles/r17_stem_pool.txt.
 #include "channel_axis.hpp"
 #include "common.hpp"
 #include "hist_bin.hpp"
@@ -536,6 +544,226 @@ int validate_elide(const char* what, int elide, bool sink_a, bool sink_b, bool h
     return PPQHIP_OK;
 }
 
+// ---- the pooled form: Conv(bias) -> Relu -> MaxPool in one launch ------------------------------------------------------
+// pool = MaxPool_{k,s,p}(act(y + bias[c])) over contiguous NCHW.  The launch has the statistics kernels' shape (at most
+// kEpStatWgPerCu workgroups of kEpStatBlock lanes per CU, one fold into slot / row blockIdx.x at the end), but its unit of
+// work is the (n, c) PLANE: a workgroup walks a contiguous range of planes in steps of kEpStatBlock * kEpTileU float4 with
+// the same ping-pong register tiles, and every step puts what it computed (a) back into y unless the store is elided, (b) into
+// the plane's image in LDS, (c) into the sink, from registers, once.  After a plane's last step the workgroup pools from LDS --
+// with the first step of the NEXT plane already in flight -- and stores the pooled plane.
+// The pool is at::native::max_pool_forward_nchw's rule, literally: start from -inf, scan the window row by row and left to
+// right, skip the padding taps, take val when `val > maxval || isnan(val)` (which of +0.0 / -0.0 wins, and which NaN payload
+// comes out, follow from that order).
+// LDS: [sink: histogram counters or 32 floats] [plane: H * W floats] [staging: 128 floats per wave].  One lane pools ONE
+// output at a time and consecutive lanes take consecutive outputs, so a stride-2 window reads LDS with a two-way bank
+// conflict at worst (four consecutive outputs per lane would be an eight-way one); each wave then turns its 128 pooled
+// values into 16-B stores through its own staging lines (no workgroup barrier: LDS operations of one wave complete in
+// order).  A pooled plane whose size is no multiple of 4 is stored element by element.
+struct EpNoSinks {
+    struct Args {};
+    __device__ __forceinline__ void init(const Args&, int*) {}
+    __device__ __forceinline__ void begin() {}
+    template <bool FULL>
+    __device__ __forceinline__ void feed4(const EpStored<float4>&, bool, bool) {}
+    __device__ __forceinline__ void finish(const Args&, uint32_t, int*) {}
+};
+
+constexpr uint32_t kEpPoolStage = 2 * kWave;                                   // pooled values a wave stages per trip
+constexpr uint32_t kEpPoolStageBytes = (kEpStatBlock / kWave) * kEpPoolStage * sizeof(float);
+constexpr uint32_t kEpPoolMaxLds = 64u * 1024u;                                // per workgroup (two per CU: 128 of 160 KB)
+constexpr int kEpPoolMaxKernel = 3;
+
+struct EpPoolArgs {
+    float* y;
+    const float* bias;
+    float* pool;
+    uint32_t planes;       // N * C
+    uint32_t hw4;          // H * W / 4
+    uint32_t H, W, ohw;    // ohw: OH * OW
+    int k, s, pad;
+    FastDiv nc;            // num_channel: channel = plane % C
+    FastDiv ow;            // OW: (oh, ow) of a pooled index
+    uint32_t store;        // 0: y keeps the convolution output (the elided store)
+    uint32_t vec;          // ohw % 4 == 0: 16-B stores of pool
+    uint32_t sink_ints;    // LDS ints in front of the plane
+};
+
+__device__ __forceinline__ void lds_barrier() {       // LDS traffic only: __syncthreads() would also wait for the loads in flight
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+// pooled value o of the plane held in LDS.  Every tap is read from an index clamped into the plane, so that the nine LDS reads
+// issue back to back with no branch between them; a tap in the padding, or beyond a window smaller than 3 x 3, then counts as
+// -inf, which the rule never takes (`-inf > maxval` is false for every maxval, -inf is no NaN): exactly as if it were skipped.
+__device__ __forceinline__ float pool_at(const float* plane, const EpPoolArgs& p, uint32_t o) {
+    const uint32_t oh = fdiv(o, p.ow), ow = o - oh * p.ow.d;
+    const int h0 = (int)oh * p.s - p.pad, w0 = (int)ow * p.s - p.pad;
+    float v[kEpPoolMaxKernel][kEpPoolMaxKernel];
+#pragma unroll
+    for (int kh = 0; kh < kEpPoolMaxKernel; kh++) {
+        const int ih = h0 + kh;
+        const bool row = kh < p.k && (uint32_t)ih < p.H;
+        const uint32_t first = (uint32_t)min(max(ih, 0), (int)p.H - 1) * p.W;
+#pragma unroll
+        for (int kw = 0; kw < kEpPoolMaxKernel; kw++) {
+            const int iw = w0 + kw;
+            const float t = plane[first + (uint32_t)min(max(iw, 0), (int)p.W - 1)];
+            v[kh][kw] = (row && kw < p.k && (uint32_t)iw < p.W) ? t : -INFINITY;
+        }
+    }
+    float m = -INFINITY;
+#pragma unroll
+    for (int kh = 0; kh < kEpPoolMaxKernel; kh++)
+#pragma unroll
+        for (int kw = 0; kw < kEpPoolMaxKernel; kw++)
+            if (v[kh][kw] > m || __builtin_isnan(v[kh][kw])) m = v[kh][kw];
+    return m;
+}
+
+// The host guarantees gridDim.x <= planes, 16-B aligned pointers, hw4 >= 1 and that the LDS layout fits.
+template <int U, bool RELU, class SINKS>
+__global__ __launch_bounds__(kEpStatBlock, (kEpStatBlock * kEpStatWgPerCu + 255) / 256)
+void epilogue_pool_kernel(EpPoolArgs p, typename SINKS::Args sk) {
+    extern __shared__ int lds[];
+    constexpr uint32_t kTile = (uint32_t)kEpStatBlock * U;
+    float* plane = reinterpret_cast<float*>(lds + p.sink_ints);
+    float4* plane4 = reinterpret_cast<float4*>(plane);
+    float* stage = plane + p.hw4 * 4u + (threadIdx.x >> 6) * kEpPoolStage;     // this wave's staging lines
+    float4* y4 = reinterpret_cast<float4*>(p.y);
+    uint32_t pl, pl_end;
+    even_split(p.planes, gridDim.x, blockIdx.x, pl, pl_end);
+    const uint32_t steps = (p.hw4 + kTile - 1) / kTile;                        // per plane
+    SINKS sinks;
+    sinks.init(sk, lds);
+
+    struct Tile { float4 a[U]; float bias; };
+    auto fetch = [&](Tile& T, uint32_t pi, uint32_t step) {                    // clamped inside the plane: straight-line loads
+        const uint32_t first = pi * p.hw4, base = step * kTile + threadIdx.x;
+#pragma unroll
+        for (int u = 0; u < U; u++) T.a[u] = y4[first + min(base + u * kEpStatBlock, p.hw4 - 1)];
+        T.bias = p.bias[pi - fdiv(pi, p.nc) * p.nc.d];
+    };
+    auto pool_plane = [&](uint32_t pi) {
+        float* dst = p.pool + (size_t)pi * p.ohw;
+        const uint32_t lane = threadIdx.x & 63, wave_first = (threadIdx.x >> 6) * kEpPoolStage;
+        for (uint32_t base = 0; base < p.ohw; base += (kEpStatBlock / kWave) * kEpPoolStage) {
+            const uint32_t o0 = base + wave_first + lane, o1 = o0 + kWave;
+            const float m0 = o0 < p.ohw ? pool_at(plane, p, o0) : 0.f;
+            const float m1 = o1 < p.ohw ? pool_at(plane, p, o1) : 0.f;
+            if (p.vec) {
+                stage[lane] = m0;
+                stage[kWave + lane] = m1;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                const uint32_t o4 = base + wave_first + 4u * lane;             // (ohw % 4 == 0: a float4 in range is whole)
+                if (lane < kEpPoolStage / 4 && o4 < p.ohw)
+                    *reinterpret_cast<float4*>(dst + o4) = *reinterpret_cast<const float4*>(stage + 4u * lane);
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            } else {
+                if (o0 < p.ohw) dst[o0] = m0;
+                if (o1 < p.ohw) dst[o1] = m1;
+            }
+        }
+    };
+    auto consume = [&](const Tile& T, uint32_t pi, uint32_t step) {
+        const uint32_t first = pi * p.hw4, base = step * kTile + threadIdx.x;
+        const float4 bias = make_float4(T.bias, T.bias, T.bias, T.bias);
+        const bool full = (step + 1) * kTile <= p.hw4;                         // workgroup uniform
+        EpStored<float4> s[U];
+        bool in[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint32_t vv = base + u * kEpStatBlock;
+            in[u] = vv < p.hw4;
+            s[u] = EpStored<float4>{};
+            s[u].a = act4<RELU>(add4(T.a[u], bias));
+            if (in[u]) {
+                if (p.store) y4[first + vv] = s[u].a;
+                plane4[vv] = s[u].a;
+            }
+        }
+        if (full) {
+#pragma unroll
+            for (int u = 0; u < U; u++) sinks.template feed4<true>(s[u], true, u == 0);
+        } else {
+#pragma unroll
+            for (int u = 0; u < U; u++)                                         // a wave with nothing in range has nothing to feed
+                if (__builtin_amdgcn_ballot_w64(in[u]) != 0ull) sinks.template feed4<false>(s[u], in[u], true);
+        }
+        if (step + 1 == steps) {                                                // the plane is complete
+            lds_barrier();
+            pool_plane(pi);
+            lds_barrier();                                                      // before the next plane overwrites it
+        }
+    };
+    // (plane, step) pairs in order; the prefetch of the pair behind the last one re-reads the last (before anything of it is stored)
+    uint32_t cp = pl, cs = 0;
+    Tile ta{}, tb{};
+    fetch(ta, cp, cs);
+    sinks.begin();
+    for (;;) {
+        uint32_t np = cp, ns = cs + 1;
+        if (ns == steps) { ns = 0; np++; }
+        bool last = np >= pl_end;
+        fetch(tb, last ? cp : np, last ? cs : ns);
+        consume(ta, cp, cs);
+        if (last) break;
+        cp = np; cs = ns;
+        ns = cs + 1;
+        if (ns == steps) { ns = 0; np++; }
+        last = np >= pl_end;
+        fetch(ta, last ? cp : np, last ? cs : ns);
+        consume(tb, cp, cs);
+        if (last) break;
+        cp = np; cs = ns;
+    }
+    sinks.finish(sk, blockIdx.x, lds);
+}
+
+// The shape checks of the pooled entry points: PPQHIP_OK with `p` filled and the dynamic LDS size in `lds_bytes`, or
+// PPQHIP_NOT_FUSED for what the kernel has no exact path for.  `sink_ints`: LDS ints the sinks own in front of the plane.
+int fill_pool_geometry(EpPoolArgs& p, int64_t n, int64_t C, int64_t H, int64_t W, int kernel, int stride, int pad, int dilation,
+                       int ceil_mode, uint32_t sink_ints, uint32_t& lds_bytes) {
+    if (kernel < 1 || kernel > kEpPoolMaxKernel || stride < 1 || pad < 0 || 2 * pad > kernel || dilation != 1 || ceil_mode != 0)
+        return PPQHIP_NOT_FUSED;                                                 // (PyTorch refuses a pad above kernel / 2 itself)
+    const int64_t hw = H * W;
+    if (hw % 4 != 0 || H + 2 * pad < kernel || W + 2 * pad < kernel || !aligned16(p.y) || !aligned16(p.pool)) return PPQHIP_NOT_FUSED;
+    const int64_t OH = (H + 2 * pad - kernel) / stride + 1, OW = (W + 2 * pad - kernel) / stride + 1, planes = n / hw;
+    if (planes * OH * OW > 0x7fffffffLL) return PPQHIP_NOT_FUSED;
+    sink_ints = (sink_ints + 3u) & ~3u;                                          // the plane starts on a 16-B boundary
+    const int64_t bytes = (int64_t)sink_ints * 4 + hw * 4 + kEpPoolStageBytes;
+    if (bytes > (int64_t)kEpPoolMaxLds) return PPQHIP_NOT_FUSED;
+    lds_bytes = (uint32_t)bytes;
+    p.planes = (uint32_t)planes; p.hw4 = (uint32_t)(hw / 4);
+    p.H = (uint32_t)H; p.W = (uint32_t)W; p.ohw = (uint32_t)(OH * OW);
+    p.k = kernel; p.s = stride; p.pad = pad;
+    p.nc = make_fastdiv((uint32_t)C); p.ow = make_fastdiv((uint32_t)OW);
+    p.vec = p.ohw % 4u == 0 ? 1u : 0u;
+    p.sink_ints = sink_ints;
+    return PPQHIP_OK;
+}
+
+uint32_t pool_grid(const EpPoolArgs& p) {
+    const uint32_t cap = (uint32_t)(num_cu() * kEpStatWgPerCu);                  // one slot / row per workgroup
+    return p.planes < cap ? p.planes : cap;
+}
+
+int validate_pool(const char* what, const float* y, const float* bias, const float* pool, int64_t n, int64_t C, int64_t H, int64_t W) {
+    if (H <= 0 || W <= 0 || H > 0x7fffffffLL || W > 0x7fffffffLL || H * W > 0x7fffffffLL) {
+        set_error("%s: the plane %lld x %lld is empty or too large", what, (long long)H, (long long)W); return PPQHIP_ERR_INVALID_VALUE;
+    }
+    if (int st = validate_channel_axis(what, n, C, H * W)) return st;
+    if (!y || !bias || !pool) { set_error("%s: null pointer", what); return PPQHIP_ERR_INVALID_VALUE; }
+    return PPQHIP_OK;
+}
+
+// an elided store (store_relu == 0) loses the Relu tensor unless a sink takes it
+int validate_pool_store(const char* what, int store_relu, bool sink) {
+    if (!store_relu && !sink) { set_error("%s: a tensor that is not stored needs a sink", what); return PPQHIP_ERR_INVALID_VALUE; }
+    return PPQHIP_OK;
+}
+
 }  // namespace
 }  // namespace ppqhip
 
@@ -662,5 +890,68 @@ int ppqhip_bias_add_act_hist(float* a, const float* bias_a, float* b, const floa
     if (bias_b) return launch_epilogue_hist<true, true>(p, n, num_channel, elem_per_channel, relu, aligned, sk, r, what, s);
     return launch_epilogue_hist<true, false>(p, n, num_channel, elem_per_channel, relu, aligned, sk, r, what, s);
 }
+
+#define PPQ_LAUNCH_POOL(RELU, SET, SK)                                                                                    \
+    hipLaunchKernelGGL((epilogue_pool_kernel<kEpTileU, RELU, SET>), dim3(pool_grid(p)), dim3(kEpStatBlock), lds_bytes,      \
+                       (hipStream_t)stream, p, SK)
+
+int ppqhip_bias_act_pool(float* y, const float* bias, float* pool, int64_t n, int64_t num_channel, int64_t height, int64_t width,
+                         int relu, int kernel, int stride, int pad, int dilation, int ceil_mode, void* stream) {
+    const char* what = "bias_act_pool";
+    if (int st = validate_pool(what, y, bias, pool, n, num_channel, height, width)) return st;
+    EpPoolArgs p{};
+    p.y = y; p.bias = bias; p.pool = pool; p.store = 1u;
+    uint32_t lds_bytes = 0;
+    if (int st = fill_pool_geometry(p, n, num_channel, height, width, kernel, stride, pad, dilation, ceil_mode, 0, lds_bytes)) return st;
+    const EpNoSinks::Args sk{};
+    if (relu) PPQ_LAUNCH_POOL(true, EpNoSinks, sk); else PPQ_LAUNCH_POOL(false, EpNoSinks, sk);
+    return finish_launch(what);
+}
+
+int ppqhip_bias_act_pool_stats(float* y, const float* bias, float* pool, int64_t n, int64_t num_channel, int64_t height,
+                               int64_t width, int relu, int kernel, int stride, int pad, int dilation, int ceil_mode,
+                               float* slots_y, int store_relu, void* stream) {
+    const char* what = "bias_act_pool_stats";
+    if (int st = validate_pool(what, y, bias, pool, n, num_channel, height, width)) return st;
+    if (int st = validate_pool_store(what, store_relu, slots_y != nullptr)) return st;
+    if (!slots_y) return PPQHIP_NOT_FUSED;
+    EpPoolArgs p{};
+    p.y = y; p.bias = bias; p.pool = pool; p.store = store_relu ? 1u : 0u;
+    uint32_t lds_bytes = 0;
+    if (int st = fill_pool_geometry(p, n, num_channel, height, width, kernel, stride, pad, dilation, ceil_mode, 32, lds_bytes)) return st;
+    const EpMinMaxSinks sk{{slots_y, nullptr, nullptr}};
+    using Set = EpMinMaxSet<false, false>;
+    if (relu) PPQ_LAUNCH_POOL(true, Set, sk); else PPQ_LAUNCH_POOL(false, Set, sk);
+    return finish_launch(what);
+}
+
+int ppqhip_bias_act_pool_hist(float* y, const float* bias, float* pool, int64_t n, int64_t num_channel, int64_t height,
+                              int64_t width, int relu, int kernel, int stride, int pad, int dilation, int ceil_mode,
+                              int32_t* rows_y, float p0_y, float p1_y, int64_t num_bins, int asymmetric, int clip_outliers,
+                              int store_relu, void* stream) {
+    const char* what = "bias_act_pool_hist";
+    if (int st = validate_pool(what, y, bias, pool, n, num_channel, height, width)) return st;
+    if (int st = validate_hist_rule(what, num_bins)) return st;
+    if (int st = validate_pool_store(what, store_relu, rows_y != nullptr)) return st;
+    if (!rows_y || !relu || num_bins > (int64_t)kEpHistLdsInts) return PPQHIP_NOT_FUSED;
+    const EpHistRule r{(int)num_bins, asymmetric ? 1 : 0, clip_outliers ? 1 : 0};
+    EpHistSinks sk{};
+    set_hist_rule(sk, 0, rows_y, p0_y, p1_y, r);
+    sk.lds_ints = (uint32_t)r.bins; sk.bins = r.bins;
+    EpPoolArgs p{};
+    p.y = y; p.bias = bias; p.pool = pool; p.store = store_relu ? 1u : 0u;
+    uint32_t lds_bytes = 0;
+    if (int st = fill_pool_geometry(p, n, num_channel, height, width, kernel, stride, pad, dilation, ceil_mode, sk.lds_ints, lds_bytes)) return st;
+#define PPQ_LAUNCH_POOLH(ASYM, CLIP) { using Set = EpHistSet<false, false, ASYM, CLIP>; PPQ_LAUNCH_POOL(true, Set, sk); }
+    switch ((r.asym ? 2 : 0) | (r.clip ? 1 : 0)) {
+        case 0: PPQ_LAUNCH_POOLH(false, false); break;
+        case 1: PPQ_LAUNCH_POOLH(false, true); break;
+        case 2: PPQ_LAUNCH_POOLH(true, false); break;
+        default: PPQ_LAUNCH_POOLH(true, true); break;
+    }
+#undef PPQ_LAUNCH_POOLH
+    return finish_launch(what);
+}
+#undef PPQ_LAUNCH_POOL
 
 }  // extern "C"

@@ -219,10 +219,31 @@ def _epilogue_geometry(ts, bias_list):
     return None
 
 
-def bias_act_(y: torch.Tensor, bias: torch.Tensor, relu: bool) -> bool:
+def _pool_launch(y: torch.Tensor, geo, pool):
+    """``(pooled, arguments)`` of a pooled launch (``ppqhip_bias_act_pool*``): the empty ``[N, C, OH, OW]`` result and the shape /
+    window arguments behind the three pointers; None when `y` is not contiguous NCHW or ``pool = (kernel, stride, pad)`` has no
+    output.  Whether the kernel has a path for the window is its own decision (PPQHIP_NOT_FUSED)."""
+    k, s, p = (int(v) for v in pool)
+    if geo is None or not y.is_contiguous() or k < 1 or s < 1 or p < 0: return None
+    N, C, H, W = (int(v) for v in y.shape)
+    if H + 2 * p < k or W + 2 * p < k: return None
+    pooled = torch.empty((N, C, (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1), dtype=_F32, device=y.device)
+    return pooled, (y.numel(), C, H, W), (k, s, p, 1, 0)
+
+
+def bias_act_(y: torch.Tensor, bias: torch.Tensor, relu: bool, pool=None):
     """In place ``y = act(y + bias.view(1, C, 1, 1))`` with act = F.relu when `relu`, one launch; bitwise
-    ``F.relu(F.conv2d(x, w, None) + b)``'s elementwise tail.  False (nothing done) when the operands are not fusable."""
+    ``F.relu(F.conv2d(x, w, None) + b)``'s elementwise tail.  False (nothing done) when the operands are not fusable.
+    ``pool = (kernel, stride, pad)``: the same launch also pools what it stores (``ppqhip_bias_act_pool``) and the call returns
+    ``F.max_pool2d(y, kernel, stride, pad)`` bit for bit, or None when NOTHING was launched."""
     geo = _epilogue_geometry([y], [bias])
+    if pool is not None:
+        args = _pool_launch(y, geo, pool)
+        if args is None: return None
+        with _DeviceOf(y):
+            ok = _fused_or_raise(lib.ppqhip_bias_act_pool(y.data_ptr(), bias.data_ptr(), args[0].data_ptr(), *args[1],
+                                                          1 if relu else 0, *args[2], _stream()))
+        return args[0] if ok else None
     if geo is None: return False
     with _DeviceOf(y):
         _raise(lib.ppqhip_bias_act(y.data_ptr(), bias.data_ptr(), y.numel(), geo[0], geo[1], 1 if relu else 0, _stream()))
@@ -257,14 +278,23 @@ def _fused_or_raise(status: int) -> bool:
     return True
 
 
-def bias_act_stats_(y: torch.Tensor, bias: torch.Tensor, relu: bool, job) -> bool:
+def bias_act_stats_(y: torch.Tensor, bias: torch.Tensor, relu: bool, job, pool=None, store: bool = True):
     """``bias_act_`` that also folds the stored ``y`` into the slots of ``job`` (an observer's ``('minmax', slots)``) from the
     registers it is stored from (``ppqhip_bias_act_stats``).  False: NOTHING was launched (operands or job not fusable) --
-    the caller runs ``bias_act_`` and observes ``y`` as usual."""
+    the caller runs ``bias_act_`` and observes ``y`` as usual.
+    ``pool = (kernel, stride, pad)``: the pooled form (``ppqhip_bias_act_pool_stats``), which returns the pooled tensor, or None
+    when nothing was launched; with ``store=False`` it folds and pools ``act(y + bias)`` but leaves ``y`` as it was."""
     geo = _epilogue_geometry([y], [bias])
-    if geo is None or job is None: return False
+    if geo is None or job is None: return None if pool is not None else False
     try: slots = _sink_slots(job, y.device)
-    except ValueError: return False
+    except ValueError: return None if pool is not None else False
+    if pool is not None:
+        args = _pool_launch(y, geo, pool)
+        if args is None: return None
+        with _DeviceOf(y):
+            ok = _fused_or_raise(lib.ppqhip_bias_act_pool_stats(y.data_ptr(), bias.data_ptr(), args[0].data_ptr(), *args[1],
+                                                                1 if relu else 0, *args[2], slots, 1 if store else 0, _stream()))
+        return args[0] if ok else None
     with _DeviceOf(y):
         return _fused_or_raise(lib.ppqhip_bias_act_stats(y.data_ptr(), bias.data_ptr(), y.numel(), geo[0], geo[1],
                                                          1 if relu else 0, slots, _stream()))
@@ -312,15 +342,24 @@ def _hist_rule(jobs):
     return next(iter(rules)) if len(rules) == 1 else None
 
 
-def bias_act_hist_(y: torch.Tensor, bias: torch.Tensor, relu: bool, job) -> bool:
+def bias_act_hist_(y: torch.Tensor, bias: torch.Tensor, relu: bool, job, pool=None, store: bool = True):
     """``bias_act_`` that also counts the stored ``y`` into the rows of ``job`` (an observer's ``('hist_rows', rows,
     asymmetric, p0, p1, clip)``) from the registers it is stored from (``ppqhip_bias_act_hist``).  False: NOTHING was
-    launched -- the caller runs ``bias_act_`` and observes ``y`` as usual."""
+    launched -- the caller runs ``bias_act_`` and observes ``y`` as usual.
+    ``pool`` / ``store``: the pooled form (``ppqhip_bias_act_pool_hist``), as in ``bias_act_stats_``."""
     geo = _epilogue_geometry([y], [bias])
-    if geo is None or job is None: return False
+    if geo is None or job is None: return None if pool is not None else False
     try: rows, p0, p1 = _sink_rows(job, y.device)
-    except ValueError: return False
+    except ValueError: return None if pool is not None else False
     bins, asym, clip = _hist_rule([job])
+    if pool is not None:
+        args = _pool_launch(y, geo, pool)
+        if args is None: return None
+        with _DeviceOf(y):
+            ok = _fused_or_raise(lib.ppqhip_bias_act_pool_hist(y.data_ptr(), bias.data_ptr(), args[0].data_ptr(), *args[1],
+                                                               1 if relu else 0, *args[2], rows, p0, p1, bins, int(asym), int(clip),
+                                                               1 if store else 0, _stream()))
+        return args[0] if ok else None
     with _DeviceOf(y):
         return _fused_or_raise(lib.ppqhip_bias_act_hist(y.data_ptr(), bias.data_ptr(), y.numel(), geo[0], geo[1],
                                                         1 if relu else 0, rows, p0, p1, bins, int(asym), int(clip), _stream()))

@@ -177,15 +177,34 @@ def _forward(op: Operation, x: List[torch.Tensor]):
 # ------------------------------------------------------------------------------------ convolution epilogues
 class EpilogueGroup:
     """Consecutive operations whose elementwise tail runs as ONE epilogue launch (ffi.bias_act_ / ffi.bias_add_act):
-    ``P1``  Conv(bias) -> Relu;  ``P2``  Conv_a(bias) [, Conv_b(bias)] -> Add(a, b) -> Relu.
+    ``P1``  Conv(bias) -> Relu [-> MaxPool: the pooled form, ffi.bias_act_(pool=...)];
+    ``P2``  Conv_a(bias) [, Conv_b(bias)] -> Add(a, b) -> Relu.
     ``ops``: the members in execution order; ``convs``: the convolutions, Add input 0's producer first; ``add`` / ``relu``;
-    ``keep``: the variable names the planner was told to keep (graph outputs, requested outputs)."""
-    __slots__ = ('kind', 'ops', 'convs', 'add', 'relu', 'keep')
+    ``keep``: the variable names the planner was told to keep (graph outputs, requested outputs); ``pool``: the MaxPool of a
+    pooled P1, else None."""
+    __slots__ = ('kind', 'ops', 'convs', 'add', 'relu', 'keep', 'pool')
 
-    def __init__(self, kind, ops, convs, add, relu, keep=()):
+    def __init__(self, kind, ops, convs, add, relu, keep=(), pool=None):
         self.kind, self.ops, self.convs, self.add, self.relu, self.keep = kind, ops, convs, add, relu, frozenset(keep)
+        self.pool = pool
 
     def __repr__(self): return f'{self.kind}({", ".join(op.name for op in self.ops)})'
+
+
+def pool_window(op: Operation) -> Optional[tuple]:
+    """``(kernel, stride, pad)`` of a MaxPool the epilogue launch can take in (what ``_forward`` hands to F.max_pool2d), or None:
+    every attribute an int or a pair of equal ints, ``dilations`` / ``ceil_mode`` absent or at their defaults.  Whether the
+    kernel has a path for the window (kernel <= 3, ...) is decided at the launch."""
+    a = op.attributes
+
+    def square(value):
+        if isinstance(value, (list, tuple)):
+            if not 1 <= len(value) <= 2 or any(v != value[0] for v in value): return None
+            value = value[0]
+        return value if isinstance(value, int) and not isinstance(value, bool) else None
+    if 'kernel_shape' not in a or square(a.get('dilations', 1)) != 1 or a.get('ceil_mode', 0) not in (0, False): return None
+    window = tuple(square(v) for v in (a['kernel_shape'], a.get('strides', 1), a.get('pads', 0)))
+    return None if any(v is None for v in window) else window
 
 
 def _in_cfg(op, i):
@@ -205,7 +224,12 @@ def plan_epilogues(operations: List[Operation], hooks: Dict[str, object] = None,
     the kernel does NOT write -- P1: the conv output, P2: the Add output, as producer output and as consumer input --
     passes through (`passes_through(cfg)`: not activated, not delegated), and so do the configs between a conv and the
     Add (the Add must see the biased conv output itself); (4) the hooks of the members are absent or plain
-    ``observer.CalibrationHook``s that observe none of the configs of (3); (5) autograd is off."""
+    ``observer.CalibrationHook``s that observe none of the configs of (3); (5) autograd is off.
+    A P1 group takes in the MaxPool behind its Relu (the pooled form) under the same rules: consecutive; the Relu output
+    feeds only the pool and is not kept; the window is one ``pool_window`` accepts; the Relu output config and the pool's input
+    config pass through (the pool must see the Relu output itself, not a fake-quantised copy); the pool's hook is absent or
+    a plain ``CalibrationHook`` that does not observe the pool's input.  Otherwise the group is the plain P1 and the pool
+    runs on its own."""
     if grad_enabled: return []
     from .observer import CalibrationHook
     hooks = hooks or {}
@@ -237,6 +261,15 @@ def plan_epilogues(operations: List[Operation], hooks: Dict[str, object] = None,
             return None
         return r
 
+    def pool_after(relu, i):
+        if i >= len(operations): return None
+        m, out = operations[i], relu.outputs[0]
+        if (m.type != 'MaxPool' or len(m.inputs) != 1 or len(m.outputs) != 1 or m.inputs[0] is not out or not only_feeds(out, m)
+                or out.name in keep or pool_window(m) is None): return None
+        between = (_out_cfg(relu, 0), _in_cfg(m, 0))
+        if not through(*between) or not hooks_ok([m], between[1:]): return None
+        return m
+
     def try_p2(i):
         for n_conv in (2, 1):
             j = i + n_conv
@@ -266,7 +299,8 @@ def plan_epilogues(operations: List[Operation], hooks: Dict[str, object] = None,
         if relu is None: return None
         unwritten = (_out_cfg(conv, 0), _in_cfg(relu, 0))
         if not through(*unwritten) or not hooks_ok([conv, relu], unwritten): return None
-        return EpilogueGroup('P1', [conv, relu], [conv], None, relu, keep)
+        pool = pool_after(relu, i + 2)
+        return EpilogueGroup('P1', [conv, relu] + ([pool] if pool is not None else []), [conv], None, relu, keep, pool)
 
     groups, i = [], 0
     while i < len(operations):
@@ -288,20 +322,25 @@ def elidable_stores(grp: EpilogueGroup, hooks, jobs: Dict[str, tuple], recorder=
     (``grp.keep``); (3) its observer got a sink in this launch (``jobs``: member name -> job) and touches the tensor
     through that job only (``reads_only_its_job``: not a subclass, not a replaced ``observe``); (4) nothing records the
     tensors of this forward (``recorder``: ``ObservationQueue.recorder`` of ``reuse_activations``); (5) no other hook of
-    the group observes the variable (the Add's input side)."""
-    if grp.kind != 'P2' or recorder is not None or not hooks: return set()
-    add_hook = hooks.get(grp.add.name)
+    the group observes the variable (the Add's input side).
+    The Relu of a pooled P1 group stands to its MaxPool as a convolution of a P2 group stands to the Add: the pool happens
+    inside the launch (``store=False`` of ffi.bias_act_stats_ / bias_act_hist_), and the same five conditions decide."""
+    if recorder is not None or not hooks: return set()
+    if grp.kind == 'P2': producers, reader = grp.convs, grp.add
+    elif grp.pool is not None: producers, reader = [grp.relu], grp.pool
+    else: return set()
+    reader_hook = hooks.get(reader.name)
     out = set()
-    for conv in grp.convs:
-        v, hook = conv.outputs[0], hooks.get(conv.name)
-        if len(v.dest_ops) != 1 or v.dest_ops[0] is not grp.add or v.name in grp.keep: continue
-        if conv.name not in jobs or hook is None or not isinstance(conv, QuantableOperation): continue
-        obs = [hook._observer_table.get(c) for c in conv.config.output_quantization_config]
+    for op in producers:
+        v, hook = op.outputs[0], hooks.get(op.name)
+        if len(v.dest_ops) != 1 or v.dest_ops[0] is not reader or v.name in grp.keep: continue
+        if op.name not in jobs or hook is None or not isinstance(op, QuantableOperation): continue
+        obs = [hook._observer_table.get(c) for c in op.config.output_quantization_config]
         if len(obs) != 1 or obs[0] is None or not obs[0].reads_only_its_job(): continue
-        if add_hook is not None and isinstance(grp.add, QuantableOperation) and any(
-                c in add_hook._observer_table for x, c in zip(grp.add.inputs, grp.add.config.input_quantization_config) if x is v):
+        if reader_hook is not None and isinstance(reader, QuantableOperation) and any(
+                c in reader_hook._observer_table for x, c in zip(reader.inputs, reader.config.input_quantization_config) if x is v):
             continue
-        out.add(conv.name)
+        out.add(op.name)
     return out
 
 
@@ -322,7 +361,7 @@ class TorchExecutor:
         self._overrides: Dict[str, Callable] = {}     # operation name -> fn(op, raw inputs): register_operation_override
         self._takes_packed: set = set()               # ... whose fn takes input 0 in the packed form a group override handed over
         self._group_overrides: Dict[str, tuple] = {}  # first member's name -> (member names, fn): register_group_override
-        self.fuse_epilogues = True                    # conv bias [+ residual Add] + Relu in ONE launch: plan_epilogues
+        self.fuse_epilogues = True                    # conv bias [+ residual Add] + Relu [+ MaxPool] in ONE launch: plan_epilogues
         self._epilogue_cache: Dict[tuple, dict] = {}
         self.channels_last = False                    # see use_channels_last()
         for v in graph.variables.values():
@@ -635,13 +674,23 @@ class TorchExecutor:
             y = ys[conv.name]
             stored = {grp.relu.name: y}                  # member -> the tensor the launch stores as that member's output
             fed = self._epilogue_sinks(grp, hooks, stored, y)
+            # the pooled form (contiguous NCHW only): sink launch, then plain pooled launch, then the group without its pool
+            window = pool_window(grp.pool) if grp.pool is not None and not self.channels_last else None
+            pooled, elided = None, set()
             if fed is not None:
                 job = fed[0].get(grp.relu.name)
                 launch = bias_act_hist_ if job is not None and job[0] == 'hist_rows' else bias_act_stats_
-                if not launch(y, biases[conv.name], True, job): fed = None
-            if fed is None and not bias_act_(y, biases[conv.name], relu=True):
-                y.add_(biases[conv.name].view(1, -1, 1, 1)).relu_()      # PyTorch's own conv-bias step, then F.relu
-            tail, elided = {conv.name: y, grp.relu.name: y}, set()
+                if window is not None:
+                    elided = elidable_stores(grp, hooks, fed[0], fed[1].recorder)
+                    pooled = launch(y, biases[conv.name], True, job, pool=window, store=not elided)
+                    if pooled is None: elided = set()
+                if pooled is None and not launch(y, biases[conv.name], True, job): fed = None
+            if fed is None:
+                if window is not None: pooled = bias_act_(y, biases[conv.name], relu=True, pool=window)
+                if pooled is None and not bias_act_(y, biases[conv.name], relu=True):
+                    y.add_(biases[conv.name].view(1, -1, 1, 1)).relu_()      # PyTorch's own conv-bias step, then F.relu
+            tail = {conv.name: y, grp.relu.name: y}
+            if grp.pool is not None: tail[grp.pool.name] = pooled    # (None: the loop below runs the pool itself)
         else:
             conv_a = grp.convs[0]
             a = ys[conv_a.name]
@@ -672,8 +721,9 @@ class TorchExecutor:
         values: Dict[str, torch.Tensor] = {}
         for op in grp.ops:
             hook = hooks.get(op.name)
-            if op.type != 'Conv':                   # Add / Relu: their input side (the launch has computed them already)
-                self._input_side(op, [values[v.name] if v.name in values else raw_of(v) for v in op.inputs], hook)
+            if op.type != 'Conv':                   # Add / Relu / MaxPool: their input side (the launch has computed them already)
+                qin = self._input_side(op, [values[v.name] if v.name in values else raw_of(v) for v in op.inputs], hook)
+                if tail[op.name] is None: tail[op.name] = _forward(op, qin)      # the MaxPool no launch took in: F.max_pool2d
             for v, y in zip(op.outputs, self._output_side(op, tail[op.name], hook)): values[v.name] = y
         # a tensor the launch did not store still holds the convolution WITHOUT its bias.  The loop above handed it on all the
         # same: to quantize_function, whose config is INITIAL (stat_job hands out jobs for INITIAL configs only) so that it
