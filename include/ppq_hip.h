@@ -373,7 +373,9 @@ float ppqhip_mse_loss_host(const int64_t* hist, int64_t num_bins, int start, int
  *   hist + h*num_bins : int32[num_bins];  hist_scale[h], min_value[h] : float64 (device)
  * Candidate k's loss is accumulated sequentially in float exactly like hist_mse.cc; the first
  * minimum wins.  Writes best[h*4 + {0,1,2,3}] = {start, end, step, candidate index} (int32).
- * `symmetrical` selects the start==0 sweep (range.py:499-509).  `workspace`: device scratch of
+ * `symmetrical` selects the start==0 sweep (range.py:499-509).  Needs 1 <= num_bins <= 16384 and
+ * 1 <= levels = quant_max - quant_min + 1; with num_bins < levels the sweep is empty (range.py:481,
+ * 502) and the result is the min-max candidate {0, levels, 1, 0}.  `workspace`: device scratch of
  * ppqhip_mse_search_workspace_bytes(num_hist) bytes. */
 int64_t ppqhip_mse_search_workspace_bytes(int64_t num_hist);
 int ppqhip_mse_search(const int32_t* hist, int64_t num_hist, int64_t num_bins,

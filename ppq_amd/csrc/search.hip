@@ -189,8 +189,10 @@ int ppqhip_mse_search(const int32_t* hist, int64_t num_hist, int64_t num_bins, c
                       const double* min_value, int quant_min, int quant_max, int symmetrical, int32_t* best,
                       void* workspace, void* stream) {
     const int levels = quant_max - quant_min + 1;
-    if (num_hist <= 0 || num_bins <= 0 || num_bins > 16384 || levels <= 0 || num_bins / levels < 1) {
-        set_error("mse_search: need 1 <= levels <= bins <= 16384 and at least one histogram");
+    // bins < levels is legal: S == 0, the step loop of range.py:481 / :502 is empty and cell 0, the min-max candidate
+    // (0, levels, step 1), is the only one -- the decode divides by S for cell != 0 alone
+    if (num_hist <= 0 || num_bins <= 0 || num_bins > 16384 || levels <= 0) {
+        set_error("mse_search: need 1 <= levels, 1 <= bins <= 16384 and at least one histogram");
         return PPQHIP_ERR_INVALID_VALUE;
     }
     if (workspace == nullptr) { set_error("mse_search: workspace is null"); return PPQHIP_ERR_INVALID_VALUE; }
