@@ -874,6 +874,25 @@ int ppqhip_mx_conv2d_fused(const uint8_t* x_elements, const uint8_t* x_scales, i
                            int64_t o, int64_t kh, int64_t kw, int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
                            int64_t dil_h, int64_t dil_w, void* stream);
 
+/* ---- pointwise (1x1) convolution on the FP32-input MFMA (ADDED under ABI 4) ---------------------------------
+ * y[n, o, oh, ow] = sum_k w[o, k] x[n, k, oh * stride, ow * stride] (+ bias[o]) for contiguous NCHW float32 x [n, c, h, wd],
+ * w [o, c] (a [o, c, 1, 1] convolution weight as it lies) and y [n, o, ho, wo], ho = (h - 1) / stride + 1, wo likewise; no padding,
+ * no dilation, groups = 1.  One launch on `stream`, no allocation, no synchronisation (capturable into a HIP graph); NOT booked by
+ * ppqhip_prof_*.
+ * Arithmetic contract: every y[n, o, p] is the float32 fmaf chain over k = 0 .. c - 1 in ASCENDING order starting from +0,
+ *     acc = fmaf(w[o, k], x[n, k, src(p)], acc),
+ * which is what a k-ordered sequence of v_mfma_f32_32x32x2_f32 computes bit for bit.  With a bias the stored value is acc + bias[o]
+ * with one further rounding; the bias never seeds the accumulator.  There is no split-K (across waves or workgroups) and no atomic:
+ * a result's bits do not depend on tile shape, grid, batch index or position in the plane, and two calls give identical bits.  NaN,
+ * +-Inf and subnormals pass through as the chain gives them (-ffp-contract=off, default denormal mode).
+ * Refused before any launch: a null x, w or y, a negative n or a non-positive c, h, wd or o, more than 2^31 - 1 elements in x, w or
+ * y, y overlapping x, w or bias (PPQHIP_ERR_INVALID_VALUE); a stride other than 1 or 2 (PPQHIP_ERR_UNSUPPORTED).  n == 0 is
+ * PPQHIP_OK with nothing launched.  Returns PPQHIP_NOT_FUSED (nothing launched, nothing wrong) for: x, w, bias or y not aligned
+ * to 4 bytes.  Nothing else is required: 16-byte loads are used where stride is 1, h * wd and c are multiples of 4 and x and w are
+ * 16-byte aligned, dword loads otherwise (odd planes, stride 2), by the same kernel and with the same bits. */
+int ppqhip_conv1x1(const float* x, const float* w, const float* bias, float* y, int64_t n, int64_t c, int64_t h, int64_t wd,
+                   int64_t o, int64_t stride, void* stream);
+
 /* profiling aid used by bench.py: when enabled, every kernel launch made through this library
  * on this thread is bracketed by hipEvents on its own stream; ppqhip_prof_collect() synchronises
  * those events and returns, per kernel id, launches / total ms / total algorithmic bytes. */

@@ -262,6 +262,29 @@ def bias_add_act(a: torch.Tensor, bias_a: torch.Tensor, b: torch.Tensor, bias_b,
     return out
 
 
+def conv1x1(x: torch.Tensor, w: torch.Tensor, bias, stride: int = 1):
+    """``F.conv2d(x, w, bias, stride=stride)`` for a 1x1 kernel on contiguous NCHW float32 operands as ONE native launch
+    (``ppqhip_conv1x1``: FP32-input MFMA, every output the ascending-k fmaf chain from +0, then ``+ bias``; include/ppq_hip.h).
+    ``w``: ``[O, C, 1, 1]`` or ``[O, C]``; ``bias``: ``[O]`` or None.  Returns the new ``[N, O, HO, WO]`` tensor, or None when
+    NOTHING was launched because the kernel has no path for the operands (PPQHIP_NOT_FUSED); anything else that is wrong raises."""
+    _f32(x, 'x'); _f32(w, 'w')
+    if x.dim() != 4 or not x.is_contiguous() or not w.is_contiguous() or w.dim() not in (2, 4) or w.numel() != w.shape[0] * w.shape[1]:
+        raise RuntimeError(_KERNEL_FAILURE + 'conv1x1: x must be contiguous NCHW and w a contiguous [O, C, 1, 1] or [O, C]')
+    N, C, H, W = (int(v) for v in x.shape)
+    O = int(w.shape[0])
+    if int(w.shape[1]) != C or w.device != x.device: raise RuntimeError(_KERNEL_FAILURE + 'conv1x1: w does not match x')
+    if bias is not None:
+        _f32(bias, 'bias')
+        if bias.dim() != 1 or bias.numel() != O or not bias.is_contiguous() or bias.device != x.device:
+            raise RuntimeError(_KERNEL_FAILURE + 'conv1x1: bias must be a contiguous [O] vector on the device of x')
+    stride = int(stride)
+    y = torch.empty((N, O, (H - 1) // max(stride, 1) + 1, (W - 1) // max(stride, 1) + 1), dtype=_F32, device=x.device)
+    with _DeviceOf(x):
+        ok = _fused_or_raise(lib.ppqhip_conv1x1(x.data_ptr(), w.data_ptr(), 0 if bias is None else bias.data_ptr(), y.data_ptr(),
+                                                N, C, H, W, O, stride, _stream()))
+    return y if ok else None
+
+
 def _sink_slots(job, dev) -> int:
     """Device address of the slots of an observer's ``('minmax', slots)`` job (``BaseTensorObserver.stat_job``), 0 for no job.
     Raises ValueError for a job the epilogue kernels have no sink for (the caller then does not fuse)."""

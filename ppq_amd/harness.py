@@ -148,12 +148,58 @@ class BaseGraph:
         return list(self.operations.values())        # operations are created in execution order
 
 
+# ------------------------------------------------------------------------------------ native pointwise convolution
+# Where ffi.conv1x1 (ppqhip_conv1x1) runs a Conv in place of F.conv2d.  Both constants are FROZEN from the
+# per-shape measurement of tools/pointwise_conv_bench.py (profiles/r18_pointwise_conv.txt), not tuned at run time:
+POINTWISE_MIN_WORK = 3.2e9        # FLOPs (2 N Co Ci Ho Wo) of one call from which the native kernel is used: every class enabled below was
+#                                   measured faster at 3.29e9 and above (ResNet-50 at batch 32); at a quarter of it only the stride-2 ones still are
+POINTWISE_KEEP_VENDOR = frozenset({   # (Ci, Co, H, W, stride) classes measured NOT faster natively by more than the spread: F.conv2d
+    (64, 64, 56, 56, 1), (64, 256, 56, 56, 1), (256, 64, 56, 56, 1), (256, 128, 56, 56, 1), (128, 512, 28, 28, 1),
+    (512, 256, 28, 28, 1), (1024, 256, 14, 14, 1), (1024, 512, 14, 14, 1), (512, 2048, 7, 7, 1), (1024, 2048, 14, 14, 2),
+    (2048, 512, 7, 7, 1)})
+#   native in ResNet-50: (256, 1024, 14, 14, 1) x 6 layers, (512, 128, 28, 28, 1) x 3 and the down convolutions (256, 512, 56, 56, 2), (512, 1024, 28, 28, 2)
+
+
+def _square(v):
+    """The one value of an ONNX per-axis attribute given as an int or as a list of equal ints; None when the axes differ."""
+    if isinstance(v, (list, tuple)):
+        return int(v[0]) if len(v) > 0 and all(int(e) == int(v[0]) for e in v) else None
+    return int(v)
+
+
+def pointwise_eligible(x, w, attributes: dict, min_work: float) -> bool:
+    """Whether ``Conv(x, w[, bias])`` with `attributes` is one the native pointwise kernel takes: a 1x1 kernel, no padding, no
+    dilation, one group, a square stride of 1 or 2, float32 contiguous-NCHW operands on the GPU, no autograd, at least
+    `min_work` FLOPs and a shape class that is not in POINTWISE_KEEP_VENDOR.  Shapes, layout and attributes only: the bias plays no
+    part, so the fused path (convolution without bias, the epilogue adds it) and the unfused one (with bias) decide alike."""
+    a = attributes or {}
+    if not (isinstance(x, torch.Tensor) and isinstance(w, torch.Tensor) and x.dim() == 4 and w.dim() == 4): return False
+    if tuple(w.shape[2:]) != (1, 1) or w.shape[1] != x.shape[1]: return False
+    if _square(a.get('pads', 0)) != 0 or _square(a.get('dilations', 1)) != 1 or a.get('group', 1) != 1: return False
+    stride = _square(a.get('strides', 1))
+    if stride not in (1, 2): return False
+    if not (x.is_cuda and w.is_cuda and x.dtype is torch.float32 and w.dtype is torch.float32): return False
+    if not (x.is_contiguous() and w.is_contiguous()) or x.numel() == 0: return False
+    if torch.is_grad_enabled() or x.requires_grad or w.requires_grad: return False
+    n, c, h, wd = (int(v) for v in x.shape)
+    o = int(w.shape[0])
+    if (c, o, h, wd, stride) in POINTWISE_KEEP_VENDOR: return False
+    return 2.0 * n * o * c * ((h - 1) // stride + 1) * ((wd - 1) // stride + 1) >= min_work
+
+
+def _conv(x, w, bias, a: dict, native_min_work=None):
+    """The executor's convolution: ffi.conv1x1 where ``pointwise_eligible`` (`native_min_work` None: never), else F.conv2d."""
+    if native_min_work is not None and pointwise_eligible(x, w, a, native_min_work):
+        from .ffi import conv1x1
+        y = conv1x1(x, w, bias, _square(a.get('strides', 1)))
+        if y is not None: return y                    # (None: PPQHIP_NOT_FUSED, the kernel has no path for these pointers)
+    return F.conv2d(x, w, bias, stride=a.get('strides', 1), padding=a.get('pads', 0), groups=a.get('group', 1))
+
+
 # ------------------------------------------------------------------------------------ op library
-def _forward(op: Operation, x: List[torch.Tensor]):
+def _forward(op: Operation, x: List[torch.Tensor], native_min_work=None):
     t, a = op.type, op.attributes
-    if t == 'Conv':
-        return F.conv2d(x[0], x[1], x[2] if len(x) > 2 else None, stride=a.get('strides', 1),
-                        padding=a.get('pads', 0), groups=a.get('group', 1))
+    if t == 'Conv': return _conv(x[0], x[1], x[2] if len(x) > 2 else None, a, native_min_work)
     if t == 'Gemm': return F.linear(x[0], x[1], x[2] if len(x) > 2 else None)
     if t == 'MatMul': return torch.matmul(x[0], x[1])
     if t == 'Relu': return F.relu(x[0])
@@ -364,6 +410,8 @@ class TorchExecutor:
         self.fuse_epilogues = True                    # conv bias [+ residual Add] + Relu [+ MaxPool] in ONE launch: plan_epilogues
         self._epilogue_cache: Dict[tuple, dict] = {}
         self.channels_last = False                    # see use_channels_last()
+        self.native_pointwise_conv = True             # eligible 1x1 convolutions on ffi.conv1x1 (pointwise_eligible); else F.conv2d
+        self.pointwise_min_work = POINTWISE_MIN_WORK  # FLOPs per call from which they are
         for v in graph.variables.values():
             if v.is_parameter and v.value is not None: v.value = v.value.to(device)
 
@@ -378,6 +426,10 @@ class TorchExecutor:
             if v.is_parameter and isinstance(v.value, torch.Tensor) and v.value.dim() == 4:
                 v.value = v.value.contiguous(memory_format=torch.channels_last)
         return self
+
+    def _native_min_work(self):
+        """What ``_conv`` takes as `native_min_work`: None (F.conv2d throughout) with the flag off or in channels-last."""
+        return self.pointwise_min_work if self.native_pointwise_conv and not self.channels_last else None
 
     def _place(self, value: torch.Tensor) -> torch.Tensor:
         value = value.to(self._device)
@@ -511,7 +563,11 @@ class TorchExecutor:
         what the group overrides of this forward handed over, where an override may take it (``_override_inputs``)."""
         override = self._overrides.get(op.name) if hook is None else None        # a hooked operation runs the simulation
         if override is not None: outs = override(op, self._override_inputs(op, raw_in, packed))
-        else: outs = _forward(op, self._input_side(op, raw_in, hook))
+        else:
+            qin, native = self._input_side(op, raw_in, hook), self._native_min_work()
+            # (the flag travels only with a convolution that takes it: everything else calls _forward as it always did)
+            if native is not None and op.type == 'Conv' and pointwise_eligible(qin[0], qin[1], op.attributes, native): outs = _forward(op, qin, native)
+            else: outs = _forward(op, qin)
         return self._output_side(op, outs, hook)
 
     def _walk(self, operations: List[Operation], hooks, output_names: List[str], read: Callable, write: Callable,
@@ -666,8 +722,7 @@ class TorchExecutor:
         for conv in grp.ops[:len(grp.convs)]:        # the convolutions, in execution order
             qin = self._input_side(conv, [raw_of(v) for v in conv.inputs], hooks.get(conv.name))
             a = conv.attributes
-            ys[conv.name] = F.conv2d(qin[0], qin[1], None, stride=a.get('strides', 1), padding=a.get('pads', 0),
-                                     groups=a.get('group', 1))
+            ys[conv.name] = _conv(qin[0], qin[1], None, a, self._native_min_work())
             biases[conv.name] = qin[2]
         if grp.kind == 'P1':
             conv = grp.convs[0]
