@@ -42,6 +42,11 @@
 // Relu store can be left out too (store_relu = 0): its readers, the observer and the pool, are both inside the launch.
 // Contiguous NCHW, H * W % 4 == 0, a plane that fits the LDS, kernel <= 3, dilation 1, floor mode; PPQHIP_NOT_FUSED otherwise.
 // Measurements: DESIGN.md section 6, profiles/r17_stem_pool.txt.
+// Host side: the eleven entry points at the end of this file keep their C signatures, and each only fills one call record
+// (EpCall: form, operands, geometry, relu, elide, the kind of sink with its destinations, the pool window) for run_epilogue.
+// That one function holds every check, in the order that decides which message wins, every PPQHIP_NOT_FUSED decision, the
+// filling of EpArgs / EpPoolArgs / the sinks and the choice of the launch.  A new sink adds fields to the record and a branch
+// in run_epilogue, not a new family of entry points.
 #include "channel_axis.hpp"
 #include "common.hpp"
 #include "hist_bin.hpp"
@@ -185,9 +190,35 @@ bool fill_vector_geometry(EpArgs& p, int64_t n, int64_t C, int64_t epc) {
     return g.plane != 0;
 }
 
+// The call record: everything any of the entry points at the end of this file can say, for run_epilogue (zero: not given).
+enum EpForm { kEpSingle, kEpResidual, kEpPooled };      // bias_act, bias_add_act, bias_act_pool (and their _stats / _hist)
+enum EpSinkKind { kEpNoSink, kEpMinMaxSink, kEpHistSink };
+struct EpCall {
+    const char* what;                  // the entry point's name, in front of its messages
+    EpForm form;
+    float* a;                          // kEpSingle, kEpPooled: y
+    const float* bias_a;
+    float* b;                          // b, bias_b, out: kEpResidual only
+    const float* bias_b;
+    float* out;
+    int64_t n, num_channel, elem_per_channel;
+    int relu, elide;
+    EpSinkKind sink;
+    void* dst[3];                      // per stored tensor (a, b, out): float slots (min/max) or int32_t rows (histogram)
+    float p0[3], p1[3];                // histogram: the bin rule's parameters of each sink ...
+    int64_t num_bins;                  // ... and what the sinks of one launch share
+    int asymmetric, clip_outliers;
+    float* pool;                       // kEpPooled only, from here on: height * width stands for elem_per_channel (not read)
+    int64_t height, width;
+    int kernel, stride, pad, dilation, ceil_mode, store_relu;
+
+    bool aligned() const { return aligned16(a) && (form != kEpResidual || (aligned16(b) && aligned16(out))); }
+};
+
 template <bool RESID, bool BIAS_B, bool RELU>
-void launch_epilogue(EpArgs p, int64_t n, int64_t C, int64_t epc, bool aligned, hipStream_t st) {
-    if (!aligned || n < 4) {
+void launch_epilogue(EpArgs p, const EpCall& c, hipStream_t st) {
+    const int64_t n = c.n, C = c.num_channel, epc = c.elem_per_channel;
+    if (!c.aligned() || n < 4) {
         p.nvec = 0; p.tail = 0; p.ntail = (int)n;
         p.epc = make_fastdiv((uint32_t)epc); p.nc = make_fastdiv((uint32_t)C);
         hipLaunchKernelGGL((epilogue_scalar_kernel<RESID, BIAS_B, RELU>), dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, st, p);
@@ -450,14 +481,11 @@ void epilogue_stats_kernel(EpArgs p, typename SINKS::Args sk) {
 // takes the booked kernel with the most device time as THE kernel of the calibration pass -- the end-of-forward statistics
 // launch -- and an epilogue id would take that place (tests/test_gpu_calibration.py pins the three names it may be).  The
 // launches are timed from kernel traces instead (profiles/r15_epilogue_hist.txt).
-// The statistics launch, or the reason there is none: PPQHIP_NOT_FUSED (nothing was launched, nothing is wrong: the caller
-// runs the plain epilogue and leaves the statistic to the observers' own launch) for what the kernel has no path for.
+// The statistics launch (run_epilogue has seen to it that the kernel has a path: a sink, aligned pointers, n >= 4).
 template <bool RESID, bool BIAS_B>
-int launch_epilogue_stats(EpArgs p, int64_t n, int64_t C, int64_t epc, int relu, bool aligned, EpMinMaxSinks sk, const char* what,
-                          hipStream_t st) {
-    if ((!sk.slots[0] && !sk.slots[1] && !sk.slots[2]) || !aligned || n < 4) return PPQHIP_NOT_FUSED;
-    const bool plane = fill_vector_geometry(p, n, C, epc);
-    const bool small = n <= kEpSmallElems;                               // the plain launch's rule
+int launch_epilogue_stats(EpArgs p, const EpCall& c, EpMinMaxSinks sk, hipStream_t st) {
+    const bool plane = fill_vector_geometry(p, c.n, c.num_channel, c.elem_per_channel);
+    const bool small = c.n <= kEpSmallElems;                             // the plain launch's rule
     const uint32_t tile = (uint32_t)kEpStatBlock * (small ? kEpSmallU : kEpTileU), tiles = (p.nvec + tile - 1) / tile;
     const uint32_t cap = (uint32_t)(num_cu() * kEpStatWgPerCu);          // one slot per workgroup
     const uint32_t grid = tiles < cap ? tiles : cap;
@@ -465,7 +493,7 @@ int launch_epilogue_stats(EpArgs p, int64_t n, int64_t C, int64_t epc, int relu,
 #define PPQ_LAUNCH_EPS(U, RELU, PLANE)                                                                                    \
     hipLaunchKernelGGL((epilogue_stats_kernel<U, RESID, BIAS_B, RELU, PLANE, Set>), dim3(grid), dim3(kEpStatBlock),         \
                        32 * sizeof(float), st, p, sk)
-    switch ((small ? 0 : 4) | (relu ? 2 : 0) | (plane ? 1 : 0)) {
+    switch ((small ? 0 : 4) | (c.relu ? 2 : 0) | (plane ? 1 : 0)) {
         case 0: PPQ_LAUNCH_EPS(kEpSmallU, false, false); break;
         case 1: PPQ_LAUNCH_EPS(kEpSmallU, false, true); break;
         case 2: PPQ_LAUNCH_EPS(kEpSmallU, true, false); break;
@@ -476,7 +504,7 @@ int launch_epilogue_stats(EpArgs p, int64_t n, int64_t C, int64_t epc, int relu,
         default: PPQ_LAUNCH_EPS(kEpTileU, true, true); break;
     }
 #undef PPQ_LAUNCH_EPS
-    return finish_launch(what);
+    return finish_launch(c.what);
 }
 
 // The histogram sinks' launch.  Instantiated: the two-float4 tile with ReLU only (3 operand forms x PLANE x ASYM x CLIP =
@@ -494,19 +522,30 @@ constexpr uint32_t kEpHistMinTiles = 2;            // tiles (32 KB per operand) 
                                                    // because the observers' rows / slots accumulators have one row per workgroup
                                                    // of exactly that grid (hist_rows = 2 per CU); the histogram sinks reach
                                                    // 0.62 of 8 TB/s with it, and another shape may do better
-struct EpHistRule { int bins, asym, clip; };
 
-template <bool RESID, bool BIAS_B>
-int launch_epilogue_hist(EpArgs p, int64_t n, int64_t C, int64_t epc, int relu, bool aligned, EpHistSinks sk, EpHistRule r,
-                         const char* what, hipStream_t st) {
-    uint32_t ints = 0;
+// The histogram sinks of a call (1 <= num_bins < 2^31), pooled or not: (p0, p1) of a sink as the observers' own launches take
+// them, sym -> (0, hist_scale), asym -> (min, (max - min) / bins), and the counters' places in LDS.  lds_ints == 0: the call
+// has no sink, or its counters do not fit kEpHistLdsInts -- there is no launch for it.
+EpHistSinks hist_sinks(const EpCall& c) {
+    EpHistSinks sk{};
+    sk.bins = (int)c.num_bins;
+    uint64_t ints = 0;
     for (int k = 0; k < 3; k++) {
-        sk.lds_off[k] = ints;
-        if (sk.rows[k]) ints += (uint32_t)r.bins;
+        sk.rows[k] = static_cast<int*>(c.dst[k]);
+        if (c.asymmetric) { sk.a0[k] = c.p0[k]; sk.hs[k] = (c.p1[k] - c.p0[k]) / (float)sk.bins; }       // sort.cu:123
+        else { sk.a0[k] = 0.f; sk.hs[k] = c.p0[k]; }
+        sk.lds_off[k] = (uint32_t)ints;
+        if (sk.rows[k]) ints += (uint64_t)c.num_bins;
     }
-    sk.lds_ints = ints; sk.bins = r.bins;
-    if (ints == 0 || ints > kEpHistLdsInts || !aligned || n <= kEpSmallElems || !relu) return PPQHIP_NOT_FUSED;
-    const bool plane = fill_vector_geometry(p, n, C, epc);
+    sk.lds_ints = ints > kEpHistLdsInts ? 0u : (uint32_t)ints;
+    return sk;
+}
+
+// (run_epilogue has seen to it that the kernel has a path: counters that fit, aligned pointers, n > kEpSmallElems, ReLU)
+template <bool RESID, bool BIAS_B>
+int launch_epilogue_hist(EpArgs p, const EpCall& c, EpHistSinks sk, hipStream_t st) {
+    const uint32_t ints = sk.lds_ints;
+    const bool plane = fill_vector_geometry(p, c.n, c.num_channel, c.elem_per_channel);
     const uint32_t tile = (uint32_t)kEpStatBlock * kEpTileU, tiles = (p.nvec + tile - 1) / tile;
     const uint32_t cap = (uint32_t)(num_cu() * kEpStatWgPerCu);          // one row per workgroup
     uint32_t grid = tiles / kEpHistMinTiles;                             // (n > kEpSmallElems: at least 128)
@@ -514,7 +553,7 @@ int launch_epilogue_hist(EpArgs p, int64_t n, int64_t C, int64_t epc, int relu, 
 #define PPQ_LAUNCH_EPH(PLANE, ASYM, CLIP)                                                                                 \
     hipLaunchKernelGGL((epilogue_stats_kernel<kEpTileU, RESID, BIAS_B, true, PLANE, EpHistSet<RESID, BIAS_B, ASYM, CLIP>>),  \
                        dim3(grid), dim3(kEpStatBlock), ints * sizeof(int), st, p, sk)
-    switch ((plane ? 4 : 0) | (r.asym ? 2 : 0) | (r.clip ? 1 : 0)) {
+    switch ((plane ? 4 : 0) | (c.asymmetric ? 2 : 0) | (c.clip_outliers ? 1 : 0)) {
         case 0: PPQ_LAUNCH_EPH(false, false, false); break;
         case 1: PPQ_LAUNCH_EPH(false, false, true); break;
         case 2: PPQ_LAUNCH_EPH(false, true, false); break;
@@ -525,24 +564,19 @@ int launch_epilogue_hist(EpArgs p, int64_t n, int64_t C, int64_t epc, int relu, 
         default: PPQ_LAUNCH_EPH(true, true, true); break;
     }
 #undef PPQ_LAUNCH_EPH
-    return finish_launch(what);
+    return finish_launch(c.what);
 }
 
-// (p0, p1) of a sink as the observers' own launches take them: sym -> (0, hist_scale), asym -> (min, (max - min) / bins)
-void set_hist_rule(EpHistSinks& sk, int k, int32_t* rows, float p0, float p1, const EpHistRule& r) {
-    sk.rows[k] = rows;
-    if (r.asym) { sk.a0[k] = p0; sk.hs[k] = (p1 - p0) / (float)r.bins; }       // sort.cu:123
-    else { sk.a0[k] = 0.f; sk.hs[k] = p0; }
-}
-
-// An elided tensor must be one the launch computes AND hands to a sink: otherwise its values would be lost.
-int validate_elide(const char* what, int elide, bool sink_a, bool sink_b, bool has_bias_b) {
-    if (elide & ~(int)(kElideA | kElideB)) { set_error("%s: elide has unknown bits", what); return PPQHIP_ERR_INVALID_VALUE; }
-    if (((elide & (int)kElideA) && !sink_a) || ((elide & (int)kElideB) && !(sink_b && has_bias_b))) {
-        set_error("%s: a tensor that is not stored needs a sink", what); return PPQHIP_ERR_INVALID_VALUE;
-    }
-    return PPQHIP_OK;
-}
+// The operand forms <RESID, BIAS_B> the three launches are instantiated for, as run_epilogue picks them:
+// [0] <0, 0> the single tensor, [1] <1, 1> the residual with bias_b, [2] <1, 0> without; plain launches also by [!relu].
+constexpr void (*kEpLaunch[3][2])(EpArgs, const EpCall&, hipStream_t) = {
+    {launch_epilogue<false, false, true>, launch_epilogue<false, false, false>},
+    {launch_epilogue<true, true, true>, launch_epilogue<true, true, false>},
+    {launch_epilogue<true, false, true>, launch_epilogue<true, false, false>}};
+constexpr int (*kEpStatsLaunch[3])(EpArgs, const EpCall&, EpMinMaxSinks, hipStream_t) = {
+    launch_epilogue_stats<false, false>, launch_epilogue_stats<true, true>, launch_epilogue_stats<true, false>};
+constexpr int (*kEpHistLaunch[3])(EpArgs, const EpCall&, EpHistSinks, hipStream_t) = {
+    launch_epilogue_hist<false, false>, launch_epilogue_hist<true, true>, launch_epilogue_hist<true, false>};
 
 // ---- the pooled form: Conv(bias) -> Relu -> MaxPool in one launch ------------------------------------------------------
 // pool = MaxPool_{k,s,p}(act(y + bias[c])) over contiguous NCHW.  The launch has the statistics kernels' shape (at most
@@ -721,47 +755,119 @@ void epilogue_pool_kernel(EpPoolArgs p, typename SINKS::Args sk) {
     sinks.finish(sk, blockIdx.x, lds);
 }
 
-// The shape checks of the pooled entry points: PPQHIP_OK with `p` filled and the dynamic LDS size in `lds_bytes`, or
-// PPQHIP_NOT_FUSED for what the kernel has no exact path for.  `sink_ints`: LDS ints the sinks own in front of the plane.
-int fill_pool_geometry(EpPoolArgs& p, int64_t n, int64_t C, int64_t H, int64_t W, int kernel, int stride, int pad, int dilation,
-                       int ceil_mode, uint32_t sink_ints, uint32_t& lds_bytes) {
-    if (kernel < 1 || kernel > kEpPoolMaxKernel || stride < 1 || pad < 0 || 2 * pad > kernel || dilation != 1 || ceil_mode != 0)
-        return PPQHIP_NOT_FUSED;                                                 // (PyTorch refuses a pad above kernel / 2 itself)
+// The shape checks of the pooled form: the dynamic LDS size, with `p` filled, or 0 for what the kernel has no exact path for.
+// On entry p.sink_ints holds the LDS ints the sinks own in front of the plane.
+uint32_t fill_pool_geometry(EpPoolArgs& p, const EpCall& c) {
+    const int64_t H = c.height, W = c.width;
+    const int kernel = c.kernel, stride = c.stride, pad = c.pad;
+    if (kernel < 1 || kernel > kEpPoolMaxKernel || stride < 1 || pad < 0 || 2 * pad > kernel || c.dilation != 1 || c.ceil_mode != 0)
+        return 0;                                                                // (PyTorch refuses a pad above kernel / 2 itself)
     const int64_t hw = H * W;
-    if (hw % 4 != 0 || H + 2 * pad < kernel || W + 2 * pad < kernel || !aligned16(p.y) || !aligned16(p.pool)) return PPQHIP_NOT_FUSED;
-    const int64_t OH = (H + 2 * pad - kernel) / stride + 1, OW = (W + 2 * pad - kernel) / stride + 1, planes = n / hw;
-    if (planes * OH * OW > 0x7fffffffLL) return PPQHIP_NOT_FUSED;
-    sink_ints = (sink_ints + 3u) & ~3u;                                          // the plane starts on a 16-B boundary
-    const int64_t bytes = (int64_t)sink_ints * 4 + hw * 4 + kEpPoolStageBytes;
-    if (bytes > (int64_t)kEpPoolMaxLds) return PPQHIP_NOT_FUSED;
-    lds_bytes = (uint32_t)bytes;
+    if (hw % 4 != 0 || H + 2 * pad < kernel || W + 2 * pad < kernel || !aligned16(p.y) || !aligned16(p.pool)) return 0;
+    const int64_t OH = (H + 2 * pad - kernel) / stride + 1, OW = (W + 2 * pad - kernel) / stride + 1, planes = c.n / hw;
+    if (planes * OH * OW > 0x7fffffffLL) return 0;
+    p.sink_ints = (p.sink_ints + 3u) & ~3u;                                      // the plane starts on a 16-B boundary
+    const int64_t bytes = (int64_t)p.sink_ints * 4 + hw * 4 + kEpPoolStageBytes;
+    if (bytes > (int64_t)kEpPoolMaxLds) return 0;
     p.planes = (uint32_t)planes; p.hw4 = (uint32_t)(hw / 4);
     p.H = (uint32_t)H; p.W = (uint32_t)W; p.ohw = (uint32_t)(OH * OW);
     p.k = kernel; p.s = stride; p.pad = pad;
-    p.nc = make_fastdiv((uint32_t)C); p.ow = make_fastdiv((uint32_t)OW);
+    p.nc = make_fastdiv((uint32_t)c.num_channel); p.ow = make_fastdiv((uint32_t)OW);
     p.vec = p.ohw % 4u == 0 ? 1u : 0u;
-    p.sink_ints = sink_ints;
-    return PPQHIP_OK;
+    return (uint32_t)bytes;
 }
 
-uint32_t pool_grid(const EpPoolArgs& p) {
+// The pooled launch with the sinks of c.sink, or PPQHIP_NOT_FUSED for a window or plane without a path: the one such decision
+// outside run_epilogue, because it falls out of the LDS layout that only this launch has.
+int launch_epilogue_pool(EpPoolArgs p, const EpCall& c, const EpMinMaxSinks& mm, const EpHistSinks& hs, hipStream_t st) {
+    const uint32_t lds_bytes = fill_pool_geometry(p, c);
+    if (lds_bytes == 0) return PPQHIP_NOT_FUSED;
     const uint32_t cap = (uint32_t)(num_cu() * kEpStatWgPerCu);                  // one slot / row per workgroup
-    return p.planes < cap ? p.planes : cap;
-}
-
-int validate_pool(const char* what, const float* y, const float* bias, const float* pool, int64_t n, int64_t C, int64_t H, int64_t W) {
-    if (H <= 0 || W <= 0 || H > 0x7fffffffLL || W > 0x7fffffffLL || H * W > 0x7fffffffLL) {
-        set_error("%s: the plane %lld x %lld is empty or too large", what, (long long)H, (long long)W); return PPQHIP_ERR_INVALID_VALUE;
+    const uint32_t grid = p.planes < cap ? p.planes : cap;
+#define PPQ_LAUNCH_POOL(RELU, SET, SK)                                                                                    \
+    hipLaunchKernelGGL((epilogue_pool_kernel<kEpTileU, RELU, SET>), dim3(grid), dim3(kEpStatBlock), lds_bytes, st, p, SK)
+#define PPQ_LAUNCH_POOLH(ASYM, CLIP) { using Set = EpHistSet<false, false, ASYM, CLIP>; PPQ_LAUNCH_POOL(true, Set, hs); }
+    if (c.sink == kEpNoSink) {
+        const EpNoSinks::Args none{};
+        if (c.relu) PPQ_LAUNCH_POOL(true, EpNoSinks, none); else PPQ_LAUNCH_POOL(false, EpNoSinks, none);
+    } else if (c.sink == kEpMinMaxSink) {
+        using Set = EpMinMaxSet<false, false>;
+        if (c.relu) PPQ_LAUNCH_POOL(true, Set, mm); else PPQ_LAUNCH_POOL(false, Set, mm);
+    } else {
+        switch ((c.asymmetric ? 2 : 0) | (c.clip_outliers ? 1 : 0)) {            // (ReLU only, like the unpooled histogram launch)
+            case 0: PPQ_LAUNCH_POOLH(false, false); break;
+            case 1: PPQ_LAUNCH_POOLH(false, true); break;
+            case 2: PPQ_LAUNCH_POOLH(true, false); break;
+            default: PPQ_LAUNCH_POOLH(true, true); break;
+        }
     }
-    if (int st = validate_channel_axis(what, n, C, H * W)) return st;
-    if (!y || !bias || !pool) { set_error("%s: null pointer", what); return PPQHIP_ERR_INVALID_VALUE; }
-    return PPQHIP_OK;
+#undef PPQ_LAUNCH_POOLH
+#undef PPQ_LAUNCH_POOL
+    return finish_launch(c.what);
 }
 
-// an elided store (store_relu == 0) loses the Relu tensor unless a sink takes it
-int validate_pool_store(const char* what, int store_relu, bool sink) {
-    if (!store_relu && !sink) { set_error("%s: a tensor that is not stored needs a sink", what); return PPQHIP_ERR_INVALID_VALUE; }
-    return PPQHIP_OK;
+int refuse(const char* what, const char* why) {
+    set_error("%s: %s", what, why);
+    return PPQHIP_ERR_INVALID_VALUE;
+}
+
+// Every entry point below: validation (the order is the precedence of the messages, pinned by
+// tests/test_host_epilogue_refusals.py), then the reasons to launch nothing -- PPQHIP_NOT_FUSED: nothing is wrong, the caller runs
+// the plain epilogue and leaves the statistic to the observers' own launch -- then the kernels' structs and the launch.
+int run_epilogue(const EpCall& c, hipStream_t st) {
+    const bool resid = c.form == kEpResidual, pooled = c.form == kEpPooled;
+    const bool minmax = c.sink == kEpMinMaxSink, hist = c.sink == kEpHistSink;
+    int64_t epc = c.elem_per_channel;
+    if (pooled) {
+        // The plane comes before the channel axis, unlike every other check of a shape here: height * width IS the axis'
+        // elem_per_channel, and the product must be known not to overflow before the axis is checked with it.
+        if (c.height <= 0 || c.width <= 0 || c.height > 0x7fffffffLL || c.width > 0x7fffffffLL || c.height * c.width > 0x7fffffffLL) {
+            set_error("%s: the plane %lld x %lld is empty or too large", c.what, (long long)c.height, (long long)c.width);
+            return PPQHIP_ERR_INVALID_VALUE;
+        }
+        epc = c.height * c.width;
+    }
+    if (int s = validate_channel_axis(c.what, c.n, c.num_channel, epc)) return s;
+    if (!c.a || !c.bias_a || (resid && (!c.b || !c.out)) || (pooled && !c.pool)) return refuse(c.what, "null pointer");
+    if (!c.bias_b && c.dst[1]) return refuse(c.what, "without bias_b, b is only read: it has no sink");
+    if (hist && (c.num_bins <= 0 || c.num_bins > 0x7fffffffLL)) return refuse(c.what, "histogram is empty or too large");
+    // An elided tensor must be one the launch computes AND hands to a sink: otherwise its values would be lost.  The pooled
+    // form's store_relu == 0 is the elision of its one tensor: its readers, the observer and the pool, are inside the launch.
+    const int elide = pooled ? (c.store_relu ? 0 : (int)kElideA) : c.elide;
+    if (elide & ~(int)(kElideA | kElideB)) return refuse(c.what, "elide has unknown bits");
+    if (((elide & (int)kElideA) && !c.dst[0]) || ((elide & (int)kElideB) && !(c.dst[1] && c.bias_b)))
+        return refuse(c.what, "a tensor that is not stored needs a sink");
+    // a workgroup reads its row of every sink ahead and writes it back at the end: two sinks on one accumulator would lose counts
+    if (hist && ((c.dst[0] && (c.dst[0] == c.dst[1] || c.dst[0] == c.dst[2])) || (c.dst[1] && c.dst[1] == c.dst[2])))
+        return refuse(c.what, "two sinks share one rows accumulator");
+
+    EpMinMaxSinks mm{};
+    EpHistSinks hs{};
+    if (minmax) {
+        for (int k = 0; k < 3; k++) mm.slots[k] = static_cast<float*>(c.dst[k]);
+        if (!mm.slots[0] && !mm.slots[1] && !mm.slots[2]) return PPQHIP_NOT_FUSED;
+    }
+    if (hist) {
+        hs = hist_sinks(c);
+        if (hs.lds_ints == 0 || !c.relu) return PPQHIP_NOT_FUSED;                // (why ReLU only: above launch_epilogue_hist)
+    }
+    if (pooled) {
+        EpPoolArgs p{};
+        p.y = c.a; p.bias = c.bias_a; p.pool = c.pool;
+        p.store = (elide & (int)kElideA) ? 0u : 1u;
+        p.sink_ints = hist ? hs.lds_ints : minmax ? 32u : 0u;                    // (min/max: the 32 floats of its block fold)
+        return launch_epilogue_pool(p, c, mm, hs, st);
+    }
+    if (minmax && (!c.aligned() || c.n < 4)) return PPQHIP_NOT_FUSED;            // the sinks' kernels are vector kernels only
+    if (hist && (!c.aligned() || c.n <= kEpSmallElems)) return PPQHIP_NOT_FUSED; // (small tensors: above launch_epilogue_hist)
+
+    EpArgs p{};
+    p.a = c.a; p.bias_a = c.bias_a; p.b = c.b; p.bias_b = c.bias_b; p.out = c.out; p.elide = (uint32_t)elide;
+    const int form = !resid ? 0 : c.bias_b ? 1 : 2;
+    if (minmax) return kEpStatsLaunch[form](p, c, mm, st);
+    if (hist) return kEpHistLaunch[form](p, c, hs, st);
+    kEpLaunch[form][c.relu ? 0 : 1](p, c, st);
+    return finish_launch(c.what);
 }
 
 }  // namespace
@@ -769,189 +875,89 @@ int validate_pool_store(const char* what, int store_relu, bool sink) {
 
 using namespace ppqhip;
 
+// Each entry point fills the call record -- its leading fields in the order of EpCall, `what` .. `dst` (.. `clip_outliers` with
+// histogram sinks) -- and runs it.
 extern "C" {
 
 int ppqhip_bias_act(float* y, const float* bias, int64_t n, int64_t num_channel, int64_t elem_per_channel, int relu,
                     void* stream) {
-    if (int st = validate_channel_axis("bias_act", n, num_channel, elem_per_channel)) return st;
-    if (!y || !bias) { set_error("bias_act: null pointer"); return PPQHIP_ERR_INVALID_VALUE; }
-    hipStream_t s = (hipStream_t)stream;
-    EpArgs p{};
-    p.a = y; p.bias_a = bias;
-    const bool aligned = aligned16(y);
-    if (relu) launch_epilogue<false, false, true>(p, n, num_channel, elem_per_channel, aligned, s);
-    else launch_epilogue<false, false, false>(p, n, num_channel, elem_per_channel, aligned, s);
-    return finish_launch("bias_act");
+    const EpCall c{"bias_act", kEpSingle, y, bias, nullptr, nullptr, nullptr, n, num_channel, elem_per_channel, relu};
+    return run_epilogue(c, (hipStream_t)stream);
 }
 
 int ppqhip_bias_add_act(float* a, const float* bias_a, float* b, const float* bias_b, float* out, int64_t n,
                         int64_t num_channel, int64_t elem_per_channel, int relu, void* stream) {
-    if (int st = validate_channel_axis("bias_add_act", n, num_channel, elem_per_channel)) return st;
-    if (!a || !bias_a || !b || !out) { set_error("bias_add_act: null pointer"); return PPQHIP_ERR_INVALID_VALUE; }
-    hipStream_t s = (hipStream_t)stream;
-    EpArgs p{};
-    p.a = a; p.bias_a = bias_a; p.b = b; p.bias_b = bias_b; p.out = out;
-    const bool aligned = aligned16(a) && aligned16(b) && aligned16(out);
-    if (bias_b) {
-        if (relu) launch_epilogue<true, true, true>(p, n, num_channel, elem_per_channel, aligned, s);
-        else launch_epilogue<true, true, false>(p, n, num_channel, elem_per_channel, aligned, s);
-    } else {
-        if (relu) launch_epilogue<true, false, true>(p, n, num_channel, elem_per_channel, aligned, s);
-        else launch_epilogue<true, false, false>(p, n, num_channel, elem_per_channel, aligned, s);
-    }
-    return finish_launch("bias_add_act");
+    const EpCall c{"bias_add_act", kEpResidual, a, bias_a, b, bias_b, out, n, num_channel, elem_per_channel, relu};
+    return run_epilogue(c, (hipStream_t)stream);
 }
 
 int ppqhip_bias_act_stats(float* y, const float* bias, int64_t n, int64_t num_channel, int64_t elem_per_channel, int relu,
                           float* slots_y, void* stream) {
-    if (int st = validate_channel_axis("bias_act_stats", n, num_channel, elem_per_channel)) return st;
-    if (!y || !bias) { set_error("bias_act_stats: null pointer"); return PPQHIP_ERR_INVALID_VALUE; }
-    EpArgs p{};
-    p.a = y; p.bias_a = bias;
-    return launch_epilogue_stats<false, false>(p, n, num_channel, elem_per_channel, relu, aligned16(y), EpMinMaxSinks{{slots_y, nullptr, nullptr}},
-                                               "bias_act_stats", (hipStream_t)stream);
-}
-
-static int bias_add_act_stats_impl(const char* what, float* a, const float* bias_a, float* b, const float* bias_b, float* out,
-                                   int64_t n, int64_t num_channel, int64_t elem_per_channel, int relu, float* slots_a,
-                                   float* slots_b, float* slots_out, int elide, void* stream) {
-    if (int st = validate_channel_axis(what, n, num_channel, elem_per_channel)) return st;
-    if (!a || !bias_a || !b || !out) { set_error("%s: null pointer", what); return PPQHIP_ERR_INVALID_VALUE; }
-    if (!bias_b && slots_b) { set_error("%s: without bias_b, b is only read: it has no sink", what); return PPQHIP_ERR_INVALID_VALUE; }
-    if (int st = validate_elide(what, elide, slots_a != nullptr, slots_b != nullptr, bias_b != nullptr)) return st;
-    EpArgs p{};
-    p.a = a; p.bias_a = bias_a; p.b = b; p.bias_b = bias_b; p.out = out; p.elide = (uint32_t)elide;
-    const bool aligned = aligned16(a) && aligned16(b) && aligned16(out);
-    const EpMinMaxSinks sk{{slots_a, slots_b, slots_out}};
-    hipStream_t s = (hipStream_t)stream;
-    if (bias_b) return launch_epilogue_stats<true, true>(p, n, num_channel, elem_per_channel, relu, aligned, sk, what, s);
-    return launch_epilogue_stats<true, false>(p, n, num_channel, elem_per_channel, relu, aligned, sk, what, s);
+    const EpCall c{"bias_act_stats", kEpSingle, y, bias, nullptr, nullptr, nullptr, n, num_channel, elem_per_channel, relu, 0,
+                   kEpMinMaxSink, {slots_y}};
+    return run_epilogue(c, (hipStream_t)stream);
 }
 
 int ppqhip_bias_add_act_stats(float* a, const float* bias_a, float* b, const float* bias_b, float* out, int64_t n,
                               int64_t num_channel, int64_t elem_per_channel, int relu, float* slots_a, float* slots_b,
                               float* slots_out, void* stream) {
-    return bias_add_act_stats_impl("bias_add_act_stats", a, bias_a, b, bias_b, out, n, num_channel, elem_per_channel, relu,
-                                   slots_a, slots_b, slots_out, 0, stream);
+    const EpCall c{"bias_add_act_stats", kEpResidual, a, bias_a, b, bias_b, out, n, num_channel, elem_per_channel, relu, 0,
+                   kEpMinMaxSink, {slots_a, slots_b, slots_out}};
+    return run_epilogue(c, (hipStream_t)stream);
 }
 
 int ppqhip_bias_add_act_stats2(float* a, const float* bias_a, float* b, const float* bias_b, float* out, int64_t n,
                                int64_t num_channel, int64_t elem_per_channel, int relu, float* slots_a, float* slots_b,
                                float* slots_out, int elide, void* stream) {
-    return bias_add_act_stats_impl("bias_add_act_stats2", a, bias_a, b, bias_b, out, n, num_channel, elem_per_channel, relu,
-                                   slots_a, slots_b, slots_out, elide, stream);
-}
-
-static int validate_hist_rule(const char* what, int64_t bins) {
-    if (bins <= 0 || bins > 0x7fffffffLL) { set_error("%s: histogram is empty or too large", what); return PPQHIP_ERR_INVALID_VALUE; }
-    return PPQHIP_OK;
+    const EpCall c{"bias_add_act_stats2", kEpResidual, a, bias_a, b, bias_b, out, n, num_channel, elem_per_channel, relu, elide,
+                   kEpMinMaxSink, {slots_a, slots_b, slots_out}};
+    return run_epilogue(c, (hipStream_t)stream);
 }
 
 int ppqhip_bias_act_hist(float* y, const float* bias, int64_t n, int64_t num_channel, int64_t elem_per_channel, int relu,
                          int32_t* rows_y, float p0_y, float p1_y, int64_t num_bins, int asymmetric, int clip_outliers,
                          void* stream) {
-    if (int st = validate_channel_axis("bias_act_hist", n, num_channel, elem_per_channel)) return st;
-    if (!y || !bias) { set_error("bias_act_hist: null pointer"); return PPQHIP_ERR_INVALID_VALUE; }
-    if (int st = validate_hist_rule("bias_act_hist", num_bins)) return st;
-    if (num_bins > (int64_t)kEpHistLdsInts) return PPQHIP_NOT_FUSED;
-    const EpHistRule r{(int)num_bins, asymmetric ? 1 : 0, clip_outliers ? 1 : 0};
-    EpHistSinks sk{};
-    set_hist_rule(sk, 0, rows_y, p0_y, p1_y, r);
-    EpArgs p{};
-    p.a = y; p.bias_a = bias;
-    return launch_epilogue_hist<false, false>(p, n, num_channel, elem_per_channel, relu, aligned16(y), sk, r, "bias_act_hist",
-                                              (hipStream_t)stream);
+    const EpCall c{"bias_act_hist", kEpSingle, y, bias, nullptr, nullptr, nullptr, n, num_channel, elem_per_channel, relu, 0,
+                   kEpHistSink, {rows_y}, {p0_y}, {p1_y}, num_bins, asymmetric, clip_outliers};
+    return run_epilogue(c, (hipStream_t)stream);
 }
 
 int ppqhip_bias_add_act_hist(float* a, const float* bias_a, float* b, const float* bias_b, float* out, int64_t n,
                              int64_t num_channel, int64_t elem_per_channel, int relu, int32_t* rows_a, float p0_a, float p1_a,
                              int32_t* rows_b, float p0_b, float p1_b, int32_t* rows_out, float p0_out, float p1_out,
                              int64_t num_bins, int asymmetric, int clip_outliers, int elide, void* stream) {
-    const char* what = "bias_add_act_hist";
-    if (int st = validate_channel_axis(what, n, num_channel, elem_per_channel)) return st;
-    if (!a || !bias_a || !b || !out) { set_error("%s: null pointer", what); return PPQHIP_ERR_INVALID_VALUE; }
-    if (!bias_b && rows_b) { set_error("%s: without bias_b, b is only read: it has no sink", what); return PPQHIP_ERR_INVALID_VALUE; }
-    if (int st = validate_hist_rule(what, num_bins)) return st;
-    if (int st = validate_elide(what, elide, rows_a != nullptr, rows_b != nullptr, bias_b != nullptr)) return st;
-    // a workgroup reads its row of every sink ahead and writes it back at the end: two sinks on one accumulator would lose counts
-    if ((rows_a && (rows_a == rows_b || rows_a == rows_out)) || (rows_b && rows_b == rows_out)) {
-        set_error("%s: two sinks share one rows accumulator", what); return PPQHIP_ERR_INVALID_VALUE;
-    }
-    if (num_bins > (int64_t)kEpHistLdsInts) return PPQHIP_NOT_FUSED;
-    const EpHistRule r{(int)num_bins, asymmetric ? 1 : 0, clip_outliers ? 1 : 0};
-    EpHistSinks sk{};
-    set_hist_rule(sk, 0, rows_a, p0_a, p1_a, r);
-    set_hist_rule(sk, 1, rows_b, p0_b, p1_b, r);
-    set_hist_rule(sk, 2, rows_out, p0_out, p1_out, r);
-    EpArgs p{};
-    p.a = a; p.bias_a = bias_a; p.b = b; p.bias_b = bias_b; p.out = out; p.elide = (uint32_t)elide;
-    const bool aligned = aligned16(a) && aligned16(b) && aligned16(out);
-    hipStream_t s = (hipStream_t)stream;
-    if (bias_b) return launch_epilogue_hist<true, true>(p, n, num_channel, elem_per_channel, relu, aligned, sk, r, what, s);
-    return launch_epilogue_hist<true, false>(p, n, num_channel, elem_per_channel, relu, aligned, sk, r, what, s);
+    const EpCall c{"bias_add_act_hist", kEpResidual, a, bias_a, b, bias_b, out, n, num_channel, elem_per_channel, relu, elide,
+                   kEpHistSink, {rows_a, rows_b, rows_out}, {p0_a, p0_b, p0_out}, {p1_a, p1_b, p1_out},
+                   num_bins, asymmetric, clip_outliers};
+    return run_epilogue(c, (hipStream_t)stream);
 }
-
-#define PPQ_LAUNCH_POOL(RELU, SET, SK)                                                                                    \
-    hipLaunchKernelGGL((epilogue_pool_kernel<kEpTileU, RELU, SET>), dim3(pool_grid(p)), dim3(kEpStatBlock), lds_bytes,      \
-                       (hipStream_t)stream, p, SK)
 
 int ppqhip_bias_act_pool(float* y, const float* bias, float* pool, int64_t n, int64_t num_channel, int64_t height, int64_t width,
                          int relu, int kernel, int stride, int pad, int dilation, int ceil_mode, void* stream) {
-    const char* what = "bias_act_pool";
-    if (int st = validate_pool(what, y, bias, pool, n, num_channel, height, width)) return st;
-    EpPoolArgs p{};
-    p.y = y; p.bias = bias; p.pool = pool; p.store = 1u;
-    uint32_t lds_bytes = 0;
-    if (int st = fill_pool_geometry(p, n, num_channel, height, width, kernel, stride, pad, dilation, ceil_mode, 0, lds_bytes)) return st;
-    const EpNoSinks::Args sk{};
-    if (relu) PPQ_LAUNCH_POOL(true, EpNoSinks, sk); else PPQ_LAUNCH_POOL(false, EpNoSinks, sk);
-    return finish_launch(what);
+    EpCall c{"bias_act_pool", kEpPooled, y, bias, nullptr, nullptr, nullptr, n, num_channel, 0, relu};
+    c.pool = pool; c.height = height; c.width = width;
+    c.kernel = kernel; c.stride = stride; c.pad = pad; c.dilation = dilation; c.ceil_mode = ceil_mode; c.store_relu = 1;
+    return run_epilogue(c, (hipStream_t)stream);
 }
 
 int ppqhip_bias_act_pool_stats(float* y, const float* bias, float* pool, int64_t n, int64_t num_channel, int64_t height,
                                int64_t width, int relu, int kernel, int stride, int pad, int dilation, int ceil_mode,
                                float* slots_y, int store_relu, void* stream) {
-    const char* what = "bias_act_pool_stats";
-    if (int st = validate_pool(what, y, bias, pool, n, num_channel, height, width)) return st;
-    if (int st = validate_pool_store(what, store_relu, slots_y != nullptr)) return st;
-    if (!slots_y) return PPQHIP_NOT_FUSED;
-    EpPoolArgs p{};
-    p.y = y; p.bias = bias; p.pool = pool; p.store = store_relu ? 1u : 0u;
-    uint32_t lds_bytes = 0;
-    if (int st = fill_pool_geometry(p, n, num_channel, height, width, kernel, stride, pad, dilation, ceil_mode, 32, lds_bytes)) return st;
-    const EpMinMaxSinks sk{{slots_y, nullptr, nullptr}};
-    using Set = EpMinMaxSet<false, false>;
-    if (relu) PPQ_LAUNCH_POOL(true, Set, sk); else PPQ_LAUNCH_POOL(false, Set, sk);
-    return finish_launch(what);
+    EpCall c{"bias_act_pool_stats", kEpPooled, y, bias, nullptr, nullptr, nullptr, n, num_channel, 0, relu, 0, kEpMinMaxSink, {slots_y}};
+    c.pool = pool; c.height = height; c.width = width;
+    c.kernel = kernel; c.stride = stride; c.pad = pad; c.dilation = dilation; c.ceil_mode = ceil_mode; c.store_relu = store_relu;
+    return run_epilogue(c, (hipStream_t)stream);
 }
 
 int ppqhip_bias_act_pool_hist(float* y, const float* bias, float* pool, int64_t n, int64_t num_channel, int64_t height,
                               int64_t width, int relu, int kernel, int stride, int pad, int dilation, int ceil_mode,
                               int32_t* rows_y, float p0_y, float p1_y, int64_t num_bins, int asymmetric, int clip_outliers,
                               int store_relu, void* stream) {
-    const char* what = "bias_act_pool_hist";
-    if (int st = validate_pool(what, y, bias, pool, n, num_channel, height, width)) return st;
-    if (int st = validate_hist_rule(what, num_bins)) return st;
-    if (int st = validate_pool_store(what, store_relu, rows_y != nullptr)) return st;
-    if (!rows_y || !relu || num_bins > (int64_t)kEpHistLdsInts) return PPQHIP_NOT_FUSED;
-    const EpHistRule r{(int)num_bins, asymmetric ? 1 : 0, clip_outliers ? 1 : 0};
-    EpHistSinks sk{};
-    set_hist_rule(sk, 0, rows_y, p0_y, p1_y, r);
-    sk.lds_ints = (uint32_t)r.bins; sk.bins = r.bins;
-    EpPoolArgs p{};
-    p.y = y; p.bias = bias; p.pool = pool; p.store = store_relu ? 1u : 0u;
-    uint32_t lds_bytes = 0;
-    if (int st = fill_pool_geometry(p, n, num_channel, height, width, kernel, stride, pad, dilation, ceil_mode, sk.lds_ints, lds_bytes)) return st;
-#define PPQ_LAUNCH_POOLH(ASYM, CLIP) { using Set = EpHistSet<false, false, ASYM, CLIP>; PPQ_LAUNCH_POOL(true, Set, sk); }
-    switch ((r.asym ? 2 : 0) | (r.clip ? 1 : 0)) {
-        case 0: PPQ_LAUNCH_POOLH(false, false); break;
-        case 1: PPQ_LAUNCH_POOLH(false, true); break;
-        case 2: PPQ_LAUNCH_POOLH(true, false); break;
-        default: PPQ_LAUNCH_POOLH(true, true); break;
-    }
-#undef PPQ_LAUNCH_POOLH
-    return finish_launch(what);
+    EpCall c{"bias_act_pool_hist", kEpPooled, y, bias, nullptr, nullptr, nullptr, n, num_channel, 0, relu, 0,
+             kEpHistSink, {rows_y}, {p0_y}, {p1_y}, num_bins, asymmetric, clip_outliers};
+    c.pool = pool; c.height = height; c.width = width;
+    c.kernel = kernel; c.stride = stride; c.pad = pad; c.dilation = dilation; c.ceil_mode = ceil_mode; c.store_relu = store_relu;
+    return run_epilogue(c, (hipStream_t)stream);
 }
-#undef PPQ_LAUNCH_POOL
 
 }  // extern "C"

@@ -231,35 +231,64 @@ def _pool_launch(y: torch.Tensor, geo, pool):
     return pooled, (y.numel(), C, H, W), (k, s, p, 1, 0)
 
 
+def _run_epilogue(ts, biases, relu, kind=None, jobs=(), elide=0, pool=None, store=True):
+    """What the six functions below share: the one call of a ``ppqhip_bias_[add_]act[_pool][_stats[2]|_hist]`` entry point.
+    ``ts``: ``[y]``, or ``[a, b]`` with ``biases = [bias_a, bias_b or None]``; ``kind``: what the sinks take, ``'minmax'`` or
+    ``'hist_rows'``, with one job (or None) per tensor the launch stores; ``elide`` / ``pool`` / ``store`` as the callers document
+    them.  Returns None when NOTHING was launched -- operands that are not fusable (a residual that is its own operand: both
+    would be written), a job for ``b`` without ``bias_b``, a job of another kind, no job at all or rules that differ, a window
+    without output, PPQHIP_NOT_FUSED; else ``out`` of the residual form, the pooled tensor, or True."""
+    a, resid = ts[0], len(ts) == 2
+    geo = _epilogue_geometry(ts, biases if biases[-1] is not None else biases[:1])
+    if geo is None or (resid and a.data_ptr() == ts[1].data_ptr()): return None
+    name, sinks = 'ppqhip_bias_add_act' if resid else 'ppqhip_bias_act', ()
+    if kind is not None:
+        if resid and biases[1] is None and jobs[1] is not None: return None
+        try:
+            if kind == 'minmax':
+                sinks = [_sink_slots(job, a.device) for job in jobs]
+                if not any(sinks): return None
+            else:
+                sinks = [v for job in jobs for v in _sink_rows(job, a.device)]
+                rule = _hist_rule(jobs)
+                if rule is None: return None
+                sinks += (rule[0], int(rule[1]), int(rule[2]))
+        except ValueError: return None
+    if resid:
+        done = torch.empty_like(a)
+        ptrs = (a.data_ptr(), biases[0].data_ptr(), ts[1].data_ptr(), 0 if biases[1] is None else biases[1].data_ptr(),
+                done.data_ptr(), a.numel(), geo[0], geo[1], 1 if relu else 0)
+        if kind == 'hist_rows': name, sinks = name + '_hist', (*sinks, int(elide))
+        elif kind == 'minmax' and elide: name, sinks = name + '_stats2', (*sinks, int(elide))
+        elif kind == 'minmax': name += '_stats'                            # (takes no elide: ppq_hip.h)
+    elif pool is not None:
+        launch = _pool_launch(a, geo, pool)
+        if launch is None: return None
+        done = launch[0]
+        ptrs = (a.data_ptr(), biases[0].data_ptr(), done.data_ptr(), *launch[1], 1 if relu else 0, *launch[2])
+        name += '_pool'
+        if kind is not None: name, sinks = name + ('_stats' if kind == 'minmax' else '_hist'), (*sinks, 1 if store else 0)
+    else:
+        done = True
+        ptrs = (a.data_ptr(), biases[0].data_ptr(), a.numel(), geo[0], geo[1], 1 if relu else 0)
+        if kind is not None: name += '_stats' if kind == 'minmax' else '_hist'
+    with _DeviceOf(a):
+        return done if _fused_or_raise(getattr(lib, name)(*ptrs, *sinks, _stream())) else None
+
+
 def bias_act_(y: torch.Tensor, bias: torch.Tensor, relu: bool, pool=None):
     """In place ``y = act(y + bias.view(1, C, 1, 1))`` with act = F.relu when `relu`, one launch; bitwise
     ``F.relu(F.conv2d(x, w, None) + b)``'s elementwise tail.  False (nothing done) when the operands are not fusable.
     ``pool = (kernel, stride, pad)``: the same launch also pools what it stores (``ppqhip_bias_act_pool``) and the call returns
     ``F.max_pool2d(y, kernel, stride, pad)`` bit for bit, or None when NOTHING was launched."""
-    geo = _epilogue_geometry([y], [bias])
-    if pool is not None:
-        args = _pool_launch(y, geo, pool)
-        if args is None: return None
-        with _DeviceOf(y):
-            ok = _fused_or_raise(lib.ppqhip_bias_act_pool(y.data_ptr(), bias.data_ptr(), args[0].data_ptr(), *args[1],
-                                                          1 if relu else 0, *args[2], _stream()))
-        return args[0] if ok else None
-    if geo is None: return False
-    with _DeviceOf(y):
-        _raise(lib.ppqhip_bias_act(y.data_ptr(), bias.data_ptr(), y.numel(), geo[0], geo[1], 1 if relu else 0, _stream()))
-    return True
+    done = _run_epilogue([y], [bias], relu, pool=pool)
+    return done if pool is not None else done is not None
 
 
 def bias_add_act(a: torch.Tensor, bias_a: torch.Tensor, b: torch.Tensor, bias_b, relu: bool):
     """``a += bias_a``, ``b += bias_b`` (when given, else b is only read), returns ``act(a + b)`` in a new tensor of a's
     layout: the conv bias(es), the graph's Add(a, b) and F.relu in one launch.  None (nothing done) when not fusable."""
-    geo = _epilogue_geometry([a, b], [bias_a] if bias_b is None else [bias_a, bias_b])
-    if geo is None or a.data_ptr() == b.data_ptr(): return None
-    out = torch.empty_like(a)
-    with _DeviceOf(a):
-        _raise(lib.ppqhip_bias_add_act(a.data_ptr(), bias_a.data_ptr(), b.data_ptr(), 0 if bias_b is None else bias_b.data_ptr(),
-                                       out.data_ptr(), a.numel(), geo[0], geo[1], 1 if relu else 0, _stream()))
-    return out
+    return _run_epilogue([a, b], [bias_a, bias_b], relu)
 
 
 def conv1x1(x: torch.Tensor, w: torch.Tensor, bias, stride: int = 1):
@@ -307,20 +336,8 @@ def bias_act_stats_(y: torch.Tensor, bias: torch.Tensor, relu: bool, job, pool=N
     the caller runs ``bias_act_`` and observes ``y`` as usual.
     ``pool = (kernel, stride, pad)``: the pooled form (``ppqhip_bias_act_pool_stats``), which returns the pooled tensor, or None
     when nothing was launched; with ``store=False`` it folds and pools ``act(y + bias)`` but leaves ``y`` as it was."""
-    geo = _epilogue_geometry([y], [bias])
-    if geo is None or job is None: return None if pool is not None else False
-    try: slots = _sink_slots(job, y.device)
-    except ValueError: return None if pool is not None else False
-    if pool is not None:
-        args = _pool_launch(y, geo, pool)
-        if args is None: return None
-        with _DeviceOf(y):
-            ok = _fused_or_raise(lib.ppqhip_bias_act_pool_stats(y.data_ptr(), bias.data_ptr(), args[0].data_ptr(), *args[1],
-                                                                1 if relu else 0, *args[2], slots, 1 if store else 0, _stream()))
-        return args[0] if ok else None
-    with _DeviceOf(y):
-        return _fused_or_raise(lib.ppqhip_bias_act_stats(y.data_ptr(), bias.data_ptr(), y.numel(), geo[0], geo[1],
-                                                         1 if relu else 0, slots, _stream()))
+    done = _run_epilogue([y], [bias], relu, 'minmax', [job], pool=pool, store=store)
+    return done if pool is not None else done is not None
 
 
 ELIDE_A, ELIDE_B = 1, 2          # PPQHIP_ELIDE_A / PPQHIP_ELIDE_B: the tensors a statistics epilogue computes, feeds, and does NOT store
@@ -333,19 +350,7 @@ def bias_add_act_stats(a: torch.Tensor, bias_a: torch.Tensor, b: torch.Tensor, b
     (ELIDE_A | ELIDE_B): those tensors are folded but not stored -- their memory keeps the convolution output
     (``ppqhip_bias_add_act_stats2``; each needs a job).
     None: NOTHING was launched -- the caller runs ``bias_add_act`` and observes as usual."""
-    geo = _epilogue_geometry([a, b], [bias_a] if bias_b is None else [bias_a, bias_b])
-    if geo is None or a.data_ptr() == b.data_ptr(): return None
-    if bias_b is None and job_b is not None: return None
-    try: slots = [_sink_slots(j, a.device) for j in (job_a, job_b, job_out)]
-    except ValueError: return None
-    if not any(slots): return None
-    out = torch.empty_like(a)
-    args = (a.data_ptr(), bias_a.data_ptr(), b.data_ptr(), 0 if bias_b is None else bias_b.data_ptr(), out.data_ptr(),
-            a.numel(), geo[0], geo[1], 1 if relu else 0, slots[0], slots[1], slots[2])
-    with _DeviceOf(a):
-        if elide: ok = _fused_or_raise(lib.ppqhip_bias_add_act_stats2(*args, int(elide), _stream()))
-        else: ok = _fused_or_raise(lib.ppqhip_bias_add_act_stats(*args, _stream()))
-    return out if ok else None
+    return _run_epilogue([a, b], [bias_a, bias_b], relu, 'minmax', [job_a, job_b, job_out], elide)
 
 
 def _sink_rows(job, dev) -> tuple:
@@ -370,22 +375,8 @@ def bias_act_hist_(y: torch.Tensor, bias: torch.Tensor, relu: bool, job, pool=No
     asymmetric, p0, p1, clip)``) from the registers it is stored from (``ppqhip_bias_act_hist``).  False: NOTHING was
     launched -- the caller runs ``bias_act_`` and observes ``y`` as usual.
     ``pool`` / ``store``: the pooled form (``ppqhip_bias_act_pool_hist``), as in ``bias_act_stats_``."""
-    geo = _epilogue_geometry([y], [bias])
-    if geo is None or job is None: return None if pool is not None else False
-    try: rows, p0, p1 = _sink_rows(job, y.device)
-    except ValueError: return None if pool is not None else False
-    bins, asym, clip = _hist_rule([job])
-    if pool is not None:
-        args = _pool_launch(y, geo, pool)
-        if args is None: return None
-        with _DeviceOf(y):
-            ok = _fused_or_raise(lib.ppqhip_bias_act_pool_hist(y.data_ptr(), bias.data_ptr(), args[0].data_ptr(), *args[1],
-                                                               1 if relu else 0, *args[2], rows, p0, p1, bins, int(asym), int(clip),
-                                                               1 if store else 0, _stream()))
-        return args[0] if ok else None
-    with _DeviceOf(y):
-        return _fused_or_raise(lib.ppqhip_bias_act_hist(y.data_ptr(), bias.data_ptr(), y.numel(), geo[0], geo[1],
-                                                        1 if relu else 0, rows, p0, p1, bins, int(asym), int(clip), _stream()))
+    done = _run_epilogue([y], [bias], relu, 'hist_rows', [job], pool=pool, store=store)
+    return done if pool is not None else done is not None
 
 
 def bias_add_act_hist(a: torch.Tensor, bias_a: torch.Tensor, b: torch.Tensor, bias_b, relu: bool, job_a, job_b, job_out,
@@ -393,20 +384,7 @@ def bias_add_act_hist(a: torch.Tensor, bias_a: torch.Tensor, b: torch.Tensor, bi
     """``bias_add_act`` that also counts ``a``, ``b`` (only with ``bias_b``) and the returned ``out`` into the rows of their
     ``'hist_rows'`` jobs (None: not counted), with ``elide`` as in ``bias_add_act_stats`` (``ppqhip_bias_add_act_hist``).
     None: NOTHING was launched -- the caller runs ``bias_add_act`` and observes as usual."""
-    geo = _epilogue_geometry([a, b], [bias_a] if bias_b is None else [bias_a, bias_b])
-    if geo is None or a.data_ptr() == b.data_ptr(): return None
-    if bias_b is None and job_b is not None: return None
-    try: sinks = [_sink_rows(j, a.device) for j in (job_a, job_b, job_out)]
-    except ValueError: return None
-    rule = _hist_rule([job_a, job_b, job_out])
-    if rule is None: return None
-    out = torch.empty_like(a)
-    with _DeviceOf(a):
-        ok = _fused_or_raise(lib.ppqhip_bias_add_act_hist(
-            a.data_ptr(), bias_a.data_ptr(), b.data_ptr(), 0 if bias_b is None else bias_b.data_ptr(), out.data_ptr(),
-            a.numel(), geo[0], geo[1], 1 if relu else 0, *sinks[0], *sinks[1], *sinks[2], rule[0], int(rule[1]), int(rule[2]),
-            int(elide), _stream()))
-    return out if ok else None
+    return _run_epilogue([a, b], [bias_a, bias_b], relu, 'hist_rows', [job_a, job_b, job_out], elide)
 
 
 # ---- the weight maps: AdaRound and round tuning (include/ppq_hip.h ppqhip_adaround_*_multi / ppqhip_roundtune_fwd_multi) ------

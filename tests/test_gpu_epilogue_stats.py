@@ -70,27 +70,30 @@ def _same(s0: _Stat, s1: _Stat):
     assert _bits_equal(a, b), (a, b)
 
 
-def _check(shape, mode, special, gen, launches=1):
+def _check(shape, mode, special, gen, launches=1, relu=True, channels_last=False):
     """mode: 'p1' bias_act; 'p2' bias_add_act without bias_b (two sinks); 'p2b' with bias_b (three sinks)."""
+    def inputs():
+        t, bias = _inputs(shape, gen, special)
+        return (t.contiguous(memory_format=torch.channels_last) if channels_last else t), bias
     n_t = {'p1': 1, 'p2': 2, 'p2b': 3}[mode]
     ref = [_Stat() for _ in range(n_t)]
     got = [_Stat() for _ in range(n_t)]
     for _ in range(launches):                  # several launches: the running statistic
-        y, bias = _inputs(shape, gen, special)
+        y, bias = inputs()
         if mode == 'p1':
             y1 = y.clone()
-            assert ffi.bias_act_(y, bias, relu=True)
+            assert ffi.bias_act_(y, bias, relu=relu)
             ref[0].observe(y)
-            assert ffi.bias_act_stats_(y1, bias, True, got[0].job())
+            assert ffi.bias_act_stats_(y1, bias, relu, got[0].job())
             assert _bits_equal(y, y1)
             continue
-        b, bias_b = _inputs(shape, gen, special)
+        b, bias_b = inputs()
         if mode == 'p2': bias_b = None
         y1, b1 = y.clone(), b.clone()
-        out = ffi.bias_add_act(y, bias, b, bias_b, relu=True)
+        out = ffi.bias_add_act(y, bias, b, bias_b, relu=relu)
         for s, t in zip(ref, [y, b, out] if mode == 'p2b' else [y, out]): s.observe(t)
         jobs = [g.job() for g in got]
-        out1 = ffi.bias_add_act_stats(y1, bias, b1, bias_b, True, jobs[0], jobs[1] if mode == 'p2b' else None, jobs[-1])
+        out1 = ffi.bias_add_act_stats(y1, bias, b1, bias_b, relu, jobs[0], jobs[1] if mode == 'p2b' else None, jobs[-1])
         assert out1 is not None
         assert _bits_equal(y, y1) and _bits_equal(b, b1) and _bits_equal(out, out1)
     for s0, s1 in zip(ref, got): _same(s0, s1)
@@ -109,6 +112,19 @@ def test_stats_kernels_equal_epilogue_then_observer_launch(mode):
     for shape in SHAPES:
         for special in (False, True):
             _check(shape, mode, special, gen)
+
+
+# The launch is picked by (tile, relu, per-float4 or per-element channels) for each of the three operand forms: the shapes above
+# reach every tile and channel geometry with ReLU only, and the per-element geometry only below 2^20 elements.  Here: no ReLU
+# on either tile with either geometry -- channels-last makes [2,64,96,96] a large tensor with per-element channels -- and
+# that last shape with ReLU too.  The oracle is the same: the plain launch with that `relu`, then the observers' own launch.
+@gpu
+@pytest.mark.parametrize('mode', ['p1', 'p2', 'p2b'])
+def test_stats_kernels_without_relu_and_large_per_element_channels(mode):
+    gen = torch.Generator().manual_seed(11)
+    for shape, channels_last, relu in (((1, 8, 4, 4), False, False), ((1, 3, 5, 7), False, False), ((2, 64, 96, 96), False, False),
+                                       ((2, 64, 96, 96), True, False), ((2, 64, 96, 96), True, True)):
+        _check(shape, mode, True, gen, relu=relu, channels_last=channels_last)
 
 
 @gpu
