@@ -893,6 +893,35 @@ int ppqhip_mx_conv2d_fused(const uint8_t* x_elements, const uint8_t* x_scales, i
 int ppqhip_conv1x1(const float* x, const float* w, const float* bias, float* y, int64_t n, int64_t c, int64_t h, int64_t wd,
                    int64_t o, int64_t stride, void* stream);
 
+/* The same GEMM with its convolution epilogue group and the calibration sinks in its store (ADDED under ABI 4).
+ * The raw convolution output is never written; each output is finished in registers, in the operand order of ppqhip_bias_add_act,
+ * every add a separately rounded float32 add, act = ReLU when `relu` (NaN keeps its payload) else the identity:
+ *   resid == NULL             (P1):  out = act(acc + bias_a[o])
+ *   resid, bias_b given       (P2b): xa = acc + bias_a[o];  r = resid + bias_b[o];  out = act(xa + r)
+ *   resid given, bias_b NULL  (P2):  xa = acc + bias_a[o];  r = resid;              out = act(xa + r)
+ * `resid` has the shape of `out`; only `out` is stored -- xa and the biased r exist in registers alone (PPQHIP_ELIDE_A | _B of
+ * the unfused launches).  So out, and every value handed to a sink, has the bits of ppqhip_conv1x1(bias = NULL) followed by
+ * ppqhip_bias_act / ppqhip_bias_add_act.  bias_a is required.
+ * Sinks (`sink_kind`): dst_a takes xa, dst_r the biased r (P2b only), dst_out takes out (P1: the one tensor); NULL: no sink.
+ * PPQHIP_SINK_MINMAX: each is an observer's float[ppqhip_minmax_slots()][2]; PPQHIP_SINK_HIST: each is its
+ * int32[ppqhip_hist_rows()][num_bins], with (p0, p1) per sink and (num_bins, asymmetric, clip_outliers) shared, as
+ * ppqhip_bias_add_act_hist takes them.  The ranges and counts are those of the unfused sink launches, as integers and bit for bit.
+ * One persistent launch of at most min(tiles, 2 * CUs, max_workgroups if > 0) workgroups; workgroup g folds once, at its end, into
+ * slot / row g: no global atomics, no synchronisation, capturable into a HIP graph.
+ * Refused before any launch (PPQHIP_ERR_INVALID_VALUE, in this order): non-positive sizes; [a stride other than 1 or 2:
+ * PPQHIP_ERR_UNSUPPORTED]; a negative max_workgroups; an unknown sink kind; [n == 0: PPQHIP_OK]; a null x, w, bias_a or out;
+ * bias_b without resid; more than 2^31 - 1 elements; dst_a or dst_r without resid; dst_r without bias_b; histogram sinks with
+ * num_bins outside [1, 2^31); two sinks on one accumulator; out overlapping an input (resid included).
+ * Returns PPQHIP_NOT_FUSED, with NOTHING written, for: a pointer not aligned to 4 bytes; PPQHIP_SINK_NONE or no sink at all (the
+ * plain forms are ppqhip_conv1x1 + ppqhip_bias_act / _add_act); histogram counters (num_bins per sink) above 3 * 2048. */
+#define PPQHIP_SINK_NONE 0
+#define PPQHIP_SINK_MINMAX 1
+#define PPQHIP_SINK_HIST 2
+int ppqhip_conv1x1_epilogue(const float* x, const float* w, const float* bias_a, const float* resid, const float* bias_b, float* out,
+                            int64_t n, int64_t c, int64_t h, int64_t wd, int64_t o, int64_t stride, int relu, int sink_kind,
+                            void* dst_a, void* dst_r, void* dst_out, float p0_a, float p1_a, float p0_r, float p1_r, float p0_out,
+                            float p1_out, int64_t num_bins, int asymmetric, int clip_outliers, int64_t max_workgroups, void* stream);
+
 /* profiling aid used by bench.py: when enabled, every kernel launch made through this library
  * on this thread is bracketed by hipEvents on its own stream; ppqhip_prof_collect() synchronises
  * those events and returns, per kernel id, launches / total ms / total algorithmic bytes. */

@@ -139,6 +139,8 @@ PROTOTYPES = {
     'ppqhip_mx_gemm_fused': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_f32p, c_f32p, c_int, c_f32p, c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_vp]),
     'ppqhip_mx_conv2d_fused': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_f32p, c_f32p, c_int, c_f32p, c_vp, c_vp, c_int] + [c_i64] * 13 + [c_vp]),
     'ppqhip_conv1x1': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
+    'ppqhip_conv1x1_epilogue': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int,
+                                        c_int, c_vp, c_vp, c_vp, c_flt, c_flt, c_flt, c_flt, c_flt, c_flt, c_i64, c_int, c_int, c_i64, c_vp]),
     'ppqhip_prof_collect':(c_int, [ctypes.POINTER(ProfEntry), c_int]),
     'ppqhip_prof_event_overhead_us': (ctypes.c_double, [c_vp, c_int]),
 }

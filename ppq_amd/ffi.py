@@ -387,6 +387,57 @@ def bias_add_act_hist(a: torch.Tensor, bias_a: torch.Tensor, b: torch.Tensor, bi
     return _run_epilogue([a, b], [bias_a, bias_b], relu, 'hist_rows', [job_a, job_b, job_out], elide)
 
 
+SINK_MINMAX, SINK_HIST = 1, 2    # PPQHIP_SINK_MINMAX / PPQHIP_SINK_HIST
+
+
+def conv1x1_epilogue(x: torch.Tensor, w: torch.Tensor, stride: int, bias_a: torch.Tensor, resid, bias_b, relu: bool, job_a, job_r,
+                     job_out, max_workgroups: int = 0):
+    """``conv1x1`` with its whole epilogue group and the group's calibration sinks in the GEMM's store, one launch
+    (``ppqhip_conv1x1_epilogue``).  ``resid`` None (P1): returns ``act(conv(x, w) + bias_a)``; with ``resid`` of the output's shape:
+    ``act((conv(x, w) + bias_a) + r)`` with ``r = resid + bias_b`` (P2b) or ``r = resid`` (``bias_b`` None, P2) -- bit for bit
+    ``conv1x1(x, w, None, stride)`` followed by ``bias_act_`` / ``bias_add_act``.  ``job_a`` / ``job_r`` / ``job_out``: the
+    observers' ``('minmax', slots)`` or ``('hist_rows', ...)`` jobs for ``conv + bias_a``, the biased ``r`` and the result (None: not
+    fed; P1 has ``job_out`` alone); neither of the first two tensors is ever stored.  ``max_workgroups``: a cap on the grid (0: none).
+    Returns the new ``[N, O, HO, WO]`` tensor, or None when NOTHING was launched: no job, jobs of two kinds or rules, a job the
+    sinks do not take, a residual that is no contiguous float32 tensor of the output's shape, PPQHIP_NOT_FUSED."""
+    _f32(x, 'x'); _f32(w, 'w'); _f32(bias_a, 'bias_a')
+    if x.dim() != 4 or not x.is_contiguous() or not w.is_contiguous() or w.dim() not in (2, 4) or w.numel() != w.shape[0] * w.shape[1]:
+        raise RuntimeError(_KERNEL_FAILURE + 'conv1x1_epilogue: x must be contiguous NCHW and w a contiguous [O, C, 1, 1] or [O, C]')
+    N, C, H, W = (int(v) for v in x.shape)
+    O, dev = int(w.shape[0]), x.device
+    if int(w.shape[1]) != C or w.device != dev: raise RuntimeError(_KERNEL_FAILURE + 'conv1x1_epilogue: w does not match x')
+    for bias in (bias_a, bias_b):
+        if bias is None: continue
+        _f32(bias, 'bias')
+        if bias.dim() != 1 or bias.numel() != O or not bias.is_contiguous() or bias.device != dev:
+            raise RuntimeError(_KERNEL_FAILURE + 'conv1x1_epilogue: a bias must be a contiguous [O] vector on the device of x')
+    stride = int(stride)
+    shape = (N, O, (H - 1) // max(stride, 1) + 1, (W - 1) // max(stride, 1) + 1)
+    if resid is None and bias_b is not None: raise RuntimeError(_KERNEL_FAILURE + 'conv1x1_epilogue: bias_b without a residual')
+    if resid is not None and not (isinstance(resid, torch.Tensor) and resid.dtype is _F32 and resid.device == dev
+                                  and tuple(resid.shape) == shape and resid.is_contiguous()): return None
+    jobs = [job_a, job_r, job_out]
+    kinds = {job[0] for job in jobs if job is not None}
+    if len(kinds) != 1: return None
+    try:
+        if kinds == {'minmax'}:
+            kind, dst, rule = SINK_MINMAX, [_sink_slots(job, dev) for job in jobs], (0, 0, 0)
+            ps = [0.0] * 6
+        else:
+            rows = [_sink_rows(job, dev) for job in jobs]
+            rule = _hist_rule(jobs)
+            if rule is None: return None
+            kind, dst, ps = SINK_HIST, [r[0] for r in rows], [v for r in rows for v in r[1:]]
+    except ValueError: return None
+    out = torch.empty(shape, dtype=_F32, device=dev)
+    with _DeviceOf(x):
+        ok = _fused_or_raise(lib.ppqhip_conv1x1_epilogue(
+            x.data_ptr(), w.data_ptr(), bias_a.data_ptr(), 0 if resid is None else resid.data_ptr(),
+            0 if bias_b is None else bias_b.data_ptr(), out.data_ptr(), N, C, H, W, O, stride, 1 if relu else 0, kind, *dst, *ps,
+            int(rule[0]), int(rule[1]), int(rule[2]), int(max_workgroups), _stream()))
+    return out if ok else None
+
+
 # ---- the weight maps: AdaRound and round tuning (include/ppq_hip.h ppqhip_adaround_*_multi / ppqhip_roundtune_fwd_multi) ------
 _ADAROUND_JOB = np.dtype([('w', '<u8'), ('v', '<u8'), ('scale', '<u8'), ('offset', '<u8'), ('out', '<u8'), ('dy', '<u8'),
                           ('n', '<i8'), ('num_channel', '<i8'), ('elem_per_channel', '<i8'), ('qmin', '<i4'), ('qmax', '<i4')])

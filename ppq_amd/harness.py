@@ -153,11 +153,18 @@ class BaseGraph:
 # per-shape measurement of tools/pointwise_conv_bench.py (profiles/r18_pointwise_conv.txt), not tuned at run time:
 POINTWISE_MIN_WORK = 3.2e9        # FLOPs (2 N Co Ci Ho Wo) of one call from which the native kernel is used: every class enabled below was
 #                                   measured faster at 3.29e9 and above (ResNet-50 at batch 32); at a quarter of it only the stride-2 ones still are
-POINTWISE_KEEP_VENDOR = frozenset({   # (Ci, Co, H, W, stride) classes measured NOT faster natively by more than the spread: F.conv2d
-    (64, 64, 56, 56, 1), (64, 256, 56, 56, 1), (256, 64, 56, 56, 1), (256, 128, 56, 56, 1), (128, 512, 28, 28, 1),
-    (512, 256, 28, 28, 1), (1024, 256, 14, 14, 1), (1024, 512, 14, 14, 1), (512, 2048, 7, 7, 1), (1024, 2048, 14, 14, 2),
-    (2048, 512, 7, 7, 1)})
-#   native in ResNet-50: (256, 1024, 14, 14, 1) x 6 layers, (512, 128, 28, 28, 1) x 3 and the down convolutions (256, 512, 56, 56, 2), (512, 1024, 28, 28, 2)
+POINTWISE_KEEP_VENDOR = frozenset({   # (Ci, Co, H, W, stride) classes that stay on F.conv2d: measured NOT faster natively by more than the
+    (64, 64, 56, 56, 1), (256, 64, 56, 56, 1), (256, 128, 56, 56, 1), (1024, 256, 14, 14, 1), (2048, 512, 7, 7, 1)})   # spread, plain (r18) AND fused (r20)
+#   native in ResNet-50 as a plain GEMM (profiles/r18_pointwise_conv.txt): (256, 1024, 14, 14, 1) x 6 layers, (512, 128, 28, 28, 1) x 3 and
+#   the down convolutions (256, 512, 56, 56, 2), (512, 1024, 28, 28, 2).  Native because the calibration forward's ONE fused launch
+#   (ffi.conv1x1_epilogue) beats F.conv2d + the sink epilogue launch by more than the spread, summed over the two phases
+#   (profiles/r20_pointwise_epilogue.txt): (64, 256, 56, 56, 1) x 4, (128, 512, 28, 28, 1) x 4, (512, 2048, 7, 7, 1) x 3,
+#   (512, 256, 28, 28, 1), (1024, 512, 14, 14, 1) and the down convolution (1024, 2048, 14, 14, 2).  These pay their r18 deficit
+#   (2 .. 9 us per layer) in forwards without sinks and as the non-owning convolution of a two-conv group; the calibration
+#   pass has no forward without sinks.  ((64, 64, 56, 56, 1) also measured faster fused, but lies below POINTWISE_MIN_WORK at batch 32,
+#   where it was measured: it stays.  (256, 128, 56, 56, 1) cleared the rule by 1 us in one run and 4 us in the other: it stays too.)
+POINTWISE_KEEP_UNFUSED = frozenset({   # (Ci, Co, H, W, stride, role) measured NOT faster as ONE ffi.conv1x1_epilogue launch than as
+    (512, 1024, 28, 28, 2, 'P2b')})    # ffi.conv1x1 + the sink epilogue launch, summed over the two calibration phases (r20)
 
 
 def _square(v):
@@ -412,6 +419,7 @@ class TorchExecutor:
         self.channels_last = False                    # see use_channels_last()
         self.native_pointwise_conv = True             # eligible 1x1 convolutions on ffi.conv1x1 (pointwise_eligible); else F.conv2d
         self.pointwise_min_work = POINTWISE_MIN_WORK  # FLOPs per call from which they are
+        self.fuse_pointwise_epilogue = True           # ... and, in a forward with sinks, take their epilogue group into the GEMM's store: _pointwise_epilogue
         for v in graph.variables.values():
             if v.is_parameter and v.value is not None: v.value = v.value.to(device)
 
@@ -722,8 +730,11 @@ class TorchExecutor:
         for conv in grp.ops[:len(grp.convs)]:        # the convolutions, in execution order
             qin = self._input_side(conv, [raw_of(v) for v in conv.inputs], hooks.get(conv.name))
             a = conv.attributes
-            ys[conv.name] = _conv(qin[0], qin[1], None, a, self._native_min_work())
             biases[conv.name] = qin[2]
+            if conv is grp.ops[len(grp.convs) - 1]:  # the last one may take the whole group into its store
+                done = self._pointwise_epilogue(grp, conv, qin, ys, biases, raw_of, hooks)
+                if done is not None: return self._group_values(grp, hooks, raw_of, *done)
+            ys[conv.name] = _conv(qin[0], qin[1], None, a, self._native_min_work())
         if grp.kind == 'P1':
             conv = grp.convs[0]
             y = ys[conv.name]
@@ -771,6 +782,52 @@ class TorchExecutor:
                 out = F.relu(a + b)
             tail = {conv_a.name: a, grp.add.name: out, grp.relu.name: out}
             if conv_b is not None: tail[conv_b.name] = b
+        return self._group_values(grp, hooks, raw_of, tail, stored, fed, elided)
+
+    def _pointwise_epilogue(self, grp: EpilogueGroup, conv: Operation, qin: list, ys: dict, biases: dict, raw_of: Callable, hooks):
+        """The fused form of a group whose LAST-EXECUTED convolution `conv` is one the native pointwise kernel takes:
+        ffi.conv1x1_epilogue runs the GEMM, the bias(es), the Add, the Relu and the sinks of the group's observers as one launch,
+        and the convolution's raw output never exists.  (tail, stored, fed, elided) as ``_run_epilogue`` builds them, or None --
+        nothing ran, the caller goes on as if this had not been tried -- unless: the flag is on, the layout is contiguous NCHW,
+        `conv` is ``pointwise_eligible`` (so the fused and the unfused forward run it on the same kernel) and its (class, role) is
+        not in POINTWISE_KEEP_UNFUSED; the forward has sinks and records nothing; in a P2 group every tensor the launch does not
+        store -- `conv`'s biased output and, with two convolutions, the other's -- is in ``elidable_stores``.  The other
+        convolution of a two-conv group has run already, without bias: its raw output is the residual, and as float addition
+        commutes bit for bit it does not matter which of the two owns the Add."""
+        native = self._native_min_work()
+        if not self.fuse_pointwise_epilogue or native is None or grp.pool is not None: return None
+        x, w = qin[0], qin[1]
+        if not pointwise_eligible(x, w, conv.attributes, native): return None
+        stride = _square(conv.attributes.get('strides', 1))
+        role = 'P1' if grp.kind == 'P1' else ('P2b' if len(grp.convs) == 2 else 'P2')
+        if (int(x.shape[1]), int(w.shape[0]), int(x.shape[2]), int(x.shape[3]), stride, role) in POINTWISE_KEEP_UNFUSED: return None
+        from .ffi import conv1x1_epilogue
+        stored = {grp.relu.name: None}
+        if grp.kind == 'P2': stored.update({c.name: None for c in grp.convs})
+        fed = self._epilogue_sinks(grp, hooks, stored, x)
+        if fed is None or fed[1].recorder is not None: return None
+        jobs = fed[0]
+        if grp.kind == 'P1':
+            out = conv1x1_epilogue(x, w, stride, biases[conv.name], None, None, True, None, None, jobs.get(grp.relu.name))
+            if out is None: return None
+            return {conv.name: out, grp.relu.name: out}, {grp.relu.name: out}, fed, set()
+        others = [c for c in grp.convs if c is not conv]
+        if elidable_stores(grp, hooks, jobs, fed[1].recorder) != {c.name for c in grp.convs}: return None
+        other = others[0] if others else None
+        resid = ys[other.name] if other is not None else raw_of(next(v for v in grp.add.inputs if v.source_op is not conv))
+        out = conv1x1_epilogue(x, w, stride, biases[conv.name], resid, biases[other.name] if other is not None else None, True,
+                               jobs.get(conv.name), jobs.get(other.name) if other is not None else None, jobs.get(grp.relu.name))
+        if out is None: return None
+        # `conv`'s own output never exists, yet it has a name in the hook walk: an uninitialised tensor of its shape (no kernel, no
+        # traffic) that its observer claims as prepaid without reading, and that nobody can read afterwards (`elided`)
+        stored = {conv.name: torch.empty_like(out), grp.relu.name: out}
+        if other is not None: stored[other.name] = resid
+        tail = {conv.name: stored[conv.name], grp.add.name: out, grp.relu.name: out}
+        if other is not None: tail[other.name] = resid
+        return tail, stored, fed, {c.name for c in grp.convs}
+
+    def _group_values(self, grp: EpilogueGroup, hooks, raw_of: Callable, tail: dict, stored: dict, fed, elided: set):
+        """What follows a group's launch: member by member, in op order, the quantize_function calls and hooks of the unfused loop."""
         if fed is not None:                              # only after a launch that took place
             for name, job in fed[0].items(): fed[1].prepay(stored[name], job[1])
         values: Dict[str, torch.Tensor] = {}
