@@ -760,6 +760,18 @@ int ppqhip_stat_shape_multi(const ppqhip_stat_job* jobs, int num_jobs, void* str
  * is allowed; any other overlap of an output with an input or another output is refused.  Sizes of 0 launch nothing. */
 enum { PPQHIP_MXFP8_E4M3 = 0, PPQHIP_MXFP8_E5M2 = 1, PPQHIP_MXFP6_E3M2 = 2, PPQHIP_MXFP6_E2M3 = 3, PPQHIP_MXFP4_E2M1 = 4,
        PPQHIP_MXINT8 = 5 };
+/* The scale rule travels above the format: `format | (rule << PPQHIP_MX_RULE_SHIFT)`, in the argument of
+ * ppqhip_mx_fq / ppqhip_mx_pack and in the `format` field of their jobs; the low byte alone is FLOOR, the rule written above.  With
+ * a = the float32 pattern of amax, code_f = the floor code, top = the largest normal and m = the mantissa bits (MXINT8: 6):
+ *   CEIL  code_f + 1 when amax * 2^(127 - code_f) > top, else code_f: amax never saturates
+ *   EVEN  the floor code of the pattern a + (1 << (22 - m)): amax rounded to the element's precision first
+ *   MSE   of c0 = code_f and c1 = code_f + 1 the one with the smaller sum over the block's finite elements of d * d in float64,
+ *         d = cast(v / X) * X - v (exact in float32); c1 only when its sum is strictly smaller
+ * every code clamped to 254: 0xFF is never made.  Cast, saturation, NaN, Inf and the all-zero block are as above with the X chosen.
+ * The entry points that make no scales (unpack, gemm, conv2d and their fused forms, out_format included) refuse a rule byte, and
+ * every entry point refuses a rule it does not know, before any launch. */
+enum { PPQHIP_MX_RULE_SHIFT = 8 };
+enum { PPQHIP_MX_FLOOR = 0, PPQHIP_MX_CEIL = 1, PPQHIP_MX_EVEN = 2, PPQHIP_MX_MSE = 3 };
 int ppqhip_mx_fq(const float* x, float* y, uint8_t* scale_codes, int64_t outer, int64_t axis_len, int64_t inner, int format,
                  void* stream);
 /* many tensors, one launch: every job exactly as ppqhip_mx_fq.  `jobs` is a HOST array that is copied into the kernel arguments

@@ -8,9 +8,9 @@ from .core import (PPQ_CONFIG, FloatingQuantizationConfig, LinearQuantizationCon
                    QuantizationProperty, QuantizationStates, RoundingPolicy, TensorQuantizationConfig)
 from .ffi import (CUDA, CUDA_COMPLIER, ENABLE_CUDA_KERNEL, HIP_EXTENSION, install_into_ppq, install_plugins_into_ppq,
                   uninstall_from_ppq)
-from .mx import (MXDelegator, MXDeployment, MXFormat, MXTensor, deploy_graph_mx, export_graph_mx, mx_conv2d, mx_conv2d_packed, mx_dequantize,
+from .mx import (MXDelegator, MXDeployment, MXFormat, MXScaleRule, MXTensor, deploy_graph_mx, export_graph_mx, mx_conv2d, mx_conv2d_packed, mx_dequantize,
                  mx_fake_quant, mx_linear, mx_matmul, mx_quantize, quantize_graph_mx)
 
-__all__ = ['MXFormat', 'MXDelegator', 'MXTensor', 'mx_fake_quant', 'mx_quantize', 'mx_dequantize', 'mx_matmul', 'mx_linear', 'mx_conv2d', 'mx_conv2d_packed', 'quantize_graph_mx', 'export_graph_mx', 'deploy_graph_mx', 'MXDeployment', 'CUDA', 'CUDA_COMPLIER', 'ENABLE_CUDA_KERNEL', 'HIP_EXTENSION', 'install_into_ppq', 'install_plugins_into_ppq', 'uninstall_from_ppq', 'PPQ_CONFIG', 'RoundingPolicy',
+__all__ = ['MXFormat', 'MXScaleRule', 'MXDelegator', 'MXTensor', 'mx_fake_quant', 'mx_quantize', 'mx_dequantize', 'mx_matmul', 'mx_linear', 'mx_conv2d', 'mx_conv2d_packed', 'quantize_graph_mx', 'export_graph_mx', 'deploy_graph_mx', 'MXDeployment', 'CUDA', 'CUDA_COMPLIER', 'ENABLE_CUDA_KERNEL', 'HIP_EXTENSION', 'install_into_ppq', 'install_plugins_into_ppq', 'uninstall_from_ppq', 'PPQ_CONFIG', 'RoundingPolicy',
            'QuantizationProperty', 'QuantizationPolicy', 'QuantizationStates', 'TensorQuantizationConfig',
            'LinearQuantizationConfig', 'FloatingQuantizationConfig']

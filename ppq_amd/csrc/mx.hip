@@ -17,6 +17,9 @@
 //   strided inner > 1: one lane per (outer, block, inner) triple, numbered with inner fastest, so that each of the 32 loads of a
 //           wave is coalesced along inner and a wave stays full when inner is small (9 for a 3x3 weight)
 // The description of a format, the scale code and the rounding of an element live in mx_common.hpp, shared with mx_pack.hip.
+// The code above is the floor rule's; a job may ask for another scale rule (CEIL, EVEN, MSE: DESIGN.md section 9.17), which travels
+// above the format id and is a workgroup-uniform choice in instantiations of their own -- still one launch, one read and one write
+// per element: under MSE the block's values wait in registers through two more casts and two float64 sums.
 #include "common.hpp"
 #include "job_table.hpp"
 #include "mx_common.hpp"
@@ -26,7 +29,7 @@ namespace {
 
 enum : uint32_t { MX_ROWS4 = 0, MX_ROWS1 = 1, MX_STRIDED = 2 };
 
-struct MxJob {                                    // 88 B
+struct MxJob {                                    // 96 B
     const float* x;
     float* y;
     uint8_t* codes;                               // E8M0 scale codes, one per block, or null
@@ -36,6 +39,7 @@ struct MxJob {                                    // 88 B
     FastDiv inner;
     uint32_t path;
     MxFmt fmt;
+    uint32_t rule;                                // PPQHIP_MX_FLOOR .. PPQHIP_MX_MSE: read by the RULED instantiations only
 };
 template <int CAP>
 struct MxArgs {
@@ -45,7 +49,10 @@ struct MxArgs {
 };
 static_assert(sizeof(MxArgs<kMxMaxJobs>) <= 4096, "kernel arguments are limited to 4 KB");
 
-template <int U, bool NT>
+// RULED (MX_PLAIN / MX_AMAX_RULES / MX_SEARCH, mx_common.hpp): the instantiations above MX_PLAIN take the block's code from the job's
+// scale rule.  The plain ones are the floor rule's and keep their code; a launch whose jobs are all FLOOR
+// runs those.
+template <int U, bool NT, int RULED>
 __device__ __forceinline__ void mx_rows4(const MxJob& j, uint32_t local) {
     constexpr uint32_t kGroups = kBlock / 8;                                     // blocks per workgroup and step
     const uint32_t q = threadIdx.x & 7u;
@@ -71,7 +78,16 @@ __device__ __forceinline__ void mx_rows4(const MxJob& j, uint32_t local) {
         m = max(m, (uint32_t)__shfl_xor((int)m, 4, 64));
         m = max(m, (uint32_t)__shfl_xor((int)m, 2, 64));
         m = max(m, (uint32_t)__shfl_xor((int)m, 1, 64));
-        const uint32_t code = mx_code(m, j.fmt);
+        uint32_t code = mx_code(m, j.fmt);
+        if constexpr (RULED != MX_PLAIN) {
+            code = mx_rule_code(m, j.fmt, j.rule);
+            if (RULED == MX_SEARCH && j.rule == PPQHIP_MX_MSE) {              // workgroup-uniform
+                MxMse s(code);
+                s.add(a[k].x, ok[k], j.fmt); s.add(a[k].y, ok[k], j.fmt); s.add(a[k].z, ok[k], j.fmt); s.add(a[k].w, ok[k], j.fmt);
+                s.reduce<8>();
+                code = s.code();
+            }
+        }
         const float X = mx_pow2(code), inv = mx_pow2(254u - code);
         float4 r;
         r.x = mx_elem(a[k].x, inv, X, j.fmt); r.y = mx_elem(a[k].y, inv, X, j.fmt);
@@ -81,6 +97,7 @@ __device__ __forceinline__ void mx_rows4(const MxJob& j, uint32_t local) {
     }
 }
 
+template <int RULED>
 __device__ __forceinline__ void mx_rows1(const MxJob& j, uint32_t local) {
     const uint32_t q = threadIdx.x & 31u;
     const uint32_t want = local * (kBlock / kMxBlock) + (threadIdx.x >> 5);
@@ -94,12 +111,22 @@ __device__ __forceinline__ void mx_rows1(const MxJob& j, uint32_t local) {
     uint32_t m = ok ? mx_finite_mag(v) : 0u;
 #pragma unroll
     for (int s = 16; s > 0; s >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, s, 64));
-    const uint32_t code = mx_code(m, j.fmt);
+    uint32_t code = mx_code(m, j.fmt);
+    if constexpr (RULED != MX_PLAIN) {
+        code = mx_rule_code(m, j.fmt, j.rule);
+        if (RULED == MX_SEARCH && j.rule == PPQHIP_MX_MSE) {
+            MxMse s(code);
+            s.add(v, ok, j.fmt);
+            s.reduce<32>();
+            code = s.code();
+        }
+    }
     const float r = mx_elem(v, mx_pow2(254u - code), mx_pow2(code), j.fmt);
     if (ok) j.y[at] = r;
     if (in && q == 0 && j.codes != nullptr) j.codes[g] = (uint8_t)code;
 }
 
+template <int RULED>
 __device__ __forceinline__ void mx_strided(const MxJob& j, uint32_t local) {
     const uint32_t want = local * kBlock + threadIdx.x;
     const bool in = want < j.units;
@@ -115,7 +142,16 @@ __device__ __forceinline__ void mx_strided(const MxJob& j, uint32_t local) {
     for (uint32_t t = 0; t < kMxBlock; t++) v[t] = j.x[base + min(t, blen - 1) * step];      // clamped: 32 loads in flight
 #pragma unroll
     for (uint32_t t = 0; t < kMxBlock; t++) m = max(m, t < blen ? mx_finite_mag(v[t]) : 0u);
-    const uint32_t code = mx_code(m, j.fmt);
+    uint32_t code = mx_code(m, j.fmt);
+    if constexpr (RULED != MX_PLAIN) {
+        code = mx_rule_code(m, j.fmt, j.rule);
+        if (RULED == MX_SEARCH && j.rule == PPQHIP_MX_MSE) {
+            MxMse s(code);
+#pragma unroll
+            for (uint32_t t = 0; t < kMxBlock; t++) s.add(v[t], t < blen, j.fmt);
+            code = s.code();
+        }
+    }
     const float X = mx_pow2(code), inv = mx_pow2(254u - code);
     if (!in) return;
 #pragma unroll
@@ -124,19 +160,29 @@ __device__ __forceinline__ void mx_strided(const MxJob& j, uint32_t local) {
     if (j.codes != nullptr) j.codes[w] = (uint8_t)code;
 }
 
-template <int CAP, int U, bool NT>
+template <int CAP, int U, bool NT, int RULED>
 __global__ __launch_bounds__(kBlock) void mx_fq_kernel(const MxArgs<CAP> args) {
     uint32_t local;
     const MxJob& j = args.jobs[job_of(args, local)];
-    if (j.path == MX_ROWS4) mx_rows4<U, NT>(j, local);                           // workgroup-uniform
-    else if (j.path == MX_ROWS1) mx_rows1(j, local);
-    else mx_strided(j, local);
+    if (j.path == MX_ROWS4) mx_rows4<U, NT, RULED>(j, local);                    // workgroup-uniform
+    else if (j.path == MX_ROWS1) mx_rows1<RULED>(j, local);
+    else mx_strided<RULED>(j, local);
+}
+
+template <int CAP, int U, bool NT>
+void launch_fq(int ruled, uint32_t blocks, hipStream_t s, const MxArgs<CAP>& args) {
+    if (ruled == MX_SEARCH) hipLaunchKernelGGL((mx_fq_kernel<CAP, U, NT, MX_SEARCH>), dim3(blocks), dim3(kBlock), 0, s, args);
+    else if (ruled == MX_AMAX_RULES) hipLaunchKernelGGL((mx_fq_kernel<CAP, U, NT, MX_AMAX_RULES>), dim3(blocks), dim3(kBlock), 0, s, args);
+    else hipLaunchKernelGGL((mx_fq_kernel<CAP, U, NT, MX_PLAIN>), dim3(blocks), dim3(kBlock), 0, s, args);
 }
 
 // the checks of one job; *n = its elements (0: nothing to do)
 int validate_job(const char* what, int k, const ppqhip_mx_job& j, int64_t* n) {
     MxFmt probe;
-    if (!make_mx_fmt(j.format, &probe)) { set_error("%s: job %d: unknown MX format %d", what, k, j.format); return PPQHIP_ERR_INVALID_VALUE; }
+    int fmt;
+    uint32_t rule;
+    if (!split_mx_format(j.format, &fmt, &rule)) { set_error("%s: job %d: unknown MX scale rule in format %d", what, k, j.format); return PPQHIP_ERR_INVALID_VALUE; }
+    if (!make_mx_fmt(fmt, &probe)) { set_error("%s: job %d: unknown MX format %d", what, k, fmt); return PPQHIP_ERR_INVALID_VALUE; }
     if (j.outer < 0 || j.axis_len < 0 || j.inner < 0) { set_error("%s: job %d: negative size", what, k); return PPQHIP_ERR_INVALID_VALUE; }
     *n = 0;
     if (j.outer == 0 || j.axis_len == 0 || j.inner == 0) return PPQHIP_OK;
@@ -167,14 +213,17 @@ int validate(const char* what, const ppqhip_mx_job* jobs, int num_jobs) {
     return check_overlap(what, ins, outs);
 }
 
-// the packed job and the workgroups it takes when a rows4 lane owns U float4
-uint32_t pack_job(const ppqhip_mx_job& src, int U, MxJob* d) {
+// the packed job and the workgroups it takes when a rows4 lane owns U float4; *ruled is raised to the class of the job's rule
+uint32_t pack_job(const ppqhip_mx_job& src, int U, MxJob* d, int* ruled) {
     d->x = src.x; d->y = src.y; d->codes = src.scale_codes;
     d->len = (uint32_t)src.axis_len;
     const int64_t nb = blocks_per_row(src);
     d->nb = make_fastdiv((uint32_t)nb);
     d->inner = make_fastdiv((uint32_t)src.inner);
-    make_mx_fmt(src.format, &d->fmt);
+    int fmt;
+    split_mx_format(src.format, &fmt, &d->rule);
+    make_mx_fmt(fmt, &d->fmt);
+    *ruled = std::max(*ruled, mx_rule_class(d->rule));
     const int64_t units = src.outer * nb * src.inner;                            // <= elements <= 2^31 - 1
     d->units = (uint32_t)units;
     int64_t per;
@@ -211,12 +260,13 @@ int ppqhip_mx_fq(const float* x, float* y, uint8_t* scale_codes, int64_t outer, 
     LaunchScope scope(K_MX_FQ, job_bytes(job), s);
     MxArgs<1> args;
     const int U = n <= kMxSmallElems ? 1 : 2;
-    const uint32_t blocks = pack_job(job, U, &args.jobs[0]);
+    int ruled = MX_PLAIN;
+    const uint32_t blocks = pack_job(job, U, &args.jobs[0], &ruled);
     args.first_block[0] = 0;
     args.count = 1;
-    if (n >= kMxStreamElems) hipLaunchKernelGGL((mx_fq_kernel<1, 2, true>), dim3(blocks), dim3(kBlock), 0, s, args);
-    else if (U == 2) hipLaunchKernelGGL((mx_fq_kernel<1, 2, false>), dim3(blocks), dim3(kBlock), 0, s, args);
-    else hipLaunchKernelGGL((mx_fq_kernel<1, 1, false>), dim3(blocks), dim3(kBlock), 0, s, args);
+    if (n >= kMxStreamElems) launch_fq<1, 2, true>(ruled, blocks, s, args);
+    else if (U == 2) launch_fq<1, 2, false>(ruled, blocks, s, args);
+    else launch_fq<1, 1, false>(ruled, blocks, s, args);
     return finish_launch("mx_fq");
 }
 
@@ -236,13 +286,14 @@ int ppqhip_mx_fq_multi(const ppqhip_mx_job* jobs, int num_jobs, void* stream) {
         MxArgs<kMxMaxJobs> args;
         const uint32_t count = (uint32_t)std::min<size_t>(kMxMaxJobs, live.size() - base);
         uint64_t blocks = 0;
+        int ruled = MX_PLAIN;
         for (uint32_t k = 0; k < count; k++) {
             args.first_block[k] = (uint32_t)blocks;
-            blocks += pack_job(*live[base + k], 1, &args.jobs[k]);
+            blocks += pack_job(*live[base + k], 1, &args.jobs[k], &ruled);
         }
         if (blocks > (uint64_t)kMxMax) { set_error("mx_fq_multi: too many workgroups in one launch"); return PPQHIP_ERR_INVALID_VALUE; }
         pad_job_table(args, count, (uint32_t)blocks);
-        hipLaunchKernelGGL((mx_fq_kernel<kMxMaxJobs, 1, false>), dim3((uint32_t)blocks), dim3(kBlock), 0, s, args);
+        launch_fq<kMxMaxJobs, 1, false>(ruled, (uint32_t)blocks, s, args);
     }
     return finish_launch("mx_fq_multi");
 }

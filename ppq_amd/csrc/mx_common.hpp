@@ -45,6 +45,21 @@ inline bool make_mx_fmt(int format, MxFmt* f) {
     return true;
 }
 
+// `format` as the scale-making entry points take it: the format in the low byte, the scale rule (PPQHIP_MX_FLOOR .. PPQHIP_MX_MSE,
+// DESIGN.md section 9.17) above it.  False: a negative value or a rule nobody knows.
+inline bool split_mx_format(int format, int* fmt, uint32_t* rule) {
+    if (format < 0 || (format >> PPQHIP_MX_RULE_SHIFT) > PPQHIP_MX_MSE) return false;
+    *fmt = format & ((1 << PPQHIP_MX_RULE_SHIFT) - 1);
+    *rule = (uint32_t)(format >> PPQHIP_MX_RULE_SHIFT);
+    return true;
+}
+
+// The instantiation a launch of the scale-making kernels needs: the floor rule's own code, the rules that read nothing but the amax
+// (CEIL, EVEN) added, or the MSE search as well -- the search keeps two float64 sums and a second cast in registers, which the other
+// rules should not pay for.  A launch of many jobs takes the largest class among them.
+enum : int { MX_PLAIN = 0, MX_AMAX_RULES = 1, MX_SEARCH = 2 };
+inline int mx_rule_class(uint32_t rule) { return rule == PPQHIP_MX_MSE ? MX_SEARCH : rule != PPQHIP_MX_FLOOR ? MX_AMAX_RULES : MX_PLAIN; }
+
 constexpr uint32_t kMxBlock = 32;                 // elements per MX block
 constexpr int kMxMaxJobs = 40;                    // jobs of one launch (the table travels in the kernel arguments)
 constexpr int64_t kMxMax = 0x7fffffffLL;          // elements of one tensor
@@ -78,6 +93,45 @@ __device__ __forceinline__ float mx_elem(float v, float inv, float X, const MxFm
     const float q = __uint_as_float(mx_round(mag, f) | sign) * X;
     return mag > 0x7f800000u ? v : q;
 }
+
+// THE scale rule: the block's code from the pattern of its amax under the three rules that need nothing
+// but the amax -- for PPQHIP_MX_MSE this is its first candidate, the floor code.  Every result is in 0 .. 254.
+//   CEIL  the floor code, one more when amax / X lies above the largest normal (the product is exact: X is a power of two)
+//   EVEN  the floor code of amax rounded to the element's precision: half an element ULP added to the pattern
+__device__ __forceinline__ uint32_t mx_rule_code(uint32_t amax_bits, const MxFmt& f, uint32_t rule) {
+    const uint32_t floor_code = mx_code(amax_bits, f);
+    if (rule == PPQHIP_MX_CEIL) {
+        const uint32_t scaled = __float_as_uint(__uint_as_float(amax_bits) * mx_pow2(254u - floor_code));
+        return min(floor_code + (scaled > f.max_bits ? 1u : 0u), 254u);
+    }
+    if (rule == PPQHIP_MX_EVEN) return min(mx_code(amax_bits + f.half_m1 + 1u, f), 254u);
+    return floor_code;
+}
+
+// PPQHIP_MX_MSE: the squared error of a block under the floor code c0 and under c1 = min(c0 + 1, 254), over its finite elements.
+// d = cast(v / X) * X - v is exact in float32 (section 9.17), its square exact in float64; the two sums run through the same adds in
+// the same order, so two candidates that quantise alike give equal sums, and the strict comparison keeps c0.
+struct MxMse {
+    uint32_t c0, c1;
+    float X0, inv0, X1, inv1;
+    double e0, e1;
+    __device__ __forceinline__ explicit MxMse(uint32_t floor_code)
+        : c0(floor_code), c1(min(floor_code + 1u, 254u)), X0(mx_pow2(c0)), inv0(mx_pow2(254u - c0)), X1(mx_pow2(c1)),
+          inv1(mx_pow2(254u - c1)), e0(0.0), e1(0.0) {}
+    __device__ __forceinline__ void add(float v, bool counts, const MxFmt& f) {
+        const bool finite = counts && (__float_as_uint(v) & 0x7fffffffu) < 0x7f800000u;
+        const float d0 = mx_elem(v, inv0, X0, f) - v, d1 = mx_elem(v, inv1, X1, f) - v;
+        e0 += finite ? (double)d0 * (double)d0 : 0.0;
+        e1 += finite ? (double)d1 * (double)d1 : 0.0;
+    }
+    // the sums of the LANES lanes that share the block (a butterfly: every lane ends with the same bits, an add commutes)
+    template <int LANES>
+    __device__ __forceinline__ void reduce() {
+#pragma unroll
+        for (int s = LANES / 2; s > 0; s >>= 1) { e0 += __shfl_xor(e0, s, 64); e1 += __shfl_xor(e1, s, 64); }
+    }
+    __device__ __forceinline__ uint32_t code() const { return e1 < e0 ? c1 : c0; }
+};
 
 #endif  // __HIPCC__
 

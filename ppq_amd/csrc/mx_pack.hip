@@ -20,6 +20,8 @@
 //   strided inner > 1: one lane per (outer, block, inner), inner fastest, with the 32 values in registers; the lane owns the B bytes of its
 //           block (16-B stores, 8-B for the 24-B blocks of FP6; bytes when `elements` is not 16-B aligned).  This is where the axis
 //           moves last.  The loads are coalesced along inner, as in mx.hip.
+// Pack takes the block's scale by the job's scale rule exactly as mx.hip does, from the same function of
+// mx_common.hpp; unpack reads scales as stored and knows no rule.
 #include "common.hpp"
 #include "job_table.hpp"
 #include "mx_coder.hpp"
@@ -41,7 +43,7 @@ struct MxPackJob {                                // 96 B; pack: f -> e, s; unpa
     uint32_t path;
     uint32_t format;
     MxFmt fmt;
-    uint32_t pad;
+    uint32_t rule;                                // pack: PPQHIP_MX_FLOOR .. PPQHIP_MX_MSE, read by the RULED instantiations only
 };
 template <int CAP>
 struct MxPackArgs {
@@ -78,7 +80,14 @@ __device__ __forceinline__ float mxp_value(uint32_t code, float X, bool scale_na
 }
 
 // ---- pack ----------------------------------------------------------------------------------------------------------------------
-template <int U>
+// RULED (MX_PLAIN / MX_AMAX_RULES / MX_SEARCH): the instantiations above MX_PLAIN take the block's code from the job's scale rule
+// (mx_common.hpp), as in mx.hip; the plain ones are the floor rule's and keep their code.  A block that is NaN as a whole keeps scale 0xFF under every rule.
+__device__ __forceinline__ uint32_t ruled_scale(uint32_t code, bool dead, float& inv) {
+    inv = mx_pow2(254u - code);
+    return dead ? 0xffu : code;
+}
+
+template <int U, int RULED>
 __device__ __forceinline__ void pack_rows4(const MxPackJob& j, uint32_t local) {
     constexpr uint32_t kGroups = kBlock / 8;                                     // blocks per workgroup and step
     const MxCoder c = make_coder(j.format, j.fmt);
@@ -104,7 +113,17 @@ __device__ __forceinline__ void pack_rows4(const MxPackJob& j, uint32_t local) {
         m = max(m, (uint32_t)__shfl_xor((int)m, 2, 64));
         m = max(m, (uint32_t)__shfl_xor((int)m, 1, 64));
         float inv; bool dead;
-        const uint32_t scale = mxp_scale(m, j.fmt, inv, dead);
+        uint32_t scale = mxp_scale(m, j.fmt, inv, dead);
+        if constexpr (RULED != MX_PLAIN) {
+            uint32_t code = mx_rule_code(dead ? 0u : m, j.fmt, j.rule);
+            if (RULED == MX_SEARCH && j.rule == PPQHIP_MX_MSE) {              // workgroup-uniform
+                MxMse s(code);
+                s.add(a[k].x, ok[k], j.fmt); s.add(a[k].y, ok[k], j.fmt); s.add(a[k].z, ok[k], j.fmt); s.add(a[k].w, ok[k], j.fmt);
+                s.reduce<8>();
+                code = s.code();
+            }
+            scale = ruled_scale(code, dead, inv);
+        }
         const bool live = ok[k] && !dead;                                        // padding and NaN blocks: +0
         const uint32_t c0 = live ? mxp_code(a[k].x, inv, j.fmt, c) : 0u, c1 = live ? mxp_code(a[k].y, inv, j.fmt, c) : 0u;
         const uint32_t c2 = live ? mxp_code(a[k].z, inv, j.fmt, c) : 0u, c3 = live ? mxp_code(a[k].w, inv, j.fmt, c) : 0u;
@@ -123,6 +142,7 @@ __device__ __forceinline__ void pack_rows4(const MxPackJob& j, uint32_t local) {
     }
 }
 
+template <int RULED>
 __device__ __forceinline__ void pack_rows1(const MxPackJob& j, uint32_t local) {
     const MxCoder c = make_coder(j.format, j.fmt);
     const uint32_t q = threadIdx.x & 31u;
@@ -137,7 +157,17 @@ __device__ __forceinline__ void pack_rows1(const MxPackJob& j, uint32_t local) {
 #pragma unroll
     for (int s = 16; s > 0; s >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, s, 64));
     float inv; bool dead;
-    const uint32_t scale = mxp_scale(m, j.fmt, inv, dead);
+    uint32_t scale = mxp_scale(m, j.fmt, inv, dead);
+    if constexpr (RULED != MX_PLAIN) {
+        uint32_t code = mx_rule_code(dead ? 0u : m, j.fmt, j.rule);
+        if (RULED == MX_SEARCH && j.rule == PPQHIP_MX_MSE) {
+            MxMse s(code);
+            s.add(v, ok, j.fmt);
+            s.reduce<32>();
+            code = s.code();
+        }
+        scale = ruled_scale(code, dead, inv);
+    }
     const uint32_t mine = ok && !dead ? mxp_code(v, inv, j.fmt, c) : 0u;
     if (c.bits == 8u) {
         if (in) j.e[(size_t)g * 32u + q] = (uint8_t)mine;
@@ -173,7 +203,7 @@ __device__ __forceinline__ MxLane strided_lane(const MxPackJob& j, uint32_t loca
     return l;
 }
 
-template <int BITS, bool BYTES>
+template <int BITS, bool BYTES, int RULED>
 __device__ __forceinline__ void pack_strided(const MxPackJob& j, uint32_t local) {
     constexpr int NW = BITS;                                                     // dwords per block: 32 * BITS / 32
     const MxCoder c = make_coder(j.format, j.fmt);
@@ -185,7 +215,17 @@ __device__ __forceinline__ void pack_strided(const MxPackJob& j, uint32_t local)
 #pragma unroll
     for (uint32_t t = 0; t < kMxBlock; t++) m = max(m, t < l.blen ? mxp_mag(v[t], c) : 0u);
     float inv; bool dead;
-    const uint32_t scale = mxp_scale(m, j.fmt, inv, dead);
+    uint32_t scale = mxp_scale(m, j.fmt, inv, dead);
+    if constexpr (RULED != MX_PLAIN) {
+        uint32_t code = mx_rule_code(dead ? 0u : m, j.fmt, j.rule);
+        if (RULED == MX_SEARCH && j.rule == PPQHIP_MX_MSE) {
+            MxMse s(code);
+#pragma unroll
+            for (uint32_t t = 0; t < kMxBlock; t++) s.add(v[t], t < l.blen, j.fmt);
+            code = s.code();
+        }
+        scale = ruled_scale(code, dead, inv);
+    }
     if (!l.in) return;
     uint32_t w[NW];
 #pragma unroll
@@ -212,22 +252,29 @@ __device__ __forceinline__ void pack_strided(const MxPackJob& j, uint32_t local)
     j.s[l.blk] = (uint8_t)scale;
 }
 
-template <int CAP, int U>
+template <int CAP, int U, int RULED>
 __global__ __launch_bounds__(kBlock) void mx_pack_kernel(const MxPackArgs<CAP> args) {
     uint32_t local;
     const MxPackJob& j = args.jobs[job_of(args, local)];
     const uint32_t bits = mx_elem_bits(j.format);                                // workgroup-uniform, like the path
-    if (j.path == MXP_ROWS4) pack_rows4<U>(j, local);
-    else if (j.path == MXP_ROWS1) pack_rows1(j, local);
+    if (j.path == MXP_ROWS4) pack_rows4<U, RULED>(j, local);
+    else if (j.path == MXP_ROWS1) pack_rows1<RULED>(j, local);
     else if (j.path == MXP_STRIDED) {
-        if (bits == 8u) pack_strided<8, false>(j, local);
-        else if (bits == 6u) pack_strided<6, false>(j, local);
-        else pack_strided<4, false>(j, local);
+        if (bits == 8u) pack_strided<8, false, RULED>(j, local);
+        else if (bits == 6u) pack_strided<6, false, RULED>(j, local);
+        else pack_strided<4, false, RULED>(j, local);
     } else {
-        if (bits == 8u) pack_strided<8, true>(j, local);
-        else if (bits == 6u) pack_strided<6, true>(j, local);
-        else pack_strided<4, true>(j, local);
+        if (bits == 8u) pack_strided<8, true, RULED>(j, local);
+        else if (bits == 6u) pack_strided<6, true, RULED>(j, local);
+        else pack_strided<4, true, RULED>(j, local);
     }
+}
+
+template <int CAP, int U>
+void launch_pack(int ruled, uint32_t blocks, hipStream_t s, const MxPackArgs<CAP>& args) {
+    if (ruled == MX_SEARCH) hipLaunchKernelGGL((mx_pack_kernel<CAP, U, MX_SEARCH>), dim3(blocks), dim3(kBlock), 0, s, args);
+    else if (ruled == MX_AMAX_RULES) hipLaunchKernelGGL((mx_pack_kernel<CAP, U, MX_AMAX_RULES>), dim3(blocks), dim3(kBlock), 0, s, args);
+    else hipLaunchKernelGGL((mx_pack_kernel<CAP, U, MX_PLAIN>), dim3(blocks), dim3(kBlock), 0, s, args);
 }
 
 // ---- unpack --------------------------------------------------------------------------------------------------------------------
@@ -346,7 +393,9 @@ struct MxPackView {
     const uint8_t* e;
     const uint8_t* s;
     int64_t outer, axis_len, inner;
-    int format;
+    int format;                                   // the format alone
+    uint32_t rule;                                // pack: the scale rule that travelled above it
+    bool known;                                   // false: `format` is the argument as it came, with a rule nobody knows
     int64_t nb() const { return (axis_len + kMxBlock - 1) / kMxBlock; }
     int64_t elems() const { return outer * axis_len * inner; }
     int64_t blocks() const { return outer * inner * nb(); }
@@ -354,11 +403,17 @@ struct MxPackView {
     bool empty() const { return outer == 0 || axis_len == 0 || inner == 0; }
     double bytes() const { return 4.0 * (double)elems() + (double)blocks() * (double)(block_bytes() + 1); }
 };
-MxPackView view_of(const ppqhip_mx_pack_job& j) { return MxPackView{j.x, j.elements, j.scales, j.outer, j.axis_len, j.inner, j.format}; }
-MxPackView view_of(const ppqhip_mx_unpack_job& j) { return MxPackView{j.y, j.elements, j.scales, j.outer, j.axis_len, j.inner, j.format}; }
+MxPackView view_of(const ppqhip_mx_pack_job& j) {
+    MxPackView v{j.x, j.elements, j.scales, j.outer, j.axis_len, j.inner, j.format, PPQHIP_MX_FLOOR, false};
+    v.known = split_mx_format(j.format, &v.format, &v.rule);
+    return v;
+}
+// unpack makes no scales: the whole argument is the format, so that a rule byte is an unknown format
+MxPackView view_of(const ppqhip_mx_unpack_job& j) { return MxPackView{j.y, j.elements, j.scales, j.outer, j.axis_len, j.inner, j.format, PPQHIP_MX_FLOOR, true}; }
 
 int validate_job(const char* what, int k, const MxPackView& j) {
     MxFmt probe;
+    if (!j.known) { set_error("%s: job %d: unknown MX scale rule in format %d", what, k, j.format); return PPQHIP_ERR_INVALID_VALUE; }
     if (!make_mx_fmt(j.format, &probe)) { set_error("%s: job %d: unknown MX format %d", what, k, j.format); return PPQHIP_ERR_INVALID_VALUE; }
     if (j.outer < 0 || j.axis_len < 0 || j.inner < 0) { set_error("%s: job %d: negative size", what, k); return PPQHIP_ERR_INVALID_VALUE; }
     if (j.empty()) return PPQHIP_OK;
@@ -385,14 +440,15 @@ int validate(const char* what, bool packing, const Job* jobs, int num_jobs) {
     return check_overlap(what, ins, outs);
 }
 
-// the device job and the workgroups it takes when a rows4 lane owns U float4
-uint32_t device_job(const MxPackView& src, int U, MxPackJob* d) {
+// the device job and the workgroups it takes when a rows4 lane owns U float4; *ruled is raised to the class of the job's rule
+uint32_t device_job(const MxPackView& src, int U, MxPackJob* d, int* ruled) {
     d->f = const_cast<float*>(src.f); d->e = const_cast<uint8_t*>(src.e); d->s = const_cast<uint8_t*>(src.s);
     d->len = (uint32_t)src.axis_len;
     d->nb = make_fastdiv((uint32_t)src.nb());
     d->inner = make_fastdiv((uint32_t)src.inner);
     d->format = (uint32_t)src.format;
-    d->pad = 0;
+    d->rule = src.rule;
+    *ruled = std::max(*ruled, mx_rule_class(src.rule));
     make_mx_fmt(src.format, &d->fmt);
     const int64_t units = src.blocks();                                          // <= elements <= 2^31 - 1
     d->units = (uint32_t)units;
@@ -422,11 +478,12 @@ int run(const char* what, bool packing, const Job* jobs, int num_jobs, void* str
     if (live.size() == 1) {
         MxPackArgs<1> args;
         const int U = live[0].elems() <= kMxSmallElems ? 1 : 2;
-        const uint32_t blocks = device_job(live[0], U, &args.jobs[0]);
+        int ruled = MX_PLAIN;
+        const uint32_t blocks = device_job(live[0], U, &args.jobs[0], &ruled);
         args.first_block[0] = 0;
         args.count = 1;
-        if (packing && U == 2) hipLaunchKernelGGL((mx_pack_kernel<1, 2>), dim3(blocks), dim3(kBlock), 0, s, args);
-        else if (packing) hipLaunchKernelGGL((mx_pack_kernel<1, 1>), dim3(blocks), dim3(kBlock), 0, s, args);
+        if (packing && U == 2) launch_pack<1, 2>(ruled, blocks, s, args);
+        else if (packing) launch_pack<1, 1>(ruled, blocks, s, args);
         else if (U == 2) hipLaunchKernelGGL((mx_unpack_kernel<1, 2>), dim3(blocks), dim3(kBlock), 0, s, args);
         else hipLaunchKernelGGL((mx_unpack_kernel<1, 1>), dim3(blocks), dim3(kBlock), 0, s, args);
         return finish_launch(what);
@@ -435,13 +492,14 @@ int run(const char* what, bool packing, const Job* jobs, int num_jobs, void* str
         MxPackArgs<kMxMaxJobs> args;
         const uint32_t count = (uint32_t)std::min<size_t>(kMxMaxJobs, live.size() - base);
         uint64_t blocks = 0;
+        int ruled = MX_PLAIN;
         for (uint32_t k = 0; k < count; k++) {
             args.first_block[k] = (uint32_t)blocks;
-            blocks += device_job(live[base + k], 1, &args.jobs[k]);
+            blocks += device_job(live[base + k], 1, &args.jobs[k], &ruled);
         }
         if (blocks > (uint64_t)kMxMax) { set_error("%s: too many workgroups in one launch", what); return PPQHIP_ERR_INVALID_VALUE; }
         pad_job_table(args, count, (uint32_t)blocks);
-        if (packing) hipLaunchKernelGGL((mx_pack_kernel<kMxMaxJobs, 1>), dim3((uint32_t)blocks), dim3(kBlock), 0, s, args);
+        if (packing) launch_pack<kMxMaxJobs, 1>(ruled, (uint32_t)blocks, s, args);
         else hipLaunchKernelGGL((mx_unpack_kernel<kMxMaxJobs, 1>), dim3((uint32_t)blocks), dim3(kBlock), 0, s, args);
     }
     return finish_launch(what);

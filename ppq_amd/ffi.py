@@ -1011,6 +1011,30 @@ def mx_format_id(format) -> int:
     raise ValueError(f'unknown MX format {format!r}: expected one of {", ".join(MX_FORMATS)}')
 
 
+MX_SCALE_RULES = {'FLOOR': 0, 'CEIL': 1, 'EVEN': 2, 'MSE': 3}      # PPQHIP_MX_FLOOR .. PPQHIP_MX_MSE
+MX_RULE_SHIFT = 8                                                   # PPQHIP_MX_RULE_SHIFT
+
+
+def mx_rule_id(rule) -> int:
+    """The library's id of an MX scale rule given as ``ppq_amd.mx.MXScaleRule``, its name or the id itself; None is FLOOR."""
+    if rule is None: return MX_SCALE_RULES['FLOOR']
+    key = getattr(rule, 'name', rule)
+    if isinstance(key, str) and key in MX_SCALE_RULES: return MX_SCALE_RULES[key]
+    if isinstance(key, int) and not isinstance(key, bool) and key in MX_SCALE_RULES.values(): return key
+    raise ValueError(f'unknown MX scale rule {rule!r}: expected one of {", ".join(MX_SCALE_RULES)}')
+
+
+def mx_format_arg(format, scale_rule=None) -> int:
+    """The ``format`` argument of the entry points that make scales: ``format | rule << 8`` (FLOOR: the format's id as it is)."""
+    return mx_format_id(format) | (mx_rule_id(scale_rule) << MX_RULE_SHIFT)
+
+
+def _mx_item(item):
+    """``(value, format, axis)`` or ``(value, format, axis, scale_rule)`` of a plan as (value, format, axis, rule id)."""
+    if len(item) not in (3, 4): raise ValueError(f'an MX plan item is (value, format, axis[, scale_rule]), got {len(item)} entries')
+    return item[0], item[1], item[2], mx_rule_id(item[3] if len(item) == 4 else None)
+
+
 def _mx_axis(ndim: int, axis: int) -> int:
     if not isinstance(axis, int) or not -ndim <= axis < ndim:
         raise RuntimeError(_KERNEL_FAILURE + f'axis {axis} out of range for a {ndim}-d tensor')
@@ -1047,16 +1071,18 @@ class MXQuantizePlan:
     inputs -- bits identical to ``CUDA.MXQuantize`` per item.  The job table travels in the kernel arguments and holds POINTERS to
     the callers' tensors: in-place updates are seen by later runs, a REPLACED tensor needs a new plan.  A value that is not dense
     (contiguous, or 4-D channels-last along axis 1) would need a private copy that later updates never reach: refused
-    (``accepts()``).  ``with_codes``: also keep every item's E8M0 scale codes (``codes``)."""
+    (``accepts()``).  ``with_codes``: also keep every item's E8M0 scale codes (``codes``).  An item may carry a fourth entry, its
+    scale rule (``ppq_amd.mx.MXScaleRule``; default FLOOR): one launch serves any mix of rules and formats."""
     @ staticmethod
     def accepts(value, axis) -> bool:
         return value.dim() > 0 and -value.dim() <= axis < value.dim() and _mx_dense(value, axis % value.dim()) is value
 
     def __init__(self, items, with_codes: bool = False):
         if not items: raise ValueError('MXQuantizePlan needs at least one item')
+        items = [_mx_item(item) for item in items]
         dev = items[0][0].device
         total = 0
-        for value, format, axis in items:
+        for value, format, axis, _ in items:
             _f32(value, 'Value')
             if value.device != dev: raise RuntimeError(_KERNEL_FAILURE + 'MXQuantizePlan: every tensor must live on one device')
             if not MXQuantizePlan.accepts(value, _mx_axis(value.dim(), axis)):
@@ -1066,7 +1092,7 @@ class MXQuantizePlan:
         self._jobs = np.zeros(len(items), dtype=_MX_JOB)
         self._keep, self._outs, self.codes = [], [], []
         at = 0
-        for k, (v, format, axis) in enumerate(items):
+        for k, (v, format, axis, rule) in enumerate(items):
             axis = _mx_axis(v.dim(), axis)
             outer, length, inner, codes_shape = _mx_geometry(v, axis)
             out = self._arena[at: at + v.numel()].as_strided(v.shape, v.stride())     # same memory format as the input
@@ -1074,7 +1100,7 @@ class MXQuantizePlan:
             codes = _mx_codes_like(v, axis, codes_shape) if with_codes else None
             self._keep.append(v); self._outs.append(out); self.codes.append(codes)
             self._jobs[k] = (v.data_ptr(), out.data_ptr(), codes.data_ptr() if with_codes else 0, outer, length, inner,
-                             mx_format_id(format), 0)
+                             mx_format_arg(format, rule), 0)
         self.bytes = 8 * sum(v.numel() for v in self._keep)
 
     def run(self) -> List[torch.Tensor]:
@@ -1182,14 +1208,15 @@ class MXPackPlan:
     (``ppqhip_mx_pack_multi``).  Built once from ``(value, format, axis)`` items; ``run()`` packs all of them into one resident
     uint8 arena (every ``elements`` and every ``scales`` starts 16-B aligned) and returns ``[(elements, scales)]`` -- bytes identical
     to ``CUDA.MXPack`` per item.  The table holds POINTERS to the callers' tensors: in-place updates are seen by later runs; a value
-    that is not dense in storage order is refused (``MXQuantizePlan.accepts``)."""
+    that is not dense in storage order is refused (``MXQuantizePlan.accepts``).  An item may carry its scale rule as a fourth entry."""
     accepts = staticmethod(MXQuantizePlan.accepts)
 
     def __init__(self, items):
         if not items: raise ValueError('MXPackPlan needs at least one item')
+        items = [_mx_item(item) for item in items]
         dev = items[0][0].device
         geometry, total = [], 0
-        for value, format, axis in items:
+        for value, format, axis, _ in items:
             _f32(value, 'Value')
             if value.device != dev: raise RuntimeError(_KERNEL_FAILURE + 'MXPackPlan: every tensor must live on one device')
             axis = _mx_axis(value.dim(), axis)
@@ -1202,7 +1229,7 @@ class MXPackPlan:
         self._jobs = np.zeros(len(items), dtype=_MX_PACK_JOB)
         self._keep, self._outs = [], []
         at = 0
-        for k, ((v, format, _), (axis, eshape, sshape)) in enumerate(zip(items, geometry)):
+        for k, ((v, format, _, rule), (axis, eshape, sshape)) in enumerate(zip(items, geometry)):
             outer, length, inner, _ = _mx_geometry(v, axis)
             ne, ns = math.prod(eshape), math.prod(sshape)
             elements = self._arena[at: at + ne].view(eshape)
@@ -1210,7 +1237,7 @@ class MXPackPlan:
             scales = self._arena[at: at + ns].view(sshape)
             at += (ns + 15) // 16 * 16
             self._keep.append(v); self._outs.append((elements, scales))
-            self._jobs[k] = (v.data_ptr(), elements.data_ptr(), scales.data_ptr(), outer, length, inner, mx_format_id(format), 0)
+            self._jobs[k] = (v.data_ptr(), elements.data_ptr(), scales.data_ptr(), outer, length, inner, mx_format_arg(format, rule), 0)
         self.bytes = sum(4 * v.numel() + e.numel() + s.numel() for v, (e, s) in zip(self._keep, self._outs))
 
     def run(self):
@@ -2259,13 +2286,15 @@ class CUDA:
         return HIP_EXTENSION.MSE_Search(histogram, hist_scale, min_value, quant_min, quant_max, symmetrical)
 
     @ staticmethod
-    def MXQuantize(tensor, format, axis: int, block_size: int = MX_BLOCK, scale_codes=None):
+    def MXQuantize(tensor, format, axis: int, block_size: int = MX_BLOCK, scale_codes=None, scale_rule=None):
         """OCP Microscaling fake quant (MI355X-native; the contract is DESIGN.md section 9): blocks of 32 along ``axis`` share one
         power-of-two scale, elements are cast to ``format`` (``ppq_amd.mx.MXFormat``, its name or id).  ``scale_codes``: an
         optional uint8 tensor with the input's shape, the axis replaced by ceil(len / 32), that receives the E8M0 codes.
-        A 4-D channels-last tensor quantised along axis 1 is read in storage order; any other non-contiguous one is copied."""
+        A 4-D channels-last tensor quantised along axis 1 is read in storage order; any other non-contiguous one is copied.
+        ``scale_rule``: how a block's scale is made from its values (``ppq_amd.mx.MXScaleRule``, its name or id; DESIGN.md section
+        9.17) -- FLOOR (the default), CEIL, EVEN or MSE."""
         if block_size != MX_BLOCK: raise ValueError(f'MX block size is {MX_BLOCK}, got {block_size}')
-        fmt = mx_format_id(format)
+        fmt = mx_format_arg(format, scale_rule)
         _f32(tensor, 'Value')
         axis = _mx_axis(tensor.dim(), axis)
         v = _mx_dense(tensor, axis)
@@ -2284,18 +2313,18 @@ class CUDA:
         return out
 
     @ staticmethod
-    def MXPack(tensor, format, axis: int, block_size: int = MX_BLOCK):
+    def MXPack(tensor, format, axis: int, block_size: int = MX_BLOCK, scale_rule=None):
         """Packed OCP Microscaling export: ``(elements, scales)``, two uint8 tensors with the block axis
         LAST -- the input's shape without ``axis`` plus ``[nb * B]`` resp. ``[nb]`` (nb = ceil(len / 32); B = 32 / 24 / 16 bytes per
         block for 8 / 6 / 4-bit elements).  Blocks, scales and rounding are those of ``MXQuantize``.  A 4-D channels-last tensor packed
-        along axis 1 is read in storage order; any other non-contiguous one is copied."""
+        along axis 1 is read in storage order; any other non-contiguous one is copied.  ``scale_rule``: as for ``MXQuantize``."""
         if block_size != MX_BLOCK: raise ValueError(f'MX block size is {MX_BLOCK}, got {block_size}')
-        fmt = mx_format_id(format)
+        fmt = mx_format_arg(format, scale_rule)
         _f32(tensor, 'Value')
         axis = _mx_axis(tensor.dim(), axis)
         v = _mx_dense(tensor, axis)
         outer, length, inner, _ = _mx_geometry(v, axis)
-        eshape, sshape = mx_packed_shapes(v.shape, axis, fmt)
+        eshape, sshape = mx_packed_shapes(v.shape, axis, format)
         elements = torch.empty(eshape, dtype=torch.uint8, device=v.device)
         scales = torch.empty(sshape, dtype=torch.uint8, device=v.device)
         with _DeviceOf(v):

@@ -8,7 +8,8 @@ reference has no MX: the contract (restated by ``tests/mx_r
 
 NaN passes through, +-Inf saturates, zero keeps its sign, float32 subnormals are honoured.  Every step is exact in float32, so the
 HIP kernels (``ppq_amd/csrc/mx.hip``, ``use_kernels=True``) and the torch restatement below (``use_kernels=False``, any device)
-give identical bits.
+give identical bits.  That ``se`` is the OCP floor rule, ``MXScaleRule.FLOOR`` and the default everywhere; ``scale_rule=`` chooses
+``CEIL``, ``EVEN`` or ``MSE`` instead (restated by ``tests/mx_scale_reference.py``), in the same one launch.
 
 ``mx_quantize`` / ``mx_dequantize`` are the export: the element codes and E8M0 scales a block-scaled GEMM or a checkpoint stores
 (``MXTensor``; the packed contract is DESIGN.md section 9.13, restated by ``tests/mx_pack_reference.py``), cut from the same rounded
@@ -29,7 +30,7 @@ import torch
 from torch.autograd import Function
 
 from .core import (FloatingQuantizationConfig, LinearQuantizationConfig, QuantizationStates)
-from .ffi import CUDA, MX_BLOCK, MX_FORMATS, MXPackPlan, MXQuantizePlan, mx_format_id, mx_packed_shapes
+from .ffi import CUDA, MX_BLOCK, MX_FORMATS, MX_SCALE_RULES, MXPackPlan, MXQuantizePlan, mx_format_id, mx_packed_shapes, mx_rule_id
 
 # name -> (exponent bits, mantissa bits, smallest normal exponent, emax, largest normal); MXINT8: k / 64 with |k| <= 127
 _SPEC = {
@@ -73,6 +74,25 @@ class MXFormat(Enum):
         return cls(mx_format_id(format))
 
 
+class MXScaleRule(Enum):
+    """How a block's E8M0 scale is made from its values; the value is the id the HIP library knows the
+    rule by.  With ``code_f`` the floor code ``max(exponent(amax) - emax, 0)`` and every code clamped to 254:
+    ``FLOOR`` -- ``code_f``, the OCP rule: amax / X may lie above the largest normal and saturate;
+    ``CEIL`` -- ``code_f + 1`` when amax / X would saturate: the largest element is never clipped;
+    ``EVEN`` -- the floor code of amax rounded to the element's precision: one more only when amax rounds up into the next binade;
+    ``MSE`` -- of ``code_f`` and ``code_f + 1`` the one with the smaller squared error over the block (a tie keeps ``code_f``)."""
+    FLOOR = MX_SCALE_RULES['FLOOR']
+    CEIL = MX_SCALE_RULES['CEIL']
+    EVEN = MX_SCALE_RULES['EVEN']
+    MSE = MX_SCALE_RULES['MSE']
+
+    @ classmethod
+    def of(cls, rule) -> 'MXScaleRule':
+        """``rule`` as a member: a member, its name, the library's id, or None (FLOOR)."""
+        if isinstance(rule, cls): return rule
+        return cls(mx_rule_id(rule))
+
+
 def _bits_to_float(bits: torch.Tensor) -> torch.Tensor:
     return bits.to(torch.int32).view(torch.float32)
 
@@ -82,26 +102,10 @@ def _pow2(biased: torch.Tensor) -> torch.Tensor:
     return _bits_to_float(torch.where(biased > 0, biased << 23, torch.full_like(biased, 0x00400000)))
 
 
-def _mx_torch(tensor: torch.Tensor, format: MXFormat, axis: int, scale_codes: Optional[torch.Tensor]) -> torch.Tensor:
-    """The contract in torch ops, on the tensor's device: integer arithmetic on the float32 patterns, exact float32 products."""
-    _, m, emin, emax, max_normal = _SPEC[format.name]
-    length = tensor.shape[axis]
-    nb = (length + MX_BLOCK - 1) // MX_BLOCK
-    x = tensor.movedim(axis, -1)
-    lead = list(x.shape[:-1])
-    x = x.contiguous()
-    if nb * MX_BLOCK != length:                       # zeros take no part in amax; the padding is cut off again below
-        x = torch.nn.functional.pad(x, (0, nb * MX_BLOCK - length))
-    x = x.reshape(lead + [nb, MX_BLOCK])
-    bits = x.view(torch.int32)
-    mag = bits & 0x7fffffff
-    amax = torch.where(mag < 0x7f800000, mag, torch.zeros_like(mag)).amax(dim=-1, keepdim=True)
-    code = ((amax >> 23) - emax).clamp_(min=0)
-    scale, inv = _pow2(code), _pow2(254 - code)
-    u = x * inv
-    ubits = u.view(torch.int32)
-    umag = ubits & 0x7fffffff
-    sign = ubits & -0x80000000
+def _mx_round(umag: torch.Tensor, format: MXFormat) -> torch.Tensor:
+    """The cast of |u| on its float32 pattern (``mx_round`` of mx_common.hpp): the pattern of the nearest element value, ties to
+    the even encoding, saturating at the largest normal.  A NaN pattern gives a pattern nobody may use."""
+    _, m, emin, _, max_normal = _SPEC[format.name]
     max_bits = int(torch.tensor(max_normal, dtype=torch.float32).view(torch.int32))
     if format.is_float:
         shift = 23 - m
@@ -111,9 +115,54 @@ def _mx_torch(tensor: torch.Tensor, format: MXFormat, axis: int, scale_codes: Op
         r = torch.where(umag < ((emin + 127) << 23), grid, normal)
     else:
         r = (torch.round(_bits_to_float(umag) * 64.0) * 0.015625).view(torch.int32)
-    r = torch.minimum(r, torch.full_like(r, max_bits))
-    y = _bits_to_float(r | sign) * scale
-    y = torch.where(umag > 0x7f800000, x, y)          # NaN: the input's own bits
+    return torch.minimum(r, torch.full_like(r, max_bits))
+
+
+def _mx_values(x: torch.Tensor, code: torch.Tensor, format: MXFormat) -> torch.Tensor:
+    """cast(x / X) * X for X = 2^(code - 127); a NaN keeps its bits."""
+    ubits = (x * _pow2(254 - code)).view(torch.int32)
+    umag = ubits & 0x7fffffff
+    y = _bits_to_float(_mx_round(umag, format) | (ubits & -0x80000000)) * _pow2(code)
+    return torch.where(umag > 0x7f800000, x, y)
+
+
+def _mx_scale_code(x: torch.Tensor, format: MXFormat, rule: MXScaleRule) -> torch.Tensor:
+    """The E8M0 code (int32, ``[..., nb, 1]``) of every block of ``x`` ``[..., nb, 32]`` under ``rule``: ``mx_rule_code`` and ``MxMse``
+    of mx_common.hpp in torch ops."""
+    _, m, _, emax, max_normal = _SPEC[format.name]
+    mag = x.view(torch.int32) & 0x7fffffff
+    finite = mag < 0x7f800000
+    amax = torch.where(finite, mag, torch.zeros_like(mag)).amax(dim=-1, keepdim=True)
+    floor_code = ((amax >> 23) - emax).clamp_(min=0)
+    if rule is MXScaleRule.FLOOR: return floor_code
+    if rule is MXScaleRule.CEIL:
+        max_bits = int(torch.tensor(max_normal, dtype=torch.float32).view(torch.int32))
+        scaled = (_bits_to_float(amax) * _pow2(254 - floor_code)).view(torch.int32)              # exact: a power of two
+        return (floor_code + (scaled > max_bits).to(torch.int32)).clamp_(max=254)
+    if rule is MXScaleRule.EVEN:
+        return (((amax + (1 << (22 - m))) >> 23) - emax).clamp_(min=0, max=254)
+    c0, c1 = floor_code, (floor_code + 1).clamp_(max=254)
+    errors = []
+    for c in (c0, c1):                                 # the same ops in the same order: equal candidates give equal sums
+        d = _mx_values(x, c, format) - x               # exact in float32
+        d = torch.where(finite, d, torch.zeros_like(d)).to(torch.float64)
+        errors.append((d * d).sum(dim=-1, keepdim=True))
+    return torch.where(errors[1] < errors[0], c1, c0)
+
+
+def _mx_torch(tensor: torch.Tensor, format: MXFormat, axis: int, scale_codes: Optional[torch.Tensor],
+              scale_rule: MXScaleRule = MXScaleRule.FLOOR) -> torch.Tensor:
+    """The contract in torch ops, on the tensor's device: integer arithmetic on the float32 patterns, exact float32 products."""
+    length = tensor.shape[axis]
+    nb = (length + MX_BLOCK - 1) // MX_BLOCK
+    x = tensor.movedim(axis, -1)
+    lead = list(x.shape[:-1])
+    x = x.contiguous()
+    if nb * MX_BLOCK != length:                       # zeros take no part in amax; the padding is cut off again below
+        x = torch.nn.functional.pad(x, (0, nb * MX_BLOCK - length))
+    x = x.reshape(lead + [nb, MX_BLOCK])
+    code = _mx_scale_code(x, format, scale_rule)
+    y = _mx_values(x, code, format)                   # NaN: the input's own bits
     y = y.reshape(lead + [nb * MX_BLOCK])[..., :length].movedim(-1, axis)
     if scale_codes is not None:
         scale_codes.copy_(code.reshape(lead + [nb]).movedim(-1, axis).to(torch.uint8))
@@ -140,24 +189,26 @@ def _check_input(tensor, axis) -> int:
 
 class _MXFakeQuant(Function):
     @ staticmethod
-    def forward(ctx, tensor, format, axis, scale_codes, use_kernels):
-        if use_kernels: return CUDA.MXQuantize(tensor, format, axis, MX_BLOCK, scale_codes)
-        return _mx_torch(tensor, format, axis, scale_codes)
+    def forward(ctx, tensor, format, axis, scale_codes, use_kernels, scale_rule):
+        if use_kernels: return CUDA.MXQuantize(tensor, format, axis, MX_BLOCK, scale_codes, scale_rule)
+        return _mx_torch(tensor, format, axis, scale_codes, scale_rule)
 
     @ staticmethod
     def backward(ctx, dy: torch.Tensor):
-        return dy, None, None, None, None
+        return dy, None, None, None, None, None
 
 
-def mx_fake_quant(tensor: torch.Tensor, format, axis: int = -1, scale_codes: torch.Tensor = None, use_kernels: bool = True) -> torch.Tensor:
+def mx_fake_quant(tensor: torch.Tensor, format, axis: int = -1, scale_codes: torch.Tensor = None, use_kernels: bool = True,
+                  scale_rule=MXScaleRule.FLOOR) -> torch.Tensor:
     """MX fake quant of ``tensor`` with blocks of 32 along ``axis``; straight-through backward (``dy`` as it is).
     ``scale_codes``: optional uint8 tensor (the input's shape, the axis replaced by ceil(len / 32)) that receives the E8M0 codes.
     ``use_kernels=True``: the HIP kernels (the tensor must be on the GPU).  ``False``: the torch restatement of the same contract
-    on whatever device the tensor lives on -- identical bits."""
-    format = MXFormat.of(format)
+    on whatever device the tensor lives on -- identical bits.  ``scale_rule``: how the block's scale is made (``MXScaleRule``, its
+    name or id): FLOOR, the OCP rule, by default."""
+    format, scale_rule = MXFormat.of(format), MXScaleRule.of(scale_rule)
     axis = _check_input(tensor, axis)
     _check_codes(tensor, axis, scale_codes)
-    return _MXFakeQuant.apply(tensor, format, axis, scale_codes, use_kernels)
+    return _MXFakeQuant.apply(tensor, format, axis, scale_codes, use_kernels, scale_rule)
 
 
 # ---- the packed export (DESIGN.md section 9.13) ------------------------------------------------------------------------------------
@@ -165,9 +216,9 @@ def _element_bits(format: MXFormat) -> int:
     return 8 if format is MXFormat.MXINT8 else 1 + format.exponent_bits + format.mantissa_bits
 
 
-def _mx_pack_torch(tensor: torch.Tensor, format: MXFormat, axis: int):
+def _mx_pack_torch(tensor: torch.Tensor, format: MXFormat, axis: int, scale_rule: MXScaleRule = MXScaleRule.FLOOR):
     """The packed contract in torch ops, on the tensor's device: the rounded pattern of ``_mx_torch``, then the code read off it."""
-    _, m, emin, emax, max_normal = _SPEC[format.name]
+    _, m, emin, _, _ = _SPEC[format.name]
     width, fp8 = _element_bits(format), format in (MXFormat.MXFP8_E4M3, MXFormat.MXFP8_E5M2)
     length = tensor.shape[axis]
     nb = (length + MX_BLOCK - 1) // MX_BLOCK
@@ -180,24 +231,16 @@ def _mx_pack_torch(tensor: torch.Tensor, format: MXFormat, axis: int):
     mag = bits & 0x7fffffff
     sign = (bits >> 31) & 1
     isnan = mag > 0x7f800000
-    amax = torch.where(mag < 0x7f800000, mag, torch.zeros_like(mag)).amax(dim=-1, keepdim=True)
-    scale = ((amax >> 23) - emax).clamp_(min=0)
+    scale = _mx_scale_code(x, format, scale_rule)
     umag = (x * _pow2(254 - scale)).view(torch.int32) & 0x7fffffff
-    max_bits = int(torch.tensor(max_normal, dtype=torch.float32).view(torch.int32))
+    r = _mx_round(umag, format)
     if format.is_float:
         shift = 23 - m
-        finite = torch.where(umag > 0x7f800000, torch.zeros_like(umag), umag)
-        normal = (finite + ((1 << (shift - 1)) - 1) + ((finite >> shift) & 1)) & ~((1 << shift) - 1)
-        grid = (torch.round(_bits_to_float(umag) * 2.0 ** (m - emin)) * 2.0 ** (emin - m)).view(torch.int32)
-        r = torch.where(umag < ((emin + 127) << 23), grid, normal)
-        r = torch.minimum(r, torch.full_like(r, max_bits))
         index = (_bits_to_float(r) * 2.0 ** (m - emin)).to(torch.int32)                            # the grid's index: exact
         code = torch.where(r < ((emin + 127) << 23), index, (r >> shift) - ((emin + 126) << m))     # emin + 126 = 127 - bias
         if fp8: code = torch.where(isnan, torch.full_like(code, 0x7f), code)
         code = code | (sign << (width - 1))
     else:
-        r = (torch.round(_bits_to_float(umag) * 64.0) * 0.015625).view(torch.int32)
-        r = torch.minimum(r, torch.full_like(r, max_bits))
         k = (_bits_to_float(r) * 64.0).to(torch.int32)
         code = torch.where(sign == 1, -k, k) & 0xff
     if not fp8:                                        # no NaN encoding: the block is NaN as a whole
@@ -308,13 +351,15 @@ class MXTensor:
         return f'MXTensor({self.format.name}, shape={list(self.shape)}, axis={self.axis}, {self.nbytes} bytes on {self.device})'
 
 
-def mx_quantize(tensor: torch.Tensor, format, axis: int = -1, use_kernels: bool = True) -> MXTensor:
+def mx_quantize(tensor: torch.Tensor, format, axis: int = -1, use_kernels: bool = True, scale_rule=MXScaleRule.FLOOR) -> MXTensor:
     """``tensor`` in packed MX form, blocks of 32 along ``axis``: the blocks, scales and roundings of ``mx_fake_quant``, stored as
     element codes and E8M0 scale codes.  ``use_kernels=True``: the HIP kernel (the tensor must be on the GPU); ``False``: the torch
-    restatement on whatever device the tensor lives on -- identical bytes."""
-    format = MXFormat.of(format)
+    restatement on whatever device the tensor lives on -- identical bytes.  ``scale_rule``: as for ``mx_fake_quant``; the rule is
+    not part of the packed tensor, whose scales say all a reader needs."""
+    format, scale_rule = MXFormat.of(format), MXScaleRule.of(scale_rule)
     axis = _check_input(tensor, axis)
-    elements, scales = CUDA.MXPack(tensor, format, axis, MX_BLOCK) if use_kernels else _mx_pack_torch(tensor.detach(), format, axis)
+    if use_kernels: elements, scales = CUDA.MXPack(tensor, format, axis, MX_BLOCK, scale_rule)
+    else: elements, scales = _mx_pack_torch(tensor.detach(), format, axis, scale_rule)
     return MXTensor(format, tensor.shape, axis, elements, scales)
 
 
@@ -412,11 +457,12 @@ def mx_matmul(a: MXTensor, b: MXTensor, bias: torch.Tensor = None, use_kernels: 
 
 
 def mx_linear(x: torch.Tensor, weight: MXTensor, activation_format, bias: torch.Tensor = None, use_kernels: bool = True,
-              residual: torch.Tensor = None, relu: bool = False, out_format=None, out_float: bool = None):
+              residual: torch.Tensor = None, relu: bool = False, out_format=None, out_float: bool = None, scale_rule=MXScaleRule.FLOOR):
     """A linear layer on an MX weight as it runs in deployment: ``mx_quantize(x, activation_format, -1)``, then ``mx_matmul`` with
     ``weight`` ``[N, K]`` -- two launches, the bias added in the GEMM's epilogue (one float32 add per output).  ``residual``, ``relu``,
-    ``out_format`` and ``out_float`` are ``mx_matmul``'s."""
-    return mx_matmul(mx_quantize(x, activation_format, -1, use_kernels=use_kernels), weight, bias, use_kernels, residual, relu, out_format, out_float)
+    ``out_format`` and ``out_float`` are ``mx_matmul``'s; ``scale_rule`` is the rule of the activation's quantisation (``out_format``
+    is packed by FLOOR)."""
+    return mx_matmul(mx_quantize(x, activation_format, -1, use_kernels=use_kernels, scale_rule=scale_rule), weight, bias, use_kernels, residual, relu, out_format, out_float)
 
 
 # ---- convolution on the packed tensors (DESIGN.md section 9.15) --------------------------------------------------------------------
@@ -489,13 +535,14 @@ def mx_conv2d_packed(x: MXTensor, w: MXTensor, bias: torch.Tensor = None, stride
 
 def mx_conv2d(x: torch.Tensor, weight: MXTensor, activation_format, bias: torch.Tensor = None, stride=1, padding=0, dilation=1,
               groups: int = 1, use_kernels: bool = True, residual: torch.Tensor = None, relu: bool = False, out_format=None,
-              out_float: bool = None):
+              out_float: bool = None, scale_rule=MXScaleRule.FLOOR):
     """A convolution on an MX weight as it runs in deployment: ``mx_quantize(x, activation_format, 1)`` -- ``x`` ``[N, C, H, W]``,
     contiguous or channels-last --, then ``mx_conv2d_packed`` with ``weight`` ``[O, C, kh, kw]``: two launches, the bias added in the
-    kernel's epilogue (one float32 add per output).  ``residual``, ``relu``, ``out_format`` and ``out_float`` are ``mx_conv2d_packed``'s."""
+    kernel's epilogue (one float32 add per output).  ``residual``, ``relu``, ``out_format`` and ``out_float`` are ``mx_conv2d_packed``'s;
+    ``scale_rule`` is the rule of the activation's quantisation (``out_format`` is packed by FLOOR)."""
     if groups != 1: raise RuntimeError(f'mx_conv2d: groups must be 1, got {groups}')
     if isinstance(x, torch.Tensor) and x.dim() != 4: raise RuntimeError(f'mx_conv2d: x must be 4-d [N, C, H, W], got shape {list(x.shape)}')
-    return mx_conv2d_packed(mx_quantize(x, activation_format, 1, use_kernels=use_kernels), weight, bias, stride, padding, dilation, use_kernels,
+    return mx_conv2d_packed(mx_quantize(x, activation_format, 1, use_kernels=use_kernels, scale_rule=scale_rule), weight, bias, stride, padding, dilation, use_kernels,
                             residual, relu, out_format, out_float)
 
 
@@ -509,7 +556,8 @@ class MXWeightGroup:
     (``data_ptr``, shape or strides changed: the plan is rebuilt) or the same one written in place (``_version``).  One refill
     serves every member, so a forward over unchanged weights launches nothing, and a step that updated all of them launches once."""
     def __init__(self, members):
-        self.members = members                      # [(variable, format, axis)]
+        self.members = [tuple(m[:3]) for m in members]                                 # [(variable, format, axis)]
+        self.rules = [MXScaleRule.of(m[3] if len(m) > 3 else None) for m in members]   # each member's scale rule (an optional fourth entry)
         self.plan = None
         self.stamps: List[tuple] = [None] * len(members)
         self.outputs = None
@@ -532,7 +580,7 @@ class MXWeightGroup:
     def refresh(self) -> None:
         stamps = [self._stamp(var.value) for var, _, _ in self.members]
         same = self.plan is not None and all(a is not None and a[0] == b[0] and a[2:] == b[2:] for a, b in zip(self.stamps, stamps))
-        if not same: self.plan = MXQuantizePlan([(var.value, fmt, axis) for var, fmt, axis in self.members])
+        if not same: self.plan = MXQuantizePlan([(var.value, fmt, axis, rule) for (var, fmt, axis), rule in zip(self.members, self.rules)])
         self.outputs = self.plan.run()
         self.stamps = stamps
         self.launches += 1
@@ -541,9 +589,11 @@ class MXWeightGroup:
 class MXDelegator:
     """``delegator(tensor, config)`` for ``TorchExecutor.register_quantize_delegate`` (this package's harness and the reference's
     executor alike): MX fake quant of the tensor with blocks along ``axis``.  A config that is not activated (a dequantised
-    operation) passes the tensor through, as the default quantize function does."""
-    def __init__(self, format, axis: int, use_kernels: bool = True):
+    operation) passes the tensor through, as the default quantize function does.  ``scale_rule``: the ``MXScaleRule`` of the blocks'
+    scales (FLOOR by default)."""
+    def __init__(self, format, axis: int, use_kernels: bool = True, scale_rule=MXScaleRule.FLOOR):
         self.format = MXFormat.of(format)
+        self.scale_rule = MXScaleRule.of(scale_rule)
         self.axis = axis
         self.use_kernels = use_kernels
         self.group, self.slot, self.var = None, None, None     # set by quantize_graph_mx: this weight rides the graph's one launch
@@ -552,10 +602,15 @@ class MXDelegator:
         if not _activated(config): return tensor
         if self.group is not None and tensor is self.var.value and MXWeightGroup.eligible(self.var, self.axis):
             return self.group.output(self.slot)
-        return mx_fake_quant(tensor, self.format, self.axis, use_kernels=self.use_kernels)
+        return mx_fake_quant(tensor, self.format, self.axis, use_kernels=self.use_kernels, scale_rule=self.scale_rule)
 
 
-def _mx_config(format: MXFormat, device):
+def _config_rule(config) -> MXScaleRule:
+    """The scale rule recorded in a config's detail; an absent entry means FLOOR."""
+    return MXScaleRule.of(getattr(config, 'detail', {}).get('MX_SCALE_RULE'))
+
+
+def _mx_config(format: MXFormat, device, scale_rule: MXScaleRule = MXScaleRule.FLOOR):
     """An ACTIVATED config that describes the element format to every report that reads configs; scale 1, offset 0 (the block
     scales live in the data, not in the config)."""
     if format.is_float:
@@ -567,6 +622,7 @@ def _mx_config(format: MXFormat, device):
     c.offset = torch.zeros(1, dtype=torch.float32, device=device)
     c.state = QuantizationStates.ACTIVATED
     c.detail['MX_FORMAT'] = format.name
+    if scale_rule is not MXScaleRule.FLOOR: c.detail['MX_SCALE_RULE'] = scale_rule.name
     return c
 
 
@@ -583,14 +639,18 @@ def mx_block_axis(op_type: str, input_index: int) -> int:
     return -1
 
 
-def quantize_graph_mx(graph, executor, weight_format, activation_format, operations=None, use_kernels: bool = True) -> dict:
+def quantize_graph_mx(graph, executor, weight_format, activation_format, operations=None, use_kernels: bool = True,
+                      weight_scale_rule=MXScaleRule.FLOOR, activation_scale_rule=MXScaleRule.FLOOR) -> dict:
     """The policy of ``harness.quantize_graph_fp8`` with MX formats: only the inputs of Conv / Gemm / MatMul are quantised, weights
     with ``weight_format`` and activations with ``activation_format``, blocks along the reduction
     axis (``mx_block_axis``); bias and everything else stay FP32.  Each quantised input gets an ACTIVATED config and an
     ``MXDelegator`` registered on ``executor``; with ``use_kernels`` all weights share one ``MXWeightGroup``.  ``operations``: names
-    of the operations to quantise (default: all).  Returns config -> delegator."""
+    of the operations to quantise (default: all).  ``weight_scale_rule`` / ``activation_scale_rule``: the ``MXScaleRule`` of the
+    weights' resp. the activations' block scales, kept on the delegator and, where it is not FLOOR, as
+    ``config.detail['MX_SCALE_RULE']``.  Returns config -> delegator."""
     from .harness import OperationQuantizationConfig, QuantableOperation
     wfmt, afmt = MXFormat.of(weight_format), MXFormat.of(activation_format)
+    wrule, arule = MXScaleRule.of(weight_scale_rule), MXScaleRule.of(activation_scale_rule)
     device = getattr(executor, '_device', 'cuda')
     delegators, weights = {}, []
 
@@ -608,8 +668,9 @@ def quantize_graph_mx(graph, executor, weight_format, activation_format, operati
             if fmt is None:
                 in_cfgs.append(fp32())
                 continue
-            c = _mx_config(fmt, device)
-            d = MXDelegator(fmt, mx_block_axis(op.type, i), use_kernels)
+            rule = wrule if v.is_parameter else arule
+            c = _mx_config(fmt, device, rule)
+            d = MXDelegator(fmt, mx_block_axis(op.type, i), use_kernels, rule)
             if v.is_parameter: weights.append((d, v))
             in_cfgs.append(c)
             delegators[c] = d
@@ -619,7 +680,7 @@ def quantize_graph_mx(graph, executor, weight_format, activation_format, operati
         graph.operations[name] = qop
     for c, d in delegators.items(): executor.register_quantize_delegate(c, d)
     if use_kernels and weights:
-        group = MXWeightGroup([(v, d.format, d.axis) for d, v in weights])
+        group = MXWeightGroup([(v, d.format, d.axis, d.scale_rule) for d, v in weights])
         for k, (d, v) in enumerate(weights): d.group, d.slot, d.var = group, k, v
     return delegators
 
@@ -627,7 +688,8 @@ def quantize_graph_mx(graph, executor, weight_format, activation_format, operati
 def export_graph_mx(graph, delegators=None, use_kernels: bool = True) -> Dict[str, MXTensor]:
     """Every parameter ``quantize_graph_mx`` put an MX config on, in packed form, keyed by the variable's name.  The format is the
     ``MXDelegator``'s (``delegators``: what ``quantize_graph_mx`` returned) or, without delegators, ``config.detail['MX_FORMAT']``;
-    the axis is ``mx_block_axis``.  With ``use_kernels`` all of them are packed by ONE launch (``ffi.MXPackPlan``)."""
+    the axis is ``mx_block_axis``; the scale rule is read where the format is read (the delegator's ``scale_rule`` resp.
+    ``config.detail['MX_SCALE_RULE']``, absent: FLOOR).  With ``use_kernels`` all of them are packed by ONE launch (``ffi.MXPackPlan``)."""
     from .harness import QuantableOperation
     names, items = [], []
     for op in graph.operations.values():
@@ -637,19 +699,19 @@ def export_graph_mx(graph, delegators=None, use_kernels: bool = True) -> Dict[st
             if delegators is not None:
                 d = delegators.get(c)
                 if not isinstance(d, MXDelegator): continue
-                fmt = d.format
-            elif 'MX_FORMAT' in getattr(c, 'detail', {}): fmt = MXFormat.of(c.detail['MX_FORMAT'])
+                fmt, rule = d.format, d.scale_rule
+            elif 'MX_FORMAT' in getattr(c, 'detail', {}): fmt, rule = MXFormat.of(c.detail['MX_FORMAT']), _config_rule(c)
             else: continue
             value = v.value
             _check_input(value, mx_block_axis(op.type, i))
             names.append(v.name)
-            items.append((value.detach(), fmt, mx_block_axis(op.type, i) % value.dim()))
+            items.append((value.detach(), fmt, mx_block_axis(op.type, i) % value.dim(), rule))
     if not items: return {}
     if not use_kernels:
-        return {n: mx_quantize(v, fmt, axis, use_kernels=False) for n, (v, fmt, axis) in zip(names, items)}
-    items = [(v if MXPackPlan.accepts(v, axis) else v.contiguous(), fmt, axis) for v, fmt, axis in items]
+        return {n: mx_quantize(v, fmt, axis, use_kernels=False, scale_rule=rule) for n, (v, fmt, axis, rule) in zip(names, items)}
+    items = [(v if MXPackPlan.accepts(v, axis) else v.contiguous(), fmt, axis, rule) for v, fmt, axis, rule in items]
     packed = MXPackPlan(items).run()
-    return {n: MXTensor(fmt, v.shape, axis, e, s) for n, (v, fmt, axis), (e, s) in zip(names, items, packed)}
+    return {n: MXTensor(fmt, v.shape, axis, e, s) for n, (v, fmt, axis, _), (e, s) in zip(names, items, packed)}
 
 
 # ---- the graph on the hardware path (DESIGN.md sections 9.15, 9.16) ------------------------------------------------------------------
@@ -700,6 +762,13 @@ class MXDeployment:
         name = getattr(config, 'detail', {}).get('MX_FORMAT')
         return MXFormat.of(name) if name is not None else None
 
+    def _rule(self, config) -> MXScaleRule:
+        """The scale rule of a config, read where ``_format`` reads the format."""
+        if self.delegators is not None:
+            d = self.delegators.get(config)
+            return d.scale_rule if isinstance(d, MXDelegator) else MXScaleRule.FLOOR
+        return _config_rule(config)
+
     def _plan(self, op):
         """(run, operand) of an eligible operation, or the reason it is not one; None for an operation without MX inputs."""
         cfgs = op.config.input_quantization_config
@@ -708,6 +777,7 @@ class MXDeployment:
         x_var, w_var = op.inputs[0], op.inputs[1]
         if x_var.is_parameter or not w_var.is_parameter: return 'the operands are not an activation and a parameter'
         afmt, wfmt = formats
+        arule = self._rule(cfgs[0])
         if afmt is None or wfmt is None: return 'only one operand carries an MX format'
         if not (afmt.is_float and wfmt.is_float): return 'MXINT8 is not an operand type of the scaled MFMA'
         if not (_activated(cfgs[0]) and _activated(cfgs[1])): return 'an MX config is not activated'
@@ -724,7 +794,7 @@ class MXDeployment:
                 bias = x[2] if len(x) > 2 else None
                 if isinstance(x[0], MXTensor):         # handed over packed by the producer's fused launch: nothing to quantise
                     return mx_conv2d_packed(_handed(op, x[0], afmt, 1), self._operands[op.name], bias, stride, padding, use_kernels=use_kernels, **tail)
-                return mx_conv2d(x[0], self._operands[op.name], afmt, bias, stride, padding, use_kernels=use_kernels, **tail)
+                return mx_conv2d(x[0], self._operands[op.name], afmt, bias, stride, padding, use_kernels=use_kernels, scale_rule=arule, **tail)
         else:
             if len(packed.shape) != 2: return f'a {len(packed.shape)}-d {op.type} weight'
             # a MatMul weight [in, out] is packed along axis 0: its bytes are those of [out, in] packed along axis 1
@@ -734,7 +804,7 @@ class MXDeployment:
                 bias = x[2] if len(x) > 2 else None
                 if isinstance(x[0], MXTensor):
                     return mx_matmul(_handed(op, x[0], afmt, len(x[0].shape) - 1), self._operands[op.name], bias, use_kernels, **tail)
-                return mx_linear(x[0], self._operands[op.name], afmt, bias, use_kernels=use_kernels, **tail)
+                return mx_linear(x[0], self._operands[op.name], afmt, bias, use_kernels=use_kernels, scale_rule=arule, **tail)
         return run, operand
 
     def refresh(self) -> None:
@@ -813,6 +883,9 @@ class MXDeployment:
             elif any(d.inputs[0] is not t or sum(1 for x in d.inputs if x is t) != 1 for d in takers): group.notes.append('float output: a deployed consumer does not read it as its activation')
             elif any(kind(d) != kind(op) for d in takers): group.notes.append('float output: a deployed consumer packs along another axis')
             elif len({self._format(d.config.input_quantization_config[0]) for d in takers}) != 1: group.notes.append('float output: the deployed consumers read it in different formats')
+            elif any(self._rule(d.config.input_quantization_config[0]) is not MXScaleRule.FLOOR for d in takers):
+                rules = sorted({self._rule(d.config.input_quantization_config[0]).name for d in takers} - {'FLOOR'})
+                group.notes.append(f'float output: a deployed consumer makes its scales by {" / ".join(rules)}, the fused epilogue packs by FLOOR')
             else: group.out_format = self._format(takers[0].config.input_quantization_config[0])
             self.groups[op.name] = group
             self.executor.register_group_override(group.members, self._group_run(group))
@@ -852,7 +925,8 @@ def deploy_graph_mx(graph, executor, delegators=None, use_kernels: bool = True, 
     ``fuse=True``: every deployed operation additionally runs together with its tail -- an optional
     residual ``Add``, then an optional ``Relu`` -- as ONE launch (``TorchExecutor.register_group_override``), and the tail's last
     tensor leaves that launch packed when every deployed consumer reads it as its activation in one format (Conv -> Conv, Gemm ->
-    Gemm): the consumer then quantises nothing.  It is written as float32 only when something reads it as float.  ``.groups``
+    Gemm) and by the FLOOR rule, the one the fused epilogue packs by (a consumer with another ``MXScaleRule`` gets the float tensor and
+    quantises it itself): the consumer then quantises nothing.  It is written as float32 only when something reads it as float.  ``.groups``
     records every group: members, residual, relu, ``out_format`` and, in ``notes``, why an Add was not fused or the output not
     packed.  A forward that hooks a member or asks for an intermediate runs that group's operations one by one, as ``fuse=False``."""
     return MXDeployment(graph, executor, delegators, use_kernels, fuse)
