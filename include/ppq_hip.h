@@ -785,6 +785,42 @@ typedef struct ppqhip_mx_job {
 } ppqhip_mx_job;
 int ppqhip_mx_fq_multi(const ppqhip_mx_job* jobs, int num_jobs, void* stream);
 
+/* Round tuning on the MX element grid (ppq_amd/mx_roundtune.py; ADDED under ABI 4) ------------------- */
+/* Per element the choice between the element value just below and just above the weight on its block's own grid; the block scale
+ * is fixed.  Tensors are addressed [outer, axis_len, inner] and blocks, amax, rule and code c are exactly those of ppqhip_mx_fq
+ * (`format | rule << PPQHIP_MX_RULE_SHIFT`, the MSE search included); X = 2^(c - 127), u = v * 2^(127 - c), mag = the pattern of |u|:
+ *   lo       the largest element magnitude <= |u|: mag with the dropped mantissa bits cleared, on the fixed-point grid (the format's
+ *            subnormals, all of MXINT8) floorf(|u| / quantum) * quantum; at most the largest normal, which also takes Inf
+ *   hi       up(lo): lo + quantum on the fixed-point grid, one mantissa step above it (the carry runs into the exponent); at most
+ *            the largest normal
+ *   floored  (sign | lo) * X        rounding  (|u| - lo) / (hi - lo) in [0, 1) when hi > lo, else 0 (saturated): both exact
+ *   a NaN element keeps its bits in floored and gets rounding 0
+ * Split reads w once and writes floored, rounding and scale_codes (uint8 [outer, ceil(axis_len / 32), inner], required).
+ * Forward, per element with c the block's code:  u = floored * 2^(127 - c) (exact: floored is on the grid);
+ *   out = rounding > .5 ? (sign | up(|u|)) * X : floored;   a NaN rounding, a NaN element and a code of 0xFF pass floored through.
+ * Its `format` carries no rule byte (the codes are given).  The backward of the forward is the identity for floored and for
+ * rounding, so there is no backward entry point.  Both take a HOST array that is copied into the kernel arguments (chunked when
+ * it does not fit one launch): no upload, no synchronisation, no atomics, capturable into a HIP graph.  No output may share memory
+ * with any other tensor of the call; every size is checked as for ppqhip_mx_fq; sizes of 0 launch nothing. */
+typedef struct ppqhip_mx_round_split_job {
+    const float* w;
+    float* floored;
+    float* rounding;
+    uint8_t* scale_codes;
+    int64_t outer, axis_len, inner;
+    int32_t format, reserved;
+} ppqhip_mx_round_split_job;
+typedef struct ppqhip_mx_round_fwd_job {
+    const float* floored;
+    const float* rounding;
+    const uint8_t* scale_codes;
+    float* out;
+    int64_t outer, axis_len, inner;
+    int32_t format, reserved;
+} ppqhip_mx_round_fwd_job;
+int ppqhip_mx_round_split_multi(const ppqhip_mx_round_split_job* jobs, int num_jobs, void* stream);
+int ppqhip_mx_round_fwd_multi(const ppqhip_mx_round_fwd_job* jobs, int num_jobs, void* stream);
+
 /* Packed MX export (ppq_amd/mx.py mx_quantize / mx_dequantize; ADDED under ABI 4) ------------------ */
 /* Blocks, amax, shared exponent, cast and saturation are exactly those of ppqhip_mx_fq.  x is contiguous [outer, axis_len, inner];
  * the packed tensor is two uint8 arrays with the BLOCK AXIS LAST and every block at full size (nb = ceil(axis_len / 32)):

@@ -10,7 +10,8 @@ from .ffi import (CUDA, CUDA_COMPLIER, ENABLE_CUDA_KERNEL, HIP_EXTENSION, instal
                   uninstall_from_ppq)
 from .mx import (MXDelegator, MXDeployment, MXFormat, MXScaleRule, MXTensor, deploy_graph_mx, export_graph_mx, mx_conv2d, mx_conv2d_packed, mx_dequantize,
                  mx_fake_quant, mx_linear, mx_matmul, mx_quantize, quantize_graph_mx)
+from .mx_roundtune import MXRoundTuningDelegator, MXRoundTuningGroup, MXRoundTuningPass, mx_round_forward, mx_round_split
 
-__all__ = ['MXFormat', 'MXScaleRule', 'MXDelegator', 'MXTensor', 'mx_fake_quant', 'mx_quantize', 'mx_dequantize', 'mx_matmul', 'mx_linear', 'mx_conv2d', 'mx_conv2d_packed', 'quantize_graph_mx', 'export_graph_mx', 'deploy_graph_mx', 'MXDeployment', 'CUDA', 'CUDA_COMPLIER', 'ENABLE_CUDA_KERNEL', 'HIP_EXTENSION', 'install_into_ppq', 'install_plugins_into_ppq', 'uninstall_from_ppq', 'PPQ_CONFIG', 'RoundingPolicy',
+__all__ = ['MXFormat', 'MXScaleRule', 'MXDelegator', 'MXTensor', 'mx_fake_quant', 'mx_quantize', 'mx_dequantize', 'mx_matmul', 'mx_linear', 'mx_conv2d', 'mx_conv2d_packed', 'quantize_graph_mx', 'export_graph_mx', 'deploy_graph_mx', 'MXDeployment', 'mx_round_split', 'mx_round_forward', 'MXRoundTuningDelegator', 'MXRoundTuningGroup', 'MXRoundTuningPass', 'CUDA', 'CUDA_COMPLIER', 'ENABLE_CUDA_KERNEL', 'HIP_EXTENSION', 'install_into_ppq', 'install_plugins_into_ppq', 'uninstall_from_ppq', 'PPQ_CONFIG', 'RoundingPolicy',
            'QuantizationProperty', 'QuantizationPolicy', 'QuantizationStates', 'TensorQuantizationConfig',
            'LinearQuantizationConfig', 'FloatingQuantizationConfig']

@@ -129,6 +129,8 @@ PROTOTYPES = {
     'ppqhip_stat_shape_multi': (c_int, [c_vp, c_int, c_vp]),
     'ppqhip_mx_fq': (c_int, [c_f32p, c_f32p, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),
     'ppqhip_mx_fq_multi': (c_int, [c_vp, c_int, c_vp]),
+    'ppqhip_mx_round_split_multi': (c_int, [c_vp, c_int, c_vp]),
+    'ppqhip_mx_round_fwd_multi': (c_int, [c_vp, c_int, c_vp]),
     'ppqhip_mx_pack': (c_int, [c_f32p, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]),
     'ppqhip_mx_pack_multi': (c_int, [c_vp, c_int, c_vp]),
     'ppqhip_mx_unpack': (c_int, [c_vp, c_vp, c_f32p, c_i64, c_i64, c_i64, c_int, c_vp]),

@@ -39,7 +39,8 @@ enum KernelId : int {
     K_FQ_LINEAR_T = 0, K_FQ_LINEAR_C, K_FQ_LINEAR_T_BWD, K_FQ_LINEAR_C_BWD, K_FQ_FLOAT_T, K_FQ_FLOAT_C,
     K_FQ_FLOAT_BWD, K_HIST_SYM_T, K_HIST_ASYM_T, K_HIST_SYM_C, K_QUANTILE, K_ISOTONE, K_MINMAX_T,
     K_MINMAX_C, K_MSE_SEARCH, K_KL_LOSSES, K_TENSOR_CLIP, K_ROUNDING_LOSS, K_CHANNEL_SUM, K_FLOAT_SCALE_SEARCH, K_LSQ_FINISH,
-    K_ADAROUND_FWD, K_ADAROUND_BWD, K_FETCH_ROWS, K_MEASURE_ROWS, K_MEASURE_FINISH, K_ROUNDTUNE_FWD, K_EQUALIZE_SCALE,
+    K_ADAROUND_FWD, K_ADAROUND_BWD, K_FETCH_ROWS, K_MEASURE_ROWS, K_MEASURE_FINISH, K_ROUNDTUNE_FWD, K_MX_ROUND_SPLIT, K_MX_ROUND_FWD,
+    K_EQUALIZE_SCALE,
     K_EQUALIZE_APPLY, K_SSD_SCALES, K_SSD_APPLY, K_FQ_MEASURE_ROWS, K_STAT_MOMENTS, K_STAT_SHAPE,
     K_SPLIT_PLAN, K_SPLIT_APPLY, K_MX_FQ, K_MX_PACK, K_MX_UNPACK, K_MX_GEMM, K_MX_CONV,
     K_MX_GEMM_FUSED, K_MX_CONV_FUSED, K_NUM

@@ -9,6 +9,8 @@
 // a normal number -- a product that lands among float32's subnormals is far below half the smallest element value and casts to zero
 // whichever way it was rounded -- and cast(u) * X is always representable: every step is exact, the function is deterministic.
 //
+// (The split of round tuning, mx_roundtune.hip, repeats these three bodies with its own stores: its codes must stay these bit for
+// bit, so a change to the addressing, the reductions or the order of the MSE adds here is made there too.)
 // Three bodies behind ONE kernel (job table in the kernel arguments, DESIGN.md "Job tables"; the single-tensor entry point is a table
 // of one job).  Each reads every element once and writes it once; the block's values wait in registers between the max and the cast:
 //   rows4   inner == 1, 16-B aligned, axis_len % 4 == 0: a block is 128 B, eight lanes load one float4 each (a short last block

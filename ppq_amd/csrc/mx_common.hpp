@@ -1,6 +1,8 @@
 // mx_common.hpp -- what the MX fake-quant kernels (mx.hip) and the packed MX export (mx_pack.hip) share: the description of an
 // element format, the E8M0 code of a block and THE rounding of an element.  Both paths take the rounded float32 pattern from
 // mx_round, so the packed codes can never disagree with the fake-quantised values on a rounding.
+// Round tuning on the element grid (mx_roundtune.hip) takes the block's code from the same functions and the two neighbours of an
+// element from mx_floor / mx_up below.
 #pragma once
 
 #include "common.hpp"
@@ -85,6 +87,21 @@ __device__ __forceinline__ uint32_t mx_round(uint32_t mag, const MxFmt& f) {
     const uint32_t rn = (mag + f.half_m1 + ((mag >> f.shift) & 1u)) & ~((1u << f.shift) - 1u);
     const uint32_t rs = __float_as_uint(__builtin_rintf(__uint_as_float(mag) * f.sub_scale) * f.sub_quantum);
     return min(mag < f.sub_limit ? rs : rn, f.max_bits);
+}
+// The two element values that enclose |u|, on float32 patterns as mx_round works.  mx_floor: the largest
+// element magnitude <= mag -- normal elements drop the mantissa bits below the format's, the fixed-point grid takes floorf() of the
+// scaled magnitude; Inf and anything above the largest normal give the largest normal.  mx_up: the element magnitude above the
+// element magnitude `lo` -- one quantum on the fixed-point grid (its last step lands on the smallest normal), one mantissa step
+// above it (the carry runs into the exponent as it should); the largest normal stays where it is.
+__device__ __forceinline__ uint32_t mx_floor(uint32_t mag, const MxFmt& f) {
+    const uint32_t fn = mag & ~((1u << f.shift) - 1u);
+    const uint32_t fs = __float_as_uint(__builtin_floorf(__uint_as_float(mag) * f.sub_scale) * f.sub_quantum);
+    return min(mag < f.sub_limit ? fs : fn, f.max_bits);
+}
+__device__ __forceinline__ uint32_t mx_up(uint32_t lo, const MxFmt& f) {
+    const uint32_t un = lo + (1u << f.shift);
+    const uint32_t us = __float_as_uint(__uint_as_float(lo) + f.sub_quantum);
+    return min(lo < f.sub_limit ? us : un, f.max_bits);
 }
 // cast(v / X) * X
 __device__ __forceinline__ float mx_elem(float v, float inv, float X, const MxFmt& f) {

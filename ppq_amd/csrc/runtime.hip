@@ -31,7 +31,8 @@ const char* const kKernelNames[K_NUM] = {
     "fq_linear_t", "fq_linear_c", "fq_linear_t_bwd", "fq_linear_c_bwd", "fq_float_t", "fq_float_c",
     "fq_float_bwd", "hist_sym_t", "hist_asym_t", "hist_sym_c", "quantile_t", "isotone_t", "minmax_t",
     "minmax_c", "mse_search", "kl_losses", "tensor_clip", "rounding_loss", "channel_sum", "float_scale_search", "lsq_finish",
-    "adaround_fwd", "adaround_bwd", "fetch_rows", "measure_rows", "measure_finish", "roundtune_fwd", "equalize_scale",
+    "adaround_fwd", "adaround_bwd", "fetch_rows", "measure_rows", "measure_finish", "roundtune_fwd", "mx_round_split", "mx_round_fwd",
+    "equalize_scale",
     "equalize_apply", "ssd_scales", "ssd_apply", "fq_measure_rows", "stat_moments", "stat_shape",
     "split_plan", "split_apply", "mx_fq", "mx_pack", "mx_unpack", "mx_gemm", "mx_conv",
     "mx_gemm_fused", "mx_conv_fused"};

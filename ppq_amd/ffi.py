@@ -1109,6 +1109,81 @@ class MXQuantizePlan:
         return self._outs
 
 
+# ---- round tuning on the MX grid (include/ppq_hip.h ppqhip_mx_round_split_multi / ppqhip_mx_round_fwd_multi) ----
+_MX_ROUND_SPLIT_JOB = np.dtype([('w', '<u8'), ('floored', '<u8'), ('rounding', '<u8'), ('scale_codes', '<u8'), ('outer', '<i8'),
+                                ('axis_len', '<i8'), ('inner', '<i8'), ('format', '<i4'), ('reserved', '<i4')])
+_MX_ROUND_FWD_JOB = np.dtype([('floored', '<u8'), ('rounding', '<u8'), ('scale_codes', '<u8'), ('out', '<u8'), ('outer', '<i8'),
+                              ('axis_len', '<i8'), ('inner', '<i8'), ('format', '<i4'), ('reserved', '<i4')])
+
+
+def _mx_round_geometry(t: torch.Tensor, axis: int):
+    """(outer, axis_len, inner) of a contiguous tensor and the shape of its scale codes."""
+    shape = list(t.shape)
+    inner = 1
+    for d in shape[axis + 1:]: inner *= int(d)
+    return t.numel() // (shape[axis] * inner), shape[axis], inner, shape[:axis] + [(shape[axis] + MX_BLOCK - 1) // MX_BLOCK] + shape[axis + 1:]
+
+
+def mx_round_split_multi(items) -> List[tuple]:
+    """The split of MX round tuning for every item in ONE launch (``ppqhip_mx_round_split_multi``).  items[k] = ``(w, format, axis)`` or
+    ``(w, format, axis, scale_rule)``: ``w`` a float32 CUDA tensor (a non-contiguous one is copied).  Returns
+    ``[(floored, rounding, scale_codes)]``: two contiguous float32 tensors shaped like ``w`` and the uint8 E8M0 codes (the axis replaced
+    by ceil(len / 32))."""
+    if not items: return []
+    items = [_mx_item(item) for item in items]
+    dev = items[0][0].device
+    jobs = np.zeros(len(items), dtype=_MX_ROUND_SPLIT_JOB)
+    keep, results = [], []
+    for k, (w, format, axis, rule) in enumerate(items):
+        _f32(w, 'Value')
+        if w.device != dev: raise RuntimeError(_KERNEL_FAILURE + f'MXRoundSplit: item {k} is on another device')
+        axis = _mx_axis(w.dim(), axis)
+        v = w.detach().contiguous()
+        outer, length, inner, codes_shape = _mx_round_geometry(v, axis)
+        floored, rounding = torch.empty_like(v), torch.empty_like(v)
+        codes = torch.empty(codes_shape, dtype=torch.uint8, device=dev)
+        keep.append(v); results.append((floored, rounding, codes))
+        jobs[k] = (v.data_ptr(), floored.data_ptr(), rounding.data_ptr(), codes.data_ptr(), outer, length, inner, mx_format_arg(format, rule), 0)
+    with _DeviceOf(items[0][0]):
+        _raise(lib.ppqhip_mx_round_split_multi(jobs.ctypes.data, len(jobs), _stream()))
+    return results
+
+
+def mx_round_forward_jobs(items, outs) -> np.ndarray:
+    """The job table of ``mx_round_forward_multi``: it holds POINTERS, so a caller whose tensors stay where they are (a group
+    that is launched every step) builds it once."""
+    if len(outs) != len(items): raise RuntimeError(_KERNEL_FAILURE + 'MXRoundForward: argument lists differ in length')
+    jobs = np.zeros(len(items), dtype=_MX_ROUND_FWD_JOB)
+    dev = items[0][0].device
+    for k, (floored, rounding, codes, format, axis) in enumerate(items):
+        ts = [('Value', floored), ('Rounding', rounding), ('Out', outs[k])]
+        for name, t in ts:
+            _f32(t, name)
+            if t.device != dev: raise RuntimeError(_KERNEL_FAILURE + f'MXRoundForward: item {k}: {name} is on another device')
+            if not t.is_contiguous(): raise RuntimeError(_KERNEL_FAILURE + f'MXRoundForward: item {k}: {name} is not contiguous')
+            if t.shape != floored.shape: raise RuntimeError(_KERNEL_FAILURE + f'MXRoundForward: item {k}: {name} is not shaped like the weight')
+        axis = _mx_axis(floored.dim(), axis)
+        outer, length, inner, codes_shape = _mx_round_geometry(floored, axis)
+        _check(codes, torch.uint8, 'Scale codes(Expect to be UINT8)')
+        if list(codes.shape) != codes_shape or not codes.is_contiguous() or codes.device != dev:
+            raise RuntimeError(_KERNEL_FAILURE + f'MXRoundForward: item {k}: scale_codes must be a contiguous uint8 tensor of shape {codes_shape} on the weight\'s device')
+        jobs[k] = (floored.data_ptr(), rounding.data_ptr(), codes.data_ptr(), outs[k].data_ptr(), outer, length, inner, mx_format_id(format), 0)
+    return jobs
+
+
+def mx_round_forward_multi(items, outs=None, jobs=None) -> List[torch.Tensor]:
+    """The forward of MX round tuning for every item in ONE launch (``ppqhip_mx_round_fwd_multi``).  items[k] =
+    ``(floored, rounding, scale_codes, format, axis)``: contiguous float32 CUDA tensors of one shape and the uint8 codes of the split;
+    ``outs`` (optional, caller-owned) receive the weights; ``jobs``: the table ``mx_round_forward_jobs`` built from the same items and
+    outs.  The job table travels in the kernel arguments: capturable.  The backward is the identity: nothing else to launch."""
+    if not items: return []
+    if outs is None: outs = [torch.empty_like(it[0]) for it in items]
+    if jobs is None: jobs = mx_round_forward_jobs(items, outs)
+    with _DeviceOf(items[0][0]):
+        _raise(lib.ppqhip_mx_round_fwd_multi(jobs.ctypes.data, len(jobs), _stream()))
+    return outs
+
+
 # ---- packed MX export (include/ppq_hip.h ppqhip_mx_pack / ppqhip_mx_unpack and their _multi forms; DESIGN.md section 9.13) ----
 _MX_PACK_JOB = np.dtype([('x', '<u8'), ('elements', '<u8'), ('scales', '<u8'), ('outer', '<i8'), ('axis_len', '<i8'), ('inner', '<i8'),
                          ('format', '<i4'), ('reserved', '<i4')])
@@ -2022,12 +2097,13 @@ def install_plugins_into_ppq(observers: bool = True) -> None:
 
     from ppq.executor.torch import TorchQuantizeDelegator
 
-    from . import adaround, calibration, lsq, observer, roundtune
+    from . import adaround, calibration, lsq, mx_roundtune, observer, roundtune
     QuantOPRuntimeHook.register(observer.CalibrationHook)
     RefPass.register(calibration.QuantizationOptimizationPass)
     TorchQuantizeDelegator.register(lsq.LSQDelegator)      # register_quantize_delegate admits by isinstance (torch.py:317-320)
     TorchQuantizeDelegator.register(adaround.AdaRoundDelegator)
     TorchQuantizeDelegator.register(roundtune.RoundTuningDelegator)
+    TorchQuantizeDelegator.register(mx_roundtune.MXRoundTuningDelegator)
     if observers:
         import ppq.quantization.observer as ref_observer
         import ppq.quantization.optim.calibration as ref_calibration
@@ -2311,6 +2387,19 @@ class CUDA:
                                     fmt, _stream()))
         if codes is not None and codes is not scale_codes: scale_codes.copy_(codes)
         return out
+
+    @ staticmethod
+    def MXRoundSplit(tensor, format, axis: int, scale_rule=None):
+        """The split of MX round tuning: ``(floored, rounding, scale_codes)`` -- the element value just
+        below every element on its block's grid, the element's position between that value and the one above in [0, 1), and the
+        blocks' E8M0 codes, those of ``MXQuantize`` under ``scale_rule``."""
+        return mx_round_split_multi([(tensor, format, axis, scale_rule)])[0]
+
+    @ staticmethod
+    def MXRoundForward(floored, rounding, scale_codes, format, axis: int):
+        """The forward of MX round tuning: ``rounding > .5`` takes the element value above ``floored`` on its block's grid
+        (``scale_codes``: the split's), anything else ``floored`` itself."""
+        return mx_round_forward_multi([(floored, rounding, scale_codes, format, axis)])[0]
 
     @ staticmethod
     def MXPack(tensor, format, axis: int, block_size: int = MX_BLOCK, scale_rule=None):
