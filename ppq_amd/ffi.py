@@ -1321,6 +1321,25 @@ class MXPackPlan:
         return self._outs
 
 
+def mx_unpack_multi(items) -> None:
+    """``ppqhip_mx_unpack_multi``: every ``(elements, scales, y, format, axis)`` item in ONE call (one launch per 40 live jobs).
+    ``y`` is the float32 tensor the packed pair unpacks INTO, dense in storage order (``MXQuantizePlan.accepts``); nothing is
+    copied, the library checks pointers, sizes and overlaps."""
+    if not items: return
+    jobs = np.zeros(len(items), dtype=_MX_UNPACK_JOB)
+    for k, (elements, scales, y, format, axis) in enumerate(items):
+        if y.numel() == 0:                                                                # an empty job: sizes 0, nothing launched for it
+            jobs[k]['format'] = mx_format_id(format)
+            continue
+        _check(elements, torch.uint8, 'Elements(Expect to be UINT8)'); _check(scales, torch.uint8, 'Scales(Expect to be UINT8)'); _f32(y, 'Out')
+        axis = _mx_axis(y.dim(), axis)
+        if not MXQuantizePlan.accepts(y, axis): raise RuntimeError(_KERNEL_FAILURE + f'mx_unpack_multi: item {k}: Out must be dense in storage order')
+        outer, length, inner, _ = _mx_geometry(y, axis)
+        jobs[k] = (elements.data_ptr(), scales.data_ptr(), y.data_ptr(), outer, length, inner, mx_format_id(format), 0)
+    with _DeviceOf(items[0][0]):
+        _raise(lib.ppqhip_mx_unpack_multi(jobs.ctypes.data, len(jobs), _stream()))
+
+
 class _HipExtension:
     """Same callables as the pybind module built from ppq/csrc/export.cc:8-34."""
     __name__ = 'PPQ_Hip_Impls'

@@ -52,6 +52,10 @@ assert PPQ_CONFIG.USING_CUDA_KERNEL is False
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 from ssd_cases import CALIB_STEPS, CASES, CHANNEL_RATIO, HIST_BINS, LOSS_THRESHOLD, case_batches, case_parameters  # noqa: E402
+sys.path.insert(0, os.path.dirname(HERE))
+# the IEEE restatement of the scales and of write_back lives with the tests' other oracles (it imports nothing but NumPy)
+from ssd_reference import apply_pair as ieee_apply  # noqa: E402
+from ssd_reference import scales as ieee_scales  # noqa: E402
 
 MARGIN = 0.05
 VERBOSE = '--verbose' in sys.argv
@@ -130,41 +134,6 @@ class Recorder(SSDEqualizationPass):
         v = super().test_ssd_loss(*a, **kw)
         self.events.append(('loss', v))
         return v
-
-
-def ieee_scales(first: np.ndarray, last: np.ndarray, act: np.ndarray, ratio: float) -> np.ndarray:
-    """one_step_equalization (optim/ssd.py:288-320) with every step the correctly rounded fp32 operation (numpy's division and
-    square root are; torch's CPU square root is not always, see make_equalization.ieee_scale).  A HIP kernel cannot (and should
-    not) reproduce a mis-rounded step, so a case whose recording differs from this is refused and re-seeded."""
-    eps, ratio = F(1e-8), F(ratio)
-    with np.errstate(all='ignore'):
-        s0 = np.clip(np.sqrt((last / (first + eps)).astype(F)), F(0.1), F(10))
-        t1, t2 = F(first.max() * ratio), F(last.max() * ratio)
-        f = np.where(first < t1, t1, first).astype(F); l = np.where(last < t2, t2, last).astype(F)
-        ks = (f.max() / (f + eps)).astype(F); nks = (l.max() / (l + eps)).astype(F)
-        a = np.where(act < F(0.01), F(0.01), act).astype(F)
-        as_ = (a.max() / (a + eps)).astype(F)
-        s1 = np.minimum(ks, as_)
-        t = np.minimum(np.minimum((ks / nks).astype(F), (as_ / nks).astype(F)), F(8))
-        s2 = np.clip((t / t.min()).astype(F), F(1), F(2))
-        s3 = np.clip(np.sqrt((as_ * np.sqrt((ks / nks).astype(F))).astype(F)), F(1), F(2))
-    return np.stack([s0, s1, s2, s3]).astype(F)
-
-
-def ieee_apply(first: dict, last: dict, first_name: str, last_name: str, params: dict, scale: np.ndarray) -> dict:
-    """write_back (optim/ssd.py:212-262) with numpy's correctly rounded product and quotient."""
-    w1, w2 = params[first_name + '_w'], params[last_name + '_w']
-    got = {}
-    if 'k' in first: got[first_name + '_w'] = w1 * scale.reshape(-1, 1, 1, 1)
-    else: got[first_name + '_w'] = w1 * (scale.reshape(-1, 1) if first['transB'] else scale.reshape(1, -1))
-    if first['bias']: got[first_name + '_b'] = params[first_name + '_b'] * scale
-    if 'k' in last:
-        G = last['group']
-        v = w2.reshape(G, w2.shape[0] // G, w2.shape[1], w2.shape[2], w2.shape[3]) / scale.reshape(G, 1, -1, 1, 1)
-        got[last_name + '_w'] = v.reshape(w2.shape)
-    else: got[last_name + '_w'] = w2 / (scale.reshape(1, -1) if last['transB'] else scale.reshape(-1, 1))
-    if last['bias']: got[last_name + '_b'] = params[last_name + '_b']
-    return {name: t.astype(F) for name, t in got.items()}
 
 
 def run_case(k: int, out: dict) -> dict:

@@ -64,6 +64,11 @@ CASES = [
               _conv('c2', 'r1_out', 8, 6, 3), _relu('r2', 'c2_out'),
               _conv('c3', 'r2_out', 6, 4, 1)], outputs=['c3_out']),
 ]
+# A pair wider than one workgroup of the SSD kernels (256 lanes): NOT among the recorded cases (CASES is what the golden-driven
+# tests iterate over), for tests that compare the two arms of the pass on the device.  `batch_seed` stands in for the case index.
+WIDE = dict(name='wide', iterations=2, per_channel=False, passive_bias=False, executable=True, input=(4, 3, 16, 16), seed=5120,
+            batch_seed=6100,
+            ops=[_conv('c1', 'input', 3, 264, 3), _relu('r1', 'c1_out'), _conv('c2', 'r1_out', 264, 40, 3)], outputs=['c2_out'])
 BATCHES = 3
 CALIB_STEPS = 8                      # more steps than batches: the calibration loops of the pass go round the loader
 
@@ -72,9 +77,14 @@ def case_index(name: str) -> int:
     return [c['name'] for c in CASES].index(name)
 
 
-def case_parameters(k: int) -> dict:
+def _case(k) -> dict:
+    """A case given as its index in CASES, or as the case dict itself (a case that is not recorded)."""
+    return k if isinstance(k, dict) else CASES[k]
+
+
+def case_parameters(k) -> dict:
     """{variable name: float32 CPU tensor} of case k: deterministic."""
-    case = CASES[k]
+    case = _case(k)
     g = torch.Generator().manual_seed(case['seed'])
     out, first = {}, True
     for kind, name, _, a in case['ops']:
@@ -96,17 +106,18 @@ def case_parameters(k: int) -> dict:
     return out
 
 
-def case_batches(k: int) -> list:
+def case_batches(k) -> list:
     """The calibration batches of case k (float32 CPU tensors): deterministic."""
-    g = torch.Generator().manual_seed(6000 + k)
-    return [torch.rand(CASES[k]['input'], generator=g) for _ in range(BATCHES)]
+    case = _case(k)
+    g = torch.Generator().manual_seed(case['batch_seed'] if isinstance(k, dict) else 6000 + k)
+    return [torch.rand(case['input'], generator=g) for _ in range(BATCHES)]
 
 
-def harness_graph(k: int, parameters: dict = None, quantize: bool = True):
-    """Case k as a ``ppq_amd.harness`` graph with CPU parameters (default: ``case_parameters(k)``), quantised as the module
-    docstring says."""
+def harness_graph(k, parameters: dict = None, quantize: bool = True):
+    """Case k (an index in CASES or a case dict) as a ``ppq_amd.harness`` graph with CPU parameters (default:
+    ``case_parameters(k)``), quantised as the module docstring says."""
     from ppq_amd import harness
-    case = CASES[k]
+    case = _case(k)
     parameters = case_parameters(k) if parameters is None else parameters
     g = harness.BaseGraph(case['name'])
     made = {'input': g.create_variable('input')}

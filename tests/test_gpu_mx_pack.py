@@ -210,6 +210,136 @@ def test_multi_tensor_plan():
     with pytest.raises(ValueError, match='at least one'): ffi.MXPackPlan([])
 
 
+# ------------------------------------------------------------------------------------------------------------------- unpack, multi
+class _Arena:
+    """A device buffer full of SENTINEL that tensors are carved out of; ``untouched()``: every byte outside them still holds it."""
+    def __init__(self, nbytes: int):
+        self.buf = torch.full((nbytes,), SENTINEL, dtype=torch.uint8, device=DEV)
+        self.at, self.spans = 64, []
+        assert self.buf.data_ptr() % 16 == 0
+
+    def take(self, nbytes: int, shift: int = 0) -> torch.Tensor:
+        """``nbytes`` bytes, ``shift`` bytes behind a 16-B boundary, at least 16 sentinel bytes away from their neighbours."""
+        lo = (self.at + 15) // 16 * 16 + shift
+        self.at = lo + nbytes + 16
+        assert self.at + 64 <= self.buf.numel()
+        self.spans.append((lo, lo + nbytes))
+        return self.buf[lo: lo + nbytes]
+
+    def floats(self, shape, shift: int = 0, channels_last: bool = False) -> torch.Tensor:
+        t = self.take(4 * int(np.prod(shape)), shift).view(torch.float32)
+        if not channels_last: return t.view(tuple(shape))
+        n, c, h, w = shape
+        return t.as_strided(tuple(shape), (c * h * w, 1, w * c, c))
+
+    def untouched(self) -> bool:
+        keep = np.ones(self.buf.numel(), bool)
+        for lo, hi in self.spans: keep[lo:hi] = False
+        return bool((self.buf.cpu().numpy()[keep] == SENTINEL).all())
+
+
+def _unpack_alone(e: torch.Tensor, s: torch.Tensor, fmt: str, shape, axis: int, channels_last: bool = False) -> np.ndarray:
+    """The single-job entry point on the same bytes, into a tensor of the same memory format."""
+    y = torch.empty(tuple(shape), dtype=torch.float32, device=DEV, memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    outer, length, inner, _ = ffi._mx_geometry(y, axis % len(shape))
+    assert _lib.lib.ppqhip_mx_unpack(e.data_ptr(), s.data_ptr(), y.data_ptr(), outer, length, inner, MXFormat[fmt].value, None) == 0, _lib.last_error()
+    return y.cpu().numpy()
+
+
+def _unpack_table(picks, ins: _Arena, outs: _Arena):
+    """picks[k] = (x or (elements, scales, shape), fmt, axis, shift of `elements`, shift of y, channels-last y) -> the items of one ``ffi.mx_unpack_multi`` call
+    on the ORACLE's packed bytes, and per item (fmt, shape, axis, elements, scales, y, channels_last, the oracle's values)."""
+    items, book = [], []
+    for x, fmt, axis, shift_e, shift_y, cl in picks:
+        if isinstance(x, tuple): pe, ps, shape = x                                       # bytes no pack produces
+        else: shape = x.shape
+        if int(np.prod(shape)) == 0:
+            e = s = torch.empty(0, dtype=torch.uint8, device=DEV)
+            y, want = torch.empty(shape, dtype=torch.float32, device=DEV), np.zeros(shape, np.float32)
+        else:
+            if not isinstance(x, tuple): pe, ps = P.pack(x, fmt, axis)
+            e, s = ins.take(pe.size, shift_e), ins.take(ps.size)
+            e.copy_(torch.from_numpy(pe.ravel())); s.copy_(torch.from_numpy(ps.ravel()))
+            y, want = outs.floats(shape, shift_y, cl), P.unpack(pe, ps, fmt, shape, axis)
+        items.append((e, s, y, MXFormat[fmt], axis))
+        book.append((fmt, tuple(shape), axis, e, s, y, cl, want))
+    return items, book
+
+
+def test_unpack_multi_on_a_mixed_table():
+    """ppqhip_mx_unpack_multi (mx_unpack_kernel<kMxMaxJobs, 1>) on a table of every body and every format, with an empty job in
+    the middle: rows4, rows1 (a 33-element row; a float side 4 bytes off), strided, the strided body with `elements` not 16-B
+    aligned (byte loads), a channels-last output, special blocks (NaN, Inf, signed zeros; NaN blocks under scale 0xFF) and every
+    E5M2 code under scales 127 and 0xFF.  Every
+    output equals the oracle's unpacking of the same bytes and the single-job entry point, on bits, NaN patterns included; no
+    byte outside the outputs changes, and the inputs are not written."""
+    foreign = P.foreign_codes('MXFP8_E5M2')
+    picks = [(R.layout_input((3, 64), 31), 'MXFP8_E4M3', -1, 0, 0, False),                              # rows4
+             (R.layout_input((2, 33), 32), 'MXFP6_E3M2', -1, 0, 0, False),                              # rows1
+             (R.layout_input((4, 35, 3, 3), 33), 'MXFP4_E2M1', 1, 0, 0, False),                         # strided
+             (np.zeros((0, 32), np.float32), 'MXINT8', -1, 0, 0, False),                                # empty
+             (R.layout_input(R.CHANNELS_LAST_SHAPE, 34), 'MXINT8', 1, 0, 0, True),                      # channels-last: rows4 of [N H W, C]
+             (R.layout_input((70, 9), 35), 'MXFP6_E2M3', 0, 4, 0, False),                               # strided, byte loads
+             (R.special_blocks('MXFP8_E5M2'), 'MXFP8_E5M2', -1, 0, 0, False),
+             (R.special_blocks('MXFP4_E2M1'), 'MXFP4_E2M1', -1, 0, 0, False),
+             (R.layout_input((3, 64), 36), 'MXFP6_E3M2', -1, 0, 4, False),                              # rows1: y is not 16-B aligned
+             (np.ascontiguousarray(R.special_blocks('MXFP6_E2M3').T), 'MXFP6_E2M3', 0, 0, 0, False),    # strided NaN blocks
+             (foreign + ((2, 32 * foreign[1].shape[-1]),), 'MXFP8_E5M2', -1, 0, 0, False)]              # every code: Inf, NaN, scale 0xFF
+    assert {p[1] for p in picks} == set(FORMATS)
+    ins, outs = _Arena(1 << 18), _Arena(1 << 19)
+    items, book = _unpack_table(picks, ins, outs)
+    assert items[5][0].data_ptr() % 16 == 4 and items[8][2].data_ptr() % 16 == 4 and items[0][2].data_ptr() % 16 == 0
+    assert not items[4][2].is_contiguous() and ffi._mx_geometry(items[4][2], 1)[:3] == (32, 64, 1)
+    before = ins.buf.clone()
+    ffi.mx_unpack_multi(items)
+    torch.cuda.synchronize()
+    nan_blocks = 0
+    for k, (fmt, shape, axis, e, s, y, cl, want) in enumerate(book):
+        if not len(want.ravel()): continue
+        assert_bits(y.cpu().numpy(), want, f'job {k} {fmt} {shape}')
+        assert_bits(_unpack_alone(e, s, fmt, shape, axis, cl), want, f'job {k} {fmt} {shape} alone')
+        nan_blocks += int((s.cpu().numpy() == 0xff).sum())
+    assert nan_blocks > 0 and np.isnan(book[6][7]).any() and np.isinf(book[10][7]).any()
+    assert outs.untouched() and torch.equal(ins.buf, before)
+
+
+@pytest.mark.parametrize('jobs', [41, 43])
+def test_unpack_multi_of_more_jobs_than_one_launch_carries(jobs):
+    """kMxMaxJobs = 40: job 41 rides in a second launch with a table of its own (43: a table of three jobs on three paths,
+    first_block restarted).  Small tensors of every format on the three paths."""
+    shapes = [((1, 32), -1), ((2, 33), -1), ((4, 35, 3, 3), 1)]
+    picks = [(R.layout_input(shapes[k % 3][0], 200 + k), FORMATS[(k // 3) % 6], shapes[k % 3][1], 0, 0, False) for k in range(jobs)]
+    assert len({(p[0].shape, p[1]) for p in picks}) == 18 and picks[40][1] != picks[0][1]
+    ins, outs = _Arena(1 << 18), _Arena(1 << 19)
+    items, book = _unpack_table(picks, ins, outs)
+    ffi.mx_unpack_multi(items)
+    torch.cuda.synchronize()
+    for k, (fmt, shape, axis, e, s, y, cl, want) in enumerate(book): assert_bits(y.cpu().numpy(), want, f'job {k} {fmt} {shape}')
+    assert outs.untouched()
+
+
+def test_pack_plan_then_unpack_multi_is_fake_quant():
+    """MXPackPlan(...).run() followed by ONE mx_unpack_multi call: every tensor is mx_fake_quant of its input, except at the NaN
+    positions (same_but_nan)."""
+    xs = [(R.layout_input((3, 64), 41), 'MXFP8_E4M3', -1), (R.layout_input((2, 33), 42), 'MXINT8', -1),
+          (R.layout_input((4, 35, 3, 3), 43), 'MXFP6_E3M2', 1), (R.layout_input((70, 9), 44), 'MXFP4_E2M1', 0)]
+    xs += [(R.special_blocks(fmt), fmt, -1) for fmt in FORMATS]
+    xs += [(R.gaussian_blocks(), 'MXFP6_E2M3', -1), (R.gaussian_blocks(), 'MXFP8_E5M2', -1)]
+    assert {fmt for _, fmt, _ in xs} == set(FORMATS)
+    tensors = [dev(x) for x, _, _ in xs]
+    packed = ffi.MXPackPlan([(t, MXFormat[fmt], axis) for t, (_, fmt, axis) in zip(tensors, xs)]).run()
+    outs = _Arena(4 * sum(x.size for x, _, _ in xs) + 64 * len(xs) + 256)
+    ys = [outs.floats(x.shape) for x, _, _ in xs]
+    ffi.mx_unpack_multi([(e, s, y, MXFormat[fmt], axis) for (e, s), y, (_, fmt, axis) in zip(packed, ys, xs)])
+    torch.cuda.synchronize()
+    nans = 0
+    for (x, fmt, axis), t, y in zip(xs, tensors, ys):
+        mask = P.nan_mask(x, fmt, axis)
+        nans += int(mask.sum())
+        assert P.same_but_nan(y.cpu().numpy(), mx_fake_quant(t, fmt, axis).cpu().numpy(), mask, fmt), (fmt, x.shape)
+    assert nans > 0 and outs.untouched()
+
+
 # ---------------------------------------------------------------------------------------------------------------------------- graph
 def _launches(fn):
     torch.cuda.synchronize(); _lib.lib.ppqhip_prof_enable(1)

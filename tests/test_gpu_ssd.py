@@ -70,7 +70,7 @@ def _states(golden, k):
 
 def _pass(k, **kw):
     from ppq_amd.ssd import SSDEqualizationPass
-    return SSDEqualizationPass(iteration=SC.CASES[k]['iterations'], channel_ratio=SC.CHANNEL_RATIO, loss_threshold=SC.LOSS_THRESHOLD, **kw)
+    return SSDEqualizationPass(iteration=SC._case(k)['iterations'], channel_ratio=SC.CHANNEL_RATIO, loss_threshold=SC.LOSS_THRESHOLD, **kw)
 
 
 def _batches(k): return [b.to(DEV) for b in SC.case_batches(k)]
@@ -237,6 +237,37 @@ def test_kernel_arm_equals_torch_arm_bit_for_bit(k):
     for name, v in ga.variables.items():
         if v.is_parameter: assert _same(v.value, gb.variables[name].value), name
     assert pa.stats['accepted'] == pb.stats['accepted']
+
+
+def test_kernel_arm_equals_torch_arm_on_a_pair_wider_than_a_workgroup():
+    """Conv(3 -> 264) -> Relu -> Conv(264 -> 40), per-tensor weights (ssd_cases.WIDE, not a recorded case): 264 channels are two
+    trips of the scales kernel over the channels, 360 elements per channel of the last weight two trips of the ranges kernel, and
+    the 95 040 elements of the last weight 372 workgroups of the apply kernel.  Bit for bit as on the case graphs -- and at least
+    one candidate is accepted, so that a write-back at this size takes place and the second iteration starts from it."""
+    from ppq_amd import harness
+    case = SC.WIDE
+    assert case not in SC.CASES and case['per_channel'] is False
+    g = _to_device(SC.harness_graph(case))
+    ex = harness.TorchExecutor(g, DEV)
+    x = _batches(case)[0]
+    first, second = ex.forward(x), ex.forward(x)
+    assert all(torch.equal(a, b) for a, b in zip(first, second)), \
+        'precondition: the forward of the wide graph does not repeat its bits on this device, the arms cannot be compared bit for bit'
+    ga, _, pa = _run(case, True)
+    gb, _, pb = _run(case, False)
+    assert [[op.name for op in pair] for pair in pa.pairs] == [['c1', 'r1', 'c2']]
+    assert pa.history.keys() == pb.history.keys() and len(pa.history) == len(pa.pairs) * case['iterations']
+    for key in pa.history:
+        a, b = pa.history[key], pb.history[key]
+        assert a['best_idx'] == b['best_idx'], key
+        assert a['basic'] == b['basic'] and a['losses'] == b['losses'], (key, a, b)
+    for name, v in ga.variables.items():
+        if v.is_parameter: assert _same(v.value, gb.variables[name].value), name
+    assert pa.stats['accepted'] == pb.stats['accepted']
+    print('ssd wide: accepted', pa.stats['accepted'], 'history', pa.history)
+    assert any(h['best_idx'] >= 0 for h in pa.history.values()), pa.history
+    assert not _same(ga.variables['c2_w'].value, SC.case_parameters(case)['c2_w'])                 # the write-back happened
+    assert pa.stats['launches'] > 0
 
 
 def _counting():

@@ -325,3 +325,133 @@ def test_convtranspose_raises():
             SSD.SSDEqualizationPass(use_kernels=use_kernels).optimize(g, dataloader=[torch.zeros(1, 3, 8, 8)], executor=None,
                                                                       collate_fn=None, calib_steps=1)
     assert torch.equal(g.variables['c1_w'].value, w1.value)
+
+
+# ---- the NumPy oracle of the kernels (tests/ssd_reference.py) --------------------------------------------------------
+import ssd_reference as REF  # noqa: E402
+
+
+def _pair_forms(case: dict, names: list):
+    """(first attributes, last attributes, first channel axis, last channel axis, groups of the last Conv) of a recorded pair."""
+    attrs = {name: a for _, name, _, a in case['ops']}
+    first, last = attrs[names[0]], attrs[names[-1]]
+    first_axis = 0 if 'k' in first or first['transB'] else 1
+    last_axis = 1 if 'k' in last or last['transB'] else 0
+    return first, last, first_axis, last_axis, last.get('group', 1)
+
+
+def _states(golden, k):
+    """[(iteration, pair index, key, {parameter name: value before this (iteration, pair)})] of case k."""
+    state = {n[len(f'c{k}_init_'):]: v for n, v in golden.items() if n.startswith(f'c{k}_init_')}
+    out = []
+    for it, q, key in _recorded(golden, k):
+        out.append((it, q, key, dict(state)))
+        best = int(golden[key + 'best'])
+        if best >= 0:
+            pre = f'{key}cand{best}_'
+            state.update({n[len(pre):]: v for n, v in golden.items() if n.startswith(pre)})
+    return out
+
+
+@pytest.mark.parametrize('k', range(len(SC.CASES)), ids=[c['name'] for c in SC.CASES])
+def test_oracle_equals_every_recorded_range_scale_and_candidate(golden, book, k):
+    """ssd_reference.ranges / scales / apply against every (case, iteration, pair) of ssd.npz, on bits."""
+    case = SC.CASES[k]
+    pairs = book['cases'][case['name']]
+    seen = cands = 0
+    for it, q, key, state in _states(golden, k):
+        first, last, first_axis, last_axis, group = _pair_forms(case, pairs[q])
+        n1, n2 = pairs[q][0], pairs[q][-1]
+        r = REF.ranges(state[n1 + '_w'], state[n2 + '_w'], group, first_axis, last_axis)
+        assert _same(r[0], golden[key + 'first']) and _same(r[1], golden[key + 'last']), (it, q)
+        s = REF.scales(r[0], r[1], golden[key + 'act'], SC.CHANNEL_RATIO)
+        assert _same(s, golden[key + 'scales']), (it, q)
+        # the tensors one by one (the form the kernel tests use) and the pair at once (the form make_ssd.py uses)
+        items = [(n1 + '_w', first_axis, False, 1), (n2 + '_w', last_axis, True, group)]
+        if first['bias']: items.append((n1 + '_b', 0, False, 1))
+        for name, axis, divide, g in items:
+            got = REF.apply(state[name], s, axis, divide, g)
+            for algo in range(4): assert _same(got[algo], golden[f'{key}cand{algo}_{name}']), (it, q, algo, name)
+            cands += 4
+        for algo in range(4):
+            for name, t in REF.apply_pair(first, last, n1, n2, state, s[algo]).items():
+                assert _same(t, golden[f'{key}cand{algo}_{name}']), (it, q, algo, name)
+        seen += 1
+    assert seen == len(pairs) * case['iterations'] and cands >= 8 * seen
+
+
+def test_oracle_scales_equal_calculate_scale(golden):
+    """The torch arm's scale of the four algorithms on every recorded input.  (The recordings were admitted only where torch's
+    CPU square root rounds correctly: make_ssd.py.)"""
+    seen = 0
+    for k in range(len(SC.CASES)):
+        for it, q, key in _recorded(golden, k):
+            first, last, act = (golden[key + n] for n in ('first', 'last', 'act'))
+            want = REF.scales(first, last, act, SC.CHANNEL_RATIO)
+            for algo in range(4):
+                got = SSD.calculate_scale(torch.from_numpy(first), torch.from_numpy(last), torch.from_numpy(act), algo, SC.CHANNEL_RATIO)
+                assert _same(got.numpy(), want[algo]), (k, it, q, algo)
+            seen += 1
+    assert seen >= 20
+
+
+def test_oracle_channel_forms_equal_the_torch_arm_at_width():
+    """ranges of the three segment forms (row, column, grouped slices) on weights wider than one workgroup: the oracle against
+    prepare_weight_for_equalization, which the recordings pin at C <= 16 only."""
+    rng = np.random.default_rng(7)
+
+    def torch_ranges(kind1, w1, a1, kind2, w2, a2):
+        g = harness.BaseGraph('wide')
+        x = g.create_variable('input'); g.inputs['input'] = x
+        y = g.create_operation(kind1, 'a', [x, g.create_variable('a_w', torch.from_numpy(w1), True)], a1)
+        y = g.create_operation('Relu', 'r', [y])
+        y = g.create_operation(kind2, 'b', [y, g.create_variable('b_w', torch.from_numpy(w2), True)], a2)
+        g.outputs[y.name] = y
+        p = SSD.SSDEqualizationPass(use_kernels=False)
+        (pair,) = p.collect_all_pairs(g)
+        return [t.numpy() for t in p.prepare_weight_for_equalization(pair)]
+
+    conv = {'strides': 1, 'pads': 1, 'group': 1}
+    w1, w2 = rng.standard_normal((300, 5, 3, 3)).astype(np.float32), rng.standard_normal((7, 300, 3, 3)).astype(np.float32)
+    want = torch_ranges('Conv', w1, conv, 'Conv', w2, conv)
+    assert _same(REF.ranges(w1, w2), np.stack(want))
+    wg = rng.standard_normal((24, 150, 3, 3)).astype(np.float32)
+    want = torch_ranges('Conv', w1, conv, 'Conv', wg, dict(conv, group=2))
+    assert _same(REF.ranges(w1, wg, 2), np.stack(want))
+    g1, g2 = rng.standard_normal((9, 300)).astype(np.float32), rng.standard_normal((11, 300)).astype(np.float32)
+    want = torch_ranges('Gemm', g1, {'transB': 0}, 'Gemm', g2, {'transB': 1})                  # [in, C] column, [out, C] column
+    assert _same(REF.ranges(g1, g2, 1, 1, 1), np.stack(want))
+    want = torch_ranges('Gemm', np.ascontiguousarray(g1.T), {'transB': 1}, 'Gemm', np.ascontiguousarray(g2.T), {'transB': 0})
+    assert _same(REF.ranges(g1.T, g2.T, 1, 0, 0), np.stack(want))                             # [C, in] row, [C, out] row
+
+
+def test_oracle_nan_behaviour():
+    """The NaN semantics the kernels document (ssd_reference's module docstring), on the oracle itself."""
+    rng = np.random.default_rng(3)
+    C = 20
+    w1 = rng.standard_normal((C, 4, 3, 3)).astype(np.float32)
+    w2 = rng.standard_normal((6, C, 3, 3)).astype(np.float32)
+    act = (rng.random(C).astype(np.float32) + np.float32(0.1))
+    clean = REF.scales(*REF.ranges(w1, w2), act, 0.5)
+    assert not np.isnan(clean).any()
+    a = w1.copy(); a[5, 2, 1, 1] = np.nan                                # first weight
+    r = REF.ranges(a, w2)
+    assert np.array_equal(np.isnan(r[0]), np.arange(C) == 5) and not np.isnan(r[1]).any()
+    s = REF.scales(r[0], r[1], act, 0.5)
+    assert np.array_equal(np.isnan(s[0]), np.arange(C) == 5) and np.isnan(s[1:]).all()
+    assert _same(s[0][np.arange(C) != 5], clean[0][np.arange(C) != 5])
+    b = w2.copy(); b[3, 7, 0, 2] = np.nan                                # last weight: algorithm 1 does not read it
+    r = REF.ranges(w1, b)
+    assert np.array_equal(np.isnan(r[1]), np.arange(C) == 7) and not np.isnan(r[0]).any()
+    s = REF.scales(r[0], r[1], act, 0.5)
+    assert np.array_equal(np.isnan(s[0]), np.arange(C) == 7) and _same(s[1], clean[1]) and np.isnan(s[2:]).all()
+    c = act.copy(); c[11] = np.nan                                       # activation range: algorithm 0 does not read it
+    s = REF.scales(*REF.ranges(w1, w2), c, 0.5)
+    assert _same(s[0], clean[0]) and np.isnan(s[1:]).all()
+    for algo in range(4):                                                # ... and the torch arm says the same
+        got = SSD.calculate_scale(torch.from_numpy(r[0]), torch.from_numpy(r[1]), torch.from_numpy(act), algo, 0.5).numpy()
+        want = REF.scales(r[0], r[1], act, 0.5)[algo]
+        assert np.array_equal(np.isnan(got), np.isnan(want)), algo
+    x = np.array([[1.0, np.nan], [-0.0, 3.0]], dtype=np.float32)         # apply: a NaN stays where it is, -0 keeps its sign
+    got = REF.apply(x, np.full((4, 2), 2.0, np.float32), 0)
+    assert np.array_equal(np.isnan(got[0]), np.isnan(x)) and np.signbit(got[0][1, 0]) and got[0][1, 1] == 6.0
