@@ -29,15 +29,14 @@ __device__ __forceinline__ MxCoder make_coder(uint32_t format, const MxFmt& fmt)
     return c;
 }
 
-// the magnitude that takes part in the block maximum; in a format without a NaN encoding a NaN marks the whole block
-constexpr uint32_t kNaNBlock = 0xffffffffu;
+// the magnitude that takes part in the block maximum; in a format without a NaN encoding a NaN marks the whole block (kMxNaNBlock)
 __device__ __forceinline__ uint32_t mxp_mag(float v, const MxCoder& c) {
     const uint32_t m = __float_as_uint(v) & 0x7fffffffu;
-    return m < 0x7f800000u ? m : (m > 0x7f800000u && !c.has_nan ? kNaNBlock : 0u);
+    return m < 0x7f800000u ? m : (m > 0x7f800000u && !c.has_nan ? kMxNaNBlock : 0u);
 }
 // scale code and 1 / X of a block from the reduced mxp_mag
 __device__ __forceinline__ uint32_t mxp_scale(uint32_t m, const MxFmt& f, float& inv, bool& dead) {
-    dead = m == kNaNBlock;
+    dead = m == kMxNaNBlock;
     const uint32_t code = mx_code(dead ? 0u : m, f);
     inv = mx_pow2(254u - code);
     return dead ? 0xffu : code;

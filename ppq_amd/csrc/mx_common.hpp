@@ -65,6 +65,7 @@ inline int mx_rule_class(uint32_t rule) { return rule == PPQHIP_MX_MSE ? MX_SEAR
 constexpr uint32_t kMxBlock = 32;                 // elements per MX block
 constexpr int kMxMaxJobs = 40;                    // jobs of one launch (the table travels in the kernel arguments)
 constexpr int64_t kMxMax = 0x7fffffffLL;          // elements of one tensor
+constexpr uint32_t kMxNaNBlock = 0xffffffffu;     // a block maximum above every magnitude: the block is NaN as a whole (mx_coder.hpp)
 
 #if defined(__HIPCC__)
 

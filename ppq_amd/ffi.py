@@ -1116,14 +1116,6 @@ _MX_ROUND_FWD_JOB = np.dtype([('floored', '<u8'), ('rounding', '<u8'), ('scale_c
                               ('axis_len', '<i8'), ('inner', '<i8'), ('format', '<i4'), ('reserved', '<i4')])
 
 
-def _mx_round_geometry(t: torch.Tensor, axis: int):
-    """(outer, axis_len, inner) of a contiguous tensor and the shape of its scale codes."""
-    shape = list(t.shape)
-    inner = 1
-    for d in shape[axis + 1:]: inner *= int(d)
-    return t.numel() // (shape[axis] * inner), shape[axis], inner, shape[:axis] + [(shape[axis] + MX_BLOCK - 1) // MX_BLOCK] + shape[axis + 1:]
-
-
 def mx_round_split_multi(items) -> List[tuple]:
     """The split of MX round tuning for every item in ONE launch (``ppqhip_mx_round_split_multi``).  items[k] = ``(w, format, axis)`` or
     ``(w, format, axis, scale_rule)``: ``w`` a float32 CUDA tensor (a non-contiguous one is copied).  Returns
@@ -1139,7 +1131,7 @@ def mx_round_split_multi(items) -> List[tuple]:
         if w.device != dev: raise RuntimeError(_KERNEL_FAILURE + f'MXRoundSplit: item {k} is on another device')
         axis = _mx_axis(w.dim(), axis)
         v = w.detach().contiguous()
-        outer, length, inner, codes_shape = _mx_round_geometry(v, axis)
+        outer, length, inner, codes_shape = _mx_geometry(v, axis)
         floored, rounding = torch.empty_like(v), torch.empty_like(v)
         codes = torch.empty(codes_shape, dtype=torch.uint8, device=dev)
         keep.append(v); results.append((floored, rounding, codes))
@@ -1163,7 +1155,7 @@ def mx_round_forward_jobs(items, outs) -> np.ndarray:
             if not t.is_contiguous(): raise RuntimeError(_KERNEL_FAILURE + f'MXRoundForward: item {k}: {name} is not contiguous')
             if t.shape != floored.shape: raise RuntimeError(_KERNEL_FAILURE + f'MXRoundForward: item {k}: {name} is not shaped like the weight')
         axis = _mx_axis(floored.dim(), axis)
-        outer, length, inner, codes_shape = _mx_round_geometry(floored, axis)
+        outer, length, inner, codes_shape = _mx_geometry(floored, axis)
         _check(codes, torch.uint8, 'Scale codes(Expect to be UINT8)')
         if list(codes.shape) != codes_shape or not codes.is_contiguous() or codes.device != dev:
             raise RuntimeError(_KERNEL_FAILURE + f'MXRoundForward: item {k}: scale_codes must be a contiguous uint8 tensor of shape {codes_shape} on the weight\'s device')

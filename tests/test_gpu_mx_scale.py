@@ -193,6 +193,34 @@ def test_large_tensors_reach_the_other_instantiations(rows):
         assert torch.equal(q.scales, qw.scales) and torch.equal(q.elements, qw.elements), rule
 
 
+@pytest.mark.parametrize('fmt', FORMATS)
+def test_fake_quant_pack_and_round_split_agree_on_every_block_code(fmt):
+    """The three kernels take a block's code from one walk (csrc/mx_walk.hpp): on one input, under every rule and on every addressing
+    (the shapes of tests/test_gpu_mx_roundtune.py: rows4, rows1 with a short last block, rows1 by misalignment, strided with inner 9
+    and with inner 32), the scale codes of mx_fake_quant, the scales of mx_quantize and the codes of mx_round_split are equal byte
+    for byte.  One exception, by contract: a format without a NaN encoding packs a block that holds a NaN with scale 0xFF; there the
+    other two still agree with each other."""
+    from ppq_amd import mx_round_split
+    from test_gpu_mx_roundtune import SHAPES, _crafted, _offset
+    for k, (shape, axis, offset) in enumerate(SHAPES):
+        x = _crafted(shape, axis, fmt, seed=k)
+        t = torch.from_numpy(x).to(DEV)
+        if offset: t = _offset(t)
+        axis %= x.ndim
+        dead = torch.from_numpy(P._blocks(np.isnan(x), axis, False).any(axis=-1)).to(DEV)      # [lead..., nb], as the packed scales
+        if fmt in P.HAS_NAN: dead = torch.zeros_like(dead)
+        else: assert dead.any() and not dead.all(), (fmt, shape)
+        for rule in S.RULES:
+            what = (fmt, rule, shape, axis, offset)
+            fq = torch.full(shape[:axis] + ((shape[axis] + 31) // 32,) + shape[axis + 1:], 0xAA, dtype=torch.uint8, device=DEV)
+            mx_fake_quant(t, fmt, axis, scale_codes=fq, scale_rule=rule)
+            split = mx_round_split(t, fmt, axis, rule)[2]
+            packed = mx_quantize(t, fmt, axis, scale_rule=rule).scales.movedim(-1, axis)
+            assert fq.shape == split.shape == packed.shape, what
+            assert torch.equal(fq, split), what
+            assert torch.equal(packed, torch.where(dead.movedim(-1, axis), torch.full_like(fq, 0xFF), fq)), what
+
+
 # ------------------------------------------------------------------------------------------------------- the loop on the hardware
 def test_linear_and_conv_quantise_their_activation_by_the_rule():
     gen = torch.Generator().manual_seed(9)
