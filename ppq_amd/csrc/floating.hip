@@ -4,10 +4,9 @@
 // (ppq/csrc/cuda/common.cuh:154-226) bit for bit, including its quirk that an exact mantissa tie
 // under ROUND_HALF_EVEN rounds toward zero (nearbyint(0.5) == 0), which is NOT IEEE / OCP RNE --
 // so the hardware v_cvt_pk_fp8_f32 conversions are deliberately not used here.
-// Same streaming structure as linear.hip (one contiguous tile of float4s per workgroup).
-#include "common.hpp"
-
-#include <vector>
+// The walks (tiles, element-wise fallback, backward rows, finish sum) are fq_walk.hpp's, shared with linear.hip; this file
+// holds the format, its arithmetic, the scale search and the entry points.
+#include "fq_walk.hpp"
 
 namespace ppqhip {
 
@@ -104,65 +103,33 @@ __device__ __forceinline__ float quant_float_rne_pow2(float value, float rcp, co
 template <int R>
 __device__ __forceinline__ bool float_fast_ok(const FloatFmt& fmt) { return R == ROUND_HALF_EVEN && fmt.mantissa <= 22; }
 
-// one contiguous tile of kBlock * U float4 per workgroup (see linear.hip)
+// The small-float grid as a quantiser policy of fq_walk.hpp.  A state with a power-of-two scale takes quant_float_rne_pow2
+// (FAST = false: never, the reference's own arithmetic throughout).
+template <int R, bool FAST = true>
+struct FloatQ {
+    const FloatFmt& fmt;
+    int rounding;
+    struct State { float s, o; uint32_t rb; };
+    __device__ __forceinline__ State make(float s, float o) const {
+        return State{s, o, (FAST && float_fast_ok<R>(fmt)) ? pow2_reciprocal_bits(s) : 0u};
+    }
+    __device__ __forceinline__ bool fast(const State& st) const { return st.rb != 0u; }
+    __device__ __forceinline__ float quant1(float v, const State& st) const {
+        const float q = st.rb ? quant_float_rne_pow2(v, __uint_as_float(st.rb), fmt) : quant_float_scalar<R>(v, st.s, fmt, rounding);
+        return (q - st.o) * st.s;
+    }
+    __device__ __forceinline__ float4 quant4(const float4& a, const State& st) const {
+        return make_float4(quant1(a.x, st), quant1(a.y, st), quant1(a.z, st), quant1(a.w, st));
+    }
+};
+
+// the fast path is kernel-uniform per tensor; per channel it diverges only where a wave straddles channels of both kinds
 template <int R, int U, bool NT>
 __global__ __launch_bounds__(kBlock) void fq_float_t_tile_kernel(
     const float4* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ offset,
     float4* __restrict__ out, uint32_t nvec, const float* __restrict__ xtail, float* __restrict__ otail,
     int ntail, FloatFmt fmt, int rounding) {
-    const uint32_t base = blockIdx.x * (kBlock * U) + threadIdx.x;
-    float4 a[U];
-#pragma unroll
-    for (int k = 0; k < U; k++)
-        a[k] = load4<NT>(&x[min(base + k * kBlock, nvec - 1)]);   // branch-free (clamped) so all U loads issue back to back
-    const float s = scale[0], o = offset[0];
-    const uint32_t rb = float_fast_ok<R>(fmt) ? pow2_reciprocal_bits(s) : 0u;
-    if (rb) {                                                     // kernel-uniform
-        const float rcp = __uint_as_float(rb);
-#pragma unroll
-        for (int k = 0; k < U; k++) {                             // unconditional arithmetic, predicated store (see linear.hip)
-            float4 r;
-            r.x = (quant_float_rne_pow2(a[k].x, rcp, fmt) - o) * s;
-            r.y = (quant_float_rne_pow2(a[k].y, rcp, fmt) - o) * s;
-            r.z = (quant_float_rne_pow2(a[k].z, rcp, fmt) - o) * s;
-            r.w = (quant_float_rne_pow2(a[k].w, rcp, fmt) - o) * s;
-            if (base + k * kBlock < nvec) out[base + k * kBlock] = r;
-        }
-        if (blockIdx.x == 0 && (int)threadIdx.x < ntail)
-            otail[threadIdx.x] = (quant_float_rne_pow2(xtail[threadIdx.x], rcp, fmt) - o) * s;
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < U; k++) {
-        if (base + k * kBlock < nvec) {
-            float4 r;
-            r.x = (quant_float_scalar<R>(a[k].x, s, fmt, rounding) - o) * s;
-            r.y = (quant_float_scalar<R>(a[k].y, s, fmt, rounding) - o) * s;
-            r.z = (quant_float_scalar<R>(a[k].z, s, fmt, rounding) - o) * s;
-            r.w = (quant_float_scalar<R>(a[k].w, s, fmt, rounding) - o) * s;
-            out[base + k * kBlock] = r;
-        }
-    }
-    if (blockIdx.x == 0 && (int)threadIdx.x < ntail)
-        otail[threadIdx.x] = (quant_float_scalar<R>(xtail[threadIdx.x], s, fmt, rounding) - o) * s;
-}
-
-// generic (scalar) per-tensor / per-channel kernel; num_channel.d == 0 selects per tensor
-template <int R>
-__global__ __launch_bounds__(kBlock) void fq_float_scalar_kernel(
-    const float* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ offset,
-    float* __restrict__ out, uint32_t n, FastDiv elem_per_channel, FastDiv num_channel, int per_channel,
-    FloatFmt fmt, int rounding) {
-    const uint32_t stride = gridDim.x * kBlock;
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-        uint32_t c = 0;
-        if (per_channel) {
-            const uint32_t row = fdiv(i, elem_per_channel);
-            c = row - fdiv(row, num_channel) * num_channel.d;
-        }
-        const float s = scale[c], o = offset[c];
-        out[i] = (quant_float_scalar<R>(x[i], s, fmt, rounding) - o) * s;
-    }
+    fq_tile_t<U, NT, FQ_GUARD_SLOW>(FloatQ<R>{fmt, rounding}, x, scale, offset, out, nvec, xtail, otail, ntail);
 }
 
 template <int R, int U, bool NT>
@@ -170,41 +137,17 @@ __global__ __launch_bounds__(kBlock) void fq_float_c_tile_kernel(
     const float4* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ offset,
     float4* __restrict__ out, uint32_t nvec, FastDiv vec_per_channel, FastDiv num_channel, FloatFmt fmt,
     int rounding) {
-    const uint32_t base = blockIdx.x * (kBlock * U) + threadIdx.x;
-    float4 a[U];
-    float s[U], o[U];
-#pragma unroll
-    for (int k = 0; k < U; k++) {
-        const uint32_t vv = min(base + k * kBlock, nvec - 1);      // clamped: branch-free loads
-        {
-            a[k] = load4<NT>(&x[vv]);
-            const uint32_t row = fdiv(vv, vec_per_channel);
-            const uint32_t c = row - fdiv(row, num_channel) * num_channel.d;
-            s[k] = scale[c];
-            o[k] = offset[c];
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < U; k++) {
-        const uint32_t vv = base + k * kBlock;
-        const uint32_t rb = float_fast_ok<R>(fmt) ? pow2_reciprocal_bits(s[k]) : 0u;
-        if (rb) {                                                  // diverges only where a wave straddles channels of both kinds
-            const float rcp = __uint_as_float(rb);                 // unconditional arithmetic, predicated store (see linear.hip)
-            float4 r;
-            r.x = (quant_float_rne_pow2(a[k].x, rcp, fmt) - o[k]) * s[k];
-            r.y = (quant_float_rne_pow2(a[k].y, rcp, fmt) - o[k]) * s[k];
-            r.z = (quant_float_rne_pow2(a[k].z, rcp, fmt) - o[k]) * s[k];
-            r.w = (quant_float_rne_pow2(a[k].w, rcp, fmt) - o[k]) * s[k];
-            if (vv < nvec) out[vv] = r;
-        } else if (vv < nvec) {
-            float4 r;
-            r.x = (quant_float_scalar<R>(a[k].x, s[k], fmt, rounding) - o[k]) * s[k];
-            r.y = (quant_float_scalar<R>(a[k].y, s[k], fmt, rounding) - o[k]) * s[k];
-            r.z = (quant_float_scalar<R>(a[k].z, s[k], fmt, rounding) - o[k]) * s[k];
-            r.w = (quant_float_scalar<R>(a[k].w, s[k], fmt, rounding) - o[k]) * s[k];
-            out[vv] = r;
-        }
-    }
+    fq_tile_c<U, NT, FQ_GUARD_SLOW>(FloatQ<R>{fmt, rounding}, x, scale, offset, out, nvec, blockIdx.x, vec_per_channel, num_channel);
+}
+
+// element-wise per-tensor (per_channel == 0) / per-channel kernel
+template <int R>
+__global__ __launch_bounds__(kBlock) void fq_float_scalar_kernel(
+    const float* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ offset,
+    float* __restrict__ out, uint32_t n, FastDiv elem_per_channel, FastDiv num_channel, int per_channel,
+    FloatFmt fmt, int rounding) {
+    fq_elems(FloatQ<R, false>{fmt, rounding}, x, scale, offset, out, blockIdx.x * kBlock + threadIdx.x, n, gridDim.x * kBlock,
+             per_channel != 0, elem_per_channel, num_channel);
 }
 
 // QuantizeTensor_FT_B / _FC_B, floating.cu:133-331: STE + scale gradient with +-1 sentinel clip.
@@ -223,6 +166,21 @@ __device__ __forceinline__ float fq_float_bwd_elem(float v, float d, float s, fl
     return (q - v) * inv_s * d;
 }
 
+// fq_float_bwd_elem for the elements of one channel, as the element functor of fq_bwd_row
+struct FloatBwdChannel {
+    float s, inv_s, o, cmin, cmax;
+    const FloatFmt& fmt_wide;
+    float clip_min, clip_max;
+    int rounding;
+    __device__ __forceinline__ FloatBwdChannel(float scale, float offset, const FloatFmt& fmt_wide, float clip_min, float clip_max,
+                                               int rounding)
+        : s(scale), inv_s(1 / scale), o(offset), cmin(s * (clip_min - o)), cmax(s * (clip_max - o)), fmt_wide(fmt_wide),
+          clip_min(clip_min), clip_max(clip_max), rounding(rounding) {}
+    __device__ __forceinline__ float operator()(float v, float d, float* gx) const {
+        return fq_float_bwd_elem(v, d, s, inv_s, o, cmin, cmax, fmt_wide, clip_min, clip_max, rounding, gx);
+    }
+};
+
 constexpr uint32_t kFloatBwdChunk = 4096;      // elements per workgroup
 template <bool NT>
 __global__ __launch_bounds__(kBlock) void fq_float_bwd_row_kernel(
@@ -233,38 +191,10 @@ __global__ __launch_bounds__(kBlock) void fq_float_bwd_row_kernel(
     const uint32_t row = fdiv(blockIdx.x, chunks);
     const uint32_t chunk = blockIdx.x - row * chunks.d;
     const uint32_t c = row - fdiv(row, num_channel) * num_channel.d;
-    const float s = scale[c], inv_s = 1 / s, o = offset[c];
-    const float cmin = s * (clip_min - o), cmax = s * (clip_max - o);
+    const FloatBwdChannel elem(scale[c], offset[c], fmt_wide, clip_min, clip_max, rounding);
     const uint32_t lo = chunk * kFloatBwdChunk, hi = min(lo + kFloatBwdChunk, epc);
     const size_t base = (size_t)row * epc;
-    float acc = 0.f;
-    if (vec_ok) {                                  // epc % 4 == 0, 16-B aligned bases: 4 (x, dy) load pairs in flight per lane
-        const float4* xv = reinterpret_cast<const float4*>(x + base);
-        const float4* dv = reinterpret_cast<const float4*>(dy + base);
-        float4* gv = reinterpret_cast<float4*>(gx + base);
-        const uint32_t v1 = hi >> 2;
-        for (uint32_t v = (lo >> 2) + threadIdx.x; v < v1; v += kBlock * 4) {
-            float4 a[4], d[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) { const uint32_t at = min(v + u * kBlock, v1 - 1); a[u] = load4<NT>(&xv[at]); d[u] = load4<NT>(&dv[at]); }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                if (v + u * kBlock >= v1) break;
-                float4 g;
-                acc += fq_float_bwd_elem(a[u].x, d[u].x, s, inv_s, o, cmin, cmax, fmt_wide, clip_min, clip_max, rounding, &g.x);
-                acc += fq_float_bwd_elem(a[u].y, d[u].y, s, inv_s, o, cmin, cmax, fmt_wide, clip_min, clip_max, rounding, &g.y);
-                acc += fq_float_bwd_elem(a[u].z, d[u].z, s, inv_s, o, cmin, cmax, fmt_wide, clip_min, clip_max, rounding, &g.z);
-                acc += fq_float_bwd_elem(a[u].w, d[u].w, s, inv_s, o, cmin, cmax, fmt_wide, clip_min, clip_max, rounding, &g.w);
-                gv[v + u * kBlock] = g;
-            }
-        }
-    } else {
-        for (uint32_t j = lo + threadIdx.x; j < hi; j += kBlock) {
-            float g;
-            acc += fq_float_bwd_elem(x[base + j], dy[base + j], s, inv_s, o, cmin, cmax, fmt_wide, clip_min, clip_max, rounding, &g);
-            gx[base + j] = g;
-        }
-    }
+    float acc = fq_bwd_row<4, NT>(x + base, dy + base, gx + base, lo, hi, vec_ok != 0, 0.f, elem);
     acc = wave_sum(acc);
     const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (lane == 0) lds[wid] = acc;
@@ -276,145 +206,39 @@ __global__ __launch_bounds__(kBlock) void fq_float_bwd_row_kernel(
     }
 }
 
-// short rows (elem_per_channel < 64: [N, C] matrices, channel-last views): grid-stride over elements, per-channel sums in
-// LDS (num_channel <= 8192) or straight global atomics, one flush per workgroup
+// short rows (elem_per_channel < 64: [N, C] matrices, channel-last views): fq_bwd_generic
 __global__ __launch_bounds__(kBlock) void fq_float_bwd_generic_kernel(
     const float* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ offset,
     const float* __restrict__ dy, float* __restrict__ gx, float* __restrict__ gs, uint32_t n, FastDiv elem_per_channel,
     FastDiv num_channel, int use_lds, FloatFmt fmt_wide, float clip_min, float clip_max, float denom, int rounding) {
-    extern __shared__ float acc_lds[];
-    const uint32_t C = num_channel.d;
-    if (use_lds) {
-        for (uint32_t c = threadIdx.x; c < C; c += kBlock) acc_lds[c] = 0.f;
-        __syncthreads();
-    }
-    const uint32_t stride = gridDim.x * kBlock;
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-        const uint32_t row = fdiv(i, elem_per_channel);
-        const uint32_t c = row - fdiv(row, num_channel) * C;
-        const float s = scale[c], inv_s = 1 / s, o = offset[c];
-        float g;
-        const float p = fq_float_bwd_elem(x[i], dy[i], s, inv_s, o, s * (clip_min - o), s * (clip_max - o), fmt_wide, clip_min,
-                                          clip_max, rounding, &g);
-        gx[i] = g;
-        if (use_lds) atomicAdd(&acc_lds[c], p);
-        else atomicAdd(&gs[c], p / denom);
-    }
-    if (use_lds) {
-        __syncthreads();
-        for (uint32_t c = threadIdx.x; c < C; c += kBlock) {
-            const float v = acc_lds[c];
-            if (v != 0.f) atomicAdd(&gs[c], v / denom);
-        }
-    }
+    fq_bwd_generic(x, dy, gx, gs, n, elem_per_channel, num_channel, use_lds,
+                   [&](uint32_t c, float v, float d, float* g) {
+                       return FloatBwdChannel(scale[c], offset[c], fmt_wide, clip_min, clip_max, rounding)(v, d, g);
+                   },
+                   [&](float sum) { return sum / denom; });
 }
 
 // grad_s[c] = (sum of the partials of channel c: rows c, c + C, .. x their chunks, in index order) / denom
 __global__ __launch_bounds__(kBlock) void fq_float_bwd_finish_kernel(const float* __restrict__ partial, uint32_t rows, uint32_t chunks,
                                                                      uint32_t C, float denom, float* __restrict__ gs) {
-    __shared__ double lds[kBlock / kWave];
     const uint32_t c = blockIdx.x;
-    const uint32_t per_channel = (rows / C) * chunks;                 // partials of this channel
-    double acc = 0.0;
-    for (uint32_t i = threadIdx.x; i < per_channel; i += 8 * kBlock) {          // 8 loads in flight per lane
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const uint32_t at = i + u * kBlock, r = at / chunks, k = at - r * chunks;
-            v[u] = at < per_channel ? partial[(size_t)(r * C + c) * chunks + k] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < 8; u++) acc += (double)v[u];
-    }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) acc += __shfl_xor(acc, m, 64);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < kBlock / kWave; w++) t += lds[w];
-        gs[c] = (float)t / denom;
-    }
+    const double t = fq_finish_sum<kBlock>((rows / C) * chunks, [&](uint32_t at) {
+        const uint32_t r = at / chunks, k = at - r * chunks;
+        return partial[(size_t)(r * C + c) * chunks + k];
+    });
+    if (threadIdx.x == 0) gs[c] = (float)t / denom;
 }
 
-// ---- many tensors, one launch (the design of fq_linear_multi_kernel, linear.hip) ---------------------------
-// The TRT_FP8 policy fake-quantises the weight of every Conv / Gemm / MatMul per channel on every forward
-// (ViT-B/16: 50 weights): one launch serves them all.  Device job table + workgroup-count prefix in the arguments.
-constexpr int kFqFloatMultiMax = 128;
-struct FqFloatJob {
-    const float* x;
-    float* out;
-    const float* scale;
-    const float* offset;
-    uint32_t n;
-    uint32_t vec_ok;
-    FastDiv per;          // vec_ok: float4 per channel row; else elements per channel row
-    FastDiv nc;
-    FloatFmt fmt;
-};
-struct FqFloatMultiArgs {
-    uint32_t first_block[kFqFloatMultiMax];
-    uint32_t count;
-    int rounding;
-    const FqFloatJob* jobs;
-};
+// ---- many tensors, one launch (fq_walk.hpp) -------------------------------------------------------------------
+typedef FqJobOf<FloatFmt> FqFloatJob;
+typedef FqMultiArgsOf<FqFloatJob> FqFloatMultiArgs;
+static_assert(sizeof(FqFloatJob) == 112, "callers size the device table with ppqhip_fq_float_multi_table_bytes");
 
 template <int R, int U>
 __global__ __launch_bounds__(kBlock) void fq_float_multi_kernel(const FqFloatMultiArgs args) {
-    uint32_t lo = 0, hi = args.count;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (args.first_block[mid] <= blockIdx.x) lo = mid; else hi = mid;
-    }
-    const FqFloatJob j = args.jobs[lo];                 // uniform address: scalar loads
-    const uint32_t base = (blockIdx.x - args.first_block[lo]) * (kBlock * U) + threadIdx.x;
-    const uint32_t C = j.nc.d;
-    auto one = [&](float v, float s, float o, uint32_t rb) {
-        const float q = rb ? quant_float_rne_pow2(v, __uint_as_float(rb), j.fmt) : quant_float_scalar<R>(v, s, j.fmt, args.rounding);
-        return (q - o) * s;
-    };
-    if (j.vec_ok) {
-        const uint32_t nvec = j.n >> 2;
-        const float4* xv = reinterpret_cast<const float4*>(j.x);
-        float4* ov = reinterpret_cast<float4*>(j.out);
-        float4 a[U];
-        float s[U], o[U];
-#pragma unroll
-        for (int k = 0; k < U; k++) {
-            const uint32_t vv = min(base + k * kBlock, nvec - 1);
-            a[k] = xv[vv];
-            const uint32_t row = fdiv(vv, j.per);
-            const uint32_t c = row - fdiv(row, j.nc) * C;
-            s[k] = j.scale[c];
-            o[k] = j.offset[c];
-        }
-#pragma unroll
-        for (int k = 0; k < U; k++) {
-            const uint32_t vv = base + k * kBlock;
-            if (vv < nvec) {
-                const uint32_t rb = float_fast_ok<R>(j.fmt) ? pow2_reciprocal_bits(s[k]) : 0u;
-                float4 r;
-                r.x = one(a[k].x, s[k], o[k], rb); r.y = one(a[k].y, s[k], o[k], rb);
-                r.z = one(a[k].z, s[k], o[k], rb); r.w = one(a[k].w, s[k], o[k], rb);
-                ov[vv] = r;
-            }
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < U; k++) {
-            const uint32_t e0 = (base + k * kBlock) * 4;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const uint32_t e = e0 + q;
-                if (e < j.n) {
-                    const uint32_t row = fdiv(e, j.per);
-                    const uint32_t c = row - fdiv(row, j.nc) * C;
-                    const float sc = j.scale[c];
-                    j.out[e] = one(j.x[e], sc, j.offset[c], float_fast_ok<R>(j.fmt) ? pow2_reciprocal_bits(sc) : 0u);
-                }
-            }
-        }
-    }
+    uint32_t local;
+    const FqFloatJob j = args.jobs[job_of(args, local)];        // uniform address: scalar loads
+    fq_multi_tile<U, FQ_GUARD_ALL>(FloatQ<R>{j.fmt, args.rounding}, j.x, j.out, j.scale, j.offset, j.n, j.vec_ok, j.per, j.nc, local);
 }
 
 // ---- the scale search of the FP8 'floating' observer, batched ------------------------------------------------
@@ -433,7 +257,7 @@ struct FloatSearchJob {
     FloatFmt fmt;
 };
 struct FloatSearchArgs {
-    uint32_t first_row[kSearchMaxJobs];      // prefix of row counts: workgroup -> job
+    uint32_t first_block[kSearchMaxJobs];    // prefix of row counts (one workgroup per row): workgroup -> job
     uint32_t count;
     int rounding, num_candidates;
     float candidate[kSearchMaxCandidates];
@@ -445,13 +269,9 @@ struct FloatSearchArgs {
 template <int R>
 __global__ __launch_bounds__(kBlock) void float_scale_search_kernel(const FloatSearchArgs args) {
     __shared__ double red[kSearchMaxCandidates][kBlock / kWave];
-    uint32_t lo = 0, hi = args.count;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (args.first_row[mid] <= blockIdx.x) lo = mid; else hi = mid;
-    }
-    const FloatSearchJob j = args.jobs[lo];
-    const float* __restrict__ row = j.x + (size_t)(blockIdx.x - args.first_row[lo]) * j.row_len;
+    uint32_t local;
+    const FloatSearchJob j = args.jobs[job_of(args, local)];
+    const float* __restrict__ row = j.x + (size_t)local * j.row_len;
     double acc[kSearchMaxCandidates];
     uint32_t rb[kSearchMaxCandidates];
 #pragma unroll
@@ -488,32 +308,18 @@ __global__ __launch_bounds__(kBlock) void float_scale_search_kernel(const FloatS
     }
 }
 
-static int validate(int64_t n, const char* what) {
-    if (n <= 0) { set_error("%s: tensor is empty", what); return PPQHIP_ERR_INVALID_VALUE; }
-    if (n > 0x7fffffffLL) { set_error("%s: too many elements", what); return PPQHIP_ERR_INVALID_VALUE; }
-    return PPQHIP_OK;
-}
-
-constexpr int64_t kStreamElems = 48ll << 20;   // >= 192 MiB: streaming loads (see linear.hip)
-constexpr int kTileU = 2;
-constexpr int kSmallU = 1;                     // latency-bound tensors: twice the waves, half the work behind each load (linear.hip)
-constexpr int64_t kSmallElems = 4ll << 20;
-
 template <int R>
 static void launch_ft(const float* x, const float* scale, const float* offset, float* out, int64_t n,
                       const FloatFmt& fmt, int rounding, hipStream_t st) {
-    if (aligned16(x) && aligned16(out) && n >= 4) {
+    if (fq_vec_ok(x, out) && n >= 4) {
         const uint32_t nvec = (uint32_t)(n >> 2);
         const int ntail = (int)(n & 3);
         const float* xt = x + (size_t)nvec * 4;
         float* ot = out + (size_t)nvec * 4;
-#define PPQ_LAUNCH_FT(U, NT)                                                                                          \
-        hipLaunchKernelGGL((fq_float_t_tile_kernel<R, U, NT>), dim3((nvec + kBlock * U - 1) / (kBlock * U)), dim3(kBlock), 0, st, \
-                           (const float4*)x, scale, offset, (float4*)out, nvec, xt, ot, ntail, fmt, rounding)
-        if (n >= kStreamElems) PPQ_LAUNCH_FT(kTileU, true);
-        else if (n <= kSmallElems) PPQ_LAUNCH_FT(kSmallU, false);
-        else PPQ_LAUNCH_FT(kTileU, false);
-#undef PPQ_LAUNCH_FT
+        with_tile_shape(n, [&](auto u, auto nt) {
+            hipLaunchKernelGGL((fq_float_t_tile_kernel<R, decltype(u)::value, decltype(nt)::value>), tile_grid(nvec, u), dim3(kBlock), 0,
+                               st, (const float4*)x, scale, offset, (float4*)out, nvec, xt, ot, ntail, fmt, rounding);
+        });
     } else {
         hipLaunchKernelGGL((fq_float_scalar_kernel<R>), dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, st, x, scale,
                            offset, out, (uint32_t)n, make_fastdiv(1), make_fastdiv(1), 0, fmt, rounding);
@@ -523,20 +329,17 @@ static void launch_ft(const float* x, const float* scale, const float* offset, f
 template <int R>
 static void launch_fc(const float* x, const float* scale, const float* offset, float* out, int64_t n, int64_t C,
                       int64_t epc, const FloatFmt& fmt, int rounding, hipStream_t st) {
-    if (aligned16(x) && aligned16(out) && epc % 4 == 0) {
+    const FastDiv nc = make_fastdiv((uint32_t)C);
+    if (fq_vec_ok(x, out, epc)) {
         const uint32_t nvec = (uint32_t)(n >> 2);
-        const FastDiv vpc = make_fastdiv((uint32_t)(epc / 4)), nc = make_fastdiv((uint32_t)C);
-#define PPQ_LAUNCH_FC(U, NT)                                                                                          \
-        hipLaunchKernelGGL((fq_float_c_tile_kernel<R, U, NT>), dim3((nvec + kBlock * U - 1) / (kBlock * U)), dim3(kBlock), 0, st, \
-                           (const float4*)x, scale, offset, (float4*)out, nvec, vpc, nc, fmt, rounding)
-        if (n >= kStreamElems) PPQ_LAUNCH_FC(kTileU, true);
-        else if (n <= kSmallElems) PPQ_LAUNCH_FC(kSmallU, false);
-        else PPQ_LAUNCH_FC(kTileU, false);
-#undef PPQ_LAUNCH_FC
+        const FastDiv vpc = make_fastdiv((uint32_t)(epc / 4));
+        with_tile_shape(n, [&](auto u, auto nt) {
+            hipLaunchKernelGGL((fq_float_c_tile_kernel<R, decltype(u)::value, decltype(nt)::value>), tile_grid(nvec, u), dim3(kBlock), 0,
+                               st, (const float4*)x, scale, offset, (float4*)out, nvec, vpc, nc, fmt, rounding);
+        });
     } else {
         hipLaunchKernelGGL((fq_float_scalar_kernel<R>), dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, st, x, scale,
-                           offset, out, (uint32_t)n, make_fastdiv((uint32_t)epc), make_fastdiv((uint32_t)C), 1, fmt,
-                           rounding);
+                           offset, out, (uint32_t)n, make_fastdiv((uint32_t)epc), nc, 1, fmt, rounding);
     }
 }
 
@@ -549,7 +352,7 @@ extern "C" {
 int ppqhip_fq_float_t(const float* x, const float* scale, const float* offset, float* out, int64_t n,
                       int exponent, int mantissa, float clip_min, float clip_max, int rounding,
                       void* stream) {
-    if (int st = validate(n, "fq_float_t")) return st;
+    if (int st = validate_n(n, "fq_float_t")) return st;
     FloatFmt fmt;
     if (int st = make_fmt(exponent, mantissa, clip_min, clip_max, &fmt, "fq_float_t")) return st;
     hipStream_t s = (hipStream_t)stream;
@@ -562,10 +365,8 @@ int ppqhip_fq_float_t(const float* x, const float* scale, const float* offset, f
 int ppqhip_fq_float_c(const float* x, const float* scale, const float* offset, float* out, int64_t n,
                       int64_t num_channel, int64_t elem_per_channel, int exponent, int mantissa,
                       float clip_min, float clip_max, int rounding, void* stream) {
-    if (int st = validate(n, "fq_float_c")) return st;
-    if (num_channel <= 0 || elem_per_channel <= 0 || n % (num_channel * elem_per_channel) != 0) {
-        set_error("fq_float_c: bad channel geometry"); return PPQHIP_ERR_INVALID_VALUE;
-    }
+    if (int st = validate_n(n, "fq_float_c")) return st;
+    if (int st = validate_channels(n, num_channel, elem_per_channel, "fq_float_c")) return st;
     FloatFmt fmt;
     if (int st = make_fmt(exponent, mantissa, clip_min, clip_max, &fmt, "fq_float_c")) return st;
     hipStream_t s = (hipStream_t)stream;
@@ -582,61 +383,18 @@ int64_t ppqhip_fq_float_multi_table_bytes(int num_jobs) {
 
 int ppqhip_fq_float_multi(const ppqhip_fq_float_job* jobs, int num_jobs, int rounding, void* device_table, int upload,
                           void* stream) {
-    if (num_jobs <= 0) return PPQHIP_OK;
-    if (jobs == nullptr || device_table == nullptr) {
-        set_error("fq_float_multi: jobs / device_table is null"); return PPQHIP_ERR_INVALID_VALUE;
-    }
     hipStream_t s = (hipStream_t)stream;
-    double bytes = 0.0;
-    for (int k = 0; k < num_jobs; k++) {
-        const ppqhip_fq_float_job& j = jobs[k];
-        if (int st = validate(j.n, "fq_float_multi")) return st;
-        if (j.num_channel <= 0 || j.elem_per_channel <= 0 || j.n % (j.num_channel * j.elem_per_channel) != 0) {
-            set_error("fq_float_multi: job %d has a bad channel geometry", k); return PPQHIP_ERR_INVALID_VALUE;
-        }
-        if (!j.x || !j.out || !j.scale || !j.offset) {
-            set_error("fq_float_multi: job %d has a null pointer", k); return PPQHIP_ERR_INVALID_VALUE;
-        }
-        FloatFmt probe;
-        if (int st = make_fmt(j.exponent, j.mantissa, j.clip_min, j.clip_max, &probe, "fq_float_multi")) return st;
-        bytes += 8.0 * (double)j.n;
-    }
-    LaunchScope scope(K_FQ_FLOAT_C, bytes, s);
-    constexpr int U = 2;
-    for (int base = 0; base < num_jobs; base += kFqFloatMultiMax) {
-        const int count = (num_jobs - base) < kFqFloatMultiMax ? (num_jobs - base) : kFqFloatMultiMax;
-        FqFloatMultiArgs args;
-        args.count = (uint32_t)count; args.rounding = rounding;
-        args.jobs = (const FqFloatJob*)device_table + base;
-        std::vector<FqFloatJob> table(upload ? count : 0);
-        uint32_t blocks = 0;
-        for (int k = 0; k < count; k++) {
-            const ppqhip_fq_float_job& src = jobs[base + k];
-            const bool vec = aligned16(src.x) && aligned16(src.out) && (src.elem_per_channel % 4 == 0);
-            args.first_block[k] = blocks;
-            const uint64_t quads = ((uint64_t)src.n + 3) / 4;
-            blocks += (uint32_t)((quads + kBlock * U - 1) / (kBlock * U));
-            if (upload) {
-                FqFloatJob& d = table[k];
-                d.x = src.x; d.out = src.out; d.scale = src.scale; d.offset = src.offset;
-                d.n = (uint32_t)src.n; d.vec_ok = vec ? 1u : 0u;
-                d.per = make_fastdiv((uint32_t)(vec ? src.elem_per_channel / 4 : src.elem_per_channel));
-                d.nc = make_fastdiv((uint32_t)src.num_channel);
-                make_fmt(src.exponent, src.mantissa, src.clip_min, src.clip_max, &d.fmt, "fq_float_multi");
-            }
-        }
-        if (upload) {
-            // pageable source: the runtime stages the copy before returning, `table` may go out of scope
-            if (int st = check_hip(hipMemcpyAsync((FqFloatJob*)device_table + base, table.data(), sizeof(FqFloatJob) * count,
-                                                  hipMemcpyHostToDevice, s), "fq_float_multi table upload"))
-                return st;
-        }
-        if (rounding == ROUND_HALF_EVEN)
-            hipLaunchKernelGGL((fq_float_multi_kernel<ROUND_HALF_EVEN, U>), dim3(blocks), dim3(kBlock), 0, s, args);
-        else
-            hipLaunchKernelGGL((fq_float_multi_kernel<-1, U>), dim3(blocks), dim3(kBlock), 0, s, args);
-    }
-    return finish_launch("fq_float_multi");
+    return fq_multi<FloatFmt>(
+        "fq_float_multi", K_FQ_FLOAT_C, jobs, num_jobs, rounding, device_table, upload, s,
+        [](const ppqhip_fq_float_job& src, FloatFmt* f) {
+            return make_fmt(src.exponent, src.mantissa, src.clip_min, src.clip_max, f, "fq_float_multi");
+        },
+        [&](uint32_t blocks, const FqFloatMultiArgs& args) {
+            if (rounding == ROUND_HALF_EVEN)
+                hipLaunchKernelGGL((fq_float_multi_kernel<ROUND_HALF_EVEN, kFqMultiU>), dim3(blocks), dim3(kBlock), 0, s, args);
+            else
+                hipLaunchKernelGGL((fq_float_multi_kernel<-1, kFqMultiU>), dim3(blocks), dim3(kBlock), 0, s, args);
+        });
 }
 
 int64_t ppqhip_float_scale_search_table_bytes(int num_jobs) {
@@ -677,7 +435,7 @@ int ppqhip_float_scale_search(const ppqhip_float_search_job* jobs, int num_jobs,
         uint32_t rows = 0;
         for (int k = 0; k < count; k++) {
             const ppqhip_float_search_job& src = jobs[base + k];
-            args.first_row[k] = rows;
+            args.first_block[k] = rows;
             rows += (uint32_t)src.rows;
             table[k].x = src.x; table[k].row_len = (uint32_t)src.row_len;
             make_fmt(src.exponent, src.mantissa, src.clip_min, src.clip_max, &table[k].fmt, "float_scale_search");
@@ -696,10 +454,8 @@ int ppqhip_fq_float_c_bwd(const float* x, const float* scale, const float* offse
                           float* grad_x, float* grad_s, int64_t n, int64_t num_channel,
                           int64_t elem_per_channel, int exponent, int mantissa, float clip_min,
                           float clip_max, int rounding, void* stream) {
-    if (int st = validate(n, "fq_float_c_bwd")) return st;
-    if (num_channel <= 0 || elem_per_channel <= 0 || n % (num_channel * elem_per_channel) != 0) {
-        set_error("fq_float_c_bwd: bad channel geometry"); return PPQHIP_ERR_INVALID_VALUE;
-    }
+    if (int st = validate_n(n, "fq_float_c_bwd")) return st;
+    if (int st = validate_channels(n, num_channel, elem_per_channel, "fq_float_c_bwd")) return st;
     FloatFmt fmt;   // the backward quantises against [clip_min - 1, clip_max + 1]: floating.cu:163-164
     if (int st = make_fmt(exponent, mantissa, clip_min - 1, clip_max + 1, &fmt, "fq_float_c_bwd")) return st;
     hipStream_t s = (hipStream_t)stream;
@@ -719,7 +475,7 @@ int ppqhip_fq_float_c_bwd(const float* x, const float* scale, const float* offse
     if (rows * chunks > 0x7fffffffLL) { set_error("fq_float_c_bwd: too many rows"); return PPQHIP_ERR_INVALID_VALUE; }
     float* partial = (float*)scratch(s, sizeof(float) * (size_t)(rows * chunks));
     if (partial == nullptr) return PPQHIP_ERR_HIP;
-    const int vec_ok = (elem_per_channel % 4 == 0 && aligned16(x) && aligned16(grad_y) && aligned16(grad_x)) ? 1 : 0;
+    const int vec_ok = fq_bwd_vec_ok(x, grad_y, grad_x, elem_per_channel) ? 1 : 0;
     // x and dy together exceed cache residency from 96 MiB each: streaming (nontemporal) loads, as the linear backward kernels
     if (n >= (24ll << 20))
         hipLaunchKernelGGL(fq_float_bwd_row_kernel<true>, dim3((uint32_t)(rows * chunks)), dim3(kBlock), 0, s, x, scale, offset, grad_y,

@@ -3,106 +3,61 @@
 // Replaces ppq/csrc/cuda/linear.cu.  Design (not a translation of the CUDA launch shapes):
 //   * HBM-bound streaming: 16 B per lane per access (global_load_dwordx4 / global_store_dwordx4),
 //     one wavefront = 1 KiB per instruction, 2 independent accesses in flight per lane;
-//   * one contiguous tile of 512 float4 per 256-thread workgroup and as many workgroups as tiles:
-//     on MI355X this streams faster than a chip-sized persistent grid-stride loop, and tiny
-//     tensors still spread over every CU;
 //   * per-tensor scale / offset live in SGPRs (uniform scalar loads);
-//   * per-channel: the channel of a float4 is found with a multiply-high division by an
-//     invariant (no integer divide in the loop); scale/offset gathers hit L1/L2;
-//   * the tail (n % 4) and unaligned tensors run through the same arithmetic in a scalar kernel,
+//   * the tail (n % 4) and unaligned tensors run through the same arithmetic element-wise,
 //     so results do not depend on the launch shape.
+// The walks themselves (tiles, element-wise fallback, backward rows, finish sum) and their tuning rationale are in fq_walk.hpp,
+// shared with floating.hip; this file holds the integer arithmetic and the entry points.
 #include <cstdlib>
 
-#include <vector>
-
-#include "common.hpp"
+#include "fq_walk.hpp"
 
 namespace ppqhip {
 
-// --------------------------------------------------------------------------- per tensor forward
-// One tile per workgroup, no loop: workgroup b owns float4s [b * kBlock * U, (b + 1) * kBlock * U).
-// Tens of thousands of short-lived workgroups over contiguous tiles stream faster than a
-// persistent grid-stride loop on MI355X (6.8 vs 4.9 TB/s on 205 MB in + 205 MB out).  NT selects
-// streaming loads for tensors that cannot be cache resident anyway; stores stay cacheable because
-// the next operation of the graph consumes the output.
+// --------------------------------------------------------------------------- forward
+// the integer grid as a quantiser policy of fq_walk.hpp
+template <int R>
+struct LinearQ {
+    int qmin, qmax, rounding;
+    struct State { float s, rc; int o; };
+    __device__ __forceinline__ State make(float s, float o) const {
+        const int oi = round_offset(o);
+        return State{s, fq_safe_rcp(s), oi};
+    }
+    __device__ __forceinline__ float4 quant4(const float4& a, const State& st) const {
+        return fq_linear4<R>(a, st.s, st.rc, st.o, qmin, qmax, rounding);
+    }
+    __device__ __forceinline__ float quant1(float x, const State& st) const {
+        return fq_linear_scalar<R>(x, st.s, st.o, qmin, qmax, rounding);
+    }
+};
+
 template <int R, int U, bool NT>
 __global__ __launch_bounds__(kBlock) void fq_linear_t_tile_kernel(
     const float4* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ offset,
     float4* __restrict__ out, uint32_t nvec, const float* __restrict__ xtail, float* __restrict__ otail,
     int ntail, int qmin, int qmax, int rounding) {
-    const uint32_t base = blockIdx.x * (kBlock * U) + threadIdx.x;
-    float4 a[U];
-#pragma unroll
-    for (int k = 0; k < U; k++)
-        a[k] = load4<NT>(&x[min(base + k * kBlock, nvec - 1)]);   // branch-free (clamped) so all U loads issue back to back
-    const float s = scale[0];
-    const int o = round_offset(offset[0]);
-    const float rc = fq_safe_rcp(s);
-    // the arithmetic is unconditional (lanes past the end recompute the clamped element), only the STORE is predicated: with
-    // the whole body under `if (v < nvec)` the compiler sinks the loads into the branch, behind the wait for the scale
-#pragma unroll
-    for (int k = 0; k < U; k++) {
-        const float4 r = fq_linear4<R>(a[k], s, rc, o, qmin, qmax, rounding);
-        if (base + k * kBlock < nvec) out[base + k * kBlock] = r;
-    }
-    if (blockIdx.x == 0 && (int)threadIdx.x < ntail)
-        otail[threadIdx.x] = fq_linear_scalar<R>(xtail[threadIdx.x], s, o, qmin, qmax, rounding);
+    fq_tile_t<U, NT, FQ_STORE_ONLY>(LinearQ<R>{qmin, qmax, rounding}, x, scale, offset, out, nvec, xtail, otail, ntail);
 }
 
+// elem_per_channel % 4 == 0, so a float4 never straddles channels
 template <int R, int U, bool NT>
 __global__ __launch_bounds__(kBlock) void fq_linear_c_tile_kernel(
     const float4* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ offset,
     float4* __restrict__ out, uint32_t nvec, FastDiv vec_per_channel, FastDiv num_channel,
     int qmin, int qmax, int rounding) {
-    const uint32_t base = blockIdx.x * (kBlock * U) + threadIdx.x;
-    float4 a[U];
-    float s[U];
-    int o[U];
-#pragma unroll
-    for (int k = 0; k < U; k++) {
-        const uint32_t vv = min(base + k * kBlock, nvec - 1);      // clamped: branch-free loads
-        {
-            a[k] = load4<NT>(&x[vv]);
-            const uint32_t row = fdiv(vv, vec_per_channel);
-            const uint32_t c = row - fdiv(row, num_channel) * num_channel.d;
-            s[k] = scale[c];
-            o[k] = round_offset(offset[c]);
-        }
-    }
-    // unconditional arithmetic, predicated store: under `if (vv < nvec)` the compiler sinks the tile's x / scale loads into the
-    // branch, BEHIND the wait for the offsets (two dependent memory round trips on a latency-bound tensor)
-#pragma unroll
-    for (int k = 0; k < U; k++) {
-        const uint32_t vv = base + k * kBlock;
-        const float4 r = fq_linear4<R>(a[k], s[k], fq_safe_rcp(s[k]), o[k], qmin, qmax, rounding);
-        if (vv < nvec) out[vv] = r;
-    }
+    fq_tile_c<U, NT, FQ_STORE_ONLY>(LinearQ<R>{qmin, qmax, rounding}, x, scale, offset, out, nvec, blockIdx.x, vec_per_channel,
+                                    num_channel);
 }
 
+// element-wise per-tensor (per_channel == 0) / per-channel kernel
 template <int R>
-__global__ __launch_bounds__(kBlock) void fq_linear_t_scalar_kernel(
+__global__ __launch_bounds__(kBlock) void fq_linear_scalar_kernel(
     const float* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ offset,
-    float* __restrict__ out, uint32_t n, int qmin, int qmax, int rounding) {
-    const float s = scale[0];
-    const int o = round_offset(offset[0]);
-    const uint32_t stride = gridDim.x * kBlock;
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
-        out[i] = fq_linear_scalar<R>(x[i], s, o, qmin, qmax, rounding);
-}
-
-// --------------------------------------------------------------------------- per channel forward
-// (vector path: fq_linear_c_tile_kernel above; elem_per_channel % 4 == 0 so a float4 never straddles channels)
-template <int R>
-__global__ __launch_bounds__(kBlock) void fq_linear_c_scalar_kernel(
-    const float* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ offset,
-    float* __restrict__ out, uint32_t n, FastDiv elem_per_channel, FastDiv num_channel,
+    float* __restrict__ out, uint32_t n, FastDiv elem_per_channel, FastDiv num_channel, int per_channel,
     int qmin, int qmax, int rounding) {
-    const uint32_t stride = gridDim.x * kBlock;
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-        const uint32_t row = fdiv(i, elem_per_channel);
-        const uint32_t c = row - fdiv(row, num_channel) * num_channel.d;
-        out[i] = fq_linear_scalar<R>(x[i], scale[c], round_offset(offset[c]), qmin, qmax, rounding);
-    }
+    fq_elems(LinearQ<R>{qmin, qmax, rounding}, x, scale, offset, out, blockIdx.x * kBlock + threadIdx.x, n, gridDim.x * kBlock,
+             per_channel != 0, elem_per_channel, num_channel);
 }
 
 // --------------------------------------------------------------------------- quantise to integer
@@ -300,30 +255,12 @@ __global__ __launch_bounds__(kBlock) void fq_linear_t_bwd_kernel(
     if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
-// One workgroup of 1024 lanes, 8 loads in flight per lane, double accumulation in a FIXED order (lane l adds
-// partial[l], partial[l + 1024], ..; then lanes, then waves, in index order): the result does not depend on timing.
-// (256 lanes adding one partial per dependent trip took 13.8 us for the 12544 partials of a [32, 512, 56, 56] tensor.)
+// the partials of fq_linear_t_bwd_kernel -> grad_s: fq_finish_sum by one workgroup of 1024 lanes
 constexpr int kLsqFinishBlock = 1024;
 __global__ __launch_bounds__(kLsqFinishBlock) void lsq_finish_kernel(const float* __restrict__ partial, uint32_t count,
                                                                      float grad_factor, float* __restrict__ gs) {
-    __shared__ double lds[kLsqFinishBlock / kWave];
-    double acc = 0.0;
-    for (uint32_t i = threadIdx.x; i < count; i += 8 * kLsqFinishBlock) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) { const uint32_t at = i + u * kLsqFinishBlock; v[u] = at < count ? partial[at] : 0.f; }
-#pragma unroll
-        for (int u = 0; u < 8; u++) acc += (double)v[u];
-    }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) acc += __shfl_xor(acc, m, 64);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < kLsqFinishBlock / kWave; w++) t += lds[w];
-        gs[0] = (float)t * grad_factor;
-    }
+    const double t = fq_finish_sum<kLsqFinishBlock>(count, [&](uint32_t i) { return partial[i]; });
+    if (threadIdx.x == 0) gs[0] = (float)t * grad_factor;
 }
 
 // the same sum for MANY scale gradients in one launch: workgroup j finishes job j exactly as lsq_finish_kernel would (same
@@ -335,28 +272,23 @@ struct LsqFinishJob { const float* partial; float* gs; uint32_t count; float gra
 struct LsqFinishArgs { LsqFinishJob job[kLsqFinishMax]; };
 static_assert(sizeof(LsqFinishArgs) <= 4096, "kernel arguments are limited to 4 KB");
 __global__ __launch_bounds__(kLsqFinishBlock) void lsq_finish_multi_kernel(const LsqFinishArgs args) {
-    __shared__ double lds[kLsqFinishBlock / kWave];
     const LsqFinishJob& j = args.job[blockIdx.x];
     const float* __restrict__ partial = j.partial;
-    const uint32_t count = j.count;
-    double acc = 0.0;
-    for (uint32_t i = threadIdx.x; i < count; i += 8 * kLsqFinishBlock) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) { const uint32_t at = i + u * kLsqFinishBlock; v[u] = at < count ? partial[at] : 0.f; }
-#pragma unroll
-        for (int u = 0; u < 8; u++) acc += (double)v[u];
-    }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) acc += __shfl_xor(acc, m, 64);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < kLsqFinishBlock / kWave; w++) t += lds[w];
-        j.gs[0] = (float)t * j.grad_factor;
-    }
+    const double t = fq_finish_sum<kLsqFinishBlock>(j.count, [&](uint32_t i) { return partial[i]; });
+    if (threadIdx.x == 0) j.gs[0] = (float)t * j.grad_factor;
 }
+
+// lsq_bwd_elem for the elements of one channel, as the element functor of fq_bwd_row
+template <int R>
+struct LsqChannel {
+    float s, rcp_s, o;
+    int oi, qmin, qmax, rounding;
+    __device__ __forceinline__ LsqChannel(float scale, float offset, int qmin, int qmax, int rounding)
+        : s(scale), rcp_s(1.0f / scale), o(__builtin_roundf(offset)), oi(f2i_sat(o)), qmin(qmin), qmax(qmax), rounding(rounding) {}
+    __device__ __forceinline__ float operator()(float v, float dy, float* gx) const {
+        return lsq_bwd_elem<true, R>(v, dy, s, rcp_s, o, oi, qmin, qmax, rounding, gx);
+    }
+};
 
 // rows = outer * C rows of `epc` contiguous elements; block b handles chunk (b % chunks) of row
 // (b / chunks) -> one channel per block, one atomic per block (spread over C addresses).
@@ -370,231 +302,73 @@ __global__ __launch_bounds__(kBlock) void fq_linear_c_bwd_row_kernel(
     const uint32_t row = fdiv(blockIdx.x, chunks);
     const uint32_t chunk = blockIdx.x - row * chunks.d;
     const uint32_t c = row - fdiv(row, num_channel) * num_channel.d;
-    const float s = scale[c];
-    const float rcp_s = 1.0f / s;
-    const float o = __builtin_roundf(offset[c]);
-    const int oi = f2i_sat(o);
+    const LsqChannel<R> elem(scale[c], offset[c], qmin, qmax, rounding);
     const uint32_t lo = chunk * chunk_elems;
     const uint32_t hi = min(lo + chunk_elems, epc);
     const size_t base = (size_t)row * epc;
-    float acc = 0.f;
-    if (vec_ok) {   // epc % 4 == 0, chunk_elems % 4 == 0, 16-B aligned bases
-        const float4* xv = reinterpret_cast<const float4*>(x + base);
-        const float4* dv = reinterpret_cast<const float4*>(dy + base);
-        float4* gv = reinterpret_cast<float4*>(gx + base);
-        // U (x, dy) load pairs in flight per lane: a 56 x 56 row (784 float4) is ONE trip of 4, all 8 loads issued up front
-        // (one pair per dependent trip kept this kernel at 0.68 of the roofline on [32, 512, 56, 56])
-        constexpr int U = kLsqCU;
-        const uint32_t v1 = hi >> 2;
-        for (uint32_t v = (lo >> 2) + threadIdx.x; v < v1; v += kBlock * U) {
-            float4 a[U], d[U];
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                const uint32_t at = min(v + u * kBlock, v1 - 1);          // clamped: loads stay unconditional
-                a[u] = load4<NT>(&xv[at]); d[u] = load4<NT>(&dv[at]);
-            }
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                if (v + u * kBlock >= v1) break;
-                float4 g;
-                acc += lsq_bwd_elem<true, R>(a[u].x, d[u].x, s, rcp_s, o, oi, qmin, qmax, rounding, &g.x);
-                acc += lsq_bwd_elem<true, R>(a[u].y, d[u].y, s, rcp_s, o, oi, qmin, qmax, rounding, &g.y);
-                acc += lsq_bwd_elem<true, R>(a[u].z, d[u].z, s, rcp_s, o, oi, qmin, qmax, rounding, &g.z);
-                acc += lsq_bwd_elem<true, R>(a[u].w, d[u].w, s, rcp_s, o, oi, qmin, qmax, rounding, &g.w);
-                gv[v + u * kBlock] = g;
-            }
-        }
-    } else {
-        for (uint32_t j = lo + threadIdx.x; j < hi; j += kBlock) {
-            float g;
-            acc += lsq_bwd_elem<true, R>(x[base + j], dy[base + j], s, rcp_s, o, oi, qmin, qmax, rounding, &g);
-            gx[base + j] = g;
-        }
-    }
+    const float acc = fq_bwd_row<kLsqCU, NT>(x + base, dy + base, gx + base, lo, hi, vec_ok != 0, 0.f, elem);
     const float tot = block_sum(acc, lds);
     if (threadIdx.x == 0) atomicAdd(&gs[c], tot * grad_factor);
 }
 
-// generic layout (small elem_per_channel, e.g. channel-last): per-element atomics into LDS
-// accumulators (num_channel <= lds_channels) or straight to global memory.
+// generic layout (small elem_per_channel, e.g. channel-last): fq_bwd_generic
 __global__ __launch_bounds__(kBlock) void fq_linear_c_bwd_generic_kernel(
     const float* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ offset,
     const float* __restrict__ dy, float* __restrict__ gx, float* __restrict__ gs, uint32_t n,
     FastDiv elem_per_channel, FastDiv num_channel, int use_lds, int qmin, int qmax, float grad_factor,
     int rounding) {
-    extern __shared__ float acc_lds[];
-    const uint32_t C = num_channel.d;
-    if (use_lds) {
-        for (uint32_t c = threadIdx.x; c < C; c += kBlock) acc_lds[c] = 0.f;
-        __syncthreads();
-    }
-    const uint32_t stride = gridDim.x * kBlock;
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-        const uint32_t row = fdiv(i, elem_per_channel);
-        const uint32_t c = row - fdiv(row, num_channel) * C;
-        float g;
-        const float sc = scale[c], oc = __builtin_roundf(offset[c]);
-        const float p = lsq_bwd_elem<true, -1>(x[i], dy[i], sc, 1.0f / sc, oc, f2i_sat(oc), qmin, qmax, rounding, &g);
-        gx[i] = g;
-        if (use_lds) atomicAdd(&acc_lds[c], p);
-        else atomicAdd(&gs[c], p * grad_factor);
-    }
-    if (use_lds) {
-        __syncthreads();
-        for (uint32_t c = threadIdx.x; c < C; c += kBlock) {
-            const float v = acc_lds[c];
-            if (v != 0.f) atomicAdd(&gs[c], v * grad_factor);
-        }
-    }
+    fq_bwd_generic(x, dy, gx, gs, n, elem_per_channel, num_channel, use_lds,
+                   [&](uint32_t c, float v, float d, float* g) { return LsqChannel<-1>(scale[c], offset[c], qmin, qmax, rounding)(v, d, g); },
+                   [&](float sum) { return sum * grad_factor; });
 }
 
 // --------------------------------------------------------------------------- host dispatch
-static int validate_n(int64_t n, const char* what) {
-    if (n <= 0) { set_error("%s: tensor is empty", what); return PPQHIP_ERR_INVALID_VALUE; }
-    if (n > 0x7fffffffLL) {
-        set_error("%s: there are too many elements in your tensor (more than 2*10^9)", what);
-        return PPQHIP_ERR_INVALID_VALUE;
-    }
-    return PPQHIP_OK;
-}
-
-static int validate_channels(int64_t n, int64_t C, int64_t epc, const char* what) {
-    if (C <= 0 || epc <= 0 || n % (C * epc) != 0) {
-        set_error("%s: n=%lld is not [outer, %lld channels, %lld elem/channel]", what, (long long)n,
-                  (long long)C, (long long)epc);
-        return PPQHIP_ERR_INVALID_VALUE;
-    }
-    return PPQHIP_OK;
-}
-
-// Tensors of at least kStreamElems elements (192 MiB) cannot be resident in the 256 MiB Infinity
-// Cache together with their output: read them with streaming (nontemporal) loads.
-constexpr int64_t kStreamElems = 48ll << 20;
-// Tile shape: U 16-B accesses per lane and workgroup.  HBM-bound tensors stream best with U = 2 (half as many workgroups to
-// dispatch); a tensor of a few MB is ONE latency chain (dispatch -> loads -> arithmetic -> stores) in which the arithmetic of
-// the last-arriving wave is exposed, so U = 1 (twice the waves, half the work behind each load) is 0.2 us faster on
-// B = [1,512,56,56]: 4.28 -> 4.08 us per tensor, 4.44 -> 4.24 per channel (rocprofv3 medians, interleaved A/B,
-// profiles/r05_floor_table.txt); the copy floor of the same 12.8 MB is 3.88 us.
-constexpr int kTileU = 2;
-constexpr int kSmallU = 1;
-constexpr long long kFqSmallElems = 4ll << 20;      // up to 16 MB in + 16 MB out
-
 template <int R>
 static void launch_lt(const float* x, const float* scale, const float* offset, float* out, int64_t n,
                       int qmin, int qmax, int rounding, hipStream_t st) {
-    if (aligned16(x) && aligned16(out) && n >= 4) {
+    if (fq_vec_ok(x, out) && n >= 4) {
         const uint32_t nvec = (uint32_t)(n >> 2);
         const int ntail = (int)(n & 3);
         const float* xt = x + (size_t)nvec * 4;
         float* ot = out + (size_t)nvec * 4;
-#define PPQ_LAUNCH_LT(U, NT)                                                                                          \
-        hipLaunchKernelGGL((fq_linear_t_tile_kernel<R, U, NT>), dim3((nvec + kBlock * U - 1) / (kBlock * U)), dim3(kBlock), 0, st, \
-                           (const float4*)x, scale, offset, (float4*)out, nvec, xt, ot, ntail, qmin, qmax, rounding)
-        if (n >= kStreamElems) PPQ_LAUNCH_LT(kTileU, true);
-        else if (n <= kFqSmallElems) PPQ_LAUNCH_LT(kSmallU, false);
-        else PPQ_LAUNCH_LT(kTileU, false);
-#undef PPQ_LAUNCH_LT
+        with_tile_shape(n, [&](auto u, auto nt) {
+            hipLaunchKernelGGL((fq_linear_t_tile_kernel<R, decltype(u)::value, decltype(nt)::value>), tile_grid(nvec, u), dim3(kBlock), 0,
+                               st, (const float4*)x, scale, offset, (float4*)out, nvec, xt, ot, ntail, qmin, qmax, rounding);
+        });
     } else {
-        hipLaunchKernelGGL((fq_linear_t_scalar_kernel<R>), dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, st, x,
-                           scale, offset, out, (uint32_t)n, qmin, qmax, rounding);
+        hipLaunchKernelGGL((fq_linear_scalar_kernel<R>), dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, st, x, scale, offset, out,
+                           (uint32_t)n, make_fastdiv(1), make_fastdiv(1), 0, qmin, qmax, rounding);
     }
 }
 
 template <int R>
 static void launch_lc(const float* x, const float* scale, const float* offset, float* out, int64_t n,
                       int64_t C, int64_t epc, int qmin, int qmax, int rounding, hipStream_t st) {
-    if (aligned16(x) && aligned16(out) && (epc % 4 == 0)) {
+    const FastDiv nc = make_fastdiv((uint32_t)C);
+    if (fq_vec_ok(x, out, epc)) {
         const uint32_t nvec = (uint32_t)(n >> 2);
-        const FastDiv vpc = make_fastdiv((uint32_t)(epc / 4)), nc = make_fastdiv((uint32_t)C);
-#define PPQ_LAUNCH_LC(U, NT)                                                                                          \
-        hipLaunchKernelGGL((fq_linear_c_tile_kernel<R, U, NT>), dim3((nvec + kBlock * U - 1) / (kBlock * U)), dim3(kBlock), 0, st, \
-                           (const float4*)x, scale, offset, (float4*)out, nvec, vpc, nc, qmin, qmax, rounding)
-        if (n >= kStreamElems) PPQ_LAUNCH_LC(kTileU, true);
-        else if (n <= kFqSmallElems) PPQ_LAUNCH_LC(kSmallU, false);
-        else PPQ_LAUNCH_LC(kTileU, false);
-#undef PPQ_LAUNCH_LC
+        const FastDiv vpc = make_fastdiv((uint32_t)(epc / 4));
+        with_tile_shape(n, [&](auto u, auto nt) {
+            hipLaunchKernelGGL((fq_linear_c_tile_kernel<R, decltype(u)::value, decltype(nt)::value>), tile_grid(nvec, u), dim3(kBlock), 0,
+                               st, (const float4*)x, scale, offset, (float4*)out, nvec, vpc, nc, qmin, qmax, rounding);
+        });
     } else {
-        const FastDiv e = make_fastdiv((uint32_t)epc), nc = make_fastdiv((uint32_t)C);
-        hipLaunchKernelGGL((fq_linear_c_scalar_kernel<R>), dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, st, x,
-                           scale, offset, out, (uint32_t)n, e, nc, qmin, qmax, rounding);
+        hipLaunchKernelGGL((fq_linear_scalar_kernel<R>), dim3(stream_grid(n, kBlock)), dim3(kBlock), 0, st, x, scale, offset, out,
+                           (uint32_t)n, make_fastdiv((uint32_t)epc), nc, 1, qmin, qmax, rounding);
     }
 }
 
-// ---- many tensors, one launch --------------------------------------------------------------------
-// Every forward of a quantised graph fake-quantises all of its weights again (the reference executor
-// does so until ParameterBakingPass); ResNet-50 has 54 of them, 0.01 .. 9 MB each -- one launch per
-// weight is pure launch latency.  Here one launch serves them all: the job table lives in device
-// memory (it only changes when a weight / scale tensor is replaced), the kernel arguments carry the
-// prefix of workgroup counts so a workgroup finds its job without touching memory, and each
-// workgroup quantises one tile of kBlock * U float4 (or the same range element-wise when the tensor
-// cannot be vectorised: elem_per_channel % 4 != 0 or unaligned).  Per-tensor jobs are C = 1.
-constexpr int kFqMultiMax = 128;
-struct FqJob {
-    const float* x;
-    float* out;
-    const float* scale;
-    const float* offset;
-    uint32_t n;
-    uint32_t vec_ok;
-    FastDiv per;          // vec_ok: float4 per channel row; else elements per channel row
-    FastDiv nc;
-    int qmin, qmax;
-};
-struct FqMultiArgs {
-    uint32_t first_block[kFqMultiMax];
-    uint32_t count;
-    int rounding;
-    const FqJob* jobs;
-};
+// ---- many tensors, one launch (fq_walk.hpp) ----------------------------------------------------------
+struct LinearClip { int qmin, qmax; };
+typedef FqJobOf<LinearClip> FqJob;
+typedef FqMultiArgsOf<FqJob> FqMultiArgs;
+static_assert(sizeof(FqJob) == 72, "callers size the device table with ppqhip_fq_linear_multi_table_bytes");
 
 template <int R, int U>
 __global__ __launch_bounds__(kBlock) void fq_linear_multi_kernel(const FqMultiArgs args) {
-    uint32_t lo = 0, hi = args.count;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (args.first_block[mid] <= blockIdx.x) lo = mid; else hi = mid;
-    }
-    const FqJob j = args.jobs[lo];                      // uniform address: scalar loads
-    const uint32_t base = (blockIdx.x - args.first_block[lo]) * (kBlock * U) + threadIdx.x;
-    const uint32_t C = j.nc.d;
-    if (j.vec_ok) {
-        const uint32_t nvec = j.n >> 2;
-        const float4* xv = reinterpret_cast<const float4*>(j.x);
-        float4* ov = reinterpret_cast<float4*>(j.out);
-        float4 a[U];
-        float s[U];
-        int o[U];
-#pragma unroll
-        for (int k = 0; k < U; k++) {
-            const uint32_t vv = min(base + k * kBlock, nvec - 1);
-            a[k] = xv[vv];
-            const uint32_t row = fdiv(vv, j.per);
-            const uint32_t c = row - fdiv(row, j.nc) * C;
-            s[k] = j.scale[c];
-            o[k] = round_offset(j.offset[c]);
-        }
-#pragma unroll
-        for (int k = 0; k < U; k++) {
-            const uint32_t vv = base + k * kBlock;
-            const float4 r = fq_linear4<R>(a[k], s[k], fq_safe_rcp(s[k]), o[k], j.qmin, j.qmax, args.rounding);
-            if (vv < nvec) ov[vv] = r;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < U; k++) {
-            const uint32_t e0 = (base + k * kBlock) * 4;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const uint32_t e = e0 + q;
-                if (e < j.n) {
-                    const uint32_t row = fdiv(e, j.per);
-                    const uint32_t c = row - fdiv(row, j.nc) * C;
-                    j.out[e] = fq_linear_scalar<R>(j.x[e], j.scale[c], round_offset(j.offset[c]), j.qmin, j.qmax,
-                                                   args.rounding);
-                }
-            }
-        }
-    }
+    uint32_t local;
+    const FqJob j = args.jobs[job_of(args, local)];     // uniform address: scalar loads
+    fq_multi_tile<U, FQ_STORE_ONLY>(LinearQ<R>{j.fmt.qmin, j.fmt.qmax, args.rounding}, j.x, j.out, j.scale, j.offset, j.n, j.vec_ok, j.per, j.nc, local);
 }
 
 // ---- LSQ backward of many per-channel tensors, one launch ------------------------------------------
@@ -630,53 +404,14 @@ struct LsqMultiArgs {
 template <int R>
 __global__ __launch_bounds__(kBlock) void fq_linear_c_bwd_multi_kernel(const LsqMultiArgs args) {
     __shared__ float lds[kBlock / kWave];
-    uint32_t lo = 0, hi = args.count;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (args.first_block[mid] <= blockIdx.x) lo = mid; else hi = mid;
-    }
-    const LsqJob& j = args.jobs[lo];                    // kernel-argument segment: scalar loads
-    const uint32_t c = blockIdx.x - args.first_block[lo];
-    const float s = j.scale[c];
-    const float rcp_s = 1.0f / s;
-    const float o = __builtin_roundf(j.offset[c]);
-    const int oi = f2i_sat(o);
+    uint32_t c;                                         // the workgroup's index inside its job: the channel
+    const LsqJob& j = args.jobs[job_of(args, c)];       // kernel-argument segment: scalar loads
+    const LsqChannel<R> elem(j.scale[c], j.offset[c], j.qmin, j.qmax, args.rounding);
     const uint32_t epc = j.epc, C = j.C;
-    const int qmin = j.qmin, qmax = j.qmax, rounding = args.rounding;
     float acc = 0.f;
     for (uint32_t n = 0; n < j.outer; n++) {
         const size_t base = ((size_t)n * C + c) * epc;
-        if (j.vec_ok) {   // epc % 4 == 0, 16-B aligned bases
-            const float4* xv = reinterpret_cast<const float4*>(j.x + base);
-            const float4* dv = reinterpret_cast<const float4*>(j.dy + base);
-            float4* gv = reinterpret_cast<float4*>(j.gx + base);
-            constexpr int U = kLsqCU;
-            const uint32_t v1 = epc >> 2;
-            for (uint32_t v = threadIdx.x; v < v1; v += kBlock * U) {
-                float4 a[U], d[U];
-#pragma unroll
-                for (int u = 0; u < U; u++) {
-                    const uint32_t at = min(v + u * kBlock, v1 - 1);
-                    a[u] = xv[at]; d[u] = dv[at];
-                }
-#pragma unroll
-                for (int u = 0; u < U; u++) {
-                    if (v + u * kBlock >= v1) break;
-                    float4 g;
-                    acc += lsq_bwd_elem<true, R>(a[u].x, d[u].x, s, rcp_s, o, oi, qmin, qmax, rounding, &g.x);
-                    acc += lsq_bwd_elem<true, R>(a[u].y, d[u].y, s, rcp_s, o, oi, qmin, qmax, rounding, &g.y);
-                    acc += lsq_bwd_elem<true, R>(a[u].z, d[u].z, s, rcp_s, o, oi, qmin, qmax, rounding, &g.z);
-                    acc += lsq_bwd_elem<true, R>(a[u].w, d[u].w, s, rcp_s, o, oi, qmin, qmax, rounding, &g.w);
-                    gv[v + u * kBlock] = g;
-                }
-            }
-        } else {
-            for (uint32_t e = threadIdx.x; e < epc; e += kBlock) {
-                float g;
-                acc += lsq_bwd_elem<true, R>(j.x[base + e], j.dy[base + e], s, rcp_s, o, oi, qmin, qmax, rounding, &g);
-                j.gx[base + e] = g;
-            }
-        }
+        acc = fq_bwd_row<kLsqCU, false>(j.x + base, j.dy + base, j.gx + base, 0, epc, j.vec_ok != 0, acc, elem);
     }
     const float tot = block_sum(acc, lds);
     if (threadIdx.x == 0) j.gs[c] = tot * j.grad_factor;
@@ -718,56 +453,16 @@ int64_t ppqhip_fq_linear_multi_table_bytes(int num_jobs) {
 
 int ppqhip_fq_linear_multi(const ppqhip_fq_job* jobs, int num_jobs, int rounding, void* device_table, int upload,
                            void* stream) {
-    if (num_jobs <= 0) return PPQHIP_OK;
-    if (jobs == nullptr || device_table == nullptr) {
-        set_error("fq_linear_multi: jobs / device_table is null"); return PPQHIP_ERR_INVALID_VALUE;
-    }
     hipStream_t s = (hipStream_t)stream;
-    double bytes = 0.0;
-    for (int k = 0; k < num_jobs; k++) {
-        if (int st = validate_n(jobs[k].n, "fq_linear_multi")) return st;
-        if (int st = validate_channels(jobs[k].n, jobs[k].num_channel, jobs[k].elem_per_channel, "fq_linear_multi")) return st;
-        if (!jobs[k].x || !jobs[k].out || !jobs[k].scale || !jobs[k].offset) {
-            set_error("fq_linear_multi: job %d has a null pointer", k); return PPQHIP_ERR_INVALID_VALUE;
-        }
-        bytes += 8.0 * (double)jobs[k].n;
-    }
-    LaunchScope scope(K_FQ_LINEAR_C, bytes, s);
-    constexpr int U = 2;
-    for (int base = 0; base < num_jobs; base += kFqMultiMax) {
-        const int count = (num_jobs - base) < kFqMultiMax ? (num_jobs - base) : kFqMultiMax;
-        FqMultiArgs args;
-        args.count = (uint32_t)count; args.rounding = rounding;
-        args.jobs = (const FqJob*)device_table + base;
-        std::vector<FqJob> table(upload ? count : 0);
-        uint32_t blocks = 0;
-        for (int k = 0; k < count; k++) {
-            const ppqhip_fq_job& src = jobs[base + k];
-            const bool vec = aligned16(src.x) && aligned16(src.out) && (src.elem_per_channel % 4 == 0);
-            args.first_block[k] = blocks;
-            const uint64_t quads = ((uint64_t)src.n + 3) / 4;
-            blocks += (uint32_t)((quads + kBlock * U - 1) / (kBlock * U));
-            if (upload) {
-                FqJob& d = table[k];
-                d.x = src.x; d.out = src.out; d.scale = src.scale; d.offset = src.offset;
-                d.n = (uint32_t)src.n; d.vec_ok = vec ? 1u : 0u;
-                d.per = make_fastdiv((uint32_t)(vec ? src.elem_per_channel / 4 : src.elem_per_channel));
-                d.nc = make_fastdiv((uint32_t)src.num_channel);
-                d.qmin = src.clip_min; d.qmax = src.clip_max;
-            }
-        }
-        if (upload) {
-            // pageable source: the runtime stages the copy before returning, `table` may go out of scope
-            if (int st = check_hip(hipMemcpyAsync((FqJob*)device_table + base, table.data(), sizeof(FqJob) * count,
-                                                  hipMemcpyHostToDevice, s), "fq_linear_multi table upload"))
-                return st;
-        }
-        if (rounding == ROUND_HALF_EVEN)
-            hipLaunchKernelGGL((fq_linear_multi_kernel<ROUND_HALF_EVEN, U>), dim3(blocks), dim3(kBlock), 0, s, args);
-        else
-            hipLaunchKernelGGL((fq_linear_multi_kernel<-1, U>), dim3(blocks), dim3(kBlock), 0, s, args);
-    }
-    return finish_launch("fq_linear_multi");
+    return fq_multi<LinearClip>(
+        "fq_linear_multi", K_FQ_LINEAR_C, jobs, num_jobs, rounding, device_table, upload, s,
+        [](const ppqhip_fq_job& src, LinearClip* f) { f->qmin = src.clip_min; f->qmax = src.clip_max; return PPQHIP_OK; },
+        [&](uint32_t blocks, const FqMultiArgs& args) {
+            if (rounding == ROUND_HALF_EVEN)
+                hipLaunchKernelGGL((fq_linear_multi_kernel<ROUND_HALF_EVEN, kFqMultiU>), dim3(blocks), dim3(kBlock), 0, s, args);
+            else
+                hipLaunchKernelGGL((fq_linear_multi_kernel<-1, kFqMultiU>), dim3(blocks), dim3(kBlock), 0, s, args);
+        });
 }
 
 static int to_int_impl(const float* x, const float* scale, const float* offset, void* out, int64_t n, int64_t C, int64_t epc,
@@ -837,7 +532,7 @@ static int lsq_t_grid(int64_t n) { return stream_grid(n, kBlock * 4 * lsq_t_u(n)
 
 static void launch_lsq_t_main(const float* x, const float* scale, const float* offset, const float* grad_y, float* grad_x,
                               float* partial, int64_t n, int grid, int clip_min, int clip_max, int rounding, hipStream_t s) {
-    const int vec_ok = (aligned16(x) && aligned16(grad_y) && aligned16(grad_x)) ? 1 : 0;
+    const int vec_ok = fq_bwd_vec_ok(x, grad_y, grad_x) ? 1 : 0;
     const bool nt = n >= kStreamElems / 2;       // x and dy together exceed cache residency: streaming loads
 #define PPQ_LAUNCH_LSQ_T(R, NT, U)                                                                                  \
     hipLaunchKernelGGL((fq_linear_t_bwd_kernel<R, NT, U>), dim3(grid), dim3(kBlock), 0, s, x, scale, offset, grad_y, \
@@ -925,7 +620,7 @@ int ppqhip_fq_linear_c_bwd(const float* x, const float* scale, const float* offs
         const uint32_t chunk_elems = 4096;
         const uint32_t chunks = (uint32_t)((elem_per_channel + chunk_elems - 1) / chunk_elems);
         const int64_t rows = n / elem_per_channel;
-        const int vec_ok = (elem_per_channel % 4 == 0 && aligned16(x) && aligned16(grad_y) && aligned16(grad_x)) ? 1 : 0;
+        const int vec_ok = fq_bwd_vec_ok(x, grad_y, grad_x, elem_per_channel) ? 1 : 0;
         const bool nt = n >= kStreamElems / 2;      // x and dy together exceed cache residency: streaming loads (as lsq_bwd_t)
 #define PPQ_LAUNCH_LSQ_C(R, NT)                                                                                        \
         hipLaunchKernelGGL((fq_linear_c_bwd_row_kernel<R, NT>), dim3((uint32_t)(rows * chunks)), dim3(kBlock), 0, s, x,   \
@@ -971,7 +666,7 @@ int ppqhip_fq_linear_c_bwd_multi(const ppqhip_lsq_job* jobs, int num_jobs, int r
             d.x = src.x; d.dy = src.grad_y; d.gx = src.grad_x; d.gs = src.grad_s; d.scale = src.scale; d.offset = src.offset;
             d.C = (uint32_t)src.num_channel; d.epc = (uint32_t)src.elem_per_channel;
             d.outer = (uint32_t)(src.n / (src.num_channel * src.elem_per_channel));
-            d.vec_ok = (src.elem_per_channel % 4 == 0 && aligned16(src.x) && aligned16(src.grad_y) && aligned16(src.grad_x)) ? 1u : 0u;
+            d.vec_ok = fq_bwd_vec_ok(src.x, src.grad_y, src.grad_x, src.elem_per_channel) ? 1u : 0u;
             d.qmin = src.clip_min; d.qmax = src.clip_max;
             d.grad_factor = (float)(1.0 / sqrt((double)src.n * (double)src.clip_max));      // rsqrtf(((double)n * clip_max)): linear.cu:402
             d.pad = 0;

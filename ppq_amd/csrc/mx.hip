@@ -103,8 +103,8 @@ uint32_t device_job(const ppqhip_mx_job& src, int U, MxJob* d, int* ruled) {
     return fill_mx_walk(&d->walk, mx_geometry_of(src), src.format, aligned16(src.x) && aligned16(src.y), U, ruled);
 }
 
-constexpr int64_t kMxStreamElems = 48ll << 20;    // >= 192 MiB: streaming loads (see linear.hip)
-constexpr int64_t kMxSmallElems = 4ll << 20;      // latency-bound tensors: one float4 per lane (see linear.hip)
+constexpr int64_t kMxStreamElems = 48ll << 20;    // >= 192 MiB: streaming loads (see fq_walk.hpp)
+constexpr int64_t kMxSmallElems = 4ll << 20;      // latency-bound tensors: one float4 per lane (see fq_walk.hpp)
 
 double job_bytes(const ppqhip_mx_job& j) {
     const MxGeometry g = mx_geometry_of(j);
