@@ -29,6 +29,7 @@
 //     device atomics when only a handful of workgroups run (small tensors: one launch).
 #include "common.hpp"
 #include "hist_bin.hpp"
+#include "stream_walk.hpp"
 
 namespace ppqhip {
 
@@ -45,7 +46,6 @@ constexpr int kHistAtomicMaxWg = 128;  // one-shot entry points: flush with devi
 constexpr long long kHistNtElems = 48ll << 20;   // streaming (nontemporal) loads beyond cache residency
 constexpr int kHistRows = kNumCU * kHistWgPerCu;       // grid limit == rows of a persistent accumulator
 constexpr uint32_t kTileVec = (uint32_t)kHistBlock * kHistU;   // float4 per tile
-constexpr uint32_t kTileElems = kTileVec * 4;
 static_assert(kHistBlock % 64 == 0 && kHistBlock >= 64 && kHistBlock <= 1024, "histogram workgroup: whole waves");
 
 struct BinRule {
@@ -114,12 +114,6 @@ struct HistJobs {
     uint32_t total_tiles;
     int bins, copies, mode;
 };
-__host__ __device__ inline uint32_t job_tiles(uint32_t n, bool vec_ok) {
-    if (!vec_ok) return (n + kTileElems - 1) / kTileElems;          // every tile through the scalar path
-    const uint32_t full = (n >> 2) / kTileVec;
-    return full + (n > full * kTileElems ? 1u : 0u);                 // + one ragged tail tile
-}
-
 // merge this workgroup's LDS copies into its destination and leave the copies zeroed
 __device__ __forceinline__ void lds_hist_flush(int* lds, int bins, int copies, int* __restrict__ dst, int mode) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // the inline-assembly ds_adds are invisible to the compiler's counters
@@ -136,100 +130,66 @@ __device__ __forceinline__ void lds_hist_flush(int* lds, int bins, int copies, i
     __syncthreads();
 }
 
+// The LDS copies of a workgroup are zeroed BEHIND its first loads (the walks' `ready`): their latency covers the stores and the
+// barrier.  The barrier is the bare s_barrier behind an LDS-only wait: __syncthreads() would also drain vmcnt, i.e. wait for the
+// loads just issued.
+__device__ __forceinline__ void lds_hist_zero(int* lds, int words) {
+    for (int i = threadIdx.x; i < words; i += kHistBlock) lds[i] = 0;
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+// a float4 of a full tile / row through the EXEC-mask commits; `elect`: this float4 also proposes the wave's hot bin
+template <bool EXEC, typename B>
+__device__ __forceinline__ void bin_float4(B& acc, const float4& v, bool elect) {
+    int b[4];
+    acc.bins4(v, b);
+    if (elect) acc.elect(b[0], true);
+    if (EXEC) acc.commit4_exec(b);
+    else {
+        acc.template commit<true>(b[0], true); acc.template commit<true>(b[1], true);
+        acc.template commit<true>(b[2], true); acc.template commit<true>(b[3], true);
+    }
+}
+// an element of a masked path; `elect` as above
+template <typename B>
+__device__ __forceinline__ void bin_masked(B& acc, float v, bool in, bool elect) {
+    const int b = acc.bin1(v);
+    if (elect) acc.elect(b, in);
+    acc.template commit<false>(b, in);
+}
+
 template <bool ASYM, bool CLIP, bool HOT, bool NT>
 __global__ __launch_bounds__(kHistBlock, (kHistBlock * kHistWgPerCu + 255) / 256)
 void hist_persistent_kernel(const HistJobs jobs) {
     extern __shared__ int lds[];
-    const uint32_t G = gridDim.x, g = blockIdx.x;
-    uint32_t t, t_end;
-    even_split(jobs.total_tiles, G, g, t, t_end);
+    const uint32_t g = blockIdx.x;
     const int bins = jobs.bins, copies = jobs.copies;
-    // The LDS copies are zeroed AFTER the first tile's loads have been issued (their latency covers the stores and the
-    // barrier; on a 6 MB tensor the kernel is a single latency chain, nothing else hides them).  The barrier is the bare
-    // s_barrier behind an LDS-only wait: __syncthreads() would also drain vmcnt, i.e. wait for the loads just issued.
-    bool zeroed = false;
-    auto zero_lds = [&]() {
-        if (zeroed) return;
-        for (int i = threadIdx.x; i < copies * bins; i += kHistBlock) lds[i] = 0;
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        zeroed = true;
-    };
-    if (t >= t_end) {                       // more workgroups than tiles: nothing to bin
+    if (g >= jobs.total_tiles) {            // more workgroups than tiles: nothing to bin (an empty share of the walk)
         if (jobs.mode == FLUSH_ROWS_STORE) for (int b = threadIdx.x; b < bins; b += kHistBlock) jobs.job[0].rows[(size_t)g * bins + b] = 0;
         return;
     }
-    uint32_t lo = 0, hi = jobs.count;       // largest lo with first_tile[lo] <= t (wave uniform)
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (jobs.job[mid].first_tile <= t) lo = mid; else hi = mid;
-    }
     Binner<ASYM, CLIP, HOT> acc;
     acc.init(lds + ((threadIdx.x >> 6) % copies) * bins, bins);
-
-    for (uint32_t j = lo; t < t_end; j++) {
-        const HistJob& job = jobs.job[j];
-        const uint32_t j_end = (j + 1 < jobs.count) ? jobs.job[j + 1].first_tile : jobs.total_tiles;
-        uint32_t k = t - job.first_tile;                                   // tiles [k, k1) of this job
-        const uint32_t k1 = min(t_end, j_end) - job.first_tile;
-        t = min(t_end, j_end);
-        acc.set_rule(job.a, job.hs);
-        const float* __restrict__ x = job.x;
-        const uint32_t n = job.n;
-        const bool vec_ok = (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
-        const uint32_t full = vec_ok ? (n >> 2) / kTileVec : 0u;
-        const uint32_t kf = min(k1, full);                                 // full tiles [k, kf)
-        if (k < kf) {
-            const float4* xv = reinterpret_cast<const float4*>(x) + threadIdx.x;
-            float4 bufa[kHistU], bufb[kHistU];
-            auto fetch = [&](float4 (&buf)[kHistU], uint32_t tile) {
-                const float4* p = xv + (size_t)tile * kTileVec;
+    bool zeroed = false;                    // (a flush leaves the copies zeroed for the next job)
+    tile_walk<kHistBlock, kHistU, PlainLoads<NT>>(
+        ArgTiles<HistJobs>{jobs},
+        [&](uint32_t j, uint32_t) {
+            const HistJob& job = jobs.job[j];
+            acc.set_rule(job.a, job.hs);
+            return StreamJob{job.x, job.n};
+        },
+        [&] { if (!zeroed) lds_hist_zero(lds, copies * bins); zeroed = true; return true; },
+        [&](const float4 (&buf)[kHistU], uint32_t) {
 #pragma unroll
-                for (int u = 0; u < kHistU; u++) buf[u] = load4<NT>(p + u * kHistBlock);
-            };
-            auto consume = [&](const float4 (&buf)[kHistU], uint32_t tile) {
-#pragma unroll
-                for (int u = 0; u < kHistU; u++) {
-                    int b[4];
-                    acc.bins4(buf[u], b);
-                    if (u == 0) acc.elect(b[0], true);
-                    if (CLIP && HOT) acc.commit4_exec(b);
-                    else {
-                        acc.template commit<true>(b[0], true); acc.template commit<true>(b[1], true);
-                        acc.template commit<true>(b[2], true); acc.template commit<true>(b[3], true);
-                    }
-                }
-            };
-            // ping-pong between two register tiles; the prefetch index is clamped (wave uniform), so the
-            // loads stay unconditional straight-line code: the last tile of the range is fetched twice.
-            fetch(bufa, k);
-            zero_lds();
-            for (;;) {
-                fetch(bufb, min(k + 1, kf - 1));
-                consume(bufa, k);
-                if (++k >= kf) break;
-                fetch(bufa, min(k + 1, kf - 1));
-                consume(bufb, k);
-                if (++k >= kf) break;
-            }
-        }
-        zero_lds();
-        for (; k < k1; k++) {             // ragged tail tile (or a tensor that is not 16-B aligned): masked 4-B loads
-            const uint32_t e0 = k * kTileElems + threadIdx.x;
-#pragma unroll 4
-            for (int r = 0; r < 4 * kHistU; r++) {
-                const uint32_t i = e0 + r * kHistBlock;
-                const bool in = i < n;
-                const float a = in ? x[i] : 0.f;
-                const int b = acc.bin1(a);
-                if ((r & 3) == 0) acc.elect(b, in);
-                acc.template commit<false>(b, in);
-            }
-        }
-        acc.flush_hot();
-        acc.hot_bin = -1;
-        int* dst = jobs.mode == FLUSH_ATOMIC ? job.rows : job.rows + (size_t)g * bins;
-        lds_hist_flush(lds, bins, copies, dst, jobs.mode);
-    }
+            for (int u = 0; u < kHistU; u++) bin_float4<CLIP && HOT>(acc, buf[u], u == 0);
+        },
+        [&](float a, bool in, int r) { bin_masked(acc, a, in, (r & 3) == 0); },
+        [&](uint32_t j) {
+            acc.flush_hot();
+            acc.hot_bin = -1;
+            int* dst = jobs.mode == FLUSH_ATOMIC ? jobs.job[j].rows : jobs.job[j].rows + (size_t)g * bins;
+            lds_hist_flush(lds, bins, copies, dst, jobs.mode);
+        });
 }
 
 // ---- the single-tensor kernel for LATENCY-BOUND sizes (one launch on a few MB: B = [1,512,56,56] is 6.4 MB) ------------------
@@ -250,81 +210,18 @@ template <bool ASYM, bool CLIP, int kSmallK, bool PING = false, bool NT = false>
 __global__ __launch_bounds__(kHistBlock) void hist_small_kernel(const float* __restrict__ x, uint32_t n, float a, float hs, int bins,
                                                                  int copies, int* __restrict__ dst, uint32_t row_mod) {
     extern __shared__ int lds[];
-    const uint32_t G = gridDim.x, g = blockIdx.x;
-    const uint32_t nvec = n >> 2;
-    const uint32_t full_rows = nvec / kHistBlock;                     // rows of kHistBlock float4 in which every lane has one
-    uint32_t r0, r1;
-    even_split(full_rows, G, g, r0, r1);
-    const float4* xv = reinterpret_cast<const float4*>(x) + threadIdx.x;
+    const uint32_t g = blockIdx.x;
     Binner<ASYM, CLIP, true> acc;
     acc.init(lds + ((threadIdx.x >> 6) % copies) * bins, bins);
     acc.set_rule(a, hs);
-    bool zeroed = false;
-    auto zero_lds = [&]() {
-        if (zeroed) return;
-        for (int i = threadIdx.x; i < copies * bins; i += kHistBlock) lds[i] = 0;
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // LDS only: the loads stay in flight
-        zeroed = true;
-    };
-    // straight-line loads with a clamped row index (the last row of the share is fetched again instead of branching): a
-    // load under `if (k < cnt)` lands in its own basic block and the compiler waits for ALL earlier loads in front of it
-    auto fetch = [&](float4 (&buf)[kSmallK], uint32_t r) {
+    row_walk<kHistBlock, kSmallK, PING, PlainLoads<NT>>(
+        x, n, [&] { lds_hist_zero(lds, copies * bins); return true; },
+        [&](const float4 (&buf)[kSmallK], uint32_t cnt) {
 #pragma unroll
-        for (int k = 0; k < kSmallK; k++) buf[k] = load4<NT>(xv + (size_t)min(r + (uint32_t)k, r1 - 1) * kHistBlock);
-    };
-    auto consume = [&](const float4 (&buf)[kSmallK], uint32_t cnt) {      // cnt: workgroup uniform
-#pragma unroll
-        for (int k = 0; k < kSmallK; k++) {
-            if ((uint32_t)k < cnt) {
-                int b[4];
-                acc.bins4(buf[k], b);
-                if ((k & 1) == 0) acc.elect(b[0], true);
-                if (CLIP) acc.commit4_exec(b);
-                else {
-                    acc.template commit<true>(b[0], true); acc.template commit<true>(b[1], true);
-                    acc.template commit<true>(b[2], true); acc.template commit<true>(b[3], true);
-                }
-            }
-        }
-    };
-    if (PING) {
-        if (r0 < r1) {
-            float4 bufa[kSmallK], bufb[kSmallK];
-            uint32_t r = r0;
-            fetch(bufa, r);
-            zero_lds();
-            for (;;) {
-                fetch(bufb, r + kSmallK);
-                consume(bufa, min((uint32_t)kSmallK, r1 - r));
-                r += kSmallK;
-                if (r >= r1) break;
-                fetch(bufa, r + kSmallK);
-                consume(bufb, min((uint32_t)kSmallK, r1 - r));
-                r += kSmallK;
-                if (r >= r1) break;
-            }
-        }
-    } else {
-        for (uint32_t r = r0; r < r1; r += kSmallK) {
-            float4 buf[kSmallK];
-            fetch(buf, r);
-            zero_lds();
-            consume(buf, min((uint32_t)kSmallK, r1 - r));
-        }
-    }
-    zero_lds();
-    if (g == G - 1) {                                                  // the ragged rest: < kHistBlock float4 + n % 4 elements, masked 4-B loads
-        const uint32_t e0 = full_rows * kHistBlock * 4;
-        const uint32_t trips = (n - e0 + kHistBlock - 1) / kHistBlock;
-        for (uint32_t t = 0; t < trips; t++) {
-            const uint32_t i = e0 + t * kHistBlock + threadIdx.x;
-            const bool in = i < n;
-            const float v = in ? x[i] : 0.f;
-            const int b = acc.bin1(v);
-            if ((t & 3) == 0) acc.elect(b, in);
-            acc.template commit<false>(b, in);
-        }
-    }
+            for (int k = 0; k < kSmallK; k++)
+                if ((uint32_t)k < cnt) bin_float4<CLIP>(acc, buf[k], (k & 1) == 0);
+        },
+        [&](float v, bool in, uint32_t t) { bin_masked(acc, v, in, (t & 3) == 0); });
     acc.flush_hot();
     int* row = dst + (size_t)(row_mod ? g % row_mod : 0u) * bins;     // row_mod: 0 one shared histogram, G own rows, R partial rows
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -397,13 +294,8 @@ void hist_c_channel_kernel(const float* __restrict__ x, FastDiv vec_per_row, uin
                            const float* __restrict__ mins, const float* __restrict__ maxs, int flush_mode) {
     extern __shared__ int lds[];
     const int bins = rule.bins;
-    bool zeroed = false;                  // zeroed behind the first tile's loads (see hist_persistent_kernel)
-    auto zero_lds = [&]() {
-        if (zeroed) return;
-        for (int i = threadIdx.x; i < copies * bins; i += kHistBlock) lds[i] = 0;
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        zeroed = true;
-    };
+    bool zeroed = false;                  // behind the first loads, whichever they are: a tile's or the rest's
+    auto zero_lds = [&]() { if (!zeroed) lds_hist_zero(lds, copies * bins); zeroed = true; };
     const uint32_t c = blockIdx.x % C, sp = blockIdx.x / C;
     const uint32_t vpr = vec_per_row.d;
     // the channel's rows as ONE virtual float4 range [0, outer * vpr); split `sp` owns [v0, v0 + V) of it
@@ -428,30 +320,13 @@ void hist_c_channel_kernel(const float* __restrict__ x, FastDiv vec_per_row, uin
 #pragma unroll
             for (int u = 0; u < kHistU; u++) buf[u] = load4<NT>(at(tile * kTileVec + u * kHistBlock + threadIdx.x));
         };
-        auto consume = [&](const float4 (&buf)[kHistU]) {
+        auto consume = [&](const float4 (&buf)[kHistU], uint32_t) {
 #pragma unroll
-            for (int u = 0; u < kHistU; u++) {
-                int b[4];
-                acc.bins4(buf[u], b);
-                if (u == 0) acc.elect(b[0], true);
-                if (CLIP) acc.commit4_exec(b);
-                else {
-                    acc.template commit<true>(b[0], true); acc.template commit<true>(b[1], true);
-                    acc.template commit<true>(b[2], true); acc.template commit<true>(b[3], true);
-                }
-            }
+            for (int u = 0; u < kHistU; u++) bin_float4<CLIP>(acc, buf[u], u == 0);
         };
-        uint32_t k = 0;
-        fetch(bufa, k);
+        fetch(bufa, 0);
         zero_lds();
-        for (;;) {
-            fetch(bufb, min(k + 1, tiles - 1));
-            consume(bufa);
-            if (++k >= tiles) break;
-            fetch(bufa, min(k + 1, tiles - 1));
-            consume(bufb);
-            if (++k >= tiles) break;
-        }
+        ping_pong<1>(bufa, bufb, 0, tiles, fetch, consume);
     }
     {   // the ragged rest (< one tile; ALL of a [1, C, 56, 56] channel: 784 float4 against a tile of 1024): every load issued
         // up front at a clamped index, then whole waves through the EXEC-mask commits and only the straddling wave masked
@@ -563,20 +438,10 @@ static void launch_reduce(const int* partial, int grid, int bins, int32_t* hist,
 
 static void launch_persistent(const HistJobs& args, int grid, int asym, int clip, bool nt, hipStream_t s) {
     const size_t lds = lds_bytes(args.bins, args.copies);
-#define PPQ_LAUNCH_HIST(A, C)                                                                                         \
-    do {                                                                                                              \
-        if (nt) hipLaunchKernelGGL((hist_persistent_kernel<A, C, true, true>), dim3(grid), dim3(kHistBlock), lds, s, \
-                                   args);                                                                             \
-        else hipLaunchKernelGGL((hist_persistent_kernel<A, C, true, false>), dim3(grid), dim3(kHistBlock), lds, s,   \
-                                args);                                                                                \
-    } while (0)
-    switch ((asym ? 2 : 0) | (clip ? 1 : 0)) {
-        case 0: PPQ_LAUNCH_HIST(false, false); break;
-        case 1: PPQ_LAUNCH_HIST(false, true); break;
-        case 2: PPQ_LAUNCH_HIST(true, false); break;
-        default: PPQ_LAUNCH_HIST(true, true); break;
-    }
-#undef PPQ_LAUNCH_HIST
+    with_flags([&](auto a, auto c, auto n) {
+        hipLaunchKernelGGL((hist_persistent_kernel<decltype(a)::value, decltype(c)::value, true, decltype(n)::value>), dim3(grid),
+                           dim3(kHistBlock), lds, s, args);
+    }, asym != 0, clip != 0, nt);
 }
 
 // grid for `tiles` tiles: every workgroup gets at least kHistMinTiles of them (twice that once the grid would
@@ -628,28 +493,15 @@ static bool launch_hist_stream(const float* x, int64_t n, BinRule rule, hipStrea
     }
     if (n > kHistStreamElems || !aligned16(x)) return false;
     const uint32_t full_rows = (uint32_t)((n >> 2) / kHistBlock);
-    uint32_t g = full_rows / (2u * (uint32_t)kHistStreamK);               // at least two tiles per workgroup
-    const uint32_t cap = (uint32_t)(num_cu() * kHistWgPerCu);
-    if (g > cap) g = cap;
+    uint32_t g = clamp_grid(full_rows / (2u * (uint32_t)kHistStreamK), (uint32_t)(num_cu() * kHistWgPerCu));   // at least two tiles per workgroup
     if (g > (uint32_t)kHistRows) g = kHistRows;
-    if (g < 1) g = 1;
     const int copies = pick_copies(rule.bins, kHistBlock);
     const bool nt = n >= kHistNtElems;
     const uint32_t row_mod = R ? (uint32_t)R : (uint32_t)kHistRows;
-#define PPQ_LAUNCH_HIST_STREAM(A, C)                                                                                  \
-    do {                                                                                                              \
-        if (nt) hipLaunchKernelGGL((hist_small_kernel<A, C, kHistStreamK, true, true>), dim3(g), dim3(kHistBlock),     \
-                                   lds_bytes(rule.bins, copies), s, x, (uint32_t)n, rule.a, rule.hs, rule.bins, copies, rows, row_mod); \
-        else hipLaunchKernelGGL((hist_small_kernel<A, C, kHistStreamK, true, false>), dim3(g), dim3(kHistBlock),       \
-                                lds_bytes(rule.bins, copies), s, x, (uint32_t)n, rule.a, rule.hs, rule.bins, copies, rows, row_mod); \
-    } while (0)
-    switch ((rule.asym ? 2 : 0) | (rule.clip ? 1 : 0)) {
-        case 0: PPQ_LAUNCH_HIST_STREAM(false, false); break;
-        case 1: PPQ_LAUNCH_HIST_STREAM(false, true); break;
-        case 2: PPQ_LAUNCH_HIST_STREAM(true, false); break;
-        default: PPQ_LAUNCH_HIST_STREAM(true, true); break;
-    }
-#undef PPQ_LAUNCH_HIST_STREAM
+    with_flags([&](auto a, auto c, auto t) {
+        hipLaunchKernelGGL((hist_small_kernel<decltype(a)::value, decltype(c)::value, kHistStreamK, true, decltype(t)::value>), dim3(g),
+                           dim3(kHistBlock), lds_bytes(rule.bins, copies), s, x, (uint32_t)n, rule.a, rule.hs, rule.bins, copies, rows, row_mod);
+    }, rule.asym != 0, rule.clip != 0, nt);
     if (R > 0) hipLaunchKernelGGL(hist_partial_reduce_kernel, dim3((rule.bins + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (int*)rows, R, rule.bins, (int*)hist);
     return true;
 }
@@ -657,34 +509,19 @@ static bool launch_hist_stream(const float* x, int64_t n, BinRule rule, hipStrea
 static bool launch_hist_small(const float* x, int64_t n, BinRule rule, int32_t* hist, hipStream_t s, int32_t* rows) {
     if (n > kHistSmallElems || !aligned16(x)) return false;
     const uint32_t full_rows = (uint32_t)((n >> 2) / kHistBlock);
-    uint32_t g;
-    if (rows) g = (full_rows + 1) / 2;                                   // own rows: no contention, two loads per lane
-    else g = full_rows / 4;                                              // shared histogram: every workgroup touches every line
-    const uint32_t cap = rows ? (uint32_t)(num_cu() * kHistWgPerCu) : (uint32_t)kHistSmallWgAtomic;
-    if (g > cap) g = cap;
-    if (g > (uint32_t)kHistRows) g = kHistRows;
-    if (g < 1) g = 1;
+    // own rows: no contention, two loads per lane; a shared histogram: every workgroup touches every line
+    const uint32_t want = rows ? (full_rows + 1) / 2 : full_rows / 4;
+    uint32_t cap = rows ? (uint32_t)(num_cu() * kHistWgPerCu) : (uint32_t)kHistSmallWgAtomic;
+    if (cap > (uint32_t)kHistRows) cap = kHistRows;
     const int copies = pick_copies(rule.bins, kHistBlock);
     int* dst = rows ? rows : hist;
     const uint32_t own = rows ? (uint32_t)kHistRows : 0u;             // (g < kHistRows: g % kHistRows == g)
-    const uint32_t share = (full_rows + g - 1) / g;                         // rows of the largest share: all of them in flight when <= 8
-#define PPQ_LAUNCH_HIST_SMALL_K(A, C, K)                                                                              \
-    hipLaunchKernelGGL((hist_small_kernel<A, C, K>), dim3(g), dim3(kHistBlock), lds_bytes(rule.bins, copies), s, x,  \
-                       (uint32_t)n, rule.a, rule.hs, rule.bins, copies, dst, own)
-#define PPQ_LAUNCH_HIST_SMALL(A, C)                                                                                   \
-    do {                                                                                                              \
-        if (share <= 2) PPQ_LAUNCH_HIST_SMALL_K(A, C, 2);                                                             \
-        else if (share <= 4) PPQ_LAUNCH_HIST_SMALL_K(A, C, 4);                                                        \
-        else PPQ_LAUNCH_HIST_SMALL_K(A, C, 8);                                                                        \
-    } while (0)
-    switch ((rule.asym ? 2 : 0) | (rule.clip ? 1 : 0)) {
-        case 0: PPQ_LAUNCH_HIST_SMALL(false, false); break;
-        case 1: PPQ_LAUNCH_HIST_SMALL(false, true); break;
-        case 2: PPQ_LAUNCH_HIST_SMALL(true, false); break;
-        default: PPQ_LAUNCH_HIST_SMALL(true, true); break;
-    }
-#undef PPQ_LAUNCH_HIST_SMALL
-#undef PPQ_LAUNCH_HIST_SMALL_K
+    with_row_share(full_rows, want, cap, [&](uint32_t g, auto k) {
+        with_flags([&](auto a, auto c) {
+            hipLaunchKernelGGL((hist_small_kernel<decltype(a)::value, decltype(c)::value, decltype(k)::value>), dim3(g), dim3(kHistBlock),
+                               lds_bytes(rule.bins, copies), s, x, (uint32_t)n, rule.a, rule.hs, rule.bins, copies, dst, own);
+        }, rule.asym != 0, rule.clip != 0);
+    });
     return true;
 }
 
@@ -696,7 +533,7 @@ static int launch_hist_one(const float* x, int64_t n, BinRule rule, int32_t* his
     args.count = 1; args.bins = rule.bins; args.copies = pick_copies(rule.bins, kHistBlock);
     HistJob& d = args.job[0];
     d.x = x; d.n = (uint32_t)n; d.a = rule.a; d.hs = rule.hs; d.first_tile = 0;
-    args.total_tiles = job_tiles((uint32_t)n, aligned16(x));
+    args.total_tiles = stream_job_tiles((uint32_t)n, aligned16(x), kTileVec);
     const int grid = persistent_grid(args.total_tiles);
     int* partial = nullptr;
     if (rows) { args.mode = FLUSH_ROWS_ADD; d.rows = rows; }
@@ -725,22 +562,13 @@ static int launch_hist_multi(const ppqhip_hist_job* jobs, int count, int bins, i
     const int copies = pick_copies(bins, kHistBlock);
     for (int base = 0; base < count; base += kMultiMax) {
         HistJobs args;
-        args.count = (uint32_t)((count - base) < kMultiMax ? (count - base) : kMultiMax);
         args.bins = bins; args.copies = copies; args.mode = FLUSH_ROWS_ADD;
-        uint32_t tiles = 0;
-        int64_t elems = 0;
-        for (uint32_t k = 0; k < args.count; k++) {
-            const ppqhip_hist_job& src = jobs[base + k];
-            HistJob& d = args.job[k];
-            d.x = src.x; d.rows = src.rows; d.n = (uint32_t)src.n;
+        const int64_t elems = fill_stream_jobs(args, jobs, base, count, kTileVec, [&](HistJob& d, const ppqhip_hist_job& src) {
+            d.rows = src.rows;
             if (asym) { d.a = src.p0; d.hs = (src.p1 - src.p0) / (float)bins; }     // sort.cu:123
             else { d.a = 0.f; d.hs = src.p0; }
-            d.first_tile = tiles;
-            tiles += job_tiles(d.n, aligned16(src.x));
-            elems += src.n;
-        }
-        args.total_tiles = tiles;
-        launch_persistent(args, persistent_grid(tiles), asym, clip, elems >= kHistNtElems, s);
+        });
+        launch_persistent(args, persistent_grid(args.total_tiles), asym, clip, elems >= kHistNtElems, s);
     }
     return PPQHIP_OK;
 }
@@ -808,7 +636,7 @@ int ppqhip_hist_asym_t_rows(const float* x, int64_t n, float min_value, float ma
 int ppqhip_hist_t_rows_multi(const ppqhip_hist_job* jobs, int num_jobs, int asymmetric, int clip_outliers,
                              int64_t num_bins, void* stream) {
     if (num_jobs <= 0) return PPQHIP_OK;
-    if (jobs == nullptr) { set_error("hist_t_rows_multi: jobs is null"); return PPQHIP_ERR_INVALID_VALUE; }
+    if (int st = check_job_table("hist_t_rows_multi", jobs, num_jobs)) return st;
     if (num_bins <= 0 || num_bins > kMaxLdsBins) {
         set_error("hist_t_rows_multi: 1..%d bins", kMaxLdsBins); return PPQHIP_ERR_UNSUPPORTED;
     }
@@ -870,22 +698,11 @@ static int hist_c_impl(const float* x, int64_t n, int64_t num_channel, int64_t e
         // tensor the (uncontended) atomic form keeps the read of the counter row out of the dependent chain
         const int flush_mode = (splits == 1 && n > kHistSmallElems) ? FLUSH_ROWS_ADD : FLUSH_ATOMIC;
         const bool nt = n >= kHistNtElems;      // streaming loads beyond cache residency, as in the per-tensor kernel
-#define PPQ_LAUNCH_HIST_CC(A, CL)                                                                                     \
-        do {                                                                                                          \
-            if (nt) hipLaunchKernelGGL((hist_c_channel_kernel<A, CL, true>), dim3(C * splits), dim3(kHistBlock), lds_bytes(rule.bins, copies), s, x, \
-                           make_fastdiv((uint32_t)(elem_per_channel / 4)), C, outer, splits, rule, copies, hist, scales, mins, maxs, \
-                           flush_mode);                                                                               \
-            else hipLaunchKernelGGL((hist_c_channel_kernel<A, CL, false>), dim3(C * splits), dim3(kHistBlock), lds_bytes(rule.bins, copies), s, x, \
-                           make_fastdiv((uint32_t)(elem_per_channel / 4)), C, outer, splits, rule, copies, hist, scales, mins, maxs, \
-                           flush_mode);                                                                               \
-        } while (0)
-        switch ((asym ? 2 : 0) | (rule.clip ? 1 : 0)) {
-            case 0: PPQ_LAUNCH_HIST_CC(false, false); break;
-            case 1: PPQ_LAUNCH_HIST_CC(false, true); break;
-            case 2: PPQ_LAUNCH_HIST_CC(true, false); break;
-            default: PPQ_LAUNCH_HIST_CC(true, true); break;
-        }
-#undef PPQ_LAUNCH_HIST_CC
+        with_flags([&](auto a, auto cl, auto t) {
+            hipLaunchKernelGGL((hist_c_channel_kernel<decltype(a)::value, decltype(cl)::value, decltype(t)::value>), dim3(C * splits),
+                               dim3(kHistBlock), lds_bytes(rule.bins, copies), s, x, make_fastdiv((uint32_t)(elem_per_channel / 4)), C, outer,
+                               splits, rule, copies, hist, scales, mins, maxs, flush_mode);
+        }, asym != 0, rule.clip != 0, nt);
     } else if (n / num_channel >= 256 && num_bins <= kMaxLdsBins) {        // >= 256 elements per channel, not float4-addressable
         const uint32_t C = (uint32_t)num_channel, outer = (uint32_t)(n / (num_channel * elem_per_channel));
         const uint32_t want_wgs = (uint32_t)num_cu() * kHistCWgPerCu;
@@ -893,16 +710,11 @@ static int hist_c_impl(const float* x, int64_t n, int64_t num_channel, int64_t e
         const uint64_t trips_per_channel = ((uint64_t)outer * (uint64_t)elem_per_channel) / (kHistBlock * 8);   // >= 8 trips per split
         if (splits > trips_per_channel) splits = trips_per_channel > 0 ? (uint32_t)trips_per_channel : 1u;
         const int copies = pick_copies(rule.bins, kHistBlock);
-#define PPQ_LAUNCH_HIST_CS(A, CL)                                                                                     \
-        hipLaunchKernelGGL((hist_c_channel_scalar_kernel<A, CL>), dim3(C * splits), dim3(kHistBlock), lds_bytes(rule.bins, copies), s, \
-                           x, make_fastdiv((uint32_t)elem_per_channel), C, outer, splits, rule, copies, hist, scales, mins, maxs)
-        switch ((asym ? 2 : 0) | (rule.clip ? 1 : 0)) {
-            case 0: PPQ_LAUNCH_HIST_CS(false, false); break;
-            case 1: PPQ_LAUNCH_HIST_CS(false, true); break;
-            case 2: PPQ_LAUNCH_HIST_CS(true, false); break;
-            default: PPQ_LAUNCH_HIST_CS(true, true); break;
-        }
-#undef PPQ_LAUNCH_HIST_CS
+        with_flags([&](auto a, auto cl) {
+            hipLaunchKernelGGL((hist_c_channel_scalar_kernel<decltype(a)::value, decltype(cl)::value>), dim3(C * splits), dim3(kHistBlock),
+                               lds_bytes(rule.bins, copies), s, x, make_fastdiv((uint32_t)elem_per_channel), C, outer, splits, rule, copies,
+                               hist, scales, mins, maxs);
+        }, asym != 0, rule.clip != 0);
     } else {
         hipLaunchKernelGGL(hist_c_global_kernel, dim3(stream_grid(n, kBlock * 4)), dim3(kBlock), 0, s, x, (uint32_t)n,
                            make_fastdiv((uint32_t)elem_per_channel), nc, rule, hist, scales, mins, maxs);

@@ -90,11 +90,7 @@ constexpr uint32_t kQSampleChunk = 32u << 10;      // elements per sample chunk 
 constexpr uint32_t kQSampleChunksMax = 1024;       // .. at most this many chunks per job (then the chunks grow)
 constexpr uint32_t kQSampleStride = 4;             // chunks per unit
 constexpr int kQMaxJobs = 1024;                    // jobs per launch sequence (the prefix arrays live in LDS)
-__host__ __device__ inline uint32_t q_job_tiles(uint32_t n, bool vec_ok) {
-    if (!vec_ok) return (n + kQTileElems - 1) / kQTileElems;
-    const uint32_t full = (n >> 2) / kQTileVec;
-    return full + (n > full * kQTileElems ? 1u : 0u);
-}
+__host__ __device__ inline uint32_t q_job_tiles(uint32_t n, bool vec_ok) { return stream_job_tiles(n, vec_ok, kQTileVec); }
 __host__ __device__ inline uint32_t q_job_chunks(uint32_t n) {
     uint32_t nb = (uint32_t)(((uint64_t)n + kQSampleChunk - 1) / kQSampleChunk);
     if (nb > kQSampleChunksMax) nb = kQSampleChunksMax;
@@ -446,6 +442,19 @@ __device__ __forceinline__ void qf_rare_key(uint32_t key, uint32_t t_hi, uint32_
     if (at < kQFLocalCap) (w ? staged_lo : staged_hi)[at] = key;
 }
 
+// first_tile staged in LDS: a sequence has up to kQMaxJobs jobs and its prefix arrays are device resident
+struct QSeqTiles {
+    const QSeq& s;
+    uint32_t* ft;
+    __device__ __forceinline__ uint32_t count() const { return s.count; }
+    __device__ __forceinline__ uint32_t total() const { return s.total_tiles; }
+    __device__ __forceinline__ void stage() const {
+        if (s.count > 1) load_prefix(ft, s.first_tile, s.count);       // (a single job: no table to look anything up in)
+        else { if (threadIdx.x == 0) ft[0] = 0u; __syncthreads(); }
+    }
+    __device__ __forceinline__ uint32_t first(uint32_t j) const { return ft[j]; }
+};
+
 __global__ __launch_bounds__(kQFBlock, (kQFBlock * kQFWgPerCu + 255) / 256)
 void quantile_filter_kernel(const QSeq s) {
     __shared__ uint32_t ft[kQMaxJobs];
@@ -453,119 +462,88 @@ void quantile_filter_kernel(const QSeq s) {
     __shared__ uint32_t staged_n[2], staged_base[2];
     __shared__ uint32_t ties[2];                  // keys seen == T_hi / == T_lo (this workgroup, this job)
     __shared__ uint32_t scratch[kQFBlock / kWave], stop[2], thr[3];
-    const uint32_t G = gridDim.x, g = blockIdx.x;
-    uint32_t t, t_end;
-    even_split(s.total_tiles, G, g, t, t_end);
-    if (t >= t_end) return;
-    if (threadIdx.x < 2) { staged_n[threadIdx.x] = 0; ties[threadIdx.x] = 0; }
-    if (s.count > 1) load_prefix(ft, s.first_tile, s.count);       // (a single job: no table to look anything up in)
-    else { if (threadIdx.x == 0) ft[0] = 0u; __syncthreads(); }
-    for (uint32_t j = find_job(ft, s.count, t); t < t_end; j++) {
-        const QJob job = s.job[j];
-        const uint32_t j_end = (j + 1 < s.count) ? ft[j + 1] : s.total_tiles;
-        const uint32_t k0 = t - ft[j];
-        uint32_t k = k0;
-        const uint32_t k1 = umin(t_end, j_end) - ft[j];
-        t = umin(t_end, j_end);
-        const float* __restrict__ x = job.x;
-        const uint32_t n = job.n;
-        uint32_t* P = job.ws + kOffSpec;
-        const bool vec_ok = aligned16_dev(x);
-        const uint32_t full = vec_ok ? (n >> 2) / kQTileVec : 0u;
-        const uint32_t kf = umin(k1, full);
+    const uint32_t g = blockIdx.x;
+    if (threadIdx.x < 2) { staged_n[threadIdx.x] = 0; ties[threadIdx.x] = 0; }       // (visible behind the barrier of stage())
+    QJob job;
+    uint32_t k0 = 0, t_hi = 0, t_lo = 0, span = 0;
+    int tie_hi = 0, tie_lo = 0;                               // wave-uniform
+    auto rare = [&](uint32_t key) { qf_rare_key(key, t_hi, staged[0], staged[1], staged_n); };
+    tile_walk<kQFBlock, kQFU, GlobalLoads<kQFNt>>(
+        QSeqTiles{s, ft},
+        [&](uint32_t j, uint32_t k) { job = s.job[j]; k0 = k; return StreamJob{job.x, job.n}; },
         // the first tile is requested BEFORE the thresholds are known: their loads (hint words, or the sample histogram of a
         // cold job) are a dependent round trip or two that every workgroup of a persistent grid would otherwise sit out idle
-        const float4* xv = reinterpret_cast<const float4*>(x) + threadIdx.x;
-        float4 bufa[kQFU], bufb[kQFU];
-        auto fetch = [&](float4 (&buf)[kQFU], uint32_t tile) {
-            const float4* p = xv + (size_t)tile * kQTileVec;
-#pragma unroll
-            for (int u = 0; u < kQFU; u++) buf[u] = gload4<kQFNt>(p + u * kQFBlock);
-        };
-        if (k < kf) fetch(bufa, k);
-        // thresholds: the hint of the previous batch, else from this batch's sample (block-uniform either way)
-        const bool hot = hint_valid(job.hint, n, job.k_hi, job.k_lo);
-        uint32_t t_hi, t_lo;
-        bool enabled;
-        if (hot) { t_hi = job.hint[kHTHi]; t_lo = job.hint[kHTLo]; enabled = t_lo <= t_hi; }
-        else if (!vec_ok) { t_hi = 0xFFFFFFFFu; t_lo = 0u; enabled = false; }
-        else {
-            thresholds_from_sample<kQFBlock>(job.ws, n, job.k_hi, job.k_lo, job.cap, scratch, stop, thr);
-            enabled = thr[0] != 0u; t_hi = thr[1]; t_lo = thr[2];
-            __syncthreads();                                  // thr is rewritten for the next job
-        }
-        if (k0 == 0 && threadIdx.x == 0) {                    // the owner of the job's first tile publishes them for select A
-            // (write-through stores: the line also holds the counters other workgroups add to with device atomics)
-            __hip_atomic_store(&P[kPTHi], t_hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&P[kPTLo], t_lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&P[kPHot], hot ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&P[kPEnabled], enabled ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (!enabled) continue;                               // nothing to filter by: the job is settled by F1..F3
-        const uint32_t span = t_hi - t_lo;                    // key - t_lo > span <=> outside [t_lo, t_hi]
-        int tie_hi = 0, tie_lo = 0;                           // wave-uniform
-        auto rare = [&](uint32_t key) { qf_rare_key(key, t_hi, staged[0], staged[1], staged_n); };
-        if (k < kf) {
-            auto consume = [&](const float4 (&buf)[kQFU]) {
-#pragma unroll
-                for (int u = 0; u < kQFU; u++) {
-                    const uint32_t q0 = f2key(buf[u].x), q1 = f2key(buf[u].y), q2 = f2key(buf[u].z), q3 = f2key(buf[u].w);
-                    const uint32_t d0 = q0 - t_lo, d1 = q1 - t_lo, d2 = q2 - t_lo, d3 = q3 - t_lo;
-                    if ((u & 1) == 0) {    // ties on the thresholds: a lower bound is all select A needs -> one element in eight
-                        tie_hi += popc_mask(__builtin_amdgcn_ballot_w64(q0 == t_hi));
-                        tie_lo += popc_mask(__builtin_amdgcn_ballot_w64(q0 == t_lo));
-                    }
-                    if (umax(umax(d0, d1), umax(d2, d3)) > span) {
-                        if (d0 > span) rare(q0);
-                        if (d1 > span) rare(q1);
-                        if (d2 > span) rare(q2);
-                        if (d3 > span) rare(q3);
-                    }
-                }
-            };
-            for (;;) {
-                fetch(bufb, umin(k + 1, kf - 1));
-                consume(bufa);
-                if (++k >= kf) break;
-                fetch(bufa, umin(k + 1, kf - 1));
-                consume(bufb);
-                if (++k >= kf) break;
+        [&] {
+            // thresholds: the hint of the previous batch, else from this batch's sample (block-uniform either way)
+            const bool hot = hint_valid(job.hint, job.n, job.k_hi, job.k_lo);
+            uint32_t* P = job.ws + kOffSpec;
+            bool enabled;
+            if (hot) { t_hi = job.hint[kHTHi]; t_lo = job.hint[kHTLo]; enabled = t_lo <= t_hi; }
+            else if (!aligned16_dev(job.x)) { t_hi = 0xFFFFFFFFu; t_lo = 0u; enabled = false; }
+            else {
+                thresholds_from_sample<kQFBlock>(job.ws, job.n, job.k_hi, job.k_lo, job.cap, scratch, stop, thr);
+                enabled = thr[0] != 0u; t_hi = thr[1]; t_lo = thr[2];
+                __syncthreads();                                  // thr is rewritten for the next job
             }
-        }
-        for (; k < k1; k++) {             // ragged tail tile: masked 4-B loads (ties are not counted here: a lower bound)
-            const uint32_t e0 = k * kQTileElems + threadIdx.x;
-#pragma unroll 4
-            for (int r = 0; r < 4 * kQFU; r++) {
-                const uint32_t i = e0 + r * kQFBlock;
-                if (i < n) {
-                    const uint32_t key = f2key(gload1(x + i));
-                    if (key - t_lo > span) rare(key);
+            if (k0 == 0 && threadIdx.x == 0) {                    // the owner of the job's first tile publishes them for select A
+                // (write-through stores: the line also holds the counters other workgroups add to with device atomics)
+                __hip_atomic_store(&P[kPTHi], t_hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&P[kPTLo], t_lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&P[kPHot], hot ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&P[kPEnabled], enabled ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            span = t_hi - t_lo;                                   // key - t_lo > span <=> outside [t_lo, t_hi]
+            tie_hi = 0; tie_lo = 0;
+            return enabled;                                       // false: nothing to filter by, the job is settled by F1..F3
+        },
+        [&](const float4 (&buf)[kQFU], uint32_t) {
+#pragma unroll
+            for (int u = 0; u < kQFU; u++) {
+                const uint32_t q0 = f2key(buf[u].x), q1 = f2key(buf[u].y), q2 = f2key(buf[u].z), q3 = f2key(buf[u].w);
+                const uint32_t d0 = q0 - t_lo, d1 = q1 - t_lo, d2 = q2 - t_lo, d3 = q3 - t_lo;
+                if ((u & 1) == 0) {    // ties on the thresholds: a lower bound is all select A needs -> one element in eight
+                    tie_hi += popc_mask(__builtin_amdgcn_ballot_w64(q0 == t_hi));
+                    tie_lo += popc_mask(__builtin_amdgcn_ballot_w64(q0 == t_lo));
+                }
+                if (umax(umax(d0, d1), umax(d2, d3)) > span) {
+                    if (d0 > span) rare(q0);
+                    if (d1 > span) rare(q1);
+                    if (d2 > span) rare(q2);
+                    if (d3 > span) rare(q3);
                 }
             }
-        }
-        if ((threadIdx.x & 63) == 0) {
-            if (tie_hi) atomicAdd(&ties[0], (uint32_t)tie_hi);
-            if (tie_lo) atomicAdd(&ties[1], (uint32_t)tie_lo);
-        }
-        __syncthreads();
-        const uint32_t shards = q_job_shards(job.tiles), shard = g & (shards - 1u), seg = job.cap / shards;
-        if (threadIdx.x < 2) {                                 // reserve this workgroup's slice of the job's lists
-            const uint32_t all = staged_n[threadIdx.x];
-            staged_base[threadIdx.x] = all ? atomicAdd(&P[kPCnt + 8 * threadIdx.x + shard], umin(all, kQFLocalCap)) : 0u;
-            if (all > kQFLocalCap) atomicOr(&P[threadIdx.x ? kPOvfLo : kPOvfHi], 1u);
-            if (ties[threadIdx.x]) atomicAdd(&P[kPTie + 8 * threadIdx.x + shard], ties[threadIdx.x]);
-        }
-        __syncthreads();
-        for (int w = 0; w < 2; w++) {
-            const uint32_t cnt = umin(staged_n[w], kQFLocalCap), at = staged_base[w];
-            uint32_t* list = job.spec + (w ? job.cap : 0u) + shard * seg;
-            for (uint32_t i = threadIdx.x; i < cnt; i += kQFBlock)
-                if (at + i < seg) list[at + i] = staged[w][i];
-        }
-        __syncthreads();
-        if (threadIdx.x < 2) { staged_n[threadIdx.x] = 0; ties[threadIdx.x] = 0; }
-        __syncthreads();
-    }
+        },
+        [&](float v, bool in, int) {      // (ties are not counted here: a lower bound)
+            if (in) {
+                const uint32_t key = f2key(v);
+                if (key - t_lo > span) rare(key);
+            }
+        },
+        [&](uint32_t) {
+            uint32_t* P = job.ws + kOffSpec;
+            if ((threadIdx.x & 63) == 0) {
+                if (tie_hi) atomicAdd(&ties[0], (uint32_t)tie_hi);
+                if (tie_lo) atomicAdd(&ties[1], (uint32_t)tie_lo);
+            }
+            __syncthreads();
+            const uint32_t shards = q_job_shards(job.tiles), shard = g & (shards - 1u), seg = job.cap / shards;
+            if (threadIdx.x < 2) {                                 // reserve this workgroup's slice of the job's lists
+                const uint32_t all = staged_n[threadIdx.x];
+                staged_base[threadIdx.x] = all ? atomicAdd(&P[kPCnt + 8 * threadIdx.x + shard], umin(all, kQFLocalCap)) : 0u;
+                if (all > kQFLocalCap) atomicOr(&P[threadIdx.x ? kPOvfLo : kPOvfHi], 1u);
+                if (ties[threadIdx.x]) atomicAdd(&P[kPTie + 8 * threadIdx.x + shard], ties[threadIdx.x]);
+            }
+            __syncthreads();
+            for (int w = 0; w < 2; w++) {
+                const uint32_t cnt = umin(staged_n[w], kQFLocalCap), at = staged_base[w];
+                uint32_t* list = job.spec + (w ? job.cap : 0u) + shard * seg;
+                for (uint32_t i = threadIdx.x; i < cnt; i += kQFBlock)
+                    if (at + i < seg) list[at + i] = staged[w][i];
+            }
+            __syncthreads();
+            if (threadIdx.x < 2) { staged_n[threadIdx.x] = 0; ties[threadIdx.x] = 0; }
+            __syncthreads();
+        });
 }
 
 // ---- selection inside a key list --------------------------------------------------------------------------------------
@@ -1212,9 +1190,8 @@ void ppqhip_quantile_hot_layout(int64_t* out) {
 
 int ppqhip_quantile_t_multi(const ppqhip_quantile_job* jobs, int num_jobs, float q, void* workspace, void* stream) {
     if (num_jobs <= 0) return PPQHIP_OK;
-    if (jobs == nullptr || workspace == nullptr) {
-        set_error("quantile_t_multi: jobs / workspace is null"); return PPQHIP_ERR_INVALID_VALUE;
-    }
+    if (int st = check_job_table("quantile_t_multi", jobs, num_jobs)) return st;
+    if (workspace == nullptr) { set_error("quantile_t_multi: workspace is null"); return PPQHIP_ERR_INVALID_VALUE; }
     double bytes = 0.0;
     for (int k = 0; k < num_jobs; k++) {
         if (int st = validate(jobs[k].n, "quantile_t_multi")) return st;

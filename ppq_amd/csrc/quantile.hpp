@@ -41,6 +41,7 @@
 #pragma once
 #include <cmath>
 #include "common.hpp"
+#include "stream_walk.hpp"
 
 namespace ppqhip {
 
@@ -114,6 +115,11 @@ __device__ __forceinline__ float4 gload4(const float4* p) {
     return make_float4(t.x, t.y, t.z, t.w);
 }
 __device__ __forceinline__ float gload1(const float* p) { return *(gf32_ptr)p; }
+template <bool NT>
+struct GlobalLoads {                // how the filters' walks read (stream_walk.hpp)
+    static __device__ __forceinline__ float4 v4(const float4* p) { return gload4<NT>(p); }
+    static __device__ __forceinline__ float v1(const float* p) { return gload1(p); }
+};
 
 // ---- block-wide helpers (THREADS = blockDim.x, a multiple of 64) --------------------------------------------------
 // exclusive prefix of v over the workgroup + the total; scratch: THREADS / 64 words.  All threads call this.

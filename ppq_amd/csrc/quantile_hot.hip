@@ -67,82 +67,59 @@ __global__ __launch_bounds__(kQHBlock) void quantile_hot_filter_kernel(const QHo
     __shared__ uint32_t staged[2][kQHStage];
     __shared__ uint32_t staged_n[2], ties[2];
     const uint32_t G = gridDim.x, g = blockIdx.x, n = a.n;
-    const uint32_t full_rows = (n >> 2) / kQHBlock;                   // rows of kQHBlock float4
-    uint32_t r, r1;
-    even_split(full_rows, G, g, r, r1);
-    const float4* xv = reinterpret_cast<const float4*>(a.x) + threadIdx.x;
-    float4 bufa[K], bufb[K];
-    auto fetch = [&](float4 (&buf)[K], uint32_t row) {                 // clamped rows: straight-line loads (see hist_small_kernel)
-#pragma unroll
-        for (int k = 0; k < K; k++) buf[k] = gload4<NT>(xv + (size_t)umin(row + (uint32_t)k, r1 - 1u) * kQHBlock);
-    };
-    if (r < r1) fetch(bufa, r);                                        // in flight while the hint is read
-    // the hint: ONE scalar load of its eight words (a short-circuit && chain compiles to five dependent round trips)
-    const uint32_t* __restrict__ H = a.hint;
-    const uint32_t h0 = H[kHValidHi], t_hi = H[kHTHi], h2 = H[kHValidLo], t_lo = H[kHTLo], h4 = H[kHN], h5 = H[kHKHi], h6 = H[kHKLo], h7 = H[kHUses];
-    const bool enabled = (((h0 & 0xFFu) == 1u) & ((h2 & 0xFFu) == 1u) & (h4 == n) & (h5 == a.k_hi) & (h6 == a.k_lo) & (t_lo <= t_hi)) != 0;   // the same in every workgroup
-    if (threadIdx.x < 2) { staged_n[threadIdx.x] = 0; ties[threadIdx.x] = 0; }
-    {   // the state of the launch behind this one: flags, barrier counter, exact histograms (zeroed whether needed or not)
-        constexpr uint32_t words = kQHZeroEnd - kQHZero0;
-        for (uint32_t i = g * kQHBlock + threadIdx.x; i < words; i += G * kQHBlock) a.ws[kQHZero0 + i] = 0u;
-        // (word 0: enabled | the sides' list-length levels, qh_target)
-        if (g == 0 && threadIdx.x == 0) *reinterpret_cast<uint4*>(a.ws) = make_uint4(enabled ? (1u | (h0 & 0x300u) | ((h2 & 0x300u) << 8)) : 0u, t_hi, t_lo, h7);
-    }
-    if (!enabled) return;
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // LDS counters are zero; the loads stay in flight
-    const uint32_t span = t_hi - t_lo;                                 // key - t_lo > span <=> outside [t_lo, t_hi]
+    uint32_t t_hi = 0, t_lo = 0, span = 0;
     int tie_hi = 0, tie_lo = 0;                                        // wave uniform
     auto rare = [&](uint32_t key) {
         const int w = key > t_hi ? 0 : 1;
         const uint32_t at = atomicAdd(&staged_n[w], 1u);
         if (at < kQHStage) staged[w][at] = key;
     };
-    auto consume = [&](const float4 (&buf)[K], uint32_t cnt) {
+    const bool enabled = row_walk<kQHBlock, K, PING, GlobalLoads<NT>>(
+        a.x, n,
+        [&] {   // the first rows are in flight while the hint is read
+            // the hint: ONE scalar load of its eight words (a short-circuit && chain compiles to five dependent round trips)
+            const uint32_t* __restrict__ H = a.hint;
+            const uint32_t h0 = H[kHValidHi], h1 = H[kHTHi], h2 = H[kHValidLo], h3 = H[kHTLo], h4 = H[kHN], h5 = H[kHKHi], h6 = H[kHKLo], h7 = H[kHUses];
+            const bool usable = (((h0 & 0xFFu) == 1u) & ((h2 & 0xFFu) == 1u) & (h4 == n) & (h5 == a.k_hi) & (h6 == a.k_lo) & (h3 <= h1)) != 0;   // the same in every workgroup
+            t_hi = h1; t_lo = h3;
+            if (threadIdx.x < 2) { staged_n[threadIdx.x] = 0; ties[threadIdx.x] = 0; }
+            {   // the state of the launch behind this one: flags, barrier counter, exact histograms (zeroed whether needed or not)
+                constexpr uint32_t words = kQHZeroEnd - kQHZero0;
+                for (uint32_t i = g * kQHBlock + threadIdx.x; i < words; i += G * kQHBlock) a.ws[kQHZero0 + i] = 0u;
+                // (word 0: enabled | the sides' list-length levels, qh_target)
+                if (g == 0 && threadIdx.x == 0) *reinterpret_cast<uint4*>(a.ws) = make_uint4(usable ? (1u | (h0 & 0x300u) | ((h2 & 0x300u) << 8)) : 0u, t_hi, t_lo, h7);
+            }
+            if (!usable) return false;
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // LDS counters are zero; the loads stay in flight
+            span = t_hi - t_lo;                                            // key - t_lo > span <=> outside [t_lo, t_hi]
+            return true;
+        },
+        [&](const float4 (&buf)[K], uint32_t cnt) {
 #pragma unroll
-        for (int k = 0; k < K; k++) {
-            if ((uint32_t)k < cnt) {                                   // block uniform
-                const uint32_t q0 = f2key(buf[k].x), q1 = f2key(buf[k].y), q2 = f2key(buf[k].z), q3 = f2key(buf[k].w);
-                const uint32_t d0 = q0 - t_lo, d1 = q1 - t_lo, d2 = q2 - t_lo, d3 = q3 - t_lo;
-                if ((k & 1) == 0) {        // ties on the thresholds: a lower bound is all the select needs -> one element in eight
-                    tie_hi += popc_mask(__builtin_amdgcn_ballot_w64(q0 == t_hi));
-                    tie_lo += popc_mask(__builtin_amdgcn_ballot_w64(q0 == t_lo));
+            for (int k = 0; k < K; k++) {
+                if ((uint32_t)k < cnt) {                                   // block uniform
+                    const uint32_t q0 = f2key(buf[k].x), q1 = f2key(buf[k].y), q2 = f2key(buf[k].z), q3 = f2key(buf[k].w);
+                    const uint32_t d0 = q0 - t_lo, d1 = q1 - t_lo, d2 = q2 - t_lo, d3 = q3 - t_lo;
+                    if ((k & 1) == 0) {        // ties on the thresholds: a lower bound is all the select needs -> one element in eight
+                        tie_hi += popc_mask(__builtin_amdgcn_ballot_w64(q0 == t_hi));
+                        tie_lo += popc_mask(__builtin_amdgcn_ballot_w64(q0 == t_lo));
+                    }
+                    if (umax(umax(d0, d1), umax(d2, d3)) > span) {
+                        if (d0 > span) rare(q0);
+                        if (d1 > span) rare(q1);
+                        if (d2 > span) rare(q2);
+                        if (d3 > span) rare(q3);
+                    }
                 }
-                if (umax(umax(d0, d1), umax(d2, d3)) > span) {
-                    if (d0 > span) rare(q0);
-                    if (d1 > span) rare(q1);
-                    if (d2 > span) rare(q2);
-                    if (d3 > span) rare(q3);
-                }
             }
-        }
-    };
-    if (r < r1) {
-        if (PING) {
-            for (;;) {
-                fetch(bufb, r + K);
-                consume(bufa, umin((uint32_t)K, r1 - r));
-                r += K;
-                if (r >= r1) break;
-                fetch(bufa, r + K);
-                consume(bufb, umin((uint32_t)K, r1 - r));
-                r += K;
-                if (r >= r1) break;
+        },
+        [&](float v, bool in, uint32_t) {
+            if (in) {
+                const uint32_t key = f2key(v);
+                if (key - t_lo > span) rare(key);
             }
-        } else {
-            for (;;) {
-                consume(bufa, umin((uint32_t)K, r1 - r));
-                r += K;
-                if (r >= r1) break;
-                fetch(bufa, r);
-            }
-        }
-    }
-    if (g == G - 1) {                                                  // the ragged rest: < kQHBlock float4 + n % 4 elements
-        for (uint32_t i = full_rows * kQHBlock * 4u + threadIdx.x; i < n; i += kQHBlock) {
-            const uint32_t key = f2key(gload1(a.x + i));
-            if (key - t_lo > span) rare(key);
-        }
-    }
+        });
+    if (!enabled) return;
     if ((threadIdx.x & 63) == 0) {
         if (tie_hi) atomicAdd(&ties[0], (uint32_t)tie_hi);
         if (tie_lo) atomicAdd(&ties[1], (uint32_t)tie_lo);
@@ -866,18 +843,12 @@ static void quantile_hot_launch(const QHot& a0, hipStream_t s) {
     uint32_t cap = (uint32_t)num_cu() * 2u;
     if (cap > kQHMaxWg) cap = kQHMaxWg;
     if ((int64_t)a.n <= kQHSmallElems) {
-        uint32_t g = (full_rows + 1) / 2;
-        if (g > cap) g = cap;
-        if (g < 1) g = 1;
-        const uint32_t share = (full_rows + g - 1) / g;
-        a.wgs = g;
-        if (share <= 2) hipLaunchKernelGGL((quantile_hot_filter_kernel<2, false, false>), dim3(g), dim3(kQHBlock), 0, s, a);
-        else if (share <= 4) hipLaunchKernelGGL((quantile_hot_filter_kernel<4, false, false>), dim3(g), dim3(kQHBlock), 0, s, a);
-        else hipLaunchKernelGGL((quantile_hot_filter_kernel<8, false, false>), dim3(g), dim3(kQHBlock), 0, s, a);
+        with_row_share(full_rows, (full_rows + 1) / 2, cap, [&](uint32_t g, auto k) {
+            a.wgs = g;
+            hipLaunchKernelGGL((quantile_hot_filter_kernel<decltype(k)::value, false, false>), dim3(g), dim3(kQHBlock), 0, s, a);
+        });
     } else {
-        uint32_t g = full_rows / 4;
-        if (g > cap) g = cap;
-        if (g < 1) g = 1;
+        const uint32_t g = clamp_grid(full_rows / 4, cap);
         a.wgs = g;
         // a filter workgroup is expected to list ~1.5 x wanted / g keys per side: more than the record holds -> the heads travel with
         // the records; lists of thousands of keys -> the two sides are selected by two workgroups

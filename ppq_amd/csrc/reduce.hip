@@ -13,6 +13,7 @@
 
 #include "common.hpp"
 #include "minmax_fold.hpp"
+#include "stream_walk.hpp"
 
 namespace ppqhip {
 
@@ -54,15 +55,14 @@ __global__ __launch_bounds__(kBlock) void minmax_t_kernel(const float* __restric
     }
 }
 
-// many tensors, one launch -- the persistent design of hist_persistent_kernel (hist.hip): the work is the
-// concatenated list of tiles (kMMBlock * kMMU float4) of all jobs, split evenly over a chip-sized grid;
-// a workgroup walks its contiguous tile range with two ping-pong register tiles and folds its running
-// (min, max) into ITS OWN slot of every job it touches (plain stream-ordered read-modify-write).
+// many tensors, one launch -- the tile walk (stream_walk.hpp): the work is the concatenated list of tiles (kMMBlock * kMMU
+// float4) of all jobs; a workgroup folds its running (min, max) into ITS OWN slot of every job it touches (plain stream-ordered
+// read-modify-write).
 constexpr int kMinMaxMultiMax = 96;              // jobs per launch (2.3 KB of kernel arguments)
 constexpr int kMMBlock = 256, kMMU = 2;
 constexpr int kMMWgPerCu = 8;
 constexpr int kMMGrid = kNumCU * kMMWgPerCu;                     // <= ppqhip_minmax_slots()
-constexpr uint32_t kMMTileVec = (uint32_t)kMMBlock * kMMU, kMMTileElems = kMMTileVec * 4;
+constexpr uint32_t kMMTileVec = (uint32_t)kMMBlock * kMMU;
 static_assert(kMMGrid <= kNumCU * 8, "one slot per workgroup");
 struct MinMaxJob {
     const float* x;
@@ -75,124 +75,47 @@ struct MinMaxJobs {
     uint32_t count;
     uint32_t total_tiles;
 };
-__host__ __device__ inline uint32_t mm_job_tiles(uint32_t n, bool vec_ok) {
-    if (!vec_ok) return (n + kMMTileElems - 1) / kMMTileElems;
-    const uint32_t full = (n >> 2) / kMMTileVec;
-    return full + (n > full * kMMTileElems ? 1u : 0u);
-}
 
 template <bool NT>
 __global__ __launch_bounds__(kMMBlock) void minmax_persistent_kernel(const MinMaxJobs jobs) {
     __shared__ float lds[32];
-    const uint32_t G = gridDim.x, g = blockIdx.x;
-    uint32_t t, t_end;
-    even_split(jobs.total_tiles, G, g, t, t_end);
-    if (t >= t_end) return;
-    uint32_t lo = 0, hi = jobs.count;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (jobs.job[mid].first_tile <= t) lo = mid; else hi = mid;
-    }
-    for (uint32_t j = lo; t < t_end; j++) {
-        const MinMaxJob& job = jobs.job[j];
-        const uint32_t j_end = (j + 1 < jobs.count) ? jobs.job[j + 1].first_tile : jobs.total_tiles;
-        uint32_t k = t - job.first_tile;
-        const uint32_t k1 = min(t_end, j_end) - job.first_tile;
-        t = min(t_end, j_end);
-        const float* __restrict__ x = job.x;
-        const uint32_t n = job.n;
-        const bool vec_ok = (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
-        const uint32_t full = vec_ok ? (n >> 2) / kMMTileVec : 0u;
-        const uint32_t kf = min(k1, full);
-        float mn = INFINITY, mx = -INFINITY;
-        if (k < kf) {
-            const float4* xv = reinterpret_cast<const float4*>(x) + threadIdx.x;
-            float4 bufa[kMMU], bufb[kMMU];
-            auto fetch = [&](float4 (&buf)[kMMU], uint32_t tile) {
-                const float4* p = xv + (size_t)tile * kMMTileVec;
+    float mn = INFINITY, mx = -INFINITY;
+    tile_walk<kMMBlock, kMMU, PlainLoads<NT>>(
+        ArgTiles<MinMaxJobs>{jobs},
+        [&](uint32_t j, uint32_t) { mn = INFINITY; mx = -INFINITY; return StreamJob{jobs.job[j].x, jobs.job[j].n}; },
+        [] { return true; },
+        [&](const float4 (&buf)[kMMU], uint32_t) {
 #pragma unroll
-                for (int u = 0; u < kMMU; u++) buf[u] = load4<NT>(p + u * kMMBlock);
-            };
-            auto consume = [&](const float4 (&buf)[kMMU]) {
-#pragma unroll
-                for (int u = 0; u < kMMU; u++) minmax_fold4(mn, mx, buf[u]);
-            };
-            fetch(bufa, k);
-            for (;;) {
-                fetch(bufb, min(k + 1, kf - 1));
-                consume(bufa);
-                if (++k >= kf) break;
-                fetch(bufa, min(k + 1, kf - 1));
-                consume(bufb);
-                if (++k >= kf) break;
-            }
-        }
-        for (; k < k1; k++) {             // ragged tail tile / unaligned tensor: masked 4-B loads
-            const uint32_t e0 = k * kMMTileElems + threadIdx.x;
-#pragma unroll 4
-            for (int r = 0; r < 4 * kMMU; r++) {
-                const uint32_t i = e0 + r * kMMBlock;
-                if (i < n) minmax_fold1(mn, mx, x[i]);
-            }
-        }
-        minmax_block_fold(mn, mx, lds);
-        if (threadIdx.x == 0) minmax_slot_fold(job.slots + 2 * g, mn, mx);
-        __syncthreads();
-    }
+            for (int u = 0; u < kMMU; u++) minmax_fold4(mn, mx, buf[u]);
+        },
+        [&](float a, bool in, int) { if (in) minmax_fold1(mn, mx, a); },
+        [&](uint32_t j) {
+            minmax_block_fold(mn, mx, lds);
+            if (threadIdx.x == 0) minmax_slot_fold(jobs.job[j].slots + 2 * blockIdx.x, mn, mx);
+            __syncthreads();
+        });
 }
 
-// The single-tensor launch for LATENCY-bound sizes (see hist_small_kernel, hist.hip: direct arguments instead of the 2.3 KB job
-// table and its two dependent scalar-load rounds, every load of the share in flight before anything else).  The workgroup's slot
-// is read FIRST, so the read-modify-write at the end is no dependent load -> store chain.  K: rows of kMMBlock float4 per share.
-// PING (mid-size and large single tensors, round 6): two register tiles of K rows ping-pong -- the persistent kernel's streaming loop
-// without its job table.  A small gain here, unlike the histogram's (the persistent min/max kernel was within 4-10 % of the read
-// floor already): interleaved A/B Bx4 6.28 -> 5.92 us, Bx16 19.9 -> 19.3, Bx32 32.4 -> 31.9 (0.805 of 8 TB/s), Bx8 equal at the
-// 10th percentile (10.3 us), profiles/r06_minmax_stream_ab.txt.
+// The single-tensor launch -- the row walk (stream_walk.hpp): direct arguments instead of the 2.3 KB job table and its two
+// dependent scalar-load rounds, every load of the share in flight before anything else.  The workgroup's slot is read FIRST, so
+// the read-modify-write at the end is no dependent load -> store chain.  K: rows of kMMBlock float4 per share.
+// PING (mid-size and large single tensors, round 6): a small gain here, unlike the histogram's (the persistent min/max kernel
+// was within 4-10 % of the read floor already): interleaved A/B Bx4 6.28 -> 5.92 us, Bx16 19.9 -> 19.3, Bx32 32.4 -> 31.9 (0.805
+// of 8 TB/s), Bx8 equal at the 10th percentile (10.3 us), profiles/r06_minmax_stream_ab.txt.
 template <int K, bool PING = false, bool NT = false>
 __global__ __launch_bounds__(kMMBlock) void minmax_small_kernel(const float* __restrict__ x, uint32_t n, float* __restrict__ slots) {
     __shared__ float lds[32];
-    const uint32_t G = gridDim.x, g = blockIdx.x;
+    const uint32_t g = blockIdx.x;
     float s_mn = INFINITY, s_mx = -INFINITY;
     if (threadIdx.x == 0) { s_mn = slots[2 * g]; s_mx = slots[2 * g + 1]; }
-    const uint32_t nvec = n >> 2, full_rows = nvec / kMMBlock;
-    uint32_t r0, r1;
-    even_split(full_rows, G, g, r0, r1);
-    const float4* xv = reinterpret_cast<const float4*>(x) + threadIdx.x;
     float mn = INFINITY, mx = -INFINITY;
-    auto fetch = [&](float4 (&buf)[K], uint32_t r) {
+    row_walk<kMMBlock, K, PING, PlainLoads<NT>>(
+        x, n, [] { return true; },
+        [&](const float4 (&buf)[K], uint32_t) {                               // clamped duplicates are harmless: all K rows
 #pragma unroll
-        for (int k = 0; k < K; k++) buf[k] = load4<NT>(xv + (size_t)min(r + (uint32_t)k, r1 - 1) * kMMBlock);      // clamped: duplicates are harmless
-    };
-    auto fold = [&](const float4 (&buf)[K]) {
-#pragma unroll
-        for (int k = 0; k < K; k++) minmax_fold4(mn, mx, buf[k]);
-    };
-    if (PING) {
-        if (r0 < r1) {
-            float4 bufa[K], bufb[K];
-            uint32_t r = r0;
-            fetch(bufa, r);
-            for (;;) {
-                fetch(bufb, r + K);
-                fold(bufa);
-                r += K;
-                if (r >= r1) break;
-                fetch(bufa, r + K);
-                fold(bufb);
-                r += K;
-                if (r >= r1) break;
-            }
-        }
-    } else {
-        for (uint32_t r = r0; r < r1; r += K) {
-            float4 buf[K];
-            fetch(buf, r);
-            fold(buf);
-        }
-    }
-    if (g == G - 1) {                                                  // the ragged rest: < kMMBlock float4 + n % 4 elements
-        for (uint32_t i = full_rows * kMMBlock * 4 + threadIdx.x; i < n; i += kMMBlock) minmax_fold1(mn, mx, x[i]);
-    }
+            for (int k = 0; k < K; k++) minmax_fold4(mn, mx, buf[k]);
+        },
+        [&](float a, bool in, uint32_t) { if (in) minmax_fold1(mn, mx, a); });
     minmax_block_fold(mn, mx, lds);
     if (threadIdx.x == 0) {
         slots[2 * g] = fminf(mn, s_mn);
@@ -566,10 +489,8 @@ int ppqhip_minmax_t(const float* x, int64_t n, float* minmax, void* workspace, v
 int64_t ppqhip_minmax_slots(void) { return (int64_t)kNumCU * 8; }
 
 static void launch_minmax_persistent(const MinMaxJobs& args, int64_t elems, hipStream_t s) {
-    uint32_t grid = args.total_tiles / 2;                       // at least two tiles per workgroup
-    if (grid < 1) grid = 1;
-    const uint32_t mm_cap = (uint32_t)(num_cu() * kMMWgPerCu);      // <= kMMGrid (one slot per workgroup)
-    if (grid > mm_cap) grid = mm_cap;
+    // at least two tiles per workgroup, at most kMMGrid workgroups (one slot each)
+    const uint32_t grid = clamp_grid(args.total_tiles / 2, (uint32_t)(num_cu() * kMMWgPerCu));
     // streaming (nontemporal) loads once the data cannot be cache resident
     if (elems >= (48ll << 20)) hipLaunchKernelGGL((minmax_persistent_kernel<true>), dim3(grid), dim3(kMMBlock), 0, s, args);
     else hipLaunchKernelGGL((minmax_persistent_kernel<false>), dim3(grid), dim3(kMMBlock), 0, s, args);
@@ -580,24 +501,16 @@ int ppqhip_minmax_t_slots(const float* x, int64_t n, float* slots, void* stream)
     if (int st = validate(n, "minmax_t_slots")) return st;
     hipStream_t s = (hipStream_t)stream;
     LaunchScope scope(K_MINMAX_T, 4.0 * (double)n, s);
+    const uint32_t full_rows = (uint32_t)((n >> 2) / kMMBlock);
+    const uint32_t cap = (uint32_t)(num_cu() * kMMWgPerCu);         // one slot per workgroup
     if (n <= (4ll << 20) && aligned16(x)) {                       // up to 16 MB: the lean kernel, two rows (8 KB) per workgroup
-        const uint32_t full_rows = (uint32_t)((n >> 2) / kMMBlock);
-        uint32_t grid = (full_rows + 1) / 2;
-        const uint32_t cap = (uint32_t)(num_cu() * kMMWgPerCu);     // one slot per workgroup
-        if (grid > cap) grid = cap;
-        if (grid < 1) grid = 1;
-        const uint32_t share = (full_rows + grid - 1) / grid;
-        if (share <= 2) hipLaunchKernelGGL((minmax_small_kernel<2>), dim3(grid), dim3(kMMBlock), 0, s, x, (uint32_t)n, slots);
-        else if (share <= 4) hipLaunchKernelGGL((minmax_small_kernel<4>), dim3(grid), dim3(kMMBlock), 0, s, x, (uint32_t)n, slots);
-        else hipLaunchKernelGGL((minmax_small_kernel<8>), dim3(grid), dim3(kMMBlock), 0, s, x, (uint32_t)n, slots);
+        with_row_share(full_rows, (full_rows + 1) / 2, cap, [&](uint32_t grid, auto k) {
+            hipLaunchKernelGGL((minmax_small_kernel<decltype(k)::value>), dim3(grid), dim3(kMMBlock), 0, s, x, (uint32_t)n, slots);
+        });
         return finish_launch("minmax_t_slots");
     }
     if (aligned16(x)) {                                           // beyond 16 MB: the same kernel with two ping-pong tiles of two rows
-        const uint32_t full_rows = (uint32_t)((n >> 2) / kMMBlock);
-        uint32_t grid = full_rows / 8;                            // >= two tile pairs per workgroup
-        const uint32_t cap = (uint32_t)(num_cu() * kMMWgPerCu);
-        if (grid > cap) grid = cap;
-        if (grid < 1) grid = 1;
+        const uint32_t grid = clamp_grid(full_rows / 8, cap);     // >= two tile pairs per workgroup
         if (n >= (48ll << 20)) hipLaunchKernelGGL((minmax_small_kernel<2, true, true>), dim3(grid), dim3(kMMBlock), 0, s, x, (uint32_t)n, slots);
         else hipLaunchKernelGGL((minmax_small_kernel<2, true, false>), dim3(grid), dim3(kMMBlock), 0, s, x, (uint32_t)n, slots);
         return finish_launch("minmax_t_slots");
@@ -605,14 +518,14 @@ int ppqhip_minmax_t_slots(const float* x, int64_t n, float* slots, void* stream)
     MinMaxJobs args;
     args.count = 1;
     args.job[0].x = x; args.job[0].slots = slots; args.job[0].n = (uint32_t)n; args.job[0].first_tile = 0;
-    args.total_tiles = mm_job_tiles((uint32_t)n, aligned16(x));
+    args.total_tiles = stream_job_tiles((uint32_t)n, aligned16(x), kMMTileVec);
     launch_minmax_persistent(args, n, s);
     return finish_launch("minmax_t_slots");
 }
 
 int ppqhip_minmax_t_slots_multi(const ppqhip_minmax_job* jobs, int num_jobs, void* stream) {
     if (num_jobs <= 0) return PPQHIP_OK;
-    if (jobs == nullptr) { set_error("minmax_t_slots_multi: jobs is null"); return PPQHIP_ERR_INVALID_VALUE; }
+    if (int st = check_job_table("minmax_t_slots_multi", jobs, num_jobs)) return st;
     double bytes = 0.0;
     for (int k = 0; k < num_jobs; k++) {
         if (int st = validate(jobs[k].n, "minmax_t_slots_multi")) return st;
@@ -625,17 +538,8 @@ int ppqhip_minmax_t_slots_multi(const ppqhip_minmax_job* jobs, int num_jobs, voi
     LaunchScope scope(K_MINMAX_T, bytes, s);
     for (int base = 0; base < num_jobs; base += kMinMaxMultiMax) {
         MinMaxJobs args;
-        args.count = (uint32_t)((num_jobs - base) < kMinMaxMultiMax ? (num_jobs - base) : kMinMaxMultiMax);
-        uint32_t tiles = 0;
-        int64_t elems = 0;
-        for (uint32_t k = 0; k < args.count; k++) {
-            const ppqhip_minmax_job& src = jobs[base + k];
-            args.job[k].x = src.x; args.job[k].slots = src.slots; args.job[k].n = (uint32_t)src.n;
-            args.job[k].first_tile = tiles;
-            tiles += mm_job_tiles((uint32_t)src.n, aligned16(src.x));
-            elems += src.n;
-        }
-        args.total_tiles = tiles;
+        const int64_t elems = fill_stream_jobs(args, jobs, base, num_jobs, kMMTileVec,
+                                               [](MinMaxJob& d, const ppqhip_minmax_job& src) { d.slots = src.slots; });
         launch_minmax_persistent(args, elems, s);
     }
     return finish_launch("minmax_t_slots_multi");
@@ -728,7 +632,7 @@ int ppqhip_isotone_t(const float* x, int64_t n, float* dest, void* workspace, vo
 
 int ppqhip_minmax_c_multi(const ppqhip_minmax_c_job* jobs, int num_jobs, void* stream) {
     if (num_jobs <= 0) return PPQHIP_OK;
-    if (jobs == nullptr) { set_error("minmax_c_multi: jobs is null"); return PPQHIP_ERR_INVALID_VALUE; }
+    if (int st = check_job_table("minmax_c_multi", jobs, num_jobs)) return st;
     hipStream_t s = (hipStream_t)stream;
     double bytes = 0.0;
     for (int k = 0; k < num_jobs; k++) {
