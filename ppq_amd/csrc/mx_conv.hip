@@ -20,8 +20,9 @@
 // channel holds one in w.
 // ppqhip_mx_conv2d_fused runs the same K loop with the fused epilogue of mx_mfma.hpp: residual, ReLU and the result
 // packed along the output columns, in a second set of 25 instantiations; the plain kernels keep their code.
+// What the kernel shares with mx_gemm_kernel is in mx_mfma.hpp; what is here is its A source: the
+// implicit-GEMM addressing.
 #include "common.hpp"
-#include "job_table.hpp"
 #include "mx_mfma.hpp"
 
 namespace ppqhip {
@@ -29,13 +30,10 @@ namespace {
 
 struct MxConvArgs {
     const uint8_t* xe; const uint8_t* xs;         // x: elements [n, h, w, nbc * BA], scales [n, h, w, nbc]
-    const uint8_t* we; const uint8_t* ws;         // w: elements [o, nb * BB], scales [o, nb]
-    const float* bias;                            // [o] or null
-    float* y;                                     // [m, o]
-    uint32_t m, o, nb, nbc;                       // nb = kh * kw * nbc (0 when x holds no block at all)
+    MxTileArgs t;                                 // B is w [o, nb * BB] / [o, nb], c is y [m, o]; nb = kh * kw * nbc (0 when x holds no block at all)
+    uint32_t nbc;
     uint32_t h, w, kw;
     int32_t sh, sw, ph, pw, dh, dw;
-    FastDiv tiles_n;                              // workgroups along O
     FastDiv ohw, ow;                              // m -> (n, oy, ox)
     FastDiv fnbc, fkw;                            // kb -> (tap, channel block), tap -> (ky, kx)
 };
@@ -53,8 +51,8 @@ struct ConvTap {                                  // block kb of a row of A: the
 template <bool TAIL>
 __device__ __forceinline__ ConvTap conv_tap(const MxConvArgs& g, uint32_t kb) {
     ConvTap t;
-    t.live = !TAIL || kb < g.nb;
-    if (TAIL) kb = min(kb, g.nb - 1u);
+    t.live = !TAIL || kb < g.t.nb;
+    if (TAIL) kb = min(kb, g.t.nb - 1u);
     const uint32_t tap = fdiv(kb, g.fnbc), ky = fdiv(tap, g.fkw);
     t.cb = kb - tap * g.nbc;
     t.dy = (int32_t)ky * g.dh;
@@ -70,86 +68,69 @@ __device__ __forceinline__ bool conv_block(const MxConvArgs& g, const ConvRow& r
     return in;
 }
 
-// The A side of load_operand (mx_mfma.hpp): for each of the wave's kGemmWaveTiles rows of this lane the operand registers of
-// K-step kb0 / 4 and the scale code of block kb0 + grp, every block through its own computed address.
-template <int F, bool TAIL>
-__device__ __forceinline__ void load_activation(const MxConvArgs& g, const ConvRow (&rows)[kGemmWaveTiles], uint32_t kb0, uint32_t grp,
-                                                v8i (&frag)[kGemmWaveTiles], int (&scale)[kGemmWaveTiles], uint32_t (&nan)[kGemmWaveTiles]) {
-    constexpr uint32_t bits = gemm_elem_bits(F);
-    const ConvTap ts = conv_tap<TAIL>(g, kb0 + grp);
-    if (bits == 8u) {
-        const ConvTap t0 = conv_tap<TAIL>(g, kb0 + (grp >> 1)), t1 = conv_tap<TAIL>(g, kb0 + 2u + (grp >> 1));
+// The A source of the kernel (mx_mfma.hpp, RowSource): m -> (n, oy, ox) once per row, then per K-step what RowSource gives for a packed row --
+// the operand registers of K-step kb0 / 4 and the scale code of block kb0 + grp -- every block through its own computed address.
+template <int F>
+struct ConvSource {
+    const MxConvArgs& g;
+    ConvRow rows[kGemmWaveTiles];                 // the lane's rows, set by prepare
+
+    __device__ __forceinline__ void prepare(uint32_t m0, uint32_t r) {
+#pragma unroll
+        for (int t = 0; t < kGemmWaveTiles; t++) {
+            const uint32_t row = min(m0 + t * kGemmTile + r, g.t.m - 1u);
+            const uint32_t n = fdiv(row, g.ohw), rem = row - n * g.ohw.d, oy = fdiv(rem, g.ow), ox = rem - oy * g.ow.d;
+            rows[t].img = n * g.h;
+            rows[t].iy0 = (int32_t)oy * g.sh - g.ph;
+            rows[t].ix0 = (int32_t)ox * g.sw - g.pw;
+        }
+    }
+    template <bool TAIL>
+    __device__ __forceinline__ void load(uint32_t kb0, uint32_t grp, v8i (&frag)[kGemmWaveTiles], int (&scale)[kGemmWaveTiles],
+                                         uint32_t (&nan)[kGemmWaveTiles]) const {
+        constexpr uint32_t bits = gemm_elem_bits(F);
+        const ConvTap ts = conv_tap<TAIL>(g, kb0 + grp);
+        const ConvTap t0 = conv_tap<TAIL>(g, kb0 + (grp >> 1)), t1 = conv_tap<TAIL>(g, kb0 + 2u + (grp >> 1));       // FP8 only
         const uint32_t half = 16u * (grp & 1u);
 #pragma unroll
         for (int t = 0; t < kGemmWaveTiles; t++) {
-            uint32_t b0, b1, bs;
-            const bool in0 = conv_block(g, rows[t], t0, b0), in1 = conv_block(g, rows[t], t1, b1), ins = conv_block(g, rows[t], ts, bs);
-            uint4 lo = *reinterpret_cast<const uint4*>(g.xe + (size_t)b0 * 32u + half);
-            uint4 hi = *reinterpret_cast<const uint4*>(g.xe + (size_t)b1 * 32u + half);
+            uint32_t bs;
+            const bool ins = conv_block(g, rows[t], ts, bs);
+            if (bits == 8u) {
+                uint32_t b0, b1;
+                const bool in0 = conv_block(g, rows[t], t0, b0), in1 = conv_block(g, rows[t], t1, b1);
+                frag[t] = fp8_fragment(g.xe + (size_t)b0 * 32u + half, g.xe + (size_t)b1 * 32u + half, in0, in1);
+            } else {
+                frag[t] = block_fragment<F>(g.xe + (size_t)bs * (4u * bits), ins);
+            }
             const int s = (int)g.xs[bs];
-            if (!in0) lo = make_uint4(0u, 0u, 0u, 0u);
-            if (!in1) hi = make_uint4(0u, 0u, 0u, 0u);
-            frag[t] = v8i{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
             scale[t] = ins ? s : 127;
         }
-    } else {
-#pragma unroll
-        for (int t = 0; t < kGemmWaveTiles; t++) {
-            uint32_t b;
-            const bool in = conv_block(g, rows[t], ts, b);
-            const uint8_t* p = g.xe + (size_t)b * (4u * bits);
-            v8i r = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (bits == 6u) {                                                    // 24-B blocks are 8-B aligned
-                const uint2 t0 = *reinterpret_cast<const uint2*>(p), t1 = *reinterpret_cast<const uint2*>(p + 8), t2 = *reinterpret_cast<const uint2*>(p + 16);
-                r[0] = (int)t0.x; r[1] = (int)t0.y; r[2] = (int)t1.x; r[3] = (int)t1.y; r[4] = (int)t2.x; r[5] = (int)t2.y;
-            } else {
-                const uint4 lo = *reinterpret_cast<const uint4*>(p);
-                r[0] = (int)lo.x; r[1] = (int)lo.y; r[2] = (int)lo.z; r[3] = (int)lo.w;
-            }
-            const int s = (int)g.xs[b];
-            frag[t] = in ? r : v8i{0, 0, 0, 0, 0, 0, 0, 0};
-            scale[t] = in ? s : 127;
-        }
+        flag_nan<F>(frag, scale, nan);
     }
-#pragma unroll
-    for (int t = 0; t < kGemmWaveTiles; t++) {
-        uint32_t bad = scale[t] == 0xff ? 1u : 0u;
-        if (F == PPQHIP_MXFP8_E4M3 || F == PPQHIP_MXFP8_E5M2) {
-#pragma unroll
-            for (int w = 0; w < 8; w++) bad |= fp8_nan_bits<F>((uint32_t)frag[t][w]);
-        }
-        nan[t] |= bad;
-    }
-}
+};
 
 // F is empty -- the plain kernel, (g) alone -- or one MxFusedOut: the epilogue of mx_mfma.hpp (fused_epilogue) in place of the plain
-// one, (g, f).  Everything up to the epilogue is the same code; in the fused kernel g.y may be null.
+// one, (g, f).  Everything up to the epilogue is the same code; in the fused kernel g.t.c may be null.  The text of this kernel
+// and of mx_gemm_kernel (mx_gemm.hip) differs in the A source alone; it stays in the kernel because the backend schedules the FP8 K loops worse
+// when it is an inlined function (profiles/mx_tile.txt).
 template <int FA, int FB, typename... F>
 __global__ __launch_bounds__(kBlock) void mx_conv_kernel(const MxConvArgs g, const F... f) {
     constexpr bool FUSED = sizeof...(F) != 0;
     static_assert(sizeof...(F) <= 1, "at most one MxFusedOut");
     constexpr int T = kGemmWaveTiles;
-    constexpr uint32_t BB = 4u * gemm_elem_bits(FB);
-    constexpr int HA = gemm_hw_format(FA), HB = gemm_hw_format(FB);               // immediates of the instruction
-    const uint32_t tm = fdiv(blockIdx.x, g.tiles_n), tn = blockIdx.x - tm * g.tiles_n.d;
+    const MxTileArgs& t = g.t;
+    const uint32_t tm = fdiv(blockIdx.x, t.tiles_n), tn = blockIdx.x - tm * t.tiles_n.d;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t r = lane & 15u, grp = lane >> 4;
     const uint32_t m0 = tm * kGemmEdge + (wave / kGemmWaves) * (T * kGemmTile);
     const uint32_t n0 = tn * kGemmEdge + (wave % kGemmWaves) * (T * kGemmTile);
-    if (m0 >= g.m || n0 >= g.o) return;                                          // wave-uniform; there is no barrier below
+    if (m0 >= t.m || n0 >= t.n) return;                                          // wave-uniform; there is no barrier below
 
-    ConvRow rows[T];
-    const uint8_t* be[T]; const uint8_t* bs[T];
-#pragma unroll
-    for (int t = 0; t < T; t++) {
-        const uint32_t row = min(m0 + t * kGemmTile + r, g.m - 1u);
-        const uint32_t n = fdiv(row, g.ohw), rem = row - n * g.ohw.d, oy = fdiv(rem, g.ow), ox = rem - oy * g.ow.d;
-        rows[t].img = n * g.h;
-        rows[t].iy0 = (int32_t)oy * g.sh - g.ph;
-        rows[t].ix0 = (int32_t)ox * g.sw - g.pw;
-        const size_t col = min(n0 + t * kGemmTile + r, g.o - 1u);
-        be[t] = g.we + col * g.nb * BB; bs[t] = g.ws + col * g.nb;
-    }
+    ConvSource<FA> a_src{g};
+    RowSource<FB> b_src{t.be, t.bs, t.n, t.nb};
+    a_src.prepare(m0, r);
+    b_src.prepare(n0, r);
     v4f acc[T][T];
 #pragma unroll
     for (int i = 0; i < T; i++)
@@ -157,43 +138,25 @@ __global__ __launch_bounds__(kBlock) void mx_conv_kernel(const MxConvArgs g, con
         for (int j = 0; j < T; j++) acc[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
     uint32_t nan_a[T], nan_b[T];
 #pragma unroll
-    for (int t = 0; t < T; t++) { nan_a[t] = 0u; nan_b[t] = 0u; }
+    for (int i = 0; i < T; i++) { nan_a[i] = 0u; nan_b[i] = 0u; }
 
-    v8i a[T], b[T];
-    int sa[T], sb[T];
-    const uint32_t full = g.nb / kGemmStepBlocks;
-    for (uint32_t s = 0; s < full; s++) {
-        load_activation<FA, false>(g, rows, s * kGemmStepBlocks, grp, a, sa, nan_a);
-        load_operand<FB, false>(be, bs, s * kGemmStepBlocks, grp, g.nb, b, sb, nan_b);
-#pragma unroll
-        for (int i = 0; i < T; i++)
-#pragma unroll
-            for (int j = 0; j < T; j++)
-                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[i], b[j], acc[i][j], HA, HB, 0, sa[i], 0, sb[j]);
-    }
-    if (g.nb % kGemmStepBlocks) {
-        load_activation<FA, true>(g, rows, full * kGemmStepBlocks, grp, a, sa, nan_a);
-        load_operand<FB, true>(be, bs, full * kGemmStepBlocks, grp, g.nb, b, sb, nan_b);
-#pragma unroll
-        for (int i = 0; i < T; i++)
-#pragma unroll
-            for (int j = 0; j < T; j++)
-                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[i], b[j], acc[i][j], HA, HB, 0, sa[i], 0, sb[j]);
-    }
+    const uint32_t full = t.nb / kGemmStepBlocks;
+    for (uint32_t s = 0; s < full; s++) mx_tile_step<FA, FB, false>(a_src, b_src, s * kGemmStepBlocks, grp, acc, nan_a, nan_b);
+    if (t.nb % kGemmStepBlocks) mx_tile_step<FA, FB, true>(a_src, b_src, full * kGemmStepBlocks, grp, acc, nan_a, nan_b);
 
     uint32_t rows_nan[T], cols_nan[T];
 #pragma unroll
-    for (int t = 0; t < T; t++) { rows_nan[t] = tile_flags(nan_a[t]); cols_nan[t] = tile_flags(nan_b[t]); }
+    for (int i = 0; i < T; i++) { rows_nan[i] = tile_flags(nan_a[i]); cols_nan[i] = tile_flags(nan_b[i]); }
     if constexpr (FUSED) {                                                       // the stage is wave-private: no barrier, the early return stands
         __shared__ __attribute__((aligned(16))) uint8_t stage[kGemmWaves * kGemmWaves * kFusedStageBytes];
-        fused_epilogue(acc, rows_nan, cols_nan, g.bias, g.y, g.m, g.o, m0, n0, lane, f..., stage + wave * kFusedStageBytes);
+        fused_epilogue(acc, rows_nan, cols_nan, t.bias, t.c, t.m, t.n, m0, n0, lane, f..., stage + wave * kFusedStageBytes);
         return;
     }
 #pragma unroll
     for (int j = 0; j < T; j++) {
         const uint32_t col = n0 + j * kGemmTile + r;
-        if (col >= g.o) continue;
-        const float bias = g.bias != nullptr ? g.bias[col] : 0.f;
+        if (col >= t.n) continue;
+        const float bias = t.bias != nullptr ? t.bias[col] : 0.f;
         const bool col_nan = (cols_nan[j] >> r) & 1u;
 #pragma unroll
         for (int i = 0; i < T; i++) {
@@ -201,34 +164,12 @@ __global__ __launch_bounds__(kBlock) void mx_conv_kernel(const MxConvArgs g, con
             for (int q = 0; q < 4; q++) {
                 const uint32_t tr = grp * 4u + q, row = m0 + i * kGemmTile + tr;
                 const bool bad = col_nan || ((rows_nan[i] >> tr) & 1u);
-                const float v = g.bias != nullptr ? acc[i][j][q] + bias : acc[i][j][q];
-                if (row < g.m) g.y[(size_t)row * g.o + col] = bad ? __uint_as_float(0x7fc00000u) : v;
+                const float v = t.bias != nullptr ? acc[i][j][q] + bias : acc[i][j][q];
+                if (row < t.m) t.c[(size_t)row * t.n + col] = bad ? __uint_as_float(0x7fc00000u) : v;
             }
         }
     }
 }
-
-template <int FA, int FB>
-void launch(const MxConvArgs& g, const MxFusedOut* f, uint32_t blocks, hipStream_t s) {
-    if (f != nullptr) hipLaunchKernelGGL((mx_conv_kernel<FA, FB, MxFusedOut>), dim3(blocks), dim3(kBlock), 0, s, g, *f);
-    else hipLaunchKernelGGL((mx_conv_kernel<FA, FB>), dim3(blocks), dim3(kBlock), 0, s, g);
-}
-template <int FA>
-void launch_b(int fb, const MxConvArgs& g, const MxFusedOut* f, uint32_t blocks, hipStream_t s) {
-    switch (fb) {
-        case PPQHIP_MXFP8_E4M3: launch<FA, PPQHIP_MXFP8_E4M3>(g, f, blocks, s); break;
-        case PPQHIP_MXFP8_E5M2: launch<FA, PPQHIP_MXFP8_E5M2>(g, f, blocks, s); break;
-        case PPQHIP_MXFP6_E3M2: launch<FA, PPQHIP_MXFP6_E3M2>(g, f, blocks, s); break;
-        case PPQHIP_MXFP6_E2M3: launch<FA, PPQHIP_MXFP6_E2M3>(g, f, blocks, s); break;
-        default: launch<FA, PPQHIP_MXFP4_E2M1>(g, f, blocks, s); break;
-    }
-}
-
-// what a fused call adds to a plain one, as the entry point received it
-struct ConvFusedHost {
-    const float* residual; int relu;
-    uint8_t* out_elements; uint8_t* out_scales; int out_format;
-};
 
 // a * b when it stays within 2^31 - 1 (both are within it already), -1 otherwise
 int64_t bounded_product(int64_t a, int64_t b) {
@@ -240,8 +181,7 @@ int64_t bounded_product(int64_t a, int64_t b) {
 int run_conv(const char* what, const uint8_t* x_elements, const uint8_t* x_scales, int x_format, const uint8_t* w_elements,
              const uint8_t* w_scales, int w_format, const float* bias, float* y, int64_t n, int64_t c, int64_t h, int64_t w, int64_t o,
              int64_t kh, int64_t kw, int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w,
-             const ConvFusedHost* fused, void* stream) {
-
+             const MxFusedHost* fused, void* stream) {
     if (int st = check_format(what, "x", x_format)) return st;
     if (int st = check_format(what, "w", w_format)) return st;
     MxFusedOut f = {};
@@ -278,8 +218,6 @@ int run_conv(const char* what, const uint8_t* x_elements, const uint8_t* x_scale
     if (!aligned16(y) || (read_x && !aligned16(x_elements)) || (read_w && !aligned16(w_elements))) {
         set_error("%s: elements and y must be 16-byte aligned", what); return PPQHIP_ERR_INVALID_VALUE;
     }
-    const int64_t tiles_m = (m + kGemmEdge - 1) / kGemmEdge, tiles_n = (o + kGemmEdge - 1) / kGemmEdge;
-    if (tiles_m * tiles_n > kMxMax) { set_error("%s: too many workgroups in one launch", what); return PPQHIP_ERR_INVALID_VALUE; }
     std::vector<Span> ins, outs;
     if (read_x) { ins.push_back(span_of(x_elements, blocks_x * BA)); ins.push_back(span_of(x_scales, blocks_x)); }
     if (read_w) { ins.push_back(span_of(w_elements, o * nb * BB)); ins.push_back(span_of(w_scales, o * nb)); }
@@ -289,41 +227,21 @@ int run_conv(const char* what, const uint8_t* x_elements, const uint8_t* x_scale
     // 2 m o nb 32 flops
     double bytes = (double)blocks_x * (double)(BA + 1) + (double)o * (double)nb * (double)(BB + 1);
     if (y != nullptr) bytes += 4.0 * (double)m * (double)o;
-    if (fused != nullptr) {                       // and what the fused epilogue moves: the residual and the packed result
-        const int64_t nbo = (o + kMxBlock - 1) / kMxBlock, BO = 4 * (int64_t)gemm_elem_bits(fused->out_format);
-        if (m * nbo > kMxMax) { set_error("%s: more than 2^31 - 1 output blocks", what); return PPQHIP_ERR_INVALID_VALUE; }
-        if (fused->residual != nullptr) { ins.push_back(span_of(fused->residual, m * o)); bytes += 4.0 * (double)m * (double)o; }
-        if (fused->out_elements != nullptr) {
-            outs.push_back(span_of(fused->out_elements, m * nbo * BO)); outs.push_back(span_of(fused->out_scales, m * nbo));
-            bytes += (double)m * (double)nbo * (double)(BO + 1);
-        }
-        f.residual = fused->residual; f.elements = fused->out_elements; f.scales = fused->out_scales;
-        f.relu = fused->relu ? 1u : 0u; f.format = (uint32_t)fused->out_format; f.nbo = (uint32_t)nbo;
-    }
-    if (int st = check_overlap(what, ins, outs)) return st;
-
     MxConvArgs g;
-    g.xe = x_elements; g.xs = x_scales; g.we = w_elements; g.ws = w_scales; g.bias = bias; g.y = y;
-    g.m = (uint32_t)m; g.o = (uint32_t)o; g.nbc = (uint32_t)nbc;
-    g.nb = read_w ? (uint32_t)nb : 0u;
+    g.xe = x_elements; g.xs = x_scales;
+    g.t.be = w_elements; g.t.bs = w_scales; g.t.bias = bias; g.t.c = y;
+    g.t.m = (uint32_t)m; g.t.n = (uint32_t)o; g.nbc = (uint32_t)nbc;
+    g.t.nb = read_w ? (uint32_t)nb : 0u;
     g.h = (uint32_t)h; g.w = (uint32_t)w; g.kw = (uint32_t)kw;
     g.sh = (int32_t)stride_h; g.sw = (int32_t)stride_w; g.ph = (int32_t)pad_h; g.pw = (int32_t)pad_w;
     g.dh = (int32_t)dil_h; g.dw = (int32_t)dil_w;
-    g.tiles_n = make_fastdiv((uint32_t)tiles_n);
     g.ohw = make_fastdiv((uint32_t)(oh * ow)); g.ow = make_fastdiv((uint32_t)ow);
     g.fnbc = make_fastdiv((uint32_t)std::max<int64_t>(nbc, 1)); g.fkw = make_fastdiv((uint32_t)kw);
-    const uint32_t blocks = (uint32_t)(tiles_m * tiles_n);
-    hipStream_t s = (hipStream_t)stream;
-    const MxFusedOut* fp = fused != nullptr ? &f : nullptr;
-    LaunchScope scope(fused != nullptr ? K_MX_CONV_FUSED : K_MX_CONV, bytes, s);
-    switch (x_format) {
-        case PPQHIP_MXFP8_E4M3: launch_b<PPQHIP_MXFP8_E4M3>(w_format, g, fp, blocks, s); break;
-        case PPQHIP_MXFP8_E5M2: launch_b<PPQHIP_MXFP8_E5M2>(w_format, g, fp, blocks, s); break;
-        case PPQHIP_MXFP6_E3M2: launch_b<PPQHIP_MXFP6_E3M2>(w_format, g, fp, blocks, s); break;
-        case PPQHIP_MXFP6_E2M3: launch_b<PPQHIP_MXFP6_E2M3>(w_format, g, fp, blocks, s); break;
-        default: launch_b<PPQHIP_MXFP4_E2M1>(w_format, g, fp, blocks, s); break;
-    }
-    return finish_launch(what);
+    return launch_mx_tiles(what, K_MX_CONV, K_MX_CONV_FUSED, x_format, w_format, fused, f, g.t, ins, outs, bytes, stream,
+                           [&g](auto fa, auto fb, uint32_t blocks, hipStream_t s, const auto&... fo) {
+        hipLaunchKernelGGL((mx_conv_kernel<decltype(fa)::value, decltype(fb)::value, std::decay_t<decltype(fo)>...>), dim3(blocks),
+                           dim3(kBlock), 0, s, g, fo...);
+    });
 }
 
 }  // namespace
@@ -344,7 +262,7 @@ extern "C" int ppqhip_mx_conv2d_fused(const uint8_t* x_elements, const uint8_t* 
                                       uint8_t* out_elements, uint8_t* out_scales, int out_format, int64_t n, int64_t c, int64_t h,
                                       int64_t w, int64_t o, int64_t kh, int64_t kw, int64_t stride_h, int64_t stride_w, int64_t pad_h,
                                       int64_t pad_w, int64_t dil_h, int64_t dil_w, void* stream) {
-    const ConvFusedHost fused = {residual, relu, out_elements, out_scales, out_format};
+    const MxFusedHost fused = {residual, relu, out_elements, out_scales, out_format};
     return run_conv("mx_conv2d_fused", x_elements, x_scales, x_format, w_elements, w_scales, w_format, bias, y, n, c, h, w, o, kh, kw,
                     stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, &fused, stream);
 }

@@ -26,8 +26,8 @@
 // as the quiet NaN 0x7fc00000.
 // ppqhip_mx_gemm_fused runs the same K loop with the fused epilogue of mx_mfma.hpp: residual, ReLU and the result
 // packed along the output columns, in a second set of 25 instantiations; the plain kernels keep their code.
+// What the kernel shares with mx_conv_kernel is in mx_mfma.hpp; A is read as B is: a RowSource.
 #include "common.hpp"
-#include "job_table.hpp"
 #include "mx_mfma.hpp"
 
 namespace ppqhip {
@@ -35,36 +35,30 @@ namespace {
 
 struct MxGemmArgs {
     const uint8_t* ae; const uint8_t* as;         // A: elements [m, nb * BA], scales [m, nb]
-    const uint8_t* be; const uint8_t* bs;         // B: elements [n, nb * BB], scales [n, nb]
-    const float* bias;                            // [n] or null
-    float* c;                                     // [m, n]
-    uint32_t m, n, nb;
-    FastDiv tiles_n;                              // workgroups along N
+    MxTileArgs t;
 };
 
 // F is empty -- the plain kernel, (g) alone -- or one MxFusedOut: the epilogue of mx_mfma.hpp (fused_epilogue) in place of the plain
-// one, (g, f).  Everything up to the epilogue is the same code; in the fused kernel g.c may be null.
+// one, (g, f).  Everything up to the epilogue is the same code; in the fused kernel g.t.c may be null.  The text of this kernel
+// and of mx_conv_kernel (mx_conv.hip) differs in the A source alone; it stays in the kernel because the backend schedules the FP8 K loops worse
+// when it is an inlined function (profiles/mx_tile.txt).
 template <int FA, int FB, typename... F>
 __global__ __launch_bounds__(kBlock) void mx_gemm_kernel(const MxGemmArgs g, const F... f) {
     constexpr bool FUSED = sizeof...(F) != 0;
     static_assert(sizeof...(F) <= 1, "at most one MxFusedOut");
     constexpr int T = kGemmWaveTiles;
-    constexpr uint32_t BA = 4u * gemm_elem_bits(FA), BB = 4u * gemm_elem_bits(FB);
-    constexpr int HA = gemm_hw_format(FA), HB = gemm_hw_format(FB);               // immediates of the instruction
-    const uint32_t tm = fdiv(blockIdx.x, g.tiles_n), tn = blockIdx.x - tm * g.tiles_n.d;
+    const MxTileArgs& t = g.t;
+    const uint32_t tm = fdiv(blockIdx.x, t.tiles_n), tn = blockIdx.x - tm * t.tiles_n.d;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t r = lane & 15u, grp = lane >> 4;
     const uint32_t m0 = tm * kGemmEdge + (wave / kGemmWaves) * (T * kGemmTile);
     const uint32_t n0 = tn * kGemmEdge + (wave % kGemmWaves) * (T * kGemmTile);
-    if (m0 >= g.m || n0 >= g.n) return;                                          // wave-uniform; there is no barrier below
+    if (m0 >= t.m || n0 >= t.n) return;                                          // wave-uniform; there is no barrier below
 
-    const uint8_t* ae[T]; const uint8_t* as[T]; const uint8_t* be[T]; const uint8_t* bs[T];
-#pragma unroll
-    for (int t = 0; t < T; t++) {
-        const size_t row = min(m0 + t * kGemmTile + r, g.m - 1u), col = min(n0 + t * kGemmTile + r, g.n - 1u);
-        ae[t] = g.ae + row * g.nb * BA; as[t] = g.as + row * g.nb;
-        be[t] = g.be + col * g.nb * BB; bs[t] = g.bs + col * g.nb;
-    }
+    RowSource<FA> a_src{g.ae, g.as, t.m, t.nb};
+    RowSource<FB> b_src{t.be, t.bs, t.n, t.nb};
+    a_src.prepare(m0, r);
+    b_src.prepare(n0, r);
     v4f acc[T][T];
 #pragma unroll
     for (int i = 0; i < T; i++)
@@ -72,43 +66,25 @@ __global__ __launch_bounds__(kBlock) void mx_gemm_kernel(const MxGemmArgs g, con
         for (int j = 0; j < T; j++) acc[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
     uint32_t nan_a[T], nan_b[T];
 #pragma unroll
-    for (int t = 0; t < T; t++) { nan_a[t] = 0u; nan_b[t] = 0u; }
+    for (int i = 0; i < T; i++) { nan_a[i] = 0u; nan_b[i] = 0u; }
 
-    v8i a[T], b[T];
-    int sa[T], sb[T];
-    const uint32_t full = g.nb / kGemmStepBlocks;
-    for (uint32_t s = 0; s < full; s++) {
-        load_operand<FA, false>(ae, as, s * kGemmStepBlocks, grp, g.nb, a, sa, nan_a);
-        load_operand<FB, false>(be, bs, s * kGemmStepBlocks, grp, g.nb, b, sb, nan_b);
-#pragma unroll
-        for (int i = 0; i < T; i++)
-#pragma unroll
-            for (int j = 0; j < T; j++)
-                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[i], b[j], acc[i][j], HA, HB, 0, sa[i], 0, sb[j]);
-    }
-    if (g.nb % kGemmStepBlocks) {
-        load_operand<FA, true>(ae, as, full * kGemmStepBlocks, grp, g.nb, a, sa, nan_a);
-        load_operand<FB, true>(be, bs, full * kGemmStepBlocks, grp, g.nb, b, sb, nan_b);
-#pragma unroll
-        for (int i = 0; i < T; i++)
-#pragma unroll
-            for (int j = 0; j < T; j++)
-                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[i], b[j], acc[i][j], HA, HB, 0, sa[i], 0, sb[j]);
-    }
+    const uint32_t full = t.nb / kGemmStepBlocks;
+    for (uint32_t s = 0; s < full; s++) mx_tile_step<FA, FB, false>(a_src, b_src, s * kGemmStepBlocks, grp, acc, nan_a, nan_b);
+    if (t.nb % kGemmStepBlocks) mx_tile_step<FA, FB, true>(a_src, b_src, full * kGemmStepBlocks, grp, acc, nan_a, nan_b);
 
     uint32_t rows_nan[T], cols_nan[T];
 #pragma unroll
-    for (int t = 0; t < T; t++) { rows_nan[t] = tile_flags(nan_a[t]); cols_nan[t] = tile_flags(nan_b[t]); }
+    for (int i = 0; i < T; i++) { rows_nan[i] = tile_flags(nan_a[i]); cols_nan[i] = tile_flags(nan_b[i]); }
     if constexpr (FUSED) {                                                       // the stage is wave-private: no barrier, the early return stands
         __shared__ __attribute__((aligned(16))) uint8_t stage[kGemmWaves * kGemmWaves * kFusedStageBytes];
-        fused_epilogue(acc, rows_nan, cols_nan, g.bias, g.c, g.m, g.n, m0, n0, lane, f..., stage + wave * kFusedStageBytes);
+        fused_epilogue(acc, rows_nan, cols_nan, t.bias, t.c, t.m, t.n, m0, n0, lane, f..., stage + wave * kFusedStageBytes);
         return;
     }
 #pragma unroll
     for (int j = 0; j < T; j++) {
         const uint32_t col = n0 + j * kGemmTile + r;
-        if (col >= g.n) continue;
-        const float bias = g.bias != nullptr ? g.bias[col] : 0.f;
+        if (col >= t.n) continue;
+        const float bias = t.bias != nullptr ? t.bias[col] : 0.f;
         const bool col_nan = (cols_nan[j] >> r) & 1u;
 #pragma unroll
         for (int i = 0; i < T; i++) {
@@ -116,38 +92,16 @@ __global__ __launch_bounds__(kBlock) void mx_gemm_kernel(const MxGemmArgs g, con
             for (int q = 0; q < 4; q++) {
                 const uint32_t tr = grp * 4u + q, row = m0 + i * kGemmTile + tr;
                 const bool bad = col_nan || ((rows_nan[i] >> tr) & 1u);
-                const float v = g.bias != nullptr ? acc[i][j][q] + bias : acc[i][j][q];
-                if (row < g.m) g.c[(size_t)row * g.n + col] = bad ? __uint_as_float(0x7fc00000u) : v;
+                const float v = t.bias != nullptr ? acc[i][j][q] + bias : acc[i][j][q];
+                if (row < t.m) t.c[(size_t)row * t.n + col] = bad ? __uint_as_float(0x7fc00000u) : v;
             }
         }
     }
 }
 
-template <int FA, int FB>
-void launch(const MxGemmArgs& g, const MxFusedOut* f, uint32_t blocks, hipStream_t s) {
-    if (f != nullptr) hipLaunchKernelGGL((mx_gemm_kernel<FA, FB, MxFusedOut>), dim3(blocks), dim3(kBlock), 0, s, g, *f);
-    else hipLaunchKernelGGL((mx_gemm_kernel<FA, FB>), dim3(blocks), dim3(kBlock), 0, s, g);
-}
-template <int FA>
-void launch_b(int fb, const MxGemmArgs& g, const MxFusedOut* f, uint32_t blocks, hipStream_t s) {
-    switch (fb) {
-        case PPQHIP_MXFP8_E4M3: launch<FA, PPQHIP_MXFP8_E4M3>(g, f, blocks, s); break;
-        case PPQHIP_MXFP8_E5M2: launch<FA, PPQHIP_MXFP8_E5M2>(g, f, blocks, s); break;
-        case PPQHIP_MXFP6_E3M2: launch<FA, PPQHIP_MXFP6_E3M2>(g, f, blocks, s); break;
-        case PPQHIP_MXFP6_E2M3: launch<FA, PPQHIP_MXFP6_E2M3>(g, f, blocks, s); break;
-        default: launch<FA, PPQHIP_MXFP4_E2M1>(g, f, blocks, s); break;
-    }
-}
-
-// what a fused call adds to a plain one, as the entry point received it
-struct GemmFusedHost {
-    const float* residual; int relu;
-    uint8_t* out_elements; uint8_t* out_scales; int out_format;
-};
-
 // both entry points; `fused` is null for ppqhip_mx_gemm, whose checks, strings and launch are unchanged
 int run_gemm(const char* what, const uint8_t* a_elements, const uint8_t* a_scales, int a_format, const uint8_t* b_elements,
-             const uint8_t* b_scales, int b_format, const float* bias, float* c, int64_t m, int64_t n, int64_t k, const GemmFusedHost* fused,
+             const uint8_t* b_scales, int b_format, const float* bias, float* c, int64_t m, int64_t n, int64_t k, const MxFusedHost* fused,
              void* stream) {
     if (int st = check_format(what, "A", a_format)) return st;
     if (int st = check_format(what, "B", b_format)) return st;
@@ -166,8 +120,6 @@ int run_gemm(const char* what, const uint8_t* a_elements, const uint8_t* a_scale
     if (!aligned16(c) || (nb > 0 && (!aligned16(a_elements) || !aligned16(b_elements)))) {
         set_error("%s: elements and c must be 16-byte aligned", what); return PPQHIP_ERR_INVALID_VALUE;
     }
-    const int64_t tiles_m = (m + kGemmEdge - 1) / kGemmEdge, tiles_n = (n + kGemmEdge - 1) / kGemmEdge;
-    if (tiles_m * tiles_n > kMxMax) { set_error("%s: too many workgroups in one launch", what); return PPQHIP_ERR_INVALID_VALUE; }
     std::vector<Span> ins, outs;
     if (nb > 0) {
         ins.push_back(span_of(a_elements, m * nb * BA)); ins.push_back(span_of(a_scales, m * nb));
@@ -178,35 +130,16 @@ int run_gemm(const char* what, const uint8_t* a_elements, const uint8_t* a_scale
     // booked: the operands and 4 m n bytes of C; the launch does 2 m n nb 32 flops
     double bytes = (double)m * (double)nb * (double)(BA + 1) + (double)n * (double)nb * (double)(BB + 1);
     if (c != nullptr) bytes += 4.0 * (double)m * (double)n;
-    if (fused != nullptr) {                       // and what the fused epilogue moves: the residual and the packed result
-        const int64_t nbo = (n + kMxBlock - 1) / kMxBlock, BO = 4 * (int64_t)gemm_elem_bits(fused->out_format);
-        if (m * nbo > kMxMax) { set_error("%s: more than 2^31 - 1 output blocks", what); return PPQHIP_ERR_INVALID_VALUE; }
-        if (fused->residual != nullptr) { ins.push_back(span_of(fused->residual, m * n)); bytes += 4.0 * (double)m * (double)n; }
-        if (fused->out_elements != nullptr) {
-            outs.push_back(span_of(fused->out_elements, m * nbo * BO)); outs.push_back(span_of(fused->out_scales, m * nbo));
-            bytes += (double)m * (double)nbo * (double)(BO + 1);
-        }
-        f.residual = fused->residual; f.elements = fused->out_elements; f.scales = fused->out_scales;
-        f.relu = fused->relu ? 1u : 0u; f.format = (uint32_t)fused->out_format; f.nbo = (uint32_t)nbo;
-    }
-    if (int st = check_overlap(what, ins, outs)) return st;
 
     MxGemmArgs g;
-    g.ae = a_elements; g.as = a_scales; g.be = b_elements; g.bs = b_scales; g.bias = bias; g.c = c;
-    g.m = (uint32_t)m; g.n = (uint32_t)n; g.nb = (uint32_t)nb;
-    g.tiles_n = make_fastdiv((uint32_t)tiles_n);
-    const uint32_t blocks = (uint32_t)(tiles_m * tiles_n);
-    hipStream_t s = (hipStream_t)stream;
-    const MxFusedOut* fp = fused != nullptr ? &f : nullptr;
-    LaunchScope scope(fused != nullptr ? K_MX_GEMM_FUSED : K_MX_GEMM, bytes, s);
-    switch (a_format) {
-        case PPQHIP_MXFP8_E4M3: launch_b<PPQHIP_MXFP8_E4M3>(b_format, g, fp, blocks, s); break;
-        case PPQHIP_MXFP8_E5M2: launch_b<PPQHIP_MXFP8_E5M2>(b_format, g, fp, blocks, s); break;
-        case PPQHIP_MXFP6_E3M2: launch_b<PPQHIP_MXFP6_E3M2>(b_format, g, fp, blocks, s); break;
-        case PPQHIP_MXFP6_E2M3: launch_b<PPQHIP_MXFP6_E2M3>(b_format, g, fp, blocks, s); break;
-        default: launch_b<PPQHIP_MXFP4_E2M1>(b_format, g, fp, blocks, s); break;
-    }
-    return finish_launch(what);
+    g.ae = a_elements; g.as = a_scales;
+    g.t.be = b_elements; g.t.bs = b_scales; g.t.bias = bias; g.t.c = c;
+    g.t.m = (uint32_t)m; g.t.n = (uint32_t)n; g.t.nb = (uint32_t)nb;
+    return launch_mx_tiles(what, K_MX_GEMM, K_MX_GEMM_FUSED, a_format, b_format, fused, f, g.t, ins, outs, bytes, stream,
+                           [&g](auto fa, auto fb, uint32_t blocks, hipStream_t s, const auto&... fo) {
+        hipLaunchKernelGGL((mx_gemm_kernel<decltype(fa)::value, decltype(fb)::value, std::decay_t<decltype(fo)>...>), dim3(blocks),
+                           dim3(kBlock), 0, s, g, fo...);
+    });
 }
 
 }  // namespace
@@ -224,6 +157,6 @@ extern "C" int ppqhip_mx_gemm_fused(const uint8_t* a_elements, const uint8_t* a_
                                     const uint8_t* b_scales, int b_format, const float* bias, const float* residual, int relu, float* c,
                                     uint8_t* out_elements, uint8_t* out_scales, int out_format, int64_t m, int64_t n, int64_t k,
                                     void* stream) {
-    const GemmFusedHost fused = {residual, relu, out_elements, out_scales, out_format};
+    const MxFusedHost fused = {residual, relu, out_elements, out_scales, out_format};
     return run_gemm("mx_gemm_fused", a_elements, a_scales, a_format, b_elements, b_scales, b_format, bias, c, m, n, k, &fused, stream);
 }

@@ -1,10 +1,14 @@
 // mx_mfma.hpp -- what the kernels on the block-scaled MFMA of gfx950 (v_mfma_scale_f32_16x16x128_f8f6f4) share: mx_gemm.hip and
 // mx_conv.hip.  The workgroup shape, the instruction's format ids, how a lane's operand registers and scale byte are read from an
-// operand packed along its last axis (DESIGN.md sections 9.13, 9.14), the NaN flags, the format check of the entry points and the fused
-// epilogue (residual, ReLU, MX re-quantisation of the result; section 9.16).
+// operand packed along its last axis (DESIGN.md sections 9.13, 9.14), the NaN flags, the A / B operand sources and the K-step (section
+// 4.4), the fused epilogue (residual, ReLU, MX re-quantisation of the result; section 9.16) and the host frame of the entry points: the
+// format check, the fused accounting, the format dispatch and the launch.
 #pragma once
 
+#include <type_traits>
+
 #include "common.hpp"
+#include "job_table.hpp"
 #include "mx_coder.hpp"
 #include "mx_common.hpp"
 
@@ -35,40 +39,61 @@ __device__ __forceinline__ uint32_t fp8_nan_bits(uint32_t w) {
     return ((w & 0x7f7f7f7fu) + (F == PPQHIP_MXFP8_E4M3 ? 0x01010101u : 0x03030303u)) & 0x80808080u;
 }
 
-// The lane's operand registers of format F for K-step `kb0 / 4` of the row that starts at e: FP6 / FP4 lanes hold block kb0 + grp,
-// its bytes in the low dwords; an FP8 lane holds bytes [16 (grp & 1), + 16) of block kb0 + (grp >> 1) in dwords 0 .. 3 and the same
-// bytes of block kb0 + 2 + (grp >> 1) in dwords 4 .. 7.  TAIL: a block at or past nb is not read (the load is clamped) and gives zeros.
+// ---- a lane's operand registers ------------------------------------------------------------------------------------------------------
+// The register layout of a fragment, once.  Whoever calls these computes addresses and liveness: the load is always issued, from
+// an address that is readable, and zeros are selected afterwards where the block is not live -- that is what makes padding, and
+// blocks past nb, safe to "read".
+// FP8: bytes [16 (grp & 1), + 16) of block kb0 + (grp >> 1) at p0 in dwords 0 .. 3, the same bytes of block kb0 + 2 + (grp >> 1) at p1
+// in dwords 4 .. 7.
+__device__ __forceinline__ v8i fp8_fragment(const uint8_t* p0, const uint8_t* p1, bool live0, bool live1) {
+    uint4 lo = *reinterpret_cast<const uint4*>(p0), hi = *reinterpret_cast<const uint4*>(p1);
+    if (!live0) lo = make_uint4(0u, 0u, 0u, 0u);
+    if (!live1) hi = make_uint4(0u, 0u, 0u, 0u);
+    return v8i{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
+}
+// FP6 / FP4: the 24 / 16 bytes of block kb0 + grp at p in the low dwords
+template <int F>
+__device__ __forceinline__ v8i block_fragment(const uint8_t* p, bool live) {
+    v8i r = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (gemm_elem_bits(F) == 6u) {                                               // 24-B blocks are 8-B aligned
+        const uint2 t0 = *reinterpret_cast<const uint2*>(p), t1 = *reinterpret_cast<const uint2*>(p + 8), t2 = *reinterpret_cast<const uint2*>(p + 16);
+        r[0] = (int)t0.x; r[1] = (int)t0.y; r[2] = (int)t1.x; r[3] = (int)t1.y; r[4] = (int)t2.x; r[5] = (int)t2.y;
+    } else {
+        const uint4 lo = *reinterpret_cast<const uint4*>(p);
+        r[0] = (int)lo.x; r[1] = (int)lo.y; r[2] = (int)lo.z; r[3] = (int)lo.w;
+    }
+    return live ? r : v8i{0, 0, 0, 0, 0, 0, 0, 0};
+}
+// the lane's NaN flag takes the scale code 0xFF and the FP8 NaN codes it has loaded
+template <int F>
+__device__ __forceinline__ void flag_nan(const v8i (&frag)[kGemmWaveTiles], const int (&scale)[kGemmWaveTiles], uint32_t (&nan)[kGemmWaveTiles]) {
+#pragma unroll
+    for (int t = 0; t < kGemmWaveTiles; t++) {
+        uint32_t bad = scale[t] == 0xff ? 1u : 0u;
+        if (F == PPQHIP_MXFP8_E4M3 || F == PPQHIP_MXFP8_E5M2) {
+#pragma unroll
+            for (int w = 0; w < 8; w++) bad |= fp8_nan_bits<F>((uint32_t)frag[t][w]);
+        }
+        nan[t] |= bad;
+    }
+}
+
+// The lane's operand registers of format F for K-step `kb0 / 4` of the row that starts at e.  TAIL: a block at or past nb is not
+// read (the load is clamped) and gives zeros.
 template <int F, bool TAIL>
 __device__ __forceinline__ v8i load_fragment(const uint8_t* e, uint32_t kb0, uint32_t grp, uint32_t nb) {
     constexpr uint32_t bits = gemm_elem_bits(F);
-    v8i r = {0, 0, 0, 0, 0, 0, 0, 0};
     if (bits == 8u) {
         const uint32_t b0 = kb0 + (grp >> 1), b1 = b0 + 2u, half = 16u * (grp & 1u);
-        const bool live0 = !TAIL || b0 < nb, live1 = !TAIL || b1 < nb;
-        uint4 lo = *reinterpret_cast<const uint4*>(e + (size_t)(TAIL ? min(b0, nb - 1u) : b0) * 32u + half);
-        uint4 hi = *reinterpret_cast<const uint4*>(e + (size_t)(TAIL ? min(b1, nb - 1u) : b1) * 32u + half);
-        if (!live0) lo = make_uint4(0u, 0u, 0u, 0u);
-        if (!live1) hi = make_uint4(0u, 0u, 0u, 0u);
-        r[0] = (int)lo.x; r[1] = (int)lo.y; r[2] = (int)lo.z; r[3] = (int)lo.w;
-        r[4] = (int)hi.x; r[5] = (int)hi.y; r[6] = (int)hi.z; r[7] = (int)hi.w;
-    } else {
-        const uint32_t kb = kb0 + grp;
-        const bool live = !TAIL || kb < nb;
-        const uint8_t* p = e + (size_t)(TAIL ? min(kb, nb - 1u) : kb) * (4u * bits);
-        if (bits == 6u) {                                                        // 24-B blocks are 8-B aligned
-            const uint2 t0 = *reinterpret_cast<const uint2*>(p), t1 = *reinterpret_cast<const uint2*>(p + 8), t2 = *reinterpret_cast<const uint2*>(p + 16);
-            r[0] = (int)t0.x; r[1] = (int)t0.y; r[2] = (int)t1.x; r[3] = (int)t1.y; r[4] = (int)t2.x; r[5] = (int)t2.y;
-        } else {
-            const uint4 lo = *reinterpret_cast<const uint4*>(p);
-            r[0] = (int)lo.x; r[1] = (int)lo.y; r[2] = (int)lo.z; r[3] = (int)lo.w;
-        }
-        if (!live) r = v8i{0, 0, 0, 0, 0, 0, 0, 0};
+        return fp8_fragment(e + (size_t)(TAIL ? min(b0, nb - 1u) : b0) * 32u + half, e + (size_t)(TAIL ? min(b1, nb - 1u) : b1) * 32u + half,
+                            !TAIL || b0 < nb, !TAIL || b1 < nb);
     }
-    return r;
+    const uint32_t kb = kb0 + grp;
+    return block_fragment<F>(e + (size_t)(TAIL ? min(kb, nb - 1u) : kb) * (4u * bits), !TAIL || kb < nb);
 }
 
 // one operand's fragments of a K-step: for each of the wave's kGemmWaveTiles rows (columns) of this lane, the registers above and the
-// scale code of block kb0 + grp (127 past nb).  The lane's NaN flag takes the scale code 0xFF and the FP8 NaN codes it has loaded.
+// scale code of block kb0 + grp (127 past nb)
 template <int F, bool TAIL>
 __device__ __forceinline__ void load_operand(const uint8_t* const (&e)[kGemmWaveTiles], const uint8_t* const (&s)[kGemmWaveTiles], uint32_t kb0,
                                              uint32_t grp, uint32_t nb, v8i (&frag)[kGemmWaveTiles], int (&scale)[kGemmWaveTiles],
@@ -81,16 +106,33 @@ __device__ __forceinline__ void load_operand(const uint8_t* const (&e)[kGemmWave
         scale[t] = (int)s[t][TAIL ? min(kb, nb - 1u) : kb];
     }
 #pragma unroll
-    for (int t = 0; t < kGemmWaveTiles; t++) {
+    for (int t = 0; t < kGemmWaveTiles; t++)
         if (!live) scale[t] = 127;
-        uint32_t bad = scale[t] == 0xff ? 1u : 0u;
-        if (F == PPQHIP_MXFP8_E4M3 || F == PPQHIP_MXFP8_E5M2) {
-#pragma unroll
-            for (int w = 0; w < 8; w++) bad |= fp8_nan_bits<F>((uint32_t)frag[t][w]);
-        }
-        nan[t] |= bad;
-    }
+    flag_nan<F>(frag, scale, nan);
 }
+
+// An operand source of a kernel does two things: prepare(m0, r) once, for the wave's kGemmWaveTiles rows
+// m0 + 16 t + r of this lane, and load<TAIL>(kb0, grp, frag, scale, nan) per K-step.  This one is an operand packed along its last
+// axis, [rows, nb * B] / [rows, nb]: A of mx_gemm.hip, and B of every kernel.  Rows past the last are clamped.
+template <int F>
+struct RowSource {
+    const uint8_t* elements; const uint8_t* scales;
+    uint32_t rows, nb;
+    const uint8_t* e[kGemmWaveTiles]; const uint8_t* s[kGemmWaveTiles];           // the lane's rows, set by prepare
+
+    __device__ __forceinline__ void prepare(uint32_t m0, uint32_t r) {
+#pragma unroll
+        for (int t = 0; t < kGemmWaveTiles; t++) {
+            const size_t row = min(m0 + t * kGemmTile + r, rows - 1u);
+            e[t] = elements + row * nb * (4u * gemm_elem_bits(F)); s[t] = scales + row * nb;
+        }
+    }
+    template <bool TAIL>
+    __device__ __forceinline__ void load(uint32_t kb0, uint32_t grp, v8i (&frag)[kGemmWaveTiles], int (&scale)[kGemmWaveTiles],
+                                         uint32_t (&nan)[kGemmWaveTiles]) const {
+        load_operand<F, TAIL>(e, s, kb0, grp, nb, frag, scale, nan);
+    }
+};
 
 // the flags of the 16 rows (columns) of a tile from the lanes' own: a row is owned by the four lanes r, r + 16, r + 32, r + 48
 __device__ __forceinline__ uint32_t tile_flags(uint32_t lane_flag) {
@@ -203,6 +245,41 @@ __device__ __forceinline__ void fused_epilogue(const v4f (&acc)[kGemmWaveTiles][
     }
 }
 
+// ---- what the kernels' bodies share ----------------------------------------------------------------------
+// What every kernel on this instruction computes C[m, n] = A . B^T (+ bias) with: B packed along its last axis, the output, the
+// sizes and the workgroup grid.  A kernel's own argument struct holds this beside whatever its A source reads.
+struct MxTileArgs {
+    const uint8_t* be; const uint8_t* bs;         // B: elements [n, nb * BB], scales [n, nb]
+    const float* bias;                            // [n] or null
+    float* c;                                     // [m, n]; may be null in a fused launch
+    uint32_t m, n, nb;                            // nb: MX blocks of one row of A and of B
+    FastDiv tiles_n;                              // workgroups along n
+};
+
+// one K-step: both operands' fragments, then the wave's kGemmWaveTiles^2 instructions
+template <int FA, int FB, bool TAIL, typename A>
+__device__ __forceinline__ void mx_tile_step(const A& a_src, const RowSource<FB>& b_src, uint32_t kb0, uint32_t grp,
+                                             v4f (&acc)[kGemmWaveTiles][kGemmWaveTiles], uint32_t (&nan_a)[kGemmWaveTiles],
+                                             uint32_t (&nan_b)[kGemmWaveTiles]) {
+    constexpr int HA = gemm_hw_format(FA), HB = gemm_hw_format(FB);               // immediates of the instruction
+    v8i a[kGemmWaveTiles], b[kGemmWaveTiles];
+    int sa[kGemmWaveTiles], sb[kGemmWaveTiles];
+    a_src.template load<TAIL>(kb0, grp, a, sa, nan_a);
+    b_src.template load<TAIL>(kb0, grp, b, sb, nan_b);
+#pragma unroll
+    for (int i = 0; i < kGemmWaveTiles; i++)
+#pragma unroll
+        for (int j = 0; j < kGemmWaveTiles; j++)
+            acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[i], b[j], acc[i][j], HA, HB, 0, sa[i], 0, sb[j]);
+}
+
+// ---- the host frame of the entry points --------------------------------------------------------------------------------------------
+// what a fused call adds to a plain one, as the entry point received it
+struct MxFusedHost {
+    const float* residual; int relu;
+    uint8_t* out_elements; uint8_t* out_scales; int out_format;
+};
+
 // the host side of MxFusedOut: what both fused entry points check about the outputs before anything else of theirs; fills *fmt
 inline int check_fused_outputs(const char* what, const char* float_name, const float* c, const uint8_t* out_elements, const uint8_t* out_scales,
                                int out_format, MxFmt* fmt) {
@@ -220,6 +297,60 @@ inline int check_format(const char* what, const char* operand, int format) {
     if (format == PPQHIP_MXINT8) { set_error("%s: %s: MXINT8 is not an operand type of the scaled MFMA", what, operand); return PPQHIP_ERR_INVALID_VALUE; }
     if (format < PPQHIP_MXFP8_E4M3 || format > PPQHIP_MXFP4_E2M1) { set_error("%s: %s: unknown MX format %d", what, operand, format); return PPQHIP_ERR_INVALID_VALUE; }
     return PPQHIP_OK;
+}
+
+// what the fused epilogue of an [m, n] result moves beyond the plain launch: the residual and the packed result join the spans
+// and the booked bytes, and f is filled (f.fmt is check_fused_outputs')
+inline int book_fused(const char* what, const MxFusedHost& fused, int64_t m, int64_t n, std::vector<Span>& ins, std::vector<Span>& outs,
+                      double& bytes, MxFusedOut& f) {
+    const int64_t nbo = (n + kMxBlock - 1) / kMxBlock, BO = 4 * (int64_t)gemm_elem_bits(fused.out_format);
+    if (m * nbo > kMxMax) { set_error("%s: more than 2^31 - 1 output blocks", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (fused.residual != nullptr) { ins.push_back(span_of(fused.residual, m * n)); bytes += 4.0 * (double)m * (double)n; }
+    if (fused.out_elements != nullptr) {
+        outs.push_back(span_of(fused.out_elements, m * nbo * BO)); outs.push_back(span_of(fused.out_scales, m * nbo));
+        bytes += (double)m * (double)nbo * (double)(BO + 1);
+    }
+    f.residual = fused.residual; f.elements = fused.out_elements; f.scales = fused.out_scales;
+    f.relu = fused.relu ? 1u : 0u; f.format = (uint32_t)fused.out_format; f.nbo = (uint32_t)nbo;
+    return PPQHIP_OK;
+}
+
+// fn(std::integral_constant<int, F>) for the operand format `format`, which check_format has let through
+template <typename Fn>
+inline void with_mx_format(int format, Fn&& fn) {
+    switch (format) {
+        case PPQHIP_MXFP8_E4M3: fn(std::integral_constant<int, PPQHIP_MXFP8_E4M3>{}); break;
+        case PPQHIP_MXFP8_E5M2: fn(std::integral_constant<int, PPQHIP_MXFP8_E5M2>{}); break;
+        case PPQHIP_MXFP6_E3M2: fn(std::integral_constant<int, PPQHIP_MXFP6_E3M2>{}); break;
+        case PPQHIP_MXFP6_E2M3: fn(std::integral_constant<int, PPQHIP_MXFP6_E2M3>{}); break;
+        default: fn(std::integral_constant<int, PPQHIP_MXFP4_E2M1>{}); break;
+    }
+}
+
+// The launch of an entry point, from its grid check on: `ins`, `outs` and `bytes` are the plain launch's, `fused` is null for
+// it, and t holds everything but tiles_n.  launch(FA, FB, blocks, stream, f...) starts the kernel of formats FA::value, FB::value on
+// `blocks` workgroups: the plain one without f, the fused one with the MxFusedOut.
+template <typename Launch>
+inline int launch_mx_tiles(const char* what, KernelId plain_id, KernelId fused_id, int a_format, int b_format, const MxFusedHost* fused,
+                           MxFusedOut& f, MxTileArgs& t, std::vector<Span>& ins, std::vector<Span>& outs, double bytes, void* stream,
+                           Launch&& launch) {
+    const int64_t tiles_m = ((int64_t)t.m + kGemmEdge - 1) / kGemmEdge, tiles_n = ((int64_t)t.n + kGemmEdge - 1) / kGemmEdge;
+    if (tiles_m * tiles_n > kMxMax) { set_error("%s: too many workgroups in one launch", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (fused != nullptr) {
+        if (int st = book_fused(what, *fused, t.m, t.n, ins, outs, bytes, f)) return st;
+    }
+    if (int st = check_overlap(what, ins, outs)) return st;
+    t.tiles_n = make_fastdiv((uint32_t)tiles_n);
+    const uint32_t blocks = (uint32_t)(tiles_m * tiles_n);
+    hipStream_t s = (hipStream_t)stream;
+    LaunchScope scope(fused != nullptr ? fused_id : plain_id, bytes, s);
+    with_mx_format(a_format, [&](auto fa) {
+        with_mx_format(b_format, [&](auto fb) {
+            if (fused != nullptr) launch(fa, fb, blocks, s, f);
+            else launch(fa, fb, blocks, s);
+        });
+    });
+    return finish_launch(what);
 }
 
 }  // namespace ppqhip

@@ -1199,28 +1199,45 @@ def mx_packed_shapes(shape, axis: int, format):
     return lead + [nb * mx_block_bytes(format)], lead + [nb]
 
 
+def _ptr(t) -> int: return t.data_ptr() if t is not None else 0                          # the address of a tensor, 0 for None
+
+
+def _mx_operand_args(rank, size, operands, shapes, bias):
+    """The operand checks of the MX MFMA bindings at rank 2 (matmul) or 4 (conv).  ``operands``: (name, elements, scales, format id)
+    each; ``shapes()``: their logical shapes, packed along axis 1, whose length ``size`` names (``'k'``) -- asked for once dtype,
+    rank and device are known.  The bias has one entry per row of the last operand.  Returns the tensors as the kernel takes them,
+    [elements, scales] of each operand in turn, the bias and the shapes."""
+    dev = operands[0][1].device
+    for op, e, s, _ in operands:
+        for kind, t in (('elements', e), ('scales', s)):
+            if isinstance(t, torch.Tensor) and t.dtype is torch.uint8 and t.is_cuda and t.dim() == rank and t.device == dev and t.numel(): continue
+            _check(t, torch.uint8, f'{op} {kind}(Expect to be UINT8)')                   # not the common case: name what is wrong
+            if t.dim() != rank: raise RuntimeError(_KERNEL_FAILURE + f'{op} {kind} must be {rank}-d, got {list(t.shape)}')
+            if t.device != dev: raise RuntimeError(_KERNEL_FAILURE + f'{op} {kind} is on another device')
+    shapes, out = shapes(), []
+    for (name, e, s, fmt), shape in zip(operands, shapes):
+        eshape, sshape = mx_packed_shapes(shape, 1, fmt)
+        if list(e.shape) != eshape or list(s.shape) != sshape:
+            raise RuntimeError(_KERNEL_FAILURE + f'{name}: elements / scales of shape {list(e.shape)} / {list(s.shape)}, expected {eshape} / {sshape} for {size} = {shape[1]}')
+        e = e.contiguous()
+        out += [e.clone() if e.data_ptr() % 16 else e, s.contiguous()]                   # the kernel's 16-byte loads; the allocator aligns
+    if bias is not None:
+        n = shapes[-1][0]
+        _f32(bias, 'Bias')
+        if list(bias.shape) != [n]: raise RuntimeError(_KERNEL_FAILURE + f'bias of shape {list(bias.shape)}, expected [{n}]')
+        if bias.device != dev: raise RuntimeError(_KERNEL_FAILURE + 'bias is on another device')
+        bias = bias.contiguous()
+    return out, bias, shapes
+
+
 def _mx_matmul_args(a_elements, a_scales, a_format, b_elements, b_scales, b_format, k, bias):
     """The checks of ``CUDA.MXMatmul`` / ``MXMatmulFused``; returns the tensors as the kernel takes them, the format ids, k, M and N."""
     fa, fb = mx_format_id(a_format), mx_format_id(b_format)
     k = int(k)
     if k <= 0: raise RuntimeError(_KERNEL_FAILURE + f'k must be positive, got {k}')
-    for name, t in (('A elements', a_elements), ('A scales', a_scales), ('B elements', b_elements), ('B scales', b_scales)):
-        _check(t, torch.uint8, name + '(Expect to be UINT8)')
-        if t.dim() != 2: raise RuntimeError(_KERNEL_FAILURE + f'{name} must be 2-d, got {list(t.shape)}')
-        if t.device != a_elements.device: raise RuntimeError(_KERNEL_FAILURE + f'{name} is on another device')
-    m, n = a_elements.shape[0], b_elements.shape[0]
-    for name, e, s, rows, fmt in (('A', a_elements, a_scales, m, fa), ('B', b_elements, b_scales, n, fb)):
-        eshape, sshape = mx_packed_shapes([rows, k], 1, fmt)
-        if list(e.shape) != eshape or list(s.shape) != sshape:
-            raise RuntimeError(_KERNEL_FAILURE + f'{name}: elements / scales of shape {list(e.shape)} / {list(s.shape)}, expected {eshape} / {sshape} for k = {k}')
-    if bias is not None:
-        _f32(bias, 'Bias')
-        if list(bias.shape) != [n]: raise RuntimeError(_KERNEL_FAILURE + f'bias of shape {list(bias.shape)}, expected [{n}]')
-        if bias.device != a_elements.device: raise RuntimeError(_KERNEL_FAILURE + 'bias is on another device')
-        bias = bias.contiguous()
-    a_elements, a_scales, b_elements, b_scales = a_elements.contiguous(), a_scales.contiguous(), b_elements.contiguous(), b_scales.contiguous()
-    if a_elements.data_ptr() % 16: a_elements = a_elements.clone()                   # the kernel's 16-byte loads; the allocator aligns
-    if b_elements.data_ptr() % 16: b_elements = b_elements.clone()
+    (a_elements, a_scales, b_elements, b_scales), bias, ((m, _), (n, _)) = _mx_operand_args(
+        2, 'k', (('A', a_elements, a_scales, fa), ('B', b_elements, b_scales, fb)),
+        lambda: ([a_elements.shape[0], k], [b_elements.shape[0], k]), bias)
     return a_elements, a_scales, fa, b_elements, b_scales, fb, k, bias, m, n
 
 
@@ -1230,29 +1247,15 @@ def _mx_conv_args(x_elements, x_scales, x_format, w_elements, w_scales, w_format
     fx, fw = mx_format_id(x_format), mx_format_id(w_format)
     c = int(c)
     if c <= 0: raise RuntimeError(_KERNEL_FAILURE + f'c must be positive, got {c}')
-    for name, t in (('x elements', x_elements), ('x scales', x_scales), ('w elements', w_elements), ('w scales', w_scales)):
-        _check(t, torch.uint8, name + '(Expect to be UINT8)')
-        if t.dim() != 4: raise RuntimeError(_KERNEL_FAILURE + f'{name} must be 4-d, got {list(t.shape)}')
-        if t.device != x_elements.device: raise RuntimeError(_KERNEL_FAILURE + f'{name} is on another device')
-    (n, h, w), (o, kh, kw) = x_scales.shape[:3], w_scales.shape[:3]
-    for name, e, s, shape, fmt in (('x', x_elements, x_scales, [n, c, h, w], fx), ('w', w_elements, w_scales, [o, c, kh, kw], fw)):
-        eshape, sshape = mx_packed_shapes(shape, 1, fmt)
-        if list(e.shape) != eshape or list(s.shape) != sshape:
-            raise RuntimeError(_KERNEL_FAILURE + f'{name}: elements / scales of shape {list(e.shape)} / {list(s.shape)}, expected {eshape} / {sshape} for c = {c}')
+    (x_elements, x_scales, w_elements, w_scales), bias, ((n, _, h, w), (o, _, kh, kw)) = _mx_operand_args(
+        4, 'c', (('x', x_elements, x_scales, fx), ('w', w_elements, w_scales, fw)),
+        lambda: [[v[0], c, v[1], v[2]] for v in (x_scales.shape, w_scales.shape)], bias)
     (sh, sw), (ph, pw), (dh, dw) = ([int(v) for v in pair] for pair in (stride, padding, dilation))
     if min(sh, sw, dh, dw) < 1 or min(ph, pw) < 0:
         raise RuntimeError(_KERNEL_FAILURE + f'stride {(sh, sw)} and dilation {(dh, dw)} must be at least 1, padding {(ph, pw)} at least 0')
     oh, ow = (h + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (w + 2 * pw - dw * (kw - 1) - 1) // sw + 1
     if oh < 1 or ow < 1:
         raise RuntimeError(_KERNEL_FAILURE + f'a {kh} x {kw} kernel with dilation {(dh, dw)} does not fit an input of {h} x {w} padded by {(ph, pw)}')
-    if bias is not None:
-        _f32(bias, 'Bias')
-        if list(bias.shape) != [o]: raise RuntimeError(_KERNEL_FAILURE + f'bias of shape {list(bias.shape)}, expected [{o}]')
-        if bias.device != x_elements.device: raise RuntimeError(_KERNEL_FAILURE + 'bias is on another device')
-        bias = bias.contiguous()
-    x_elements, x_scales, w_elements, w_scales = x_elements.contiguous(), x_scales.contiguous(), w_elements.contiguous(), w_scales.contiguous()
-    if x_elements.data_ptr() % 16: x_elements = x_elements.clone()                   # the kernel's 16-byte loads; the allocator aligns
-    if w_elements.data_ptr() % 16: w_elements = w_elements.clone()
     return x_elements, x_scales, fx, w_elements, w_scales, fw, bias, (n, c, h, w, o, kh, kw, sh, sw, ph, pw, dh, dw, oh, ow)
 
 
@@ -1268,6 +1271,15 @@ def _mx_fused_args(out_format, out_float, residual, shape, device):
         if residual.device != device: raise RuntimeError(_KERNEL_FAILURE + 'residual is on another device')
         if len(shape) == 2: residual = residual.contiguous()
     return fo, residual
+
+
+def _mx_fused_outputs(shape, fo, out_format, out_float, device):
+    """The outputs of a fused binding for a result of ``shape`` packed along axis 1: the float32 tensor with that axis last, or
+    None, and the packed pair, or None, None."""
+    out = torch.empty(shape[:1] + shape[2:] + shape[1:2], dtype=torch.float32, device=device) if out_float else None
+    if out_format is None: return out, None, None
+    eshape, sshape = mx_packed_shapes(shape, 1, fo)
+    return out, torch.empty(eshape, dtype=torch.uint8, device=device), torch.empty(sshape, dtype=torch.uint8, device=device)
 
 
 class MXPackPlan:
@@ -2394,7 +2406,7 @@ class CUDA:
             codes = scale_codes if scale_codes.stride() == _mx_codes_like(v, axis, codes_shape).stride() else _mx_codes_like(v, axis, codes_shape)
         out = torch.empty_like(v)
         with _DeviceOf(v):
-            _raise(lib.ppqhip_mx_fq(v.data_ptr(), out.data_ptr(), codes.data_ptr() if codes is not None else 0, outer, length, inner,
+            _raise(lib.ppqhip_mx_fq(v.data_ptr(), out.data_ptr(), _ptr(codes), outer, length, inner,
                                     fmt, _stream()))
         if codes is not None and codes is not scale_codes: scale_codes.copy_(codes)
         return out
@@ -2460,7 +2472,7 @@ class CUDA:
         out = torch.empty([m, n], dtype=torch.float32, device=a_elements.device)
         with _DeviceOf(out):
             _raise(lib.ppqhip_mx_gemm(a_elements.data_ptr(), a_scales.data_ptr(), fa, b_elements.data_ptr(), b_scales.data_ptr(), fb,
-                                      bias.data_ptr() if bias is not None else 0, out.data_ptr(), m, n, k, _stream()))
+                                      _ptr(bias), out.data_ptr(), m, n, k, _stream()))
         return out
 
     @ staticmethod
@@ -2472,17 +2484,10 @@ class CUDA:
         exactly as ``MXPack`` packs it (None, None without ``out_format``).  ``out_format``: one of the five float formats."""
         a_elements, a_scales, fa, b_elements, b_scales, fb, k, bias, m, n = _mx_matmul_args(a_elements, a_scales, a_format, b_elements, b_scales, b_format, k, bias)
         fo, residual = _mx_fused_args(out_format, out_float, residual, [m, n], a_elements.device)
-        dev = a_elements.device
-        out = torch.empty([m, n], dtype=torch.float32, device=dev) if out_float else None
-        elements = scales = None
-        if out_format is not None:
-            eshape, sshape = mx_packed_shapes([m, n], 1, fo)
-            elements, scales = torch.empty(eshape, dtype=torch.uint8, device=dev), torch.empty(sshape, dtype=torch.uint8, device=dev)
+        out, elements, scales = _mx_fused_outputs([m, n], fo, out_format, out_float, a_elements.device)
         with _DeviceOf(a_elements):
             _raise(lib.ppqhip_mx_gemm_fused(a_elements.data_ptr(), a_scales.data_ptr(), fa, b_elements.data_ptr(), b_scales.data_ptr(), fb,
-                                            bias.data_ptr() if bias is not None else 0, residual.data_ptr() if residual is not None else 0,
-                                            1 if relu else 0, out.data_ptr() if out is not None else 0,
-                                            elements.data_ptr() if elements is not None else 0, scales.data_ptr() if scales is not None else 0,
+                                            _ptr(bias), _ptr(residual), 1 if relu else 0, _ptr(out), _ptr(elements), _ptr(scales),
                                             fo, m, n, k, _stream()))
         return out, elements, scales
 
@@ -2500,7 +2505,7 @@ class CUDA:
         out = torch.empty([n, geo[-2], geo[-1], o], dtype=torch.float32, device=x_elements.device)
         with _DeviceOf(out):
             _raise(lib.ppqhip_mx_conv2d(x_elements.data_ptr(), x_scales.data_ptr(), fx, w_elements.data_ptr(), w_scales.data_ptr(), fw,
-                                        bias.data_ptr() if bias is not None else 0, out.data_ptr(), *geo[:13], _stream()))
+                                        _ptr(bias), out.data_ptr(), *geo[:13], _stream()))
         return out.permute(0, 3, 1, 2)
 
     @ staticmethod
@@ -2516,16 +2521,10 @@ class CUDA:
         dev = x_elements.device
         fo, residual = _mx_fused_args(out_format, out_float, residual, [n, o, oh, ow], dev)
         if residual is not None: residual = residual.permute(0, 2, 3, 1).contiguous()               # no copy when it is channels-last
-        out = torch.empty([n, oh, ow, o], dtype=torch.float32, device=dev) if out_float else None
-        elements = scales = None
-        if out_format is not None:
-            eshape, sshape = mx_packed_shapes([n, o, oh, ow], 1, fo)
-            elements, scales = torch.empty(eshape, dtype=torch.uint8, device=dev), torch.empty(sshape, dtype=torch.uint8, device=dev)
+        out, elements, scales = _mx_fused_outputs([n, o, oh, ow], fo, out_format, out_float, dev)
         with _DeviceOf(x_elements):
             _raise(lib.ppqhip_mx_conv2d_fused(x_elements.data_ptr(), x_scales.data_ptr(), fx, w_elements.data_ptr(), w_scales.data_ptr(), fw,
-                                              bias.data_ptr() if bias is not None else 0, residual.data_ptr() if residual is not None else 0,
-                                              1 if relu else 0, out.data_ptr() if out is not None else 0,
-                                              elements.data_ptr() if elements is not None else 0, scales.data_ptr() if scales is not None else 0,
+                                              _ptr(bias), _ptr(residual), 1 if relu else 0, _ptr(out), _ptr(elements), _ptr(scales),
                                               fo, *geo[:13], _stream()))
         return (out.permute(0, 3, 1, 2) if out is not None else None), elements, scales
 

@@ -57,11 +57,12 @@ def same_float(got: torch.Tensor, want: torch.Tensor, what) -> None:
 
 
 @functools.lru_cache(maxsize=None)
-def random_gemm():
-    """x [37, 200], w [70, 200] with rows spread over 12 octaves, a bias and a residual of the outputs' own magnitude."""
-    x, w = G.random_inputs(0, FUSED_SHAPE)
+def random_gemm(shape=FUSED_SHAPE):
+    """x [m, k], w [n, k] (by default [37, 200] and [70, 200]) with rows spread over 12 octaves, a bias and a residual of the outputs' own
+    magnitude."""
+    x, w = G.random_inputs(0, shape)
     rng = np.random.default_rng(5)
-    m, n, _ = FUSED_SHAPE
+    m, n, _ = shape
     bias = rng.standard_normal(n).astype(np.float32)
     residual = (rng.standard_normal((m, n)) * np.exp2(rng.uniform(-4, 8, (m, 1)))).astype(np.float32)
     return dev(x), dev(w), dev(bias), dev(residual)
@@ -73,8 +74,8 @@ def unfused(A, B, bias, residual, relu):
     return relu_positive_zero(v) if relu else v
 
 
-def check_gemm(fa, fb, fo):
-    x, w, bias, residual = random_gemm()
+def check_gemm(fa, fb, fo, shape=FUSED_SHAPE):
+    x, w, bias, residual = random_gemm(shape)
     A, B = mx_quantize(x, fa, -1), mx_quantize(w, fb, -1)
     for use_bias, use_res, relu in ((True, True, True), (False, False, False), (False, True, False), (True, False, True)):
         b, r = (bias if use_bias else None), (residual if use_res else None)
@@ -89,7 +90,7 @@ def check_gemm(fa, fb, fo):
             assert torch.equal(bits(mx_matmul(A, B, b, residual=r, relu=relu)), bits(want)), what
     # the elements a short last block lacks are +0: 70 = 2 * 32 + 6
     width = P.WIDTH[fo]
-    codes = P.unpack_fields(packed.elements.cpu().numpy().reshape(FUSED_SHAPE[0], -1, P.BLOCK_BYTES[fo]), width)
+    codes = P.unpack_fields(packed.elements.cpu().numpy().reshape(shape[0], -1, P.BLOCK_BYTES[fo]), width)
     assert codes.shape[1] == 3 and (codes[:, 2, 6:] == 0).all() and (codes[:, 2, :6] != 0).any()
 
 
@@ -102,6 +103,14 @@ def test_gemm_all_pairs(fa, fb):
 @pytest.mark.parametrize('fa,fb', G.EDGE_PAIRS)
 def test_gemm_all_out_formats(fa, fb, fo):
     check_gemm(fa, fb, fo)
+
+
+@pytest.mark.parametrize('fa,fb', G.EDGE_PAIRS)
+def test_gemm_more_than_one_workgroup_along_m(fa, fb):
+    """(130, 70, 416): three tile rows, so the fused epilogue's rows and block index are computed for m0 = 64 and 128 too (the
+    shape above has one tile row), with nb = 13: three full K-steps and a tail of one block."""
+    assert G.EDGE_SHAPES[-1] == (130, 70, 416)
+    check_gemm(fa, fb, OUT_ONE, G.EDGE_SHAPES[-1])
 
 
 def test_relu_gives_positive_zero():
@@ -306,6 +315,39 @@ def test_conv_all_pairs(fx, fw):
 @pytest.mark.parametrize('g', [C.FIRST, C.EDGE_GEOMETRIES[1], C.DILATED], ids=str)
 def test_conv_geometries_and_out_formats(g, fx, fw, fo):
     check_conv(g, fx, fw, fo)
+
+
+@functools.lru_cache(maxsize=None)
+def gathered_conv(g, fx, fw):
+    """x and w of random_conv with one NaN each, packed, and the same bytes as the operands of the GEMM: gather_im2col(x) [M, K'] and
+    the weight viewed as [O, K']."""
+    x, w = random_conv(g)[:2]
+    x, w = x.clone(), w.clone()
+    x[g.n - 1, 5, 1, g.w - 1] = float('nan')
+    w[3, g.c - 1, 0, g.kw - 1] = float('nan')
+    X, W = mx_quantize(x, fx, 1), mx_quantize(w, fw, 1)
+    ae, as_ = C.gather_im2col((X.elements.cpu().numpy(), X.scales.cpu().numpy()), fx, g)
+    we, ws = C.weight_operand((W.elements.cpu().numpy(), W.scales.cpu().numpy()))
+    return X, W, MXTensor(fx, (g.m, g.k), 1, dev(ae), dev(as_)), MXTensor(fw, (g.o, g.k), 1, dev(we), dev(ws))
+
+
+@pytest.mark.parametrize('fo', FR.OUT_FORMATS)
+@pytest.mark.parametrize('g', C.RANDOM_GEOMETRIES, ids=str)
+@pytest.mark.parametrize('fx,fw', G.EDGE_PAIRS)
+def test_fused_conv_has_the_bits_of_fused_matmul_on_the_gathered_operand(fx, fw, g, fo):
+    """Both kernels run one K-step and one fused epilogue on two A sources, so the tie that
+    tests/test_gpu_mx_conv.py pins for the plain kernels holds for the fused ones: bias, residual, ReLU, a NaN in x and one in w, the float and the packed output.  M = 70
+    and 18, O = 70 and 33: a short last output block, waves that return early, a K tail.  Both sides run on the device: ==."""
+    _, _, bias, residual = random_conv(g)
+    X, W, A, B = gathered_conv(g, fx, fw)
+    y, packed = mx_conv2d_packed(X, W, bias, g.stride, g.pad, g.dil, residual=residual, relu=True, out_format=fo, out_float=True)
+    v, p = mx_matmul(A, B, bias, residual=residual.permute(0, 2, 3, 1).reshape(g.m, g.o), relu=True, out_format=fo, out_float=True)
+    what = (fx, fw, str(g), fo)
+    nan = torch.isnan(y)
+    assert nan.any() and not nan.all() and nan[:, 3].all(), what
+    same_float(y, v.reshape(g.n, g.oh, g.ow, g.o).permute(0, 3, 1, 2), what)
+    lead = (g.n, g.oh, g.ow)
+    same_packed(packed, MXTensor(fo, packed.shape, 1, p.elements.reshape(*lead, -1), p.scales.reshape(*lead, -1)), what)
 
 
 @pytest.mark.parametrize('fo', FR.OUT_FORMATS)
