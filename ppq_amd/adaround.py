@@ -15,11 +15,12 @@ import numpy as np
 import torch
 from torch.autograd import Function
 
-from .blocks import COMPUTING_OP, block_forward, torch_mean_square_error
+from .blocks import COMPUTING_OP, torch_mean_square_error
 from .core import QuantizationProperty as P
 from .core import QuantizationStates, rounding_value, state_value
 from .ffi import adaround_backward_multi, adaround_forward_multi
-from .lsq import LearnedStepSizePass, LSQActivationGroup, LSQDelegator, LSQWeightGroup
+from .lsq import (BlockTraining, LaunchGroup, LearnedStepSizePass, LSQActivationGroup, LSQDelegator, LSQWeightGroup, _channel_axis,
+                  _unique)
 
 
 class TimeDecay:
@@ -70,10 +71,6 @@ class AdaroundRegTerm(torch.nn.Module):
         return np.array([k, np.float32(beta), np.float32(beta - 1.0)], dtype=np.float32)
 
 
-def _channel_axis(config):
-    return config.channel_axis if config.policy.has_property(P.PER_CHANNEL) else None
-
-
 class _AdaRoundFunction(Function):
     """One weight, one job of each kernel: forward = AdaRoundDelegator.__call__, backward = dV (plus the regulariser's
     gradient when ``reg[0]`` != 0).  W, the scale and the offset receive no gradient (they are in no optimizer)."""
@@ -104,19 +101,16 @@ class _GroupedAdaRound(Function):
         return None, None, None, None
 
 
-class AdaroundGroup:
+class AdaroundGroup(LaunchGroup):
     """The AdaRound delegators of one block as ONE ``ppqhip_adaround_fwd_multi`` launch (:meth:`prepare`, start of a step) and
     ONE ``ppqhip_adaround_bwd_multi`` launch (:meth:`flush`, end of the backward sweep).  Outputs and dV buffers are allocated
     once and dV is installed as V's ``.grad``, so a captured HIP graph of the step finds them at fixed addresses."""
     def __init__(self, members, reg: torch.Tensor):
-        self.members = members                              # [(delegator, config, var)]
+        super().__init__(members)
         self.reg = reg
         self.outs = [torch.empty_like(v.value) for _, _, v in members]
         self.gv = [torch.empty_like(d.rounding) for d, _, _ in members]
         self.dys = [None] * len(members)
-        self.outputs = None
-        self.launches = 0
-        for k, (d, _, _) in enumerate(members): d.group, d.slot = self, k
 
     @ staticmethod
     def eligible(delegator, config, var) -> bool:
@@ -147,9 +141,6 @@ class AdaroundGroup:
             if leaf.grad is None: leaf.grad = g
             elif leaf.grad is not g: leaf.grad.add_(g)
         self.dys = [None] * len(self.members)
-
-    def release(self) -> None:
-        for d, _, _ in self.members: d.group, d.slot = None, None
 
 
 class AdaRoundDelegator:
@@ -223,22 +214,21 @@ class AdaRoundDelegator:
 
 
 class AdaroundPass(LearnedStepSizePass):
-    """legacy.py:139-297: block-wise AdaRound.  Per block (``block_size`` = the reference's depth limit, default 4):
+    """legacy.py:139-297: block-wise AdaRound (``block_size`` = the reference's depth limit, default 4) on
+    ``LearnedStepSizePass.finetune``'s frame.  What is this pass's own:
 
-    1. ``pre_loss``;
-    2. ``tune_block_weight_scale``: 900 steps of Adam(lr) + MultiStepLR([450, 600]) on MSE(Q(W), W) per computing-op weight
-       through ``LSQDelegator(is_parameter_trainable=False)`` -- all weights of the block in ONE loop (Adam is elementwise and
-       the losses are independent: the values of one loop per weight), each weight keeping its own withdraw decision;
-    3. an AdaRound delegator on every ACTIVATED, non-PASSIVE parameter config, an ``LSQDelegator(is_offset_trainable=False)`` on
-       the other ACTIVATED / PASSIVE configs when ``is_scale_trainable``;
-    4. ``steps`` of Adam on the block MSE plus ``gamma`` x the regulariser;
-    5. ``post_loss``, then every delegator withdraws when the block ended worse, else finalises.
+    * between the pre-loss and the delegators, ``tune_block_weight_scale``: 900 steps of Adam(lr) + MultiStepLR([450, 600]) on
+      MSE(Q(W), W) per computing-op weight through ``LSQDelegator(is_parameter_trainable=False)`` -- all weights of the block in
+      ONE loop (Adam is elementwise and the losses are independent: the values of one loop per weight), each weight keeping its
+      own withdraw decision.  A failure later in the block does not take it back;
+    * an AdaRound delegator on every ACTIVATED, non-PASSIVE parameter config, an ``LSQDelegator(is_offset_trainable=False)`` on
+      the other ACTIVATED / PASSIVE configs when ``is_scale_trainable``;
+    * the step loss is the block MSE; ``gamma`` x the regulariser's gradient is added by the backward launch, from a device row
+      ``before_step`` refreshes.  ``anneal_regularization=True`` evaluates the regulariser at the true step instead of the
+      reference's shadowed index (INTEGRATION.md section 6 (a));
+    * every delegator withdraws when the block ended worse, else finalises.
 
-    The MI355X-side execution choices are LearnedStepSizePass's: the block's AdaRound weights in ONE forward and ONE backward
-    launch per step (``group_weights``), the step captured once as a HIP graph with the capturable Adam and replayed
-    (``use_hip_graph``; ``use_hip_graph=False`` is the reference's optimizer).  ``anneal_regularization=True`` evaluates the
-    regulariser at the true step instead of the reference's shadowed index.
-    ``report`` = [(block, pre_loss, post_loss)]."""
+    ``group_weights``: the block's AdaRound weights in ONE forward and ONE backward launch per step."""
     def __init__(self, name: str = 'Block-wise Adaround Reconstruction', interested_layers: List[str] = [],
                  is_scale_trainable: bool = False, steps: int = 8000, lr: float = 1e-3, gamma: float = 1.0,
                  collecting_device: str = 'cuda', block_size: int = 4, *, anneal_regularization: bool = False,
@@ -280,10 +270,7 @@ class AdaroundPass(LearnedStepSizePass):
                 if len(d.trainable_tensors()) == 0: continue
                 members.append((d, c, v))
         if not members: return
-        params, seen = [], set()
-        for d, _, _ in members:
-            for t in d.trainable_tensors():
-                if id(t) not in seen: seen.add(id(t)); params.append(t)
+        params = _unique(t for d, _, _ in members for t in d.trainable_tensors())
         self.stats['tuned_weights'] += len(members)
         optimizer = torch.optim.Adam(params, lr=self.lr)
         scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, [int(steps / 2), int(steps * 2 / 3)])
@@ -335,88 +322,48 @@ class AdaroundPass(LearnedStepSizePass):
                     if not (isinstance(var.value, torch.Tensor) and var.value.is_cuda):
                         raise TypeError(f'AdaroundPass: {var.name} is not a CUDA tensor (ppq_amd has no CPU path)')
 
-    def finetune(self, block, executor, qt_inputs, fp_outputs):
-        """legacy.py:205-297 for one block."""
-        self._check_block(block)
-        if len(qt_inputs) == 0: raise ValueError('Dataset is empty.')
-        self.enable_block_gradient(block)
-        with self._phase('pre_loss'):
-            pre_loss = self._block_loss(block, qt_inputs, fp_outputs, executor)
+    def _before_delegators(self, block) -> None:
         with self._phase('tune_weight_scale'):
             self.tune_block_weight_scale(block)
 
-        delegators, tensors = {}, []
+    def _delegate(self, block, executor, job: BlockTraining) -> None:
+        """legacy.py:222-240."""
         for op in block.rps:
             if not hasattr(op, 'config'): continue
             for cfg, var in op.config_with_variable:
                 st = state_value(cfg.state)
                 if st not in (QuantizationStates.ACTIVATED.value, QuantizationStates.PASSIVE.value): continue
                 if var.is_parameter and st != QuantizationStates.PASSIVE.value:
-                    d = AdaRoundDelegator(config=cfg, var=var, steps=self.steps)
+                    job.register(executor, cfg, AdaRoundDelegator(config=cfg, var=var, steps=self.steps))
                 elif self.is_scale_trainable:
-                    d = LSQDelegator(config=cfg, var=var, is_offset_trainable=False)
-                else: continue
-                tensors.extend(d.trainable_tensors())
-                executor.register_quantize_delegate(cfg, d)
-                delegators[cfg] = d
-        uniq, seen = [], set()
-        for t in tensors:
-            if t.requires_grad and id(t) not in seen: seen.add(id(t)); uniq.append(t)
-        if not uniq:                                   # (d): nothing stays requires_grad on the early exit
-            for cfg in delegators: executor.remove_quantize_delegate(cfg)
-            self.disable_block_gradient(block)
-            return 0.0, 0.0
+                    job.register(executor, cfg, LSQDelegator(config=cfg, var=var, is_offset_trainable=False))
 
-        names = [v.name for v in block.ep.outputs]
-        device = uniq[0].device
-        table = self._reg_table(len(names), device)
-        reg = table[0].clone()                         # the device buffer every backward launch reads
-        ada = [(d, cfg, d.var) for cfg, d in delegators.items() if isinstance(d, AdaRoundDelegator)]
+    @ staticmethod
+    def _adaround_members(job: BlockTraining) -> list:
+        return [(d, cfg, d.var) for cfg, d in job.delegators.items() if isinstance(d, AdaRoundDelegator)]
+
+    def _build_groups(self, block, job: BlockTraining, uniq) -> None:
+        table = self._reg_table(len(block.ep.outputs), uniq[0].device)
+        reg = table[0].clone()                         # the device buffer every backward launch reads: the regulariser's
+        ada = self._adaround_members(job)              # gradient is added there, the step loss is the block MSE alone
         for d, _, _ in ada: d.reg_values = reg
         self.stats['adaround_weights'] += len(ada)
         members = [m for m in ada if AdaroundGroup.eligible(*m)] if self.group_weights else []
-        group = AdaroundGroup(members, reg) if members else None
-        act_group = LSQActivationGroup.build(delegators) if (self.group_activations and self.is_scale_trainable) else None
-        self.stats['blocks'] += 1
-        self.stats['grouped_weights'] += len(members)
-        self.stats['grouped_activations'] += len(act_group.members) if act_group is not None else 0
-        graphable = self._graphable(qt_inputs, fp_outputs, uniq)
-        opt = self._make_optimizer(uniq, graphable)
+        if members: job.groups = [AdaroundGroup(members, reg)]
+        if self.group_activations and self.is_scale_trainable: job.act_groups = LSQActivationGroup.build(job.delegators)
         constant = not self.anneal_regularization
 
         def before_step(step: int) -> None:
             if step == 0 or not constant: reg.copy_(table[step])
+        job.before_step = before_step
 
-        def train_step(qt_input, fp_output) -> None:
-            opt.zero_grad()
-            if act_group is not None: act_group.live.clear()
-            if group is not None: group.prepare()
-            with torch.enable_grad():
-                outs = block_forward(executor, block.rps, qt_input, names, with_gradient=True)
-                loss = sum(self._loss(y, fp_output[n]) for n, y in zip(names, outs))
-            loss.backward()                            # the regulariser's gradient is added by the backward launch (reg)
-            if group is not None: group.flush()
-            if act_group is not None: act_group.flush()
-            opt.step()
+    def _step_loss(self, block, names, outs, fp_output):
+        return sum(self._loss(y, fp_output[n]) for n, y in zip(names, outs))
 
-        try:
-            done = self._train_with_graph(train_step, qt_inputs, fp_outputs, before_step=before_step) if graphable else 0
-            with self._phase('eager_steps'):
-                for step in range(done, self.steps):
-                    before_step(step)
-                    train_step(qt_inputs[step % len(qt_inputs)], fp_outputs[step % len(qt_inputs)])
-                    self.stats['eager_steps'] += 1
-        finally:
-            if group is not None: group.outputs = None
-        with self._phase('post_loss'):               # (c): measured with the soft rounding h(V) still delegated
-            post_loss = self._block_loss(block, qt_inputs, fp_outputs, executor)
-        if group is not None: group.release()
-        if act_group is not None: act_group.release()
-        if self.keep_roundings: self.roundings.update({d.var.name: d.rounding.detach().clone() for d, _, _ in ada})
-        for cfg, d in delegators.items():
-            if post_loss > pre_loss: d.withdraw()
+    def _settle(self, job: BlockTraining, worse: bool) -> None:
+        """legacy.py:286-293.  (The post-loss was measured with the soft rounding h(V) still delegated: quirk (c).)"""
+        if self.keep_roundings:
+            self.roundings.update({d.var.name: d.rounding.detach().clone() for d, _, _ in self._adaround_members(job)})
+        for d in job.delegators.values():
+            if worse: d.withdraw()
             else: d.finalize()
-            executor.remove_quantize_delegate(cfg)
-        for d, _, _ in ada: d.rounding.grad = None
-        self.disable_block_gradient(block)
-        return pre_loss, post_loss

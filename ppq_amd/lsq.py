@@ -62,6 +62,36 @@ class CuLSQ_LC(Function):
         return dx, ds.reshape(scales.shape), None, None, None, None, None
 
 
+def _channel_axis(config):
+    return config.channel_axis if config.policy.has_property(P.PER_CHANNEL) else None
+
+
+def _unique(tensors) -> list:
+    """``tensors`` without repeats of the same object (``id``), in first-seen order: a tensor goes to an optimizer once."""
+    uniq, seen = [], set()
+    for t in tensors:
+        if id(t) not in seen: seen.add(id(t)); uniq.append(t)
+    return uniq
+
+
+class LaunchGroup:
+    """The weight delegators of one block that share multi-tensor launches.  The protocol the block-training frame
+    (:meth:`LearnedStepSizePass.finetune`) drives: :meth:`prepare` at the start of a step fills ``outputs`` -- while it is set, a
+    member delegator hands out its slot instead of launching --, :meth:`flush` after ``backward``, ``outputs = None`` when training
+    ends (the per-tensor path from there), :meth:`release` at the end.  ``launches`` counts what the group launched."""
+    def __init__(self, members):
+        self.members = members                              # [(delegator, config, var)]
+        self.outputs = None
+        self.launches = 0
+        for k, (d, _, _) in enumerate(members): d.group, d.slot = self, k
+
+    def flush(self) -> None:
+        """End of the backward sweep: nothing to launch unless the group computes gradients."""
+
+    def release(self) -> None:
+        for d, _, _ in self.members: d.group, d.slot = None, None
+
+
 class _GroupedLSQ(Function):
     """``CuLSQ_LC`` for a weight that belongs to an :class:`LSQWeightGroup`: forward hands out the slice the group's ONE
     forward launch already filled, backward only stashes ``dy`` -- weight and scale are autograd LEAVES, so nothing further
@@ -77,7 +107,7 @@ class _GroupedLSQ(Function):
         return None, None, None, None, None
 
 
-class LSQWeightGroup:
+class LSQWeightGroup(LaunchGroup):
     """All per-channel weight delegators of one block as ONE forward launch (``ppqhip_fq_linear_multi``: the arena of
     ``ffi.LinearQuantizePlan`` re-filled from the current weights / scales at the start of every step) and ONE backward
     launch (``ppqhip_fq_linear_c_bwd_multi``) -- where the per-tensor path issues a forward kernel, a memset and a backward
@@ -87,7 +117,7 @@ class LSQWeightGroup:
     of the step finds them at fixed addresses."""
     def __init__(self, members):
         from .ffi import LinearQuantizePlan
-        self.members = members                              # [(delegator, config, var)]
+        super().__init__(members)
         cfg0 = members[0][1]
         self.rounding = rounding_value(cfg0.rounding)
         self.plan = LinearQuantizePlan([(v.value, c.scale, c.offset, c.channel_axis, c.quant_min, c.quant_max)
@@ -95,9 +125,6 @@ class LSQWeightGroup:
         self.gx = [torch.empty_like(v.value, memory_format=torch.contiguous_format) for _, _, v in members]
         self.gs = [torch.empty_like(c.scale) for _, c, _ in members]
         self.dys = [None] * len(members)
-        self.outputs = None
-        self.launches = 0
-        for k, (d, _, _) in enumerate(members): d.group, d.slot = self, k
 
     @ staticmethod
     def eligible(delegator, config, var) -> bool:
@@ -145,9 +172,6 @@ class LSQWeightGroup:
                 #  overwrote it, which is the gradient)
         self.dys = [None] * len(m)
 
-    def release(self) -> None:
-        for d, _, _ in self.members: d.group, d.slot = None, None
-
 
 class _DeferredScaleLSQ(Function):
     """``CuLSQ_LT`` for an activation that belongs to an :class:`LSQActivationGroup`: forward is the same fake-quant launch,
@@ -192,9 +216,16 @@ class LSQActivationGroup:
                 and config.scale.is_leaf and config.scale.numel() == 1 and isinstance(config.offset, torch.Tensor))
 
     @ classmethod
-    def build(cls, delegators: dict):
+    def build(cls, delegators: dict) -> list:
+        """The group of the eligible delegators of a block, as a list like ``LSQWeightGroup.build``'s: empty under two members."""
         members = [(d, cfg) for cfg, d in delegators.items() if cls.eligible(d, cfg)]
-        return cls(members) if len(members) >= 2 else None
+        return [cls(members)] if len(members) >= 2 else []
+
+    def prepare(self) -> None:
+        """Start of a step: a step that aborted between a backward and its flush (a failed graph capture) must not leak
+        half-built state into this one -- partial sums whose kernels never ran would be finished and ADDED to the scale
+        gradients."""
+        self.live.clear()
 
     def backward_main(self, slot: int, tensor, scales, offsets, dy, quant_min: int, quant_max: int, rounding: int) -> torch.Tensor:
         need = CUDA.lsq_t_partials(tensor.numel())
@@ -289,6 +320,23 @@ class LSQDelegator:
         elif config.policy.has_property(P.FLOATING):
             return PPQuantFunction(tensor=tensor, config=config)      # scale is not trainable for FP8
         raise ValueError('LSQDelegator: unsupported quantization policy')
+
+
+class BlockTraining:
+    """What the hooks of a block-wise pass hand :meth:`LearnedStepSizePass.finetune` for one block."""
+    def __init__(self) -> None:
+        self.delegators = {}                    # config -> delegator, in the order of registration
+        self.saved = {}                         # config -> the delegate the executor held before: registered again at the end
+        self.tensors = []                       # what the optimizer may get: those with requires_grad, each once
+        self.loose = []                         # (tensor, backup) of the trained tensors no delegator answers for
+        self.groups, self.act_groups = [], []   # the launch groups of the weights and of the activations
+        self.before_step = None                 # before_step(step): refreshes a device input of the step, where a pass has one
+
+    def register(self, executor, config, delegator, keep_held: bool = False) -> None:
+        if keep_held: self.saved[config] = getattr(executor, '_delegates', {}).get(config)
+        self.delegators[config] = delegator     # before the registration: a delegator the executor refuses is rolled back too
+        self.tensors.extend(delegator.trainable_tensors())
+        executor.register_quantize_delegate(config, delegator)
 
 
 class LearnedStepSizePass(QuantizationOptimizationPass):
@@ -502,87 +550,131 @@ class LearnedStepSizePass(QuantizationOptimizationPass):
         self.stats['fused_adam_blocks'] = self.stats.get('fused_adam_blocks', 0) + 1
         return opt
 
-    def finetune(self, block, executor, qt_inputs, fp_outputs):
-        """training.py:728-826 for one block."""
-        self.enable_block_gradient(block)
-        with self._phase('pre_loss'):
-            pre_loss = self._block_loss(block, qt_inputs, fp_outputs, executor)
-        delegators, tensors = {}, []
+    # ---- what a pass contributes to the frame; these are LSQ's -----------------------------------------
+    def _check_block(self, block) -> None:
+        """Refuse a block this pass cannot train, before anything of it is touched."""
+
+    def _pre_loss(self, block, qt_inputs, fp_outputs, executor) -> float:
+        return self._block_loss(block, qt_inputs, fp_outputs, executor)
+
+    def _post_loss(self, block, qt_inputs, fp_outputs, executor) -> float:
+        return self._block_loss(block, qt_inputs, fp_outputs, executor)
+
+    def _before_delegators(self, block) -> None:
+        """Between the pre-loss and the first delegator."""
+
+    def _delegate(self, block, executor, job: BlockTraining) -> None:
+        """training.py:745-760: ``job.register`` a delegator on every config to train, ``job.tensors`` += what else is trained."""
         for op in block.rps:
             if not hasattr(op, 'config'): continue
             if op.type in COMPUTING_OP or op.type in {'Add', 'Mul'}:          # a lone Add / Mul trains its constant too
                 for var in op.inputs:
-                    if var.is_parameter and isinstance(var.value, torch.Tensor): tensors.append(var.value)
+                    if var.is_parameter and isinstance(var.value, torch.Tensor): job.tensors.append(var.value)
             for cfg, var in op.config_with_variable:
                 if state_value(cfg.state) in (QuantizationStates.ACTIVATED.value, QuantizationStates.PASSIVE.value):
-                    d = LSQDelegator(config=cfg, var=var, is_scale_trainable=self.is_scale_trainable)
-                    tensors.extend(d.trainable_tensors())
-                    executor.register_quantize_delegate(cfg, d)
-                    delegators[cfg] = d
-        uniq, seen = [], set()
-        for t in tensors:                              # offsets never carry requires_grad: CuLSQ has no offset gradient
-            if t.requires_grad and id(t) not in seen: seen.add(id(t)); uniq.append(t)
-        if not uniq:
-            for cfg in delegators: executor.remove_quantize_delegate(cfg)
-            self.disable_block_gradient(block)
-            return 0.0, 0.0
-        # parameters whose config carries no delegator (an FP32 bias when the quantizer leaves biases unquantised -- with
-        # quantize_graph(passive_bias=True) + PassiveParameterQuantizePass the bias config is PASSIVE and its delegator holds
-        # the backup, as in the reference) are trained too -- keep their own backup
-        covered = {id(d.var.value) for d in delegators.values() if d.is_parameter}
-        loose = [(t, t.detach().clone()) for t in uniq if id(t) not in covered
-                 and not any(t is c.scale or t is c.offset for c in delegators)]
-        names = [v.name for v in block.ep.outputs]
-        if len(qt_inputs) == 0: raise ValueError('Dataset is empty.')
-        groups = LSQWeightGroup.build(delegators) if (self.group_weights and uniq[0].is_cuda) else []
-        act_group = LSQActivationGroup.build(delegators) if (self.group_activations and uniq[0].is_cuda) else None
-        self.stats['blocks'] += 1
-        self.stats['grouped_weights'] += sum(len(g.members) for g in groups)
-        self.stats['grouped_activations'] += len(act_group.members) if act_group is not None else 0
-        graphable = self._graphable(qt_inputs, fp_outputs, uniq)
-        opt = self._make_optimizer(uniq, graphable)
+                    job.register(executor, cfg, LSQDelegator(config=cfg, var=var, is_scale_trainable=self.is_scale_trainable))
 
-        def train_step(qt_input, fp_output) -> None:
-            opt.zero_grad()
-            # a step that aborted between a backward and its flush (a failed graph capture) must not leak half-built state into
-            # this one: partial sums whose kernels never ran would be finished and ADDED to the scale gradients (ADVICE r5)
-            if act_group is not None: act_group.live.clear()
-            for g in groups: g.prepare()
-            with torch.enable_grad():
-                outs = block_forward(executor, block.rps, qt_input, names, with_gradient=True)
-                loss = sum(self._loss(y, fp_output[n]) for n, y in zip(names, outs))
-                if self.gamma:
-                    for op in block.rps:                                  # training.py:793-798 (the STE gradient passes)
-                        if hasattr(op, 'config') and op.type in COMPUTING_OP:
-                            w, wc = op.inputs[1].value, op.config.input_quantization_config[1]
-                            # always the reference's own MSE over PPQLinearQuantFunction, whatever `loss_fn` is (ADVICE r4)
-                            loss = loss + torch_mean_square_error(w, PPQLinearQuantFunction(w, wc)) * self.gamma
-            loss.backward()
-            for g in groups: g.flush()
-            if act_group is not None: act_group.flush()
-            with torch.no_grad():
-                self._average([t.grad for t in uniq if t.grad is not None])
-            opt.step()
+    def _nothing_to_train(self, job: BlockTraining, uniq) -> bool:
+        return not uniq
 
-        done = self._train_with_graph(train_step, qt_inputs, fp_outputs) if graphable else 0
-        with self._phase('eager_steps'):
-            for step in range(done, self.steps):
-                train_step(qt_inputs[step % len(qt_inputs)], fp_outputs[step % len(qt_inputs)])
-                self.stats['eager_steps'] += 1
-        for g in groups: g.outputs = None             # the arena is stale after the last optimizer step: per-tensor path from here
-        with self._phase('post_loss'):
-            post_loss = self._block_loss(block, qt_inputs, fp_outputs, executor)
-        for g in groups: g.release()
-        if act_group is not None: act_group.release()
-        for cfg, d in delegators.items():
-            if post_loss > pre_loss: d.withdraw()
+    def _build_groups(self, block, job: BlockTraining, uniq) -> None:
+        """Fill ``job.groups`` / ``job.act_groups`` (and ``job.before_step``) for the tensors ``uniq`` that will be trained."""
+        if self.group_weights and uniq[0].is_cuda: job.groups = LSQWeightGroup.build(job.delegators)
+        if self.group_activations and uniq[0].is_cuda: job.act_groups = LSQActivationGroup.build(job.delegators)
+
+    def _capturable(self, block, executor) -> bool:
+        """A condition of the pass's own on top of :meth:`_graphable`."""
+        return True
+
+    def _step_loss(self, block, names, outs, fp_output):
+        loss = sum(self._loss(y, fp_output[n]) for n, y in zip(names, outs))
+        if self.gamma:
+            for op in block.rps:                                  # training.py:793-798 (the STE gradient passes)
+                if hasattr(op, 'config') and op.type in COMPUTING_OP:
+                    w, wc = op.inputs[1].value, op.config.input_quantization_config[1]
+                    # always the reference's own MSE over PPQLinearQuantFunction, whatever `loss_fn` is
+                    loss = loss + torch_mean_square_error(w, PPQLinearQuantFunction(w, wc)) * self.gamma
+        return loss
+
+    def _settle(self, job: BlockTraining, worse: bool) -> None:
+        """Keep or withdraw what every delegator trained (training.py:815-822: finalised either way)."""
+        for d in job.delegators.values():
+            if worse: d.withdraw()
             d.finalize()
-            executor.remove_quantize_delegate(cfg)
-        if post_loss > pre_loss:
-            with torch.no_grad():
-                for t, backup in loose: t.copy_(backup)
-        self.disable_block_gradient(block)
-        return pre_loss, post_loss
+
+    # ---- the frame ---------------------------------------------------------------------------------------------------------
+    def finetune(self, block, executor, qt_inputs, fp_outputs):
+        """One block through the block-training frame every block-wise pass shares (training.py:728-826 is LSQ's instance; the
+        order of calls and what each pass contributes: DESIGN.md section 4.5).  Whatever raises once the first delegator
+        exists leaves the block as it was found and is raised again."""
+        self._check_block(block)
+        if len(qt_inputs) == 0: raise ValueError('Dataset is empty.')
+        self.enable_block_gradient(block)
+        with self._phase('pre_loss'):
+            pre_loss = self._pre_loss(block, qt_inputs, fp_outputs, executor)
+        self._before_delegators(block)
+        job, undo = BlockTraining(), True              # undo: the loose tensors get their backups (the block ended worse, or raised)
+        try:
+            self._delegate(block, executor, job)
+            # (offsets never carry requires_grad: CuLSQ has no offset gradient)
+            uniq = _unique(t for t in job.tensors if t.requires_grad)
+            if self._nothing_to_train(job, uniq): return 0.0, 0.0
+            # trained tensors no delegator answers for (an FP32 bias when the quantizer leaves biases unquantised -- with
+            # quantize_graph(passive_bias=True) + PassiveParameterQuantizePass the bias config is PASSIVE and its delegator holds
+            # the backup, as in the reference; the biases of the round-tuning passes) keep a backup here
+            owned = {id(t) for d in job.delegators.values() for t in d.trainable_tensors()}
+            job.loose = [(t, t.detach().clone()) for t in uniq if id(t) not in owned]
+            names = [v.name for v in block.ep.outputs]
+            self._build_groups(block, job, uniq)
+            groups, act_groups, before_step = job.groups, job.act_groups, job.before_step
+            self.stats['blocks'] += 1
+            self.stats['grouped_weights'] += sum(len(g.members) for g in groups)
+            self.stats['grouped_activations'] += sum(len(g.members) for g in act_groups)
+            graphable = self._graphable(qt_inputs, fp_outputs, uniq) and self._capturable(block, executor)
+            opt = self._make_optimizer(uniq, graphable)
+
+            def train_step(qt_input, fp_output) -> None:
+                opt.zero_grad()
+                for g in act_groups: g.prepare()
+                for g in groups: g.prepare()
+                with torch.enable_grad():
+                    outs = block_forward(executor, block.rps, qt_input, names, with_gradient=True)
+                    loss = self._step_loss(block, names, outs, fp_output)
+                loss.backward()
+                for g in groups: g.flush()
+                for g in act_groups: g.flush()
+                with torch.no_grad():                  # (one process: returns at once)
+                    self._average([t.grad for t in uniq if t.grad is not None])
+                opt.step()
+
+            try:
+                done = self._train_with_graph(train_step, qt_inputs, fp_outputs, before_step=before_step) if graphable else 0
+                with self._phase('eager_steps'):
+                    for step in range(done, self.steps):
+                        if before_step is not None: before_step(step)
+                        train_step(qt_inputs[step % len(qt_inputs)], fp_outputs[step % len(qt_inputs)])
+                        self.stats['eager_steps'] += 1
+            finally:
+                for g in groups: g.outputs = None      # stale after the last optimizer step: the per-tensor path from here
+            with self._phase('post_loss'):             # measured with the delegators still registered
+                post_loss = self._post_loss(block, qt_inputs, fp_outputs, executor)
+            undo = post_loss > pre_loss                # a NaN keeps the block
+            self._settle(job, undo)
+            return pre_loss, post_loss
+        except BaseException:
+            undo = True
+            for d in job.delegators.values(): d.withdraw()
+            raise
+        finally:
+            for g in job.groups + job.act_groups: g.release()
+            for cfg in job.delegators:
+                executor.remove_quantize_delegate(cfg)
+                if job.saved.get(cfg) is not None: executor.register_quantize_delegate(cfg, job.saved[cfg])
+            if undo:
+                with torch.no_grad():
+                    for t, backup in job.loose: t.copy_(backup)
+            for t in job.tensors: t.grad = None        # the roundings are no part of the block: disable_block_gradient misses them
+            self.disable_block_gradient(block)
 
     def optimize(self, graph, dataloader, executor, collate_fn=None, **kwargs):
         from .blocks import TrainableBlock, collect, split_graph_into_blocks

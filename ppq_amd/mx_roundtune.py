@@ -19,10 +19,10 @@ from typing import Any, Dict, List
 import torch
 from torch.autograd import Function
 
-from .blocks import block_forward, compute_block_loss, torch_mean_square_error
 from .core import QuantizationStates, state_value
 from .ffi import MX_BLOCK, mx_round_forward_jobs, mx_round_forward_multi, mx_round_split_multi
-from .lsq import LearnedStepSizePass
+from .lsq import BlockTraining, LaunchGroup, LearnedStepSizePass
+from .roundtune import RoundTuningPass, _GroupedRound, _train_bias
 from .mx import (_SPEC, MX_OPERATIONS, MXDelegator, MXFormat, MXScaleRule, _activated, _bits_to_float, _check_codes, _check_input, _config_rule,
                  _mx_scale_code, _pow2, mx_block_axis)
 
@@ -138,18 +138,6 @@ class _MXRoundFunction(Function):
         return dy, dy, None, None, None, None
 
 
-class _GroupedMXRound(Function):
-    """A member of an :class:`MXRoundTuningGroup`: forward hands out what the group's ONE launch wrote, backward is the same
-    identity."""
-    @ staticmethod
-    def forward(ctx, tensor, rounding, group, slot: int) -> torch.Tensor:
-        return group.outputs[slot].detach()
-
-    @ staticmethod
-    def backward(ctx, dy: torch.Tensor):
-        return dy, dy, None, None
-
-
 def mx_round_forward(floored: torch.Tensor, rounding: torch.Tensor, scale_codes: torch.Tensor, format, axis: int = -1,
                      use_kernels: bool = True) -> torch.Tensor:
     """The weight a rounding selects: ``rounding > .5`` takes the element value above ``floored`` on its block's grid, anything else
@@ -162,19 +150,16 @@ def mx_round_forward(floored: torch.Tensor, rounding: torch.Tensor, scale_codes:
 
 
 # ---- delegator and group ------------------------------------------------------------------------------------------------------------
-class MXRoundTuningGroup:
+class MXRoundTuningGroup(LaunchGroup):
     """The MX round-tuning delegators of one block as ONE ``ppqhip_mx_round_fwd_multi`` launch per step (:meth:`prepare`).  Outputs
     are allocated and the job table is built once: floored weight, rounding, codes and outputs stay where they are through a block's
-    training (Adam updates the rounding in place), so a captured HIP graph of the step finds them.  dR = dy exactly, so :meth:`flush`
-    has nothing to launch (it is there for the group protocol of the block-wise passes)."""
+    training (Adam updates the rounding in place), so a captured HIP graph of the step finds them.  dR = dy exactly, so there is no
+    backward launch."""
     def __init__(self, members):
-        self.members = members                              # [(delegator, config, var)]
+        super().__init__(members)
         self.outs = [torch.empty_like(v.value) for _, _, v in members]
         self._items = [(v.value.detach(), d.rounding.detach(), d.scale_codes, d.format, d.axis) for d, _, v in members]
         self._jobs = mx_round_forward_jobs(self._items, self.outs)
-        self.outputs = None
-        self.launches = 0
-        for k, (d, _, _) in enumerate(members): d.group, d.slot = self, k
 
     @ staticmethod
     def eligible(delegator, config, var) -> bool:
@@ -185,12 +170,6 @@ class MXRoundTuningGroup:
         """Start of a step: the delegator's forward of every member (ONE launch)."""
         self.outputs = mx_round_forward_multi(self._items, outs=self.outs, jobs=self._jobs)
         self.launches += 1
-
-    def flush(self) -> None:
-        """End of the backward sweep: nothing to do, every rounding already holds its ``dy``."""
-
-    def release(self) -> None:
-        for d, _, _ in self.members: d.group, d.slot = None, None
 
 
 class MXRoundTuningDelegator:
@@ -243,23 +222,22 @@ class MXRoundTuningDelegator:
     def __call__(self, tensor: torch.Tensor, config=None) -> torch.Tensor:
         if not _activated(config): return tensor
         if self.group is not None and self.group.outputs is not None and tensor is self.var.value:
-            return _GroupedMXRound.apply(tensor, self._rounding, self.group, self.slot)
+            return _GroupedRound.apply(tensor, self._rounding, self.group, self.slot)
         return _MXRoundFunction.apply(tensor, self._rounding, self.scale_codes, self.format, self.axis, self.use_kernels)
 
 
 # ---- the pass -----------------------------------------------------------------------------------------------------------------------
 class MXRoundTuningPass(LearnedStepSizePass):
-    """Block-wise round tuning of MX weights: ``RoundTuningPass.finetune`` step for step with :class:`MXRoundTuningDelegator`.  Per
-    block (``block_size`` = the depth limit, default 5):
+    """Block-wise round tuning of MX weights (``block_size`` = the depth limit, default 5) on ``LearnedStepSizePass.finetune``'s frame
+    (DESIGN.md section 4.5), with ``RoundTuningPass``'s losses, launch group and keep / withdraw rule.  What is this pass's own:
 
-    1. ``pre_loss`` (``torch_mean_square_error``), with the graph's own delegators (``quantize_graph_mx``'s ``MXDelegator``);
-    2. a delegator on the weight of every Conv / Gemm / MatMul whose input 1 is a parameter with an ACTIVATED config that carries
-       ``detail['MX_FORMAT']`` -- format and scale rule from the config, the axis from ``mx_block_axis``; the bias of a three-input
-       op is trained as it is.  The delegate the executor held for the config is saved;
-    3. ``steps`` of Adam(lr) (or the user's optimizer class) on the sum of ``torch.nn.MSELoss()`` over the block outputs;
-    4. ``post_loss`` (``MSELoss``) with the delegators still registered; a block that ended worse gets its weights AND biases back bit
-       for bit, any other block is finalised: every weight is the forward of its final rounding.  The saved delegates are registered
-       again -- the very objects.
+    * the pre-loss runs with the graph's own delegators (``quantize_graph_mx``'s ``MXDelegator``);
+    * an :class:`MXRoundTuningDelegator` on the weight of every Conv / Gemm / MatMul whose input 1 is a parameter with an ACTIVATED
+      config that carries ``detail['MX_FORMAT']`` -- format and scale rule from the config, the axis from ``mx_block_axis``; the bias
+      of a three-input op is trained as it is, but biases alone are not tuned.  The delegate the executor held for the config is
+      saved and registered again at the end -- the very object;
+    * the step is captured only when every delegate inside the block is known to launch without a synchronisation;
+    * a kept block is finalised: every weight is the forward of its final rounding.
 
     Weights that take no part are left untouched and listed in ``skipped`` (name -> reason): no MX config, a config that is not
     activated, and MXFP8_E4M3 under EVEN, whose tuned weights ``mx_fake_quant`` would change.
@@ -303,103 +281,38 @@ class MXRoundTuningPass(LearnedStepSizePass):
                 if d is not None and not isinstance(d, (MXDelegator, MXRoundTuningDelegator)): return False
         return True
 
-    def finetune(self, block, executor, qt_inputs, fp_outputs):
+    def _check_block(self, block) -> None:
         if self._world() != 1:
             raise ValueError('MXRoundTuningPass runs in one process: data-parallel round tuning is not supported')
-        if len(qt_inputs) == 0: raise ValueError('Dataset is empty.')
-        self.enable_block_gradient(block)
-        with self._phase('pre_loss'):
-            pre_loss = compute_block_loss(block, qt_inputs, fp_outputs, executor, torch_mean_square_error)
 
-        held = getattr(executor, '_delegates', {})
-        delegators, saved, tensors, biases = {}, {}, [], []
+    def _delegate(self, block, executor, job: BlockTraining) -> None:
+        for op in block.rps:
+            if not hasattr(op, 'config') or op.type not in MX_OPERATIONS: continue
+            if len(op.inputs) > 1 and op.inputs[1].is_parameter:
+                cfg, var = op.config.input_quantization_config[1], op.inputs[1]
+                reason = self.refusal(cfg)
+                if reason is not None:
+                    if var.name not in self.skipped: self.stats['skipped_weights'] += 1
+                    self.skipped[var.name] = reason
+                elif cfg not in job.delegators:
+                    if self.use_kernels and not (isinstance(var.value, torch.Tensor) and var.value.is_cuda):
+                        raise TypeError(f'MXRoundTuningPass: {var.name} is not a CUDA tensor (the kernels have no CPU path)')
+                    d = MXRoundTuningDelegator(var, cfg, cfg.detail['MX_FORMAT'], mx_block_axis(op.type, 1), _config_rule(cfg), self.use_kernels)
+                    job.register(executor, cfg, d, keep_held=True)     # the graph's own delegate comes back at the end
+            _train_bias(op, job)
 
-        def restore() -> None:
-            for cfg in delegators:
-                executor.remove_quantize_delegate(cfg)
-                if saved[cfg] is not None: executor.register_quantize_delegate(cfg, saved[cfg])
+    def _nothing_to_train(self, job: BlockTraining, uniq) -> bool:
+        return not job.delegators                          # biases alone are not tuned
 
-        try:
-            for op in block.rps:
-                if not hasattr(op, 'config') or op.type not in MX_OPERATIONS: continue
-                if len(op.inputs) > 1 and op.inputs[1].is_parameter:
-                    cfg, var = op.config.input_quantization_config[1], op.inputs[1]
-                    reason = self.refusal(cfg)
-                    if reason is not None:
-                        if var.name not in self.skipped: self.stats['skipped_weights'] += 1
-                        self.skipped[var.name] = reason
-                    elif cfg not in delegators:
-                        if self.use_kernels and not (isinstance(var.value, torch.Tensor) and var.value.is_cuda):
-                            raise TypeError(f'MXRoundTuningPass: {var.name} is not a CUDA tensor (the kernels have no CPU path)')
-                        d = MXRoundTuningDelegator(var, cfg, cfg.detail['MX_FORMAT'], mx_block_axis(op.type, 1), _config_rule(cfg), self.use_kernels)
-                        saved[cfg] = held.get(cfg)
-                        tensors.append(d.rounding)
-                        delegators[cfg] = d                # before the registration: an executor that refuses d leaves it to the handler below
-                        executor.register_quantize_delegate(cfg, d)
-                if len(op.inputs) == 3 and op.inputs[-1].is_parameter and isinstance(op.inputs[-1].value, torch.Tensor) \
-                        and op.inputs[-1].value.is_floating_point():
-                    op.inputs[-1].value.requires_grad = True
-                    tensors.append(op.inputs[-1].value)
-                    biases.append(op.inputs[-1].value)
-        except Exception:                                  # a refusal half-way leaves the block as it was found
-            for d in delegators.values(): d.withdraw()
-            restore()
-            self.disable_block_gradient(block)
-            raise
-        uniq, seen = [], set()
-        for t in tensors:
-            if t.requires_grad and id(t) not in seen: seen.add(id(t)); uniq.append(t)
-        if not delegators:                                 # nothing of this block is tuned: nothing stays requires_grad
-            self.disable_block_gradient(block)
-            return 0.0, 0.0
-        loose = [(t, t.detach().clone()) for t in uniq if any(t is b for b in biases)]
+    # losses, the one launch group and the keep / withdraw rule are RoundTuningPass's
+    _pre_loss, _post_loss, _step_loss = RoundTuningPass._pre_loss, RoundTuningPass._post_loss, RoundTuningPass._step_loss
+    _build_groups, _settle = RoundTuningPass._build_groups, RoundTuningPass._settle
+    _group_class, _weights_stat = MXRoundTuningGroup, 'mx_weights'
 
-        names = [v.name for v in block.ep.outputs]
-        every = [(d, cfg, d.var) for cfg, d in delegators.items()]
-        members = [m for m in every if MXRoundTuningGroup.eligible(*m)] if self.group_weights else []
-        group = MXRoundTuningGroup(members) if members else None
-        self.stats['blocks'] += 1
-        self.stats['mx_weights'] += len(every)
-        self.stats['grouped_weights'] += len(members)
-        graphable = self._graphable(qt_inputs, fp_outputs, uniq) and self._capturable(block, executor)
-        opt = self._make_optimizer(uniq, graphable)
+    @ staticmethod
+    def _keep(delegator) -> torch.Tensor:
+        """``flipped()`` reads the floored weight, so it comes before ``finalize()`` here."""
+        flipped = delegator.flipped()
+        delegator.finalize()
+        return flipped
 
-        def train_step(qt_input, fp_output) -> None:
-            opt.zero_grad()
-            if group is not None: group.prepare()
-            with torch.enable_grad():
-                outs = block_forward(executor, block.rps, qt_input, names, with_gradient=True)
-                loss = 0.0
-                for n, y in zip(names, outs): loss += self.loss_fn(y, fp_output[n])
-            loss.backward()
-            if group is not None: group.flush()
-            opt.step()
-
-        try:
-            done = self._train_with_graph(train_step, qt_inputs, fp_outputs) if graphable else 0
-            with self._phase('eager_steps'):
-                for step in range(done, self.steps):
-                    train_step(qt_inputs[step % len(qt_inputs)], fp_outputs[step % len(qt_inputs)])
-                    self.stats['eager_steps'] += 1
-        finally:
-            if group is not None: group.outputs = None  # stale after the last optimizer step: one job per weight from here
-        with self._phase('post_loss'):                 # measured with the delegators still registered
-            post_loss = compute_block_loss(block, qt_inputs, fp_outputs, executor, self.loss_fn)
-        if group is not None: group.release()
-        if self.keep_roundings: self.roundings.update({d.var.name: d.rounding.detach().clone() for d, _, _ in every})
-        keep = not post_loss > pre_loss
-        flipped = []
-        for cfg, d in delegators.items():
-            if keep:
-                flipped.append(d.flipped())
-                d.finalize()                               # a withdrawn block is NOT finalised
-                self.stats['tuned_elements'] += d.rounding.numel()
-            else: d.withdraw()
-            d.rounding.grad = None
-        restore()
-        if flipped: self.stats['flipped'] += int(torch.stack(flipped).sum())
-        if not keep:
-            with torch.no_grad():
-                for t, backup in loose: t.copy_(backup)
-        self.disable_block_gradient(block)
-        return pre_loss, post_loss

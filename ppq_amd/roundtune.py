@@ -13,17 +13,13 @@ from typing import Any, List
 import torch
 from torch.autograd import Function
 
-from .blocks import block_forward, compute_block_loss, torch_mean_square_error
+from .blocks import compute_block_loss, torch_mean_square_error
 from .core import QuantizationProperty as P
 from .core import QuantizationStates, state_value
 from .ffi import roundtune_forward_multi
-from .lsq import LearnedStepSizePass
+from .lsq import BlockTraining, LaunchGroup, LearnedStepSizePass, _channel_axis
 
 ROUND_TUNING_OP = {'Gemm', 'MatMul', 'ConvTranspose', 'PPQBiasFusedMatMul', 'Conv'}           # optim/training.py:929
-
-
-def _channel_axis(config):
-    return config.channel_axis if config.policy.has_property(P.PER_CHANNEL) else None
 
 
 class _RoundTuneFunction(Function):
@@ -39,9 +35,10 @@ class _RoundTuneFunction(Function):
         return dy, dy, None, None, None, None, None
 
 
-class _GroupedRoundTune(Function):
-    """A member of a :class:`RoundTuningGroup`: forward hands out what the group's ONE launch wrote, backward is the same
-    identity -- autograd installs ``dy`` as R's ``.grad`` and sums when one weight is read twice in a forward."""
+class _GroupedRound(Function):
+    """A member of a :class:`RoundTuningGroup` or an ``MXRoundTuningGroup``: forward hands out what the group's ONE launch
+    wrote, backward is the same identity -- autograd installs ``dy`` as the rounding's ``.grad`` and sums when one weight is read
+    twice in a forward."""
     @ staticmethod
     def forward(ctx, tensor, rounding, group, slot: int) -> torch.Tensor:
         return group.outputs[slot].detach()
@@ -51,16 +48,13 @@ class _GroupedRoundTune(Function):
         return dy, dy, None, None
 
 
-class RoundTuningGroup:
+class RoundTuningGroup(LaunchGroup):
     """The round-tuning delegators of one block as ONE ``ppqhip_roundtune_fwd_multi`` launch per step (:meth:`prepare`).
-    Outputs are allocated once, so a captured HIP graph of the step finds them at fixed addresses.  dR = dy exactly, so
-    :meth:`flush` has nothing to launch (it is there for the group protocol of the block-wise passes)."""
+    Outputs are allocated once, so a captured HIP graph of the step finds them at fixed addresses.  dR = dy exactly, so there
+    is no backward launch."""
     def __init__(self, members):
-        self.members = members                              # [(delegator, config, var)]
+        super().__init__(members)
         self.outs = [torch.empty_like(v.value) for _, _, v in members]
-        self.outputs = None
-        self.launches = 0
-        for k, (d, _, _) in enumerate(members): d.group, d.slot = self, k
 
     @ staticmethod
     def eligible(delegator, config, var) -> bool:
@@ -75,12 +69,6 @@ class RoundTuningGroup:
                   c.quant_max) for d, c, v in self.members]
         self.outputs = roundtune_forward_multi(items, outs=self.outs)
         self.launches += 1
-
-    def flush(self) -> None:
-        """End of the backward sweep: nothing to do, every R already holds its ``dy``."""
-
-    def release(self) -> None:
-        for d, _, _ in self.members: d.group, d.slot = None, None
 
 
 class RoundTuningDelegator:
@@ -138,7 +126,7 @@ class RoundTuningDelegator:
 
     def __call__(self, tensor: torch.Tensor, config) -> torch.Tensor:
         if self.group is not None and self.group.outputs is not None and tensor is self.var.value:
-            return _GroupedRoundTune.apply(tensor, self._rounding, self.group, self.slot)
+            return _GroupedRound.apply(tensor, self._rounding, self.group, self.slot)
         if not tensor.is_contiguous(): tensor = tensor.contiguous()
         return _RoundTuneFunction.apply(tensor, self._rounding, config.scale, config.offset, _channel_axis(config),
                                         config.quant_min, config.quant_max)
@@ -147,20 +135,28 @@ class RoundTuningDelegator:
 RoundTruningDelegator = RoundTuningDelegator                # the reference's spelling (training.py:529)
 
 
+def _train_bias(op, job: BlockTraining) -> None:
+    """The bias of a three-input op is trained as it is (optim/training.py:944-947).  The reference keeps no backup of it (b);
+    the frame does: it is a trained tensor no delegator answers for."""
+    if len(op.inputs) != 3: return
+    bias = op.inputs[-1]
+    if bias.is_parameter and isinstance(bias.value, torch.Tensor) and bias.value.is_floating_point():
+        bias.value.requires_grad = True
+        job.tensors.append(bias.value)
+
+
 class RoundTuningPass(LearnedStepSizePass):
-    """optim/training.py:866-1034: block-wise round tuning.  Per block (``block_size`` = the reference's depth limit, default 5):
+    """optim/training.py:866-1034: block-wise round tuning (``block_size`` = the reference's depth limit, default 5) on
+    ``LearnedStepSizePass.finetune``'s frame.  What is this pass's own:
 
-    1. ``pre_loss`` (``torch_mean_square_error``), before any delegator exists;
-    2. a :class:`RoundTuningDelegator` on the weight of every Conv / ConvTranspose / Gemm / MatMul / PPQBiasFusedMatMul whose
-       config is ACTIVATED with a tensor scale; the bias of a three-input op is trained as it is;
-    3. ``steps`` of Adam(lr) (or the user's optimizer class) on the sum of ``torch.nn.MSELoss()`` over the block outputs;
-    4. ``post_loss`` (``MSELoss``) with the delegators still registered; a block that ended worse gets its weights AND biases
-       back bit for bit, any other block is finalised: ``W = floor(W / s) * s + (R > .5) * s``.
+    * the pre-loss is ``torch_mean_square_error``, the step loss and the post-loss the sum of ``torch.nn.MSELoss()`` over the
+      block outputs;
+    * a :class:`RoundTuningDelegator` on the weight of every Conv / ConvTranspose / Gemm / MatMul / PPQBiasFusedMatMul whose
+      config is ACTIVATED with a tensor scale; the bias of a three-input op is trained as it is;
+    * a block that ended worse gets its weights AND biases back bit for bit, any other block is finalised:
+      ``W = floor(W / s) * s + (R > .5) * s``.
 
-    The MI355X-side execution choices are LearnedStepSizePass's: the block's weights in ONE launch per step
-    (``group_weights``), the step captured once as a HIP graph with the capturable Adam and replayed (``use_hip_graph``;
-    ``use_hip_graph=False`` is the reference's optimizer).  ``report`` = [(block, pre_loss, post_loss)];
-    ``stats['flipped']`` of ``stats['tuned_elements']`` weight elements of the kept blocks ended on the other side of .5 than
+    ``group_weights``: the block's weights in ONE launch per step.  ``stats['flipped']`` of ``stats['tuned_elements']`` weight elements of the kept blocks ended on the other side of .5 than
     they started: with the default lr and steps R moves by a few hundredths at most, so this is what tells whether the pass
     did anything."""
     def __init__(self, interested_layers: List[str] = [], steps: int = 500, lr: float = 1e-4, block_size: int = 5,
@@ -183,96 +179,56 @@ class RoundTuningPass(LearnedStepSizePass):
         if self._world() != 1:
             raise ValueError('RoundTuningPass runs in one process: data-parallel round tuning is not supported')
 
-    def finetune(self, block, executor, qt_inputs, fp_outputs):
-        """optim/training.py:910-999 for one block."""
-        self._check_block(block)
-        if len(qt_inputs) == 0: raise ValueError('Dataset is empty.')
-        self.enable_block_gradient(block)
-        with self._phase('pre_loss'):
-            pre_loss = compute_block_loss(block, qt_inputs, fp_outputs, executor, torch_mean_square_error)
+    def _delegate(self, block, executor, job: BlockTraining) -> None:
+        """optim/training.py:926-947."""
+        for op in block.rps:
+            if not hasattr(op, 'config') or op.type not in ROUND_TUNING_OP: continue
+            if len(op.inputs) > 1 and op.inputs[1].is_parameter:
+                cfg, var = op.config.input_quantization_config[1], op.inputs[1]
+                if cfg.policy.has_property(P.FLOATING) or cfg.policy.has_property(P.DYNAMIC):
+                    RoundTuningDelegator(config=cfg, var=var)          # raises the reference's TypeError, touches nothing
+                if not isinstance(cfg.scale, torch.Tensor) or state_value(cfg.state) != QuantizationStates.ACTIVATED.value:
+                    self.stats['skipped_weights'] += 1                 # (d): never floored, never delegated
+                elif cfg not in job.delegators:
+                    if not (isinstance(var.value, torch.Tensor) and var.value.is_cuda):
+                        raise TypeError(f'RoundTuningPass: {var.name} is not a CUDA tensor (ppq_amd has no CPU path)')
+                    job.register(executor, cfg, RoundTuningDelegator(config=cfg, var=var))
+            _train_bias(op, job)
 
-        delegators, tensors, biases = {}, [], []
-        try:
-            for op in block.rps:
-                if not hasattr(op, 'config') or op.type not in ROUND_TUNING_OP: continue
-                if len(op.inputs) > 1 and op.inputs[1].is_parameter:
-                    cfg, var = op.config.input_quantization_config[1], op.inputs[1]
-                    if cfg.policy.has_property(P.FLOATING) or cfg.policy.has_property(P.DYNAMIC):
-                        RoundTuningDelegator(config=cfg, var=var)          # raises the reference's TypeError, touches nothing
-                    if not isinstance(cfg.scale, torch.Tensor) or state_value(cfg.state) != QuantizationStates.ACTIVATED.value:
-                        self.stats['skipped_weights'] += 1                 # (d): never floored, never delegated
-                    elif cfg not in delegators:
-                        if not (isinstance(var.value, torch.Tensor) and var.value.is_cuda):
-                            raise TypeError(f'RoundTuningPass: {var.name} is not a CUDA tensor (ppq_amd has no CPU path)')
-                        d = RoundTuningDelegator(config=cfg, var=var)
-                        tensors.append(d.rounding)
-                        executor.register_quantize_delegate(cfg, d)
-                        delegators[cfg] = d
-                if len(op.inputs) == 3 and op.inputs[-1].is_parameter and isinstance(op.inputs[-1].value, torch.Tensor) \
-                        and op.inputs[-1].value.is_floating_point():
-                    op.inputs[-1].value.requires_grad = True
-                    tensors.append(op.inputs[-1].value)
-                    biases.append(op.inputs[-1].value)
-        except Exception:                                  # (c): a refusal half-way leaves the block as it was found
-            for cfg, d in delegators.items():
-                d.withdraw(); executor.remove_quantize_delegate(cfg)
-            self.disable_block_gradient(block)
-            raise
-        uniq, seen = [], set()
-        for t in tensors:
-            if t.requires_grad and id(t) not in seen: seen.add(id(t)); uniq.append(t)
-        if not uniq:                                       # (c): nothing stays requires_grad on the early exit
-            for cfg in delegators: executor.remove_quantize_delegate(cfg)
-            self.disable_block_gradient(block)
-            return 0.0, 0.0
-        loose = [(t, t.detach().clone()) for t in uniq if any(t is b for b in biases)]     # (b): the reference has no backup
+    # The hooks from here to _settle are MXRoundTuningPass's too (it takes them as they are): what differs is named by
+    # _group_class, _weights_stat and _keep.
+    _group_class, _weights_stat = RoundTuningGroup, 'roundtune_weights'
 
-        names = [v.name for v in block.ep.outputs]
-        every = [(d, cfg, d.var) for cfg, d in delegators.items()]
-        members = [m for m in every if RoundTuningGroup.eligible(*m)] if self.group_weights else []
-        group = RoundTuningGroup(members) if members else None
-        self.stats['blocks'] += 1
-        self.stats['roundtune_weights'] += len(every)
-        self.stats['grouped_weights'] += len(members)
-        graphable = self._graphable(qt_inputs, fp_outputs, uniq)
-        opt = self._make_optimizer(uniq, graphable)
+    def _pre_loss(self, block, qt_inputs, fp_outputs, executor) -> float:
+        return compute_block_loss(block, qt_inputs, fp_outputs, executor, torch_mean_square_error)
 
-        def train_step(qt_input, fp_output) -> None:
-            opt.zero_grad()
-            if group is not None: group.prepare()
-            with torch.enable_grad():
-                outs = block_forward(executor, block.rps, qt_input, names, with_gradient=True)
-                loss = 0.0
-                for n, y in zip(names, outs): loss += self.loss_fn(y, fp_output[n])
-            loss.backward()
-            if group is not None: group.flush()
-            opt.step()
+    def _post_loss(self, block, qt_inputs, fp_outputs, executor) -> float:
+        return compute_block_loss(block, qt_inputs, fp_outputs, executor, self.loss_fn)      # training.py:982-984
 
-        try:
-            done = self._train_with_graph(train_step, qt_inputs, fp_outputs) if graphable else 0
-            with self._phase('eager_steps'):
-                for step in range(done, self.steps):
-                    train_step(qt_inputs[step % len(qt_inputs)], fp_outputs[step % len(qt_inputs)])
-                    self.stats['eager_steps'] += 1
-        finally:
-            if group is not None: group.outputs = None  # stale after the last optimizer step: one job per weight from here
-        with self._phase('post_loss'):                 # measured with the delegators still registered (training.py:982-984)
-            post_loss = compute_block_loss(block, qt_inputs, fp_outputs, executor, self.loss_fn)
-        if group is not None: group.release()
-        if self.keep_roundings: self.roundings.update({d.var.name: d.rounding.detach().clone() for d, _, _ in every})
-        keep = not post_loss > pre_loss
+    def _build_groups(self, block, job: BlockTraining, uniq) -> None:
+        every = [(d, cfg, d.var) for cfg, d in job.delegators.items()]
+        self.stats[self._weights_stat] += len(every)
+        members = [m for m in every if self._group_class.eligible(*m)] if self.group_weights else []
+        if members: job.groups = [self._group_class(members)]
+
+    def _step_loss(self, block, names, outs, fp_output):
+        loss = 0.0
+        for n, y in zip(names, outs): loss += self.loss_fn(y, fp_output[n])
+        return loss
+
+    def _settle(self, job: BlockTraining, worse: bool) -> None:
+        """A block that ended worse gets its weights back (the frame: its biases), any other is finalised -- (a): a withdrawn
+        block is NOT finalised -- and counted in ``stats``."""
+        if self.keep_roundings: self.roundings.update({d.var.name: d.rounding.detach().clone() for d in job.delegators.values()})
         flipped = []
-        for cfg, d in delegators.items():
-            if keep:
-                d.finalize()                               # (a): a withdrawn block is NOT finalised
-                flipped.append(d.flipped())
-                self.stats['tuned_elements'] += d.rounding.numel()
-            else: d.withdraw()
-            executor.remove_quantize_delegate(cfg)
-            d.rounding.grad = None
+        for d in job.delegators.values():
+            if worse: d.withdraw(); continue
+            flipped.append(self._keep(d))
+            self.stats['tuned_elements'] += d.rounding.numel()
         if flipped: self.stats['flipped'] += int(torch.stack(flipped).sum())
-        if not keep:
-            with torch.no_grad():
-                for t, backup in loose: t.copy_(backup)
-        self.disable_block_gradient(block)
-        return pre_loss, post_loss
+
+    @ staticmethod
+    def _keep(delegator) -> torch.Tensor:
+        """Finalise ``delegator``; returns its ``flipped()``."""
+        delegator.finalize()
+        return delegator.flipped()

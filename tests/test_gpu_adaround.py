@@ -538,6 +538,32 @@ def test_keep_withdraw_contract_clean_exit_and_one_launch_each_per_step():
     _check_clean(graph, ex)
 
 
+def test_a_training_step_that_raises_leaves_the_block_as_it_was_found():
+    """The failure path of the block-training frame (tests/test_host_block_training.py runs it on the CPU
+    through the MX pass): the third gradient forward of the first block raises -- a Python exception, before that step launches
+    anything -- after two optimizer steps on V and the activation scales.  ``tune_block_weight_scale`` runs before the first
+    delegator exists and is not taken back, so "as found" is the first block after its scale tuning: a twin graph taken to that
+    point.  Every tensor equals the twin's bit for bit, no delegate of the pass is registered, nothing keeps ``requires_grad``."""
+    from block_training_double import StepRefused, assert_same_bits, refuse_gradient_forward, snapshot
+    from ppq_amd.adaround import AdaroundPass
+    from ppq_amd.blocks import split_graph_into_blocks
+    kw = dict(steps=4, use_hip_graph=False, tune_steps=5, is_scale_trainable=True)
+    with _deterministic():
+        twin, _, _ = _setup()
+        p = AdaroundPass(**kw)
+        first = split_graph_into_blocks(twin, twin.topological_sort(), p.block_size)[0]
+        p.enable_block_gradient(first); p.tune_block_weight_scale(first); p.disable_block_gradient(first)
+        graph, ex, batches = _setup()
+        untuned = snapshot(graph)
+        with refuse_gradient_forward(ex, at=3) as seen, pytest.raises(StepRefused, match='gradient forward 3 refused'):
+            AdaroundPass(**kw).optimize(graph, batches, ex)
+    assert seen[0] == 3
+    as_found = snapshot(twin)
+    assert any(not torch.equal(as_found[k], untuned[k]) for k in as_found)           # the tuning did move the first block
+    assert_same_bits(snapshot(graph), as_found)
+    _check_clean(graph, ex)
+
+
 def test_early_exit_leaves_nothing_trainable():
     """(d): a block with nothing to train returns (0, 0) with nothing requires_grad (the reference leaves it set)."""
     from ppq_amd.adaround import AdaroundPass

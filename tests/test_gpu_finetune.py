@@ -237,10 +237,9 @@ def test_yolov6s_int4_blockwise_lsq_and_bias_correction():
           f'block loss {pre:.4f} -> {post:.4f}; kept {sum(1 for _, a, b in lsq.report if b <= a)}/27')
 
 
-def _lsq_variant(steps, **kw):
+def _small_cnn():
     from ppq_amd import harness
     from ppq_amd.calibration import RuntimeCalibrationPass
-    from ppq_amd.lsq import LearnedStepSizePass
     torch.manual_seed(0)
     graph = harness.small_cnn_graph(seed=5, width=16)
     harness.quantize_graph(graph, 'minmax')
@@ -250,9 +249,32 @@ def _lsq_variant(steps, **kw):
     g = torch.Generator().manual_seed(7)
     batches = [torch.rand(8, 3, 24, 24, generator=g).to(DEV) for _ in range(4)]
     RuntimeCalibrationPass(check_steps=False).optimize(graph, dataloader=batches, executor=ex, calib_steps=4)
+    return graph, ex, batches
+
+
+def _lsq_variant(steps, **kw):
+    from ppq_amd.lsq import LearnedStepSizePass
+    graph, ex, batches = _small_cnn()
     p = LearnedStepSizePass(steps=steps, lr=1e-3, **kw)
     p.optimize(graph, batches, ex)
     return graph, ex, p, _snapshot(graph)
+
+
+def test_a_training_step_that_raises_leaves_the_block_as_it_was_found():
+    """The failure path of the block-training frame (tests/test_host_block_training.py runs it on the CPU
+    through the MX pass): the third gradient forward of the first block raises -- a Python exception, before that step launches
+    anything -- after two optimizer steps moved weights, scales and the loose biases.  Everything is back bit for bit, no
+    delegate of the pass is registered, nothing keeps ``requires_grad``."""
+    from block_training_double import StepRefused, assert_nothing_trainable, assert_same_bits, refuse_gradient_forward, snapshot
+    from ppq_amd.lsq import LearnedStepSizePass
+    graph, ex, batches = _small_cnn()
+    before = snapshot(graph)
+    with refuse_gradient_forward(ex, at=3) as seen, pytest.raises(StepRefused, match='gradient forward 3 refused'):
+        LearnedStepSizePass(steps=4, lr=1e-3, use_hip_graph=False).optimize(graph, batches, ex)
+    assert seen[0] == 3
+    assert_same_bits(snapshot(graph), before)
+    assert_nothing_trainable(graph)
+    assert not ex._delegates
 
 
 def test_grouped_weight_launches_equal_the_per_tensor_lsq_path():

@@ -484,6 +484,22 @@ def test_a_block_that_ends_worse_is_restored_bit_for_bit():
         _check_clean(graph, ex)
 
 
+def test_a_training_step_that_raises_leaves_the_block_as_it_was_found():
+    """The failure path of the block-training frame (tests/test_host_block_training.py runs it on the CPU
+    through the MX pass): the third gradient forward of the first block raises -- a Python exception, before that step launches
+    anything -- with the weights floored and two optimizer steps on R and the biases.  Everything is back bit for bit, no
+    delegate of the pass is registered, nothing keeps ``requires_grad``."""
+    from block_training_double import StepRefused, assert_same_bits, refuse_gradient_forward, snapshot
+    from ppq_amd.roundtune import RoundTuningPass
+    graph, ex, batches = _setup()
+    before = snapshot(graph)
+    with refuse_gradient_forward(ex, at=3) as seen, pytest.raises(StepRefused, match='gradient forward 3 refused'):
+        RoundTuningPass(steps=4, lr=1e-2, use_hip_graph=False).optimize(graph, batches, ex)
+    assert seen[0] == 3
+    assert_same_bits(snapshot(graph), before)
+    _check_clean(graph, ex)
+
+
 def test_early_exit_leaves_nothing_trainable(monkeypatch):
     """(c): a block with nothing to train returns (0, 0) with nothing requires_grad (the reference leaves it set)."""
     from ppq_amd import roundtune
