@@ -4,7 +4,7 @@ Mirror of ppq/quantization/qfunction/{__init__,linear,floating}.py -- same funct
 dispatch on the TensorQuantizationConfig policy bits and state, same straight-through backward
 (``return dy, None ...`` linear.py:48-50), same errors.  The difference: there is no PyTorch
 arithmetic branch; every activated config runs ``CUDA.LinearQuantize_T/C`` or
-``CUDA.FloatingQuantize_T/C`` (ppq_amd/ffi.py), and a CPU tensor raises.
+``CUDA.FloatingQuantize_T/C`` (ppq_amd/ffi/), and a CPU tensor raises.
 
 ``TorchExecutor.quantize_function`` (ppq/executor/torch.py:610-613) calls ``PPQuantFunction`` by
 default, so assigning ``executor._default_quant_fn = ppq_amd.qfunction.PPQuantFunction`` -- or just
