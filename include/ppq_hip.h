@@ -922,6 +922,18 @@ int ppqhip_mx_conv2d_fused(const uint8_t* x_elements, const uint8_t* x_scales, i
                            int64_t o, int64_t kh, int64_t kw, int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
                            int64_t dil_h, int64_t dil_w, void* stream);
 
+/* GEMM on two MXINT8 operands (ppq_amd/mx.py mx_int8_matmul / mx_int8_linear; ADDED under ABI 4) ------------ */
+/* c[m, n] (float32, row-major) = A[m, k] . B[n, k]^T (+ bias[n]) on v_mfma_i32_16x16x32_i8.  Both operands are PPQHIP_MXINT8, packed
+ * along their LAST axis exactly as ppqhip_mx_pack leaves them: elements [rows, nb * 32] (two's-complement codes, value code / 64; 0x80
+ * is -128), scales [rows, nb], nb = ceil(k / 32).  Per output and block b the integer dot product P_b is exact; t_b = P_b *
+ * 2^(sa_b + sb_b - 266) is rounded ONCE to float32 (nearest even; subnormals kept, overflow +-Inf); c = (((+0 + t_0) + t_1) + ...) in
+ * float32 in block order, then + bias[n] (may be NULL) as one more float32 add.  One accumulation order, no atomics, no split-K: two
+ * calls give identical bits.  An output is the quiet NaN 0x7fc00000 exactly where its row of A or its row of B holds a scale code 0xFF.
+ * Refused before any launch: negative sizes or sizes above 2^31 - 1, null pointers (bias excepted), elements or c not 16-byte
+ * aligned, c overlapping any input.  m == 0 or n == 0 launches nothing; k == 0 writes the bias (or 0).  Booked under "mx_int8_gemm". */
+int ppqhip_mx_int8_gemm(const uint8_t* a_elements, const uint8_t* a_scales, const uint8_t* b_elements, const uint8_t* b_scales,
+                        const float* bias, float* c, int64_t m, int64_t n, int64_t k, void* stream);
+
 /* ---- pointwise (1x1) convolution on the FP32-input MFMA (ADDED under ABI 4) ---------------------------------
  * y[n, o, oh, ow] = sum_k w[o, k] x[n, k, oh * stride, ow * stride] (+ bias[o]) for contiguous NCHW float32 x [n, c, h, wd],
  * w [o, c] (a [o, c, 1, 1] convolution weight as it lies) and y [n, o, ho, wo], ho = (h - 1) / stride + 1, wo likewise; no padding,

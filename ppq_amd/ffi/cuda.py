@@ -6,7 +6,7 @@ from .._lib import lib
 from ._base import _KERNEL_FAILURE, _DeviceOf, _check, _f32, _ptr, _raise, _stream
 from .extension import HIP_EXTENSION
 from .mx import (MX_BLOCK, _mx_axis, _mx_codes_like, _mx_conv_args, _mx_dense, _mx_fused_args, _mx_fused_outputs, _mx_geometry,
-                 _mx_matmul_args, mx_format_arg, mx_format_id, mx_packed_shapes)
+                 _mx_int8_matmul_args, _mx_matmul_args, mx_format_arg, mx_format_id, mx_packed_shapes)
 from .seam import CUDA_COMPLIER
 
 
@@ -360,6 +360,20 @@ class CUDA:
                                             _ptr(bias), _ptr(residual), 1 if relu else 0, _ptr(out), _ptr(elements), _ptr(scales),
                                             fo, m, n, k, _stream()))
         return out, elements, scales
+
+    @ staticmethod
+    def MXInt8Matmul(a_elements, a_scales, b_elements, b_scales, k: int, bias=None):
+        """``A[M, k] . B[N, k]^T (+ bias[N])`` as float32 ``[M, N]`` on the int8 MFMA, rescaled per block.
+        Both operands are MXINT8, packed along their last axis as ``MXPack`` leaves them: ``elements [rows, nb * 32]`` and ``scales
+        [rows, nb]``, uint8, nb = ceil(k / 32).  Per block the integer dot product is exact, its scaled value is rounded once to
+        float32 and the blocks are added in order: the bits of ``tests/mx_int8_gemm_reference.py``.  Non-contiguous inputs are
+        copied, and so is an ``elements`` tensor whose data does not start on a 16-byte boundary."""
+        a_elements, a_scales, b_elements, b_scales, k, bias, m, n = _mx_int8_matmul_args(a_elements, a_scales, b_elements, b_scales, k, bias)
+        out = torch.empty([m, n], dtype=torch.float32, device=a_elements.device)
+        with _DeviceOf(out):
+            _raise(lib.ppqhip_mx_int8_gemm(a_elements.data_ptr(), a_scales.data_ptr(), b_elements.data_ptr(), b_scales.data_ptr(),
+                                           _ptr(bias), out.data_ptr(), m, n, k, _stream()))
+        return out
 
     @ staticmethod
     def MXConv2d(x_elements, x_scales, x_format, w_elements, w_scales, w_format, c: int, bias=None, stride=(1, 1), padding=(0, 0),

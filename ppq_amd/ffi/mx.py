@@ -1,6 +1,6 @@
 """OCP Microscaling: fake quant, round tuning on the MX grid, the packed export and the operand checks of the MX MFMA bindings
 (include/ppq_hip.h ppqhip_mx_fq[_multi], ppqhip_mx_round_*_multi, ppqhip_mx_pack / ppqhip_mx_unpack and their _multi forms;
-DESIGN.md sections 9.13 - 9.18)."""
+DESIGN.md sections 9.13 - 9.19)."""
 import math
 from typing import List
 
@@ -228,6 +228,31 @@ def _mx_matmul_args(a_elements, a_scales, a_format, b_elements, b_scales, b_form
         2, 'k', (('A', a_elements, a_scales, fa), ('B', b_elements, b_scales, fb)),
         lambda: ([a_elements.shape[0], k], [b_elements.shape[0], k]), bias)
     return a_elements, a_scales, fa, b_elements, b_scales, fb, k, bias, m, n
+
+
+def _mx_int8_matmul_args(a_elements, a_scales, b_elements, b_scales, k, bias):
+    """The checks of ``CUDA.MXInt8Matmul``; returns the tensors as the kernel takes them, k, M and N.  Unlike ``MXMatmul`` nothing is
+    copied behind the caller's back: a non-contiguous operand is refused."""
+    k = int(k)
+    if k <= 0: raise RuntimeError(_KERNEL_FAILURE + f'k must be positive, got {k}')
+    dev, out = a_elements.device if isinstance(a_elements, torch.Tensor) else None, []
+    for op, e, s in (('A', a_elements, a_scales), ('B', b_elements, b_scales)):
+        for kind, t in (('elements', e), ('scales', s)):
+            _check(t, torch.uint8, f'{op} {kind}(Expect to be UINT8)')
+            if t.dim() != 2: raise RuntimeError(_KERNEL_FAILURE + f'{op} {kind} must be 2-d, got {list(t.shape)}')
+            if t.device != dev: raise RuntimeError(_KERNEL_FAILURE + f'{op} {kind} is on another device')
+            if not t.is_contiguous(): raise RuntimeError(_KERNEL_FAILURE + f'{op} {kind} must be contiguous')
+        eshape, sshape = mx_packed_shapes([e.shape[0], k], 1, MX_FORMATS['MXINT8'])
+        if list(e.shape) != eshape or list(s.shape) != sshape:
+            raise RuntimeError(_KERNEL_FAILURE + f'{op}: elements / scales of shape {list(e.shape)} / {list(s.shape)}, expected {eshape} / {sshape} for k = {k}')
+        out += [e.clone() if e.data_ptr() % 16 else e, s]                                # the kernel's 16-byte loads; the allocator aligns
+    m, n = a_elements.shape[0], b_elements.shape[0]
+    if bias is not None:
+        _f32(bias, 'Bias')
+        if list(bias.shape) != [n]: raise RuntimeError(_KERNEL_FAILURE + f'bias of shape {list(bias.shape)}, expected [{n}]')
+        if bias.device != dev: raise RuntimeError(_KERNEL_FAILURE + 'bias is on another device')
+        bias = bias.contiguous()
+    return (*out, k, bias, m, n)
 
 
 def _mx_conv_args(x_elements, x_scales, x_format, w_elements, w_scales, w_format, c, bias, stride, padding, dilation):

@@ -465,6 +465,64 @@ def mx_linear(x: torch.Tensor, weight: MXTensor, activation_format, bias: torch.
     return mx_matmul(mx_quantize(x, activation_format, -1, use_kernels=use_kernels, scale_rule=scale_rule), weight, bias, use_kernels, residual, relu, out_format, out_float)
 
 
+# ---- GEMM on two MXINT8 tensors ----------------------------------------------------------------------------
+def _check_int8_matmul(a, b, bias):
+    """The argument checks of ``mx_int8_matmul``; returns (lead shape of a, N, K)."""
+    for name, t in (('a', a), ('b', b)):
+        if not isinstance(t, MXTensor): raise TypeError(f'mx_int8_matmul: {name}: expected an MXTensor, got {type(t)}')
+        if t.format is not MXFormat.MXINT8:
+            raise RuntimeError(f'mx_int8_matmul: {name} is {t.format.name}, not MXINT8; mx_matmul multiplies the float formats')
+        if t.axis != len(t.shape) - 1:
+            raise RuntimeError(f'mx_int8_matmul: {name} of shape {list(t.shape)} is packed along axis {t.axis}, not along its last axis')
+    if len(b.shape) != 2: raise RuntimeError(f'mx_int8_matmul: b must be 2-d [N, K], got shape {list(b.shape)}')
+    if a.shape[-1] != b.shape[-1]: raise RuntimeError(f'mx_int8_matmul: K mismatch: a has {a.shape[-1]}, b has {b.shape[-1]}')
+    if a.device != b.device: raise RuntimeError(f'mx_int8_matmul: a is on {a.device}, b on {b.device}')
+    n = b.shape[0]
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32: raise RuntimeError('mx_int8_matmul: bias must be a float32 tensor')
+        if list(bias.shape) != [n]: raise RuntimeError(f'mx_int8_matmul: bias of shape {list(bias.shape)}, expected [{n}]')
+    return list(a.shape[:-1]), n, a.shape[-1]
+
+
+def _mx_int8_matmul_torch(ae, as_, be, bs, bias):
+    """The contract of DESIGN.md section 9.19 in torch ops on ``[M, nb * 32]`` / ``[M, nb]`` and ``[N, nb * 32]`` / ``[N, nb]``: per block
+    the integer dot product (exact in float64: at most 2^19), times 2^(sa + sb - 266) in float64 (exact), ONE rounding to float32, then
+    the float32 chain over the blocks in order.  Not ``torch.ldexp`` on float32: it multiplies by a float32 2^e, which does not exist
+    for the extreme exponents."""
+    m, n, nb = ae.shape[0], be.shape[0], as_.shape[-1]
+    ka, kb = ae.to(torch.int16).reshape(m, nb, MX_BLOCK), be.to(torch.int16).reshape(n, nb, MX_BLOCK)
+    ka, kb = torch.where(ka >= 128, ka - 256, ka).to(torch.float64), torch.where(kb >= 128, kb - 256, kb).to(torch.float64)
+    sa, sb = as_.to(torch.int32), bs.to(torch.int32)
+    acc = torch.zeros(m, n, dtype=torch.float32, device=ae.device)
+    for blk in range(nb):
+        dot = ka[:, blk] @ kb[:, blk].t()
+        e = (sa[:, blk, None] + sb[None, :, blk] - 266).to(torch.float64)
+        acc = acc + (dot * torch.pow(torch.full_like(e, 2.0), e)).to(torch.float32)
+    if bias is not None: acc = acc + bias
+    nan = (sa == 0xff).any(dim=1)[:, None] | (sb == 0xff).any(dim=1)[None, :]
+    return torch.where(nan, _bits_to_float(torch.full_like(acc, 0, dtype=torch.int32) + 0x7fc00000), acc)
+
+
+def mx_int8_matmul(a: MXTensor, b: MXTensor, bias: torch.Tensor = None, use_kernels: bool = True) -> torch.Tensor:
+    """``a . b^T (+ bias)`` in float32 on two MXINT8 tensors: ``a`` is ``lead + [K]``, ``b`` is ``[N, K]``, both packed along their
+    last axis; the result is ``lead + [N]``.  Per output and block of 32 the integer dot product is exact; scaled by the two block
+    scales it is rounded once to float32, and the blocks are added in float32 in order, then the bias.  An
+    output whose row of ``a`` or of ``b`` holds a NaN block (scale code 0xFF) is NaN.
+    ``use_kernels=True``: the packed bytes go to the int8 MFMA as they are (``CUDA.MXInt8Matmul``; the tensors must be on the GPU).
+    ``False``: the same contract in torch ops on any device -- identical bits.  The five float formats are ``mx_matmul``'s."""
+    lead, n, k = _check_int8_matmul(a, b, bias)
+    ae, as_ = a.elements.reshape(-1, a.elements.shape[-1]), a.scales.reshape(-1, a.scales.shape[-1])
+    if use_kernels: y = CUDA.MXInt8Matmul(ae.contiguous(), as_.contiguous(), b.elements.contiguous(), b.scales.contiguous(), k, bias)
+    else: y = _mx_int8_matmul_torch(ae, as_, b.elements, b.scales, bias)
+    return y.reshape(lead + [n])
+
+
+def mx_int8_linear(x: torch.Tensor, weight: MXTensor, bias: torch.Tensor = None, use_kernels: bool = True, scale_rule=MXScaleRule.FLOOR) -> torch.Tensor:
+    """A linear layer on an MXINT8 weight ``[N, K]``: ``mx_quantize(x, 'MXINT8', -1, scale_rule=...)``, then ``mx_int8_matmul`` -- two
+    launches, the bias added in the GEMM's epilogue."""
+    return mx_int8_matmul(mx_quantize(x, MXFormat.MXINT8, -1, use_kernels=use_kernels, scale_rule=scale_rule), weight, bias, use_kernels)
+
+
 # ---- convolution on the packed tensors (DESIGN.md section 9.15) --------------------------------------------------------------------
 def _pair(value, name: str, least: int):
     """An int or a pair of ints (h, w), each at least ``least``."""
