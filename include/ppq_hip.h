@@ -934,6 +934,26 @@ int ppqhip_mx_conv2d_fused(const uint8_t* x_elements, const uint8_t* x_scales, i
 int ppqhip_mx_int8_gemm(const uint8_t* a_elements, const uint8_t* a_scales, const uint8_t* b_elements, const uint8_t* b_scales,
                         const float* bias, float* c, int64_t m, int64_t n, int64_t k, void* stream);
 
+/* Convolution on two MXINT8 operands (ppq_amd/mx.py mx_int8_conv2d / mx_int8_conv2d_packed; ADDED under ABI 4) */
+/* y[n, oh, ow, o] (float32: the channels-last storage of [n, o, oh, ow]) = conv2d(x[n, c, h, w], w[o, c, kh, kw]) (+ bias[o]) on
+ * v_mfma_i32_16x16x32_i8, as an implicit GEMM: no im2col buffer.  Both operands are PPQHIP_MXINT8, packed along axis 1 exactly as
+ * ppqhip_mx_pack leaves them (the block axis stored last): x elements [n, h, w, nbc * 32] and scales [n, h, w, nbc], w elements
+ * [o, kh, kw, nbc * 32] and scales [o, kh, kw, nbc], nbc = ceil(c / 32).  Sizes and geometry are those of ppqhip_mx_conv2d: oh =
+ * (h + 2 pad_h - dil_h (kh - 1) - 1) / stride_h + 1, likewise ow; padding is symmetric; groups = 1.  Row (n, oy, ox) of the implicit
+ * GEMM has the nb' = kh * kw * nbc blocks (ky, kx, channel block) in that order, and y has exactly the bits of ppqhip_mx_int8_gemm on
+ * the gathered rows: per block the exact integer dot product, t_b = P_b * 2^(sx_b + sw_b - 266) rounded ONCE to float32, the float32
+ * chain from +0 in ascending block order, then + bias[o] (may be NULL).  A tap in the padding is not read and adds +0, which leaves
+ * the chain as it is.  One accumulation order, no atomics, no split-K: two calls give identical bits.  An output is the quiet NaN
+ * 0x7fc00000 exactly where its window covers, INSIDE the image, a block of x whose scale code is 0xFF, or where its output channel of w
+ * holds one; padding never makes a NaN.
+ * Refused before any launch: negative sizes; sizes, n oh ow, kh kw nbc, the blocks of x or the workgroup count above 2^31 - 1; kernel
+ * size, stride or dilation below 1; a window that does not fit the padded input (oh or ow < 1); null pointers (bias excepted);
+ * elements or y not 16-byte aligned; y overlapping any input.  n == 0 or o == 0 launches nothing; c == 0 (or an input without a
+ * pixel) reads nothing and writes the bias (or 0).  Booked under "mx_int8_conv": packed x once, packed w and 4 m o bytes of y. */
+int ppqhip_mx_int8_conv2d(const uint8_t* x_elements, const uint8_t* x_scales, const uint8_t* w_elements, const uint8_t* w_scales,
+                          const float* bias, float* y, int64_t n, int64_t c, int64_t h, int64_t w, int64_t o, int64_t kh, int64_t kw,
+                          int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, void* stream);
+
 /* ---- pointwise (1x1) convolution on the FP32-input MFMA (ADDED under ABI 4) ---------------------------------
  * y[n, o, oh, ow] = sum_k w[o, k] x[n, k, oh * stride, ow * stride] (+ bias[o]) for contiguous NCHW float32 x [n, c, h, wd],
  * w [o, c] (a [o, c, 1, 1] convolution weight as it lies) and y [n, o, ho, wo], ho = (h - 1) / stride + 1, wo likewise; no padding,

@@ -22,24 +22,15 @@
 // Scales: in the C layout a lane needs sb of its own column but sa of the four rows 4 (l >> 4) + q, which are not the row it holds
 // as A; both come from the LDS scale stage -- [row][4 codes], so the four rows' codes of a chunk are one 16-byte read.
 // NaN: a scale code 0xFF seen while the scales are staged flags the row (column); flagged outputs are written as 0x7fc00000.
+// What the kernel shares with mx_int8_conv_kernel (mx_int8_conv.hip) is in mx_int8_tile.hpp: the stage's geometry, the multiply of a
+// staged chunk, the NaN flags and the store of the tile; what is here is where a thread's share of a chunk lies in two packed operands.
 #include "common.hpp"
 #include "job_table.hpp"
 #include "mx_mfma.hpp"
+#include "mx_int8_tile.hpp"
 
 namespace ppqhip {
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-
-constexpr uint32_t kI8Pitch = kGemmStepBlocks * kMxBlock + 16u;                  // 144: a staged row of 4 blocks, padded
-constexpr uint32_t kI8TileBytes = kGemmEdge * kI8Pitch;                          // 64 rows of one operand
-constexpr uint32_t kI8ScaleBytes = kGemmEdge * kGemmStepBlocks;                  // their 4 codes each
-constexpr uint32_t kI8BufBytes = 2u * kI8TileBytes + 2u * kI8ScaleBytes;         // A, B, A's scales, B's scales
-constexpr int kI8ExpBias = 2 * 127 + 12;                                         // the two E8M0 biases and the two 1 / 64
-static_assert(kI8Pitch % 16u == 0 && kI8BufBytes % 16u == 0, "16-byte stores into the stage");
-static_assert(kGemmEdge * kGemmStepBlocks * kMxBlock == 2u * 16u * (uint32_t)kBlock, "two 16-byte loads per thread and operand");
-static_assert(2u * kI8ScaleBytes == 2u * (uint32_t)kBlock, "two scale codes per thread");
 
 struct MxInt8Args {
     const uint8_t* ae; const uint8_t* as;         // A: elements [m, nb * 32], scales [m, nb]
@@ -48,12 +39,6 @@ struct MxInt8Args {
     float* c;                                     // [m, n]
     uint32_t m, n, nb;
     FastDiv tiles_n;
-};
-
-// what a thread carries from global memory to LDS for one chunk: 2 x 16 bytes of A, 2 x 16 bytes of B, 2 scale codes
-struct Staged {
-    v4u a0, a1, b0, b1;                         // the thread's segment of rows t >> 3 and 32 + (t >> 3) of A and of B
-    uint32_t s;                                   // the codes of blocks kb0 + 2 pair and + 1 in bytes 0 and 1
 };
 
 // Where a thread's share of a chunk lies: element segment t & 7 (16 bytes; block (t & 7) >> 1 of the chunk) of rows t >> 3 and
@@ -91,54 +76,8 @@ struct StageMap {
         return (c0 == 0xffu && (!TAIL || s0 < nb)) || (c1 == 0xffu && (!TAIL || s1 < nb));
     }
 
-    __device__ __forceinline__ void store(uint8_t* buf, const Staged& st) const {
-        *reinterpret_cast<v4u*>(buf + lds_e[0]) = st.a0; *reinterpret_cast<v4u*>(buf + lds_e[1]) = st.a1;
-        *reinterpret_cast<v4u*>(buf + kI8TileBytes + lds_e[0]) = st.b0; *reinterpret_cast<v4u*>(buf + kI8TileBytes + lds_e[1]) = st.b1;
-        *reinterpret_cast<uint16_t*>(buf + lds_s) = (uint16_t)st.s;
-    }
+    __device__ __forceinline__ void store(uint8_t* buf, const Staged& st) const { store_staged(buf, lds_e, lds_s, st); }
 };
-
-// The wave's 2 x 2 tiles over the `live` (1 .. 4; 4 unless TAIL) blocks of the chunk staged in buf: per block and tile one MFMA
-// from a zero accumulator, then per output the conversion, the scaling by 2^(sa + sb - 266) and the float32 add.
-template <bool TAIL>
-__device__ __forceinline__ void chunk_tiles(const uint8_t* buf, uint32_t wm, uint32_t wn, uint32_t r, uint32_t grp, uint32_t live,
-                                            v4f (&acc)[kGemmWaveTiles][kGemmWaveTiles]) {
-    constexpr int T = kGemmWaveTiles;
-    const uint8_t* la = buf + (wm + r) * kI8Pitch + grp * 8u;
-    const uint8_t* lb = buf + kI8TileBytes + (wn + r) * kI8Pitch + grp * 8u;
-    uint4 sa[T]; uint32_t sb[T];                                                 // sa[i]: rows 4 grp + q of tile i, 4 codes each
-#pragma unroll
-    for (int i = 0; i < T; i++) {
-        sa[i] = *reinterpret_cast<const uint4*>(buf + 2u * kI8TileBytes + (wm + i * kGemmTile + grp * 4u) * kGemmStepBlocks);
-        sb[i] = *reinterpret_cast<const uint32_t*>(buf + 2u * kI8TileBytes + kI8ScaleBytes + (wn + i * kGemmTile + r) * kGemmStepBlocks);
-    }
-#pragma unroll
-    for (uint32_t b = 0; b < kGemmStepBlocks; b++) {
-        if (TAIL && b >= live) break;                                            // wave-uniform
-        long a[T], bb[T];
-#pragma unroll
-        for (int i = 0; i < T; i++) {
-            a[i] = *reinterpret_cast<const long*>(la + i * kGemmTile * kI8Pitch + b * kMxBlock);
-            bb[i] = *reinterpret_cast<const long*>(lb + i * kGemmTile * kI8Pitch + b * kMxBlock);
-        }
-        int ea[T][4], eb[T];
-#pragma unroll
-        for (int i = 0; i < T; i++) {
-            const uint32_t w[4] = {sa[i].x, sa[i].y, sa[i].z, sa[i].w};
-#pragma unroll
-            for (int q = 0; q < 4; q++) ea[i][q] = (int)((w[q] >> (8u * b)) & 0xffu);
-            eb[i] = (int)((sb[i] >> (8u * b)) & 0xffu) - kI8ExpBias;
-        }
-#pragma unroll
-        for (int i = 0; i < T; i++)
-#pragma unroll
-            for (int j = 0; j < T; j++) {
-                const v4i p = __builtin_amdgcn_mfma_i32_16x16x32_i8(a[i], bb[j], v4i{0, 0, 0, 0}, 0, 0, 0);
-#pragma unroll
-                for (int q = 0; q < 4; q++) acc[i][j][q] = acc[i][j][q] + __builtin_ldexpf((float)p[q], ea[i][q] + eb[j]);
-            }
-    }
-}
 
 __global__ __launch_bounds__(kBlock) void mx_int8_gemm_kernel(const MxInt8Args g) {
     constexpr int T = kGemmWaveTiles;
@@ -156,7 +95,7 @@ __global__ __launch_bounds__(kBlock) void mx_int8_gemm_kernel(const MxInt8Args g
     for (int i = 0; i < T; i++)
 #pragma unroll
         for (int j = 0; j < T; j++) acc[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
-    if (t < 2u * kGemmEdge) nan_flags[t] = 0u;
+    clear_nan_flags(nan_flags, t);
 
     bool bad = false;
     if (g.nb > 0u) {                                                             // nb == 0: the operands may be null
@@ -177,28 +116,12 @@ __global__ __launch_bounds__(kBlock) void mx_int8_gemm_kernel(const MxInt8Args g
             if (more) map.store(stage[(c + 1u) & 1u], st);                       // last read before the barrier that ended chunk c - 1
             __syncthreads();
         }
-        if (bad) nan_flags[(t >> 7) * kGemmEdge + ((t & 127u) >> 1)] = 1u;       // after the zeroing: at least one barrier lies between
+        raise_nan_flag(nan_flags, t, bad);
     }
     __syncthreads();
     if (!busy) return;
 
-#pragma unroll
-    for (int j = 0; j < T; j++) {
-        const uint32_t lc = wn + j * kGemmTile + r, col = col0 + lc;
-        if (col >= g.n) continue;
-        const float bias = g.bias != nullptr ? g.bias[col] : 0.f;
-        const bool col_nan = nan_flags[kGemmEdge + lc] != 0u;
-#pragma unroll
-        for (int i = 0; i < T; i++) {
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const uint32_t lr = wm + i * kGemmTile + grp * 4u + q, row = row0 + lr;
-                const bool nan = col_nan || nan_flags[lr] != 0u;
-                const float v = g.bias != nullptr ? acc[i][j][q] + bias : acc[i][j][q];
-                if (row < g.m) g.c[(size_t)row * g.n + col] = nan ? __uint_as_float(0x7fc00000u) : v;
-            }
-        }
-    }
+    store_tiles(acc, nan_flags, g.bias, g.c, g.m, g.n, row0, col0, wm, wn, r, grp);
 }
 
 }  // namespace

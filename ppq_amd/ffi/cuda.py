@@ -6,7 +6,7 @@ from .._lib import lib
 from ._base import _KERNEL_FAILURE, _DeviceOf, _check, _f32, _ptr, _raise, _stream
 from .extension import HIP_EXTENSION
 from .mx import (MX_BLOCK, _mx_axis, _mx_codes_like, _mx_conv_args, _mx_dense, _mx_fused_args, _mx_fused_outputs, _mx_geometry,
-                 _mx_int8_matmul_args, _mx_matmul_args, mx_format_arg, mx_format_id, mx_packed_shapes)
+                 _mx_int8_conv_args, _mx_int8_matmul_args, _mx_matmul_args, mx_format_arg, mx_format_id, mx_packed_shapes)
 from .seam import CUDA_COMPLIER
 
 
@@ -411,6 +411,23 @@ class CUDA:
                                               _ptr(bias), _ptr(residual), 1 if relu else 0, _ptr(out), _ptr(elements), _ptr(scales),
                                               fo, *geo[:13], _stream()))
         return (out.permute(0, 3, 1, 2) if out is not None else None), elements, scales
+
+    @ staticmethod
+    def MXInt8Conv2d(x_elements, x_scales, w_elements, w_scales, c: int, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1)):
+        """``conv2d(x[N, c, H, W], w[O, c, kh, kw]) (+ bias[O])`` as float32 ``[N, O, OH, OW]`` with channels-last strides, on the int8
+        MFMA as an implicit GEMM, rescaled per block.  Both operands are MXINT8, packed along axis 1 as
+        ``MXPack`` leaves them: x ``elements [N, H, W, nbc * 32]`` / ``scales [N, H, W, nbc]``, w ``elements [O, kh, kw, nbc * 32]`` /
+        ``scales [O, kh, kw, nbc]``, uint8, nbc = ceil(c / 32).  The result has the bits of ``MXInt8Matmul`` on the gathered rows
+        (``tests/mx_int8_conv_reference.py``); a tap in the padding is not read.  ``stride``, ``padding`` (symmetric) and ``dilation``
+        are (h, w) pairs.  Non-contiguous inputs are copied, and so is an ``elements`` tensor whose data does not start on a 16-byte
+        boundary."""
+        x_elements, x_scales, w_elements, w_scales, bias, geo = _mx_int8_conv_args(x_elements, x_scales, w_elements, w_scales, c, bias, stride, padding, dilation)
+        n, o = geo[0], geo[4]
+        out = torch.empty([n, geo[-2], geo[-1], o], dtype=torch.float32, device=x_elements.device)
+        with _DeviceOf(out):
+            _raise(lib.ppqhip_mx_int8_conv2d(x_elements.data_ptr(), x_scales.data_ptr(), w_elements.data_ptr(), w_scales.data_ptr(),
+                                             _ptr(bias), out.data_ptr(), *geo[:13], _stream()))
+        return out.permute(0, 3, 1, 2)
 
     @ staticmethod
     def Sync():

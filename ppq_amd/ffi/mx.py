@@ -273,6 +273,14 @@ def _mx_conv_args(x_elements, x_scales, x_format, w_elements, w_scales, w_format
     return x_elements, x_scales, fx, w_elements, w_scales, fw, bias, (n, c, h, w, o, kh, kw, sh, sw, ph, pw, dh, dw, oh, ow)
 
 
+def _mx_int8_conv_args(x_elements, x_scales, w_elements, w_scales, c, bias, stride, padding, dilation):
+    """The checks of ``CUDA.MXInt8Conv2d``: those of ``_mx_conv_args`` with both operands MXINT8 (32 bytes per block); returns the
+    tensors as the kernel takes them, the bias and ``geo``."""
+    x_elements, x_scales, _, w_elements, w_scales, _, bias, geo = _mx_conv_args(x_elements, x_scales, 'MXINT8', w_elements, w_scales, 'MXINT8', c, bias,
+                                                                                stride, padding, dilation)
+    return x_elements, x_scales, w_elements, w_scales, bias, geo
+
+
 def _mx_fused_args(out_format, out_float, residual, shape, device):
     """The checks the fused bindings add: returns the id of ``out_format`` (a float format; without one nothing is packed and the id
     is a placeholder) and the residual, float32 of ``shape`` on ``device``."""

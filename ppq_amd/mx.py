@@ -524,12 +524,12 @@ def mx_int8_linear(x: torch.Tensor, weight: MXTensor, bias: torch.Tensor = None,
 
 
 # ---- convolution on the packed tensors --------------------------------------------------------------------
-def _pair(value, name: str, least: int):
+def _pair(value, name: str, least: int, what: str = 'mx_conv2d'):
     """An int or a pair of ints (h, w), each at least ``least``."""
     pair = (value, value) if isinstance(value, int) and not isinstance(value, bool) else tuple(value)
     if len(pair) != 2 or not all(isinstance(v, int) and not isinstance(v, bool) for v in pair):
-        raise RuntimeError(f'mx_conv2d: {name} must be an int or a pair of ints, got {value!r}')
-    if min(pair) < least: raise RuntimeError(f'mx_conv2d: {name} must be at least {least}, got {value!r}')
+        raise RuntimeError(f'{what}: {name} must be an int or a pair of ints, got {value!r}')
+    if min(pair) < least: raise RuntimeError(f'{what}: {name} must be at least {least}, got {value!r}')
     return pair
 
 
@@ -602,6 +602,77 @@ def mx_conv2d(x: torch.Tensor, weight: MXTensor, activation_format, bias: torch.
     if isinstance(x, torch.Tensor) and x.dim() != 4: raise RuntimeError(f'mx_conv2d: x must be 4-d [N, C, H, W], got shape {list(x.shape)}')
     return mx_conv2d_packed(mx_quantize(x, activation_format, 1, use_kernels=use_kernels, scale_rule=scale_rule), weight, bias, stride, padding, dilation, use_kernels,
                             residual, relu, out_format, out_float)
+
+
+# ---- convolution on two MXINT8 tensors ----------------------------------------------------------------------
+def _check_int8_conv(x, w, bias, stride, padding, dilation):
+    """The argument checks of ``mx_int8_conv2d_packed``, those of ``_check_conv``; returns (stride, padding, dilation, (OH, OW))."""
+    what = 'mx_int8_conv2d'
+    for name, t in (('x', x), ('w', w)):
+        if not isinstance(t, MXTensor): raise TypeError(f'{what}: {name}: expected an MXTensor, got {type(t)}')
+        if t.format is not MXFormat.MXINT8: raise RuntimeError(f'{what}: {name} is {t.format.name}, not MXINT8; mx_conv2d convolves the float formats')
+        if len(t.shape) != 4: raise RuntimeError(f'{what}: {name} must be 4-d, got shape {list(t.shape)}')
+        if t.axis != 1: raise RuntimeError(f'{what}: {name} of shape {list(t.shape)} is packed along axis {t.axis}, not along its channels (axis 1)')
+    if x.shape[1] != w.shape[1]:
+        raise RuntimeError(f'{what}: C mismatch: x has {x.shape[1]} channels, w has {w.shape[1]} (groups must be 1)')
+    if x.device != w.device: raise RuntimeError(f'{what}: x is on {x.device}, w on {w.device}')
+    if 0 in x.shape or 0 in w.shape: raise RuntimeError(f'{what}: empty operand: x {list(x.shape)}, w {list(w.shape)}')
+    stride, padding, dilation = _pair(stride, 'stride', 1, what), _pair(padding, 'padding', 0, what), _pair(dilation, 'dilation', 1, what)
+    out = tuple((x.shape[2 + i] + 2 * padding[i] - dilation[i] * (w.shape[2 + i] - 1) - 1) // stride[i] + 1 for i in range(2))
+    if min(out) < 1:
+        raise RuntimeError(f'{what}: a {w.shape[2]} x {w.shape[3]} kernel with dilation {dilation} does not fit an input of '
+                           f'{x.shape[2]} x {x.shape[3]} padded by {padding}')
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32: raise RuntimeError(f'{what}: bias must be a float32 tensor')
+        if list(bias.shape) != [w.shape[0]]: raise RuntimeError(f'{what}: bias of shape {list(bias.shape)}, expected [{w.shape[0]}]')
+    return stride, padding, dilation, out
+
+
+def _mx_int8_gather_torch(x: MXTensor, kernel, stride, padding, dilation, out):
+    """The packed A operand of the implicit GEMM by indexing: elements ``[M, nb' * 32]`` and scales
+    ``[M, nb']``, rows (n, oy, ox), blocks (ky, kx, channel block); zero bytes under scale code 127 where a tap is in the padding."""
+    (n, _, h, w), (kh, kw), (sh, sw), (ph, pw), (dh, dw), (oh, ow) = x.shape, kernel, stride, padding, dilation, out
+    ar = lambda k: torch.arange(k, device=x.device)
+    iy = (ar(oh) * sh - ph)[:, None] + (ar(kh) * dh)[None, :]                            # [OH, kh]
+    ix = (ar(ow) * sw - pw)[:, None] + (ar(kw) * dw)[None, :]                            # [OW, kw]
+    inside = ((iy >= 0) & (iy < h))[:, None, :, None] & ((ix >= 0) & (ix < w))[None, :, None, :]       # [OH, OW, kh, kw]
+    pixel = (ar(n)[:, None, None, None, None] * h + iy[None, :, None, :, None]) * w + ix[None, None, :, None, :]
+    inside = inside[None].expand_as(pixel).reshape(n * oh * ow, kh * kw)
+    pixel = torch.where(inside, pixel.reshape(n * oh * ow, kh * kw), torch.zeros_like(inside, dtype=torch.int64))
+    e, s = x.elements.reshape(n * h * w, -1), x.scales.reshape(n * h * w, -1)
+    ge = torch.where(inside[:, :, None], e[pixel], torch.zeros_like(e[:1, None]))
+    gs = torch.where(inside[:, :, None], s[pixel], torch.full_like(s[:1, None], 127))
+    return ge.reshape(n * oh * ow, -1), gs.reshape(n * oh * ow, -1)
+
+
+def mx_int8_conv2d_packed(x: MXTensor, w: MXTensor, bias: torch.Tensor = None, stride=1, padding=0, dilation=1, use_kernels: bool = True) -> torch.Tensor:
+    """``conv2d(x, w) (+ bias)`` in float32 on two MXINT8 tensors: ``x`` is ``[N, C, H, W]``, ``w`` is ``[O, C, kh, kw]``, both packed
+    along axis 1; ``stride``, ``padding`` (symmetric) and ``dilation`` are ints or (h, w) pairs, groups is 1.  The result is
+    ``[N, O, OH, OW]`` with the bits of ``mx_int8_matmul`` on the rows of the implicit GEMM: per output and
+    block (ky, kx, channel block) the exact integer dot product, scaled and rounded once to float32, the blocks added in float32 in
+    order, then the bias.  A tap in the padding adds +0; an output is NaN where its window covers a NaN block (scale code 0xFF) of
+    ``x`` inside the image, or its output channel of ``w`` holds one.
+    ``use_kernels=True``: the packed bytes go to the int8 MFMA as they are, the rows gathered by address (``CUDA.MXInt8Conv2d``; the
+    tensors must be on the GPU); the result has channels-last strides.  ``False``: the same contract in torch ops on any device --
+    identical bits: the packed blocks of the windows gathered by indexing, then the torch arm of ``mx_int8_matmul``.  The five float
+    formats are ``mx_conv2d_packed``'s."""
+    stride, padding, dilation, out = _check_int8_conv(x, w, bias, stride, padding, dilation)
+    if use_kernels: return CUDA.MXInt8Conv2d(x.elements, x.scales, w.elements, w.scales, x.shape[1], bias, stride, padding, dilation)
+    o = w.shape[0]
+    ge, gs = _mx_int8_gather_torch(x, w.shape[2:], stride, padding, dilation, out)
+    y = _mx_int8_matmul_torch(ge, gs, w.elements.reshape(o, -1), w.scales.reshape(o, -1), bias)
+    return y.reshape(x.shape[0], out[0], out[1], o).permute(0, 3, 1, 2)
+
+
+def mx_int8_conv2d(x: torch.Tensor, weight: MXTensor, bias: torch.Tensor = None, stride=1, padding=0, dilation=1, groups: int = 1,
+                   use_kernels: bool = True, scale_rule=MXScaleRule.FLOOR) -> torch.Tensor:
+    """A convolution on an MXINT8 weight as it runs in deployment: ``mx_quantize(x, 'MXINT8', 1, scale_rule=...)`` -- ``x``
+    ``[N, C, H, W]``, contiguous or channels-last --, then ``mx_int8_conv2d_packed`` with ``weight`` ``[O, C, kh, kw]``: two launches,
+    the bias added in the kernel's epilogue."""
+    if groups != 1: raise RuntimeError(f'mx_int8_conv2d: groups must be 1, got {groups}')
+    if isinstance(x, torch.Tensor) and x.dim() != 4: raise RuntimeError(f'mx_int8_conv2d: x must be 4-d [N, C, H, W], got shape {list(x.shape)}')
+    return mx_int8_conv2d_packed(mx_quantize(x, MXFormat.MXINT8, 1, use_kernels=use_kernels, scale_rule=scale_rule), weight, bias, stride, padding,
+                                 dilation, use_kernels)
 
 
 def _activated(config) -> bool:
@@ -811,6 +882,7 @@ class MXDeployment:
         self.weights: Dict[str, MXTensor] = {}
         self._operands: Dict[str, MXTensor] = {}      # operation name -> its weight as the kernel takes it
         self._runs: Dict[str, object] = {}            # operation name -> its override
+        self._int8: set = set()                       # the deployed operations on the int8 MFMA: no fused epilogue, no packed hand-over
         self.refresh()
 
     def _format(self, config) -> Optional[MXFormat]:
@@ -837,7 +909,8 @@ class MXDeployment:
         afmt, wfmt = formats
         arule = self._rule(cfgs[0])
         if afmt is None or wfmt is None: return 'only one operand carries an MX format'
-        if not (afmt.is_float and wfmt.is_float): return 'MXINT8 is not an operand type of the scaled MFMA'
+        int8 = afmt is MXFormat.MXINT8 and wfmt is MXFormat.MXINT8                       # both sides: the int8 MFMA (section 9.20)
+        if not int8 and not (afmt.is_float and wfmt.is_float): return 'MXINT8 is not an operand type of the scaled MFMA'
         if not (_activated(cfgs[0]) and _activated(cfgs[1])): return 'an MX config is not activated'
         packed = self.weights.get(w_var.name)
         if packed is None: return 'export_graph_mx left the weight out'
@@ -847,6 +920,11 @@ class MXDeployment:
             if a.get('group', 1) != 1: return 'a grouped convolution'
             if len(packed.shape) != 4: return f'a {len(packed.shape)}-d Conv weight'
             stride, padding, operand = a.get('strides', 1), a.get('pads', 0), packed
+            dilation = a.get('dilations', 1)
+
+            def run_int8(op, x):
+                return mx_int8_conv2d(x[0], self._operands[op.name], x[2] if len(x) > 2 else None, stride, padding, dilation,
+                                      use_kernels=use_kernels, scale_rule=arule)
 
             def run(op, x, **tail):
                 bias = x[2] if len(x) > 2 else None
@@ -858,12 +936,16 @@ class MXDeployment:
             # a MatMul weight [in, out] is packed along axis 0: its bytes are those of [out, in] packed along axis 1
             operand = packed if op.type == 'Gemm' else MXTensor(packed.format, packed.shape[::-1], 1, packed.elements, packed.scales)
 
+            def run_int8(op, x):
+                return mx_int8_linear(x[0], self._operands[op.name], x[2] if len(x) > 2 else None, use_kernels=use_kernels, scale_rule=arule)
+
             def run(op, x, **tail):
                 bias = x[2] if len(x) > 2 else None
                 if isinstance(x[0], MXTensor):
                     return mx_matmul(_handed(op, x[0], afmt, len(x[0].shape) - 1), self._operands[op.name], bias, use_kernels, **tail)
                 return mx_linear(x[0], self._operands[op.name], afmt, bias, use_kernels=use_kernels, scale_rule=arule, **tail)
-        return run, operand
+        if int8: self._int8.add(op.name)
+        return (run_int8 if int8 else run), operand
 
     def refresh(self) -> None:
         """Pack the weights as they are now and (re)register the overrides."""
@@ -879,7 +961,7 @@ class MXDeployment:
                 continue
             run, self._operands[name] = plan
             self._runs[name] = run
-            self.executor.register_operation_override(name, run, takes_packed=self.fuse)
+            self.executor.register_operation_override(name, run, takes_packed=self.fuse and name not in self._int8)
             self.deployed.append(name)
         if self.fuse: self._plan_groups()
 
@@ -907,7 +989,7 @@ class MXDeployment:
             return v.dest_ops[0]
 
         for op in order:
-            if op.name not in self._runs: continue
+            if op.name not in self._runs or op.name in self._int8: continue            # the int8 kernels have no fused epilogue
             group = MXFusedGroup([op.name])
             t = op.outputs[0]
             if len(op.outputs) != 1 or not all(passes(c) for c in op.config.output_quantization_config):
@@ -935,7 +1017,7 @@ class MXDeployment:
                     claimed.add(relu.name)
                     t = relu.outputs[0]
             group.output = t.name
-            takers = [d for d in t.dest_ops if d.name in self._runs]
+            takers = [d for d in t.dest_ops if d.name in self._runs and d.name not in self._int8]
             kind = (lambda o: 'Conv' if o.type == 'Conv' else 'Gemm')
             if not takers: group.notes.append('float output: no deployed consumer')
             elif any(d.inputs[0] is not t or sum(1 for x in d.inputs if x is t) != 1 for d in takers): group.notes.append('float output: a deployed consumer does not read it as its activation')
@@ -971,14 +1053,17 @@ class MXDeployment:
         for name in getattr(self, 'groups', {}): self.executor.remove_group_override(name)
         for name in self.deployed: self.executor.remove_operation_override(name)
         self.deployed, self.skipped, self._operands, self._runs, self.groups = [], {}, {}, {}, {}
+        self._int8 = set()
 
 
 def deploy_graph_mx(graph, executor, delegators=None, use_kernels: bool = True, fuse: bool = False) -> MXDeployment:
     """Put the MX operations of a ``quantize_graph_mx`` graph on the hardware path: the weights are packed (``export_graph_mx``) and
     every eligible operation gets an operation override on ``executor`` that quantises its activation and runs the packed kernel --
     a Conv with ``group`` 1 ``mx_conv2d`` (the activation delegator's format, the bias, ``strides`` and ``pads``), a Gemm ``mx_linear``,
-    a MatMul with a 2-D parameter on the right ``mx_linear`` on the weight's own bytes.  MXINT8 on either side, grouped convolutions,
-    a MatMul of two activations and weights the export left out stay on the simulated path (``.skipped``).  ``delegators``: what
+    a MatMul with a 2-D parameter on the right ``mx_linear`` on the weight's own bytes.  An operation whose activation AND weight are
+    MXINT8 runs on the int8 MFMA: a Conv ``mx_int8_conv2d`` (its ``dilations`` included), a Gemm or such a
+    MatMul ``mx_int8_linear``.  MXINT8 on one side only, grouped convolutions, a MatMul of two activations and weights the export left
+    out stay on the simulated path (``.skipped``).  ``delegators``: what
     ``quantize_graph_mx`` returned (default: the formats recorded in the configs).  ``use_kernels=False``: the torch arms, any device.
     ``fuse=True``: every deployed operation additionally runs together with its tail -- an optional
     residual ``Add``, then an optional ``Relu`` -- as ONE launch (``TorchExecutor.register_group_override``), and the tail's last
@@ -986,5 +1071,6 @@ def deploy_graph_mx(graph, executor, delegators=None, use_kernels: bool = True, 
     Gemm) and by the FLOOR rule, the one the fused epilogue packs by (a consumer with another ``MXScaleRule`` gets the float tensor and
     quantises it itself): the consumer then quantises nothing.  It is written as float32 only when something reads it as float.  ``.groups``
     records every group: members, residual, relu, ``out_format`` and, in ``notes``, why an Add was not fused or the output not
-    packed.  A forward that hooks a member or asks for an intermediate runs that group's operations one by one, as ``fuse=False``."""
+    packed.  A forward that hooks a member or asks for an intermediate runs that group's operations one by one, as ``fuse=False``.
+    The MXINT8 kernels have no fused epilogue: such an operation is deployed alone, heads no group and is handed nothing packed."""
     return MXDeployment(graph, executor, delegators, use_kernels, fuse)
