@@ -954,6 +954,32 @@ int ppqhip_mx_int8_conv2d(const uint8_t* x_elements, const uint8_t* x_scales, co
                           const float* bias, float* y, int64_t n, int64_t c, int64_t h, int64_t w, int64_t o, int64_t kh, int64_t kw,
                           int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, void* stream);
 
+/* The same two with a fused epilogue (ppq_amd/mx.py residual= / relu= / out_format= of the mx_int8_* functions; DESIGN.md section
+ * 9.21; ADDED under ABI 4) ---------------------------------------------------------------------------------------------------------- */
+/* Operands, sizes, the float32 chain and the NaN flags are those of ppqhip_mx_int8_gemm / ppqhip_mx_int8_conv2d; the K loop is the same
+ * code.  Per output, in this order: v = acc + bias (bias set); v = v + residual[row, col] (residual set: float32 [m, n] row-major, for
+ * the conv [n, oh, ow, o]), each one float32 add; v = 0x7fc00000 where the row or column is NaN-flagged; relu != 0: v = v > 0 ? v : +0
+ * with a NaN staying a NaN (so -0 becomes +0); c / y set: v is stored as float32 in the plain call's layout; out_elements /
+ * out_scales set (both or neither): v is packed as PPQHIP_MXINT8 along the columns (output channels) in blocks of 32, out_scales
+ * [m, nbo] and out_elements [m, nbo * 32], nbo = ceil(n / 32) -- byte for byte what ppqhip_mx_pack makes of the float32 [m, n] along
+ * its last axis under the FLOOR rule (for the conv: of [n, o, oh, ow] along axis 1, which is the x of ppqhip_mx_int8_conv2d): a NaN
+ * gives scale 0xFF and zero codes for the whole block, a short last block holds code 0 in the elements it lacks.  There is no
+ * out_format: these kernels pack MXINT8.
+ * Refused before any launch, beyond what the plain calls refuse: out_elements and out_scales not both set or both null; no output at
+ * all (c / y and out_elements null); out_elements not 16-byte aligned (c / y as in the plain call when set); more than 2^31 - 1
+ * output blocks; an output overlapping an input (the residual included) or another output.  m == 0 or n == 0 (n == 0 or o == 0)
+ * launches nothing; k == 0 (c == 0) runs the epilogue on bias (or 0) plus residual.  Two calls give identical bits.  Booked under
+ * "mx_int8_gemm_fused" / "mx_int8_conv_fused": the operands, and 4 m n bytes for each of residual and c, and the packed bytes, where
+ * present. */
+int ppqhip_mx_int8_gemm_fused(const uint8_t* a_elements, const uint8_t* a_scales, const uint8_t* b_elements, const uint8_t* b_scales,
+                              const float* bias, const float* residual, int relu, float* c, uint8_t* out_elements, uint8_t* out_scales,
+                              int64_t m, int64_t n, int64_t k, void* stream);
+int ppqhip_mx_int8_conv2d_fused(const uint8_t* x_elements, const uint8_t* x_scales, const uint8_t* w_elements, const uint8_t* w_scales,
+                                const float* bias, const float* residual, int relu, float* y, uint8_t* out_elements,
+                                uint8_t* out_scales, int64_t n, int64_t c, int64_t h, int64_t w, int64_t o, int64_t kh, int64_t kw,
+                                int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w,
+                                void* stream);
+
 /* ---- pointwise (1x1) convolution on the FP32-input MFMA (ADDED under ABI 4) ---------------------------------
  * y[n, o, oh, ow] = sum_k w[o, k] x[n, k, oh * stride, ow * stride] (+ bias[o]) for contiguous NCHW float32 x [n, c, h, wd],
  * w [o, c] (a [o, c, 1, 1] convolution weight as it lies) and y [n, o, ho, wo], ho = (h - 1) / stride + 1, wo likewise; no padding,

@@ -23,6 +23,9 @@
 // while a term is -0 for no P.  So multiplying such a block (as here) and skipping it give the same bits.
 // Rows past M or O are clamped on load and not stored; the tail chunk multiplies only its live blocks.
 // NaN: a scale code 0xFF read from INSIDE the image, or from w, flags the row (column); flagged outputs are written as 0x7fc00000.
+// ppqhip_mx_int8_conv2d_fused runs the same K loop with the fused epilogue (fused_tiles in mx_int8_tile.hpp):
+// residual, ReLU and the result packed as MXINT8 along the output channels -- the x of the next launch --, in a second instantiation;
+// the plain kernel keeps its code.
 #include "common.hpp"
 #include "job_table.hpp"
 #include "mx_mfma.hpp"
@@ -35,7 +38,7 @@ struct MxInt8ConvArgs {
     const uint8_t* xe; const uint8_t* xs;         // x: elements [n, h, w, nbc * 32], scales [n, h, w, nbc]
     const uint8_t* we; const uint8_t* ws;         // w: elements [o, nb * 32], scales [o, nb]; nb = kh * kw * nbc (0 when x holds no block at all)
     const float* bias;                            // [o] or null
-    float* y;                                     // [m, o]
+    float* y;                                     // [m, o]; may be null in a fused launch
     uint32_t m, o, nb, nbc;
     uint32_t h, w, kw;
     int32_t sh, sw, ph, pw, dh, dw;
@@ -150,8 +153,12 @@ struct ConvStageMap {
     __device__ __forceinline__ void store(uint8_t* buf, const Staged& st) const { store_staged(buf, lds_e, lds_s, st); }
 };
 
-// The K loop is the one of mx_int8_gemm_kernel (the maps differ, the order of loads, multiplies, stores and barriers does not).
-__global__ __launch_bounds__(kBlock) void mx_int8_conv_kernel(const MxInt8ConvArgs g) {
+// The K loop is the one of mx_int8_gemm_kernel (the maps differ, the order of loads, multiplies, stores and barriers does not), and so
+// is F: empty for the plain kernel, one MxFusedOut for the fused one.
+template <typename... F>
+__global__ __launch_bounds__(kBlock) void mx_int8_conv_kernel(const MxInt8ConvArgs g, const F... f) {
+    constexpr bool FUSED = sizeof...(F) != 0;
+    static_assert(sizeof...(F) <= 1, "at most one MxFusedOut");
     constexpr int T = kGemmWaveTiles;
     __shared__ __attribute__((aligned(16))) uint8_t stage[2][kI8BufBytes];
     __shared__ uint32_t nan_flags[2 * kGemmEdge];                                // rows of A, then rows of B (columns of Y)
@@ -193,6 +200,10 @@ __global__ __launch_bounds__(kBlock) void mx_int8_conv_kernel(const MxInt8ConvAr
     __syncthreads();
     if (!busy) return;
 
+    if constexpr (FUSED) {                                                       // the operand stage is dead: the waves gather their codes in it
+        fused_tiles(acc, nan_flags, g.bias, g.y, g.m, g.o, row0, col0, wm, wn, lane, f..., &stage[0][0]);
+        return;
+    }
     store_tiles(acc, nan_flags, g.bias, g.y, g.m, g.o, row0, col0, wm, wn, r, grp);
 }
 
@@ -202,16 +213,15 @@ int64_t bounded_product(int64_t a, int64_t b) {
     return p > kMxMax ? -1 : p;
 }
 
-}  // namespace
-}  // namespace ppqhip
-
-using namespace ppqhip;
-
-extern "C" int ppqhip_mx_int8_conv2d(const uint8_t* x_elements, const uint8_t* x_scales, const uint8_t* w_elements, const uint8_t* w_scales,
-                                     const float* bias, float* y, int64_t n, int64_t c, int64_t h, int64_t w, int64_t o, int64_t kh,
-                                     int64_t kw, int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h,
-                                     int64_t dil_w, void* stream) {
-    const char* what = "mx_int8_conv2d";
+// both entry points; `fused` is null for ppqhip_mx_int8_conv2d, whose checks, strings and launch are unchanged
+int run_int8_conv(const char* what, const uint8_t* x_elements, const uint8_t* x_scales, const uint8_t* w_elements, const uint8_t* w_scales,
+                  const float* bias, float* y, int64_t n, int64_t c, int64_t h, int64_t w, int64_t o, int64_t kh, int64_t kw,
+                  int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, const MxFusedHost* fused,
+                  void* stream) {
+    MxFusedOut f = {};
+    if (fused != nullptr) {
+        if (int st = check_int8_fused(what, "y", y, *fused, f)) return st;
+    }
     const int64_t sizes[] = {n, c, h, w, o, kh, kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w};
     for (int64_t v : sizes) {
         if (v < 0) { set_error("%s: negative size", what); return PPQHIP_ERR_INVALID_VALUE; }
@@ -235,7 +245,7 @@ extern "C" int ppqhip_mx_int8_conv2d(const uint8_t* x_elements, const uint8_t* x
     if (m < 0 || nb < 0 || blocks_x < 0) { set_error("%s: a size above 2^31 - 1", what); return PPQHIP_ERR_INVALID_VALUE; }
     if (n == 0 || o == 0) return PPQHIP_OK;
     const bool read_x = blocks_x > 0, read_w = read_x && nb > 0;     // an input without a pixel: every tap is padding, nothing is read
-    if (y == nullptr || (read_x && (x_elements == nullptr || x_scales == nullptr)) || (read_w && (w_elements == nullptr || w_scales == nullptr))) {
+    if ((y == nullptr && fused == nullptr) || (read_x && (x_elements == nullptr || x_scales == nullptr)) || (read_w && (w_elements == nullptr || w_scales == nullptr))) {
         set_error("%s: null pointer", what); return PPQHIP_ERR_INVALID_VALUE;
     }
     if (!aligned16(y) || (read_x && !aligned16(x_elements)) || (read_w && !aligned16(w_elements))) {
@@ -245,13 +255,11 @@ extern "C" int ppqhip_mx_int8_conv2d(const uint8_t* x_elements, const uint8_t* x
     if (read_x) { ins.push_back(span_of(x_elements, blocks_x * kMxBlock)); ins.push_back(span_of(x_scales, blocks_x)); }
     if (read_w) { ins.push_back(span_of(w_elements, o * nb * kMxBlock)); ins.push_back(span_of(w_scales, o * nb)); }
     if (bias != nullptr) ins.push_back(span_of(bias, o));
-    outs.push_back(span_of(y, m * o));
-    const int64_t tiles_m = (m + kGemmEdge - 1) / kGemmEdge, tiles_n = (o + kGemmEdge - 1) / kGemmEdge;
-    if (tiles_m * tiles_n > kMxMax) { set_error("%s: too many workgroups in one launch", what); return PPQHIP_ERR_INVALID_VALUE; }
-    if (int st = check_overlap(what, ins, outs)) return st;
+    if (y != nullptr) outs.push_back(span_of(y, m * o));
     // booked: packed x once (a pixel is read by up to kh kw windows, from cache), packed w and 4 m o bytes of y; the launch does
     // 2 m o nb 32 integer operations
-    const double bytes = ((double)blocks_x + (double)o * (double)nb) * (double)(kMxBlock + 1) + 4.0 * (double)m * (double)o;
+    double bytes = ((double)blocks_x + (double)o * (double)nb) * (double)(kMxBlock + 1);
+    if (y != nullptr) bytes += 4.0 * (double)m * (double)o;
 
     MxInt8ConvArgs g;
     g.xe = x_elements; g.xs = x_scales; g.we = w_elements; g.ws = w_scales; g.bias = bias; g.y = y;
@@ -260,11 +268,33 @@ extern "C" int ppqhip_mx_int8_conv2d(const uint8_t* x_elements, const uint8_t* x
     g.h = (uint32_t)h; g.w = (uint32_t)w; g.kw = (uint32_t)kw;
     g.sh = (int32_t)stride_h; g.sw = (int32_t)stride_w; g.ph = (int32_t)pad_h; g.pw = (int32_t)pad_w;
     g.dh = (int32_t)dil_h; g.dw = (int32_t)dil_w;
-    g.tiles_n = make_fastdiv((uint32_t)tiles_n);
     g.ohw = make_fastdiv((uint32_t)(oh * ow)); g.ow = make_fastdiv((uint32_t)ow);
     g.fnbc = make_fastdiv((uint32_t)std::max<int64_t>(nbc, 1)); g.fkw = make_fastdiv((uint32_t)kw);
-    hipStream_t s = (hipStream_t)stream;
-    LaunchScope scope(K_MX_INT8_CONV, bytes, s);
-    hipLaunchKernelGGL(mx_int8_conv_kernel, dim3((uint32_t)(tiles_m * tiles_n)), dim3(kBlock), 0, s, g);
-    return finish_launch(what);
+    return launch_int8_tiles(what, K_MX_INT8_CONV, K_MX_INT8_CONV_FUSED, fused, f, m, o, ins, outs, bytes, stream, g.tiles_n,
+                             [&g](uint32_t blocks, hipStream_t s, const auto&... fo) {
+        hipLaunchKernelGGL((mx_int8_conv_kernel<std::decay_t<decltype(fo)>...>), dim3(blocks), dim3(kBlock), 0, s, g, fo...);
+    });
+}
+
+}  // namespace
+}  // namespace ppqhip
+
+using namespace ppqhip;
+
+extern "C" int ppqhip_mx_int8_conv2d(const uint8_t* x_elements, const uint8_t* x_scales, const uint8_t* w_elements, const uint8_t* w_scales,
+                                     const float* bias, float* y, int64_t n, int64_t c, int64_t h, int64_t w, int64_t o, int64_t kh,
+                                     int64_t kw, int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h,
+                                     int64_t dil_w, void* stream) {
+    return run_int8_conv("mx_int8_conv2d", x_elements, x_scales, w_elements, w_scales, bias, y, n, c, h, w, o, kh, kw, stride_h, stride_w,
+                         pad_h, pad_w, dil_h, dil_w, nullptr, stream);
+}
+
+extern "C" int ppqhip_mx_int8_conv2d_fused(const uint8_t* x_elements, const uint8_t* x_scales, const uint8_t* w_elements,
+                                           const uint8_t* w_scales, const float* bias, const float* residual, int relu, float* y,
+                                           uint8_t* out_elements, uint8_t* out_scales, int64_t n, int64_t c, int64_t h, int64_t w,
+                                           int64_t o, int64_t kh, int64_t kw, int64_t stride_h, int64_t stride_w, int64_t pad_h,
+                                           int64_t pad_w, int64_t dil_h, int64_t dil_w, void* stream) {
+    const MxFusedHost fused = {residual, relu, out_elements, out_scales, PPQHIP_MXINT8};
+    return run_int8_conv("mx_int8_conv2d_fused", x_elements, x_scales, w_elements, w_scales, bias, y, n, c, h, w, o, kh, kw, stride_h,
+                         stride_w, pad_h, pad_w, dil_h, dil_w, &fused, stream);
 }

@@ -24,6 +24,8 @@
 // NaN: a scale code 0xFF seen while the scales are staged flags the row (column); flagged outputs are written as 0x7fc00000.
 // What the kernel shares with mx_int8_conv_kernel (mx_int8_conv.hip) is in mx_int8_tile.hpp: the stage's geometry, the multiply of a
 // staged chunk, the NaN flags and the store of the tile; what is here is where a thread's share of a chunk lies in two packed operands.
+// ppqhip_mx_int8_gemm_fused runs the same K loop with the fused epilogue (fused_tiles in mx_int8_tile.hpp):
+// residual, ReLU and the result packed as MXINT8 along the output columns, in a second instantiation; the plain kernel keeps its code.
 #include "common.hpp"
 #include "job_table.hpp"
 #include "mx_mfma.hpp"
@@ -36,7 +38,7 @@ struct MxInt8Args {
     const uint8_t* ae; const uint8_t* as;         // A: elements [m, nb * 32], scales [m, nb]
     const uint8_t* be; const uint8_t* bs;         // B: elements [n, nb * 32], scales [n, nb]
     const float* bias;                            // [n] or null
-    float* c;                                     // [m, n]
+    float* c;                                     // [m, n]; may be null in a fused launch
     uint32_t m, n, nb;
     FastDiv tiles_n;
 };
@@ -79,7 +81,12 @@ struct StageMap {
     __device__ __forceinline__ void store(uint8_t* buf, const Staged& st) const { store_staged(buf, lds_e, lds_s, st); }
 };
 
-__global__ __launch_bounds__(kBlock) void mx_int8_gemm_kernel(const MxInt8Args g) {
+// F is empty -- the plain kernel, (g) alone -- or one MxFusedOut: fused_tiles in place of store_tiles, (g, f).  Everything up to the
+// final barrier is the same code.
+template <typename... F>
+__global__ __launch_bounds__(kBlock) void mx_int8_gemm_kernel(const MxInt8Args g, const F... f) {
+    constexpr bool FUSED = sizeof...(F) != 0;
+    static_assert(sizeof...(F) <= 1, "at most one MxFusedOut");
     constexpr int T = kGemmWaveTiles;
     __shared__ __attribute__((aligned(16))) uint8_t stage[2][kI8BufBytes];
     __shared__ uint32_t nan_flags[2 * kGemmEdge];                                // rows of A, then rows of B (columns of C)
@@ -121,22 +128,25 @@ __global__ __launch_bounds__(kBlock) void mx_int8_gemm_kernel(const MxInt8Args g
     __syncthreads();
     if (!busy) return;
 
+    if constexpr (FUSED) {                                                       // the operand stage is dead: the waves gather their codes in it
+        fused_tiles(acc, nan_flags, g.bias, g.c, g.m, g.n, row0, col0, wm, wn, lane, f..., &stage[0][0]);
+        return;
+    }
     store_tiles(acc, nan_flags, g.bias, g.c, g.m, g.n, row0, col0, wm, wn, r, grp);
 }
 
-}  // namespace
-}  // namespace ppqhip
-
-using namespace ppqhip;
-
-extern "C" int ppqhip_mx_int8_gemm(const uint8_t* a_elements, const uint8_t* a_scales, const uint8_t* b_elements, const uint8_t* b_scales,
-                                   const float* bias, float* c, int64_t m, int64_t n, int64_t k, void* stream) {
-    const char* what = "mx_int8_gemm";
+// both entry points; `fused` is null for ppqhip_mx_int8_gemm, whose checks, strings and launch are unchanged
+int run_int8_gemm(const char* what, const uint8_t* a_elements, const uint8_t* a_scales, const uint8_t* b_elements, const uint8_t* b_scales,
+                  const float* bias, float* c, int64_t m, int64_t n, int64_t k, const MxFusedHost* fused, void* stream) {
+    MxFusedOut f = {};
+    if (fused != nullptr) {
+        if (int st = check_int8_fused(what, "c", c, *fused, f)) return st;
+    }
     if (m < 0 || n < 0 || k < 0) { set_error("%s: negative size", what); return PPQHIP_ERR_INVALID_VALUE; }
     if (m > kMxMax || n > kMxMax || k > kMxMax) { set_error("%s: a size above 2^31 - 1", what); return PPQHIP_ERR_INVALID_VALUE; }
     if (m == 0 || n == 0) return PPQHIP_OK;
     const int64_t nb = (k + kMxBlock - 1) / kMxBlock;
-    if (c == nullptr || (nb > 0 && (a_elements == nullptr || a_scales == nullptr || b_elements == nullptr || b_scales == nullptr))) {
+    if ((c == nullptr && fused == nullptr) || (nb > 0 && (a_elements == nullptr || a_scales == nullptr || b_elements == nullptr || b_scales == nullptr))) {
         set_error("%s: null pointer", what); return PPQHIP_ERR_INVALID_VALUE;
     }
     if (!aligned16(c) || (nb > 0 && (!aligned16(a_elements) || !aligned16(b_elements)))) {
@@ -148,19 +158,33 @@ extern "C" int ppqhip_mx_int8_gemm(const uint8_t* a_elements, const uint8_t* a_s
         ins.push_back(span_of(b_elements, n * nb * kMxBlock)); ins.push_back(span_of(b_scales, n * nb));
     }
     if (bias != nullptr) ins.push_back(span_of(bias, n));
-    outs.push_back(span_of(c, m * n));
-    const int64_t tiles_m = (m + kGemmEdge - 1) / kGemmEdge, tiles_n = (n + kGemmEdge - 1) / kGemmEdge;
-    if (tiles_m * tiles_n > kMxMax) { set_error("%s: too many workgroups in one launch", what); return PPQHIP_ERR_INVALID_VALUE; }
-    if (int st = check_overlap(what, ins, outs)) return st;
+    if (c != nullptr) outs.push_back(span_of(c, m * n));
     // booked: the operands and 4 m n bytes of C; the launch does 2 m n nb 32 integer operations
-    const double bytes = ((double)m + (double)n) * (double)nb * (double)(kMxBlock + 1) + 4.0 * (double)m * (double)n;
+    double bytes = ((double)m + (double)n) * (double)nb * (double)(kMxBlock + 1);
+    if (c != nullptr) bytes += 4.0 * (double)m * (double)n;
 
     MxInt8Args g;
     g.ae = a_elements; g.as = a_scales; g.be = b_elements; g.bs = b_scales; g.bias = bias; g.c = c;
     g.m = (uint32_t)m; g.n = (uint32_t)n; g.nb = (uint32_t)nb;
-    g.tiles_n = make_fastdiv((uint32_t)tiles_n);
-    hipStream_t s = (hipStream_t)stream;
-    LaunchScope scope(K_MX_INT8_GEMM, bytes, s);
-    hipLaunchKernelGGL(mx_int8_gemm_kernel, dim3((uint32_t)(tiles_m * tiles_n)), dim3(kBlock), 0, s, g);
-    return finish_launch(what);
+    return launch_int8_tiles(what, K_MX_INT8_GEMM, K_MX_INT8_GEMM_FUSED, fused, f, m, n, ins, outs, bytes, stream, g.tiles_n,
+                             [&g](uint32_t blocks, hipStream_t s, const auto&... fo) {
+        hipLaunchKernelGGL((mx_int8_gemm_kernel<std::decay_t<decltype(fo)>...>), dim3(blocks), dim3(kBlock), 0, s, g, fo...);
+    });
+}
+
+}  // namespace
+}  // namespace ppqhip
+
+using namespace ppqhip;
+
+extern "C" int ppqhip_mx_int8_gemm(const uint8_t* a_elements, const uint8_t* a_scales, const uint8_t* b_elements, const uint8_t* b_scales,
+                                   const float* bias, float* c, int64_t m, int64_t n, int64_t k, void* stream) {
+    return run_int8_gemm("mx_int8_gemm", a_elements, a_scales, b_elements, b_scales, bias, c, m, n, k, nullptr, stream);
+}
+
+extern "C" int ppqhip_mx_int8_gemm_fused(const uint8_t* a_elements, const uint8_t* a_scales, const uint8_t* b_elements,
+                                         const uint8_t* b_scales, const float* bias, const float* residual, int relu, float* c,
+                                         uint8_t* out_elements, uint8_t* out_scales, int64_t m, int64_t n, int64_t k, void* stream) {
+    const MxFusedHost fused = {residual, relu, out_elements, out_scales, PPQHIP_MXINT8};
+    return run_int8_gemm("mx_int8_gemm_fused", a_elements, a_scales, b_elements, b_scales, bias, c, m, n, k, &fused, stream);
 }

@@ -3,7 +3,8 @@
 // blocks it stages 64 rows of each operand (128 bytes each, pitch 144) and their 4 scale codes per row in LDS, double buffered.  Here
 // are the stage's geometry, what a thread carries into it and where it puts it, the multiply of a staged chunk, the NaN flags and the
 // store of the tile.  What a kernel adds is where a thread's share of a chunk comes from in global memory: a packed row (the GEMM) or a
-// gathered one (the convolution).
+// gathered one (the convolution).  Below those: the fused epilogue of both (section 9.21) -- fused_tiles, which hands the tile to
+// fused_epilogue of mx_mfma.hpp -- and the host frame of the two fused entry points.
 #pragma once
 #include "common.hpp"
 #include "mx_mfma.hpp"
@@ -111,6 +112,65 @@ __device__ __forceinline__ void store_tiles(const v4f (&acc)[kGemmWaveTiles][kGe
             }
         }
     }
+}
+
+// ---- the fused epilogue on the int8 tile -------------------------------------------------------------------
+// A wave of this tile owns 32 rows x 32 columns with acc[i][j][q] at row wm + 16 i + 4 grp + q, column wn + 16 j + r: the layout
+// fused_epilogue of mx_mfma.hpp is written for, and 32 columns that start at a multiple of 32 are one output MX block per row.  So the
+// int8 kernels call that epilogue as it is -- one block maximum, one coder (its is_int arm), one code gather -- and add two things.
+//
+// The NaN masks.  fused_epilogue takes, per 16 x 16 tile, a 16-bit mask of flagged rows and one of flagged columns; the int8 kernels
+// keep one word per row and column of the workgroup in LDS (nan_flags).  After the kernel's final barrier lane l reads the flag of
+// row wm + 16 i + (l & 15) resp. column wn + 16 j + (l & 15); a ballot puts the 16 flags of lanes 0 .. 15 in the low bits (the three
+// other lane groups read the same words; tile_flags ORs the four copies).
+//
+// The LDS of the code gather.  No LDS is declared for it: wave w takes bytes [w * kFusedStageBytes, + kFusedStageBytes) of the
+// operand stage.  The stage's last readers are the chunk_tiles of the last K chunk, and every wave passes the barrier that ends that
+// chunk, and the kernel's final barrier after it, before any wave reaches its epilogue: no fragment read can follow a code write.
+// From there on a wave touches its own slice only, so the waves that returned at the edge are not waited for.
+static_assert(kGemmWaves * kGemmWaves * kFusedStageBytes <= kI8BufBytes, "the four waves' code stages fit the first operand buffer");
+
+__device__ __forceinline__ void fused_tiles(const v4f (&acc)[kGemmWaveTiles][kGemmWaveTiles], const uint32_t* nan_flags, const float* bias,
+                                            float* c, uint32_t m, uint32_t n, uint32_t row0, uint32_t col0, uint32_t wm, uint32_t wn,
+                                            uint32_t lane, const MxFusedOut& f, uint8_t* operand_stage) {
+    constexpr int T = kGemmWaveTiles;
+    const uint32_t r = lane & 15u, wave = (wm / (T * kGemmTile)) * kGemmWaves + wn / (T * kGemmTile);
+    uint32_t rows_nan[T], cols_nan[T];
+#pragma unroll
+    for (int i = 0; i < T; i++) {
+        rows_nan[i] = tile_flags(nan_flags[wm + i * kGemmTile + r]);
+        cols_nan[i] = tile_flags(nan_flags[kGemmEdge + wn + i * kGemmTile + r]);
+    }
+    fused_epilogue(acc, rows_nan, cols_nan, bias, c, m, n, row0 + wm, col0 + wn, lane, f, operand_stage + wave * kFusedStageBytes);
+}
+
+// ---- the host side of the two fused entry points ----------------------------------------------------------------------------------------
+// What ppqhip_mx_int8_gemm_fused / ppqhip_mx_int8_conv2d_fused check about their outputs before anything else: the pointer rules of
+// ppqhip_mx_gemm_fused; there is no out_format -- these kernels pack MXINT8 -- so f.fmt is that format's.
+inline int check_int8_fused(const char* what, const char* float_name, const float* c, const MxFusedHost& fused, MxFusedOut& f) {
+    make_mx_fmt(PPQHIP_MXINT8, &f.fmt);
+    return check_fused_pointers(what, float_name, c, fused.out_elements, fused.out_scales);
+}
+
+// The launch of an int8 entry point, from its grid check on (the int8 side of launch_mx_tiles): `ins`, `outs` and `bytes` are the
+// plain launch's and `fused` is null for it.  launch(blocks, stream, f...) starts the plain kernel without f, the fused one with it.
+template <typename Launch>
+inline int launch_int8_tiles(const char* what, KernelId plain_id, KernelId fused_id, const MxFusedHost* fused, MxFusedOut& f, int64_t m,
+                             int64_t n, std::vector<Span>& ins, std::vector<Span>& outs, double bytes, void* stream, FastDiv& tiles_n_div,
+                             Launch&& launch) {
+    const int64_t tiles_m = (m + kGemmEdge - 1) / kGemmEdge, tiles_n = (n + kGemmEdge - 1) / kGemmEdge;
+    if (tiles_m * tiles_n > kMxMax) { set_error("%s: too many workgroups in one launch", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (fused != nullptr) {
+        if (int st = book_fused(what, *fused, m, n, ins, outs, bytes, f)) return st;
+    }
+    if (int st = check_overlap(what, ins, outs)) return st;
+    tiles_n_div = make_fastdiv((uint32_t)tiles_n);
+    const uint32_t blocks = (uint32_t)(tiles_m * tiles_n);
+    hipStream_t s = (hipStream_t)stream;
+    LaunchScope scope(fused != nullptr ? fused_id : plain_id, bytes, s);
+    if (fused != nullptr) launch(blocks, s, f);
+    else launch(blocks, s);
+    return finish_launch(what);
 }
 
 }  // namespace ppqhip

@@ -280,6 +280,15 @@ struct MxFusedHost {
     uint8_t* out_elements; uint8_t* out_scales; int out_format;
 };
 
+// what every fused entry point checks about its output pointers, whatever format it packs (the int8 kernels pack MXINT8 and take no
+// out_format: mx_int8_tile.hpp)
+inline int check_fused_pointers(const char* what, const char* float_name, const float* c, const uint8_t* out_elements, const uint8_t* out_scales) {
+    if ((out_elements == nullptr) != (out_scales == nullptr)) { set_error("%s: out_elements and out_scales must both be set or both be null", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (c == nullptr && out_elements == nullptr) { set_error("%s: no output: %s and out_elements are both null", what, float_name); return PPQHIP_ERR_INVALID_VALUE; }
+    if (out_elements != nullptr && !aligned16(out_elements)) { set_error("%s: out_elements must be 16-byte aligned", what); return PPQHIP_ERR_INVALID_VALUE; }
+    return PPQHIP_OK;
+}
+
 // the host side of MxFusedOut: what both fused entry points check about the outputs before anything else of theirs; fills *fmt
 inline int check_fused_outputs(const char* what, const char* float_name, const float* c, const uint8_t* out_elements, const uint8_t* out_scales,
                                int out_format, MxFmt* fmt) {
@@ -287,10 +296,7 @@ inline int check_fused_outputs(const char* what, const char* float_name, const f
     if (out_format < PPQHIP_MXFP8_E4M3 || out_format > PPQHIP_MXFP4_E2M1 || !make_mx_fmt(out_format, fmt)) {
         set_error("%s: out_format: unknown MX format %d", what, out_format); return PPQHIP_ERR_INVALID_VALUE;
     }
-    if ((out_elements == nullptr) != (out_scales == nullptr)) { set_error("%s: out_elements and out_scales must both be set or both be null", what); return PPQHIP_ERR_INVALID_VALUE; }
-    if (c == nullptr && out_elements == nullptr) { set_error("%s: no output: %s and out_elements are both null", what, float_name); return PPQHIP_ERR_INVALID_VALUE; }
-    if (out_elements != nullptr && !aligned16(out_elements)) { set_error("%s: out_elements must be 16-byte aligned", what); return PPQHIP_ERR_INVALID_VALUE; }
-    return PPQHIP_OK;
+    return check_fused_pointers(what, float_name, c, out_elements, out_scales);
 }
 
 inline int check_format(const char* what, const char* operand, int format) {

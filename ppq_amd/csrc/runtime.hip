@@ -35,7 +35,8 @@ const char* const kKernelNames[K_NUM] = {
     "equalize_scale",
     "equalize_apply", "ssd_scales", "ssd_apply", "fq_measure_rows", "stat_moments", "stat_shape",
     "split_plan", "split_apply", "mx_fq", "mx_pack", "mx_unpack", "mx_gemm", "mx_conv",
-    "mx_gemm_fused", "mx_conv_fused", "mx_int8_gemm", "mx_int8_conv"};
+    "mx_gemm_fused", "mx_conv_fused", "mx_int8_gemm", "mx_int8_conv",
+    "mx_int8_gemm_fused", "mx_int8_conv_fused"};
 
 int num_cu() {
     static std::mutex mu;

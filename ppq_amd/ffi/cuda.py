@@ -6,7 +6,7 @@ from .._lib import lib
 from ._base import _KERNEL_FAILURE, _DeviceOf, _check, _f32, _ptr, _raise, _stream
 from .extension import HIP_EXTENSION
 from .mx import (MX_BLOCK, _mx_axis, _mx_codes_like, _mx_conv_args, _mx_dense, _mx_fused_args, _mx_fused_outputs, _mx_geometry,
-                 _mx_int8_conv_args, _mx_int8_matmul_args, _mx_matmul_args, mx_format_arg, mx_format_id, mx_packed_shapes)
+                 _mx_int8_conv_args, _mx_int8_fused_args, _mx_int8_matmul_args, _mx_matmul_args, mx_format_arg, mx_format_id, mx_packed_shapes)
 from .seam import CUDA_COMPLIER
 
 
@@ -428,6 +428,43 @@ class CUDA:
             _raise(lib.ppqhip_mx_int8_conv2d(x_elements.data_ptr(), x_scales.data_ptr(), w_elements.data_ptr(), w_scales.data_ptr(),
                                              _ptr(bias), out.data_ptr(), *geo[:13], _stream()))
         return out.permute(0, 3, 1, 2)
+
+    @ staticmethod
+    def MXInt8MatmulFused(a_elements, a_scales, b_elements, b_scales, k: int, bias=None, residual=None, relu: bool = False, out_format=None,
+                          out_float: bool = True):
+        """``MXInt8Matmul`` with the fused epilogue: ``v = A . B^T (+ bias) (+ residual[M, N])``, then the
+        ReLU (``v > 0 ? v : +0``, NaN kept), in ONE launch.  Returns ``(c, elements, scales)``: ``c`` the float32 ``[M, N]`` (None with
+        ``out_float=False``), ``elements [M, nbo * 32]`` / ``scales [M, nbo]`` ``v`` packed along its last axis as MXINT8 exactly as
+        ``MXPack`` packs it (None, None without ``out_format``).  ``out_format``: None or MXINT8, the one format these kernels pack."""
+        a_elements, a_scales, b_elements, b_scales, k, bias, m, n = _mx_int8_matmul_args(a_elements, a_scales, b_elements, b_scales, k, bias)
+        fo, residual = _mx_int8_fused_args(out_format, out_float, residual, [m, n], a_elements.device)
+        out, elements, scales = _mx_fused_outputs([m, n], fo, out_format, out_float, a_elements.device)
+        with _DeviceOf(a_elements):
+            _raise(lib.ppqhip_mx_int8_gemm_fused(a_elements.data_ptr(), a_scales.data_ptr(), b_elements.data_ptr(), b_scales.data_ptr(),
+                                                 _ptr(bias), _ptr(residual), 1 if relu else 0, _ptr(out), _ptr(elements), _ptr(scales),
+                                                 m, n, k, _stream()))
+        return out, elements, scales
+
+    @ staticmethod
+    def MXInt8Conv2dFused(x_elements, x_scales, w_elements, w_scales, c: int, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1),
+                          residual=None, relu: bool = False, out_format=None, out_float: bool = True):
+        """``MXInt8Conv2d`` with the fused epilogue: ``v = conv2d(x, w) (+ bias) (+ residual)``, then the ReLU
+        (``v > 0 ? v : +0``, NaN kept), in ONE launch.  ``residual`` is ``[N, O, OH, OW]``; a tensor that is not channels-last is
+        copied into that layout.  Returns ``(y, elements, scales)``: ``y`` the float32 ``[N, O, OH, OW]`` with channels-last strides
+        (None with ``out_float=False``), ``elements [N, OH, OW, nbo * 32]`` / ``scales [N, OH, OW, nbo]`` ``v`` packed along axis 1 as
+        MXINT8 exactly as ``MXPack`` packs it -- the x of the next ``MXInt8Conv2d`` -- (None, None without ``out_format``).
+        ``out_format``: None or MXINT8."""
+        x_elements, x_scales, w_elements, w_scales, bias, geo = _mx_int8_conv_args(x_elements, x_scales, w_elements, w_scales, c, bias, stride, padding, dilation)
+        n, o, oh, ow = geo[0], geo[4], geo[-2], geo[-1]
+        dev = x_elements.device
+        fo, residual = _mx_int8_fused_args(out_format, out_float, residual, [n, o, oh, ow], dev)
+        if residual is not None: residual = residual.permute(0, 2, 3, 1).contiguous()               # no copy when it is channels-last
+        out, elements, scales = _mx_fused_outputs([n, o, oh, ow], fo, out_format, out_float, dev)
+        with _DeviceOf(x_elements):
+            _raise(lib.ppqhip_mx_int8_conv2d_fused(x_elements.data_ptr(), x_scales.data_ptr(), w_elements.data_ptr(), w_scales.data_ptr(),
+                                                   _ptr(bias), _ptr(residual), 1 if relu else 0, _ptr(out), _ptr(elements), _ptr(scales),
+                                                   *geo[:13], _stream()))
+        return (out.permute(0, 3, 1, 2) if out is not None else None), elements, scales
 
     @ staticmethod
     def Sync():

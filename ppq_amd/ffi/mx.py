@@ -286,13 +286,28 @@ def _mx_fused_args(out_format, out_float, residual, shape, device):
     is a placeholder) and the residual, float32 of ``shape`` on ``device``."""
     fo = mx_format_id(out_format) if out_format is not None else MX_FORMATS['MXFP8_E4M3']
     if fo == MX_FORMATS['MXINT8']: raise RuntimeError(_KERNEL_FAILURE + 'out_format MXINT8 is not a format the fused epilogue packs')
+    return fo, _mx_fused_residual(out_format, out_float, residual, shape, device)
+
+
+def _mx_fused_residual(out_format, out_float, residual, shape, device):
+    """What every fused binding checks whatever it packs: that there is an output at all, and the residual, float32 of ``shape`` on
+    ``device``, which it returns."""
     if out_format is None and not out_float: raise RuntimeError(_KERNEL_FAILURE + 'no output: out_format is None and out_float is False')
     if residual is not None:
         _f32(residual, 'Residual')
         if list(residual.shape) != list(shape): raise RuntimeError(_KERNEL_FAILURE + f'residual of shape {list(residual.shape)}, expected {list(shape)}')
         if residual.device != device: raise RuntimeError(_KERNEL_FAILURE + 'residual is on another device')
         if len(shape) == 2: residual = residual.contiguous()
-    return fo, residual
+    return residual
+
+
+def _mx_int8_fused_args(out_format, out_float, residual, shape, device):
+    """The checks the fused int8 bindings add: ``out_format`` is None -- nothing is packed -- or MXINT8, the one format these kernels
+    pack (the entry points take no format); returns its id or None, and the residual."""
+    fo = mx_format_id(out_format) if out_format is not None else None
+    if fo is not None and fo != MX_FORMATS['MXINT8']:
+        raise RuntimeError(_KERNEL_FAILURE + f'out_format {getattr(out_format, "name", out_format)}: the int8 kernels pack MXINT8 only')
+    return fo, _mx_fused_residual(out_format, out_float, residual, shape, device)
 
 
 def _mx_fused_outputs(shape, fo, out_format, out_float, device):

@@ -377,14 +377,16 @@ def relu_positive_zero(v: torch.Tensor) -> torch.Tensor:
     return torch.where(v > 0, v, torch.where(v != v, v, torch.zeros_like(v)))
 
 
-def _check_fused(what: str, like, shape, residual, relu, out_format, out_float):
+def _check_fused(what: str, like, shape, residual, relu, out_format, out_float, int8: bool = False):
     """The checks of the keywords ``residual`` / ``relu`` / ``out_format`` / ``out_float``; ``like`` is an operand (for the device),
-    ``shape`` the result's.  Returns (fused, out_format as a member or None, out_float as a bool)."""
+    ``shape`` the result's; ``int8``: the kernels on the int8 MFMA, which pack MXINT8 and nothing else.
+    Returns (fused, out_format as a member or None, out_float as a bool)."""
     fused = residual is not None or bool(relu) or out_format is not None or out_float is not None
     if not fused: return False, None, True
     if out_format is not None:
         out_format = MXFormat.of(out_format)
-        if not out_format.is_float: raise RuntimeError(f'{what}: out_format {out_format.name} is not a format the fused epilogue packs')
+        if int8 and out_format is not MXFormat.MXINT8: raise RuntimeError(f'{what}: out_format {out_format.name}: the int8 kernels pack MXINT8 only')
+        if not int8 and not out_format.is_float: raise RuntimeError(f'{what}: out_format {out_format.name} is not a format the fused epilogue packs')
     if out_float is None: out_float = out_format is None
     if out_format is None and not out_float: raise RuntimeError(f'{what}: no output: out_format is None and out_float is False')
     if residual is not None:
@@ -503,24 +505,41 @@ def _mx_int8_matmul_torch(ae, as_, be, bs, bias):
     return torch.where(nan, _bits_to_float(torch.full_like(acc, 0, dtype=torch.int32) + 0x7fc00000), acc)
 
 
-def mx_int8_matmul(a: MXTensor, b: MXTensor, bias: torch.Tensor = None, use_kernels: bool = True) -> torch.Tensor:
+def mx_int8_matmul(a: MXTensor, b: MXTensor, bias: torch.Tensor = None, use_kernels: bool = True, residual: torch.Tensor = None,
+                   relu: bool = False, out_format=None, out_float: bool = None):
     """``a . b^T (+ bias)`` in float32 on two MXINT8 tensors: ``a`` is ``lead + [K]``, ``b`` is ``[N, K]``, both packed along their
     last axis; the result is ``lead + [N]``.  Per output and block of 32 the integer dot product is exact; scaled by the two block
     scales it is rounded once to float32, and the blocks are added in float32 in order, then the bias.  An
     output whose row of ``a`` or of ``b`` holds a NaN block (scale code 0xFF) is NaN.
     ``use_kernels=True``: the packed bytes go to the int8 MFMA as they are (``CUDA.MXInt8Matmul``; the tensors must be on the GPU).
-    ``False``: the same contract in torch ops on any device -- identical bits.  The five float formats are ``mx_matmul``'s."""
+    ``False``: the same contract in torch ops on any device -- identical bits.  The five float formats are ``mx_matmul``'s.
+    The fused epilogue, all in the ONE launch and with the meaning and return shapes of ``mx_matmul``'s:
+    ``residual`` (float32, the result's shape) is added after the bias; ``relu`` is ``v > 0 ? v : +0`` with NaN kept; ``out_format``
+    -- None or MXINT8, the one format these kernels pack -- returns the result as an ``MXTensor`` packed along its last axis, the bytes
+    of ``mx_quantize(v, 'MXINT8', -1)``; with ``out_float=True`` ``(tensor, MXTensor)``.  ``use_kernels=False`` is the torch arm followed
+    by the same steps in torch ops: identical bits here too.  With the defaults this is the plain kernel."""
     lead, n, k = _check_int8_matmul(a, b, bias)
+    fused, out_format, out_float = _check_fused('mx_int8_matmul', a, lead + [n], residual, relu, out_format, out_float, int8=True)
     ae, as_ = a.elements.reshape(-1, a.elements.shape[-1]), a.scales.reshape(-1, a.scales.shape[-1])
+    if use_kernels and fused:
+        y, oe, os_ = CUDA.MXInt8MatmulFused(ae.contiguous(), as_.contiguous(), b.elements.contiguous(), b.scales.contiguous(), k, bias,
+                                            residual.reshape(-1, n) if residual is not None else None, relu, out_format, out_float)
+        if y is not None: y = y.reshape(lead + [n])
+        packed = MXTensor(out_format, lead + [n], len(lead), oe.reshape(lead + [oe.shape[-1]]), os_.reshape(lead + [os_.shape[-1]])) if oe is not None else None
+        return _fused_result(y, packed, out_float)
     if use_kernels: y = CUDA.MXInt8Matmul(ae.contiguous(), as_.contiguous(), b.elements.contiguous(), b.scales.contiguous(), k, bias)
     else: y = _mx_int8_matmul_torch(ae, as_, b.elements, b.scales, bias)
-    return y.reshape(lead + [n])
+    y = y.reshape(lead + [n])
+    return _fused_torch(y, residual, relu, out_format, out_float, -1) if fused else y
 
 
-def mx_int8_linear(x: torch.Tensor, weight: MXTensor, bias: torch.Tensor = None, use_kernels: bool = True, scale_rule=MXScaleRule.FLOOR) -> torch.Tensor:
+def mx_int8_linear(x: torch.Tensor, weight: MXTensor, bias: torch.Tensor = None, use_kernels: bool = True, scale_rule=MXScaleRule.FLOOR,
+                   residual: torch.Tensor = None, relu: bool = False, out_format=None, out_float: bool = None):
     """A linear layer on an MXINT8 weight ``[N, K]``: ``mx_quantize(x, 'MXINT8', -1, scale_rule=...)``, then ``mx_int8_matmul`` -- two
-    launches, the bias added in the GEMM's epilogue."""
-    return mx_int8_matmul(mx_quantize(x, MXFormat.MXINT8, -1, use_kernels=use_kernels, scale_rule=scale_rule), weight, bias, use_kernels)
+    launches, the bias added in the GEMM's epilogue.  ``residual``, ``relu``, ``out_format`` and ``out_float`` are ``mx_int8_matmul``'s
+    (``out_format`` is packed by FLOOR)."""
+    return mx_int8_matmul(mx_quantize(x, MXFormat.MXINT8, -1, use_kernels=use_kernels, scale_rule=scale_rule), weight, bias, use_kernels,
+                          residual, relu, out_format, out_float)
 
 
 # ---- convolution on the packed tensors (DESIGN.md section 9.15) --------------------------------------------------------------------
@@ -645,7 +664,8 @@ def _mx_int8_gather_torch(x: MXTensor, kernel, stride, padding, dilation, out):
     return ge.reshape(n * oh * ow, -1), gs.reshape(n * oh * ow, -1)
 
 
-def mx_int8_conv2d_packed(x: MXTensor, w: MXTensor, bias: torch.Tensor = None, stride=1, padding=0, dilation=1, use_kernels: bool = True) -> torch.Tensor:
+def mx_int8_conv2d_packed(x: MXTensor, w: MXTensor, bias: torch.Tensor = None, stride=1, padding=0, dilation=1, use_kernels: bool = True,
+                          residual: torch.Tensor = None, relu: bool = False, out_format=None, out_float: bool = None):
     """``conv2d(x, w) (+ bias)`` in float32 on two MXINT8 tensors: ``x`` is ``[N, C, H, W]``, ``w`` is ``[O, C, kh, kw]``, both packed
     along axis 1; ``stride``, ``padding`` (symmetric) and ``dilation`` are ints or (h, w) pairs, groups is 1.  The result is
     ``[N, O, OH, OW]`` with the bits of ``mx_int8_matmul`` on the rows of the implicit GEMM: per output and
@@ -655,24 +675,39 @@ def mx_int8_conv2d_packed(x: MXTensor, w: MXTensor, bias: torch.Tensor = None, s
     ``use_kernels=True``: the packed bytes go to the int8 MFMA as they are, the rows gathered by address (``CUDA.MXInt8Conv2d``; the
     tensors must be on the GPU); the result has channels-last strides.  ``False``: the same contract in torch ops on any device --
     identical bits: the packed blocks of the windows gathered by indexing, then the torch arm of ``mx_int8_matmul``.  The five float
-    formats are ``mx_conv2d_packed``'s."""
+    formats are ``mx_conv2d_packed``'s.
+    The fused epilogue, all in the ONE launch and with the meaning and return shapes of
+    ``mx_conv2d_packed``'s: ``residual`` (float32 ``[N, O, OH, OW]``; channels-last is read in place, anything else is copied) is added
+    after the bias; ``relu`` is ``v > 0 ? v : +0`` with NaN kept; ``out_format`` -- None or MXINT8 -- returns the result as an
+    ``MXTensor`` ``[N, O, OH, OW]`` packed along axis 1, the bytes of ``mx_quantize(v, 'MXINT8', 1)`` and what this function takes as
+    ``x``; with ``out_float=True`` ``(tensor, MXTensor)``.  ``use_kernels=False``: the torch arm, then the same steps in torch ops --
+    identical bits.  With the defaults this is the plain kernel."""
     stride, padding, dilation, out = _check_int8_conv(x, w, bias, stride, padding, dilation)
-    if use_kernels: return CUDA.MXInt8Conv2d(x.elements, x.scales, w.elements, w.scales, x.shape[1], bias, stride, padding, dilation)
     o = w.shape[0]
+    shape = [x.shape[0], o, out[0], out[1]]
+    fused, out_format, out_float = _check_fused('mx_int8_conv2d', x, shape, residual, relu, out_format, out_float, int8=True)
+    if use_kernels and fused:
+        y, oe, os_ = CUDA.MXInt8Conv2dFused(x.elements, x.scales, w.elements, w.scales, x.shape[1], bias, stride, padding, dilation,
+                                            residual, relu, out_format, out_float)
+        return _fused_result(y, MXTensor(out_format, shape, 1, oe, os_) if oe is not None else None, out_float)
+    if use_kernels: return CUDA.MXInt8Conv2d(x.elements, x.scales, w.elements, w.scales, x.shape[1], bias, stride, padding, dilation)
     ge, gs = _mx_int8_gather_torch(x, w.shape[2:], stride, padding, dilation, out)
     y = _mx_int8_matmul_torch(ge, gs, w.elements.reshape(o, -1), w.scales.reshape(o, -1), bias)
-    return y.reshape(x.shape[0], out[0], out[1], o).permute(0, 3, 1, 2)
+    y = y.reshape(x.shape[0], out[0], out[1], o).permute(0, 3, 1, 2)
+    return _fused_torch(y, residual, relu, out_format, out_float, 1) if fused else y
 
 
 def mx_int8_conv2d(x: torch.Tensor, weight: MXTensor, bias: torch.Tensor = None, stride=1, padding=0, dilation=1, groups: int = 1,
-                   use_kernels: bool = True, scale_rule=MXScaleRule.FLOOR) -> torch.Tensor:
+                   use_kernels: bool = True, scale_rule=MXScaleRule.FLOOR, residual: torch.Tensor = None, relu: bool = False,
+                   out_format=None, out_float: bool = None):
     """A convolution on an MXINT8 weight as it runs in deployment: ``mx_quantize(x, 'MXINT8', 1, scale_rule=...)`` -- ``x``
     ``[N, C, H, W]``, contiguous or channels-last --, then ``mx_int8_conv2d_packed`` with ``weight`` ``[O, C, kh, kw]``: two launches,
-    the bias added in the kernel's epilogue."""
+    the bias added in the kernel's epilogue.  ``residual``, ``relu``, ``out_format`` and ``out_float`` are ``mx_int8_conv2d_packed``'s
+    (``out_format`` is packed by FLOOR)."""
     if groups != 1: raise RuntimeError(f'mx_int8_conv2d: groups must be 1, got {groups}')
     if isinstance(x, torch.Tensor) and x.dim() != 4: raise RuntimeError(f'mx_int8_conv2d: x must be 4-d [N, C, H, W], got shape {list(x.shape)}')
     return mx_int8_conv2d_packed(mx_quantize(x, MXFormat.MXINT8, 1, use_kernels=use_kernels, scale_rule=scale_rule), weight, bias, stride, padding,
-                                 dilation, use_kernels)
+                                 dilation, use_kernels, residual, relu, out_format, out_float)
 
 
 def _activated(config) -> bool:
@@ -874,15 +909,17 @@ class MXDeployment:
     name -> reason for every MX operation that stays on the simulated path --, ``weights`` -- the packed weights
     (``export_graph_mx``).  ``refresh()`` packs the weights again after they changed; ``remove()`` drops the overrides, after which
     the executor runs the simulation again."""
-    def __init__(self, graph, executor, delegators=None, use_kernels: bool = True, fuse: bool = False):
+    def __init__(self, graph, executor, delegators=None, use_kernels: bool = True, fuse: bool = False, fuse_int8: bool = False):
+        if fuse_int8 and not fuse: raise RuntimeError('deploy_graph_mx: fuse_int8=True groups the int8 operations of a fused deployment: it needs fuse=True')
         self.graph, self.executor, self.delegators, self.use_kernels, self.fuse = graph, executor, delegators, use_kernels, fuse
+        self.fuse_int8 = fuse_int8
         self.deployed: List[str] = []
         self.skipped: Dict[str, str] = {}
         self.groups: Dict[str, MXFusedGroup] = {}     # fuse=True: first operation's name -> what its one launch covers
         self.weights: Dict[str, MXTensor] = {}
         self._operands: Dict[str, MXTensor] = {}      # operation name -> its weight as the kernel takes it
         self._runs: Dict[str, object] = {}            # operation name -> its override
-        self._int8: set = set()                       # the deployed operations on the int8 MFMA: no fused epilogue, no packed hand-over
+        self._int8: set = set()                       # the deployed operations on the int8 MFMA: grouped and handed packed tensors with fuse_int8 only
         self.refresh()
 
     def _format(self, config) -> Optional[MXFormat]:
@@ -922,9 +959,12 @@ class MXDeployment:
             stride, padding, operand = a.get('strides', 1), a.get('pads', 0), packed
             dilation = a.get('dilations', 1)
 
-            def run_int8(op, x):
-                return mx_int8_conv2d(x[0], self._operands[op.name], x[2] if len(x) > 2 else None, stride, padding, dilation,
-                                      use_kernels=use_kernels, scale_rule=arule)
+            def run_int8(op, x, **tail):
+                bias = x[2] if len(x) > 2 else None
+                if isinstance(x[0], MXTensor):         # handed over packed by an int8 producer's fused launch (fuse_int8)
+                    return mx_int8_conv2d_packed(_handed(op, x[0], afmt, 1), self._operands[op.name], bias, stride, padding, dilation,
+                                                 use_kernels=use_kernels, **tail)
+                return mx_int8_conv2d(x[0], self._operands[op.name], bias, stride, padding, dilation, use_kernels=use_kernels, scale_rule=arule, **tail)
 
             def run(op, x, **tail):
                 bias = x[2] if len(x) > 2 else None
@@ -936,8 +976,11 @@ class MXDeployment:
             # a MatMul weight [in, out] is packed along axis 0: its bytes are those of [out, in] packed along axis 1
             operand = packed if op.type == 'Gemm' else MXTensor(packed.format, packed.shape[::-1], 1, packed.elements, packed.scales)
 
-            def run_int8(op, x):
-                return mx_int8_linear(x[0], self._operands[op.name], x[2] if len(x) > 2 else None, use_kernels=use_kernels, scale_rule=arule)
+            def run_int8(op, x, **tail):
+                bias = x[2] if len(x) > 2 else None
+                if isinstance(x[0], MXTensor):
+                    return mx_int8_matmul(_handed(op, x[0], afmt, len(x[0].shape) - 1), self._operands[op.name], bias, use_kernels, **tail)
+                return mx_int8_linear(x[0], self._operands[op.name], bias, use_kernels=use_kernels, scale_rule=arule, **tail)
 
             def run(op, x, **tail):
                 bias = x[2] if len(x) > 2 else None
@@ -961,9 +1004,13 @@ class MXDeployment:
                 continue
             run, self._operands[name] = plan
             self._runs[name] = run
-            self.executor.register_operation_override(name, run, takes_packed=self.fuse and name not in self._int8)
+            self.executor.register_operation_override(name, run, takes_packed=self.fuse and self._groups(name))
             self.deployed.append(name)
         if self.fuse: self._plan_groups()
+
+    def _groups(self, name: str) -> bool:
+        """Whether a deployed operation takes part in the groups: a float-format one always, one on the int8 MFMA with ``fuse_int8``."""
+        return name not in self._int8 or self.fuse_int8
 
     def _plan_groups(self) -> None:
         """A tail behind every deployed operation -- an optional Add whose other operand is a float activation computed earlier,
@@ -989,7 +1036,7 @@ class MXDeployment:
             return v.dest_ops[0]
 
         for op in order:
-            if op.name not in self._runs or op.name in self._int8: continue            # the int8 kernels have no fused epilogue
+            if op.name not in self._runs or not self._groups(op.name): continue       # an int8 operation heads a group with fuse_int8 only
             group = MXFusedGroup([op.name])
             t = op.outputs[0]
             if len(op.outputs) != 1 or not all(passes(c) for c in op.config.output_quantization_config):
@@ -1017,12 +1064,15 @@ class MXDeployment:
                     claimed.add(relu.name)
                     t = relu.outputs[0]
             group.output = t.name
-            takers = [d for d in t.dest_ops if d.name in self._runs and d.name not in self._int8]
+            takers = [d for d in t.dest_ops if d.name in self._runs and self._groups(d.name)]
             kind = (lambda o: 'Conv' if o.type == 'Conv' else 'Gemm')
             if not takers: group.notes.append('float output: no deployed consumer')
             elif any(d.inputs[0] is not t or sum(1 for x in d.inputs if x is t) != 1 for d in takers): group.notes.append('float output: a deployed consumer does not read it as its activation')
             elif any(kind(d) != kind(op) for d in takers): group.notes.append('float output: a deployed consumer packs along another axis')
             elif len({self._format(d.config.input_quantization_config[0]) for d in takers}) != 1: group.notes.append('float output: the deployed consumers read it in different formats')
+            elif (takers[0].name in self._int8) != (op.name in self._int8):
+                group.notes.append('float output: the int8 kernels pack MXINT8 and nothing else, the scaled-MFMA kernels never pack it: '
+                                   f'{op.name} and its deployed consumers run on different ones')
             elif any(self._rule(d.config.input_quantization_config[0]) is not MXScaleRule.FLOOR for d in takers):
                 rules = sorted({self._rule(d.config.input_quantization_config[0]).name for d in takers} - {'FLOOR'})
                 group.notes.append(f'float output: a deployed consumer makes its scales by {" / ".join(rules)}, the fused epilogue packs by FLOOR')
@@ -1056,7 +1106,7 @@ class MXDeployment:
         self._int8 = set()
 
 
-def deploy_graph_mx(graph, executor, delegators=None, use_kernels: bool = True, fuse: bool = False) -> MXDeployment:
+def deploy_graph_mx(graph, executor, delegators=None, use_kernels: bool = True, fuse: bool = False, fuse_int8: bool = False) -> MXDeployment:
     """Put the MX operations of a ``quantize_graph_mx`` graph on the hardware path: the weights are packed (``export_graph_mx``) and
     every eligible operation gets an operation override on ``executor`` that quantises its activation and runs the packed kernel --
     a Conv with ``group`` 1 ``mx_conv2d`` (the activation delegator's format, the bias, ``strides`` and ``pads``), a Gemm ``mx_linear``,
@@ -1072,5 +1122,10 @@ def deploy_graph_mx(graph, executor, delegators=None, use_kernels: bool = True, 
     quantises it itself): the consumer then quantises nothing.  It is written as float32 only when something reads it as float.  ``.groups``
     records every group: members, residual, relu, ``out_format`` and, in ``notes``, why an Add was not fused or the output not
     packed.  A forward that hooks a member or asks for an intermediate runs that group's operations one by one, as ``fuse=False``.
-    The MXINT8 kernels have no fused epilogue: such an operation is deployed alone, heads no group and is handed nothing packed."""
-    return MXDeployment(graph, executor, delegators, use_kernels, fuse)
+    ``fuse_int8=True`` (with ``fuse=True`` only): the operations on the int8 MFMA take part as well -- each heads
+    a group exactly as a float-format one does, with the same tail and the same notes, its launch the fused int8 kernel, and the
+    tail's last tensor leaves it packed as MXINT8 when every deployed consumer is an int8 operation that reads it as its activation,
+    along the packed axis and by FLOOR.  Between an int8 launch and a float-format one the tensor is handed over as float32 (a note says
+    so): neither kind packs the other's format.  Without ``fuse_int8`` (the default) an int8 operation is deployed alone, heads no
+    group and is handed nothing packed."""
+    return MXDeployment(graph, executor, delegators, use_kernels, fuse, fuse_int8)
