@@ -980,6 +980,38 @@ int ppqhip_mx_int8_conv2d_fused(const uint8_t* x_elements, const uint8_t* x_scal
                                 int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w,
                                 void* stream);
 
+/* Linear INT8 layers on the int8 MFMA (ppq_amd/int8.py int8_matmul / int8_conv2d_packed; ADDED under ABI 4) --- */
+/* What an integer backend runs for a per-tensor / per-channel linear INT8 layer, on v_mfma_i32_16x16x32_i8 with the int32 accumulator
+ * chained through the instruction's C operand over all of K.  a [m, kp] and b [n, kp] are int8 codes, kp = ceil32(k), bytes k .. kp - 1
+ * of every row of b zero; b is symmetric (zero point 0), zx (-128 .. 127) is a's zero point as stored.  Per output, in this order:
+ *   I = sum_k b[n, k] (a[m, k] - zx), exact in int32 -- the accumulator starts at -zx * b_sums[n], b_sums[n] = sum_k b[n, k] (int32 [n];
+ *       may be NULL when zx == 0), and the MFMAs add sum_k b a;
+ *   t = float32(I), round to nearest even;  v = t * mul[n] (float32 [n], sx * sw[n] made by the caller; one multiply, no FMA);
+ *   v = v + bias[n] (bias set);  v = v + residual[m, n] (residual set: float32 [m, n] row-major);  relu != 0: v = v > 0 ? v : +0, a NaN
+ *       staying a NaN;
+ *   c set: v is stored as float32 [m, n];  q set: its code is stored as int8 [m, op], op = ceil32(n): exactly the bits ppqhip_to_int_t
+ *       gives for v under (sy, zy, qmin, qmax, rounding) -- clamp(ppq_tensor_round(v / sy) + zy, qmin, qmax) in float32, truncated --
+ *       with zy, qmin, qmax in the stored int8 domain (a 0 .. 255 grid is passed re-centred by -128, which gives the same clamp), q_nan
+ *       for a NaN v (ppqhip_to_int_t's 0, re-centred likewise), and zy in the padding columns n .. op - 1.
+ * One accumulation order, no atomics, no split-K: two calls give identical bits.
+ * Refused before any launch: no output (c and q null); zx outside int8; with q set: zy, qmin, qmax or q_nan outside int8, qmin > qmax,
+ * a rounding policy without a tensor form; negative sizes or sizes above 2^31 - 1; kp >= 65536 (|I| could leave int32); a null a, b or
+ * mul; b_sums null with zx != 0; a, b, c or q not 16-byte aligned; an output overlapping an input or the other output.  m == 0 or
+ * n == 0 launches nothing; k == 0 runs the tail on I = 0.  Booked under "int8_gemm" / "int8_conv". */
+int ppqhip_int8_gemm(const int8_t* a, const int8_t* b, const int32_t* b_sums, int zx, const float* mul, const float* bias,
+                     const float* residual, int relu, float* c, int8_t* q, float sy, int zy, int qmin, int qmax, int rounding, int q_nan,
+                     int64_t m, int64_t n, int64_t k, void* stream);
+/* The same layer as a convolution, an implicit GEMM without an im2col buffer: x [n, h, wd, cp] and w [o, kh, kw, cp] int8 codes,
+ * cp = ceil32(c), the channels c .. cp - 1 of w zero; y [n, oh, ow, o] (the channels-last storage of [n, o, oh, ow]) and q
+ * [n, oh, ow, op]; residual [n, oh, ow, o].  Sizes and geometry are those of ppqhip_mx_int8_conv2d; row (n, oy, ox) of the implicit
+ * GEMM has kp = kh * kw * cp bytes ordered (ky, kx, channel), and the result has exactly the bits of ppqhip_int8_gemm on the gathered
+ * rows.  A tap in the padding is a real 0, the code zx: it is not read, the kernel stages the byte zx for it.  Refused as
+ * ppqhip_int8_gemm and ppqhip_mx_int8_conv2d refuse. */
+int ppqhip_int8_conv2d(const int8_t* x, const int8_t* w, const int32_t* w_sums, int zx, const float* mul, const float* bias,
+                       const float* residual, int relu, float* y, int8_t* q, float sy, int zy, int qmin, int qmax, int rounding,
+                       int q_nan, int64_t n, int64_t c, int64_t h, int64_t wd, int64_t o, int64_t kh, int64_t kw, int64_t stride_h,
+                       int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, void* stream);
+
 /* ---- pointwise (1x1) convolution on the FP32-input MFMA (ADDED under ABI 4) ---------------------------------
  * y[n, o, oh, ow] = sum_k w[o, k] x[n, k, oh * stride, ow * stride] (+ bias[o]) for contiguous NCHW float32 x [n, c, h, wd],
  * w [o, c] (a [o, c, 1, 1] convolution weight as it lies) and y [n, o, ho, wo], ho = (h - 1) / stride + 1, wo likewise; no padding,

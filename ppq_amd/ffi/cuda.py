@@ -5,6 +5,7 @@ from .. import ffi as _package     # public entry points are called through the 
 from .._lib import lib
 from ._base import _KERNEL_FAILURE, _DeviceOf, _check, _f32, _ptr, _raise, _stream
 from .extension import HIP_EXTENSION
+from .int8 import int8_conv2d as _int8_conv2d, int8_matmul as _int8_matmul
 from .mx import (MX_BLOCK, _mx_axis, _mx_codes_like, _mx_conv_args, _mx_dense, _mx_fused_args, _mx_fused_outputs, _mx_geometry,
                  _mx_int8_conv_args, _mx_int8_fused_args, _mx_int8_matmul_args, _mx_matmul_args, mx_format_arg, mx_format_id, mx_packed_shapes)
 from .seam import CUDA_COMPLIER
@@ -465,6 +466,21 @@ class CUDA:
                                                    _ptr(bias), _ptr(residual), 1 if relu else 0, _ptr(out), _ptr(elements), _ptr(scales),
                                                    *geo[:13], _stream()))
         return (out.permute(0, 3, 1, 2) if out is not None else None), elements, scales
+
+    @ staticmethod
+    def Int8Matmul(a, b, b_sums, zx: int, mul, bias=None, residual=None, relu: bool = False, out_float: bool = True, out_q=None):
+        """A linear INT8 layer on the int8 MFMA, the int32 accumulator chained over all of K: ``a [M, Kp]`` and
+        ``b [N, Kp]`` int8 codes (``b`` symmetric, ``zx`` the zero point of ``a``), ``v = float32(sum b (a - zx)) * mul[n] (+ bias)
+        (+ residual)``, the ReLU; ``(c, q)``: ``v`` as float32 and / or its int8 codes under ``out_q = (sy, zy, qmin, qmax, rounding,
+        q_nan)`` with the bits of ``LinearQuantize_ToInt``.  The bits of ``tests/int8_reference.py``."""
+        return _int8_matmul(a, b, b_sums, zx, mul, bias, residual, relu, out_float, out_q)
+
+    @ staticmethod
+    def Int8Conv2d(x, w, w_sums, zx: int, mul, c: int, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), residual=None,
+                   relu: bool = False, out_float: bool = True, out_q=None):
+        """``Int8Matmul`` as a convolution, an implicit GEMM: ``x [N, H, W, Cp]``, ``w [O, kh, kw, Cp]`` int8 codes; a tap in the padding
+        is the code ``zx``.  ``(y, q)``: float32 ``[N, O, OH, OW]`` with channels-last strides, int8 ``[N, OH, OW, ceil32(O)]``."""
+        return _int8_conv2d(x, w, w_sums, zx, mul, c, bias, stride, padding, dilation, residual, relu, out_float, out_q)
 
     @ staticmethod
     def Sync():

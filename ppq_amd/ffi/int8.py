@@ -1,0 +1,90 @@
+"""The bindings of the linear INT8 kernels (``csrc/int8_gemm.hip``, ``csrc/int8_conv.hip``): ``CUDA.Int8Matmul``
+and ``CUDA.Int8Conv2d`` forward here.  Operands are int8 codes with the reduction axis last and padded to a multiple of 32."""
+import torch
+
+from .._lib import lib
+from ._base import _KERNEL_FAILURE, _DeviceOf, _check, _f32, _ptr, _raise, _stream
+
+INT8_BLOCK = 32          # the K of one v_mfma_i32_16x16x32_i8: rows are padded to it
+
+
+def _refuse(what: str): raise RuntimeError(_KERNEL_FAILURE + what)
+
+
+def _int8_operands(rank, names, operands):
+    """int8, on one GPU, ``rank``-d, contiguous, the last axis a multiple of 32 and the same for both; a tensor whose data does not
+    start on a 16-byte boundary is copied (the allocator aligns)."""
+    dev, out = operands[0].device if isinstance(operands[0], torch.Tensor) else None, []
+    for name, t in zip(names, operands):
+        _check(t, torch.int8, f'{name}(Expect to be INT8)')
+        if t.dim() != rank: _refuse(f'{name} must be {rank}-d, got {list(t.shape)}')
+        if t.device != dev: _refuse(f'{name} is on another device')
+        if not t.is_contiguous(): _refuse(f'{name} must be contiguous')
+        if t.shape[-1] % INT8_BLOCK: _refuse(f'{name}: the last axis ({t.shape[-1]}) must be padded to a multiple of {INT8_BLOCK}')
+        out.append(t.clone() if t.data_ptr() % 16 else t)
+    if out[0].shape[-1] != out[1].shape[-1]: _refuse(f'{names[0]} and {names[1]} differ in their last axis: {out[0].shape[-1]} and {out[1].shape[-1]}')
+    return out
+
+
+def _int8_tail(n, shape, dev, sums, zx, mul, bias, residual, out_float, out_q):
+    """The checks of everything but the operands; ``shape`` is the result's with the columns last.  Returns the tensors as the kernel
+    takes them, the outputs and the seven scalars of the output grid."""
+    zx = int(zx)
+    if not -128 <= zx <= 127: _refuse(f'zx {zx} is not an int8 zero point')
+    for name, t in (('mul', mul), ('bias', bias)):
+        if t is None and name == 'bias': continue
+        _f32(t, name)
+        if list(t.shape) != [n]: _refuse(f'{name} of shape {list(t.shape)}, expected [{n}]')
+        if t.device != dev: _refuse(f'{name} is on another device')
+    if sums is not None:
+        _check(sums, torch.int32, 'sums(Expect to be INT32)')
+        if list(sums.shape) != [n] or sums.device != dev: _refuse(f'sums of shape {list(sums.shape)} on {sums.device}, expected [{n}] on {dev}')
+        sums = sums.contiguous()
+    elif zx != 0: _refuse('sums is required with a zero point other than 0')
+    if residual is not None:
+        _f32(residual, 'Residual')
+        if list(residual.shape) != list(shape): _refuse(f'residual of shape {list(residual.shape)}, expected {list(shape)}')
+        if residual.device != dev: _refuse('residual is on another device')
+        residual = residual.contiguous()
+    if out_q is None and not out_float: _refuse('no output: out_q is None and out_float is False')
+    c = torch.empty(shape, dtype=torch.float32, device=dev) if out_float else None
+    q, grid = None, (1.0, 0, -128, 127, 0, 0)
+    if out_q is not None:
+        sy, zy, qmin, qmax, rounding, q_nan = out_q
+        grid = (float(sy), int(zy), int(qmin), int(qmax), int(rounding), int(q_nan))
+        q = torch.empty(list(shape[:-1]) + [(n + INT8_BLOCK - 1) // INT8_BLOCK * INT8_BLOCK], dtype=torch.int8, device=dev)
+    return sums, zx, mul.contiguous(), (bias.contiguous() if bias is not None else None), residual, c, q, grid
+
+
+def int8_matmul(a, b, b_sums, zx: int, mul, bias=None, residual=None, relu: bool = False, out_float: bool = True, out_q=None):
+    """``ppqhip_int8_gemm``: ``a [M, Kp]`` and ``b [N, Kp]`` int8 codes, ``b_sums [N]`` int32 (None with ``zx == 0``), ``mul [N]``
+    float32.  ``out_q``: None or ``(sy, zy, qmin, qmax, rounding, q_nan)`` in the stored int8 domain.  Returns ``(c, q)``: float32
+    ``[M, N]`` (None with ``out_float=False``) and int8 ``[M, ceil32(N)]`` (None without ``out_q``)."""
+    a, b = _int8_operands(2, ('A', 'B'), (a, b))
+    m, n = a.shape[0], b.shape[0]
+    sums, zx, mul, bias, residual, c, q, grid = _int8_tail(n, [m, n], a.device, b_sums, zx, mul, bias, residual, out_float, out_q)
+    with _DeviceOf(a):
+        _raise(lib.ppqhip_int8_gemm(a.data_ptr(), b.data_ptr(), _ptr(sums), zx, mul.data_ptr(), _ptr(bias), _ptr(residual), 1 if relu else 0,
+                                    _ptr(c), _ptr(q), *grid, m, n, a.shape[1], _stream()))
+    return c, q
+
+
+def int8_conv2d(x, w, w_sums, zx: int, mul, c: int, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), residual=None,
+                relu: bool = False, out_float: bool = True, out_q=None):
+    """``ppqhip_int8_conv2d``: ``x [N, H, W, Cp]`` and ``w [O, kh, kw, Cp]`` int8 codes of a convolution with ``c`` channels.
+    ``residual`` is ``[N, O, OH, OW]``; a tensor that is not channels-last is copied into that layout.  Returns ``(y, q)``: float32
+    ``[N, O, OH, OW]`` with channels-last strides and int8 ``[N, OH, OW, ceil32(O)]``."""
+    x, w = _int8_operands(4, ('x', 'w'), (x, w))
+    c = int(c)
+    if not 0 < c <= x.shape[-1] or x.shape[-1] - c >= INT8_BLOCK: _refuse(f'c = {c} does not pad to the {x.shape[-1]} stored channels')
+    (n, h, wd, _), (o, kh, kw, _) = x.shape, w.shape
+    (sh, sw), (ph, pw), (dh, dw) = ([int(v) for v in pair] for pair in (stride, padding, dilation))
+    if min(sh, sw, dh, dw) < 1 or min(ph, pw) < 0: _refuse(f'stride {(sh, sw)} and dilation {(dh, dw)} must be at least 1, padding {(ph, pw)} at least 0')
+    oh, ow = (h + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (wd + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    if oh < 1 or ow < 1: _refuse(f'a {kh} x {kw} kernel with dilation {(dh, dw)} does not fit an input of {h} x {wd} padded by {(ph, pw)}')
+    if residual is not None and isinstance(residual, torch.Tensor) and residual.dim() == 4: residual = residual.permute(0, 2, 3, 1)
+    sums, zx, mul, bias, residual, y, q, grid = _int8_tail(o, [n, oh, ow, o], x.device, w_sums, zx, mul, bias, residual, out_float, out_q)
+    with _DeviceOf(x):
+        _raise(lib.ppqhip_int8_conv2d(x.data_ptr(), w.data_ptr(), _ptr(sums), zx, mul.data_ptr(), _ptr(bias), _ptr(residual), 1 if relu else 0,
+                                      _ptr(y), _ptr(q), *grid, n, c, h, wd, o, kh, kw, sh, sw, ph, pw, dh, dw, _stream()))
+    return (y.permute(0, 3, 1, 2) if y is not None else None), q

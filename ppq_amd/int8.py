@@ -1,0 +1,243 @@
+"""Linear INT8 layers as an integer backend runs them: the per-tensor / per-channel INT8 graphs PPQ calibrates,
+executed on integers instead of simulated in float32.  An ``Int8Tensor`` holds the codes ``LinearQuantize_ToInt`` makes of a tensor under
+a PPQ ``TensorQuantizationConfig``; ``int8_matmul`` and ``int8_conv2d_packed`` multiply two of them on the int8 MFMA of gfx950 with the
+int32 accumulator chained over all of K (``csrc/int8_gemm.hip``, ``csrc/int8_conv.hip``) and finish every output once:
+
+    I = sum_k w[o, k] (x[m, k] - zx)       exact, int32
+    v = float32(I) * (sx * sw[o])          one conversion (nearest even), one float32 multiply
+    v = v + bias[o];  v = v + residual[m, o];  ReLU as v > 0 ? v : +0 (NaN kept)
+    q = clamp(round(v / sy) + zy, qmin, qmax)   the bits of LinearQuantize_ToInt on v
+
+``use_kernels=False`` states the same contract in torch ops on any device, with identical bits (``tests/int8_reference.py`` is the NumPy
+oracle of both).  Codes are stored as int8: a config whose range lies in 0 .. 255 is stored re-centred, code - 128 and zero point - 128.
+"""
+from typing import Optional
+
+import torch
+
+from .core import QuantizationProperty, rounding_value
+from .ffi import CUDA, INT8_BLOCK
+from .mx import _pair, relu_positive_zero
+from .round import ppq_tensor_round
+
+__all__ = ['Int8Tensor', 'int8_quantize', 'int8_dequantize', 'int8_matmul', 'int8_linear', 'int8_conv2d_packed', 'int8_conv2d']
+
+MAX_KP = 65536           # padded reduction lengths from here on are refused: |I| could leave int32
+
+
+class Int8Tensor:
+    """int8 codes of a tensor of ``shape`` under one linear grid.  ``values``: the codes with axis ``axis`` -- the reduction axis of
+    the layer -- moved last and padded to a multiple of 32 (with the zero point; a weight's is 0).  ``scale``: float32, a scalar
+    tensor or ``[shape[0]]`` (a weight quantised per output channel); ``zero_point``, ``qmin``, ``qmax``: ints in the stored int8
+    domain; ``rounding``: the policy's number.  A weight also carries ``sums``: int32 ``[shape[0]]``, the sum of its codes per row."""
+    __slots__ = ('values', 'shape', 'axis', 'scale', 'zero_point', 'qmin', 'qmax', 'rounding', 'sums')
+
+    def __init__(self, values, shape, axis, scale, zero_point, qmin, qmax, rounding, sums=None):
+        self.values, self.shape, self.axis = values, tuple(int(d) for d in shape), int(axis)
+        self.scale, self.zero_point, self.qmin, self.qmax, self.rounding, self.sums = scale, int(zero_point), int(qmin), int(qmax), int(rounding), sums
+
+    @ property
+    def device(self): return self.values.device
+
+    def dequantize(self) -> torch.Tensor:
+        """``(code - zero_point) * scale`` in float32, in the tensor's own layout."""
+        codes = self.values[..., :self.shape[self.axis]].movedim(-1, self.axis).to(torch.float32)
+        scale = self.scale.reshape([-1] + [1] * (len(self.shape) - 1)) if self.scale.numel() > 1 else self.scale
+        return (codes - float(self.zero_point)) * scale
+
+
+def _grid(what: str, config):
+    """(scale, offset, recentre, stored zero point or None for a per-channel config, stored qmin, stored qmax, rounding, channel
+    axis) of a linear INT8 config; refuses what int8 codes cannot hold."""
+    policy = getattr(config, 'policy', None)
+    if policy is not None and policy.has_property(QuantizationProperty.FLOATING): raise RuntimeError(f'{what}: a floating-point config has no int8 codes')
+    scale, offset = config.scale, config.offset
+    if not isinstance(scale, torch.Tensor) or not isinstance(offset, torch.Tensor): raise RuntimeError(f'{what}: the config has no scale / offset tensors: calibrate it first')
+    qmin, qmax = int(config.quant_min), int(config.quant_max)
+    if qmin > qmax: raise RuntimeError(f'{what}: quant_min {qmin} above quant_max {qmax}')
+    if -128 <= qmin and qmax <= 127: recentre = 0
+    elif 0 <= qmin and qmax <= 255: recentre = 128
+    else: raise RuntimeError(f'{what}: the range {qmin} .. {qmax} fits neither -128 .. 127 nor 0 .. 255')
+    scale, offset = scale.detach().to(torch.float32), offset.detach().to(torch.float32)
+    if not bool((offset == offset.round()).all()): raise RuntimeError(f'{what}: the offset is not an integer: an int8 zero point cannot hold it')
+    per_channel = policy is not None and policy.has_property(QuantizationProperty.PER_CHANNEL)
+    zero_point = None
+    if not per_channel:
+        if scale.numel() != 1 or offset.numel() != 1: raise RuntimeError(f'{what}: a per-tensor config with {scale.numel()} scales')
+        zero_point = int(offset.reshape(-1)[0]) - recentre
+        if not -128 <= zero_point <= 127: raise RuntimeError(f'{what}: the offset {zero_point + recentre} lies outside the range it is stored in')
+    return scale, offset, recentre, zero_point, qmin - recentre, qmax - recentre, rounding_value(config.rounding), (config.channel_axis if per_channel else None)
+
+
+def _to_int_torch(v, scale, offset, qmin, qmax, rounding, nan_code=0):
+    """``LinearQuantize_ToInt`` in torch ops: ``clamp(ppq_tensor_round(v / s) + o, qmin, qmax)`` in float32, truncated; NaN gives ``nan_code``."""
+    t = torch.clamp(ppq_tensor_round(v / scale, rounding) + offset, qmin, qmax)
+    return torch.where(t != t, torch.full_like(t, nan_code), t).to(torch.int32)
+
+
+def _pad_last(values, fill: int):
+    pad = -values.shape[-1] % INT8_BLOCK
+    return torch.nn.functional.pad(values, (0, pad), value=fill) if pad else values
+
+
+def int8_quantize(tensor: torch.Tensor, config, axis: int = -1, weight: bool = False, use_kernels: bool = True) -> Int8Tensor:
+    """The codes of float32 ``tensor`` under ``config`` -- scale, offset, quant_min / quant_max, rounding and, for a per-channel
+    config, channel_axis of a PPQ ``TensorQuantizationConfig`` (anything with those attributes) -- as an ``Int8Tensor`` whose
+    reduction axis is ``axis``.  ``use_kernels=True``: the codes are ``CUDA.LinearQuantize_ToInt``'s (the tensor must be on the GPU);
+    ``False``: the same arithmetic in torch ops, identical bits.  The move of ``axis`` to the end, the padding and the re-centring
+    are torch ops.  ``weight=True``: the B operand of a layer -- symmetric (offset 0), per tensor or per channel along axis 0, with
+    ``sums``; an activation (``weight=False``) is per tensor and may have any zero point.
+    Refused: a range that fits neither -128 .. 127 nor 0 .. 255, a fractional offset, a weight with a non-zero offset, a per-channel
+    activation, a channel axis other than 0."""
+    what = 'int8_quantize'
+    if not isinstance(tensor, torch.Tensor) or tensor.dtype != torch.float32: raise RuntimeError(f'{what}: expected a float32 tensor')
+    if tensor.dim() < 1 or tensor.numel() == 0: raise RuntimeError(f'{what}: empty tensor of shape {list(tensor.shape)}')
+    axis = axis % tensor.dim()
+    scale, offset, recentre, zero_point, qmin, qmax, rounding, channel_axis = _grid(what, config)
+    scale, offset = scale.to(tensor.device), offset.to(tensor.device)
+    if weight:
+        if bool((offset != 0).any()): raise RuntimeError(f'{what}: a weight must be symmetric: its offset is not 0')
+        if channel_axis is not None and (channel_axis % tensor.dim() != 0 or axis == 0 or scale.numel() != tensor.shape[0]):
+            raise RuntimeError(f'{what}: a weight is quantised per tensor or along axis 0 with one scale per row, got axis {channel_axis} and {scale.numel()} scales')
+        if recentre: raise RuntimeError(f'{what}: a weight must be symmetric: its range {qmin + recentre} .. {qmax + recentre} is an unsigned one')
+        zero_point = 0
+    elif channel_axis is not None: raise RuntimeError(f'{what}: an activation must be quantised per tensor')
+    if use_kernels:
+        codes = CUDA.LinearQuantize_ToInt(tensor, scale.reshape(-1), offset.reshape(-1), qmin + recentre, qmax + recentre, rounding, channel_axis,
+                                          torch.uint8 if recentre else torch.int8)
+        if recentre: codes = codes.view(torch.int8) ^ -128                                  # code - 128, on the byte
+    else:
+        shape = [-1] + [1] * (tensor.dim() - 1) if channel_axis is not None else [1] * tensor.dim()
+        codes = (_to_int_torch(tensor, scale.reshape(shape), offset.reshape(shape), qmin + recentre, qmax + recentre, rounding) - recentre).to(torch.int8)
+    values = _pad_last(codes.movedim(axis, -1), zero_point).contiguous()
+    sums = values.sum(dim=tuple(range(1, values.dim())), dtype=torch.int32) if weight else None
+    return Int8Tensor(values, tensor.shape, axis, scale.reshape(-1) if channel_axis is not None else scale.reshape(()), zero_point, qmin, qmax, rounding, sums)
+
+
+def int8_dequantize(t: Int8Tensor) -> torch.Tensor:
+    """The inverse of ``int8_quantize`` on the grid: ``(code - zero_point) * scale`` as float32 of ``t.shape``."""
+    return t.dequantize()
+
+
+def _check_operands(what, x, w, rank, bias):
+    for name, t in (('x', x), ('w', w)):
+        if not isinstance(t, Int8Tensor): raise TypeError(f'{what}: {name}: expected an Int8Tensor, got {type(t)}')
+        if t.values.dtype != torch.int8: raise RuntimeError(f'{what}: {name}: the codes are {t.values.dtype}, not int8')
+    if len(w.shape) != rank or (rank == 4 and len(x.shape) != 4): raise RuntimeError(f'{what}: operands must be {rank}-d, got x {list(x.shape)}, w {list(w.shape)}')
+    if x.axis != (len(x.shape) - 1 if rank == 2 else 1) or w.axis != 1:
+        raise RuntimeError(f'{what}: x {list(x.shape)} / w {list(w.shape)} are packed along axes {x.axis} / {w.axis}, not along the reduction axis')
+    if x.shape[x.axis] != w.shape[1]: raise RuntimeError(f'{what}: K mismatch: x reduces over {x.shape[x.axis]}, w over {w.shape[1]} (groups must be 1)')
+    if x.device != w.device: raise RuntimeError(f'{what}: x is on {x.device}, w on {w.device}')
+    if (w.sums is None and x.zero_point != 0) or w.zero_point != 0: raise RuntimeError(f'{what}: w is not a weight: quantise it with int8_quantize(..., weight=True)')
+    if x.scale.numel() != 1: raise RuntimeError(f'{what}: x must be quantised per tensor')
+    kp = w.values[0].numel()
+    if kp >= MAX_KP: raise RuntimeError(f'{what}: a padded reduction length of {kp}: {MAX_KP} and more could overflow int32')
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32: raise RuntimeError(f'{what}: bias must be a float32 tensor')
+        if list(bias.shape) != [w.shape[0]]: raise RuntimeError(f'{what}: bias of shape {list(bias.shape)}, expected [{w.shape[0]}]')
+
+
+def _check_tail(what, like, shape, residual, out_config, out_float):
+    """The checks of ``residual`` / ``out_config`` / ``out_float``; returns (out_float, the output grid ``(sy, zy, qmin, qmax,
+    rounding, q_nan)`` in the stored domain or None)."""
+    if out_float is None: out_float = out_config is None
+    if out_config is None and not out_float: raise RuntimeError(f'{what}: no output: out_config is None and out_float is False')
+    if residual is not None:
+        if not isinstance(residual, torch.Tensor) or residual.dtype != torch.float32: raise RuntimeError(f'{what}: residual must be a float32 tensor')
+        if list(residual.shape) != list(shape): raise RuntimeError(f'{what}: residual of shape {list(residual.shape)}, expected {list(shape)}')
+        if residual.device != like.device: raise RuntimeError(f'{what}: residual is on {residual.device}, the operands on {like.device}')
+    if out_config is None: return bool(out_float), None
+    scale, _, recentre, zero_point, qmin, qmax, rounding, channel_axis = _grid(what + ': out_config', out_config)
+    if channel_axis is not None: raise RuntimeError(f'{what}: out_config must be per tensor')
+    return bool(out_float), (float(scale.reshape(-1)[0]), zero_point, qmin, qmax, rounding, -recentre)
+
+
+def _mul(x: Int8Tensor, w: Int8Tensor) -> torch.Tensor:
+    """``sx * sw`` as float32 ``[O]``: one float32 multiply per channel, a per-tensor weight scale broadcast."""
+    return (x.scale.reshape(1).to(w.device) * w.scale.reshape(-1).to(w.device)).expand(w.shape[0]).contiguous()
+
+
+def _tail_torch(i, mul, bias, residual, relu, out_q):
+    """The contract's steps 2 .. 6 on the exact integer sums ``i`` (columns last): the float32 result and the padded codes or None."""
+    v = i.to(torch.float32) * mul
+    if bias is not None: v = v + bias
+    if residual is not None: v = v + residual
+    if relu: v = relu_positive_zero(v)
+    if out_q is None: return v, None
+    sy, zy, qmin, qmax, rounding, q_nan = out_q
+    sy = torch.tensor(sy, dtype=torch.float32, device=v.device)                         # a tensor: a Python scalar may be divided by as a reciprocal
+    return v, _pad_last(_to_int_torch(v, sy, float(zy), qmin, qmax, rounding, q_nan).to(torch.int8), zy)
+
+
+def _result(y, q, shape, axis, out_q, out_float, like):
+    if q is None: return y
+    sy, zy, qmin, qmax, rounding, _ = out_q
+    scale = torch.full((), sy, dtype=torch.float32, device=like.device)                 # a fill, not a copy from the host: no synchronisation
+    packed = Int8Tensor(q, shape, axis, scale, zy, qmin, qmax, rounding)
+    return (y, packed) if out_float else packed
+
+
+def int8_matmul(a: Int8Tensor, b: Int8Tensor, bias: torch.Tensor = None, residual: torch.Tensor = None, relu: bool = False, out_config=None,
+                out_float: Optional[bool] = None, use_kernels: bool = True):
+    """``a . b^T`` as a linear INT8 layer (the contract at the top of this module): ``a`` an activation ``[..., K]`` packed along its
+    last axis, ``b`` a weight ``[N, K]`` (``int8_quantize(..., axis=1, weight=True)``), ``bias`` float32 ``[N]``, ``residual`` float32
+    ``[..., N]``.  Returns the float32 ``[..., N]``; with ``out_config`` (a per-tensor config: the next layer's activation) the result
+    as an ``Int8Tensor`` packed along its last axis -- the bits of ``int8_quantize`` on the float32 result --, and with
+    ``out_float=True`` both, ``(tensor, Int8Tensor)``.  ONE launch (``CUDA.Int8Matmul``); ``use_kernels=False``: torch ops, any device."""
+    what = 'int8_matmul'
+    _check_operands(what, a, b, 2, bias)
+    shape = list(a.shape[:-1]) + [b.shape[0]]
+    out_float, out_q = _check_tail(what, a, shape, residual, out_config, out_float)
+    av, mul = a.values.reshape(-1, a.values.shape[-1]), _mul(a, b)
+    res = residual.reshape(-1, shape[-1]) if residual is not None else None
+    if use_kernels: y, q = CUDA.Int8Matmul(av, b.values, b.sums if a.zero_point else None, a.zero_point, mul, bias, res, relu, out_float, out_q)
+    else:
+        i = (av.to(torch.float64) - a.zero_point) @ b.values.to(torch.float64).t()       # every partial sum is an integer below 2^31: exact
+        y, q = _tail_torch(i.to(torch.int64), mul, bias, res, relu, out_q)
+    y = y.reshape(shape) if y is not None and out_float else None
+    return _result(y, q.reshape(shape[:-1] + [-1]) if q is not None else None, shape, len(shape) - 1, out_q, out_float, a)
+
+
+def int8_linear(x: torch.Tensor, weight: Int8Tensor, x_config, bias: torch.Tensor = None, residual: torch.Tensor = None, relu: bool = False,
+                out_config=None, out_float: Optional[bool] = None, use_kernels: bool = True):
+    """A Gemm on an INT8 weight as it runs in deployment: ``int8_quantize(x, x_config, -1)``, then ``int8_matmul``: two launches."""
+    return int8_matmul(int8_quantize(x, x_config, -1, use_kernels=use_kernels), weight, bias, residual, relu, out_config, out_float, use_kernels)
+
+
+def int8_conv2d_packed(x: Int8Tensor, w: Int8Tensor, bias: torch.Tensor = None, stride=1, padding=0, dilation=1, residual: torch.Tensor = None,
+                       relu: bool = False, out_config=None, out_float: Optional[bool] = None, use_kernels: bool = True):
+    """``conv2d(x, w)`` as a linear INT8 layer: ``x`` an activation ``[N, C, H, W]`` and ``w`` a weight ``[O, C, kh, kw]``, both packed
+    along axis 1; ``stride``, ``padding`` (symmetric) and ``dilation`` are ints or (h, w) pairs, groups is 1.  A tap in the padding is a
+    real 0, which is the code ``x.zero_point``.  The float32 result is ``[N, O, OH, OW]`` (channels-last strides from the kernel);
+    ``residual`` (float32, that shape; channels-last is read in place), ``relu``, ``out_config`` and ``out_float`` as in ``int8_matmul``
+    -- the ``Int8Tensor`` is packed along axis 1, what this function takes as ``x``.  ONE launch (``CUDA.Int8Conv2d``), an implicit
+    GEMM; ``use_kernels=False``: torch ops on any device, identical bits."""
+    what = 'int8_conv2d'
+    _check_operands(what, x, w, 4, bias)
+    stride, padding, dilation = _pair(stride, 'stride', 1, what), _pair(padding, 'padding', 0, what), _pair(dilation, 'dilation', 1, what)
+    out = tuple((x.shape[2 + i] + 2 * padding[i] - dilation[i] * (w.shape[2 + i] - 1) - 1) // stride[i] + 1 for i in range(2))
+    if min(out) < 1:
+        raise RuntimeError(f'{what}: a {w.shape[2]} x {w.shape[3]} kernel with dilation {dilation} does not fit an input of '
+                           f'{x.shape[2]} x {x.shape[3]} padded by {padding}')
+    shape = [x.shape[0], w.shape[0], out[0], out[1]]
+    out_float, out_q = _check_tail(what, x, shape, residual, out_config, out_float)
+    mul = _mul(x, w)
+    if use_kernels:
+        y, q = CUDA.Int8Conv2d(x.values, w.values, w.sums if x.zero_point else None, x.zero_point, mul, x.shape[1], bias, stride, padding, dilation,
+                               residual, relu, out_float, out_q)
+    else:
+        xf = torch.nn.functional.pad(x.values.permute(0, 3, 1, 2).to(torch.float64), (padding[1],) * 2 + (padding[0],) * 2, value=x.zero_point)
+        i = torch.nn.functional.conv2d(xf - x.zero_point, w.values.permute(0, 3, 1, 2).to(torch.float64), None, stride, 0, dilation)      # exact: integers below 2^31
+        y, q = _tail_torch(i.permute(0, 2, 3, 1).to(torch.int64), mul, bias, residual.permute(0, 2, 3, 1) if residual is not None else None, relu, out_q)
+        y = y.permute(0, 3, 1, 2)
+    return _result(y if out_float else None, q, shape, 1, out_q, out_float, x)
+
+
+def int8_conv2d(x: torch.Tensor, weight: Int8Tensor, x_config, bias: torch.Tensor = None, stride=1, padding=0, dilation=1, groups: int = 1,
+                residual: torch.Tensor = None, relu: bool = False, out_config=None, out_float: Optional[bool] = None, use_kernels: bool = True):
+    """A convolution on an INT8 weight as it runs in deployment: ``int8_quantize(x, x_config, 1)`` -- ``x`` ``[N, C, H, W]`` --, then
+    ``int8_conv2d_packed``: two launches."""
+    if groups != 1: raise RuntimeError(f'int8_conv2d: groups must be 1, got {groups}')
+    if isinstance(x, torch.Tensor) and x.dim() != 4: raise RuntimeError(f'int8_conv2d: x must be 4-d [N, C, H, W], got shape {list(x.shape)}')
+    return int8_conv2d_packed(int8_quantize(x, x_config, 1, use_kernels=use_kernels), weight, bias, stride, padding, dilation, residual, relu,
+                              out_config, out_float, use_kernels)
