@@ -1012,6 +1012,23 @@ int ppqhip_int8_conv2d(const int8_t* x, const int8_t* w, const int32_t* w_sums, 
                        int q_nan, int64_t n, int64_t c, int64_t h, int64_t wd, int64_t o, int64_t kh, int64_t kw, int64_t stride_h,
                        int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, void* stream);
 
+/* The same two layers with an INT4 weight that stays packed up to the matrix unit (W4A8; ppq_amd/int8.py Int4Weight; DESIGN.md section
+ * 9.23; ADDED under ABI 4).  Every argument but the weight is that of ppqhip_int8_gemm / ppqhip_int8_conv2d, and so is every bit of
+ * the result on the same codes.  The weight's codes lie in -8 .. 7; b is [n, kp / 2] bytes (w: [o, kh, kw, cp / 2], the channels of a
+ * tap packed), two's complement nibbles: of every 8 consecutive k (group g) byte 4 g + j, j = 0 .. 3, holds code 8 g + j in bits
+ * 0 .. 3 and code 8 g + 4 + j in bits 4 .. 7; codes k .. kp - 1 are 0.  b_sums / w_sums are the sums of the TRUE codes.  The kernel
+ * multiplies 16 w (a nibble moved to the top of its byte), starts the accumulators at -16 zx sums[n] and shifts the sum right by 4,
+ * exactly, before step t = float32(I): |16 w| <= 128, so the int32 bound of the int8 layer holds as it stands.
+ * Refused as ppqhip_int8_gemm / ppqhip_int8_conv2d refuse, in the same order, under the names "int4_gemm" / "int4_conv2d"; the span of
+ * the weight checked for overlaps is n * kp / 2 bytes.  Booked under "int4_gemm" / "int4_conv", the weight at half its int8 bytes. */
+int ppqhip_int4_gemm(const int8_t* a, const uint8_t* b, const int32_t* b_sums, int zx, const float* mul, const float* bias,
+                     const float* residual, int relu, float* c, int8_t* q, float sy, int zy, int qmin, int qmax, int rounding, int q_nan,
+                     int64_t m, int64_t n, int64_t k, void* stream);
+int ppqhip_int4_conv2d(const int8_t* x, const uint8_t* w, const int32_t* w_sums, int zx, const float* mul, const float* bias,
+                       const float* residual, int relu, float* y, int8_t* q, float sy, int zy, int qmin, int qmax, int rounding,
+                       int q_nan, int64_t n, int64_t c, int64_t h, int64_t wd, int64_t o, int64_t kh, int64_t kw, int64_t stride_h,
+                       int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, void* stream);
+
 /* ---- pointwise (1x1) convolution on the FP32-input MFMA (ADDED under ABI 4) ---------------------------------
  * y[n, o, oh, ow] = sum_k w[o, k] x[n, k, oh * stride, ow * stride] (+ bias[o]) for contiguous NCHW float32 x [n, c, h, wd],
  * w [o, c] (a [o, c, 1, 1] convolution weight as it lies) and y [n, o, ho, wo], ho = (h - 1) / stride + 1, wo likewise; no padding,

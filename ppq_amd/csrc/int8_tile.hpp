@@ -1,5 +1,8 @@
-// int8_tile.hpp -- what the two linear INT8 kernels on the int8 MFMA of gfx950 (v_mfma_i32_16x16x32_i8) share: int8_gemm.hip and
-// int8_conv.hip.  The contract is DESIGN.md section 9.22 and tests/int8_reference.py.
+// int8_tile.hpp -- what the linear INT8 kernels on the int8 MFMA of gfx950 (v_mfma_i32_16x16x32_i8) share: the GEMM (int8_gemm.hpp)
+// and the convolution (int8_conv.hpp), each with an int8 weight (int8_gemm.hip, int8_conv.hip) or a packed int4 one (int4_gemm.hip,
+// int4_conv.hip).  The contract is DESIGN.md sections 9.22 / 9.23 and tests/int8_reference.py.  The frame is generic over the B
+// operand alone -- how a weight is staged and how a lane reads its fragment (the codecs Q8B8 / Q8B4 below); what follows describes it
+// with int8 weights.
 //
 // Linear INT8 has ONE scale per tensor or channel, so -- unlike the MXINT8 kernels of mx_int8_tile.hpp, which start every MFMA from a
 // zero accumulator and pay a conversion, an ldexp and a float add per output and block of 32 -- the int32 accumulator stays in the
@@ -44,14 +47,15 @@ constexpr uint32_t kQ8Block = 32;                                               
 constexpr uint32_t kQ8ChunkBlocks = 4;                                           // instructions of one row per chunk
 constexpr uint32_t kQ8Pitch = kQ8ChunkBlocks * kQ8Block + 16u;                   // 144: a staged row of 128 bytes, padded
 constexpr uint32_t kQ8TileBytes = kQ8Edge * kQ8Pitch;                            // 64 rows of one operand
-constexpr uint32_t kQ8BufBytes = 2u * kQ8TileBytes;                              // A, B
+constexpr uint32_t kQ4BlockBytes = kQ8Block / 2u;                                // an int4 B row: 16 bytes per block of 32 k
+constexpr uint32_t kQ4Pitch = kQ8ChunkBlocks * kQ4BlockBytes + 16u;              // 80: a staged int4 row of 64 bytes, padded
 constexpr uint32_t kQ8CodeBytes = (kQ8WaveTiles * kQ8Tile) * (kQ8WaveTiles * kQ8Tile);       // a wave's 32 rows of 32 codes
 constexpr int64_t kQ8MaxK = 65536;                                               // padded reduction lengths from here on are refused
 constexpr int64_t kQ8Max = 0x7fffffffLL;
 static_assert(kQ8Waves * kQ8Waves * kWave == kBlock, "four waves per workgroup");
-static_assert(kQ8Pitch % 16u == 0, "16-byte stores into the stage");
-static_assert(kQ8Edge * kQ8ChunkBlocks * kQ8Block == 2u * 16u * (uint32_t)kBlock, "two 16-byte loads per thread and operand");
-static_assert(kQ8Waves * kQ8Waves * kQ8CodeBytes <= kQ8BufBytes, "the four waves' code stages fit the first operand buffer");
+static_assert(kQ8Pitch % 16u == 0 && kQ4Pitch % 16u == 0, "16-byte stores into the stage");
+static_assert(kQ8Edge * kQ8ChunkBlocks * kQ8Block == 2u * 16u * (uint32_t)kBlock, "two 16-byte loads per thread and int8 operand");
+static_assert(kQ8Edge * kQ8ChunkBlocks * kQ4BlockBytes == 16u * (uint32_t)kBlock, "one 16-byte load per thread of an int4 B");
 static_assert(kQ8WaveTiles * kQ8Tile == (int)kQ8Block, "a wave's columns are one 32-byte group of a code row");
 
 // What both kernels take beyond their operands: the column data, the tail and the outputs of an [m, n] result.
@@ -72,24 +76,102 @@ struct Int8Tail {
 
 #if defined(__HIPCC__)
 
-// what a thread carries from global memory to LDS for one chunk: 2 x 16 bytes of each operand
-struct Q8Staged {
-    v4u a0, a1, b0, b1;                           // the thread's segment t & 7 of rows t >> 3 and 32 + (t >> 3) of A and of B
+// ---- the B operand: how a weight lies in global memory, how a chunk of it is staged and how a lane reads its fragment ---------------
+// A codec B has: kBlockBytes, the bytes of a row per block of 32 k; kPitch, the pitch of a staged row; kShift, log2 of what its
+// fragments are scaled by (the accumulators then hold I << kShift); kMinBlocks, the workgroups per CU its kernels are bounded to;
+// Regs, what a thread carries of a chunk; Map, where a thread's share lies -- Map(b, nb, n, col0, t) for the rows col0 .. col0 + 63 (clamped to n - 1) of b [n, nb * kBlockBytes], load<TAIL>(kb0, regs)
+// as in q8_k_loop, store(stage, regs) into the B stage --; frag(row, b, grp): the 8 bytes 8 grp .. + 7 of block b of a staged row.
+
+// int8 codes as they are: segment t & 7 (16 bytes; block (t & 7) >> 1 of the chunk) of rows t >> 3 and 32 + (t >> 3)
+struct Q8B8 {
+    static constexpr uint32_t kBlockBytes = kQ8Block, kPitch = kQ8Pitch;
+    static constexpr int kShift = 0, kMinBlocks = 1;
+    struct Regs { v4u b0, b1; };
+    struct Map {
+        const uint8_t* gb[2]; uint32_t seg, lds_e[2], nb;
+        __device__ __forceinline__ Map(const uint8_t* b, uint32_t nblocks, uint32_t n, uint32_t col0, uint32_t t) {
+            nb = nblocks; seg = t & 7u;
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const uint32_t row = (t >> 3) + 32u * h;
+                gb[h] = b + min(col0 + row, n - 1u) * ((size_t)nb * kBlockBytes);
+                lds_e[h] = row * kPitch + seg * 16u;
+            }
+        }
+        template <bool TAIL>
+        __device__ __forceinline__ void load(uint32_t kb0, Regs& st) const {
+            const uint32_t eb = kb0 + (seg >> 1);
+            const size_t off = (size_t)(TAIL ? min(eb, nb - 1u) : eb) * kBlockBytes + 16u * (seg & 1u);
+            st.b0 = *reinterpret_cast<const v4u*>(gb[0] + off); st.b1 = *reinterpret_cast<const v4u*>(gb[1] + off);
+        }
+        __device__ __forceinline__ void store(uint8_t* stage, const Regs& st) const {
+            *reinterpret_cast<v4u*>(stage + lds_e[0]) = st.b0; *reinterpret_cast<v4u*>(stage + lds_e[1]) = st.b1;
+        }
+    };
+    static __device__ __forceinline__ long frag(const uint8_t* row, uint32_t b, uint32_t grp) {
+        return *reinterpret_cast<const long*>(row + b * kBlockBytes + grp * 8u);
+    }
 };
 
-__device__ __forceinline__ void q8_store_staged(uint8_t* buf, const uint32_t (&lds_e)[2], const Q8Staged& st) {
+// int4 codes, two per byte: of every 8 consecutive k (group g) byte 4 g + j holds code 8 g + j in bits 0 .. 3
+// and code 8 g + 4 + j in bits 4 .. 7, two's complement.  A chunk of 64 rows is 4096 bytes: ONE 16-byte load per thread, block t & 3 of
+// row t >> 2.  A lane's fragment is one dword p, the one of group 4 b + grp: a nibble moved to the top of its byte is the int8 value
+// 16 w, sign included, so {(p << 4) & 0xf0f0f0f0, p & 0xf0f0f0f0} are the bytes 8 grp .. + 7 of the block, times 16, in A's byte order:
+// three VALU operations, no sign extension, no permutation of A.  The accumulators hold 16 I; |16 w| <= 128 is the bound of Q8B8.
+// Pitch 80 bytes = 20 dwords: 20 r mod 64, r = 0 .. 15, are the 16 multiples of 4 below 64, each once, so the dwords 20 r + 4 b + grp of
+// the 64 lanes of a fragment read lie in 64 different banks; 80 keeps the 16-byte stores aligned.
+struct Q8B4 {
+    static constexpr uint32_t kBlockBytes = kQ4BlockBytes, kPitch = kQ4Pitch;
+    static constexpr int kShift = 4, kMinBlocks = 4;          // without the bound the allocator takes 132 registers: 3 workgroups a CU, not Q8B8's 4
+    struct Regs { v4u b; };
+    struct Map {
+        const uint8_t* gb; uint32_t seg, lds_e, nb;
+        __device__ __forceinline__ Map(const uint8_t* b, uint32_t nblocks, uint32_t n, uint32_t col0, uint32_t t) {
+            nb = nblocks; seg = t & 3u;
+            gb = b + min(col0 + (t >> 2), n - 1u) * ((size_t)nb * kBlockBytes);
+            lds_e = (t >> 2) * kPitch + seg * 16u;
+        }
+        template <bool TAIL>
+        __device__ __forceinline__ void load(uint32_t kb0, Regs& st) const {
+            const uint32_t eb = kb0 + seg;
+            st.b = *reinterpret_cast<const v4u*>(gb + (size_t)(TAIL ? min(eb, nb - 1u) : eb) * kBlockBytes);
+        }
+        __device__ __forceinline__ void store(uint8_t* stage, const Regs& st) const { *reinterpret_cast<v4u*>(stage + lds_e) = st.b; }
+    };
+    static __device__ __forceinline__ long frag(const uint8_t* row, uint32_t b, uint32_t grp) {
+        const uint32_t p = *reinterpret_cast<const uint32_t*>(row + b * kBlockBytes + grp * 4u);
+        const uint32_t lo = (p << 4) & 0xf0f0f0f0u, hi = p & 0xf0f0f0f0u;
+        return (long)(((uint64_t)hi << 32) | lo);
+    }
+};
+
+// one buffer of the double-buffered stage: 64 rows of A at pitch 144, then 64 rows of B at the codec's pitch
+template <typename B> constexpr uint32_t kQ8BufBytes = kQ8TileBytes + kQ8Edge * B::kPitch;
+static_assert(kQ8Waves * kQ8Waves * kQ8CodeBytes <= kQ8BufBytes<Q8B8> && kQ8Waves * kQ8Waves * kQ8CodeBytes <= kQ8BufBytes<Q8B4>,
+              "the four waves' code stages fit the first operand buffer");
+
+// what a thread carries from global memory to LDS for one chunk: of A its segment t & 7 (16 bytes) of rows t >> 3 and 32 + (t >> 3)
+template <typename B>
+struct Q8Staged {
+    v4u a0, a1;
+    typename B::Regs b;
+};
+
+// A into its stage at the thread's two places, B through its map
+template <typename B>
+__device__ __forceinline__ void q8_store_staged(uint8_t* buf, const uint32_t (&lds_e)[2], const typename B::Map& bmap, const Q8Staged<B>& st) {
     *reinterpret_cast<v4u*>(buf + lds_e[0]) = st.a0; *reinterpret_cast<v4u*>(buf + lds_e[1]) = st.a1;
-    *reinterpret_cast<v4u*>(buf + kQ8TileBytes + lds_e[0]) = st.b0; *reinterpret_cast<v4u*>(buf + kQ8TileBytes + lds_e[1]) = st.b1;
+    bmap.store(buf + kQ8TileBytes, st.b);
 }
 
-// The wave's 2 x 2 tiles over the `live` (1 .. 4; 4 unless TAIL) blocks of the chunk staged in buf: per block four 8-byte LDS
-// reads and four MFMAs, each chained through its accumulator.
-template <bool TAIL>
+// The wave's 2 x 2 tiles over the `live` (1 .. 4; 4 unless TAIL) blocks of the chunk staged in buf: per block four fragment reads
+// from LDS (8 bytes of A, B as its codec reads it) and four MFMAs, each chained through its accumulator.
+template <bool TAIL, typename B>
 __device__ __forceinline__ void q8_chunk(const uint8_t* buf, uint32_t wm, uint32_t wn, uint32_t r, uint32_t grp, uint32_t live,
                                          v4i (&acc)[kQ8WaveTiles][kQ8WaveTiles]) {
     constexpr int T = kQ8WaveTiles;
     const uint8_t* la = buf + (wm + r) * kQ8Pitch + grp * 8u;
-    const uint8_t* lb = buf + kQ8TileBytes + (wn + r) * kQ8Pitch + grp * 8u;
+    const uint8_t* lb = buf + kQ8TileBytes + (wn + r) * B::kPitch;
 #pragma unroll
     for (uint32_t b = 0; b < kQ8ChunkBlocks; b++) {
         if (TAIL && b >= live) break;                                            // wave-uniform
@@ -97,7 +179,7 @@ __device__ __forceinline__ void q8_chunk(const uint8_t* buf, uint32_t wm, uint32
 #pragma unroll
         for (int i = 0; i < T; i++) {
             a[i] = *reinterpret_cast<const long*>(la + i * kQ8Tile * kQ8Pitch + b * kQ8Block);
-            bb[i] = *reinterpret_cast<const long*>(lb + i * kQ8Tile * kQ8Pitch + b * kQ8Block);
+            bb[i] = B::frag(lb + i * kQ8Tile * B::kPitch, b, grp);
         }
 #pragma unroll
         for (int i = 0; i < T; i++)
@@ -109,11 +191,11 @@ __device__ __forceinline__ void q8_chunk(const uint8_t* buf, uint32_t wm, uint32
 // The K loop of both kernels over nb >= 1 blocks of 32 bytes.  A Map knows where a thread's share of a chunk lies: load<TAIL>(kb0, st)
 // issues the global loads of the chunk that starts at block kb0 (TAIL: the chunk holds fewer than 4 live blocks; a dead one is not
 // multiplied and its address is clamped), store(buf, st) puts them into the stage.  A wave past the edge (!busy) only stages.
-template <typename Map>
-__device__ __forceinline__ void q8_k_loop(const Map& map, uint8_t (&stage)[2][kQ8BufBytes], uint32_t nb, bool busy, uint32_t wm, uint32_t wn,
+template <typename B, typename Map>
+__device__ __forceinline__ void q8_k_loop(const Map& map, uint8_t (&stage)[2][kQ8BufBytes<B>], uint32_t nb, bool busy, uint32_t wm, uint32_t wn,
                                           uint32_t r, uint32_t grp, v4i (&acc)[kQ8WaveTiles][kQ8WaveTiles]) {
     const uint32_t chunks = (nb + kQ8ChunkBlocks - 1u) / kQ8ChunkBlocks, rest = nb % kQ8ChunkBlocks;
-    Q8Staged st;
+    Q8Staged<B> st;
     if (chunks == 1u && rest) map.template load<true>(0u, st); else map.template load<false>(0u, st);
     map.store(stage[0], st);
     __syncthreads();
@@ -123,20 +205,22 @@ __device__ __forceinline__ void q8_k_loop(const Map& map, uint8_t (&stage)[2][kQ
             if (last_short) map.template load<true>((c + 1u) * kQ8ChunkBlocks, st); else map.template load<false>((c + 1u) * kQ8ChunkBlocks, st);
         }
         if (busy) {
-            if (!more && rest) q8_chunk<true>(stage[c & 1u], wm, wn, r, grp, rest, acc);
-            else q8_chunk<false>(stage[c & 1u], wm, wn, r, grp, kQ8ChunkBlocks, acc);
+            if (!more && rest) q8_chunk<true, B>(stage[c & 1u], wm, wn, r, grp, rest, acc);
+            else q8_chunk<false, B>(stage[c & 1u], wm, wn, r, grp, kQ8ChunkBlocks, acc);
         }
         if (more) map.store(stage[(c + 1u) & 1u], st);                           // last read before the barrier that ended chunk c - 1
         __syncthreads();
     }
 }
 
-// the accumulators of the wave's columns n0 + 16 j + r before the first MFMA: -zx * sums[column], 0 without sums
+// the accumulators of the wave's columns n0 + 16 j + r before the first MFMA: -zx * sums[column] in the scale of the codec's
+// fragments (SHIFT), 0 without sums
+template <int SHIFT>
 __device__ __forceinline__ void q8_start(const Int8Tail& e, uint32_t n0, uint32_t r, v4i (&acc)[kQ8WaveTiles][kQ8WaveTiles]) {
 #pragma unroll
     for (int j = 0; j < kQ8WaveTiles; j++) {
         const uint32_t col = min(n0 + j * kQ8Tile + r, e.n - 1u);
-        const int s = e.sums != nullptr ? (int)(0u - (uint32_t)e.zx * (uint32_t)e.sums[col]) : 0;
+        const int s = e.sums != nullptr ? (int)((0u - (uint32_t)e.zx * (uint32_t)e.sums[col]) << SHIFT) : 0;
 #pragma unroll
         for (int i = 0; i < kQ8WaveTiles; i++) acc[i][j] = v4i{s, s, s, s};
     }
@@ -192,9 +276,10 @@ __device__ __forceinline__ void q8_epilogue(const v4i (&acc)[kQ8WaveTiles][kQ8Wa
     if (row < e.m) *reinterpret_cast<v4u*>(e.q + (size_t)row * e.op + n0 + half * 16u) = w;      // n0 + 32 <= op: n0 < n and n0 % 32 == 0
 }
 
-// what a kernel does around its Map: the wave's place, the accumulators, the K loop, the final barrier and the epilogue
-template <typename MakeMap>
-__device__ __forceinline__ void q8_tile(const Int8Tail& e, uint32_t nb, uint8_t (&stage)[2][kQ8BufBytes], MakeMap&& make_map) {
+// what a kernel does around its Map: the wave's place, the accumulators, the K loop, the final barrier and the epilogue.  Where the
+// codec's fragments are scaled the accumulators end as I << kShift, a multiple of 2^kShift: the arithmetic shift back is exact.
+template <typename B, typename MakeMap>
+__device__ __forceinline__ void q8_tile(const Int8Tail& e, uint32_t nb, uint8_t (&stage)[2][kQ8BufBytes<B>], MakeMap&& make_map) {
     constexpr int T = kQ8WaveTiles;
     const uint32_t tm = fdiv(blockIdx.x, e.tiles_n), tn = blockIdx.x - tm * e.tiles_n.d;
     const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
@@ -204,13 +289,19 @@ __device__ __forceinline__ void q8_tile(const Int8Tail& e, uint32_t nb, uint8_t 
     const bool busy = row0 + wm < e.m && col0 + wn < e.n;                        // wave-uniform: a wave past the edge only stages
 
     v4i acc[T][T];
-    q8_start(e, col0 + wn, r, acc);
+    q8_start<B::kShift>(e, col0 + wn, r, acc);
     if (nb > 0u) {                                                               // nb == 0: the operands may be null
         const auto map = make_map(row0, col0, t);
-        q8_k_loop(map, stage, nb, busy, wm, wn, r, grp, acc);
+        q8_k_loop<B>(map, stage, nb, busy, wm, wn, r, grp, acc);
     }
     __syncthreads();
     if (!busy) return;
+    if (B::kShift) {
+#pragma unroll
+        for (int i = 0; i < T; i++)
+#pragma unroll
+            for (int j = 0; j < T; j++) acc[i][j] = acc[i][j] >> B::kShift;
+    }
     q8_epilogue(acc, e, row0 + wm, col0 + wn, lane, &stage[0][0] + wave * kQ8CodeBytes);
 }
 

@@ -483,6 +483,20 @@ class CUDA:
         return _int8_conv2d(x, w, w_sums, zx, mul, c, bias, stride, padding, dilation, residual, relu, out_float, out_q)
 
     @ staticmethod
+    def Int4Matmul(a, b, b_sums, zx: int, mul, bias=None, residual=None, relu: bool = False, out_float: bool = True, out_q=None):
+        """``Int8Matmul`` with an INT4 weight that stays packed up to the matrix unit: ``a [M, Kp]`` int8,
+        ``b [N, Kp / 2]`` uint8 -- codes in -8 .. 7, two per byte in the layout of ``int4_pack`` --, ``b_sums`` the sums of the codes.
+        The bits of ``Int8Matmul`` on the unpacked codes."""
+        return _int8_matmul(a, b, b_sums, zx, mul, bias, residual, relu, out_float, out_q, int4=True)
+
+    @ staticmethod
+    def Int4Conv2d(x, w, w_sums, zx: int, mul, c: int, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), residual=None,
+                   relu: bool = False, out_float: bool = True, out_q=None):
+        """``Int8Conv2d`` with an INT4 weight: ``x [N, H, W, Cp]`` int8, ``w [O, kh, kw, Cp / 2]`` uint8, the channels of a tap packed
+        as ``Int4Matmul`` takes a row.  The bits of ``Int8Conv2d`` on the unpacked codes."""
+        return _int8_conv2d(x, w, w_sums, zx, mul, c, bias, stride, padding, dilation, residual, relu, out_float, out_q, int4=True)
+
+    @ staticmethod
     def Sync():
         """Synchronize device (ffi.py:347-350)."""
         torch.cuda.synchronize()

@@ -1,5 +1,7 @@
-"""The bindings of the linear INT8 kernels (``csrc/int8_gemm.hip``, ``csrc/int8_conv.hip``): ``CUDA.Int8Matmul``
-and ``CUDA.Int8Conv2d`` forward here.  Operands are int8 codes with the reduction axis last and padded to a multiple of 32."""
+"""The bindings of the linear INT8 kernels (``csrc/int8_gemm.hip``, ``csrc/int8_conv.hip``) and of their forms
+with a packed INT4 weight (``csrc/int4_gemm.hip``, ``csrc/int4_conv.hip``; section 9.23): ``CUDA.Int8Matmul`` / ``Int8Conv2d`` /
+``Int4Matmul`` / ``Int4Conv2d`` forward here.  Operands are int8 codes with the reduction axis last and padded to a multiple of 32; an
+INT4 weight is uint8, two codes per byte, half as many bytes along that axis."""
 import torch
 
 from .._lib import lib
@@ -11,18 +13,20 @@ INT8_BLOCK = 32          # the K of one v_mfma_i32_16x16x32_i8: rows are padded 
 def _refuse(what: str): raise RuntimeError(_KERNEL_FAILURE + what)
 
 
-def _int8_operands(rank, names, operands):
-    """int8, on one GPU, ``rank``-d, contiguous, the last axis a multiple of 32 and the same for both; a tensor whose data does not
-    start on a 16-byte boundary is copied (the allocator aligns)."""
+def _int8_operands(rank, names, operands, int4=False):
+    """int8 -- with ``int4`` the second one uint8, two codes per byte --, on one GPU, ``rank``-d, contiguous, the last axis a multiple
+    of 32 codes and the same for both; a tensor whose data does not start on a 16-byte boundary is copied (the allocator aligns)."""
     dev, out = operands[0].device if isinstance(operands[0], torch.Tensor) else None, []
-    for name, t in zip(names, operands):
-        _check(t, torch.int8, f'{name}(Expect to be INT8)')
+    for name, t, per_byte in zip(names, operands, (1, 2 if int4 else 1)):
+        if per_byte == 2: _check(t, torch.uint8, f'{name}(Expect to be UINT8: packed INT4)')
+        else: _check(t, torch.int8, f'{name}(Expect to be INT8)')
         if t.dim() != rank: _refuse(f'{name} must be {rank}-d, got {list(t.shape)}')
         if t.device != dev: _refuse(f'{name} is on another device')
         if not t.is_contiguous(): _refuse(f'{name} must be contiguous')
-        if t.shape[-1] % INT8_BLOCK: _refuse(f'{name}: the last axis ({t.shape[-1]}) must be padded to a multiple of {INT8_BLOCK}')
+        if t.shape[-1] * per_byte % INT8_BLOCK: _refuse(f'{name}: the last axis ({t.shape[-1] * per_byte} codes) must be padded to a multiple of {INT8_BLOCK}')
         out.append(t.clone() if t.data_ptr() % 16 else t)
-    if out[0].shape[-1] != out[1].shape[-1]: _refuse(f'{names[0]} and {names[1]} differ in their last axis: {out[0].shape[-1]} and {out[1].shape[-1]}')
+    if out[0].shape[-1] != out[1].shape[-1] * (2 if int4 else 1):
+        _refuse(f'{names[0]} and {names[1]} differ in their last axis: {out[0].shape[-1]} and {out[1].shape[-1] * (2 if int4 else 1)}' + (' codes' if int4 else ''))
     return out
 
 
@@ -56,25 +60,28 @@ def _int8_tail(n, shape, dev, sums, zx, mul, bias, residual, out_float, out_q):
     return sums, zx, mul.contiguous(), (bias.contiguous() if bias is not None else None), residual, c, q, grid
 
 
-def int8_matmul(a, b, b_sums, zx: int, mul, bias=None, residual=None, relu: bool = False, out_float: bool = True, out_q=None):
+def int8_matmul(a, b, b_sums, zx: int, mul, bias=None, residual=None, relu: bool = False, out_float: bool = True, out_q=None, int4: bool = False):
     """``ppqhip_int8_gemm``: ``a [M, Kp]`` and ``b [N, Kp]`` int8 codes, ``b_sums [N]`` int32 (None with ``zx == 0``), ``mul [N]``
     float32.  ``out_q``: None or ``(sy, zy, qmin, qmax, rounding, q_nan)`` in the stored int8 domain.  Returns ``(c, q)``: float32
-    ``[M, N]`` (None with ``out_float=False``) and int8 ``[M, ceil32(N)]`` (None without ``out_q``)."""
-    a, b = _int8_operands(2, ('A', 'B'), (a, b))
+    ``[M, N]`` (None with ``out_float=False``) and int8 ``[M, ceil32(N)]`` (None without ``out_q``).
+    ``int4``: ``ppqhip_int4_gemm``, ``b [N, Kp / 2]`` uint8, the packed INT4 codes."""
+    a, b = _int8_operands(2, ('A', 'B'), (a, b), int4)
     m, n = a.shape[0], b.shape[0]
     sums, zx, mul, bias, residual, c, q, grid = _int8_tail(n, [m, n], a.device, b_sums, zx, mul, bias, residual, out_float, out_q)
+    gemm = lib.ppqhip_int4_gemm if int4 else lib.ppqhip_int8_gemm
     with _DeviceOf(a):
-        _raise(lib.ppqhip_int8_gemm(a.data_ptr(), b.data_ptr(), _ptr(sums), zx, mul.data_ptr(), _ptr(bias), _ptr(residual), 1 if relu else 0,
-                                    _ptr(c), _ptr(q), *grid, m, n, a.shape[1], _stream()))
+        _raise(gemm(a.data_ptr(), b.data_ptr(), _ptr(sums), zx, mul.data_ptr(), _ptr(bias), _ptr(residual), 1 if relu else 0, _ptr(c), _ptr(q), *grid,
+                    m, n, a.shape[1], _stream()))
     return c, q
 
 
 def int8_conv2d(x, w, w_sums, zx: int, mul, c: int, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), residual=None,
-                relu: bool = False, out_float: bool = True, out_q=None):
+                relu: bool = False, out_float: bool = True, out_q=None, int4: bool = False):
     """``ppqhip_int8_conv2d``: ``x [N, H, W, Cp]`` and ``w [O, kh, kw, Cp]`` int8 codes of a convolution with ``c`` channels.
     ``residual`` is ``[N, O, OH, OW]``; a tensor that is not channels-last is copied into that layout.  Returns ``(y, q)``: float32
-    ``[N, O, OH, OW]`` with channels-last strides and int8 ``[N, OH, OW, ceil32(O)]``."""
-    x, w = _int8_operands(4, ('x', 'w'), (x, w))
+    ``[N, O, OH, OW]`` with channels-last strides and int8 ``[N, OH, OW, ceil32(O)]``.
+    ``int4``: ``ppqhip_int4_conv2d``, ``w [O, kh, kw, Cp / 2]`` uint8, the packed INT4 codes."""
+    x, w = _int8_operands(4, ('x', 'w'), (x, w), int4)
     c = int(c)
     if not 0 < c <= x.shape[-1] or x.shape[-1] - c >= INT8_BLOCK: _refuse(f'c = {c} does not pad to the {x.shape[-1]} stored channels')
     (n, h, wd, _), (o, kh, kw, _) = x.shape, w.shape
@@ -84,7 +91,8 @@ def int8_conv2d(x, w, w_sums, zx: int, mul, c: int, bias=None, stride=(1, 1), pa
     if oh < 1 or ow < 1: _refuse(f'a {kh} x {kw} kernel with dilation {(dh, dw)} does not fit an input of {h} x {wd} padded by {(ph, pw)}')
     if residual is not None and isinstance(residual, torch.Tensor) and residual.dim() == 4: residual = residual.permute(0, 2, 3, 1)
     sums, zx, mul, bias, residual, y, q, grid = _int8_tail(o, [n, oh, ow, o], x.device, w_sums, zx, mul, bias, residual, out_float, out_q)
+    conv = lib.ppqhip_int4_conv2d if int4 else lib.ppqhip_int8_conv2d
     with _DeviceOf(x):
-        _raise(lib.ppqhip_int8_conv2d(x.data_ptr(), w.data_ptr(), _ptr(sums), zx, mul.data_ptr(), _ptr(bias), _ptr(residual), 1 if relu else 0,
-                                      _ptr(y), _ptr(q), *grid, n, c, h, wd, o, kh, kw, sh, sw, ph, pw, dh, dw, _stream()))
+        _raise(conv(x.data_ptr(), w.data_ptr(), _ptr(sums), zx, mul.data_ptr(), _ptr(bias), _ptr(residual), 1 if relu else 0, _ptr(y), _ptr(q), *grid,
+                    n, c, h, wd, o, kh, kw, sh, sw, ph, pw, dh, dw, _stream()))
     return (y.permute(0, 3, 1, 2) if y is not None else None), q

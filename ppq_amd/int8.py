@@ -10,6 +10,10 @@ int32 accumulator chained over all of K (``csrc/int8_gemm.hip``, ``csrc/int8_con
 
 ``use_kernels=False`` states the same contract in torch ops on any device, with identical bits (``tests/int8_reference.py`` is the NumPy
 oracle of both).  Codes are stored as int8: a config whose range lies in 0 .. 255 is stored re-centred, code - 128 and zero point - 128.
+
+A weight may also be INT4 (section 9.23): an ``Int4Weight`` holds codes in -8 .. 7 two per byte, and every layer function takes it where
+it takes a weight.  The layer then has the bits of the int8 layer on the same codes, from ONE launch of ``csrc/int4_gemm.hip`` /
+``csrc/int4_conv.hip``, which read half the weight bytes and unpack a nibble on its way from LDS to the MFMA.
 """
 from typing import Optional
 
@@ -20,7 +24,8 @@ from .ffi import CUDA, INT8_BLOCK
 from .mx import _pair, relu_positive_zero
 from .round import ppq_tensor_round
 
-__all__ = ['Int8Tensor', 'int8_quantize', 'int8_dequantize', 'int8_matmul', 'int8_linear', 'int8_conv2d_packed', 'int8_conv2d']
+__all__ = ['Int8Tensor', 'Int4Weight', 'int8_quantize', 'int8_dequantize', 'int4_quantize_weight', 'int4_pack', 'int4_unpack', 'int8_matmul', 'int8_linear',
+           'int8_conv2d_packed', 'int8_conv2d']
 
 MAX_KP = 65536           # padded reduction lengths from here on are refused: |I| could leave int32
 
@@ -44,6 +49,27 @@ class Int8Tensor:
         codes = self.values[..., :self.shape[self.axis]].movedim(-1, self.axis).to(torch.float32)
         scale = self.scale.reshape([-1] + [1] * (len(self.shape) - 1)) if self.scale.numel() > 1 else self.scale
         return (codes - float(self.zero_point)) * scale
+
+
+class Int4Weight:
+    """INT4 codes (-8 .. 7) of a symmetric weight of ``shape``, packed for the int4 kernels.  ``values``: uint8, the reduction axis
+    ``axis`` moved last, padded with code 0 to a multiple of 32 codes and packed two per byte: of every 8 consecutive codes (group
+    ``g``) byte ``4 g + j``, ``j`` = 0 .. 3, holds code ``8 g + j`` in bits 0 .. 3 and code ``8 g + 4 + j`` in bits 4 .. 7, two's
+    complement -- so that one dword is a lane's MFMA fragment.  ``scale``, ``qmin``, ``qmax``, ``rounding``
+    as in ``Int8Tensor``; ``sums``: int32 ``[shape[0]]``, the sums of the codes; ``zero_point`` is 0."""
+    __slots__ = ('values', 'shape', 'axis', 'scale', 'qmin', 'qmax', 'rounding', 'sums')
+    zero_point = 0
+
+    def __init__(self, values, shape, axis, scale, qmin, qmax, rounding, sums):
+        self.values, self.shape, self.axis = values, tuple(int(d) for d in shape), int(axis)
+        self.scale, self.qmin, self.qmax, self.rounding, self.sums = scale, int(qmin), int(qmax), int(rounding), sums
+
+    @ property
+    def device(self): return self.values.device
+
+    def dequantize(self) -> torch.Tensor:
+        """``code * scale`` in float32, in the tensor's own layout."""
+        return int4_unpack(self).dequantize()
 
 
 def _grid(what: str, config):
@@ -80,7 +106,7 @@ def _pad_last(values, fill: int):
     return torch.nn.functional.pad(values, (0, pad), value=fill) if pad else values
 
 
-def int8_quantize(tensor: torch.Tensor, config, axis: int = -1, weight: bool = False, use_kernels: bool = True) -> Int8Tensor:
+def int8_quantize(tensor: torch.Tensor, config, axis: int = -1, weight: bool = False, use_kernels: bool = True, what: str = 'int8_quantize') -> Int8Tensor:
     """The codes of float32 ``tensor`` under ``config`` -- scale, offset, quant_min / quant_max, rounding and, for a per-channel
     config, channel_axis of a PPQ ``TensorQuantizationConfig`` (anything with those attributes) -- as an ``Int8Tensor`` whose
     reduction axis is ``axis``.  ``use_kernels=True``: the codes are ``CUDA.LinearQuantize_ToInt``'s (the tensor must be on the GPU);
@@ -88,8 +114,7 @@ def int8_quantize(tensor: torch.Tensor, config, axis: int = -1, weight: bool = F
     are torch ops.  ``weight=True``: the B operand of a layer -- symmetric (offset 0), per tensor or per channel along axis 0, with
     ``sums``; an activation (``weight=False``) is per tensor and may have any zero point.
     Refused: a range that fits neither -128 .. 127 nor 0 .. 255, a fractional offset, a weight with a non-zero offset, a per-channel
-    activation, a channel axis other than 0."""
-    what = 'int8_quantize'
+    activation, a channel axis other than 0 -- under the name ``what``."""
     if not isinstance(tensor, torch.Tensor) or tensor.dtype != torch.float32: raise RuntimeError(f'{what}: expected a float32 tensor')
     if tensor.dim() < 1 or tensor.numel() == 0: raise RuntimeError(f'{what}: empty tensor of shape {list(tensor.shape)}')
     axis = axis % tensor.dim()
@@ -119,10 +144,43 @@ def int8_dequantize(t: Int8Tensor) -> torch.Tensor:
     return t.dequantize()
 
 
+def int4_pack(w: Int8Tensor) -> Int4Weight:
+    """The weight ``w`` -- ``int8_quantize(..., weight=True)`` or codes that already exist -- as an ``Int4Weight``: torch ops, done
+    once.  Refused: anything but a symmetric ``Int8Tensor``, a code outside -8 .. 7."""
+    what = 'int4_pack'
+    if not isinstance(w, Int8Tensor) or w.values.dtype != torch.int8: raise TypeError(f'{what}: expected an Int8Tensor of int8 codes, got {type(w)}')
+    if w.zero_point != 0: raise RuntimeError(f'{what}: a weight must be symmetric: its zero point is {w.zero_point}')
+    v = _pad_last(w.values, 0).to(torch.int32)
+    if v.numel() and (int(v.min()) < -8 or int(v.max()) > 7): raise RuntimeError(f'{what}: the codes reach {int(v.min())} .. {int(v.max())}: outside -8 .. 7')
+    v = v.reshape(list(v.shape[:-1]) + [-1, 2, 4]) & 15                                 # groups of 8 codes: the low and the high nibbles' four
+    packed = (v[..., 0, :] | (v[..., 1, :] << 4)).to(torch.uint8).reshape(list(v.shape[:-3]) + [-1])
+    sums = w.sums if w.sums is not None else w.values.sum(dim=tuple(range(1, w.values.dim())), dtype=torch.int32)
+    return Int4Weight(packed.contiguous(), w.shape, w.axis, w.scale, max(w.qmin, -8), min(w.qmax, 7), w.rounding, sums)
+
+
+def int4_unpack(w: Int4Weight) -> Int8Tensor:
+    """The codes of ``w`` back as an ``Int8Tensor`` weight (one code per byte, padded to a multiple of 32)."""
+    if not isinstance(w, Int4Weight) or w.values.dtype != torch.uint8: raise TypeError(f'int4_unpack: expected an Int4Weight of uint8 bytes, got {type(w)}')
+    b = w.values.reshape(list(w.values.shape[:-1]) + [-1, 1, 4]).to(torch.int32)
+    codes = ((torch.cat((b & 15, b >> 4), -2) ^ 8) - 8).to(torch.int8)                  # sign extension of a nibble
+    return Int8Tensor(codes.reshape(list(w.values.shape[:-1]) + [-1]).contiguous(), w.shape, w.axis, w.scale, 0, w.qmin, w.qmax, w.rounding, w.sums)
+
+
+def int4_quantize_weight(tensor: torch.Tensor, config, axis: int = 1, use_kernels: bool = True) -> Int4Weight:
+    """The INT4 codes of the float32 weight ``tensor`` under ``config`` -- ``LinearQuantize_ToInt``'s, exactly as
+    ``int8_quantize(..., weight=True)`` makes them --, packed: ``int4_pack`` of that.  Refused by name: a range outside -8 .. 7, a
+    non-zero offset, and everything ``int8_quantize`` refuses of a weight."""
+    what = 'int4_quantize_weight'
+    qmin, qmax = int(getattr(config, 'quant_min', 0)), int(getattr(config, 'quant_max', 0))
+    if not -8 <= qmin <= qmax <= 7: raise RuntimeError(f'{what}: the range {qmin} .. {qmax} does not lie in -8 .. 7')
+    return int4_pack(int8_quantize(tensor, config, axis, weight=True, use_kernels=use_kernels, what=what))
+
+
 def _check_operands(what, x, w, rank, bias):
-    for name, t in (('x', x), ('w', w)):
-        if not isinstance(t, Int8Tensor): raise TypeError(f'{what}: {name}: expected an Int8Tensor, got {type(t)}')
-        if t.values.dtype != torch.int8: raise RuntimeError(f'{what}: {name}: the codes are {t.values.dtype}, not int8')
+    for name, t, kinds in (('x', x, Int8Tensor), ('w', w, (Int8Tensor, Int4Weight))):
+        if not isinstance(t, kinds): raise TypeError(f'{what}: {name}: expected an Int8Tensor{" or an Int4Weight" if name == "w" else ""}, got {type(t)}')
+        want = torch.uint8 if isinstance(t, Int4Weight) else torch.int8
+        if t.values.dtype != want: raise RuntimeError(f'{what}: {name}: the codes are {t.values.dtype}, not {str(want)[6:]}')
     if len(w.shape) != rank or (rank == 4 and len(x.shape) != 4): raise RuntimeError(f'{what}: operands must be {rank}-d, got x {list(x.shape)}, w {list(w.shape)}')
     if x.axis != (len(x.shape) - 1 if rank == 2 else 1) or w.axis != 1:
         raise RuntimeError(f'{what}: x {list(x.shape)} / w {list(w.shape)} are packed along axes {x.axis} / {w.axis}, not along the reduction axis')
@@ -130,7 +188,7 @@ def _check_operands(what, x, w, rank, bias):
     if x.device != w.device: raise RuntimeError(f'{what}: x is on {x.device}, w on {w.device}')
     if (w.sums is None and x.zero_point != 0) or w.zero_point != 0: raise RuntimeError(f'{what}: w is not a weight: quantise it with int8_quantize(..., weight=True)')
     if x.scale.numel() != 1: raise RuntimeError(f'{what}: x must be quantised per tensor')
-    kp = w.values[0].numel()
+    kp = w.values[0].numel() * (2 if isinstance(w, Int4Weight) else 1)
     if kp >= MAX_KP: raise RuntimeError(f'{what}: a padded reduction length of {kp}: {MAX_KP} and more could overflow int32')
     if bias is not None:
         if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32: raise RuntimeError(f'{what}: bias must be a float32 tensor')
@@ -177,10 +235,11 @@ def _result(y, q, shape, axis, out_q, out_float, like):
     return (y, packed) if out_float else packed
 
 
-def int8_matmul(a: Int8Tensor, b: Int8Tensor, bias: torch.Tensor = None, residual: torch.Tensor = None, relu: bool = False, out_config=None,
+def int8_matmul(a: Int8Tensor, b, bias: torch.Tensor = None, residual: torch.Tensor = None, relu: bool = False, out_config=None,
                 out_float: Optional[bool] = None, use_kernels: bool = True):
     """``a . b^T`` as a linear INT8 layer (the contract at the top of this module): ``a`` an activation ``[..., K]`` packed along its
-    last axis, ``b`` a weight ``[N, K]`` (``int8_quantize(..., axis=1, weight=True)``), ``bias`` float32 ``[N]``, ``residual`` float32
+    last axis, ``b`` a weight ``[N, K]`` (``int8_quantize(..., axis=1, weight=True)``, or an ``Int4Weight``: ``CUDA.Int4Matmul`` then,
+    the same bits from half the weight bytes), ``bias`` float32 ``[N]``, ``residual`` float32
     ``[..., N]``.  Returns the float32 ``[..., N]``; with ``out_config`` (a per-tensor config: the next layer's activation) the result
     as an ``Int8Tensor`` packed along its last axis -- the bits of ``int8_quantize`` on the float32 result --, and with
     ``out_float=True`` both, ``(tensor, Int8Tensor)``.  ONE launch (``CUDA.Int8Matmul``); ``use_kernels=False``: torch ops, any device."""
@@ -190,24 +249,25 @@ def int8_matmul(a: Int8Tensor, b: Int8Tensor, bias: torch.Tensor = None, residua
     out_float, out_q = _check_tail(what, a, shape, residual, out_config, out_float)
     av, mul = a.values.reshape(-1, a.values.shape[-1]), _mul(a, b)
     res = residual.reshape(-1, shape[-1]) if residual is not None else None
-    if use_kernels: y, q = CUDA.Int8Matmul(av, b.values, b.sums if a.zero_point else None, a.zero_point, mul, bias, res, relu, out_float, out_q)
+    int4 = isinstance(b, Int4Weight)
+    if use_kernels: y, q = (CUDA.Int4Matmul if int4 else CUDA.Int8Matmul)(av, b.values, b.sums if a.zero_point else None, a.zero_point, mul, bias, res, relu, out_float, out_q)
     else:
-        i = (av.to(torch.float64) - a.zero_point) @ b.values.to(torch.float64).t()       # every partial sum is an integer below 2^31: exact
+        i = (av.to(torch.float64) - a.zero_point) @ (int4_unpack(b) if int4 else b).values.to(torch.float64).t()       # every partial sum is an integer below 2^31: exact
         y, q = _tail_torch(i.to(torch.int64), mul, bias, res, relu, out_q)
     y = y.reshape(shape) if y is not None and out_float else None
     return _result(y, q.reshape(shape[:-1] + [-1]) if q is not None else None, shape, len(shape) - 1, out_q, out_float, a)
 
 
-def int8_linear(x: torch.Tensor, weight: Int8Tensor, x_config, bias: torch.Tensor = None, residual: torch.Tensor = None, relu: bool = False,
+def int8_linear(x: torch.Tensor, weight, x_config, bias: torch.Tensor = None, residual: torch.Tensor = None, relu: bool = False,
                 out_config=None, out_float: Optional[bool] = None, use_kernels: bool = True):
-    """A Gemm on an INT8 weight as it runs in deployment: ``int8_quantize(x, x_config, -1)``, then ``int8_matmul``: two launches."""
+    """A Gemm on an INT8 (or ``Int4Weight``) weight as it runs in deployment: ``int8_quantize(x, x_config, -1)``, then ``int8_matmul``: two launches."""
     return int8_matmul(int8_quantize(x, x_config, -1, use_kernels=use_kernels), weight, bias, residual, relu, out_config, out_float, use_kernels)
 
 
-def int8_conv2d_packed(x: Int8Tensor, w: Int8Tensor, bias: torch.Tensor = None, stride=1, padding=0, dilation=1, residual: torch.Tensor = None,
+def int8_conv2d_packed(x: Int8Tensor, w, bias: torch.Tensor = None, stride=1, padding=0, dilation=1, residual: torch.Tensor = None,
                        relu: bool = False, out_config=None, out_float: Optional[bool] = None, use_kernels: bool = True):
     """``conv2d(x, w)`` as a linear INT8 layer: ``x`` an activation ``[N, C, H, W]`` and ``w`` a weight ``[O, C, kh, kw]``, both packed
-    along axis 1; ``stride``, ``padding`` (symmetric) and ``dilation`` are ints or (h, w) pairs, groups is 1.  A tap in the padding is a
+    along axis 1 (``w`` may be an ``Int4Weight``: ``CUDA.Int4Conv2d`` then); ``stride``, ``padding`` (symmetric) and ``dilation`` are ints or (h, w) pairs, groups is 1.  A tap in the padding is a
     real 0, which is the code ``x.zero_point``.  The float32 result is ``[N, O, OH, OW]`` (channels-last strides from the kernel);
     ``residual`` (float32, that shape; channels-last is read in place), ``relu``, ``out_config`` and ``out_float`` as in ``int8_matmul``
     -- the ``Int8Tensor`` is packed along axis 1, what this function takes as ``x``.  ONE launch (``CUDA.Int8Conv2d``), an implicit
@@ -222,20 +282,21 @@ def int8_conv2d_packed(x: Int8Tensor, w: Int8Tensor, bias: torch.Tensor = None, 
     shape = [x.shape[0], w.shape[0], out[0], out[1]]
     out_float, out_q = _check_tail(what, x, shape, residual, out_config, out_float)
     mul = _mul(x, w)
+    int4 = isinstance(w, Int4Weight)
     if use_kernels:
-        y, q = CUDA.Int8Conv2d(x.values, w.values, w.sums if x.zero_point else None, x.zero_point, mul, x.shape[1], bias, stride, padding, dilation,
-                               residual, relu, out_float, out_q)
+        y, q = (CUDA.Int4Conv2d if int4 else CUDA.Int8Conv2d)(x.values, w.values, w.sums if x.zero_point else None, x.zero_point, mul, x.shape[1], bias, stride, padding, dilation,
+                                                              residual, relu, out_float, out_q)
     else:
         xf = torch.nn.functional.pad(x.values.permute(0, 3, 1, 2).to(torch.float64), (padding[1],) * 2 + (padding[0],) * 2, value=x.zero_point)
-        i = torch.nn.functional.conv2d(xf - x.zero_point, w.values.permute(0, 3, 1, 2).to(torch.float64), None, stride, 0, dilation)      # exact: integers below 2^31
+        i = torch.nn.functional.conv2d(xf - x.zero_point, (int4_unpack(w) if int4 else w).values.permute(0, 3, 1, 2).to(torch.float64), None, stride, 0, dilation)      # exact: integers below 2^31
         y, q = _tail_torch(i.permute(0, 2, 3, 1).to(torch.int64), mul, bias, residual.permute(0, 2, 3, 1) if residual is not None else None, relu, out_q)
         y = y.permute(0, 3, 1, 2)
     return _result(y if out_float else None, q, shape, 1, out_q, out_float, x)
 
 
-def int8_conv2d(x: torch.Tensor, weight: Int8Tensor, x_config, bias: torch.Tensor = None, stride=1, padding=0, dilation=1, groups: int = 1,
+def int8_conv2d(x: torch.Tensor, weight, x_config, bias: torch.Tensor = None, stride=1, padding=0, dilation=1, groups: int = 1,
                 residual: torch.Tensor = None, relu: bool = False, out_config=None, out_float: Optional[bool] = None, use_kernels: bool = True):
-    """A convolution on an INT8 weight as it runs in deployment: ``int8_quantize(x, x_config, 1)`` -- ``x`` ``[N, C, H, W]`` --, then
+    """A convolution on an INT8 (or ``Int4Weight``) weight as it runs in deployment: ``int8_quantize(x, x_config, 1)`` -- ``x`` ``[N, C, H, W]`` --, then
     ``int8_conv2d_packed``: two launches."""
     if groups != 1: raise RuntimeError(f'int8_conv2d: groups must be 1, got {groups}')
     if isinstance(x, torch.Tensor) and x.dim() != 4: raise RuntimeError(f'int8_conv2d: x must be 4-d [N, C, H, W], got shape {list(x.shape)}')
