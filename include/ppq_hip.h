@@ -1029,6 +1029,26 @@ int ppqhip_int4_conv2d(const int8_t* x, const uint8_t* w, const int32_t* w_sums,
                        int q_nan, int64_t n, int64_t c, int64_t h, int64_t wd, int64_t o, int64_t kh, int64_t kw, int64_t stride_h,
                        int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, void* stream);
 
+/* The depthwise convolution of the same family (groups == c, channel multiplier 1; ppq_amd/int8.py int8_depthwise_conv2d_packed;
+ * DESIGN.md section 9.24; ADDED under ABI 4), on v_dot4c_i32_i8: the MFMA has no reduction over channels to work on.  x [n, h, wd, cp]
+ * int8 codes, cp = ceil32(c), as ppqhip_int8_conv2d takes them; w [kh, kw, cp] int8, tap-major and channels-last, the channels
+ * c .. cp - 1 zero; w_sums [c] int32, the sum of a channel's taps (may be NULL when zx == 0); mul, bias [c]; y and residual
+ * [n, oh, ow, c] float32, q [n, oh, ow, cp] int8 with zy in the channels c .. cp - 1.  Per output
+ *   I = sum_{ky, kx} w[ky, kx, c] (x[n, oy * stride_h - pad_h + ky * dil_h, ox * stride_w - pad_w + kx * dil_w, c] - zx), exact in int32,
+ * a tap in the padding being a real 0 (the code zx: not read, the kernel stages the byte zx for it), then the steps t, v, c / q of
+ * ppqhip_int8_gemm with n -> c, in that order and by the same device functions: the result has the bits of ppqhip_int8_conv2d on the
+ * dense [c, c, kh, kw] weight that is zero off the diagonal.  One launch on `stream`, no allocation, no synchronisation (capturable).
+ * Refused as ppqhip_int8_conv2d refuses, with the same texts in the same order under the name "int8_dwconv2d"; there is no bound on a
+ * reduction length to refuse (kh * kw * 128 * 255 < 2^31 for every window that is not refused below).  PPQHIP_ERR_UNSUPPORTED, after
+ * the size checks and before n == 0 or c == 0 returns PPQHIP_OK: a geometry whose staged input patch -- (7 stride + (k - 1) dil + 1)
+ * pixels per axis at 32 bytes, 48 where stride_w % 4 == 2 -- and expanded weights (128 kh kw bytes) exceed 65536 bytes of LDS; the
+ * message states the bytes it would need.  Every window with (k - 1) dil <= 6 per axis fits at stride 1 and 2.  Booked under
+ * "int8_dwconv": x once, w, the channel data, the residual and every output. */
+int ppqhip_int8_dwconv2d(const int8_t* x, const int8_t* w, const int32_t* w_sums, int zx, const float* mul, const float* bias,
+                         const float* residual, int relu, float* y, int8_t* q, float sy, int zy, int qmin, int qmax, int rounding,
+                         int q_nan, int64_t n, int64_t c, int64_t h, int64_t wd, int64_t kh, int64_t kw, int64_t stride_h,
+                         int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, void* stream);
+
 /* ---- pointwise (1x1) convolution on the FP32-input MFMA (ADDED under ABI 4) ---------------------------------
  * y[n, o, oh, ow] = sum_k w[o, k] x[n, k, oh * stride, ow * stride] (+ bias[o]) for contiguous NCHW float32 x [n, c, h, wd],
  * w [o, c] (a [o, c, 1, 1] convolution weight as it lies) and y [n, o, ho, wo], ho = (h - 1) / stride + 1, wo likewise; no padding,

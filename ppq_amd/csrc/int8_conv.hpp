@@ -89,12 +89,6 @@ __global__ __launch_bounds__(kBlock, B::kMinBlocks) void q8_conv_kernel(const In
     q8_tile<B>(g.e, g.nb, stage, [&g](uint32_t row0, uint32_t col0, uint32_t t) { return ConvMap<B>(g, row0, col0, t); });
 }
 
-// a * b when it stays within 2^31 - 1 (both are within it already), -1 otherwise
-inline int64_t bounded_product(int64_t a, int64_t b) {
-    const int64_t p = a * b;
-    return p > kQ8Max ? -1 : p;
-}
-
 // the body of ppqhip_int8_conv2d / ppqhip_int4_conv2d: `what` names the entry point in its refusals, `id` books the launch
 template <typename B>
 int q8_conv(const char* what, KernelId id, const int8_t* x, const void* w, const Int8TailHost& t, int64_t n, int64_t c, int64_t h, int64_t wd,

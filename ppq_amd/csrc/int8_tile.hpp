@@ -226,10 +226,25 @@ __device__ __forceinline__ void q8_start(const Int8Tail& e, uint32_t n0, uint32_
     }
 }
 
+// One output's float32 chain, shared by every kernel of the family (the depthwise one of int8_dwconv.hip included): t = float32(I)
+// (v_cvt_f32_i32, nearest even); v = t * mul; + bias (where the layer has one); + res (where it has a residual); the ReLU.
+__device__ __forceinline__ float q8_value(const Int8Tail& e, int i, float mul, float bias, float res) {
+    const float t = (float)i;
+    float v = t * mul;
+    if (e.bias != nullptr) v = v + bias;
+    if (e.residual != nullptr) v = v + res;
+    if (e.relu) v = v > 0.f ? v : (v != v ? v : 0.f);                             // -0 -> +0; NaN stays
+    return v;
+}
+
+// ... and its code: to_int_scalar of linear.hip's export kernels on the stored-domain grid, the NaN code for a NaN
+__device__ __forceinline__ uint32_t q8_code(const Int8Tail& e, float v) {
+    return v != v ? (uint32_t)e.q_nan : (uint32_t)to_int_scalar(v, e.sy, e.zy, e.qmin, e.qmax, e.rounding);
+}
+
 // The epilogue of a wave that owns rows m0 .. m0 + 31 and columns n0 .. n0 + 31 (n0 % 32 == 0) of the [m, n] result; acc[i][j][q] is
-// row m0 + 16 i + 4 grp + q, column n0 + 16 j + r.  Per output, in this order: t = float32(I) (v_cvt_f32_i32, nearest even);
-// v = t * mul[col]; + bias[col]; + residual[row, col]; the ReLU; then v as float32 and / or its code: to_int_scalar of linear.hip's
-// export kernels on the stored-domain grid, the NaN code for a NaN, the zero point in the padding columns n .. op - 1.  `stage` is
+// row m0 + 16 i + 4 grp + q, column n0 + 16 j + r.  Per output q8_value on mul[col], bias[col] and residual[row, col]; then v as
+// float32 and / or its code (q8_code), the zero point in the padding columns n .. op - 1.  `stage` is
 // this wave's own kQ8CodeBytes of LDS: the codes of a row sit in 16 lanes x 2 tiles and are gathered through it; then lane l stores
 // half l & 1 of row l >> 1.  Only the wave itself touches its stage, so no workgroup barrier is needed.
 __device__ __forceinline__ void q8_epilogue(const v4i (&acc)[kQ8WaveTiles][kQ8WaveTiles], const Int8Tail& e, uint32_t m0, uint32_t n0,
@@ -254,14 +269,10 @@ __device__ __forceinline__ void q8_epilogue(const v4i (&acc)[kQ8WaveTiles][kQ8Wa
             const size_t at = (size_t)min(row, e.m - 1u) * e.n;                  // rows past m: copies of the last one, not stored
 #pragma unroll
             for (int j = 0; j < T; j++) {
-                const float t = (float)acc[i][j][q];
-                float v = t * mul[j];
-                if (e.bias != nullptr) v = v + b[j];
-                if (e.residual != nullptr) v = v + e.residual[at + col[j]];
-                if (e.relu) v = v > 0.f ? v : (v != v ? v : 0.f);                 // -0 -> +0; NaN stays
+                const float v = q8_value(e, acc[i][j][q], mul[j], b[j], e.residual != nullptr ? e.residual[at + col[j]] : 0.f);
                 if (e.c != nullptr && row < e.m && col_in[j]) e.c[at + col[j]] = v;
                 if (e.q != nullptr) {
-                    const uint32_t code = v != v ? (uint32_t)e.q_nan : (uint32_t)to_int_scalar(v, e.sy, e.zy, e.qmin, e.qmax, e.rounding);
+                    const uint32_t code = q8_code(e, v);
                     stage[tr * kQ8Block + j * kQ8Tile + r] = (uint8_t)(col_in[j] ? code & 0xffu : pad_code);
                 }
             }
@@ -331,20 +342,25 @@ inline int check_int8_tail(const char* what, const char* float_name, const Int8T
     return PPQHIP_OK;
 }
 
+// a * b when it stays within 2^31 - 1 (both are within it already), -1 otherwise
+inline int64_t bounded_product(int64_t a, int64_t b) {
+    const int64_t p = a * b;
+    return p > kQ8Max ? -1 : p;
+}
+
 // The rest of an entry point once its sizes are known: m x n the result, kp the padded reduction length (kp == 0 reads no operand),
-// `ins` the operands' spans and `bytes` what they book.  Checks the tail's pointers, alignment and overlaps, fills e and calls
-// launch(blocks, stream).
+// `workgroups` what it launches, `ins` the operands' spans and `bytes` what they book.  Checks the tail's pointers, alignment and
+// overlaps, fills e (but for tiles_n) and calls launch(workgroups, stream).
 template <typename Launch>
-inline int launch_q8_tiles(const char* what, const char* float_name, KernelId id, const Int8TailHost& h, int64_t m, int64_t n, int64_t kp,
-                           std::vector<Span>& ins, double bytes, void* stream, Int8Tail& e, Launch&& launch) {
+inline int launch_q8(const char* what, const char* float_name, KernelId id, const Int8TailHost& h, int64_t m, int64_t n, int64_t kp,
+                     int64_t workgroups, std::vector<Span>& ins, double bytes, void* stream, Int8Tail& e, Launch&& launch) {
     if (kp >= kQ8MaxK) { set_error("%s: a padded reduction length of %lld: 65536 and more could overflow int32", what, (long long)kp); return PPQHIP_ERR_INVALID_VALUE; }
     if (h.mul == nullptr || (h.zx != 0 && kp > 0 && h.sums == nullptr)) {
         set_error(h.mul == nullptr ? "%s: null pointer" : "%s: sums is required with a zero point other than 0", what); return PPQHIP_ERR_INVALID_VALUE;
     }
     if (!aligned16(h.c) || !aligned16(h.q)) { set_error("%s: operands, %s and q must be 16-byte aligned", what, float_name); return PPQHIP_ERR_INVALID_VALUE; }
     const int64_t op = (n + kQ8Block - 1) / kQ8Block * kQ8Block;
-    const int64_t tiles_m = (m + kQ8Edge - 1) / kQ8Edge, tiles_n = (n + kQ8Edge - 1) / kQ8Edge;
-    if (tiles_m * tiles_n > kQ8Max) { set_error("%s: too many workgroups in one launch", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (workgroups < 0 || workgroups > kQ8Max) { set_error("%s: too many workgroups in one launch", what); return PPQHIP_ERR_INVALID_VALUE; }
     std::vector<Span> outs;
     ins.push_back(span_of(h.mul, n)); bytes += 4.0 * (double)n;
     if (h.sums != nullptr && kp > 0) ins.push_back(span_of(h.sums, n));
@@ -357,11 +373,19 @@ inline int launch_q8_tiles(const char* what, const char* float_name, KernelId id
     e.m = (uint32_t)m; e.n = (uint32_t)n; e.op = (uint32_t)op;
     e.zx = h.zx; e.relu = h.relu ? 1u : 0u;
     e.sy = h.sy; e.zy = (float)h.zy; e.qmin = (float)h.qmin; e.qmax = (float)h.qmax; e.rounding = h.rounding; e.q_nan = h.q_nan;
-    e.tiles_n = make_fastdiv((uint32_t)tiles_n);
     hipStream_t s = (hipStream_t)stream;
     LaunchScope scope(id, bytes, s);
-    launch((uint32_t)(tiles_m * tiles_n), s);
+    launch((uint32_t)workgroups, s);
     return finish_launch(what);
+}
+
+// launch_q8 for the kernels of q8_tile: one workgroup per 64 x 64 tile of the result
+template <typename Launch>
+inline int launch_q8_tiles(const char* what, const char* float_name, KernelId id, const Int8TailHost& h, int64_t m, int64_t n, int64_t kp,
+                           std::vector<Span>& ins, double bytes, void* stream, Int8Tail& e, Launch&& launch) {
+    const int64_t tiles_m = (m + kQ8Edge - 1) / kQ8Edge, tiles_n = (n + kQ8Edge - 1) / kQ8Edge;
+    e.tiles_n = make_fastdiv((uint32_t)tiles_n);
+    return launch_q8(what, float_name, id, h, m, n, kp, tiles_m * tiles_n, ins, bytes, stream, e, launch);
 }
 
 }  // namespace ppqhip

@@ -1,23 +1,26 @@
 """The bindings of the linear INT8 kernels (``csrc/int8_gemm.hip``, ``csrc/int8_conv.hip``) and of their forms
 with a packed INT4 weight (``csrc/int4_gemm.hip``, ``csrc/int4_conv.hip``; section 9.23): ``CUDA.Int8Matmul`` / ``Int8Conv2d`` /
-``Int4Matmul`` / ``Int4Conv2d`` forward here.  Operands are int8 codes with the reduction axis last and padded to a multiple of 32; an
-INT4 weight is uint8, two codes per byte, half as many bytes along that axis."""
+``Int4Matmul`` / ``Int4Conv2d`` forward here, and ``Int8DepthwiseConv2d`` to the depthwise kernel (``csrc/int8_dwconv.hip``; section
+9.24).  Operands are int8 codes with the reduction axis last and padded to a multiple of 32; an INT4 weight is uint8, two codes per
+byte, half as many bytes along that axis; a depthwise weight is ``[kh, kw, Cp]``."""
 import torch
 
 from .._lib import lib
 from ._base import _KERNEL_FAILURE, _DeviceOf, _check, _f32, _ptr, _raise, _stream
 
 INT8_BLOCK = 32          # the K of one v_mfma_i32_16x16x32_i8: rows are padded to it
+DEPTHWISE_LDS_BYTES = 65536      # what a workgroup of the depthwise kernel may stage
 
 
 def _refuse(what: str): raise RuntimeError(_KERNEL_FAILURE + what)
 
 
 def _int8_operands(rank, names, operands, int4=False):
-    """int8 -- with ``int4`` the second one uint8, two codes per byte --, on one GPU, ``rank``-d, contiguous, the last axis a multiple
-    of 32 codes and the same for both; a tensor whose data does not start on a 16-byte boundary is copied (the allocator aligns)."""
+    """int8 -- with ``int4`` the second one uint8, two codes per byte --, on one GPU, ``rank``-d (a pair: one rank each), contiguous,
+    the last axis a multiple of 32 codes and the same for both; a tensor whose data does not start on a 16-byte boundary is copied
+    (the allocator aligns)."""
     dev, out = operands[0].device if isinstance(operands[0], torch.Tensor) else None, []
-    for name, t, per_byte in zip(names, operands, (1, 2 if int4 else 1)):
+    for name, t, per_byte, rank in zip(names, operands, (1, 2 if int4 else 1), rank if isinstance(rank, tuple) else (rank, rank)):
         if per_byte == 2: _check(t, torch.uint8, f'{name}(Expect to be UINT8: packed INT4)')
         else: _check(t, torch.int8, f'{name}(Expect to be INT8)')
         if t.dim() != rank: _refuse(f'{name} must be {rank}-d, got {list(t.shape)}')
@@ -95,4 +98,37 @@ def int8_conv2d(x, w, w_sums, zx: int, mul, c: int, bias=None, stride=(1, 1), pa
     with _DeviceOf(x):
         _raise(conv(x.data_ptr(), w.data_ptr(), _ptr(sums), zx, mul.data_ptr(), _ptr(bias), _ptr(residual), 1 if relu else 0, _ptr(y), _ptr(q), *grid,
                     n, c, h, wd, o, kh, kw, sh, sw, ph, pw, dh, dw, _stream()))
+    return (y.permute(0, 3, 1, 2) if y is not None else None), q
+
+
+def depthwise_lds_bytes(kh: int, kw: int, stride, dilation) -> int:
+    """What a workgroup of ``csrc/int8_dwconv.hip`` stages for one 8 x 8 tile: the input patch, ``7 stride + (k - 1) dilation + 1``
+    pixels per axis at 32 bytes (48 where the horizontal stride is 2 mod 4: DESIGN.md section 9.24), and ``128 kh kw`` bytes of
+    expanded weights."""
+    (sh, sw), (dh, dw) = stride, dilation
+    return (7 * sh + (kh - 1) * dh + 1) * (7 * sw + (kw - 1) * dw + 1) * (48 if sw % 4 == 2 else 32) + 128 * kh * kw
+
+
+def int8_depthwise_conv2d(x, w, w_sums, zx: int, mul, c: int, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), residual=None,
+                          relu: bool = False, out_float: bool = True, out_q=None):
+    """``ppqhip_int8_dwconv2d``: ``x [N, H, W, Cp]`` and ``w [kh, kw, Cp]`` int8 codes of a depthwise convolution (groups == ``c``,
+    channel multiplier 1), ``w_sums`` / ``mul`` / ``bias`` ``[c]``.  ``residual`` is ``[N, c, OH, OW]``; a tensor that is not
+    channels-last is copied into that layout.  Returns ``(y, q)``: float32 ``[N, c, OH, OW]`` with channels-last strides and int8
+    ``[N, OH, OW, Cp]``.  Refused like ``int8_conv2d``, and a geometry that stages more than 64 KiB of LDS."""
+    x, w = _int8_operands((4, 3), ('x', 'w'), (x, w))
+    c = int(c)
+    if not 0 < c <= x.shape[-1] or x.shape[-1] - c >= INT8_BLOCK: _refuse(f'c = {c} does not pad to the {x.shape[-1]} stored channels')
+    (n, h, wd, _), (kh, kw, _) = x.shape, w.shape
+    (sh, sw), (ph, pw), (dh, dw) = ([int(v) for v in pair] for pair in (stride, padding, dilation))
+    if min(sh, sw, dh, dw) < 1 or min(ph, pw) < 0: _refuse(f'stride {(sh, sw)} and dilation {(dh, dw)} must be at least 1, padding {(ph, pw)} at least 0')
+    oh, ow = (h + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (wd + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    if oh < 1 or ow < 1: _refuse(f'a {kh} x {kw} kernel with dilation {(dh, dw)} does not fit an input of {h} x {wd} padded by {(ph, pw)}')
+    need = depthwise_lds_bytes(kh, kw, (sh, sw), (dh, dw))
+    if need > DEPTHWISE_LDS_BYTES:
+        _refuse(f'a {kh} x {kw} window at stride {(sh, sw)} and dilation {(dh, dw)} stages {need} bytes of LDS: a workgroup has {DEPTHWISE_LDS_BYTES}')
+    if residual is not None and isinstance(residual, torch.Tensor) and residual.dim() == 4: residual = residual.permute(0, 2, 3, 1)
+    sums, zx, mul, bias, residual, y, q, grid = _int8_tail(c, [n, oh, ow, c], x.device, w_sums, zx, mul, bias, residual, out_float, out_q)
+    with _DeviceOf(x):
+        _raise(lib.ppqhip_int8_dwconv2d(x.data_ptr(), w.data_ptr(), _ptr(sums), zx, mul.data_ptr(), _ptr(bias), _ptr(residual), 1 if relu else 0, _ptr(y),
+                                        _ptr(q), *grid, n, c, h, wd, kh, kw, sh, sw, ph, pw, dh, dw, _stream()))
     return (y.permute(0, 3, 1, 2) if y is not None else None), q

@@ -14,18 +14,22 @@ oracle of both).  Codes are stored as int8: a config whose range lies in 0 .. 25
 A weight may also be INT4 (section 9.23): an ``Int4Weight`` holds codes in -8 .. 7 two per byte, and every layer function takes it where
 it takes a weight.  The layer then has the bits of the int8 layer on the same codes, from ONE launch of ``csrc/int4_gemm.hip`` /
 ``csrc/int4_conv.hip``, which read half the weight bytes and unpack a nibble on its way from LDS to the MFMA.
+
+A depthwise convolution (groups == C, channel multiplier 1; section 9.24) has no reduction over channels for the MFMA: the sum over
+``k`` is the sum over the taps of one channel, and ``int8_depthwise_conv2d_packed`` runs it on ``v_dot4c_i32_i8``
+(``csrc/int8_dwconv.hip``) on an ``Int8DepthwiseWeight``, with the same tail and the bits of the dense layer on the block-diagonal weight.
 """
 from typing import Optional
 
 import torch
 
 from .core import QuantizationProperty, rounding_value
-from .ffi import CUDA, INT8_BLOCK
+from .ffi import CUDA, DEPTHWISE_LDS_BYTES, INT8_BLOCK, depthwise_lds_bytes
 from .mx import _pair, relu_positive_zero
 from .round import ppq_tensor_round
 
 __all__ = ['Int8Tensor', 'Int4Weight', 'int8_quantize', 'int8_dequantize', 'int4_quantize_weight', 'int4_pack', 'int4_unpack', 'int8_matmul', 'int8_linear',
-           'int8_conv2d_packed', 'int8_conv2d']
+           'int8_conv2d_packed', 'int8_conv2d', 'Int8DepthwiseWeight', 'int8_depthwise_weight', 'int8_depthwise_conv2d_packed', 'int8_depthwise_conv2d']
 
 MAX_KP = 65536           # padded reduction lengths from here on are refused: |I| could leave int32
 
@@ -70,6 +74,27 @@ class Int4Weight:
     def dequantize(self) -> torch.Tensor:
         """``code * scale`` in float32, in the tensor's own layout."""
         return int4_unpack(self).dequantize()
+
+
+class Int8DepthwiseWeight:
+    """int8 codes of a symmetric depthwise weight of ``shape`` ``(C, 1, kh, kw)``, laid out for ``csrc/int8_dwconv.hip``: ``values``
+    int8 ``[kh, kw, Cp]``, tap-major and channels-last, ``Cp = ceil32(C)``, the channels ``C .. Cp - 1`` code 0.  ``scale``: float32, a
+    scalar tensor or ``[C]``; ``sums``: int32 ``[C]``, the sum of a channel's taps; ``qmin``, ``qmax``, ``rounding`` as in
+    ``Int8Tensor``; ``zero_point`` is 0."""
+    __slots__ = ('values', 'shape', 'scale', 'qmin', 'qmax', 'rounding', 'sums')
+    zero_point = 0
+
+    def __init__(self, values, shape, scale, qmin, qmax, rounding, sums):
+        self.values, self.shape = values, tuple(int(d) for d in shape)
+        self.scale, self.qmin, self.qmax, self.rounding, self.sums = scale, int(qmin), int(qmax), int(rounding), sums
+
+    @ property
+    def device(self): return self.values.device
+
+    def dequantize(self) -> torch.Tensor:
+        """``code * scale`` in float32 ``[C, 1, kh, kw]``."""
+        codes = self.values[..., :self.shape[0]].permute(2, 0, 1).unsqueeze(1).to(torch.float32)
+        return codes * (self.scale.reshape(-1, 1, 1, 1) if self.scale.numel() > 1 else self.scale)
 
 
 def _grid(what: str, config):
@@ -294,10 +319,79 @@ def int8_conv2d_packed(x: Int8Tensor, w, bias: torch.Tensor = None, stride=1, pa
     return _result(y if out_float else None, q, shape, 1, out_q, out_float, x)
 
 
+def int8_depthwise_weight(tensor: torch.Tensor, config, use_kernels: bool = True) -> Int8DepthwiseWeight:
+    """The codes of the float32 depthwise weight ``tensor`` ``[C, 1, kh, kw]`` under ``config`` -- ``int8_quantize(..., weight=True)``'s,
+    per tensor or per channel along axis 0, with its refusals under this name --, re-laid as an ``Int8DepthwiseWeight`` (torch ops, done
+    once).  Refused too: a weight whose axis 1 is not 1 (a channel multiplier, or a grouped convolution that is not depthwise)."""
+    what = 'int8_depthwise_weight'
+    if not isinstance(tensor, torch.Tensor) or tensor.dim() != 4 or tensor.shape[1] != 1:
+        raise RuntimeError(f'{what}: expected a [C, 1, kh, kw] weight (groups == C, channel multiplier 1), got shape {list(getattr(tensor, "shape", []))}')
+    t = int8_quantize(tensor, config, 1, weight=True, use_kernels=use_kernels, what=what)             # [C, kh, kw, 32]: code, then 31 zeros
+    values = _pad_last(t.values[..., 0].permute(1, 2, 0), 0).contiguous()
+    return Int8DepthwiseWeight(values, tensor.shape, t.scale, t.qmin, t.qmax, t.rounding, t.sums)
+
+
+def int8_depthwise_conv2d_packed(x: Int8Tensor, w: Int8DepthwiseWeight, bias: torch.Tensor = None, stride=1, padding=0, dilation=1,
+                                 residual: torch.Tensor = None, relu: bool = False, out_config=None, out_float: Optional[bool] = None,
+                                 use_kernels: bool = True):
+    """``conv2d(x, w, groups=C)`` as a linear INT8 layer: ``x`` an activation ``[N, C, H, W]`` packed along axis 1, ``w`` an
+    ``Int8DepthwiseWeight`` ``[C, 1, kh, kw]``.  Everything else -- the geometry, the padding's code, ``bias`` ``[C]``, ``residual``,
+    ``relu``, ``out_config``, ``out_float`` and what is returned -- is ``int8_conv2d_packed``'s: the ``Int8Tensor`` is packed along axis
+    1, so depthwise and dense layers chain.  ONE launch (``CUDA.Int8DepthwiseConv2d``, on ``v_dot4c_i32_i8``); ``use_kernels=False``:
+    torch ops on any device, identical bits.  Refused under either arm: a geometry whose input patch and weights exceed the 64 KiB of
+    LDS the kernel stages them in (every window with ``(k - 1) * dilation <= 6`` per axis fits at stride 1 and 2)."""
+    what = 'int8_depthwise_conv2d'
+    if not isinstance(x, Int8Tensor): raise TypeError(f'{what}: x: expected an Int8Tensor, got {type(x)}')
+    if not isinstance(w, Int8DepthwiseWeight): raise TypeError(f'{what}: w: expected an Int8DepthwiseWeight, got {type(w)}')
+    for name, t in (('x', x), ('w', w)):
+        if t.values.dtype != torch.int8: raise RuntimeError(f'{what}: {name}: the codes are {t.values.dtype}, not int8')
+    if len(x.shape) != 4 or x.axis != 1: raise RuntimeError(f'{what}: x {list(x.shape)} must be 4-d and packed along axis 1, not {x.axis}')
+    if x.shape[1] != w.shape[0]: raise RuntimeError(f'{what}: channel mismatch: x has {x.shape[1]} channels, w {w.shape[0]}')
+    if x.device != w.device: raise RuntimeError(f'{what}: x is on {x.device}, w on {w.device}')
+    if x.scale.numel() != 1: raise RuntimeError(f'{what}: x must be quantised per tensor')
+    c, kh, kw = w.shape[0], w.shape[2], w.shape[3]
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32: raise RuntimeError(f'{what}: bias must be a float32 tensor')
+        if list(bias.shape) != [c]: raise RuntimeError(f'{what}: bias of shape {list(bias.shape)}, expected [{c}]')
+    stride, padding, dilation = _pair(stride, 'stride', 1, what), _pair(padding, 'padding', 0, what), _pair(dilation, 'dilation', 1, what)
+    out = tuple((x.shape[2 + i] + 2 * padding[i] - dilation[i] * (w.shape[2 + i] - 1) - 1) // stride[i] + 1 for i in range(2))
+    if min(out) < 1:
+        raise RuntimeError(f'{what}: a {kh} x {kw} kernel with dilation {dilation} does not fit an input of {x.shape[2]} x {x.shape[3]} padded by {padding}')
+    need = depthwise_lds_bytes(kh, kw, stride, dilation)
+    if need > DEPTHWISE_LDS_BYTES:
+        raise RuntimeError(f'{what}: a {kh} x {kw} window at stride {stride} and dilation {dilation} stages {need} bytes of LDS: a workgroup has {DEPTHWISE_LDS_BYTES}')
+    shape = [x.shape[0], c, out[0], out[1]]
+    out_float, out_q = _check_tail(what, x, shape, residual, out_config, out_float)
+    mul = _mul(x, w)
+    if use_kernels:
+        y, q = CUDA.Int8DepthwiseConv2d(x.values, w.values, w.sums if x.zero_point else None, x.zero_point, mul, c, bias, stride, padding, dilation,
+                                        residual, relu, out_float, out_q)
+    else:
+        xf = torch.nn.functional.pad(x.values[..., :c].permute(0, 3, 1, 2).to(torch.float64), (padding[1],) * 2 + (padding[0],) * 2, value=x.zero_point)
+        wf = w.values[..., :c].permute(2, 0, 1).unsqueeze(1).to(torch.float64)
+        i = torch.nn.functional.conv2d(xf - x.zero_point, wf, None, stride, 0, dilation, groups=c)          # exact: integers below 2^31
+        y, q = _tail_torch(i.permute(0, 2, 3, 1).to(torch.int64), mul, bias, residual.permute(0, 2, 3, 1) if residual is not None else None, relu, out_q)
+        y = y.permute(0, 3, 1, 2)
+    return _result(y if out_float else None, q, shape, 1, out_q, out_float, x)
+
+
+def int8_depthwise_conv2d(x: torch.Tensor, weight: Int8DepthwiseWeight, x_config, bias: torch.Tensor = None, stride=1, padding=0, dilation=1,
+                          residual: torch.Tensor = None, relu: bool = False, out_config=None, out_float: Optional[bool] = None, use_kernels: bool = True):
+    """A depthwise convolution on an INT8 weight as it runs in deployment: ``int8_quantize(x, x_config, 1)`` -- ``x`` ``[N, C, H, W]`` --,
+    then ``int8_depthwise_conv2d_packed``: two launches."""
+    if isinstance(x, torch.Tensor) and x.dim() != 4: raise RuntimeError(f'int8_depthwise_conv2d: x must be 4-d [N, C, H, W], got shape {list(x.shape)}')
+    return int8_depthwise_conv2d_packed(int8_quantize(x, x_config, 1, use_kernels=use_kernels), weight, bias, stride, padding, dilation, residual, relu,
+                                        out_config, out_float, use_kernels)
+
+
 def int8_conv2d(x: torch.Tensor, weight, x_config, bias: torch.Tensor = None, stride=1, padding=0, dilation=1, groups: int = 1,
                 residual: torch.Tensor = None, relu: bool = False, out_config=None, out_float: Optional[bool] = None, use_kernels: bool = True):
     """A convolution on an INT8 (or ``Int4Weight``) weight as it runs in deployment: ``int8_quantize(x, x_config, 1)`` -- ``x`` ``[N, C, H, W]`` --, then
-    ``int8_conv2d_packed``: two launches."""
+    ``int8_conv2d_packed``: two launches.  With an ``Int8DepthwiseWeight`` and ``groups == C`` it is ``int8_depthwise_conv2d``; any other
+    grouped convolution is refused."""
+    if isinstance(weight, Int8DepthwiseWeight):
+        if groups != weight.shape[0]: raise RuntimeError(f'int8_conv2d: a depthwise weight of {weight.shape[0]} channels needs groups == {weight.shape[0]}, got {groups}')
+        return int8_depthwise_conv2d(x, weight, x_config, bias, stride, padding, dilation, residual, relu, out_config, out_float, use_kernels)
     if groups != 1: raise RuntimeError(f'int8_conv2d: groups must be 1, got {groups}')
     if isinstance(x, torch.Tensor) and x.dim() != 4: raise RuntimeError(f'int8_conv2d: x must be 4-d [N, C, H, W], got shape {list(x.shape)}')
     return int8_conv2d_packed(int8_quantize(x, x_config, 1, use_kernels=use_kernels), weight, bias, stride, padding, dilation, residual, relu,
