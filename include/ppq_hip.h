@@ -1049,6 +1049,25 @@ int ppqhip_int8_dwconv2d(const int8_t* x, const int8_t* w, const int32_t* w_sums
                          int q_nan, int64_t n, int64_t c, int64_t h, int64_t wd, int64_t kh, int64_t kw, int64_t stride_h,
                          int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, void* stream);
 
+/* The grouped convolution of the same family (1 < groups < c, or a depthwise layer with a channel multiplier; ppq_amd/int8.py
+ * int8_grouped_conv2d_packed; ADDED under ABI 4), on v_mfma_i32_16x16x32_i8 with a tile of 128 pixel rows x one
+ * slice of 32 output channels per workgroup.  Every argument up to dil_w is ppqhip_int8_conv2d's but w: with c_g = c / groups and
+ * o_g = o / groups, output channel oc sums over the c_g kh kw inputs of its own group oc / o_g only, and the result has the bits of
+ * ppqhip_int8_conv2d on the dense [o, kh, kw, cp] weight that is zero outside each row's group.  Slice s is the output channels
+ * 32 s .. 32 s + 31; cb0 [ceil(o / 32)] int32 (device memory) holds the first 32-channel block of x that slice s reads and nbs the
+ * number of blocks a row of w stores per tap: w is [o, kh, kw, 32 nbs] int8, block j of a tap of row oc holding the codes of w[oc] for
+ * the input channels 32 (cb0[oc / 32] + j) .. + 31 -- those of the row's own group in their places, 0 for every other channel, for
+ * channels at or past c and for blocks at or past cp / 32 (the kernel reads block min(cb0[s] + j, cp / 32 - 1) of x there, which the
+ * zeros cancel).  w_sums [o] is the sum of a row's codes.  One launch on `stream`, no allocation, no synchronisation (capturable).
+ * Refused as ppqhip_int8_conv2d refuses, with the same texts in the same order under the name "int8_gconv2d" -- the padded reduction
+ * length that must stay below 65536 is 32 kh kw nbs --, and after the geometry's checks: groups < 1; c or o no multiple of groups;
+ * nbs < 1; a null cb0.  Booked under "int8_gconv": x once, w, the column data, the residual and every output. */
+int ppqhip_int8_gconv2d(const int8_t* x, const int8_t* w, const int32_t* w_sums, int zx, const float* mul, const float* bias,
+                        const float* residual, int relu, float* y, int8_t* q, float sy, int zy, int qmin, int qmax, int rounding,
+                        int q_nan, int64_t n, int64_t c, int64_t h, int64_t wd, int64_t o, int64_t kh, int64_t kw, int64_t stride_h,
+                        int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t groups, int64_t nbs,
+                        const int32_t* cb0, void* stream);
+
 /* ---- pointwise (1x1) convolution on the FP32-input MFMA (ADDED under ABI 4) ---------------------------------
  * y[n, o, oh, ow] = sum_k w[o, k] x[n, k, oh * stride, ow * stride] (+ bias[o]) for contiguous NCHW float32 x [n, c, h, wd],
  * w [o, c] (a [o, c, 1, 1] convolution weight as it lies) and y [n, o, ho, wo], ho = (h - 1) / stride + 1, wo likewise; no padding,

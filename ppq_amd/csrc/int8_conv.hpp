@@ -40,20 +40,19 @@ struct ConvRow {                                  // output pixel of one row of 
     int32_t iy0, ix0;                             // oy * sh - ph, ox * sw - pw
 };
 
-// Where a thread's share of a chunk lies.  In the stage: as in int8_gemm.hpp.  In global memory: B by its codec's map, A by the
-// decoded output pixels of its rows.
-template <typename B>
-struct ConvMap {
+// The A side of a thread's share of a chunk, for the dense (NA = 2) and the grouped (NA = 4, int8_gconv.hpp) convolution: the decoded
+// output pixels of its rows t >> 3 + 32 h, where its segments lie in the stage, and the gather.
+template <int NA>
+struct ConvA {
     const Int8ConvArgs& g;
-    ConvRow ra[2];
-    uint32_t seg, lds_e[2];
-    typename B::Map bmap;
+    ConvRow ra[NA];
+    uint32_t seg, lds_e[NA];
 
-    __device__ __forceinline__ ConvMap(const Int8ConvArgs& args, uint32_t row0, uint32_t col0, uint32_t t) : g(args), bmap(args.w, args.nb, args.e.n, col0, t) {
+    __device__ __forceinline__ ConvA(const Int8ConvArgs& args, uint32_t row0, uint32_t t) : g(args) {
         seg = t & 7u;
 #pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const uint32_t row = (t >> 3) + 32u * h, pix = min(row0 + row, g.e.m - 1u);
+        for (int h = 0; h < NA; h++) {
+            const uint32_t row = (t >> 3) + kQ8Slab * h, pix = min(row0 + row, g.e.m - 1u);
             const uint32_t n = fdiv(pix, g.ohw), rem = pix - n * g.ohw.d, oy = fdiv(rem, g.ow), ox = rem - oy * g.ow.d;
             ra[h].img = n * g.h;
             ra[h].iy0 = (int32_t)oy * g.sh - g.ph;
@@ -70,17 +69,34 @@ struct ConvMap {
         return *reinterpret_cast<const v4u*>(g.x + block * kQ8Block + 16u * (seg & 1u));
     }
 
+    // the thread's segment of channel block cb of tap `tap`, for each of its rows
+    __device__ __forceinline__ void load(uint32_t tap, uint32_t cb, v4u (&a)[NA]) const {
+        const uint32_t ky = fdiv(tap, g.fkw);
+        const int32_t dy = (int32_t)ky * g.dh, dx = (int32_t)(tap - ky * g.kw) * g.dw;
+#pragma unroll
+        for (int h = 0; h < NA; h++) a[h] = gather(ra[h], cb, dy, dx);
+    }
+};
+
+// Where a thread's share of a chunk lies.  In the stage: as in int8_gemm.hpp.  In global memory: B by its codec's map, A by the
+// decoded output pixels of its rows.
+template <typename B>
+struct ConvMap {
+    ConvA<2> a;
+    typename B::Map bmap;
+
+    __device__ __forceinline__ ConvMap(const Int8ConvArgs& g, uint32_t row0, uint32_t col0, uint32_t t) : a(g, row0, t), bmap(g.w, g.nb, g.e.n, col0, t) {}
+
     template <bool TAIL>
     __device__ __forceinline__ void load(uint32_t kb0, Q8Staged<B>& st) const {
-        uint32_t kb = kb0 + (seg >> 1);
-        if (TAIL) kb = min(kb, g.nb - 1u);                                       // a dead block: a live one's bytes, never multiplied
-        const uint32_t tap = fdiv(kb, g.fnbc), ky = fdiv(tap, g.fkw), cb = kb - tap * g.nbc;
-        const int32_t dy = (int32_t)ky * g.dh, dx = (int32_t)(tap - ky * g.kw) * g.dw;
-        st.a0 = gather(ra[0], cb, dy, dx); st.a1 = gather(ra[1], cb, dy, dx);
+        uint32_t kb = kb0 + (a.seg >> 1);
+        if (TAIL) kb = min(kb, a.g.nb - 1u);                                     // a dead block: a live one's bytes, never multiplied
+        const uint32_t tap = fdiv(kb, a.g.fnbc);
+        a.load(tap, kb - tap * a.g.nbc, st.a);
         bmap.template load<TAIL>(kb0, st.b);
     }
 
-    __device__ __forceinline__ void store(uint8_t* buf, const Q8Staged<B>& st) const { q8_store_staged<B>(buf, lds_e, bmap, st); }
+    __device__ __forceinline__ void store(uint8_t* buf, const Q8Staged<B>& st) const { q8_store_staged<B, 2>(buf, a.lds_e, bmap, st); }
 };
 
 template <typename B>
@@ -89,53 +105,80 @@ __global__ __launch_bounds__(kBlock, B::kMinBlocks) void q8_conv_kernel(const In
     q8_tile<B>(g.e, g.nb, stage, [&g](uint32_t row0, uint32_t col0, uint32_t t) { return ConvMap<B>(g, row0, col0, t); });
 }
 
+// a convolution as an entry point received it, and what the checks make of it
+struct ConvShape {
+    int64_t n, c, h, wd, o, kh, kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w;
+    int64_t oh, ow, nbc, m, blocks_x;             // nbc = ceil(c / 32); m = n oh ow rows; blocks_x = n h wd nbc blocks of x
+};
+
+// What the dense and the grouped entry point check about the geometry, in this order; `extra` are further sizes (groups, nbs) that
+// must lie in 0 .. 2^31 - 1.  Fills oh .. blocks_x; a product above 2^31 - 1 is left as -1 for the caller's own size check.
+inline int check_conv_shape(const char* what, ConvShape& z, std::initializer_list<int64_t> extra = {}) {
+    std::vector<int64_t> sizes = {z.n, z.c, z.h, z.wd, z.o, z.kh, z.kw, z.stride_h, z.stride_w, z.pad_h, z.pad_w, z.dil_h, z.dil_w};
+    sizes.insert(sizes.end(), extra);
+    for (int64_t v : sizes) {
+        if (v < 0) { set_error("%s: negative size", what); return PPQHIP_ERR_INVALID_VALUE; }
+        if (v > kQ8Max) { set_error("%s: a size above 2^31 - 1", what); return PPQHIP_ERR_INVALID_VALUE; }
+    }
+    if (z.kh < 1 || z.kw < 1) { set_error("%s: kernel size must be at least 1", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (z.stride_h < 1 || z.stride_w < 1) { set_error("%s: stride must be at least 1", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (z.dil_h < 1 || z.dil_w < 1) { set_error("%s: dilation must be at least 1", what); return PPQHIP_ERR_INVALID_VALUE; }
+    const int64_t span_h = z.h + 2 * z.pad_h - z.dil_h * (z.kh - 1) - 1, span_w = z.wd + 2 * z.pad_w - z.dil_w * (z.kw - 1) - 1;
+    if (span_h < 0 || span_w < 0) { set_error("%s: the kernel window does not fit the padded input: no output", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (z.h + 2 * z.pad_h > kQ8Max || z.wd + 2 * z.pad_w > kQ8Max) { set_error("%s: a padded size above 2^31 - 1", what); return PPQHIP_ERR_INVALID_VALUE; }
+    z.oh = span_h / z.stride_h + 1; z.ow = span_w / z.stride_w + 1;
+    z.nbc = (z.c + kQ8Block - 1) / kQ8Block;
+    z.m = bounded_product(z.n, z.oh);
+    if (z.m >= 0) z.m = bounded_product(z.m, z.ow);
+    z.blocks_x = bounded_product(z.n, z.h);
+    if (z.blocks_x >= 0) z.blocks_x = bounded_product(z.blocks_x, z.wd);
+    if (z.blocks_x >= 0) z.blocks_x = bounded_product(z.blocks_x, z.nbc);
+    return PPQHIP_OK;
+}
+
+// The rest of either entry point once its reduction is known: a row of the implicit GEMM has nb blocks, of which nbk belong to one
+// tap (the dense layer's nbc, the grouped one's nbs).  Checks the products, the operands' pointers and alignment, books, fills g (but
+// for its tail) and hands over to launch_q8_tiles<NA>; `more` are further inputs to check for overlaps.
+template <typename B, int NA, typename Launch>
+int launch_q8_conv(const char* what, KernelId id, const int8_t* x, const void* w, const Int8TailHost& t, const ConvShape& z, int64_t nbk,
+                   std::vector<Span> more, void* stream, Int8ConvArgs& g, Launch&& launch) {
+    int64_t nb = bounded_product(z.kh, z.kw);
+    if (nb >= 0) nb = bounded_product(nb, nbk);
+    if (z.m < 0 || nb < 0 || z.blocks_x < 0) { set_error("%s: a size above 2^31 - 1", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (z.n == 0 || z.o == 0) return PPQHIP_OK;
+    const bool read = z.blocks_x > 0 && nb > 0;                      // an input without a pixel or a channel: I is 0, nothing is read
+    if (read && (x == nullptr || w == nullptr)) { set_error("%s: null pointer", what); return PPQHIP_ERR_INVALID_VALUE; }
+    if (read && (!aligned16(x) || !aligned16(w))) { set_error("%s: operands, y and q must be 16-byte aligned", what); return PPQHIP_ERR_INVALID_VALUE; }
+    const int64_t kp = read ? nb * kQ8Block : 0, w_row = read ? nb * B::kBlockBytes : 0;
+    std::vector<Span> ins;
+    if (read && kp < kQ8MaxK) {
+        ins.push_back(span_of(x, z.blocks_x * kQ8Block)); ins.push_back(span_of(static_cast<const uint8_t*>(w), z.o * w_row));
+        ins.insert(ins.end(), more.begin(), more.end());
+    }
+    // booked: x once (a pixel is read by up to kh kw windows, from cache), w, the column data, every output and the residual
+    const double bytes = read ? (double)z.blocks_x * kQ8Block + (double)z.o * (double)w_row : 0.0;
+
+    g.x = reinterpret_cast<const uint8_t*>(x); g.w = static_cast<const uint8_t*>(w);
+    g.nb = read ? (uint32_t)nb : 0u; g.nbc = (uint32_t)z.nbc;
+    g.h = (uint32_t)z.h; g.wd = (uint32_t)z.wd; g.kw = (uint32_t)z.kw;
+    g.sh = (int32_t)z.stride_h; g.sw = (int32_t)z.stride_w; g.ph = (int32_t)z.pad_h; g.pw = (int32_t)z.pad_w;
+    g.dh = (int32_t)z.dil_h; g.dw = (int32_t)z.dil_w;
+    g.fill = 0x01010101u * ((uint32_t)t.zx & 0xffu);
+    g.ohw = make_fastdiv((uint32_t)(z.oh * z.ow)); g.ow = make_fastdiv((uint32_t)z.ow);
+    g.fnbc = make_fastdiv((uint32_t)std::max<int64_t>(nbk, 1)); g.fkw = make_fastdiv((uint32_t)z.kw);
+    return launch_q8_tiles<NA>(what, "y", id, t, z.m, z.o, kp, ins, bytes, stream, g.e, launch);
+}
+
 // the body of ppqhip_int8_conv2d / ppqhip_int4_conv2d: `what` names the entry point in its refusals, `id` books the launch
 template <typename B>
 int q8_conv(const char* what, KernelId id, const int8_t* x, const void* w, const Int8TailHost& t, int64_t n, int64_t c, int64_t h, int64_t wd,
             int64_t o, int64_t kh, int64_t kw, int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w,
             void* stream) {
     if (int st = check_int8_tail(what, "y", t)) return st;
-    const int64_t sizes[] = {n, c, h, wd, o, kh, kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w};
-    for (int64_t v : sizes) {
-        if (v < 0) { set_error("%s: negative size", what); return PPQHIP_ERR_INVALID_VALUE; }
-        if (v > kQ8Max) { set_error("%s: a size above 2^31 - 1", what); return PPQHIP_ERR_INVALID_VALUE; }
-    }
-    if (kh < 1 || kw < 1) { set_error("%s: kernel size must be at least 1", what); return PPQHIP_ERR_INVALID_VALUE; }
-    if (stride_h < 1 || stride_w < 1) { set_error("%s: stride must be at least 1", what); return PPQHIP_ERR_INVALID_VALUE; }
-    if (dil_h < 1 || dil_w < 1) { set_error("%s: dilation must be at least 1", what); return PPQHIP_ERR_INVALID_VALUE; }
-    const int64_t span_h = h + 2 * pad_h - dil_h * (kh - 1) - 1, span_w = wd + 2 * pad_w - dil_w * (kw - 1) - 1;
-    if (span_h < 0 || span_w < 0) { set_error("%s: the kernel window does not fit the padded input: no output", what); return PPQHIP_ERR_INVALID_VALUE; }
-    if (h + 2 * pad_h > kQ8Max || wd + 2 * pad_w > kQ8Max) { set_error("%s: a padded size above 2^31 - 1", what); return PPQHIP_ERR_INVALID_VALUE; }
-    const int64_t oh = span_h / stride_h + 1, ow = span_w / stride_w + 1;
-    const int64_t nbc = (c + kQ8Block - 1) / kQ8Block;
-    int64_t m = bounded_product(n, oh);
-    if (m >= 0) m = bounded_product(m, ow);
-    int64_t nb = bounded_product(kh, kw);
-    if (nb >= 0) nb = bounded_product(nb, nbc);
-    int64_t blocks_x = bounded_product(n, h);
-    if (blocks_x >= 0) blocks_x = bounded_product(blocks_x, wd);
-    if (blocks_x >= 0) blocks_x = bounded_product(blocks_x, nbc);
-    if (m < 0 || nb < 0 || blocks_x < 0) { set_error("%s: a size above 2^31 - 1", what); return PPQHIP_ERR_INVALID_VALUE; }
-    if (n == 0 || o == 0) return PPQHIP_OK;
-    const bool read = blocks_x > 0 && nb > 0;                        // an input without a pixel or a channel: I is 0, nothing is read
-    if (read && (x == nullptr || w == nullptr)) { set_error("%s: null pointer", what); return PPQHIP_ERR_INVALID_VALUE; }
-    if (read && (!aligned16(x) || !aligned16(w))) { set_error("%s: operands, y and q must be 16-byte aligned", what); return PPQHIP_ERR_INVALID_VALUE; }
-    const int64_t kp = read ? nb * kQ8Block : 0, w_row = read ? nb * B::kBlockBytes : 0;
-    std::vector<Span> ins;
-    if (read && kp < kQ8MaxK) { ins.push_back(span_of(x, blocks_x * kQ8Block)); ins.push_back(span_of(static_cast<const uint8_t*>(w), o * w_row)); }
-    // booked: x once (a pixel is read by up to kh kw windows, from cache), w, the column data, every output and the residual
-    const double bytes = read ? (double)blocks_x * kQ8Block + (double)o * (double)w_row : 0.0;
-
+    ConvShape z = {n, c, h, wd, o, kh, kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w};
+    if (int st = check_conv_shape(what, z)) return st;
     Int8ConvArgs g;
-    g.x = reinterpret_cast<const uint8_t*>(x); g.w = static_cast<const uint8_t*>(w);
-    g.nb = read ? (uint32_t)nb : 0u; g.nbc = (uint32_t)nbc;
-    g.h = (uint32_t)h; g.wd = (uint32_t)wd; g.kw = (uint32_t)kw;
-    g.sh = (int32_t)stride_h; g.sw = (int32_t)stride_w; g.ph = (int32_t)pad_h; g.pw = (int32_t)pad_w;
-    g.dh = (int32_t)dil_h; g.dw = (int32_t)dil_w;
-    g.fill = 0x01010101u * ((uint32_t)t.zx & 0xffu);
-    g.ohw = make_fastdiv((uint32_t)(oh * ow)); g.ow = make_fastdiv((uint32_t)ow);
-    g.fnbc = make_fastdiv((uint32_t)std::max<int64_t>(nbc, 1)); g.fkw = make_fastdiv((uint32_t)kw);
-    return launch_q8_tiles(what, "y", id, t, m, o, kp, ins, bytes, stream, g.e, [&g](uint32_t blocks, hipStream_t s) {
+    return launch_q8_conv<B, 2>(what, id, x, w, t, z, z.nbc, {}, stream, g, [&g](uint32_t blocks, hipStream_t s) {
         hipLaunchKernelGGL(q8_conv_kernel<B>, dim3(blocks), dim3(kBlock), 0, s, g);
     });
 }

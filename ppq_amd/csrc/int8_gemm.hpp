@@ -47,11 +47,11 @@ struct GemmMap {
     __device__ __forceinline__ void load(uint32_t kb0, Q8Staged<B>& st) const {
         const uint32_t eb = kb0 + (seg >> 1);
         const size_t off = (size_t)(TAIL ? min(eb, nb - 1u) : eb) * kQ8Block + 16u * (seg & 1u);
-        st.a0 = *reinterpret_cast<const v4u*>(ga[0] + off); st.a1 = *reinterpret_cast<const v4u*>(ga[1] + off);
+        st.a[0] = *reinterpret_cast<const v4u*>(ga[0] + off); st.a[1] = *reinterpret_cast<const v4u*>(ga[1] + off);
         bmap.template load<TAIL>(kb0, st.b);
     }
 
-    __device__ __forceinline__ void store(uint8_t* buf, const Q8Staged<B>& st) const { q8_store_staged<B>(buf, lds_e, bmap, st); }
+    __device__ __forceinline__ void store(uint8_t* buf, const Q8Staged<B>& st) const { q8_store_staged<B, 2>(buf, lds_e, bmap, st); }
 };
 
 template <typename B>

@@ -29,6 +29,11 @@
 // last readers are the MFMA reads of the last chunk, and every wave passes the barrier that ends that chunk, and the kernel's final
 // barrier after it, before any wave reaches its epilogue: no fragment read can follow a code write.  From there on a wave touches its
 // own slice only, so the waves that returned at the edge are not waited for (the pattern of fused_tiles in mx_int8_tile.hpp).
+//
+// The frame has ONE shape parameter, NA: the 16-byte segments of A a thread stages per chunk, of its rows t >> 3 + 32 h, h < NA.  The
+// four waves are NA along M and 4 / NA along N: NA = 2 is the 64 x 64 tile described above (every dense kernel); NA = 4 is 128 rows x
+// 32 columns, four waves stacked along M over ONE 32-row B stage -- the grouped convolution of int8_gconv.hpp, whose 32-column slices
+// each need input channels of their own, so that two wave columns could not share an A stage.
 #pragma once
 #include "common.hpp"
 #include "job_table.hpp"
@@ -46,13 +51,17 @@ constexpr uint32_t kQ8Edge = kQ8Tile * kQ8WaveTiles * kQ8Waves;                 
 constexpr uint32_t kQ8Block = 32;                                                // bytes of K per instruction; rows are padded to it
 constexpr uint32_t kQ8ChunkBlocks = 4;                                           // instructions of one row per chunk
 constexpr uint32_t kQ8Pitch = kQ8ChunkBlocks * kQ8Block + 16u;                   // 144: a staged row of 128 bytes, padded
-constexpr uint32_t kQ8TileBytes = kQ8Edge * kQ8Pitch;                            // 64 rows of one operand
+constexpr uint32_t kQ8Slab = 32;                                                 // rows between a thread's segments: 256 threads / 8 segments a row
+template <int NA> constexpr uint32_t kQ8Rows = kQ8Slab * NA;                     // rows of the result per workgroup: NA waves of 32 ...
+template <int NA> constexpr uint32_t kQ8Cols = kQ8Slab * (kQ8Waves * kQ8Waves / NA);         // ... and its columns: 32 per wave along N
+template <int NA> constexpr uint32_t kQ8TileBytes = kQ8Rows<NA> * kQ8Pitch;      // the staged rows of A
 constexpr uint32_t kQ4BlockBytes = kQ8Block / 2u;                                // an int4 B row: 16 bytes per block of 32 k
 constexpr uint32_t kQ4Pitch = kQ8ChunkBlocks * kQ4BlockBytes + 16u;              // 80: a staged int4 row of 64 bytes, padded
 constexpr uint32_t kQ8CodeBytes = (kQ8WaveTiles * kQ8Tile) * (kQ8WaveTiles * kQ8Tile);       // a wave's 32 rows of 32 codes
 constexpr int64_t kQ8MaxK = 65536;                                               // padded reduction lengths from here on are refused
 constexpr int64_t kQ8Max = 0x7fffffffLL;
 static_assert(kQ8Waves * kQ8Waves * kWave == kBlock, "four waves per workgroup");
+static_assert(kQ8Rows<2> == kQ8Edge && kQ8Cols<2> == kQ8Edge && kQ8Rows<4> == 128u && kQ8Cols<4> == 32u, "the two shapes of the frame");
 static_assert(kQ8Pitch % 16u == 0 && kQ4Pitch % 16u == 0, "16-byte stores into the stage");
 static_assert(kQ8Edge * kQ8ChunkBlocks * kQ8Block == 2u * 16u * (uint32_t)kBlock, "two 16-byte loads per thread and int8 operand");
 static_assert(kQ8Edge * kQ8ChunkBlocks * kQ4BlockBytes == 16u * (uint32_t)kBlock, "one 16-byte load per thread of an int4 B");
@@ -79,21 +88,24 @@ struct Int8Tail {
 // ---- the B operand: how a weight lies in global memory, how a chunk of it is staged and how a lane reads its fragment ---------------
 // A codec B has: kBlockBytes, the bytes of a row per block of 32 k; kPitch, the pitch of a staged row; kShift, log2 of what its
 // fragments are scaled by (the accumulators then hold I << kShift); kMinBlocks, the workgroups per CU its kernels are bounded to;
-// Regs, what a thread carries of a chunk; Map, where a thread's share lies -- Map(b, nb, n, col0, t) for the rows col0 .. col0 + 63 (clamped to n - 1) of b [n, nb * kBlockBytes], load<TAIL>(kb0, regs)
+// kRows, the rows it stages (the workgroup's columns of the result);
+// Regs, what a thread carries of a chunk; Map, where a thread's share lies -- Map(b, nb, n, col0, t) for the rows col0 .. col0 + kRows - 1 (clamped to n - 1) of b [n, nb * kBlockBytes], load<TAIL>(kb0, regs)
 // as in q8_k_loop, store(stage, regs) into the B stage --; frag(row, b, grp): the 8 bytes 8 grp .. + 7 of block b of a staged row.
 
-// int8 codes as they are: segment t & 7 (16 bytes; block (t & 7) >> 1 of the chunk) of rows t >> 3 and 32 + (t >> 3)
-struct Q8B8 {
-    static constexpr uint32_t kBlockBytes = kQ8Block, kPitch = kQ8Pitch;
+// int8 codes as they are: segment t & 7 (16 bytes; block (t & 7) >> 1 of the chunk) of rows t >> 3 + 32 h, h < NB: 64 rows (Q8B8, the
+// dense kernels) or 32 (the grouped convolution)
+template <int NB>
+struct Q8B8Rows {
+    static constexpr uint32_t kBlockBytes = kQ8Block, kPitch = kQ8Pitch, kRows = kQ8Slab * NB;
     static constexpr int kShift = 0, kMinBlocks = 1;
-    struct Regs { v4u b0, b1; };
+    struct Regs { v4u b[NB]; };
     struct Map {
-        const uint8_t* gb[2]; uint32_t seg, lds_e[2], nb;
+        const uint8_t* gb[NB]; uint32_t seg, lds_e[NB], nb;
         __device__ __forceinline__ Map(const uint8_t* b, uint32_t nblocks, uint32_t n, uint32_t col0, uint32_t t) {
             nb = nblocks; seg = t & 7u;
 #pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const uint32_t row = (t >> 3) + 32u * h;
+            for (int h = 0; h < NB; h++) {
+                const uint32_t row = (t >> 3) + kQ8Slab * h;
                 gb[h] = b + min(col0 + row, n - 1u) * ((size_t)nb * kBlockBytes);
                 lds_e[h] = row * kPitch + seg * 16u;
             }
@@ -102,16 +114,19 @@ struct Q8B8 {
         __device__ __forceinline__ void load(uint32_t kb0, Regs& st) const {
             const uint32_t eb = kb0 + (seg >> 1);
             const size_t off = (size_t)(TAIL ? min(eb, nb - 1u) : eb) * kBlockBytes + 16u * (seg & 1u);
-            st.b0 = *reinterpret_cast<const v4u*>(gb[0] + off); st.b1 = *reinterpret_cast<const v4u*>(gb[1] + off);
+#pragma unroll
+            for (int h = 0; h < NB; h++) st.b[h] = *reinterpret_cast<const v4u*>(gb[h] + off);
         }
         __device__ __forceinline__ void store(uint8_t* stage, const Regs& st) const {
-            *reinterpret_cast<v4u*>(stage + lds_e[0]) = st.b0; *reinterpret_cast<v4u*>(stage + lds_e[1]) = st.b1;
+#pragma unroll
+            for (int h = 0; h < NB; h++) *reinterpret_cast<v4u*>(stage + lds_e[h]) = st.b[h];
         }
     };
     static __device__ __forceinline__ long frag(const uint8_t* row, uint32_t b, uint32_t grp) {
         return *reinterpret_cast<const long*>(row + b * kBlockBytes + grp * 8u);
     }
 };
+using Q8B8 = Q8B8Rows<2>;
 
 // int4 codes, two per byte: of every 8 consecutive k (group g) byte 4 g + j holds code 8 g + j in bits 0 .. 3
 // and code 8 g + 4 + j in bits 4 .. 7, two's complement.  A chunk of 64 rows is 4096 bytes: ONE 16-byte load per thread, block t & 3 of
@@ -121,7 +136,7 @@ struct Q8B8 {
 // Pitch 80 bytes = 20 dwords: 20 r mod 64, r = 0 .. 15, are the 16 multiples of 4 below 64, each once, so the dwords 20 r + 4 b + grp of
 // the 64 lanes of a fragment read lie in 64 different banks; 80 keeps the 16-byte stores aligned.
 struct Q8B4 {
-    static constexpr uint32_t kBlockBytes = kQ4BlockBytes, kPitch = kQ4Pitch;
+    static constexpr uint32_t kBlockBytes = kQ4BlockBytes, kPitch = kQ4Pitch, kRows = kQ8Edge;
     static constexpr int kShift = 4, kMinBlocks = 4;          // without the bound the allocator takes 132 registers: 3 workgroups a CU, not Q8B8's 4
     struct Regs { v4u b; };
     struct Map {
@@ -145,33 +160,34 @@ struct Q8B4 {
     }
 };
 
-// one buffer of the double-buffered stage: 64 rows of A at pitch 144, then 64 rows of B at the codec's pitch
-template <typename B> constexpr uint32_t kQ8BufBytes = kQ8TileBytes + kQ8Edge * B::kPitch;
-static_assert(kQ8Waves * kQ8Waves * kQ8CodeBytes <= kQ8BufBytes<Q8B8> && kQ8Waves * kQ8Waves * kQ8CodeBytes <= kQ8BufBytes<Q8B4>,
-              "the four waves' code stages fit the first operand buffer");
+// one buffer of the double-buffered stage: the 32 NA rows of A at pitch 144, then the codec's rows of B at its pitch
+template <typename B, int NA = 2> constexpr uint32_t kQ8BufBytes = kQ8TileBytes<NA> + B::kRows * B::kPitch;
+static_assert(kQ8Waves * kQ8Waves * kQ8CodeBytes <= kQ8BufBytes<Q8B8> && kQ8Waves * kQ8Waves * kQ8CodeBytes <= kQ8BufBytes<Q8B4> &&
+              kQ8Waves * kQ8Waves * kQ8CodeBytes <= kQ8BufBytes<Q8B8Rows<1>, 4>, "the four waves' code stages fit the first operand buffer");
 
-// what a thread carries from global memory to LDS for one chunk: of A its segment t & 7 (16 bytes) of rows t >> 3 and 32 + (t >> 3)
-template <typename B>
+// what a thread carries from global memory to LDS for one chunk: of A its segment t & 7 (16 bytes) of rows t >> 3 + 32 h, h < NA
+template <typename B, int NA = 2>
 struct Q8Staged {
-    v4u a0, a1;
+    v4u a[NA];
     typename B::Regs b;
 };
 
-// A into its stage at the thread's two places, B through its map
-template <typename B>
-__device__ __forceinline__ void q8_store_staged(uint8_t* buf, const uint32_t (&lds_e)[2], const typename B::Map& bmap, const Q8Staged<B>& st) {
-    *reinterpret_cast<v4u*>(buf + lds_e[0]) = st.a0; *reinterpret_cast<v4u*>(buf + lds_e[1]) = st.a1;
-    bmap.store(buf + kQ8TileBytes, st.b);
+// A into its stage at the thread's NA places, B through its map
+template <typename B, int NA>
+__device__ __forceinline__ void q8_store_staged(uint8_t* buf, const uint32_t (&lds_e)[NA], const typename B::Map& bmap, const Q8Staged<B, NA>& st) {
+#pragma unroll
+    for (int h = 0; h < NA; h++) *reinterpret_cast<v4u*>(buf + lds_e[h]) = st.a[h];
+    bmap.store(buf + kQ8TileBytes<NA>, st.b);
 }
 
 // The wave's 2 x 2 tiles over the `live` (1 .. 4; 4 unless TAIL) blocks of the chunk staged in buf: per block four fragment reads
 // from LDS (8 bytes of A, B as its codec reads it) and four MFMAs, each chained through its accumulator.
-template <bool TAIL, typename B>
+template <bool TAIL, typename B, int NA>
 __device__ __forceinline__ void q8_chunk(const uint8_t* buf, uint32_t wm, uint32_t wn, uint32_t r, uint32_t grp, uint32_t live,
                                          v4i (&acc)[kQ8WaveTiles][kQ8WaveTiles]) {
     constexpr int T = kQ8WaveTiles;
     const uint8_t* la = buf + (wm + r) * kQ8Pitch + grp * 8u;
-    const uint8_t* lb = buf + kQ8TileBytes + (wn + r) * B::kPitch;
+    const uint8_t* lb = buf + kQ8TileBytes<NA> + (wn + r) * B::kPitch;
 #pragma unroll
     for (uint32_t b = 0; b < kQ8ChunkBlocks; b++) {
         if (TAIL && b >= live) break;                                            // wave-uniform
@@ -191,11 +207,11 @@ __device__ __forceinline__ void q8_chunk(const uint8_t* buf, uint32_t wm, uint32
 // The K loop of both kernels over nb >= 1 blocks of 32 bytes.  A Map knows where a thread's share of a chunk lies: load<TAIL>(kb0, st)
 // issues the global loads of the chunk that starts at block kb0 (TAIL: the chunk holds fewer than 4 live blocks; a dead one is not
 // multiplied and its address is clamped), store(buf, st) puts them into the stage.  A wave past the edge (!busy) only stages.
-template <typename B, typename Map>
-__device__ __forceinline__ void q8_k_loop(const Map& map, uint8_t (&stage)[2][kQ8BufBytes<B>], uint32_t nb, bool busy, uint32_t wm, uint32_t wn,
+template <typename B, int NA, typename Map>
+__device__ __forceinline__ void q8_k_loop(const Map& map, uint8_t (&stage)[2][kQ8BufBytes<B, NA>], uint32_t nb, bool busy, uint32_t wm, uint32_t wn,
                                           uint32_t r, uint32_t grp, v4i (&acc)[kQ8WaveTiles][kQ8WaveTiles]) {
     const uint32_t chunks = (nb + kQ8ChunkBlocks - 1u) / kQ8ChunkBlocks, rest = nb % kQ8ChunkBlocks;
-    Q8Staged<B> st;
+    Q8Staged<B, NA> st;
     if (chunks == 1u && rest) map.template load<true>(0u, st); else map.template load<false>(0u, st);
     map.store(stage[0], st);
     __syncthreads();
@@ -205,8 +221,8 @@ __device__ __forceinline__ void q8_k_loop(const Map& map, uint8_t (&stage)[2][kQ
             if (last_short) map.template load<true>((c + 1u) * kQ8ChunkBlocks, st); else map.template load<false>((c + 1u) * kQ8ChunkBlocks, st);
         }
         if (busy) {
-            if (!more && rest) q8_chunk<true, B>(stage[c & 1u], wm, wn, r, grp, rest, acc);
-            else q8_chunk<false, B>(stage[c & 1u], wm, wn, r, grp, kQ8ChunkBlocks, acc);
+            if (!more && rest) q8_chunk<true, B, NA>(stage[c & 1u], wm, wn, r, grp, rest, acc);
+            else q8_chunk<false, B, NA>(stage[c & 1u], wm, wn, r, grp, kQ8ChunkBlocks, acc);
         }
         if (more) map.store(stage[(c + 1u) & 1u], st);                           // last read before the barrier that ended chunk c - 1
         __syncthreads();
@@ -289,21 +305,24 @@ __device__ __forceinline__ void q8_epilogue(const v4i (&acc)[kQ8WaveTiles][kQ8Wa
 
 // what a kernel does around its Map: the wave's place, the accumulators, the K loop, the final barrier and the epilogue.  Where the
 // codec's fragments are scaled the accumulators end as I << kShift, a multiple of 2^kShift: the arithmetic shift back is exact.
-template <typename B, typename MakeMap>
-__device__ __forceinline__ void q8_tile(const Int8Tail& e, uint32_t nb, uint8_t (&stage)[2][kQ8BufBytes<B>], MakeMap&& make_map) {
+// Consecutive workgroups walk the column tiles of one row tile: tiles_n is the fast index.
+template <typename B, int NA = 2, typename MakeMap>
+__device__ __forceinline__ void q8_tile(const Int8Tail& e, uint32_t nb, uint8_t (&stage)[2][kQ8BufBytes<B, NA>], MakeMap&& make_map) {
     constexpr int T = kQ8WaveTiles;
+    constexpr uint32_t WN = kQ8Cols<NA> / kQ8Slab;                               // waves along N
+    static_assert(B::kRows == kQ8Cols<NA>, "the codec stages the workgroup's columns");
     const uint32_t tm = fdiv(blockIdx.x, e.tiles_n), tn = blockIdx.x - tm * e.tiles_n.d;
     const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
     const uint32_t r = lane & 15u, grp = lane >> 4;
-    const uint32_t row0 = tm * kQ8Edge, col0 = tn * kQ8Edge;
-    const uint32_t wm = (wave / kQ8Waves) * (T * kQ8Tile), wn = (wave % kQ8Waves) * (T * kQ8Tile);
+    const uint32_t row0 = tm * kQ8Rows<NA>, col0 = tn * kQ8Cols<NA>;
+    const uint32_t wm = (wave / WN) * (T * kQ8Tile), wn = (wave % WN) * (T * kQ8Tile);
     const bool busy = row0 + wm < e.m && col0 + wn < e.n;                        // wave-uniform: a wave past the edge only stages
 
     v4i acc[T][T];
     q8_start<B::kShift>(e, col0 + wn, r, acc);
     if (nb > 0u) {                                                               // nb == 0: the operands may be null
         const auto map = make_map(row0, col0, t);
-        q8_k_loop<B>(map, stage, nb, busy, wm, wn, r, grp, acc);
+        q8_k_loop<B, NA>(map, stage, nb, busy, wm, wn, r, grp, acc);
     }
     __syncthreads();
     if (!busy) return;
@@ -379,11 +398,11 @@ inline int launch_q8(const char* what, const char* float_name, KernelId id, cons
     return finish_launch(what);
 }
 
-// launch_q8 for the kernels of q8_tile: one workgroup per 64 x 64 tile of the result
-template <typename Launch>
+// launch_q8 for the kernels of q8_tile<B, NA>: one workgroup per tile of the result, 64 x 64 (NA = 2) or 128 x 32 (NA = 4)
+template <int NA = 2, typename Launch>
 inline int launch_q8_tiles(const char* what, const char* float_name, KernelId id, const Int8TailHost& h, int64_t m, int64_t n, int64_t kp,
                            std::vector<Span>& ins, double bytes, void* stream, Int8Tail& e, Launch&& launch) {
-    const int64_t tiles_m = (m + kQ8Edge - 1) / kQ8Edge, tiles_n = (n + kQ8Edge - 1) / kQ8Edge;
+    const int64_t tiles_m = (m + kQ8Rows<NA> - 1) / kQ8Rows<NA>, tiles_n = (n + kQ8Cols<NA> - 1) / kQ8Cols<NA>;
     e.tiles_n = make_fastdiv((uint32_t)tiles_n);
     return launch_q8(what, float_name, id, h, m, n, kp, tiles_m * tiles_n, ins, bytes, stream, e, launch);
 }

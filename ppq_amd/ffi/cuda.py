@@ -5,7 +5,8 @@ from .. import ffi as _package     # public entry points are called through the 
 from .._lib import lib
 from ._base import _KERNEL_FAILURE, _DeviceOf, _check, _f32, _ptr, _raise, _stream
 from .extension import HIP_EXTENSION
-from .int8 import int8_conv2d as _int8_conv2d, int8_depthwise_conv2d as _int8_depthwise_conv2d, int8_matmul as _int8_matmul
+from .int8 import (int8_conv2d as _int8_conv2d, int8_depthwise_conv2d as _int8_depthwise_conv2d, int8_grouped_conv2d as _int8_grouped_conv2d,
+                   int8_matmul as _int8_matmul)
 from .mx import (MX_BLOCK, _mx_axis, _mx_codes_like, _mx_conv_args, _mx_dense, _mx_fused_args, _mx_fused_outputs, _mx_geometry,
                  _mx_int8_conv_args, _mx_int8_fused_args, _mx_int8_matmul_args, _mx_matmul_args, mx_format_arg, mx_format_id, mx_packed_shapes)
 from .seam import CUDA_COMPLIER
@@ -503,6 +504,15 @@ class CUDA:
         ``x [N, H, W, Cp]``, ``w [kh, kw, Cp]`` int8 codes, ``w_sums`` / ``mul`` / ``bias`` ``[c]``.  ``(y, q)``: float32
         ``[N, c, OH, OW]`` with channels-last strides, int8 ``[N, OH, OW, Cp]``.  The bits of ``tests/int8_depthwise_reference.py``."""
         return _int8_depthwise_conv2d(x, w, w_sums, zx, mul, c, bias, stride, padding, dilation, residual, relu, out_float, out_q)
+
+    @ staticmethod
+    def Int8GroupedConv2d(x, w, w_sums, zx: int, mul, c: int, groups: int, nbs: int, cb0, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1),
+                          residual=None, relu: bool = False, out_float: bool = True, out_q=None):
+        """``Int8Conv2d`` for a grouped layer, on the int8 MFMA with a 128 x 32 tile per slice of 32 output
+        channels: ``x [N, H, W, Cp]``, ``w [O, kh, kw, 32 nbs]`` int8 codes in the layout of ``int8_grouped_weight``, ``cb0`` int32
+        ``[ceil(O / 32)]`` the first channel block of each slice.  ``(y, q)`` as ``Int8Conv2d`` returns them, with the bits of
+        ``Int8Conv2d`` on the block-diagonal dense weight.  The bits of ``tests/int8_grouped_reference.py``."""
+        return _int8_grouped_conv2d(x, w, w_sums, zx, mul, c, groups, nbs, cb0, bias, stride, padding, dilation, residual, relu, out_float, out_q)
 
     @ staticmethod
     def Sync():

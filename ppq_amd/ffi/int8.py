@@ -1,8 +1,9 @@
 """The bindings of the linear INT8 kernels (``csrc/int8_gemm.hip``, ``csrc/int8_conv.hip``) and of their forms
 with a packed INT4 weight (``csrc/int4_gemm.hip``, ``csrc/int4_conv.hip``; section 9.23): ``CUDA.Int8Matmul`` / ``Int8Conv2d`` /
-``Int4Matmul`` / ``Int4Conv2d`` forward here, and ``Int8DepthwiseConv2d`` to the depthwise kernel (``csrc/int8_dwconv.hip``; section
-9.24).  Operands are int8 codes with the reduction axis last and padded to a multiple of 32; an INT4 weight is uint8, two codes per
-byte, half as many bytes along that axis; a depthwise weight is ``[kh, kw, Cp]``."""
+``Int4Matmul`` / ``Int4Conv2d`` forward here, ``Int8DepthwiseConv2d`` to the depthwise kernel (``csrc/int8_dwconv.hip``; section
+9.24) and ``Int8GroupedConv2d`` to the grouped one (``csrc/int8_gconv.hip``; section 9.25).  Operands are int8 codes with the reduction
+axis last and padded to a multiple of 32; an INT4 weight is uint8, two codes per byte, half as many bytes along that axis; a depthwise
+weight is ``[kh, kw, Cp]``, a grouped one ``[O, kh, kw, 32 nbs]``."""
 import torch
 
 from .._lib import lib
@@ -15,10 +16,10 @@ DEPTHWISE_LDS_BYTES = 65536      # what a workgroup of the depthwise kernel may 
 def _refuse(what: str): raise RuntimeError(_KERNEL_FAILURE + what)
 
 
-def _int8_operands(rank, names, operands, int4=False):
+def _int8_operands(rank, names, operands, int4=False, same_k=True):
     """int8 -- with ``int4`` the second one uint8, two codes per byte --, on one GPU, ``rank``-d (a pair: one rank each), contiguous,
-    the last axis a multiple of 32 codes and the same for both; a tensor whose data does not start on a 16-byte boundary is copied
-    (the allocator aligns)."""
+    the last axis a multiple of 32 codes and (``same_k``) the same for both; a tensor whose data does not start on a 16-byte boundary
+    is copied (the allocator aligns)."""
     dev, out = operands[0].device if isinstance(operands[0], torch.Tensor) else None, []
     for name, t, per_byte, rank in zip(names, operands, (1, 2 if int4 else 1), rank if isinstance(rank, tuple) else (rank, rank)):
         if per_byte == 2: _check(t, torch.uint8, f'{name}(Expect to be UINT8: packed INT4)')
@@ -28,7 +29,7 @@ def _int8_operands(rank, names, operands, int4=False):
         if not t.is_contiguous(): _refuse(f'{name} must be contiguous')
         if t.shape[-1] * per_byte % INT8_BLOCK: _refuse(f'{name}: the last axis ({t.shape[-1] * per_byte} codes) must be padded to a multiple of {INT8_BLOCK}')
         out.append(t.clone() if t.data_ptr() % 16 else t)
-    if out[0].shape[-1] != out[1].shape[-1] * (2 if int4 else 1):
+    if same_k and out[0].shape[-1] != out[1].shape[-1] * (2 if int4 else 1):
         _refuse(f'{names[0]} and {names[1]} differ in their last axis: {out[0].shape[-1]} and {out[1].shape[-1] * (2 if int4 else 1)}' + (' codes' if int4 else ''))
     return out
 
@@ -131,4 +132,34 @@ def int8_depthwise_conv2d(x, w, w_sums, zx: int, mul, c: int, bias=None, stride=
     with _DeviceOf(x):
         _raise(lib.ppqhip_int8_dwconv2d(x.data_ptr(), w.data_ptr(), _ptr(sums), zx, mul.data_ptr(), _ptr(bias), _ptr(residual), 1 if relu else 0, _ptr(y),
                                         _ptr(q), *grid, n, c, h, wd, kh, kw, sh, sw, ph, pw, dh, dw, _stream()))
+    return (y.permute(0, 3, 1, 2) if y is not None else None), q
+
+
+def int8_grouped_conv2d(x, w, w_sums, zx: int, mul, c: int, groups: int, nbs: int, cb0, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1),
+                        residual=None, relu: bool = False, out_float: bool = True, out_q=None):
+    """``ppqhip_int8_gconv2d``: ``x [N, H, W, Cp]`` int8 codes of ``c`` channels and ``w [O, kh, kw, 32 nbs]`` the grouped weight as
+    ``int8_grouped_weight`` lays it out for ``groups`` groups -- block ``j`` of a tap of row ``o`` is channel block ``cb0[o // 32] + j``,
+    zero outside the row's own group --, ``cb0`` int32 ``[ceil(O / 32)]``, ``w_sums`` / ``mul`` / ``bias`` ``[O]``.  ``residual`` is
+    ``[N, O, OH, OW]``; a tensor that is not channels-last is copied into that layout.  Returns ``(y, q)``: float32 ``[N, O, OH, OW]``
+    with channels-last strides and int8 ``[N, OH, OW, ceil32(O)]``.  Refused like ``int8_conv2d``, and groups that do not divide ``c``
+    and ``O``."""
+    x, w = _int8_operands(4, ('x', 'w'), (x, w), same_k=False)
+    c, groups, nbs = int(c), int(groups), int(nbs)
+    if not 0 < c <= x.shape[-1] or x.shape[-1] - c >= INT8_BLOCK: _refuse(f'c = {c} does not pad to the {x.shape[-1]} stored channels')
+    (n, h, wd, _), (o, kh, kw, wk) = x.shape, w.shape
+    if groups < 1 or c % groups or o % groups: _refuse(f'c = {c} and o = {o} must both be multiples of groups = {groups}')
+    if nbs < 1 or wk != nbs * INT8_BLOCK: _refuse(f'w stores {wk} codes per tap, expected {INT8_BLOCK} * nbs = {nbs * INT8_BLOCK}')
+    slices = (o + INT8_BLOCK - 1) // INT8_BLOCK
+    _check(cb0, torch.int32, 'cb0(Expect to be INT32)')
+    if list(cb0.shape) != [slices] or cb0.device != x.device: _refuse(f'cb0 of shape {list(cb0.shape)} on {cb0.device}, expected [{slices}] on {x.device}')
+    (sh, sw), (ph, pw), (dh, dw) = ([int(v) for v in pair] for pair in (stride, padding, dilation))
+    if min(sh, sw, dh, dw) < 1 or min(ph, pw) < 0: _refuse(f'stride {(sh, sw)} and dilation {(dh, dw)} must be at least 1, padding {(ph, pw)} at least 0')
+    oh, ow = (h + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (wd + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    if oh < 1 or ow < 1: _refuse(f'a {kh} x {kw} kernel with dilation {(dh, dw)} does not fit an input of {h} x {wd} padded by {(ph, pw)}')
+    if residual is not None and isinstance(residual, torch.Tensor) and residual.dim() == 4: residual = residual.permute(0, 2, 3, 1)
+    sums, zx, mul, bias, residual, y, q, grid = _int8_tail(o, [n, oh, ow, o], x.device, w_sums, zx, mul, bias, residual, out_float, out_q)
+    cb0 = cb0.contiguous()
+    with _DeviceOf(x):
+        _raise(lib.ppqhip_int8_gconv2d(x.data_ptr(), w.data_ptr(), _ptr(sums), zx, mul.data_ptr(), _ptr(bias), _ptr(residual), 1 if relu else 0, _ptr(y),
+                                       _ptr(q), *grid, n, c, h, wd, o, kh, kw, sh, sw, ph, pw, dh, dw, groups, nbs, cb0.data_ptr(), _stream()))
     return (y.permute(0, 3, 1, 2) if y is not None else None), q

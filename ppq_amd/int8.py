@@ -18,6 +18,10 @@ it takes a weight.  The layer then has the bits of the int8 layer on the same co
 A depthwise convolution (groups == C, channel multiplier 1; section 9.24) has no reduction over channels for the MFMA: the sum over
 ``k`` is the sum over the taps of one channel, and ``int8_depthwise_conv2d_packed`` runs it on ``v_dot4c_i32_i8``
 (``csrc/int8_dwconv.hip``) on an ``Int8DepthwiseWeight``, with the same tail and the bits of the dense layer on the block-diagonal weight.
+
+Every other grouped convolution (1 < groups < C, or a channel multiplier; section 9.25) runs on the int8 MFMA again:
+``int8_grouped_conv2d_packed`` on an ``Int8GroupedWeight`` (``csrc/int8_gconv.hip``), whose rows hold only the channel blocks their
+slice of 32 output channels needs -- the bits of the dense layer on the block-diagonal weight at 1 / groups of its work.
 """
 from typing import Optional
 
@@ -29,7 +33,8 @@ from .mx import _pair, relu_positive_zero
 from .round import ppq_tensor_round
 
 __all__ = ['Int8Tensor', 'Int4Weight', 'int8_quantize', 'int8_dequantize', 'int4_quantize_weight', 'int4_pack', 'int4_unpack', 'int8_matmul', 'int8_linear',
-           'int8_conv2d_packed', 'int8_conv2d', 'Int8DepthwiseWeight', 'int8_depthwise_weight', 'int8_depthwise_conv2d_packed', 'int8_depthwise_conv2d']
+           'int8_conv2d_packed', 'int8_conv2d', 'Int8DepthwiseWeight', 'int8_depthwise_weight', 'int8_depthwise_conv2d_packed', 'int8_depthwise_conv2d',
+           'Int8GroupedWeight', 'int8_grouped_weight', 'int8_grouped_conv2d_packed', 'int8_grouped_conv2d']
 
 MAX_KP = 65536           # padded reduction lengths from here on are refused: |I| could leave int32
 
@@ -95,6 +100,41 @@ class Int8DepthwiseWeight:
         """``code * scale`` in float32 ``[C, 1, kh, kw]``."""
         codes = self.values[..., :self.shape[0]].permute(2, 0, 1).unsqueeze(1).to(torch.float32)
         return codes * (self.scale.reshape(-1, 1, 1, 1) if self.scale.numel() > 1 else self.scale)
+
+
+class Int8GroupedWeight:
+    """int8 codes of a symmetric grouped weight of ``shape`` ``(O, C_g, kh, kw)`` for ``groups`` groups, laid out for
+    ``csrc/int8_gconv.hip``: ``values`` int8 ``[O, kh, kw, 32 nbs]``, block ``j`` of a tap of row ``o`` holding the codes of ``w[o]`` for
+    the input channels ``32 (cb0[o // 32] + j) .. + 31`` -- the channels of the row's own group in their places, code 0 everywhere else.
+    ``cb0``: int32 ``[ceil(O / 32)]``, the first channel block the slice of output channels ``32 s .. 32 s + 31`` reads; ``nbs``: the
+    most channel blocks any slice reads.  ``scale``: float32, a scalar tensor or ``[O]``; ``sums``: int32 ``[O]``, the sum of a row's
+    codes; ``qmin``, ``qmax``, ``rounding`` as in ``Int8Tensor``; ``zero_point`` is 0."""
+    __slots__ = ('values', 'shape', 'groups', 'nbs', 'cb0', 'scale', 'qmin', 'qmax', 'rounding', 'sums')
+    zero_point = 0
+
+    def __init__(self, values, shape, groups, nbs, cb0, scale, qmin, qmax, rounding, sums):
+        self.values, self.shape, self.groups, self.nbs, self.cb0 = values, tuple(int(d) for d in shape), int(groups), int(nbs), cb0
+        self.scale, self.qmin, self.qmax, self.rounding, self.sums = scale, int(qmin), int(qmax), int(rounding), sums
+
+    @ property
+    def device(self): return self.values.device
+
+    def codes(self) -> torch.Tensor:
+        """The codes of the rows' own groups, int8 ``[O, kh, kw, C_g]``."""
+        return self.values.gather(3, _grouped_places(self.shape, self.groups, self.cb0).expand(-1, *self.shape[2:], -1))
+
+    def dequantize(self) -> torch.Tensor:
+        """``code * scale`` in float32 ``[O, C_g, kh, kw]``."""
+        return self.codes().permute(0, 3, 1, 2).to(torch.float32) * (self.scale.reshape(-1, 1, 1, 1) if self.scale.numel() > 1 else self.scale)
+
+
+def _grouped_places(shape, groups: int, cb0: torch.Tensor) -> torch.Tensor:
+    """Where the ``C_g`` codes of a tap of row ``o`` lie in its ``32 nbs`` stored ones: int64 ``[O, 1, 1, C_g]``, channel
+    ``(o // O_g) C_g + i`` relative to the first channel of the row's slice, ``32 cb0[o // 32]``."""
+    o, cg = shape[0], shape[1]
+    rows = torch.arange(o, device=cb0.device)
+    first = torch.div(rows, o // groups, rounding_mode='floor') * cg - INT8_BLOCK * cb0.to(torch.int64)[torch.div(rows, INT8_BLOCK, rounding_mode='floor')]
+    return (first[:, None] + torch.arange(cg, device=cb0.device)).reshape(o, 1, 1, cg)
 
 
 def _grid(what: str, config):
@@ -384,11 +424,89 @@ def int8_depthwise_conv2d(x: torch.Tensor, weight: Int8DepthwiseWeight, x_config
                                         out_config, out_float, use_kernels)
 
 
+def int8_grouped_weight(tensor: torch.Tensor, config, groups: int, use_kernels: bool = True) -> Int8GroupedWeight:
+    """The codes of the float32 grouped weight ``tensor`` ``[O, C_g, kh, kw]`` of a convolution with ``groups`` groups under ``config`` --
+    ``int8_quantize(..., weight=True)``'s, per tensor or per output channel, with its refusals under this name --, re-laid as an
+    ``Int8GroupedWeight`` (torch ops, done once).  ``groups == 1`` and a depthwise weight are laid out like any other, though
+    ``int8_conv2d_packed`` and ``int8_depthwise_conv2d_packed`` are the fast paths for them.  Refused too: an ``Int4Weight`` (INT4 grouped
+    weights are not supported), ``groups`` that do not divide ``O``."""
+    what = 'int8_grouped_weight'
+    if isinstance(tensor, Int4Weight): raise TypeError(f'{what}: INT4 grouped weights are not supported: got an Int4Weight')
+    if not isinstance(tensor, torch.Tensor) or tensor.dim() != 4: raise RuntimeError(f'{what}: expected a [O, C_g, kh, kw] weight, got shape {list(getattr(tensor, "shape", []))}')
+    groups, (o, cg) = int(groups), tensor.shape[:2]
+    if groups < 1 or o % groups: raise RuntimeError(f'{what}: {groups} groups do not divide the {o} output channels')
+    t = int8_quantize(tensor, config, 1, weight=True, use_kernels=use_kernels, what=what)             # [O, kh, kw, ceil32(C_g)]
+    # slice s (outputs 32 s .. 32 s + 31) reads the channels of its first to its last group, rounded outwards to blocks of 32
+    og, starts = o // groups, range(0, o, INT8_BLOCK)
+    first = [s // og * cg // INT8_BLOCK for s in starts]
+    last = [((min(s + INT8_BLOCK, o) - 1) // og + 1) * cg - 1 for s in starts]
+    nbs = max(b // INT8_BLOCK - a + 1 for a, b in zip(first, last))
+    cb0 = torch.tensor(first, dtype=torch.int32, device=tensor.device)
+    values = torch.zeros(list(t.values.shape[:3]) + [INT8_BLOCK * nbs], dtype=torch.int8, device=tensor.device)
+    values.scatter_(3, _grouped_places(tensor.shape, groups, cb0).expand(-1, *tensor.shape[2:], -1), t.values[..., :cg])
+    return Int8GroupedWeight(values, tensor.shape, groups, nbs, cb0, t.scale, t.qmin, t.qmax, t.rounding, t.sums)
+
+
+def int8_grouped_conv2d_packed(x: Int8Tensor, w: Int8GroupedWeight, bias: torch.Tensor = None, stride=1, padding=0, dilation=1,
+                               residual: torch.Tensor = None, relu: bool = False, out_config=None, out_float: Optional[bool] = None,
+                               use_kernels: bool = True):
+    """``conv2d(x, w, groups=w.groups)`` as a linear INT8 layer: ``x`` an activation ``[N, C, H, W]`` packed along axis 1, ``w`` an
+    ``Int8GroupedWeight`` ``[O, C / groups, kh, kw]``.  Everything else -- the geometry, the padding's code, ``bias`` ``[O]``,
+    ``residual``, ``relu``, ``out_config``, ``out_float`` and what is returned -- is ``int8_conv2d_packed``'s: the ``Int8Tensor`` is
+    packed along axis 1, so dense, depthwise and grouped layers chain.  ONE launch (``CUDA.Int8GroupedConv2d``, on the int8 MFMA);
+    ``use_kernels=False``: torch ops on any device, identical bits."""
+    what = 'int8_grouped_conv2d'
+    if not isinstance(x, Int8Tensor): raise TypeError(f'{what}: x: expected an Int8Tensor, got {type(x)}')
+    if isinstance(w, Int4Weight): raise TypeError(f'{what}: w: INT4 grouped weights are not supported: got an Int4Weight')
+    if not isinstance(w, Int8GroupedWeight): raise TypeError(f'{what}: w: expected an Int8GroupedWeight, got {type(w)}')
+    for name, t in (('x', x), ('w', w)):
+        if t.values.dtype != torch.int8: raise RuntimeError(f'{what}: {name}: the codes are {t.values.dtype}, not int8')
+    if len(x.shape) != 4 or x.axis != 1: raise RuntimeError(f'{what}: x {list(x.shape)} must be 4-d and packed along axis 1, not {x.axis}')
+    o, cg, kh, kw = w.shape
+    c = cg * w.groups
+    if x.shape[1] != c: raise RuntimeError(f'{what}: channel mismatch: x has {x.shape[1]} channels, w {cg} for each of {w.groups} groups')
+    if x.device != w.device: raise RuntimeError(f'{what}: x is on {x.device}, w on {w.device}')
+    if x.scale.numel() != 1: raise RuntimeError(f'{what}: x must be quantised per tensor')
+    kp = w.values[0].numel()
+    if kp >= MAX_KP: raise RuntimeError(f'{what}: a padded reduction length of {kp}: {MAX_KP} and more could overflow int32')
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32: raise RuntimeError(f'{what}: bias must be a float32 tensor')
+        if list(bias.shape) != [o]: raise RuntimeError(f'{what}: bias of shape {list(bias.shape)}, expected [{o}]')
+    stride, padding, dilation = _pair(stride, 'stride', 1, what), _pair(padding, 'padding', 0, what), _pair(dilation, 'dilation', 1, what)
+    out = tuple((x.shape[2 + i] + 2 * padding[i] - dilation[i] * (w.shape[2 + i] - 1) - 1) // stride[i] + 1 for i in range(2))
+    if min(out) < 1:
+        raise RuntimeError(f'{what}: a {kh} x {kw} kernel with dilation {dilation} does not fit an input of {x.shape[2]} x {x.shape[3]} padded by {padding}')
+    shape = [x.shape[0], o, out[0], out[1]]
+    out_float, out_q = _check_tail(what, x, shape, residual, out_config, out_float)
+    mul = _mul(x, w)
+    if use_kernels:
+        y, q = CUDA.Int8GroupedConv2d(x.values, w.values, w.sums if x.zero_point else None, x.zero_point, mul, c, w.groups, w.nbs, w.cb0, bias, stride, padding,
+                                      dilation, residual, relu, out_float, out_q)
+    else:
+        xf = torch.nn.functional.pad(x.values[..., :c].permute(0, 3, 1, 2).to(torch.float64), (padding[1],) * 2 + (padding[0],) * 2, value=x.zero_point)
+        i = torch.nn.functional.conv2d(xf - x.zero_point, w.codes().permute(0, 3, 1, 2).to(torch.float64), None, stride, 0, dilation, groups=w.groups)  # exact: integers below 2^31
+        y, q = _tail_torch(i.permute(0, 2, 3, 1).to(torch.int64), mul, bias, residual.permute(0, 2, 3, 1) if residual is not None else None, relu, out_q)
+        y = y.permute(0, 3, 1, 2)
+    return _result(y if out_float else None, q, shape, 1, out_q, out_float, x)
+
+
+def int8_grouped_conv2d(x: torch.Tensor, weight: Int8GroupedWeight, x_config, bias: torch.Tensor = None, stride=1, padding=0, dilation=1,
+                        residual: torch.Tensor = None, relu: bool = False, out_config=None, out_float: Optional[bool] = None, use_kernels: bool = True):
+    """A grouped convolution on an INT8 weight as it runs in deployment: ``int8_quantize(x, x_config, 1)`` -- ``x`` ``[N, C, H, W]`` --,
+    then ``int8_grouped_conv2d_packed``: two launches."""
+    if isinstance(x, torch.Tensor) and x.dim() != 4: raise RuntimeError(f'int8_grouped_conv2d: x must be 4-d [N, C, H, W], got shape {list(x.shape)}')
+    return int8_grouped_conv2d_packed(int8_quantize(x, x_config, 1, use_kernels=use_kernels), weight, bias, stride, padding, dilation, residual, relu,
+                                      out_config, out_float, use_kernels)
+
+
 def int8_conv2d(x: torch.Tensor, weight, x_config, bias: torch.Tensor = None, stride=1, padding=0, dilation=1, groups: int = 1,
                 residual: torch.Tensor = None, relu: bool = False, out_config=None, out_float: Optional[bool] = None, use_kernels: bool = True):
     """A convolution on an INT8 (or ``Int4Weight``) weight as it runs in deployment: ``int8_quantize(x, x_config, 1)`` -- ``x`` ``[N, C, H, W]`` --, then
-    ``int8_conv2d_packed``: two launches.  With an ``Int8DepthwiseWeight`` and ``groups == C`` it is ``int8_depthwise_conv2d``; any other
-    grouped convolution is refused."""
+    ``int8_conv2d_packed``: two launches.  With an ``Int8DepthwiseWeight`` and ``groups == C`` it is ``int8_depthwise_conv2d``, with an
+    ``Int8GroupedWeight`` and ``groups == weight.groups`` ``int8_grouped_conv2d``; groups other than 1 with any other weight are refused."""
+    if isinstance(weight, Int8GroupedWeight):
+        if groups != weight.groups: raise RuntimeError(f'int8_conv2d: a grouped weight of {weight.groups} groups needs groups == {weight.groups}, got {groups}')
+        return int8_grouped_conv2d(x, weight, x_config, bias, stride, padding, dilation, residual, relu, out_config, out_float, use_kernels)
     if isinstance(weight, Int8DepthwiseWeight):
         if groups != weight.shape[0]: raise RuntimeError(f'int8_conv2d: a depthwise weight of {weight.shape[0]} channels needs groups == {weight.shape[0]}, got {groups}')
         return int8_depthwise_conv2d(x, weight, x_config, bias, stride, padding, dilation, residual, relu, out_config, out_float, use_kernels)
