@@ -1068,6 +1068,22 @@ int ppqhip_int8_gconv2d(const int8_t* x, const int8_t* w, const int32_t* w_sums,
                         int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t groups, int64_t nbs,
                         const int32_t* cb0, void* stream);
 
+/* ppqhip_int8_gemm / ppqhip_int4_gemm for 1 <= m <= 64 rows, where the layer is bound by reading the weight once (ppq_amd/int8.py
+ * int8_matmul(..., skinny=True); ADDED under ABI 4).  Every argument, the contract and every bit of the result
+ * are those of ppqhip_int8_gemm / ppqhip_int4_gemm; the kernel is another one: a workgroup owns 16 columns and all m rows, its four
+ * waves split K between them and read their MFMA fragments straight from global memory, so that the grid is ceil32(n) / 16 workgroups
+ * and the weight is read exactly once.  Integer sums do not depend on the order: the split changes no bit.  One launch on `stream`, no
+ * atomics, no workspace, no allocation, no synchronisation (capturable).
+ * Refused as ppqhip_int8_gemm refuses, with the same texts in the same order under the names "int8_gemm_skinny" / "int4_gemm_skinny",
+ * and, after the size checks and before m == 0 or n == 0 returns PPQHIP_OK: m > 64, "m = <m>: the skinny kernel takes at most 64
+ * rows".  k == 0 runs the tail on I = 0.  Booked under "int8_skinny" / "int4_skinny", the bytes as the tile kernels book them. */
+int ppqhip_int8_gemm_skinny(const int8_t* a, const int8_t* b, const int32_t* b_sums, int zx, const float* mul, const float* bias,
+                            const float* residual, int relu, float* c, int8_t* q, float sy, int zy, int qmin, int qmax, int rounding,
+                            int q_nan, int64_t m, int64_t n, int64_t k, void* stream);
+int ppqhip_int4_gemm_skinny(const int8_t* a, const uint8_t* b, const int32_t* b_sums, int zx, const float* mul, const float* bias,
+                            const float* residual, int relu, float* c, int8_t* q, float sy, int zy, int qmin, int qmax, int rounding,
+                            int q_nan, int64_t m, int64_t n, int64_t k, void* stream);
+
 /* ---- pointwise (1x1) convolution on the FP32-input MFMA (ADDED under ABI 4) ---------------------------------
  * y[n, o, oh, ow] = sum_k w[o, k] x[n, k, oh * stride, ow * stride] (+ bias[o]) for contiguous NCHW float32 x [n, c, h, wd],
  * w [o, c] (a [o, c, 1, 1] convolution weight as it lies) and y [n, o, ho, wo], ho = (h - 1) / stride + 1, wo likewise; no padding,

@@ -44,7 +44,8 @@ enum KernelId : int {
     K_EQUALIZE_APPLY, K_SSD_SCALES, K_SSD_APPLY, K_FQ_MEASURE_ROWS, K_STAT_MOMENTS, K_STAT_SHAPE,
     K_SPLIT_PLAN, K_SPLIT_APPLY, K_MX_FQ, K_MX_PACK, K_MX_UNPACK, K_MX_GEMM, K_MX_CONV,
     K_MX_GEMM_FUSED, K_MX_CONV_FUSED, K_MX_INT8_GEMM, K_MX_INT8_CONV,
-    K_MX_INT8_GEMM_FUSED, K_MX_INT8_CONV_FUSED, K_INT8_GEMM, K_INT8_CONV, K_INT4_GEMM, K_INT4_CONV, K_INT8_DWCONV, K_INT8_GCONV, K_NUM
+    K_MX_INT8_GEMM_FUSED, K_MX_INT8_CONV_FUSED, K_INT8_GEMM, K_INT8_CONV, K_INT4_GEMM, K_INT4_CONV, K_INT8_DWCONV, K_INT8_GCONV,
+    K_INT8_SKINNY, K_INT4_SKINNY, K_NUM
 };
 extern const char* const kKernelNames[K_NUM];
 

@@ -491,6 +491,19 @@ class CUDA:
         return _int8_matmul(a, b, b_sums, zx, mul, bias, residual, relu, out_float, out_q, int4=True)
 
     @ staticmethod
+    def Int8MatmulSkinny(a, b, b_sums, zx: int, mul, bias=None, residual=None, relu: bool = False, out_float: bool = True, out_q=None):
+        """``Int8Matmul`` for ``M <= 64`` rows on the kernel that reads the weight once: a workgroup owns 16
+        columns and all rows, its waves split K and read their fragments from global memory.  Same arguments, same bits; more than 64
+        rows are refused."""
+        return _int8_matmul(a, b, b_sums, zx, mul, bias, residual, relu, out_float, out_q, skinny=True)
+
+    @ staticmethod
+    def Int4MatmulSkinny(a, b, b_sums, zx: int, mul, bias=None, residual=None, relu: bool = False, out_float: bool = True, out_q=None):
+        """``Int4Matmul`` for ``M <= 64`` rows on the skinny kernel: half the weight bytes where the layer is bound by reading them.
+        Same arguments, same bits; more than 64 rows are refused."""
+        return _int8_matmul(a, b, b_sums, zx, mul, bias, residual, relu, out_float, out_q, int4=True, skinny=True)
+
+    @ staticmethod
     def Int4Conv2d(x, w, w_sums, zx: int, mul, c: int, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), residual=None,
                    relu: bool = False, out_float: bool = True, out_q=None):
         """``Int8Conv2d`` with an INT4 weight: ``x [N, H, W, Cp]`` int8, ``w [O, kh, kw, Cp / 2]`` uint8, the channels of a tap packed

@@ -64,15 +64,22 @@ def _int8_tail(n, shape, dev, sums, zx, mul, bias, residual, out_float, out_q):
     return sums, zx, mul.contiguous(), (bias.contiguous() if bias is not None else None), residual, c, q, grid
 
 
-def int8_matmul(a, b, b_sums, zx: int, mul, bias=None, residual=None, relu: bool = False, out_float: bool = True, out_q=None, int4: bool = False):
+SKINNY_MAX_M = 64        # the rows the skinny GEMM takes (csrc/int8_skinny.hpp)
+
+
+def int8_matmul(a, b, b_sums, zx: int, mul, bias=None, residual=None, relu: bool = False, out_float: bool = True, out_q=None, int4: bool = False,
+                skinny: bool = False):
     """``ppqhip_int8_gemm``: ``a [M, Kp]`` and ``b [N, Kp]`` int8 codes, ``b_sums [N]`` int32 (None with ``zx == 0``), ``mul [N]``
     float32.  ``out_q``: None or ``(sy, zy, qmin, qmax, rounding, q_nan)`` in the stored int8 domain.  Returns ``(c, q)``: float32
     ``[M, N]`` (None with ``out_float=False``) and int8 ``[M, ceil32(N)]`` (None without ``out_q``).
-    ``int4``: ``ppqhip_int4_gemm``, ``b [N, Kp / 2]`` uint8, the packed INT4 codes."""
+    ``int4``: ``ppqhip_int4_gemm``, ``b [N, Kp / 2]`` uint8, the packed INT4 codes.  ``skinny``: ``ppqhip_int8_gemm_skinny`` /
+    ``ppqhip_int4_gemm_skinny``, the kernel for ``M <= 64`` (section 9.26): the same bits; more rows are refused."""
     a, b = _int8_operands(2, ('A', 'B'), (a, b), int4)
     m, n = a.shape[0], b.shape[0]
+    if skinny and m > SKINNY_MAX_M: _refuse(f'M = {m}: the skinny kernel takes at most {SKINNY_MAX_M} rows')
     sums, zx, mul, bias, residual, c, q, grid = _int8_tail(n, [m, n], a.device, b_sums, zx, mul, bias, residual, out_float, out_q)
-    gemm = lib.ppqhip_int4_gemm if int4 else lib.ppqhip_int8_gemm
+    if skinny: gemm = lib.ppqhip_int4_gemm_skinny if int4 else lib.ppqhip_int8_gemm_skinny
+    else: gemm = lib.ppqhip_int4_gemm if int4 else lib.ppqhip_int8_gemm
     with _DeviceOf(a):
         _raise(gemm(a.data_ptr(), b.data_ptr(), _ptr(sums), zx, mul.data_ptr(), _ptr(bias), _ptr(residual), 1 if relu else 0, _ptr(c), _ptr(q), *grid,
                     m, n, a.shape[1], _stream()))

@@ -22,13 +22,18 @@ A depthwise convolution (groups == C, channel multiplier 1; section 9.24) has no
 Every other grouped convolution (1 < groups < C, or a channel multiplier; section 9.25) runs on the int8 MFMA again:
 ``int8_grouped_conv2d_packed`` on an ``Int8GroupedWeight`` (``csrc/int8_gconv.hip``), whose rows hold only the channel blocks their
 slice of 32 output channels needs -- the bits of the dense layer on the block-diagonal weight at 1 / groups of its work.
+
+A Gemm with at most 64 rows -- a classifier head, a transformer's Gemms at small batch -- is bound by reading its weight once, not by
+the MFMA (section 9.26).  ``int8_matmul(..., skinny=True)`` / ``int8_linear(..., skinny=True)`` run it on a kernel of its own
+(``csrc/int8_skinny.hip``): a workgroup per 16 columns, K split between its waves, fragments straight from global memory, for int8
+and INT4 weights alike -- the same bits, since integer sums do not depend on their order.  The flag is opt-in.
 """
 from typing import Optional
 
 import torch
 
 from .core import QuantizationProperty, rounding_value
-from .ffi import CUDA, DEPTHWISE_LDS_BYTES, INT8_BLOCK, depthwise_lds_bytes
+from .ffi import CUDA, DEPTHWISE_LDS_BYTES, INT8_BLOCK, SKINNY_MAX_M, depthwise_lds_bytes
 from .mx import _pair, relu_positive_zero
 from .round import ppq_tensor_round
 
@@ -301,21 +306,29 @@ def _result(y, q, shape, axis, out_q, out_float, like):
 
 
 def int8_matmul(a: Int8Tensor, b, bias: torch.Tensor = None, residual: torch.Tensor = None, relu: bool = False, out_config=None,
-                out_float: Optional[bool] = None, use_kernels: bool = True):
+                out_float: Optional[bool] = None, use_kernels: bool = True, skinny: bool = False):
     """``a . b^T`` as a linear INT8 layer (the contract at the top of this module): ``a`` an activation ``[..., K]`` packed along its
     last axis, ``b`` a weight ``[N, K]`` (``int8_quantize(..., axis=1, weight=True)``, or an ``Int4Weight``: ``CUDA.Int4Matmul`` then,
     the same bits from half the weight bytes), ``bias`` float32 ``[N]``, ``residual`` float32
     ``[..., N]``.  Returns the float32 ``[..., N]``; with ``out_config`` (a per-tensor config: the next layer's activation) the result
     as an ``Int8Tensor`` packed along its last axis -- the bits of ``int8_quantize`` on the float32 result --, and with
-    ``out_float=True`` both, ``(tensor, Int8Tensor)``.  ONE launch (``CUDA.Int8Matmul``); ``use_kernels=False``: torch ops, any device."""
+    ``out_float=True`` both, ``(tensor, Int8Tensor)``.  ONE launch (``CUDA.Int8Matmul``); ``use_kernels=False``: torch ops, any device.
+    ``skinny=True``: the launch is ``CUDA.Int8MatmulSkinny`` / ``Int4MatmulSkinny``, the kernel for a layer bound by reading its weight
+    (section 9.26) -- the same bits; the flattened ``M = prod(a.shape[:-1])`` must be 1 .. 64, under either arm."""
     what = 'int8_matmul'
     _check_operands(what, a, b, 2, bias)
     shape = list(a.shape[:-1]) + [b.shape[0]]
+    if skinny:
+        m = a.values[..., 0].numel()
+        if not 1 <= m <= SKINNY_MAX_M: raise RuntimeError(f'{what}: skinny=True takes M = 1 .. {SKINNY_MAX_M} rows, got M = {m}')
     out_float, out_q = _check_tail(what, a, shape, residual, out_config, out_float)
     av, mul = a.values.reshape(-1, a.values.shape[-1]), _mul(a, b)
     res = residual.reshape(-1, shape[-1]) if residual is not None else None
     int4 = isinstance(b, Int4Weight)
-    if use_kernels: y, q = (CUDA.Int4Matmul if int4 else CUDA.Int8Matmul)(av, b.values, b.sums if a.zero_point else None, a.zero_point, mul, bias, res, relu, out_float, out_q)
+    if use_kernels:
+        if skinny: gemm = CUDA.Int4MatmulSkinny if int4 else CUDA.Int8MatmulSkinny
+        else: gemm = CUDA.Int4Matmul if int4 else CUDA.Int8Matmul
+        y, q = gemm(av, b.values, b.sums if a.zero_point else None, a.zero_point, mul, bias, res, relu, out_float, out_q)
     else:
         i = (av.to(torch.float64) - a.zero_point) @ (int4_unpack(b) if int4 else b).values.to(torch.float64).t()       # every partial sum is an integer below 2^31: exact
         y, q = _tail_torch(i.to(torch.int64), mul, bias, res, relu, out_q)
@@ -324,9 +337,10 @@ def int8_matmul(a: Int8Tensor, b, bias: torch.Tensor = None, residual: torch.Ten
 
 
 def int8_linear(x: torch.Tensor, weight, x_config, bias: torch.Tensor = None, residual: torch.Tensor = None, relu: bool = False,
-                out_config=None, out_float: Optional[bool] = None, use_kernels: bool = True):
-    """A Gemm on an INT8 (or ``Int4Weight``) weight as it runs in deployment: ``int8_quantize(x, x_config, -1)``, then ``int8_matmul``: two launches."""
-    return int8_matmul(int8_quantize(x, x_config, -1, use_kernels=use_kernels), weight, bias, residual, relu, out_config, out_float, use_kernels)
+                out_config=None, out_float: Optional[bool] = None, use_kernels: bool = True, skinny: bool = False):
+    """A Gemm on an INT8 (or ``Int4Weight``) weight as it runs in deployment: ``int8_quantize(x, x_config, -1)``, then ``int8_matmul``: two launches.
+    ``skinny`` is ``int8_matmul``'s: the kernel for at most 64 rows."""
+    return int8_matmul(int8_quantize(x, x_config, -1, use_kernels=use_kernels), weight, bias, residual, relu, out_config, out_float, use_kernels, skinny)
 
 
 def int8_conv2d_packed(x: Int8Tensor, w, bias: torch.Tensor = None, stride=1, padding=0, dilation=1, residual: torch.Tensor = None,
