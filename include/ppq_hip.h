@@ -1084,6 +1084,25 @@ int ppqhip_int4_gemm_skinny(const int8_t* a, const uint8_t* b, const int32_t* b_
                             const float* residual, int relu, float* c, int8_t* q, float sy, int zy, int qmin, int qmax, int rounding,
                             int q_nan, int64_t m, int64_t n, int64_t k, void* stream);
 
+/* The batched matmul of TWO activations of the same family: attention's Q.K^T and P.V (ppq_amd/int8.py int8_bmm; DESIGN.md section
+ * 9.27; ADDED under ABI 4).  a [batch, m, kp] int8 codes, kp = ceil32(k), bytes k .. kp - 1 of every row the code za.  transpose_b != 0:
+ * b [batch, n, kp], packed along the reduction axis like a, its padding the code zb (c = a . b^T); transpose_b == 0: b [batch, k, np],
+ * np = ceil32(n), packed along n with zb in the columns n .. np - 1 -- its k rows are not padded and no row at or past k is read
+ * (c = a . b); the kernel transposes it on its way to the MFMA.  za, zb (-128 .. 127) are the operands' zero points as stored; neither
+ * operand comes with sums, the kernel makes them.  mul points at ONE float32 in device memory, sa * sb.  Per output of every batch g
+ *   I = sum_k (a[g, m, k] - za) (b[g, k, n] - zb), exact in int32;
+ * then the steps t, v (no bias), residual [batch, m, n], relu, c [batch, m, n] / q [batch, m, np] of ppqhip_int8_gemm, in that order
+ * and by the same device functions.  One launch on `stream` for all batches, no atomics, no workspace, no allocation, no
+ * synchronisation (capturable); two calls give identical bits.
+ * Refused before any launch, under the name "int8_bmm": what ppqhip_int8_gemm refuses of its outputs and output grid; za or zb
+ * outside int8; negative sizes; sizes, batch * m or batch * n above 2^31 - 1; kp > 32768 ("a padded reduction length of <kp>: more
+ * than 32768 could overflow int32": 32768 * 255 * 255 < 2^31); a null a, b or mul; a, b, c or q not 16-byte aligned; an output
+ * overlapping an input or the other output.  batch == 0, m == 0 or n == 0 launches nothing; k == 0 runs the tail on I = 0.  Booked
+ * under "int8_bmm": both operands once, the residual and every output. */
+int ppqhip_int8_bmm(const int8_t* a, const int8_t* b, int transpose_b, int za, int zb, const float* mul, const float* residual, int relu,
+                    float* c, int8_t* q, float sy, int zy, int qmin, int qmax, int rounding, int q_nan, int64_t batch, int64_t m,
+                    int64_t n, int64_t k, void* stream);
+
 /* ---- pointwise (1x1) convolution on the FP32-input MFMA (ADDED under ABI 4) ---------------------------------
  * y[n, o, oh, ow] = sum_k w[o, k] x[n, k, oh * stride, ow * stride] (+ bias[o]) for contiguous NCHW float32 x [n, c, h, wd],
  * w [o, c] (a [o, c, 1, 1] convolution weight as it lies) and y [n, o, ho, wo], ho = (h - 1) / stride + 1, wo likewise; no padding,

@@ -8,12 +8,12 @@ from .core import (PPQ_CONFIG, FloatingQuantizationConfig, LinearQuantizationCon
                    QuantizationProperty, QuantizationStates, RoundingPolicy, TensorQuantizationConfig)
 from .ffi import (CUDA, CUDA_COMPLIER, ENABLE_CUDA_KERNEL, HIP_EXTENSION, install_into_ppq, install_plugins_into_ppq,
                   uninstall_from_ppq)
-from .int8 import (Int4Weight, Int8DepthwiseWeight, Int8GroupedWeight, Int8Tensor, int8_grouped_conv2d, int8_grouped_conv2d_packed, int8_grouped_weight, int8_depthwise_conv2d, int8_depthwise_conv2d_packed, int8_depthwise_weight, int4_pack, int4_quantize_weight, int4_unpack, int8_conv2d, int8_conv2d_packed, int8_dequantize, int8_linear,
+from .int8 import (Int4Weight, Int8DepthwiseWeight, Int8GroupedWeight, Int8Tensor, int8_grouped_conv2d, int8_grouped_conv2d_packed, int8_grouped_weight, int8_depthwise_conv2d, int8_depthwise_conv2d_packed, int8_depthwise_weight, int4_pack, int4_quantize_weight, int4_unpack, int8_bmm, int8_conv2d, int8_conv2d_packed, int8_dequantize, int8_linear,
                    int8_matmul, int8_quantize)
 from .mx import (MXDelegator, MXDeployment, MXFormat, MXScaleRule, MXTensor, deploy_graph_mx, export_graph_mx, mx_conv2d, mx_conv2d_packed, mx_dequantize,
                  mx_fake_quant, mx_int8_conv2d, mx_int8_conv2d_packed, mx_int8_linear, mx_int8_matmul, mx_linear, mx_matmul, mx_quantize, quantize_graph_mx)
 from .mx_roundtune import MXRoundTuningDelegator, MXRoundTuningGroup, MXRoundTuningPass, mx_round_forward, mx_round_split
 
-__all__ = ['Int8Tensor', 'Int4Weight', 'int4_quantize_weight', 'int4_pack', 'int4_unpack', 'int8_quantize', 'int8_dequantize', 'int8_matmul', 'int8_linear', 'int8_conv2d', 'int8_conv2d_packed', 'Int8DepthwiseWeight', 'int8_depthwise_weight', 'int8_depthwise_conv2d', 'int8_depthwise_conv2d_packed', 'Int8GroupedWeight', 'int8_grouped_weight', 'int8_grouped_conv2d', 'int8_grouped_conv2d_packed', 'MXFormat', 'MXScaleRule', 'MXDelegator', 'MXTensor', 'mx_fake_quant', 'mx_quantize', 'mx_dequantize', 'mx_matmul', 'mx_linear', 'mx_int8_matmul', 'mx_int8_linear', 'mx_int8_conv2d', 'mx_int8_conv2d_packed', 'mx_conv2d', 'mx_conv2d_packed', 'quantize_graph_mx', 'export_graph_mx', 'deploy_graph_mx', 'MXDeployment', 'mx_round_split', 'mx_round_forward', 'MXRoundTuningDelegator', 'MXRoundTuningGroup', 'MXRoundTuningPass', 'CUDA', 'CUDA_COMPLIER', 'ENABLE_CUDA_KERNEL', 'HIP_EXTENSION', 'install_into_ppq', 'install_plugins_into_ppq', 'uninstall_from_ppq', 'PPQ_CONFIG', 'RoundingPolicy',
+__all__ = ['Int8Tensor', 'Int4Weight', 'int4_quantize_weight', 'int4_pack', 'int4_unpack', 'int8_quantize', 'int8_dequantize', 'int8_matmul', 'int8_bmm', 'int8_linear', 'int8_conv2d', 'int8_conv2d_packed', 'Int8DepthwiseWeight', 'int8_depthwise_weight', 'int8_depthwise_conv2d', 'int8_depthwise_conv2d_packed', 'Int8GroupedWeight', 'int8_grouped_weight', 'int8_grouped_conv2d', 'int8_grouped_conv2d_packed', 'MXFormat', 'MXScaleRule', 'MXDelegator', 'MXTensor', 'mx_fake_quant', 'mx_quantize', 'mx_dequantize', 'mx_matmul', 'mx_linear', 'mx_int8_matmul', 'mx_int8_linear', 'mx_int8_conv2d', 'mx_int8_conv2d_packed', 'mx_conv2d', 'mx_conv2d_packed', 'quantize_graph_mx', 'export_graph_mx', 'deploy_graph_mx', 'MXDeployment', 'mx_round_split', 'mx_round_forward', 'MXRoundTuningDelegator', 'MXRoundTuningGroup', 'MXRoundTuningPass', 'CUDA', 'CUDA_COMPLIER', 'ENABLE_CUDA_KERNEL', 'HIP_EXTENSION', 'install_into_ppq', 'install_plugins_into_ppq', 'uninstall_from_ppq', 'PPQ_CONFIG', 'RoundingPolicy',
            'QuantizationProperty', 'QuantizationPolicy', 'QuantizationStates', 'TensorQuantizationConfig',
            'LinearQuantizationConfig', 'FloatingQuantizationConfig']

@@ -152,6 +152,7 @@ PROTOTYPES = {
     'ppqhip_int8_gconv2d': (c_int, [c_vp, c_vp, c_vp, c_int, c_f32p, c_f32p, c_f32p, c_int, c_f32p, c_vp, c_flt] + [c_int] * 5 + [c_i64] * 15 + [c_vp, c_vp]),
     'ppqhip_int8_gemm_skinny': (c_int, [c_vp, c_vp, c_vp, c_int, c_f32p, c_f32p, c_f32p, c_int, c_f32p, c_vp, c_flt] + [c_int] * 5 + [c_i64] * 3 + [c_vp]),
     'ppqhip_int4_gemm_skinny': (c_int, [c_vp, c_vp, c_vp, c_int, c_f32p, c_f32p, c_f32p, c_int, c_f32p, c_vp, c_flt] + [c_int] * 5 + [c_i64] * 3 + [c_vp]),
+    'ppqhip_int8_bmm': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_f32p, c_f32p, c_int, c_f32p, c_vp, c_flt] + [c_int] * 5 + [c_i64] * 4 + [c_vp]),
     'ppqhip_conv1x1': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
     'ppqhip_conv1x1_epilogue': (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int,
                                         c_int, c_vp, c_vp, c_vp, c_flt, c_flt, c_flt, c_flt, c_flt, c_flt, c_i64, c_int, c_int, c_i64, c_vp]),

@@ -45,7 +45,7 @@ enum KernelId : int {
     K_SPLIT_PLAN, K_SPLIT_APPLY, K_MX_FQ, K_MX_PACK, K_MX_UNPACK, K_MX_GEMM, K_MX_CONV,
     K_MX_GEMM_FUSED, K_MX_CONV_FUSED, K_MX_INT8_GEMM, K_MX_INT8_CONV,
     K_MX_INT8_GEMM_FUSED, K_MX_INT8_CONV_FUSED, K_INT8_GEMM, K_INT8_CONV, K_INT4_GEMM, K_INT4_CONV, K_INT8_DWCONV, K_INT8_GCONV,
-    K_INT8_SKINNY, K_INT4_SKINNY, K_NUM
+    K_INT8_SKINNY, K_INT4_SKINNY, K_INT8_BMM, K_NUM
 };
 extern const char* const kKernelNames[K_NUM];
 

@@ -262,7 +262,9 @@ __device__ __forceinline__ uint32_t q8_code(const Int8Tail& e, float v) {
 // row m0 + 16 i + 4 grp + q, column n0 + 16 j + r.  Per output q8_value on mul[col], bias[col] and residual[row, col]; then v as
 // float32 and / or its code (q8_code), the zero point in the padding columns n .. op - 1.  `stage` is
 // this wave's own kQ8CodeBytes of LDS: the codes of a row sit in 16 lanes x 2 tiles and are gathered through it; then lane l stores
-// half l & 1 of row l >> 1.  Only the wave itself touches its stage, so no workgroup barrier is needed.
+// half l & 1 of row l >> 1.  Only the wave itself touches its stage, so no workgroup barrier is needed.  MUL1: mul is ONE float32 for
+// every column (the batched matmul of two per-tensor activations, int8_bmm.hpp).
+template <bool MUL1 = false>
 __device__ __forceinline__ void q8_epilogue(const v4i (&acc)[kQ8WaveTiles][kQ8WaveTiles], const Int8Tail& e, uint32_t m0, uint32_t n0,
                                             uint32_t lane, uint8_t* stage) {
     constexpr int T = kQ8WaveTiles;
@@ -273,7 +275,7 @@ __device__ __forceinline__ void q8_epilogue(const v4i (&acc)[kQ8WaveTiles][kQ8Wa
         col[j] = n0 + j * kQ8Tile + r;
         col_in[j] = col[j] < e.n;
         col[j] = min(col[j], e.n - 1u);
-        mul[j] = e.mul[col[j]];
+        mul[j] = e.mul[MUL1 ? 0u : col[j]];
         b[j] = e.bias != nullptr ? e.bias[col[j]] : 0.f;
     }
     const uint32_t pad_code = (uint32_t)(int)e.zy & 0xffu;
@@ -369,10 +371,11 @@ inline int64_t bounded_product(int64_t a, int64_t b) {
 
 // The rest of an entry point once its sizes are known: m x n the result, kp the padded reduction length (kp == 0 reads no operand),
 // `workgroups` what it launches, `ins` the operands' spans and `bytes` what they book.  Checks the tail's pointers, alignment and
-// overlaps, fills e (but for tiles_n) and calls launch(workgroups, stream).
+// overlaps, fills e (but for tiles_n) and calls launch(workgroups, stream).  mul holds mul_len floats: one per column unless given.
 template <typename Launch>
 inline int launch_q8(const char* what, const char* float_name, KernelId id, const Int8TailHost& h, int64_t m, int64_t n, int64_t kp,
-                     int64_t workgroups, std::vector<Span>& ins, double bytes, void* stream, Int8Tail& e, Launch&& launch) {
+                     int64_t workgroups, std::vector<Span>& ins, double bytes, void* stream, Int8Tail& e, Launch&& launch, int64_t mul_len = -1) {
+    if (mul_len < 0) mul_len = n;
     if (kp >= kQ8MaxK) { set_error("%s: a padded reduction length of %lld: 65536 and more could overflow int32", what, (long long)kp); return PPQHIP_ERR_INVALID_VALUE; }
     if (h.mul == nullptr || (h.zx != 0 && kp > 0 && h.sums == nullptr)) {
         set_error(h.mul == nullptr ? "%s: null pointer" : "%s: sums is required with a zero point other than 0", what); return PPQHIP_ERR_INVALID_VALUE;
@@ -381,7 +384,7 @@ inline int launch_q8(const char* what, const char* float_name, KernelId id, cons
     const int64_t op = (n + kQ8Block - 1) / kQ8Block * kQ8Block;
     if (workgroups < 0 || workgroups > kQ8Max) { set_error("%s: too many workgroups in one launch", what); return PPQHIP_ERR_INVALID_VALUE; }
     std::vector<Span> outs;
-    ins.push_back(span_of(h.mul, n)); bytes += 4.0 * (double)n;
+    ins.push_back(span_of(h.mul, mul_len)); bytes += 4.0 * (double)mul_len;
     if (h.sums != nullptr && kp > 0) ins.push_back(span_of(h.sums, n));
     if (h.bias != nullptr) ins.push_back(span_of(h.bias, n));
     if (h.residual != nullptr) { ins.push_back(span_of(h.residual, m * n)); bytes += 4.0 * (double)m * (double)n; }

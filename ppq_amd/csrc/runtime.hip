@@ -37,7 +37,7 @@ const char* const kKernelNames[K_NUM] = {
     "split_plan", "split_apply", "mx_fq", "mx_pack", "mx_unpack", "mx_gemm", "mx_conv",
     "mx_gemm_fused", "mx_conv_fused", "mx_int8_gemm", "mx_int8_conv",
     "mx_int8_gemm_fused", "mx_int8_conv_fused", "int8_gemm", "int8_conv", "int4_gemm", "int4_conv", "int8_dwconv", "int8_gconv",
-    "int8_skinny", "int4_skinny"};
+    "int8_skinny", "int4_skinny", "int8_bmm"};
 
 int num_cu() {
     static std::mutex mu;

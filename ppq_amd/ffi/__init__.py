@@ -28,7 +28,7 @@ from .equalize import (SPLIT_BIT, SPLIT_MAX_JOBS, SPLIT_MAX_SEGMENTS, EqualizeTa
                        split_plan_launches, split_plan_multi, split_plan_table, ssd_apply_multi, ssd_scales_multi)
 from .extension import HIP_EXTENSION, _HipExtension
 from .hints import _hint_owner, _owner_hints, _owner_quantile_hint, quantile_hint, quantile_hint_owner
-from .int8 import DEPTHWISE_LDS_BYTES, INT8_BLOCK, SKINNY_MAX_M, depthwise_lds_bytes
+from .int8 import BMM_MAX_KP, DEPTHWISE_LDS_BYTES, INT8_BLOCK, SKINNY_MAX_M, depthwise_lds_bytes
 from .measure import (MEASURE_METHODS, MEASURE_REDUCES, STAT_MAX_BINS, STAT_WORDS, fetch_rows_multi, fq_measure_rows_multi,
                       measure_finish_multi, measure_rows_multi, stat_counts, stat_moments_multi, stat_shape_multi, stat_table)
 from .mx import (MX_BLOCK, MX_BLOCK_BYTES, MX_FORMATS, MX_RULE_SHIFT, MX_SCALE_RULES, MXPackPlan, MXQuantizePlan, _mx_axis,

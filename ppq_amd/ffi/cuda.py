@@ -5,7 +5,7 @@ from .. import ffi as _package     # public entry points are called through the 
 from .._lib import lib
 from ._base import _KERNEL_FAILURE, _DeviceOf, _check, _f32, _ptr, _raise, _stream
 from .extension import HIP_EXTENSION
-from .int8 import (int8_conv2d as _int8_conv2d, int8_depthwise_conv2d as _int8_depthwise_conv2d, int8_grouped_conv2d as _int8_grouped_conv2d,
+from .int8 import (int8_bmm as _int8_bmm, int8_conv2d as _int8_conv2d, int8_depthwise_conv2d as _int8_depthwise_conv2d, int8_grouped_conv2d as _int8_grouped_conv2d,
                    int8_matmul as _int8_matmul)
 from .mx import (MX_BLOCK, _mx_axis, _mx_codes_like, _mx_conv_args, _mx_dense, _mx_fused_args, _mx_fused_outputs, _mx_geometry,
                  _mx_int8_conv_args, _mx_int8_fused_args, _mx_int8_matmul_args, _mx_matmul_args, mx_format_arg, mx_format_id, mx_packed_shapes)
@@ -526,6 +526,15 @@ class CUDA:
         ``[ceil(O / 32)]`` the first channel block of each slice.  ``(y, q)`` as ``Int8Conv2d`` returns them, with the bits of
         ``Int8Conv2d`` on the block-diagonal dense weight.  The bits of ``tests/int8_grouped_reference.py``."""
         return _int8_grouped_conv2d(x, w, w_sums, zx, mul, c, groups, nbs, cb0, bias, stride, padding, dilation, residual, relu, out_float, out_q)
+
+    @ staticmethod
+    def Int8Bmm(a, b, transpose_b: bool, za: int, zb: int, mul, n: int = None, residual=None, relu: bool = False, out_float: bool = True, out_q=None):
+        """The batched matmul of TWO INT8 activations on the int8 MFMA, attention's ``Q . K^T`` and ``P . V``:
+        ``a [B, M, Kp]`` with zero point ``za``; ``b`` with zero point ``zb`` is ``[B, N, Kp]`` (``transpose_b``) or ``[B, K, Np]`` with
+        ``n`` live columns, transposed inside the kernel; ``mul`` one float32 on the device.  ``v = float32(sum (a - za)(b - zb)) * mul
+        (+ residual)``, the ReLU; ``(c, q)`` as ``Int8Matmul`` returns them, ``[B, M, N]`` / ``[B, M, ceil32(N)]``.  One launch for all
+        batches; the kernel sums the rows of ``a`` and the columns of ``b`` itself.  The bits of ``tests/int8_bmm_reference.py``."""
+        return _int8_bmm(a, b, transpose_b, za, zb, mul, n, residual, relu, out_float, out_q)
 
     @ staticmethod
     def Sync():

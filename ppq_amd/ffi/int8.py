@@ -1,7 +1,8 @@
 """The bindings of the linear INT8 kernels (``csrc/int8_gemm.hip``, ``csrc/int8_conv.hip``) and of their forms
 with a packed INT4 weight (``csrc/int4_gemm.hip``, ``csrc/int4_conv.hip``; section 9.23): ``CUDA.Int8Matmul`` / ``Int8Conv2d`` /
 ``Int4Matmul`` / ``Int4Conv2d`` forward here, ``Int8DepthwiseConv2d`` to the depthwise kernel (``csrc/int8_dwconv.hip``; section
-9.24) and ``Int8GroupedConv2d`` to the grouped one (``csrc/int8_gconv.hip``; section 9.25).  Operands are int8 codes with the reduction
+9.24) and ``Int8GroupedConv2d`` to the grouped one (``csrc/int8_gconv.hip``; section 9.25), ``Int8Bmm`` to the batched matmul of two activations
+(``csrc/int8_bmm.hip``; section 9.27).  Operands are int8 codes with the reduction
 axis last and padded to a multiple of 32; an INT4 weight is uint8, two codes per byte, half as many bytes along that axis; a depthwise
 weight is ``[kh, kw, Cp]``, a grouped one ``[O, kh, kw, 32 nbs]``."""
 import torch
@@ -34,21 +35,23 @@ def _int8_operands(rank, names, operands, int4=False, same_k=True):
     return out
 
 
-def _int8_tail(n, shape, dev, sums, zx, mul, bias, residual, out_float, out_q):
+def _int8_tail(n, shape, dev, sums, zx, mul, bias, residual, out_float, out_q, mul_len=None, need_sums=True):
     """The checks of everything but the operands; ``shape`` is the result's with the columns last.  Returns the tensors as the kernel
-    takes them, the outputs and the seven scalars of the output grid."""
+    takes them, the outputs and the seven scalars of the output grid.  ``mul`` is ``[n]`` unless ``mul_len`` says otherwise;
+    ``need_sums=False``: the kernel makes the sums a zero point needs itself."""
     zx = int(zx)
     if not -128 <= zx <= 127: _refuse(f'zx {zx} is not an int8 zero point')
     for name, t in (('mul', mul), ('bias', bias)):
         if t is None and name == 'bias': continue
         _f32(t, name)
-        if list(t.shape) != [n]: _refuse(f'{name} of shape {list(t.shape)}, expected [{n}]')
+        want = n if mul_len is None or name == 'bias' else mul_len
+        if list(t.shape) != [want]: _refuse(f'{name} of shape {list(t.shape)}, expected [{want}]')
         if t.device != dev: _refuse(f'{name} is on another device')
     if sums is not None:
         _check(sums, torch.int32, 'sums(Expect to be INT32)')
         if list(sums.shape) != [n] or sums.device != dev: _refuse(f'sums of shape {list(sums.shape)} on {sums.device}, expected [{n}] on {dev}')
         sums = sums.contiguous()
-    elif zx != 0: _refuse('sums is required with a zero point other than 0')
+    elif zx != 0 and need_sums: _refuse('sums is required with a zero point other than 0')
     if residual is not None:
         _f32(residual, 'Residual')
         if list(residual.shape) != list(shape): _refuse(f'residual of shape {list(residual.shape)}, expected {list(shape)}')
@@ -83,6 +86,33 @@ def int8_matmul(a, b, b_sums, zx: int, mul, bias=None, residual=None, relu: bool
     with _DeviceOf(a):
         _raise(gemm(a.data_ptr(), b.data_ptr(), _ptr(sums), zx, mul.data_ptr(), _ptr(bias), _ptr(residual), 1 if relu else 0, _ptr(c), _ptr(q), *grid,
                     m, n, a.shape[1], _stream()))
+    return c, q
+
+
+BMM_MAX_KP = 32768       # the longest padded reduction of int8_bmm: 32768 * 255 * 255 < 2^31 (csrc/int8_bmm.hpp)
+
+
+def int8_bmm(a, b, transpose_b: bool, za: int, zb: int, mul, n: int = None, residual=None, relu: bool = False, out_float: bool = True, out_q=None):
+    """``ppqhip_int8_bmm``: ``a [B, M, Kp]`` int8 codes with zero point ``za``; ``b`` with zero point ``zb`` is ``[B, N, Kp]``
+    (``transpose_b``: ``a . b^T``) or ``[B, K, Np]`` with ``n`` of its ``Np`` columns live (``a . b``: K is the rows ``b`` has, not
+    padded); ``mul`` ONE float32 on the device, ``sa * sb``.  Neither operand has sums: the kernel makes them.  ``out_q`` as in
+    ``int8_matmul``.  Returns ``(c, q)``: float32 ``[B, M, N]`` (None with ``out_float=False``) and int8 ``[B, M, ceil32(N)]`` (None
+    without ``out_q``).  ONE launch for all batches."""
+    a, b = _int8_operands(3, ('A', 'B'), (a, b), same_k=bool(transpose_b))
+    batch, m, kp = a.shape
+    if b.shape[0] != batch: _refuse(f'A and B differ in their batch: {batch} and {b.shape[0]}')
+    if transpose_b: k, n = kp, b.shape[1]
+    else:
+        k, n = b.shape[1], int(b.shape[2] if n is None else n)
+        if not kp - INT8_BLOCK < k <= kp: _refuse(f'B has {k} rows, which do not pad to the {kp} codes of a row of A')
+        if not b.shape[2] - INT8_BLOCK < n <= b.shape[2]: _refuse(f'n = {n} does not pad to the {b.shape[2]} stored columns of B')
+    if kp > BMM_MAX_KP: _refuse(f'a padded reduction length of {kp}: more than {BMM_MAX_KP} could overflow int32')
+    zb = int(zb)
+    if not -128 <= zb <= 127: _refuse(f'zb {zb} is not an int8 zero point')
+    _, za, mul, _, residual, c, q, grid = _int8_tail(n, [batch, m, n], a.device, None, za, mul, None, residual, out_float, out_q, mul_len=1, need_sums=False)
+    with _DeviceOf(a):
+        _raise(lib.ppqhip_int8_bmm(a.data_ptr(), b.data_ptr(), 1 if transpose_b else 0, za, zb, mul.data_ptr(), _ptr(residual), 1 if relu else 0, _ptr(c), _ptr(q),
+                                   *grid, batch, m, n, k, _stream()))
     return c, q
 
 

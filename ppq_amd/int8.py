@@ -27,17 +27,21 @@ A Gemm with at most 64 rows -- a classifier head, a transformer's Gemms at small
 the MFMA (section 9.26).  ``int8_matmul(..., skinny=True)`` / ``int8_linear(..., skinny=True)`` run it on a kernel of its own
 (``csrc/int8_skinny.hip``): a workgroup per 16 columns, K split between its waves, fragments straight from global memory, for int8
 and INT4 weights alike -- the same bits, since integer sums do not depend on their order.  The flag is opt-in.
+
+Attention multiplies two ACTIVATIONS (section 9.27): ``int8_bmm`` is the batched ``Q . K^T`` / ``P . V`` of two ``Int8Tensor`` with a
+zero point each and no precomputed sums (``csrc/int8_bmm.hip``): one launch for all batches, the row and column sums made in the
+kernel from the fragments it holds, and a ``b`` packed along ``N`` transposed on its way to the MFMA.
 """
 from typing import Optional
 
 import torch
 
 from .core import QuantizationProperty, rounding_value
-from .ffi import CUDA, DEPTHWISE_LDS_BYTES, INT8_BLOCK, SKINNY_MAX_M, depthwise_lds_bytes
+from .ffi import BMM_MAX_KP, CUDA, DEPTHWISE_LDS_BYTES, INT8_BLOCK, SKINNY_MAX_M, depthwise_lds_bytes
 from .mx import _pair, relu_positive_zero
 from .round import ppq_tensor_round
 
-__all__ = ['Int8Tensor', 'Int4Weight', 'int8_quantize', 'int8_dequantize', 'int4_quantize_weight', 'int4_pack', 'int4_unpack', 'int8_matmul', 'int8_linear',
+__all__ = ['Int8Tensor', 'Int4Weight', 'int8_quantize', 'int8_dequantize', 'int4_quantize_weight', 'int4_pack', 'int4_unpack', 'int8_matmul', 'int8_bmm', 'int8_linear',
            'int8_conv2d_packed', 'int8_conv2d', 'Int8DepthwiseWeight', 'int8_depthwise_weight', 'int8_depthwise_conv2d_packed', 'int8_depthwise_conv2d',
            'Int8GroupedWeight', 'int8_grouped_weight', 'int8_grouped_conv2d_packed', 'int8_grouped_conv2d']
 
@@ -332,6 +336,52 @@ def int8_matmul(a: Int8Tensor, b, bias: torch.Tensor = None, residual: torch.Ten
     else:
         i = (av.to(torch.float64) - a.zero_point) @ (int4_unpack(b) if int4 else b).values.to(torch.float64).t()       # every partial sum is an integer below 2^31: exact
         y, q = _tail_torch(i.to(torch.int64), mul, bias, res, relu, out_q)
+    y = y.reshape(shape) if y is not None and out_float else None
+    return _result(y, q.reshape(shape[:-1] + [-1]) if q is not None else None, shape, len(shape) - 1, out_q, out_float, a)
+
+
+def int8_bmm(a: Int8Tensor, b: Int8Tensor, transpose_b: bool = False, residual: torch.Tensor = None, relu: bool = False, out_config=None,
+             out_float: Optional[bool] = None, use_kernels: bool = True):
+    """The batched matmul of TWO activations, attention's ``Q . K^T`` and ``P . V`` (section 9.27): ``a`` ``[*batch, M, K]`` and ``b``
+    ``[*batch, N, K]`` (``transpose_b=True``: ``a @ b^T``) or ``[*batch, K, N]`` (``a @ b``), each an ``Int8Tensor`` packed along its
+    LAST axis -- so with ``transpose_b=False`` ``b`` is packed along ``N``, as the Gemm that made it left it, and the kernel transposes
+    it on its way to the MFMA.  Both are per-tensor activations with any zero point and no ``sums``; the batch shapes are equal (no
+    broadcasting) and ``values`` contiguous.  Per batch
+
+        I = sum_k (a[m, k] - za) (b[k, n] - zb)     exact, int32
+        v = float32(I) * (sa * sb)                  sa * sb one float32 product
+
+    then ``residual`` (float32 ``[*batch, M, N]``: an additive mask), ``relu``, ``out_config`` and ``out_float`` as in ``int8_matmul``;
+    there is no bias.  Returns the float32 ``[*batch, M, N]``, the ``Int8Tensor`` packed along its last axis, or both.  ONE launch
+    for all batches (``CUDA.Int8Bmm``); ``use_kernels=False``: torch ops on any device, identical bits.  A padded reduction length
+    above 32768 is refused: ``32768 * 255 * 255 < 2^31``."""
+    what = 'int8_bmm'
+    for name, t in (('a', a), ('b', b)):
+        if not isinstance(t, Int8Tensor): raise TypeError(f'{what}: {name}: expected an Int8Tensor, got {type(t)}')
+        if t.values.dtype != torch.int8: raise RuntimeError(f'{what}: {name}: the codes are {t.values.dtype}, not int8')
+        if t.scale.numel() != 1: raise RuntimeError(f'{what}: {name} must be quantised per tensor')
+        if len(t.shape) < 2 or t.axis != len(t.shape) - 1:
+            raise RuntimeError(f'{what}: {name} {list(t.shape)} must be at least 2-d and packed along its last axis, not along axis {t.axis}')
+        if list(t.values.shape) != list(t.shape[:-1]) + [t.shape[-1] + -t.shape[-1] % INT8_BLOCK] or not t.values.is_contiguous() or t.values.numel() == 0:
+            raise RuntimeError(f'{what}: {name}: values of shape {list(t.values.shape)} are not the contiguous, padded codes of a non-empty {list(t.shape)}')
+    if a.shape[:-2] != b.shape[:-2]: raise RuntimeError(f'{what}: batch mismatch: a {list(a.shape)}, b {list(b.shape)} (no broadcasting)')
+    (kb, n), k = (b.shape[-1], b.shape[-2]) if transpose_b else (b.shape[-2], b.shape[-1]), a.shape[-1]
+    if k != kb: raise RuntimeError(f'{what}: K mismatch: a reduces over {k}, b over {kb} (transpose_b={bool(transpose_b)})')
+    if a.device != b.device: raise RuntimeError(f'{what}: a is on {a.device}, b on {b.device}')
+    m, kp = a.shape[-2], a.values.shape[-1]
+    if kp > BMM_MAX_KP: raise RuntimeError(f'{what}: a padded reduction length of {kp}: more than {BMM_MAX_KP} could overflow int32')
+    shape = list(a.shape[:-1]) + [n]
+    out_float, out_q = _check_tail(what, a, shape, residual, out_config, out_float)
+    av, bv = a.values.reshape(-1, m, kp), b.values.reshape([-1] + list(b.values.shape[-2:]))
+    mul = a.scale.reshape(1) * b.scale.reshape(1)                                       # one float32 multiply, on the device
+    res = residual.reshape(-1, m, n) if residual is not None else None
+    if use_kernels:
+        y, q = CUDA.Int8Bmm(av, bv, transpose_b, a.zero_point, b.zero_point, mul, n, res, relu, out_float, out_q)
+    else:
+        bf = bv.to(torch.float64) - b.zero_point                                        # the padding of both is (za, zb): it adds 0 . 0
+        bf = bf.transpose(1, 2) if transpose_b else bf[..., :n]
+        i = (av[..., :bf.shape[1]].to(torch.float64) - a.zero_point) @ bf               # every partial sum is an integer below 2^31: exact
+        y, q = _tail_torch(i.to(torch.int64), mul, None, res, relu, out_q)
     y = y.reshape(shape) if y is not None and out_float else None
     return _result(y, q.reshape(shape[:-1] + [-1]) if q is not None else None, shape, len(shape) - 1, out_q, out_float, a)
 
